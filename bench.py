@@ -31,6 +31,11 @@ viscosity (default, the headline); 3 = configs[2], 256^3 4-level, mu(x) = 200 (1
 
 Launch: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no launcher environment the
 script starts its own ranks (python -m torch.distributed.run, 127.0.0.1); under torchrun it joins.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, ms_per_step, config, and the
+roofline derived from the timed steps' own SpMV events).  --full adds what takes work of its own: the post-solve transfer
+timings, the cpu_baseline, the extra_workloads, and the full record in bench_extra.json.  --dump-outputs DIR writes what
+the last timed step computed (the solution vector in the reference's DOF numbering and the solve's summary) as .npy files.
 """
 from __future__ import annotations
 
@@ -82,7 +87,15 @@ def parse(argv=None):
                          "time-slice one GPU and every flag wait costs a context switch)")
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, form the process group, all-reduce once and print a JSON line")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline: post-solve transfer timings, cpu_baseline, extra_workloads, "
+                         "and the full record (bench_extra.json)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, <= 64 MB in all)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------
@@ -491,11 +504,11 @@ def write_full_record(full):
     return os.path.relpath(paths[0], ROOT) if paths else None
 
 
-def emit(obj, headline=True):
+def emit(obj, headline=True, record=True):
     """the ONE JSON line on the real stdout (libraries -- RCCL prints its version banner -- write to fd 1, which points to stderr).
-    With headline=True the full record goes to a file and the line is its <= 4 KB digest."""
+    With headline=True the line is the <= 4 KB digest of obj, and with record=True (--full) the full record goes to a file."""
     if headline:
-        obj = headline_of(obj, write_full_record(obj))
+        obj = headline_of(obj, write_full_record(obj) if record else None)
     text = json.dumps(obj, allow_nan=False)
     if headline and len(text) + 1 >= HEADLINE_LIMIT:
         raise RuntimeError(f"bench headline is {len(text)} bytes (limit {HEADLINE_LIMIT})")
@@ -505,6 +518,26 @@ def emit(obj, headline=True):
         sys.stdout.flush()
     else:
         os.write(_JSON_FD, line)
+
+
+DUMP_LIMIT = 64_000_000   # bytes: --dump-outputs writes at most this much in all
+
+
+def dump_outputs(d, x, info):
+    """--dump-outputs: what the last timed step hands its caller -- the velocity solution (float64, the reference's DOF numbering) and
+    the solve's summary (iterations, converged, relative residual, |rhs|^2).  A solution over the budget is written as a fixed seeded
+    sample, its indices beside it (float64: exact up to 2^53)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    budget = DUMP_LIMIT - (1 << 16)              # room for the summary and the .npy headers
+    if x.nbytes > budget:
+        idx = np.unique(np.random.default_rng(12345).integers(0, x.size, size=budget // 16))
+        np.save(os.path.join(d, "solution_sample_index.npy"), idx.astype(np.float64))
+        x = x[idx]
+    np.save(os.path.join(d, "solution.npy"), x)
+    np.save(os.path.join(d, "solve_info.npy"),
+            np.array([info.iterations, info.converged, info.error, info.rhs_norm2], dtype=np.float64))
 
 
 def main():
@@ -705,7 +738,7 @@ def main():
                                          "verification": verification}) + "\n")
             if rank == 0:
                 emit({"metric": "cg_iterations_per_sec", "value": 0.0, "unit": "iter/s", "n_gpus": world, "error":
-                      "no multi-GPU transport reproduced the single-GPU solve", "verification": verification})
+                      "no multi-GPU transport reproduced the single-GPU solve", "verification": verification}, record=a.full)
             raise SystemExit(3)
         del x_ref
         torch.cuda.synchronize()
@@ -749,10 +782,15 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs:
+        x_out = dist_solution().cpu().numpy() if use_dist else solver.solution()   # (collective in the distributed path)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, x_out, info)
+        del x_out
 
     transfer_ms = None
     transfer_in_place_ms = None
-    if not use_dist:
+    if a.full and not use_dist:
         # post-solve transfer to the regular MAC grid (cpp:655-707), outputs stay in HBM
         outs = [torch.empty_like(v) for v in fsc.velocity]
         from adaptiveviscositysolver_amd import capi
@@ -911,7 +949,7 @@ def main():
                            **solver.dist_comm_info(), "resident_loop": bool(info.resident), "verification": verification}
             if slab_local is not None:
                 out["dist"]["slab_local"] = slab_local
-        if world == 1 and not a.no_cpu_baseline and not use_dist and a.precision == "f64":
+        if a.full and world == 1 and not a.no_cpu_baseline and not use_dist and a.precision == "f64":
             # CPU assembly baseline: the oracle's own assembly of the same scene at 256^3 (rows per second)
             asm_scene = None
             if a.config in (None, 1, 2, 3, 4) and not getattr(a, "no_cpu_assembly", False):
@@ -923,7 +961,7 @@ def main():
                 out["speedup_assembly_vs_cpu_rows_per_s"] = out["assembly_rows_per_s"] / cb_asm["rows_per_s"]
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
             out["speedup_vs_cpu_all_parallel"] = out["value"] / out["cpu_baseline"]["all_parallel"]["iter_per_s"]
-        if world == 1 and not use_dist and not a.no_extra and a.config == 4 and not a.scene and not a.variable_viscosity and not a.n and a.precision == "f64":
+        if a.full and world == 1 and not use_dist and not a.no_extra and a.config == 4 and not a.scene and not a.variable_viscosity and not a.n and a.precision == "f64":
             # the secondary workloads, observed by whoever runs the headline: BASELINE configs[2], its field at 512^3, configs[4],
             # and the two scene-equivalents -- one timed pair of solves each, headline fields untouched
             solver.close()
@@ -952,7 +990,7 @@ def main():
                     extras.append({"workload": label, "error": str(e)[:300]})
                 torch.cuda.empty_cache()
             out["extra_workloads"] = extras
-        emit(out)
+        emit(out, record=a.full)
     if world > 1 or under_launcher:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

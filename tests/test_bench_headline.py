@@ -70,3 +70,36 @@ def test_the_last_committed_round_record_digests_under_the_limit():
     full = json.load(open(p))
     line = json.dumps(bench.headline_of(full, "bench_extra.json"), allow_nan=False)
     assert len(line) < 4096
+
+
+def test_plain_run_is_the_default_and_steps_are_validated():
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_writes_float64_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    from types import SimpleNamespace
+    info = SimpleNamespace(iterations=12, converged=1, error=7.5e-4, rhs_norm2=3.0)
+    x = np.linspace(-1.0, 1.0, 5000)
+    bench.dump_outputs(str(tmp_path / "whole"), x, info)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["solution.npy", "solve_info.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "solution.npy"), x)
+    assert np.load(tmp_path / "whole" / "solve_info.npy").tolist() == [12.0, 1.0, 7.5e-4, 3.0]
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT", (1 << 16) + 16 * 1000)   # room for 1000 sampled entries
+    y = np.arange(200000, dtype=np.float64) * 0.5
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), y, info)
+    files = {f: np.load(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")}
+    assert set(files) == {"solution.npy", "solve_info.npy", "solution_sample_index.npy"}
+    assert all(v.dtype == np.float64 for v in files.values())
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= bench.DUMP_LIMIT
+    idx = files["solution_sample_index.npy"]
+    assert 0 < idx.size <= 1000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(files["solution.npy"], y[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "solution_sample_index.npy"))   # the sample is fixed

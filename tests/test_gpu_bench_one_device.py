@@ -21,7 +21,7 @@ def test_bench_gpus_n_on_one_device(ranks, vtol, built_lib):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--one-device", "--n", "64", "--levels", "3",
-           "--steps", "1", "--warmup", "1", "--verify-tol", str(vtol), "--no-cpu-baseline", "--no-extra"]
+           "--steps", "1", "--warmup", "1", "--verify-tol", str(vtol), "--no-cpu-baseline", "--no-extra", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -45,7 +45,7 @@ def test_bench_slab_local_frame_on_one_device(built_lib):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--one-device", "--slab-local", "--n", "64", "--levels", "3",
-           "--steps", "1", "--warmup", "1", "--verify-tol", "1e-8", "--no-cpu-baseline", "--no-extra"]
+           "--steps", "1", "--warmup", "1", "--verify-tol", "1e-8", "--no-cpu-baseline", "--no-extra", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
