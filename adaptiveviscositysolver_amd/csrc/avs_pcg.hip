@@ -33,6 +33,27 @@ static constexpr int kFuseAlphaMax = 4096;   // single-GPU loop: SpMV partial su
                                              // 5.9 k partials at 380 k rows: 27.1 -> 25.4 k it/s, so not beyond)
 static constexpr int kSampleEvery = 4;       // SpMV launches bracketed by HIP events: every 4th (events are not free)
 
+// What a captured chunk (PcgWork::graph) was recorded against: the loop, the buffers and sizes its launches read, its flags and the
+// tolerance.  It is replayed only while every field matches.  Each loop sets what it depends on and leaves the rest zero; the loop tag
+// keeps one loop from ever replaying another's graph on the same workspace.
+enum GraphLoop { kGraphF64 = 1, kGraphF32, kGraphDirect };
+struct GraphKey {
+    int loop = 0;
+    const void *row_ptr = nullptr, *col = nullptr, *val = nullptr, *codes = nullptr, *packed = nullptr, *table = nullptr;
+    const void *x = nullptr, *b = nullptr, *dd = nullptr;
+    int64_t n = 0, table_size = 0, col_bits = 0, ntiles = 0;
+    uint64_t epoch = 0;
+    bool coded = false, fuse_beta = false, fuse_vec = false, brick = false;
+    double tol = 0.;
+};
+static bool operator==(const GraphKey &a, const GraphKey &b)
+{
+    return a.loop == b.loop && a.row_ptr == b.row_ptr && a.col == b.col && a.val == b.val && a.codes == b.codes && a.packed == b.packed &&
+           a.table == b.table && a.x == b.x && a.b == b.b && a.dd == b.dd && a.n == b.n && a.table_size == b.table_size &&
+           a.col_bits == b.col_bits && a.ntiles == b.ntiles && a.epoch == b.epoch && a.coded == b.coded && a.fuse_beta == b.fuse_beta &&
+           a.fuse_vec == b.fuse_vec && a.brick == b.brick && a.tol == b.tol;
+}
+
 struct PcgWork {
     int64_t n = 0, n_ext = 0;
     DevBuf<double> r, p, t, invd, partial;
@@ -52,11 +73,10 @@ struct PcgWork {
     DevBuf<double> stage;          // multi-block reduction: kRedBlocks x 4 block sums ...
     DevBuf<unsigned> ticket;       // ... and the arrival counter (reset by the last block)
     PcgScalars *host_sc = nullptr; // pinned
-    // one chunk of kChunk iterations captured as a hipGraph (single-GPU loop): relaunched while the key matches
+    // one chunk of kChunk iterations captured as a hipGraph (enqueue_chunk: the f64, f32 and direct loops): relaunched while the key matches
     hipGraphExec_t graph = nullptr;
-    const void *graph_key[10] = {};
-    double graph_tol = 0.;
-    bool graph_broken = false;
+    GraphKey graph_key;
+    bool graph_broken = false; // a capture failed: plain launches for the rest of this workspace's life
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t evA[kChunk] = {}, evB[kChunk] = {}; // per-launch SpMV timing inside the solve
     size_t npartial = 0;
@@ -1489,6 +1509,168 @@ static void reduce_launch(PcgWork *w, const double *partial, int nb, int nred, P
         hipLaunchKernelGGL(k_reduce, dim3(1), dim3(kRedBlock), 0, stream, partial, nb, nred, sc, op, tol, skip_if_done, red_off);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side shared by the solve loops.  Every chunked loop has the same shape:
+//   for (;;) { poll_scalars; sample_spmv; done / max_iters / cancel -> break; enqueue_chunk; }   then finish_info
+// ---------------------------------------------------------------------------------------------
+static int vec_grid(int64_t n) // grid-stride vector kernels
+{
+    const int64_t g = (n + kBlock - 1) / kBlock;
+    return (int)(g < 1 ? 1 : (g < kVecGrid ? g : kVecGrid));
+}
+static int row_grid(int64_t n) // one thread per row
+{
+    const int64_t g = (n + kBlock - 1) / kBlock;
+    return (int)(g < 1 ? 1 : g);
+}
+
+static void drop_graph(PcgWork *w)
+{
+    if (w->graph) (void)hipGraphExecDestroy(w->graph);
+    w->graph = nullptr;
+}
+
+// the partial-sum buffer holds at least `need` doubles (a captured chunk holds the old buffer's address: it goes with it)
+static avs_status ensure_partials(PcgWork *w, size_t need)
+{
+    if (need <= w->npartial) return AVS_OK;
+    AVS_TRY(w->partial.alloc(need));
+    w->npartial = need;
+    drop_graph(w);
+    return AVS_OK;
+}
+
+// invd (nullptr: not wanted -- the float loop keeps its own) = the inverse of the diagonal; for a `coded` matrix (one dictionary of
+// few values) also the rows' 2-B diagonal codes and the table of inverted values (k_inv_diag_coded; never with tile-local tables)
+static avs_status prepare_diagonal(PcgWork *w, const CsrView &A, bool coded, double *invd, hipStream_t stream)
+{
+    const int64_t n = A.n;
+    if (invd) hipLaunchKernelGGL(k_inv_diag, dim3(row_grid(n)), dim3(kBlock), 0, stream, A, invd);
+    if (!coded) return AVS_OK;
+    if (!w->dcode.p) AVS_TRY(w->dcode.alloc((size_t)n + 8)); // (+ 8: the float loop's vector loads)
+    if (!w->invtab.p) AVS_TRY(w->invtab.alloc((size_t)kViLdsTable + 1));
+    const int cg = (int)(((n > A.table_size + 1 ? n : A.table_size + 1) + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_inv_diag_coded, dim3(cg), dim3(kBlock), 0, stream, A, w->dcode.p, w->invtab.p);
+    return AVS_OK;
+}
+
+// the key fields every graph-replaying loop shares; the loop adds its own
+static GraphKey matrix_key(GraphLoop loop, const CsrView &A, const void *x, double tol)
+{
+    GraphKey k;
+    k.loop = loop;
+    k.row_ptr = A.row_ptr;
+    k.col = A.col;
+    k.codes = A.codes;
+    k.packed = A.packed;
+    k.table = A.table;
+    k.x = x;
+    k.n = A.n;
+    k.table_size = A.table_size;
+    k.col_bits = A.col_bits;
+    k.epoch = A.epoch;
+    k.tol = tol;
+    return k;
+}
+
+struct ChunkState {
+    int enqueued = 0, last = 0; // iterations enqueued so far / by the last chunk
+    bool timed = true;          // the last chunk was enqueued launch by launch: its SpMV events were recorded
+    double spmv_ms_sum = 0.;
+    int spmv_samples = 0;
+};
+
+// host_sc := the scalar state `slot`, once everything enqueued so far has run
+static avs_status poll_scalars(PcgWork *w, const PcgScalars *slot, hipStream_t stream)
+{
+    AVS_HIP(hipMemcpyAsync(w->host_sc, slot, sizeof(PcgScalars), hipMemcpyDeviceToHost, stream));
+    AVS_HIP(hipStreamSynchronize(stream));
+    return AVS_OK;
+}
+
+// Adds the SpMV timing samples of the last chunk's launches that really ran: iterations 0 .. iter, plus the one that stopped the loop
+// when it ran too -- done == 1 or 2 in the standard loops, any done != 0 in the single-reduction ones (`any_done`).
+static void sample_spmv(PcgWork *w, bool sample, bool any_done, ChunkState *cs)
+{
+    if (!sample || cs->last == 0 || !cs->timed) return;
+    const int done = w->host_sc->done;
+    const int ran = w->host_sc->iter + ((any_done ? done != 0 : (done == 1 || done == 2)) ? 1 : 0);
+    const int first = cs->enqueued - cs->last;
+    for (int c = 0; c < cs->last && first + c < ran; c += kSampleEvery) {
+        float ems = 0.f;
+        if (hipEventElapsedTime(&ems, w->evA[c], w->evB[c]) == hipSuccess) {
+            cs->spmv_ms_sum += ems;
+            ++cs->spmv_samples;
+        }
+    }
+}
+
+// Enqueues the next chunk: kChunk iterations (fewer only at max_iters), iteration c by enqueue_iteration(c, timed).  With a `key`
+// (nullptr: never a graph), full chunks replay one captured hipGraph -- recaptured when the key changes -- except every
+// kTimedChunkEvery-th, which is enqueued launch by launch with the SpMV timing events so that the samples cover the whole solve.
+// No per-launch host work in a replay: smaller gaps between the short kernels of small systems.  Kernels past convergence exit at
+// once, so enqueueing a whole chunk is always safe.
+template <typename F>
+static avs_status enqueue_chunk(PcgWork *w, hipStream_t stream, const GraphKey *key, int max_iters, bool sample, F &&enqueue_iteration,
+                                ChunkState *cs)
+{
+    const int chunk = (max_iters - cs->enqueued) < kChunk ? (max_iters - cs->enqueued) : kChunk;
+    const bool replay = key && (cs->enqueued / kChunk) % kTimedChunkEvery != 0 && chunk == kChunk && !w->graph_broken;
+    if (replay && w->graph && !(w->graph_key == *key)) drop_graph(w);
+    if (replay && !w->graph) {
+        hipGraph_t gr = nullptr;
+        bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) == hipSuccess;
+        if (ok) {
+            for (int c = 0; c < kChunk && ok; ++c) ok = enqueue_iteration(c, false) == AVS_OK;
+            ok = (hipStreamEndCapture(stream, &gr) == hipSuccess) && ok && gr;
+        }
+        if (ok) ok = hipGraphInstantiate(&w->graph, gr, nullptr, nullptr, 0) == hipSuccess;
+        if (gr) (void)hipGraphDestroy(gr);
+        if (ok) {
+            w->graph_key = *key;
+        } else { // plain launches for the rest of this workspace's life
+            (void)hipGetLastError();
+            w->graph = nullptr;
+            w->graph_broken = true;
+        }
+    }
+    cs->timed = !(replay && w->graph);
+    if (cs->timed) {
+        for (int c = 0; c < chunk; ++c) AVS_TRY(enqueue_iteration(c, sample && (c % kSampleEvery == 0)));
+    } else {
+        AVS_HIP(hipGraphLaunch(w->graph, stream));
+    }
+    AVS_HIP(hipGetLastError());
+    cs->enqueued += chunk;
+    cs->last = chunk;
+    return AVS_OK;
+}
+
+// The end of every loop: ev1 recorded and waited for (solve_ms: ev0 -> ev1), then *info from the polled state.  cs: the loop's SpMV
+// samples (nullptr: spmv_ms = 0).  f32: the relative error as the float loop computes it.
+static avs_status finish_info(PcgWork *w, const CsrView &A, hipStream_t stream, avs_solve_info *info, const ChunkState *cs, bool cancelled,
+                              int resident, bool f32)
+{
+    AVS_HIP(hipEventRecord(w->ev1, stream));
+    AVS_HIP(hipEventSynchronize(w->ev1));
+    float ms = 0.f;
+    AVS_HIP(hipEventElapsedTime(&ms, w->ev0, w->ev1));
+    if (!info) return AVS_OK;
+    const PcgScalars &h = *w->host_sc;
+    info->iterations = h.iter;
+    info->converged = (h.done != 0 && !cancelled) ? 1 : 0;
+    info->rhs_norm2 = h.rhs_norm2;
+    if (h.done == 3 || h.rhs_norm2 == 0.) info->error = 0.;
+    else info->error = f32 ? (double)sqrtf((float)h.rr / (float)h.rhs_norm2) : sqrt(h.rr / h.rhs_norm2);
+    info->n = A.n;
+    info->nnz = A.nnz;
+    info->solve_ms = ms;
+    info->spmv_ms = (cs && cs->spmv_samples) ? cs->spmv_ms_sum / cs->spmv_samples : 0.;
+    info->resident = resident;
+    info->cancelled = cancelled ? 1 : 0;
+    return AVS_OK;
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // Single-reduction PCG (Chronopoulos & Gear 1989) -- used when the solve is partitioned over several
@@ -1585,126 +1767,108 @@ __global__ __launch_bounds__(kBlock) void k_sr_update(int64_t n, double *__restr
     }
 }
 
+// Set-up of the single-reduction loops: r = b - A x (x staged through u for the halo), u = M^-1 r, w = A u, and the sums |b|^2, r.u,
+// |r|^2, w.u -> OP_SR_INIT in sc[0] (sc[1] zeroed).  dist == nullptr: one GPU, no exchange and no all-reduce.
+static avs_status sr_setup(PcgWork *w, const CsrView &A, const double *b, const double *x, double tol, bool coded, PcgDist *dist,
+                           hipStream_t stream)
+{
+    const int64_t n = A.n;
+    const int g = vec_grid(n);
+    const int variant = spmv_default_variant(A);
+    AVS_TRY(w->s.alloc((size_t)n));
+    AVS_TRY(w->u.alloc((size_t)w->n_ext));
+    double *wv = w->t.p, *u = w->u.p;
+    double *pvec = w->partial.p, *pspmv = w->partial.p + 4 * (size_t)kVecGrid; // 3 * g vector-kernel partials, the SpMV's behind them
+    PcgScalars *sc = w->sc.p;
+    AVS_HIP(hipMemsetAsync(sc, 0, 2 * sizeof(PcgScalars), stream));
+    AVS_HIP(hipMemsetAsync(w->p.p, 0, (size_t)w->n_ext * sizeof(double), stream));
+    AVS_HIP(hipMemsetAsync(w->s.p, 0, (size_t)n * sizeof(double), stream));
+    AVS_TRY(prepare_diagonal(w, A, coded, w->invd.p, stream));
+    AVS_HIP(hipEventRecord(w->ev0, stream));
+    AVS_HIP(hipMemcpyAsync(u, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    if (dist) AVS_TRY(dist_halo_exchange(dist, u, stream));
+    AVS_TRY(spmv_dispatch<false>(A, u, wv, nullptr, nullptr, variant, stream, nullptr));
+    hipLaunchKernelGGL(k_sr_init, dim3(g), dim3(kBlock), 0, stream, n, b, wv, w->invd.p, w->r.p, u, pvec);
+    if (dist) AVS_TRY(dist_halo_exchange(dist, u, stream));
+    int nb = 0;
+    AVS_TRY(spmv_dispatch<true>(A, u, wv, pspmv, nullptr, variant, stream, &nb));
+    reduce_launch(w, pvec, g, 3, sc, (int)OP_NONE, tol, 0, 0, stream);
+    reduce_launch(w, pspmv, nb, 1, sc, (int)OP_NONE, tol, 0, 3, stream);
+    if (dist) AVS_TRY(dist_allreduce(dist, sc->red, 4, stream));
+    hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc, (int)OP_SR_INIT, tol);
+    AVS_HIP(hipGetLastError());
+    return AVS_OK;
+}
+
 static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const double *b, double *x, double tol,
                                              int max_iters, hipStream_t stream, avs_solve_info *info, PcgDist *dist)
 {
     const int64_t n = A.n;
-    const int g = (int)((n + kBlock - 1) / kBlock < kVecGrid ? ((n + kBlock - 1) / kBlock > 0 ? (n + kBlock - 1) / kBlock : 1) : kVecGrid);
-    const int rowgrid = (int)((n + kBlock - 1) / kBlock) > 0 ? (int)((n + kBlock - 1) / kBlock) : 1;
+    const int g = vec_grid(n);
     const int variant = spmv_default_variant(A);
-    AVS_TRY(w->s.alloc((size_t)n));
-    AVS_TRY(w->u.alloc((size_t)w->n_ext));
+    AVS_TRY(sr_setup(w, A, b, x, tol, false, dist, stream));
     double *p = w->p.p, *r = w->r.p, *wv = w->t.p, *sv = w->s.p, *u = w->u.p, *invd = w->invd.p;
     double *pvec = w->partial.p;                        // 3 * g vector-kernel partials
     double *pspmv = w->partial.p + 4 * (size_t)kVecGrid; // SpMV partials behind them
     PcgScalars *sc = w->sc.p; // two states, ping-pong: sc[cur] is current, k_sr_update writes sc[cur ^ 1]
     int cur = 0;
-    auto red_of = [&](int k) { return reinterpret_cast<double *>(reinterpret_cast<char *>(sc + cur) + offsetof(PcgScalars, red)) + k; };
 
-    AVS_HIP(hipMemsetAsync(sc, 0, 2 * sizeof(PcgScalars), stream));
-    AVS_HIP(hipMemsetAsync(p, 0, (size_t)w->n_ext * sizeof(double), stream));
-    AVS_HIP(hipMemsetAsync(sv, 0, (size_t)n * sizeof(double), stream));
-    hipLaunchKernelGGL(k_inv_diag, dim3(rowgrid), dim3(kBlock), 0, stream, A, invd);
-    AVS_HIP(hipEventRecord(w->ev0, stream));
-    // r = b - A x (x staged through u for the halo), u = M^-1 r, w = A u
-    AVS_HIP(hipMemcpyAsync(u, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    AVS_TRY(dist_halo_exchange(dist, u, stream));
-    AVS_TRY(spmv_dispatch<false>(A, u, wv, nullptr, nullptr, variant, stream, nullptr));
-    hipLaunchKernelGGL(k_sr_init, dim3(g), dim3(kBlock), 0, stream, n, b, wv, invd, r, u, pvec);
-    AVS_TRY(dist_halo_exchange(dist, u, stream));
-    int nb = 0;
-    AVS_TRY(spmv_dispatch<true>(A, u, wv, pspmv, nullptr, variant, stream, &nb));
-    reduce_launch(w, pvec, g, 3, sc, (int)OP_NONE, tol, 0, 0, stream);
-    reduce_launch(w, pspmv, nb, 1, sc, (int)OP_NONE, tol, 0, 3, stream);
-    AVS_TRY(dist_allreduce(dist, red_of(0), 4, stream));
-    hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc, (int)OP_SR_INIT, tol);
-    AVS_HIP(hipGetLastError());
-
-    int enqueued = 0, last_chunk = 0, spmv_samples = 0;
-    double spmv_ms_sum = 0.;
+    auto enqueue_iteration = [&](int c, bool timed) -> avs_status {
+        // first iteration of a chunk: scalars are final (SR_INIT or the explicit step after the chunk); afterwards the step of
+        // the previous iteration rides in k_sr_update, which moves the state to the other slot
+        const int step = c > 0 ? 1 : 0;
+        hipLaunchKernelGGL(k_sr_update, dim3(g), dim3(kBlock), 0, stream, n, x, r, p, sv, u, wv, invd, (const PcgScalars *)(sc + cur),
+                           sc + (step ? (cur ^ 1) : cur), step, pvec);
+        if (step) cur ^= 1;
+        const PcgScalars *now = sc + cur;
+        const int32_t *t_int = nullptr, *t_bnd = nullptr;
+        int n_int = 0, n_bnd = 0, nb = 0;
+        if (variant == 24 && !(A.brick && A.brick->ntiles > 0) && dist_tile_lists(dist, &t_int, &n_int, &t_bnd, &n_bnd)) {
+            // overlap: the exchange runs on the communication stream while the tiles that touch no halo
+            // column are multiplied; the halo-touching tiles follow once the halo has landed
+            AVS_TRY(dist_halo_begin(dist, u, stream));
+            if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
+            AVS_TRY(spmv_dot_tiles(A, u, wv, pspmv, now, t_int, n_int, stream));
+            AVS_TRY(dist_halo_end(dist, stream));
+            AVS_TRY(spmv_dot_tiles(A, u, wv, pspmv + (size_t)n_int * (A.codes ? kTileRows / 64 : 1), now, t_bnd, n_bnd, stream));
+            if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
+            nb = (n_int + n_bnd) * (A.codes ? kTileRows / 64 : 1); // value-indexed kernel: one partial per wave
+        } else {
+            AVS_TRY(dist_halo_exchange(dist, u, stream));
+            if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
+            AVS_TRY(spmv_dispatch<true>(A, u, wv, pspmv, now, variant, stream, &nb));
+            if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
+        }
+        if (nb < 16384) hipLaunchKernelGGL(k_reduce_pair, dim3(1), dim3(kRedBlock), 0, stream, pvec, g, 2, pspmv, nb, 1, sc + cur);
+        else {
+            reduce_launch(w, pvec, g, 2, sc + cur, (int)OP_NONE, tol, 0, 0, stream);
+            reduce_launch(w, pspmv, nb, 1, sc + cur, (int)OP_NONE, tol, 0, 2, stream);
+        }
+        return dist_allreduce(dist, sc[cur].red, 3, stream);
+    };
+    ChunkState cs;
     bool cancelled = false;
     AVS_TRY(w->cancel_word.alloc(2));
-    while (true) {
+    for (;;) {
         // avs_cancel: every rank contributes its request (0 / 1), the sum is the verdict of ALL ranks for this chunk boundary
         double stop_h[2] = {cancel_requested() ? 1. : 0., 0.};
         AVS_HIP(hipMemcpyAsync(w->cancel_word.p, stop_h, sizeof(double), hipMemcpyHostToDevice, stream));
         AVS_TRY(dist_allreduce(dist, w->cancel_word.p, 1, stream));
         AVS_HIP(hipMemcpyAsync(stop_h + 1, w->cancel_word.p, sizeof(double), hipMemcpyDeviceToHost, stream));
-        AVS_HIP(hipMemcpyAsync(w->host_sc, sc + cur, sizeof(PcgScalars), hipMemcpyDeviceToHost, stream));
-        AVS_HIP(hipStreamSynchronize(stream));
-        if (info && last_chunk > 0) {
-            const int ran = w->host_sc->iter + (w->host_sc->done ? 1 : 0);
-            const int first = enqueued - last_chunk;
-            for (int c2 = 0; c2 < last_chunk && first + c2 < ran; c2 += kSampleEvery) {
-                float ems = 0.f;
-                if (hipEventElapsedTime(&ems, w->evA[c2], w->evB[c2]) == hipSuccess) { spmv_ms_sum += ems; ++spmv_samples; }
-            }
-        }
-        if (w->host_sc->done || enqueued >= max_iters) break;
+        AVS_TRY(poll_scalars(w, sc + cur, stream));
+        sample_spmv(w, info != nullptr, true, &cs);
+        if (w->host_sc->done || cs.enqueued >= max_iters) break;
         if (stop_h[1] != 0.) { (void)cancel_consume(); cancelled = true; break; }
-        const int chunk = (max_iters - enqueued) < kChunk ? (max_iters - enqueued) : kChunk;
-        for (int c = 0; c < chunk; ++c) {
-            // first iteration of a chunk: scalars are final (SR_INIT or the explicit step below); afterwards the step of
-            // the previous iteration rides in k_sr_update, which moves the state to the other slot
-            const int step = c > 0 ? 1 : 0;
-            const bool timed = info && (c % kSampleEvery == 0); // SpMV timing samples: every 4th iteration
-            hipLaunchKernelGGL(k_sr_update, dim3(g), dim3(kBlock), 0, stream, n, x, r, p, sv, u, wv, invd, (const PcgScalars *)(sc + cur),
-                               sc + (step ? (cur ^ 1) : cur), step, pvec);
-            if (step) cur ^= 1;
-            const PcgScalars *now = sc + cur;
-            const int32_t *t_int = nullptr, *t_bnd = nullptr;
-            int n_int = 0, n_bnd = 0;
-            if (variant == 24 && !(A.brick && A.brick->ntiles > 0) && dist_tile_lists(dist, &t_int, &n_int, &t_bnd, &n_bnd)) {
-                // overlap: the exchange runs on the communication stream while the tiles that touch no halo
-                // column are multiplied; the halo-touching tiles follow once the halo has landed
-                AVS_TRY(dist_halo_begin(dist, u, stream));
-                if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
-                AVS_TRY(spmv_dot_tiles(A, u, wv, pspmv, now, t_int, n_int, stream));
-                AVS_TRY(dist_halo_end(dist, stream));
-                AVS_TRY(spmv_dot_tiles(A, u, wv, pspmv + (size_t)n_int * (A.codes ? kTileRows / 64 : 1), now, t_bnd, n_bnd, stream));
-                if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
-                nb = (n_int + n_bnd) * (A.codes ? kTileRows / 64 : 1); // value-indexed kernel: one partial per wave
-            } else {
-                AVS_TRY(dist_halo_exchange(dist, u, stream));
-                if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
-                AVS_TRY(spmv_dispatch<true>(A, u, wv, pspmv, now, variant, stream, &nb));
-                if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
-            }
-            if (nb < 16384) hipLaunchKernelGGL(k_reduce_pair, dim3(1), dim3(kRedBlock), 0, stream, pvec, g, 2, pspmv, nb, 1, sc + cur);
-            else {
-                reduce_launch(w, pvec, g, 2, sc + cur, (int)OP_NONE, tol, 0, 0, stream);
-                reduce_launch(w, pspmv, nb, 1, sc + cur, (int)OP_NONE, tol, 0, 2, stream);
-            }
-            AVS_TRY(dist_allreduce(dist, red_of(0), 3, stream));
-        }
+        AVS_TRY(enqueue_chunk(w, stream, nullptr, max_iters, info != nullptr, enqueue_iteration, &cs)); // (no graph: RCCL calls inside)
         // the last iteration's step, explicitly: the host polls a final state
         hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc + cur, (int)OP_SR_STEP, tol);
         AVS_HIP(hipGetLastError());
-        enqueued += chunk;
-        last_chunk = chunk;
     }
     if (w->host_sc->done == 3) { // rhs == 0: x := 0
         hipLaunchKernelGGL(k_sr_update, dim3(g), dim3(kBlock), 0, stream, n, x, r, p, sv, u, wv, invd, (const PcgScalars *)(sc + cur), sc + cur, 0,
                            pvec);
     }
-    AVS_HIP(hipEventRecord(w->ev1, stream));
-    AVS_HIP(hipEventSynchronize(w->ev1));
-    float ms = 0.f;
-    AVS_HIP(hipEventElapsedTime(&ms, w->ev0, w->ev1));
-    if (info) {
-        const PcgScalars &h = *w->host_sc;
-        info->iterations = h.iter;
-        info->converged = (h.done != 0) ? 1 : 0;
-        info->rhs_norm2 = h.rhs_norm2;
-        info->error = (h.done == 3 || h.rhs_norm2 == 0.) ? 0. : sqrt(h.rr / h.rhs_norm2);
-        info->n = n;
-        info->nnz = A.nnz;
-        info->solve_ms = ms;
-        info->spmv_ms = spmv_samples ? spmv_ms_sum / spmv_samples : 0.;
-        info->resident = 0;
-        info->cancelled = cancelled ? 1 : 0;
-    }
-    return AVS_OK;
+    return finish_info(w, A, stream, info, &cs, cancelled, 0, false);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1980,7 +2144,6 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
     int g = 1, chunk_rows = kBlock; // every vector kernel of this loop uses the fused kernel's geometry (same partial layout)
     sr_update_geometry((long long)n, &g, &chunk_rows);
     AVS_REQUIRE(g == da.push_grid && chunk_rows == da.push_chunk, AVS_EINTERNAL, "push segments were built for another geometry");
-    const int rowgrid = (int)((n + kBlock - 1) / kBlock) > 0 ? (int)((n + kBlock - 1) / kBlock) : 1;
     AVS_TRY(w->s.alloc((size_t)n));
     AVS_TRY(w->u.alloc((size_t)w->n_ext));
     double *p = w->p.p, *r = w->r.p, *wv = w->t.p, *sv = w->s.p, *u = w->u.p, *invd = w->invd.p;
@@ -2001,15 +2164,9 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
     AVS_HIP(hipMemsetAsync(sc, 0, 2 * sizeof(PcgScalars), stream));
     AVS_HIP(hipMemsetAsync(p, 0, (size_t)w->n_ext * sizeof(double), stream));
     AVS_HIP(hipMemsetAsync(sv, 0, (size_t)n * sizeof(double), stream));
-    hipLaunchKernelGGL(k_inv_diag, dim3(rowgrid), dim3(kBlock), 0, stream, A, invd);
-    // one dictionary of few values: the loop's vector kernel reads a 2-B diagonal code (k_inv_diag_coded; never with tile-local tables)
+    // one dictionary of few values: the loop's vector kernel reads a 2-B diagonal code
     const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable;
-    if (coded) {
-        if (!w->dcode.p) AVS_TRY(w->dcode.alloc((size_t)n + 2));
-        if (!w->invtab.p) AVS_TRY(w->invtab.alloc((size_t)kViLdsTable + 1));
-        const int cg = (int)(((n > A.table_size + 1 ? n : A.table_size + 1) + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_inv_diag_coded, dim3(cg), dim3(kBlock), 0, stream, A, w->dcode.p, w->invtab.p);
-    }
+    AVS_TRY(prepare_diagonal(w, A, coded, invd, stream));
     AVS_HIP(hipEventRecord(w->ev0, stream));
 
     // one round: exchange `vec`, wv = A vec (+ partials of vec.wv), fold `nred_vec` vector partial arrays + that one, step `op`
@@ -2082,13 +2239,16 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
                                (const uint16_t *)nullptr, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch, da.push_ticket);
         return round(u, 2, (int)OP_SR_STEP, timed ? w->evA[c] : nullptr, timed ? w->evB[c] : nullptr, false);
     };
-    bool use_graph = cur_opt().graph != 0;
-    int enqueued = 0, last_chunk = 0, spmv_samples = 0;
-    double spmv_ms_sum = 0.;
-    bool timed_chunk = true, cancel_sent = false;
-    while (true) {
-        AVS_HIP(hipMemcpyAsync(w->host_sc, sc, sizeof(PcgScalars), hipMemcpyDeviceToHost, stream));
-        AVS_HIP(hipStreamSynchronize(stream));
+    GraphKey key = matrix_key(kGraphDirect, A, x, tol);
+    key.b = b;
+    key.dd = da.dd;
+    key.ntiles = ntiles;
+    key.brick = brick;
+    const GraphKey *gkey = cur_opt().graph != 0 ? &key : nullptr;
+    ChunkState cs;
+    bool cancel_sent = false;
+    for (;;) {
+        AVS_TRY(poll_scalars(w, sc, stream));
         if (w->host_sc->fault) {
             if (w->resident_used && w->resident) w->resident->ok = false; // the next distributed solve takes the launch-per-phase loop
             if (w->host_sc->fault == 4)
@@ -2099,79 +2259,18 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
                           w->host_sc->fault == 1 ? "a peer's halo entries" : (w->host_sc->fault == 2 ? "a peer's partial sums" : "a workgroup's partial sums"));
             return AVS_ERCCL;
         }
-        if (info && last_chunk > 0 && timed_chunk) {
-            const int ran = w->host_sc->iter + (w->host_sc->done ? 1 : 0);
-            const int first = enqueued - last_chunk;
-            for (int c2 = 0; c2 < last_chunk && first + c2 < ran; c2 += kSampleEvery) {
-                float ems = 0.f;
-                if (hipEventElapsedTime(&ems, w->evA[c2], w->evB[c2]) == hipSuccess) { spmv_ms_sum += ems; ++spmv_samples; }
-            }
-        }
-        if (w->host_sc->done || enqueued >= max_iters || w->resident_used) break;
+        sample_spmv(w, info != nullptr, true, &cs);
+        if (w->host_sc->done || cs.enqueued >= max_iters || w->resident_used) break;
         if (cancel_requested() && !cancel_sent) { // avs_cancel: the request word the finalizer adds to the round's sums -- every rank stops in the same round
             static const int one = 1;
             AVS_HIP(hipMemcpyAsync(w->cancel_dev.p, &one, sizeof(int), hipMemcpyHostToDevice, stream));
             cancel_sent = true;
         }
-        const int chunk = (max_iters - enqueued) < kChunk ? (max_iters - enqueued) : kChunk;
-        const bool replay = use_graph && (enqueued / kChunk) % kTimedChunkEvery != 0 && chunk == kChunk && !w->graph_broken;
-        timed_chunk = !replay;
-        if (replay) {
-            const void *key[10] = {A.row_ptr, A.col, A.codes, A.packed, A.table, x, b, (const void *)da.dd, (const void *)(intptr_t)A.n,
-                                   (const void *)(intptr_t)(((int64_t)A.table_size << 8) + A.col_bits + 1000003ll * ntiles + 1000000007ll * (int64_t)A.epoch + (brick ? 7 : 0))};
-            (void)da.tiles_int;
-            if (w->graph && (memcmp(key, w->graph_key, sizeof(key)) != 0 || w->graph_tol != tol)) {
-                (void)hipGraphExecDestroy(w->graph);
-                w->graph = nullptr;
-            }
-            if (!w->graph) {
-                hipGraph_t gr = nullptr;
-                bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) == hipSuccess;
-                if (ok) {
-                    for (int c = 0; c < kChunk && ok; ++c) ok = enqueue_iteration(c, false) == AVS_OK;
-                    ok = (hipStreamEndCapture(stream, &gr) == hipSuccess) && ok && gr;
-                }
-                if (ok) ok = hipGraphInstantiate(&w->graph, gr, nullptr, nullptr, 0) == hipSuccess;
-                if (gr) (void)hipGraphDestroy(gr);
-                if (!ok) {
-                    (void)hipGetLastError();
-                    w->graph = nullptr;
-                    w->graph_broken = true;
-                } else {
-                    memcpy(w->graph_key, key, sizeof(key));
-                    w->graph_tol = tol;
-                }
-            }
-        }
-        if (replay && w->graph) {
-            AVS_HIP(hipGraphLaunch(w->graph, stream));
-        } else {
-            timed_chunk = true;
-            for (int c = 0; c < chunk; ++c) AVS_TRY(enqueue_iteration(c, info && (c % kSampleEvery == 0)));
-        }
-        AVS_HIP(hipGetLastError());
-        enqueued += chunk;
-        last_chunk = chunk;
+        AVS_TRY(enqueue_chunk(w, stream, gkey, max_iters, info != nullptr, enqueue_iteration, &cs));
     }
     if (w->host_sc->done == 3) // rhs == 0: x := 0
         hipLaunchKernelGGL(k_sr_update, dim3(g), dim3(kBlock), 0, stream, n, x, r, p, sv, u, wv, invd, (const PcgScalars *)sc, sc, 0, pvec);
-    AVS_HIP(hipEventRecord(w->ev1, stream));
-    AVS_HIP(hipEventSynchronize(w->ev1));
-    float ms = 0.f;
-    AVS_HIP(hipEventElapsedTime(&ms, w->ev0, w->ev1));
-    if (info) {
-        const PcgScalars &h = *w->host_sc;
-        info->iterations = h.iter;
-        info->converged = (h.done != 0 && !h.cancelled) ? 1 : 0;
-        info->rhs_norm2 = h.rhs_norm2;
-        info->error = (h.done == 3 || h.rhs_norm2 == 0.) ? 0. : sqrt(h.rr / h.rhs_norm2);
-        info->n = n;
-        info->nnz = A.nnz;
-        info->solve_ms = ms;
-        info->spmv_ms = spmv_samples ? spmv_ms_sum / spmv_samples : 0.;
-        info->resident = w->resident_used;
-        info->cancelled = h.cancelled ? 1 : 0;
-    }
+    AVS_TRY(finish_info(w, A, stream, info, &cs, w->host_sc->cancelled != 0, w->resident_used, false));
     if (w->host_sc->cancelled) (void)cancel_consume();
     return AVS_OK;
 }
@@ -2223,7 +2322,7 @@ void pcg_destroy(PcgWork *w)
 {
     if (!w) return;
     delete w->resident;
-    if (w->graph) (void)hipGraphExecDestroy(w->graph);
+    drop_graph(w);
     if (w->host_sc) (void)hipHostFree(w->host_sc);
     if (w->ev0) (void)hipEventDestroy(w->ev0);
     if (w->ev1) (void)hipEventDestroy(w->ev1);
@@ -2261,41 +2360,16 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
     if (!w->resident) w->resident = new (std::nothrow) ResidentPlan();
     if (cancel_requested()) return AVS_OK; // (the launch-per-phase loop consumes the request at its first poll: 0 iterations, cancelled = 1)
     if (!w->resident || !resident_prepare(w->resident, A, A.n, nullptr, stream)) return AVS_OK;
-    const int g = (int)((n + kBlock - 1) / kBlock < kVecGrid ? ((n + kBlock - 1) / kBlock > 0 ? (n + kBlock - 1) / kBlock : 1) : kVecGrid);
-    const int rowgrid = (int)((n + kBlock - 1) / kBlock) > 0 ? (int)((n + kBlock - 1) / kBlock) : 1;
-    const int variant = spmv_default_variant(A);
-    AVS_TRY(w->s.alloc((size_t)n));
-    AVS_TRY(w->u.alloc((size_t)w->n_ext));
-    double *p = w->p.p, *r = w->r.p, *wv = w->t.p, *sv = w->s.p, *u = w->u.p, *invd = w->invd.p;
-    double *pvec = w->partial.p, *pspmv = w->partial.p + 4 * (size_t)kVecGrid;
-    PcgScalars *sc = w->sc.p;
-    AVS_HIP(hipMemsetAsync(sc, 0, 2 * sizeof(PcgScalars), stream));
-    AVS_HIP(hipMemsetAsync(p, 0, (size_t)w->n_ext * sizeof(double), stream));
-    AVS_HIP(hipMemsetAsync(sv, 0, (size_t)n * sizeof(double), stream));
-    hipLaunchKernelGGL(k_inv_diag, dim3(rowgrid), dim3(kBlock), 0, stream, A, invd);
-    if (!w->dcode.p) AVS_TRY(w->dcode.alloc((size_t)n + 2));
-    if (!w->invtab.p) AVS_TRY(w->invtab.alloc((size_t)kViLdsTable + 1));
-    const int cg = (int)(((n > A.table_size + 1 ? n : A.table_size + 1) + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_inv_diag_coded, dim3(cg), dim3(kBlock), 0, stream, A, w->dcode.p, w->invtab.p);
-    AVS_HIP(hipEventRecord(w->ev0, stream));
-    AVS_HIP(hipMemcpyAsync(u, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    AVS_TRY(spmv_dispatch<false>(A, u, wv, nullptr, nullptr, variant, stream, nullptr));
-    hipLaunchKernelGGL(k_sr_init, dim3(g), dim3(kBlock), 0, stream, n, b, wv, invd, r, u, pvec);
-    int nb = 0;
-    AVS_TRY(spmv_dispatch<true>(A, u, wv, pspmv, nullptr, variant, stream, &nb));
-    reduce_launch(w, pvec, g, 3, sc, (int)OP_NONE, tol, 0, 0, stream);
-    reduce_launch(w, pspmv, nb, 1, sc, (int)OP_NONE, tol, 0, 3, stream);
-    hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc, (int)OP_SR_INIT, tol);
-    AVS_HIP(hipGetLastError());
+    AVS_TRY(sr_setup(w, A, b, x, tol, true, nullptr, stream));
     // the initial guess is kept: if a bounded wait inside the cooperative launch times out (the grid was not co-resident in time: a GPU
     // shared with a viewport or OpenCL work) the solve is redone from it by the launch-per-phase loop IN THIS CALL
     AVS_TRY(w->x_save.alloc((size_t)n));
     AVS_HIP(hipMemcpyAsync(w->x_save.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     bool launched = false;
-    AVS_TRY(resident_run(w->resident, A, x, r, p, sv, u, wv, w->dcode.p, w->invtab.p, sc, max_iters, nullptr, stream, &launched));
+    AVS_TRY(resident_run(w->resident, A, x, w->r.p, w->p.p, w->s.p, w->u.p, w->t.p, w->dcode.p, w->invtab.p, w->sc.p, max_iters, nullptr,
+                         stream, &launched));
     if (!launched) return AVS_OK; // (x is untouched: the launch-per-phase loop starts over from it)
-    AVS_HIP(hipMemcpyAsync(w->host_sc, sc, sizeof(PcgScalars), hipMemcpyDeviceToHost, stream));
-    AVS_HIP(hipStreamSynchronize(stream));
+    AVS_TRY(poll_scalars(w, w->sc.p, stream));
     bool faulted = w->host_sc->fault != 0;
 #ifdef AVS_PROBES
     if (getenv("AVS_CG_RESIDENT_FAKE_FAULT")) faulted = true; // test hook of exactly this path (probe build only)
@@ -2309,23 +2383,7 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
     *ran = true;
     w->resident_used = 1;
     if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), stream)); // rhs == 0: x := 0
-    AVS_HIP(hipEventRecord(w->ev1, stream));
-    AVS_HIP(hipEventSynchronize(w->ev1));
-    float ms = 0.f;
-    AVS_HIP(hipEventElapsedTime(&ms, w->ev0, w->ev1));
-    if (info) {
-        const PcgScalars &h = *w->host_sc;
-        info->iterations = h.iter;
-        info->converged = (h.done != 0) ? 1 : 0;
-        info->rhs_norm2 = h.rhs_norm2;
-        info->error = (h.done == 3 || h.rhs_norm2 == 0.) ? 0. : sqrt(h.rr / h.rhs_norm2);
-        info->n = n;
-        info->nnz = A.nnz;
-        info->solve_ms = ms;
-        info->spmv_ms = 0.; // no separate SpMV launch to time
-        info->resident = 1;
-        info->cancelled = 0;
-    }
+    AVS_TRY(finish_info(w, A, stream, info, nullptr, false, 1, false)); // (spmv_ms = 0: no separate SpMV launch to time)
     // avs_cancel during the cooperative launch: the launch cannot be interrupted, but the request ends HERE -- consumed, and reported when the
     // loop stopped at max_iterations without converging (a converged solve is a converged solve; the request is consumed either way, so that
     // it cannot hit the next solve on this context)
@@ -2362,31 +2420,17 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
         if (ran || rs != AVS_OK) return rs;
     }
     if (!dist && A.f32_vectors < 0) return pcg_solve_f32(w, A, b, x, tol, max_iters, stream, info); // (auto: the resident loop did not take it)
-    if (A.brick && A.brick->ntiles > 0) { // one partial per wave of every tile: tiles may be smaller than 512 rows
-        const size_t need = 2 * ((size_t)A.brick->ntiles * 8 + 16) + 4 * (size_t)kVecGrid + 16;
-        if (need > w->npartial) {
-            AVS_TRY(w->partial.alloc(need));
-            w->npartial = need;
-            if (w->graph) { (void)hipGraphExecDestroy(w->graph); w->graph = nullptr; }
-        }
-    }
-    const int vgrid = (int)((n + kBlock - 1) / kBlock < kVecGrid ? (n + kBlock - 1) / kBlock : kVecGrid);
-    const int g = vgrid > 0 ? vgrid : 1;
-    const int rowgrid = (int)((n + kBlock - 1) / kBlock) > 0 ? (int)((n + kBlock - 1) / kBlock) : 1;
+    if (A.brick && A.brick->ntiles > 0) // one partial per wave of every tile: tiles may be smaller than 512 rows
+        AVS_TRY(ensure_partials(w, 2 * ((size_t)A.brick->ntiles * 8 + 16) + 4 * (size_t)kVecGrid + 16));
+    const int g = vec_grid(n);
     const int variant = spmv_default_variant(A);
     double *p = w->p.p, *r = w->r.p, *t = w->t.p, *invd = w->invd.p, *partial = w->partial.p;
     PcgScalars *sc = w->sc.p;
 
     AVS_HIP(hipMemsetAsync(sc, 0, sizeof(PcgScalars), stream));
-    hipLaunchKernelGGL(k_inv_diag, dim3(rowgrid), dim3(kBlock), 0, stream, A, invd);
     // few distinct values: the two vector kernels of the loop read a 2-B diagonal code instead of the 8-B inverse
     const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable; // (tile-local codes are not indices into one table)
-    if (coded) {
-        if (!w->dcode.p) AVS_TRY(w->dcode.alloc((size_t)n + 2));
-        if (!w->invtab.p) AVS_TRY(w->invtab.alloc((size_t)kViLdsTable + 1));
-        const int cg = (int)(((n > A.table_size + 1 ? n : A.table_size + 1) + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_inv_diag_coded, dim3(cg), dim3(kBlock), 0, stream, A, w->dcode.p, w->invtab.p);
-    }
+    AVS_TRY(prepare_diagonal(w, A, coded, invd, stream));
     AVS_HIP(hipEventRecord(w->ev0, stream));
 
     // residual = rhs - mat * x
@@ -2404,14 +2448,7 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
     AVS_TRY(reduce_stage(w, g, 1, OP_RHO0, tol, 0, stream, dist));
     AVS_HIP(hipGetLastError());
 
-    int enqueued = 0, last_chunk = 0;
-    double spmv_ms_sum = 0.;
-    int spmv_samples = 0;
-    const bool sample = (info != nullptr);
-    bool finished = false, cancelled = false;
-    bool timed_chunk = true;
-    bool use_graph = !dist;
-    use_graph = use_graph && cur_opt().graph != 0;
+    const bool use_graph = !dist && cur_opt().graph != 0;
     bool fuse_beta = !dist; // multi-GPU (RCCL transport): the sums are all-reduced between the two vector kernels
     fuse_beta = fuse_beta && cur_opt().fuse_beta != 0;
     static_assert(kChunk % 2 == 0, "the parity of an iteration is taken from its position in the chunk");
@@ -2488,65 +2525,22 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
         else AVS_VEC_LAUNCH(k_update_xp, false, false, n, x, p, r, invd, nullptr, sc, nullptr, 0, 0);
         return AVS_OK;
     };
-    while (!finished) {
-        AVS_HIP(hipMemcpyAsync(w->host_sc, sc, sizeof(PcgScalars), hipMemcpyDeviceToHost, stream));
-        AVS_HIP(hipStreamSynchronize(stream));
-        if (sample && last_chunk > 0 && timed_chunk) {
-            // SpMV launches that really ran: iterations 0..iter (the one that detected convergence included)
-            const int ran = w->host_sc->iter + ((w->host_sc->done == 1 || w->host_sc->done == 2) ? 1 : 0);
-            const int first = enqueued - last_chunk;
-            for (int c2 = 0; c2 < last_chunk && first + c2 < ran; c2 += kSampleEvery) {
-                float ems = 0.f;
-                if (hipEventElapsedTime(&ems, w->evA[c2], w->evB[c2]) == hipSuccess) {
-                    spmv_ms_sum += ems;
-                    ++spmv_samples;
-                }
-            }
-        }
-        if (w->host_sc->done || enqueued >= max_iters) break;
-        if (!dist && cancel_consume()) { cancelled = true; break; } // avs_cancel (single GPU: the host's poll is the only party to agree with)
-        const int chunk = (max_iters - enqueued) < kChunk ? (max_iters - enqueued) : kChunk;
-        // some chunks are enqueued launch by launch with the SpMV timing events; the other full chunks replay one captured
-        // hipGraph (4 kernel nodes per iteration): no per-launch host work, smaller gaps between the short kernels of small
-        // systems.  Kernels past convergence exit at once, so replaying a whole chunk is always safe.
-        // every kTimedChunkEvery-th chunk stays a plain, timed one so that the SpMV samples cover the whole solve
-        const bool replay = use_graph && (enqueued / kChunk) % kTimedChunkEvery != 0 && chunk == kChunk && !w->graph_broken;
-        timed_chunk = !replay;
-        if (replay) {
-            const void *key[10] = {A.row_ptr, A.col, A.val, A.codes, A.packed, A.table, x, (const void *)(intptr_t)A.n,
-                                   (const void *)(intptr_t)(A.table_size * 64 + A.col_bits), (const void *)(intptr_t)((coded ? 1 : 0) | (fuse_beta ? 2 : 0) | (A.brick ? 4 : 0) | (int64_t)(A.epoch << 4) | (fuse_vec ? 8 : 0))};
-            if (w->graph && (memcmp(key, w->graph_key, sizeof(key)) != 0 || w->graph_tol != tol)) {
-                (void)hipGraphExecDestroy(w->graph);
-                w->graph = nullptr;
-            }
-            if (!w->graph) {
-                hipGraph_t gr = nullptr;
-                bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) == hipSuccess;
-                if (ok) {
-                    for (int c = 0; c < kChunk && ok; ++c) ok = enqueue_iteration(c, false) == AVS_OK;
-                    ok = (hipStreamEndCapture(stream, &gr) == hipSuccess) && ok && gr;
-                }
-                if (ok) ok = hipGraphInstantiate(&w->graph, gr, nullptr, nullptr, 0) == hipSuccess;
-                if (gr) (void)hipGraphDestroy(gr);
-                if (!ok) { // fall back to plain launches for the rest of this workspace's life
-                    (void)hipGetLastError();
-                    w->graph = nullptr;
-                    w->graph_broken = true;
-                } else {
-                    memcpy(w->graph_key, key, sizeof(key));
-                    w->graph_tol = tol;
-                }
-            }
-        }
-        if (replay && w->graph) {
-            AVS_HIP(hipGraphLaunch(w->graph, stream));
-        } else {
-            timed_chunk = true;
-            for (int c = 0; c < chunk; ++c) AVS_TRY(enqueue_iteration(c, sample && (c % kSampleEvery == 0)));
-        }
-        AVS_HIP(hipGetLastError());
-        enqueued += chunk;
-        last_chunk = chunk;
+    GraphKey key = matrix_key(kGraphF64, A, x, tol);
+    key.val = A.val;
+    key.coded = coded;
+    key.fuse_beta = fuse_beta;
+    key.fuse_vec = fuse_vec;
+    key.brick = A.brick != nullptr;
+    ChunkState cs;
+    bool cancelled = false;
+    for (;;) {
+        AVS_TRY(poll_scalars(w, sc, stream));
+        sample_spmv(w, info != nullptr, false, &cs);
+        if (w->host_sc->done || cs.enqueued >= max_iters) break;
+        // avs_cancel (single GPU: the host's poll is the only party to agree with).  Known gap: the RCCL standard-CG path (dist)
+        // ignores it -- there is no all-rank vote here, so the request is neither consumed nor acted on
+        if (!dist && cancel_consume()) { cancelled = true; break; }
+        AVS_TRY(enqueue_chunk(w, stream, use_graph ? &key : nullptr, max_iters, info != nullptr, enqueue_iteration, &cs));
     }
 #ifdef AVS_PROBES
     if (fuse_vec && getenv("AVS_PCG_FUSED_FAKE_FAULT")) w->host_sc->fault = 4; // test hook of exactly the path below (probe build only)
@@ -2554,28 +2548,11 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
     if (fuse_vec && w->host_sc->fault == 4) { // the fused launch's grid barrier timed out (GPU shared with other work): the solve again, from
         w->fused_off = true;                    // the initial guess, with the two vector launches -- on this workspace from now on
         w->fused_faults++;
-        if (w->graph) { (void)hipGraphExecDestroy(w->graph); w->graph = nullptr; }
+        drop_graph(w);
         AVS_HIP(hipMemcpyAsync(x, w->x_save.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
         return pcg_solve(w, A, b, x, tol, max_iters, stream, info, dist);
     }
-    AVS_HIP(hipEventRecord(w->ev1, stream));
-    AVS_HIP(hipEventSynchronize(w->ev1));
-    float ms = 0.f;
-    AVS_HIP(hipEventElapsedTime(&ms, w->ev0, w->ev1));
-    if (info) {
-        const PcgScalars &h = *w->host_sc;
-        info->iterations = h.iter;
-        info->converged = (h.done != 0) ? 1 : 0;
-        info->rhs_norm2 = h.rhs_norm2;
-        info->error = (h.done == 3 || h.rhs_norm2 == 0.) ? 0. : sqrt(h.rr / h.rhs_norm2);
-        info->n = n;
-        info->nnz = A.nnz;
-        info->solve_ms = ms;
-        info->spmv_ms = spmv_samples ? spmv_ms_sum / spmv_samples : 0.;
-        info->resident = 0;
-        info->cancelled = cancelled ? 1 : 0;
-    }
-    return AVS_OK;
+    return finish_info(w, A, stream, info, &cs, cancelled, 0, false);
 }
 
 #ifdef AVS_PROBES

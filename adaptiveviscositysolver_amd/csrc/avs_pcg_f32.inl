@@ -333,15 +333,9 @@ static avs_status pcg_solve_f32(PcgWork *w, const CsrView &A, const double *b, d
     {
         size_t need = 2 * ((size_t)((n + kBlock - 1) / kBlock) + 16) + 4 * (size_t)kVecGrid + 16; // the streaming kernel: one partial per 256 rows
         if (brick) { const size_t nb = 2 * ((size_t)A.brick->ntiles * 8 + 16) + 4 * (size_t)kVecGrid + 16; need = nb > need ? nb : need; }
-        if (need > w->npartial) {
-            AVS_TRY(w->partial.alloc(need));
-            w->npartial = need;
-            if (w->graph) { (void)hipGraphExecDestroy(w->graph); w->graph = nullptr; }
-        }
+        AVS_TRY(ensure_partials(w, need));
     }
-    const int vgrid = (int)((n + kBlock - 1) / kBlock < kVecGrid ? (n + kBlock - 1) / kBlock : kVecGrid);
-    const int g = vgrid > 0 ? vgrid : 1;
-    const int rowgrid = (int)((n + kBlock - 1) / kBlock) > 0 ? (int)((n + kBlock - 1) / kBlock) : 1;
+    const int g = vec_grid(n);
     float *xf = w->f_x.p, *p = w->f_p.p, *r = w->f_r.p, *t = w->f_t.p, *bf = w->f_b.p;
     double *partial = w->partial.p;
     PcgScalars *sc = w->sc.p;
@@ -351,17 +345,14 @@ static avs_status pcg_solve_f32(PcgWork *w, const CsrView &A, const double *b, d
     hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, (const double *)x, xf);
     const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable;
     float *invd = nullptr;
+    AVS_TRY(prepare_diagonal(w, A, coded, nullptr, stream));
     if (coded) {
-        if (!w->dcode.p) AVS_TRY(w->dcode.alloc((size_t)n + 8));
-        if (!w->invtab.p) AVS_TRY(w->invtab.alloc((size_t)kViLdsTable + 1));
         if (!w->f_invtab.p) AVS_TRY(w->f_invtab.alloc((size_t)kViLdsTable + 1));
-        const int cg = (int)(((n > A.table_size + 1 ? n : A.table_size + 1) + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_inv_diag_coded, dim3(cg), dim3(kBlock), 0, stream, A, w->dcode.p, w->invtab.p);
         hipLaunchKernelGGL(k_f32_invtab, dim3((A.table_size + kBlock) / kBlock), dim3(kBlock), 0, stream, A, w->f_invtab.p);
         invd = w->f_invtab.p;
     } else {
         if (!w->f_invd.p) AVS_TRY(w->f_invd.alloc(na));
-        hipLaunchKernelGGL(k_f32_inv_diag, dim3(rowgrid), dim3(kBlock), 0, stream, A, w->f_invd.p);
+        hipLaunchKernelGGL(k_f32_inv_diag, dim3(row_grid(n)), dim3(kBlock), 0, stream, A, w->f_invd.p);
         invd = w->f_invd.p;
     }
     const uint16_t *dcode = coded ? w->dcode.p : nullptr;
@@ -376,12 +367,6 @@ static avs_status pcg_solve_f32(PcgWork *w, const CsrView &A, const double *b, d
     AVS_TRY(reduce_stage(w, g, 1, OP_RHO0, tol, 0, stream, nullptr));
     AVS_HIP(hipGetLastError());
 
-    int enqueued = 0, last_chunk = 0;
-    double spmv_ms_sum = 0.;
-    int spmv_samples = 0;
-    const bool sample = (info != nullptr);
-    bool cancelled = false;
-    bool timed_chunk = true;
     const bool use_graph = cur_opt().graph != 0;
     // float vectors are half as large: matrix + vectors fit the Infinity Cache more often (same rule, half the vector bytes)
     const int keep = A.keep_cached ? 1 : 0;
@@ -405,81 +390,22 @@ static avs_status pcg_solve_f32(PcgWork *w, const CsrView &A, const double *b, d
         else AVS_F32_LAUNCH_XP(false, n, xf, p, r, invd, dcode, sc, vpart, g, parity);
         return AVS_OK;
     };
+    GraphKey key = matrix_key(kGraphF32, A, xf, tol);
+    key.val = A.val;
+    key.coded = coded;
+    key.fuse_beta = true;
+    key.brick = brick;
+    ChunkState cs;
+    bool cancelled = false;
     for (;;) {
-        AVS_HIP(hipMemcpyAsync(w->host_sc, sc, sizeof(PcgScalars), hipMemcpyDeviceToHost, stream));
-        AVS_HIP(hipStreamSynchronize(stream));
-        if (sample && last_chunk > 0 && timed_chunk) {
-            const int ran = w->host_sc->iter + ((w->host_sc->done == 1 || w->host_sc->done == 2) ? 1 : 0);
-            const int first = enqueued - last_chunk;
-            for (int c2 = 0; c2 < last_chunk && first + c2 < ran; c2 += kSampleEvery) {
-                float ems = 0.f;
-                if (hipEventElapsedTime(&ems, w->evA[c2], w->evB[c2]) == hipSuccess) {
-                    spmv_ms_sum += ems;
-                    ++spmv_samples;
-                }
-            }
-        }
-        if (w->host_sc->done || enqueued >= max_iters) break;
+        AVS_TRY(poll_scalars(w, sc, stream));
+        sample_spmv(w, info != nullptr, false, &cs);
+        if (w->host_sc->done || cs.enqueued >= max_iters) break;
         if (cancel_consume()) { cancelled = true; break; }
-        const int chunk = (max_iters - enqueued) < kChunk ? (max_iters - enqueued) : kChunk;
-        const bool replay = use_graph && (enqueued / kChunk) % kTimedChunkEvery != 0 && chunk == kChunk && !w->graph_broken;
-        timed_chunk = !replay;
-        if (replay) {
-            const void *key[10] = {A.row_ptr, A.col, A.val, A.codes, A.packed, A.table, xf, (const void *)(intptr_t)A.n,
-                                   (const void *)(intptr_t)(A.table_size * 64 + A.col_bits),
-                                   (const void *)(intptr_t)((coded ? 1 : 0) | 2 | (brick ? 4 : 0) | (int64_t)(A.epoch << 3))};
-            if (w->graph && (memcmp(key, w->graph_key, sizeof(key)) != 0 || w->graph_tol != tol)) {
-                (void)hipGraphExecDestroy(w->graph);
-                w->graph = nullptr;
-            }
-            if (!w->graph) {
-                hipGraph_t gr = nullptr;
-                bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) == hipSuccess;
-                if (ok) {
-                    for (int c = 0; c < kChunk && ok; ++c) ok = enqueue_iteration(c, false) == AVS_OK;
-                    ok = (hipStreamEndCapture(stream, &gr) == hipSuccess) && ok && gr;
-                }
-                if (ok) ok = hipGraphInstantiate(&w->graph, gr, nullptr, nullptr, 0) == hipSuccess;
-                if (gr) (void)hipGraphDestroy(gr);
-                if (!ok) {
-                    (void)hipGetLastError();
-                    w->graph = nullptr;
-                    w->graph_broken = true;
-                } else {
-                    memcpy(w->graph_key, key, sizeof(key));
-                    w->graph_tol = tol;
-                }
-            }
-        }
-        if (replay && w->graph) {
-            AVS_HIP(hipGraphLaunch(w->graph, stream));
-        } else {
-            timed_chunk = true;
-            for (int c = 0; c < chunk; ++c) AVS_TRY(enqueue_iteration(c, sample && (c % kSampleEvery == 0)));
-        }
-        AVS_HIP(hipGetLastError());
-        enqueued += chunk;
-        last_chunk = chunk;
+        AVS_TRY(enqueue_chunk(w, stream, use_graph ? &key : nullptr, max_iters, info != nullptr, enqueue_iteration, &cs));
     }
     hipLaunchKernelGGL(k_f32_widen, dim3(g), dim3(kBlock), 0, stream, n, (const float *)xf, x);
-    AVS_HIP(hipEventRecord(w->ev1, stream));
-    AVS_HIP(hipEventSynchronize(w->ev1));
-    float ms = 0.f;
-    AVS_HIP(hipEventElapsedTime(&ms, w->ev0, w->ev1));
-    if (info) {
-        const PcgScalars &h = *w->host_sc;
-        info->iterations = h.iter;
-        info->converged = (h.done != 0) ? 1 : 0;
-        info->rhs_norm2 = h.rhs_norm2;
-        info->error = (h.done == 3 || h.rhs_norm2 == 0.) ? 0. : (double)sqrtf((float)h.rr / (float)h.rhs_norm2);
-        info->n = n;
-        info->nnz = A.nnz;
-        info->solve_ms = ms;
-        info->spmv_ms = spmv_samples ? spmv_ms_sum / spmv_samples : 0.;
-        info->resident = 0;
-        info->cancelled = cancelled ? 1 : 0;
-    }
-    return AVS_OK;
+    return finish_info(w, A, stream, info, &cs, cancelled, 0, true);
 }
 #undef AVS_F32_LAUNCH_R
 #undef AVS_F32_LAUNCH_XP
