@@ -1128,6 +1128,47 @@ avs_status avs_spmv_solver_form(avs_ctx *c, const double *x, double *y, int32_t 
     return AVS_OK;
 }
 
+// y = A x on a caller's CSR with the storage form avs_pcg_csr would build for it (build_matrix_index under the AVS_* environment of the
+// call) and the kernel the solve would launch on that form; *fmt reports the form (the fields avs_get_matrix_format fills for it)
+avs_status avs_spmv_csr_form(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val, const double *x, double *y,
+                             int32_t flags, double *dot_out, avs_matrix_format *fmt, void *stream)
+{
+    avs::OptScope opt_scope_(nullptr); // context-free entry, like avs_pcg_csr
+    AVS_REQUIRE(n >= 0 && row_ptr && x && y && (n == 0 || (col && val)), AVS_EINVAL, "null argument");
+    AVS_REQUIRE(!fmt || fmt->struct_size >= (int32_t)(offsetof(avs_matrix_format, column_windows) + sizeof(int32_t)), AVS_EINVAL,
+                "avs_matrix_format.struct_size must be set to sizeof(avs_matrix_format) before the call");
+    AVS_REQUIRE((flags & ~(AVS_SPMV_FORM_FUSED_DOT | AVS_SPMV_FORM_F32 | AVS_SPMV_FORM_NO_CACHE_HINT)) == 0, AVS_EINVAL, "unknown flags 0x%x",
+                (unsigned)flags);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int32_t nnz = 0;
+    AVS_HIP(hipMemcpyAsync(&nnz, row_ptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AVS_HIP(hipStreamSynchronize(st));
+    CsrView A;
+    A.n = n;
+    A.nnz = nnz;
+    A.row_ptr = row_ptr;
+    A.col = col;
+    A.val = val;
+    ValueIndex vi;
+    if (nnz > 0) AVS_TRY(build_matrix_index(row_ptr, col, val, n, nnz, n, vi, st));
+    vi.apply(A);
+    if (flags & AVS_SPMV_FORM_NO_CACHE_HINT) A.keep_cached = false;
+    if (flags & AVS_SPMV_FORM_F32) A.f32_vectors = 1;
+    if (fmt) {
+        const bool coded = vi.table_size > 0;
+        fmt->reordered = 0;
+        fmt->value_table_size = coded ? vi.table_size : 0;
+        fmt->column_bits = coded ? vi.col_bits : 0;
+        fmt->bytes_per_nonzero = vi.bytes_per_nonzero();
+        fmt->tile_local_tables = coded && vi.tile_tables ? 1 : 0;
+        fmt->column_windows = coded && vi.col_windows ? 1 : 0;
+    }
+    if (dot_out) *dot_out = 0.;
+    if (n > 0) AVS_TRY(probe_spmv_form(A, x, y, (flags & AVS_SPMV_FORM_FUSED_DOT) != 0, dot_out, st));
+    AVS_HIP(hipStreamSynchronize(st)); // the form's arrays die here
+    return AVS_OK;
+}
+
 // Measured stream ceilings (mode 0: read-only 16 B/lane, 1: read-only non-temporal, 2: copy) on
 // `bytes` of HBM; returns GB/s of bytes MOVED (copy counts read + write).
 avs_status avs_bench_stream(int32_t mode, int64_t bytes, int32_t repeats, int32_t device, double *gbps)

@@ -237,7 +237,7 @@ avs_status build_reordered_system(avs_ctx *c, int brick_shift)
 // => no dictionary (plain CSR).
 // ---------------------------------------------------------------------------------------------
 static constexpr int kHashBits = 18; // 262144 slots for <= 65536 keys
-static constexpr unsigned long long kEmpty = 0xFFFFFFFFFFFFFFFFull; // a NaN pattern: never a matrix value
+static constexpr unsigned long long kEmpty = 0xFFFFFFFFFFFFFFFFull; // a NaN pattern: a matrix holding it gets no dictionary (k_vi_insert, k_tlt_build)
 
 __device__ __forceinline__ unsigned hash64(unsigned long long k)
 {
@@ -249,6 +249,8 @@ __device__ __forceinline__ unsigned hash64(unsigned long long k)
 
 static constexpr int kInsertBlock = 1024; // one LDS filter serves 16 waves: first sightings (global look-ups) per wave stay few
 
+// count[0]: distinct values inserted; count[2]: set when a value has the bit pattern of kEmpty -- it cannot be a key of the table (its
+// look-ups would stop at the first empty slot and read a code nobody wrote), so the matrix gets no dictionary
 __global__ __launch_bounds__(kInsertBlock) void k_vi_insert(const double *__restrict__ val, int64_t nnz, unsigned long long *__restrict__ slots,
                                                       int *__restrict__ count)
 {
@@ -271,7 +273,10 @@ __global__ __launch_bounds__(kInsertBlock) void k_vi_insert(const double *__rest
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
             const unsigned long long key = keys[u];
-            if (key == kEmpty) continue;
+            if (key == kEmpty) {
+                if (k0 + (int64_t)u * kInsertBlock < nnz) count[2] = 1; // a stored value, not the padding of the last round
+                continue;
+            }
             unsigned h = hash64(key);
             bool hit = false;
 #pragma unroll
@@ -347,14 +352,14 @@ avs_status build_value_index(const double *val, int64_t nnz, DevBuf<uint16_t> &c
     AVS_TRY(slots.alloc(1u << kHashBits));
     AVS_TRY(keys.alloc(65536));
     AVS_TRY(slot_code.alloc(1u << kHashBits));
-    AVS_TRY(counters.alloc(2));
+    AVS_TRY(counters.alloc(3));
     AVS_HIP(hipMemsetAsync(slots.p, 0xFF, sizeof(unsigned long long) << kHashBits, st));
-    AVS_HIP(hipMemsetAsync(counters.p, 0, 2 * sizeof(int), st));
+    AVS_HIP(hipMemsetAsync(counters.p, 0, 3 * sizeof(int), st));
     hipLaunchKernelGGL(k_vi_insert, dim3(256), dim3(kInsertBlock), 0, st, val, nnz, slots.p, counters.p); // persistent: see the kernel
-    int h_count[2] = {0, 0};
+    int h_count[3] = {0, 0, 0};
     AVS_HIP(hipMemcpyAsync(h_count, counters.p, sizeof(h_count), hipMemcpyDeviceToHost, st));
     AVS_HIP(hipStreamSynchronize(st));
-    if (h_count[0] > 65536) return AVS_OK; // plain CSR
+    if (h_count[0] > 65536 || h_count[2]) return AVS_OK; // plain CSR (or tile-local dictionaries)
     const int nkeys = h_count[0];
     hipLaunchKernelGGL(k_vi_collect, dim3((1u << kHashBits) / kBlock), dim3(kBlock), 0, st, slots.p, keys.p, counters.p + 1);
     std::vector<unsigned long long> h_keys((size_t)nkeys);
@@ -453,6 +458,7 @@ __global__ __launch_bounds__(kTltRows) void k_tlt_build(int64_t n, const int32_t
     __syncthreads();
     for (int k = s + tid; k < e; k += kTltRows) {
         const unsigned long long key = (unsigned long long)__double_as_longlong(val[k]);
+        if (key == kEmpty) { atomicMax(&count, kTltMaxKeys + 1); break; } // the empty-slot pattern cannot be a key: treated as an overflow
         unsigned h = tlt_hash(key);
         while (true) {
             const unsigned long long cur = slots[h];

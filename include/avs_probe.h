@@ -31,6 +31,18 @@ avs_status avs_spmv_solver_form(avs_ctx *ctx, const double *x, double *y, int32_
  * [owned | halo] entries in local numbering (n_own + n_halo doubles, device), y its n_own rows */
 avs_status avs_dist_spmv_local_form(avs_ctx *ctx, const double *x_ext, double *y, int32_t fused_dot, double *dot_out);
 
+/* y = A x on a caller's device CSR (reference numbering kept) with the lossless storage form avs_pcg_csr builds for it -- chosen under the
+ * AVS_* environment of the call -- and the kernel the solve launches on that form.  *fmt (may be NULL; struct_size set by the caller) gets
+ * value_table_size, column_bits, bytes_per_nonzero, tile_local_tables and column_windows of the form; the other fields are not written.
+ * flags: AVS_SPMV_FORM_FUSED_DOT the fused-dot instantiation, the folded x.y in *dot_out; AVS_SPMV_FORM_F32 the float kernel of
+ * AVS_PRECISION_F32 (x narrowed to float, y widened); AVS_SPMV_FORM_NO_CACHE_HINT the instantiation with non-temporal matrix loads, which
+ * small matrices (those that fit the Infinity Cache) never reach otherwise. */
+#define AVS_SPMV_FORM_FUSED_DOT 1
+#define AVS_SPMV_FORM_F32 2
+#define AVS_SPMV_FORM_NO_CACHE_HINT 4
+avs_status avs_spmv_csr_form(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val, const double *x, double *y,
+                             int32_t flags, double *dot_out, avs_matrix_format *fmt, void *stream);
+
 /* Measurement: load balance of the brick kernel's row walk -- per G tile the quads of the slowest of the eight waves against the mean wave
  * (printed to stderr; out6 = {tiles, rows per tile, quads per row, slowest-wave quads, mean-wave quads, 0}) */
 avs_status avs_brick_wave_stats(avs_ctx *ctx, double *out6);

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from adaptiveviscositysolver_amd import ViscositySolve, capi, scenes
-from util import build_pyramid, feed, oracle_from_pyramid, rel_l2
+from util import build_pyramid, feed, float_row_sums, oracle_from_pyramid, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -46,21 +46,6 @@ def _oracle_f32(sc, pyr):
     return o
 
 
-def _float_row_sums(row_ptr, col, val, x):
-    """SPMV_F of the oracle (oracle/avs_oracle.c, orc_pcg_csr_f32): s = 0.f; s += v[k] * x[col[k]] for k in the row's stored order."""
-    rp = np.asarray(row_ptr, dtype=np.int64)
-    v = val.astype(np.float32)
-    xf = x.astype(np.float32)
-    n = len(rp) - 1
-    length = rp[1:] - rp[:-1]
-    s = np.zeros(n, dtype=np.float32)
-    for j in range(int(length.max()) if n else 0):
-        m = length > j
-        k = rp[:-1][m] + j
-        s[m] = s[m] + v[k] * xf[col[k]]          # float32 multiply, float32 add: one rounding each
-    return s
-
-
 @pytest.mark.parametrize("name", list(SCENES))
 def test_f32_product_is_the_float_row_sum(name, monkeypatch, built_lib):
     make, brick = SCENES[name]
@@ -80,7 +65,7 @@ def test_f32_product_is_the_float_row_sum(name, monkeypatch, built_lib):
     rng = np.random.default_rng(5)
     for trial in range(2):
         x = (rng.standard_normal(n) * (10.0 ** rng.integers(-3, 4, n))).astype(np.float32).astype(np.float64)
-        want = _float_row_sums(A.row_ptr, A.col, A.val, x)
+        want = float_row_sums(A.row_ptr, A.col, A.val, x)
         dx = torch.from_numpy(x).to(dev)
         for fused in (0, 1):
             dy = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)

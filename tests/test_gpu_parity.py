@@ -138,20 +138,27 @@ def test_rigid_translation_is_a_fixed_point(dev, built_lib):
     assert np.array_equal(x, s.initial_guess())
 
 
-@pytest.mark.parametrize("variant", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24])
-def test_spmv_variants(variant, dev, built_lib):
+@pytest.fixture(scope="module")
+def beam64_csr(dev, built_lib):
+    """the assembled fat_beam(64, 3) system on the device, a random x and the oracle's product: shared by the 24 variants"""
     sc = scenes.fat_beam(64, 3, device=dev)
     pyr = build_pyramid(sc)
     s = gpu_solve_for(sc, pyr)
     s.assemble()
     rp, col, val, rhs = s.csr()
+    s.close()
     n = len(rhs)
     rng = np.random.default_rng(7)
     x = rng.standard_normal(n)
     want = O.spmv_csr(rp.astype(np.int64), col, val, x)
-    lib = capi.load_probe()      # avs_spmv_csr: a measurement entry (include/avs_probe.h)
     t = lambda a: torch.from_numpy(a).to(dev)
-    d_rp, d_col, d_val, d_x = t(rp), t(col), t(val), t(x)
+    return n, t(rp), t(col), t(val), t(x), want
+
+
+@pytest.mark.parametrize("variant", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24])
+def test_spmv_variants(variant, dev, beam64_csr):
+    n, d_rp, d_col, d_val, d_x, want = beam64_csr
+    lib = capi.load_probe()      # avs_spmv_csr: a measurement entry (include/avs_probe.h)
     d_y = torch.zeros(n, dtype=torch.float64, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
     capi.check(lib.avs_spmv_csr(n, d_rp.data_ptr(), d_col.data_ptr(), d_val.data_ptr(), d_x.data_ptr(),

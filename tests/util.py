@@ -58,6 +58,21 @@ def rel_l2(a, b):
     return float(np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300))
 
 
+def float_row_sums(row_ptr, col, val, x):
+    """SPMV_F of the oracle (oracle/avs_oracle.c, orc_pcg_csr_f32): s = 0.f; s += v[k] * x[col[k]] for k in the row's stored order."""
+    rp = np.asarray(row_ptr, dtype=np.int64)
+    v = val.astype(np.float32)
+    xf = x.astype(np.float32)
+    n = len(rp) - 1
+    length = rp[1:] - rp[:-1]
+    s = np.zeros(n, dtype=np.float32)
+    for j in range(int(length.max()) if n else 0):
+        m = length > j
+        k = rp[:-1][m] + j
+        s[m] = s[m] + v[k] * xf[col[k]]          # float32 multiply, float32 add: one rounding each
+    return s
+
+
 class DevicePyramid:
     """Hot-path inputs produced by the PRODUCT pre-pass (avs_prepass.hip through the C ABI).  Array attributes
     mirror prepass_torch.Pyramid (numpy, downloaded on first use) so that oracle_from_pyramid accepts both."""
