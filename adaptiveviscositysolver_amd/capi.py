@@ -27,7 +27,8 @@ STATUS_NAMES = {0: "AVS_OK", 1: "AVS_EINVAL", 2: "AVS_ENOMEM", 3: "AVS_EHIP", 4:
 MEM_HOST, MEM_DEVICE = 0, 1
 PRECISION_F64, PRECISION_F32 = 0, 1   # avs_desc.precision (SolveType of the reference, util.h:25-37)
 (OPTION_PRECONDITIONER, OPTION_RESIDENT_LOOP, OPTION_TRANSPORT, OPTION_PARANOID, OPTION_GRAPH_REPLAY, OPTION_BRICK_FORM,
- OPTION_FUSED_SCALAR_STEPS, OPTION_RELOAD_ENVIRONMENT, OPTION_F32_VECTORS, OPTION_FUSED_VECTOR_UPDATE) = range(10)  # avs_set_solver_option
+ OPTION_FUSED_SCALAR_STEPS, OPTION_RELOAD_ENVIRONMENT, OPTION_F32_VECTORS, OPTION_FUSED_VECTOR_UPDATE,
+ OPTION_DIST_F32_VECTORS) = range(11)  # avs_set_solver_option
 USE_TRANSPORT_AUTO, USE_TRANSPORT_RCCL, USE_TRANSPORT_DIRECT = 0, 1, 2
 BRICK_AUTO, BRICK_NEVER, BRICK_ALWAYS, BRICK_TUNE = -1, 0, 1, 2
 PRECONDITIONER_JACOBI, PRECONDITIONER_NONE = 0, 1
@@ -118,7 +119,7 @@ class MatrixFormat(C.Structure):
                 ("bytes_per_nonzero", C.c_int32), ("tile_local_tables", C.c_int32),
                 ("column_windows", C.c_int32), ("brick_tiles", C.c_int32), ("brick_patterns", C.c_int32), ("_pad", C.c_int32),
                 ("brick_pattern_rows", C.c_int64), ("brick_bytes", C.c_int64), ("brick_walk", C.c_int32), ("brick_value_codes", C.c_int32),
-                ("fused_vector_update", C.c_int32), ("fused_vector_faults", C.c_int32)]
+                ("fused_vector_update", C.c_int32), ("fused_vector_faults", C.c_int32), ("float_vectors", C.c_int32)]
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)

@@ -110,6 +110,7 @@ Options options_from_env()
     { const int v = env_int("AVS_PCG_FUSE_VECTORS", 0); o.fuse_vectors = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.fused_timeout_ms = env_int("AVS_PCG_FUSED_TIMEOUT_MS", 2000);
     { const int v = env_int("AVS_F32_VECTORS", -1); o.f32_vectors = v < 0 ? -1 : (v > 0 ? 1 : 0); }
+    o.dist_f32_vectors = env_int("AVS_DIST_F32_VECTORS", 0) != 0;
     o.prepass_temporal = env_int("AVS_PREPASS_TEMPORAL", 1) != 0;
     { const int v = env_int("AVS_POST_DOF_SAMPLE", -1); o.post_dof_sample = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.resident_cus = env_int("AVS_CG_RESIDENT_CUS", 0);
@@ -586,6 +587,7 @@ avs_status avs_get_matrix_format(avs_ctx *c, avs_matrix_format *out)
         memcpy(out, &f, (size_t)size < sizeof(f) ? (size_t)size : sizeof(f));
         out->struct_size = size;
     };
+    f.float_vectors = c->float_vectors;
     if (!c->system_ready && dist_matrix_format(c, fmt)) { hand_over(); return AVS_OK; } // avs_dist_assemble: the rank's own rows
     AVS_REQUIRE(c->system_ready, AVS_ESTATE, "no system: call avs_assemble first");
     const bool vi = c->reordered && c->vi.table_size > 0;
@@ -666,6 +668,7 @@ avs_status avs_set_solver_option(avs_ctx *c, avs_solver_option option, int32_t v
     case AVS_OPTION_RELOAD_ENVIRONMENT: c->opt = options_from_env(); c->brick_verdict_rows = 0; return AVS_OK;
     case AVS_OPTION_F32_VECTORS: c->opt.f32_vectors = value < 0 ? -1 : (value > 0 ? 1 : 0); return AVS_OK;
     case AVS_OPTION_FUSED_VECTOR_UPDATE: c->opt.fuse_vectors = value < 0 ? -1 : (value > 0 ? 1 : 0); return AVS_OK;
+    case AVS_OPTION_DIST_F32_VECTORS: c->opt.dist_f32_vectors = value != 0; return AVS_OK;
     }
     set_error("unknown solver option %d", (int)option);
     return AVS_EINVAL;
@@ -724,6 +727,7 @@ avs_status avs_solve(avs_ctx *c, double tol, int32_t max_iters, avs_solve_info *
         AVS_TRY(pcg_solve(c->pcg, csr_of(c), c->rhs.p, c->x.p, tol, max_iters, c->stream, &local, nullptr));
     }
     narrow_solution_if_f32(c, c->x.p, n);
+    c->float_vectors = pcg_float_vectors(c->pcg);
     if (info) *info = local;
     c->solved = true;
     return AVS_OK;

@@ -79,6 +79,8 @@ struct PcgDist {
     DevBuf<int32_t> local_ref; // reference DOF id behind every local column [owned | halo] (what the brick builder reads the geometry from)
     PcgWork *pcg = nullptr;
     bool partitioned = false, solved = false, reordered = false;
+    bool f32 = false; // AVS_PRECISION_F32 + AVS_OPTION_DIST_F32_VECTORS when this plan was made: the single-reduction loops run on float vectors
+    DevBuf<double> recvbuf; // float halo exchange (RCCL / in-process): the peers' entries, widened, before they are narrowed into the vector
     // slab cuts along cut_axis (fine cells, world + 1 entries): the ones this assembly used, and the ones its per-plane weights suggest
     // for the next frame (slab-local assembly: the pre-pass needs the cuts BEFORE anything is counted)
     std::vector<int32_t> cuts, next_cuts;
@@ -163,6 +165,18 @@ __global__ __launch_bounds__(256) void k_gather_i(const T *__restrict__ src, con
     if (i < n) dst[i] = src[idx[i]];
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void k_pack_wide(const T *__restrict__ p, const int32_t *__restrict__ idx, double *__restrict__ out, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (double)p[idx[i]];
+}
+__global__ __launch_bounds__(256) void k_unpack_narrow(const double *__restrict__ in, float *__restrict__ out, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (float)in[i];
+}
+
 // C1: p_ext = [owned | halo]; fills the halo tail from the peers' owned entries
 avs_status dist_halo_exchange(PcgDist *d, double *p_ext, hipStream_t stream)
 {
@@ -197,6 +211,53 @@ avs_status dist_halo_exchange(PcgDist *d, double *p_ext, hipStream_t stream)
         AVS_HIP(hipMemcpyAsync(p_ext + d->n_own + d->recv_offs[i], peer->sendbuf.p + off,
                                (size_t)d->recv_counts[i] * sizeof(double), hipMemcpyDeviceToDevice, stream));
     }
+    AVS_HIP(hipStreamSynchronize(stream));
+    g->barrier(); // nobody repacks before everybody has copied
+    return AVS_OK;
+}
+
+// the same for a float vector [owned | halo]: the entries travel widened to double through the send buffer (exact: they are floats),
+// land in recvbuf and are narrowed into the tail
+avs_status dist_halo_exchange_f32(PcgDist *d, float *p_ext, hipStream_t stream)
+{
+    if (d->world == 1) return AVS_OK;
+    AVS_TRY(d->recvbuf.reserve((size_t)(d->n_halo > 0 ? d->n_halo : 1)));
+    if (d->n_send)
+        hipLaunchKernelGGL(k_pack_wide<float>, dim3((unsigned)((d->n_send + 255) / 256)), dim3(256), 0, stream, (const float *)p_ext, d->send_idx.p,
+                           d->sendbuf.p, d->n_send);
+    if (d->comm) {
+        AVS_NCCL(ncclGroupStart());
+        for (size_t i = 0; i < d->peers.size(); ++i) {
+            if (d->send_counts[i])
+                AVS_NCCL(ncclSend(d->sendbuf.p + d->send_offs[i], (size_t)d->send_counts[i], ncclDouble, d->peers[i], d->comm_p2p, stream));
+            if (d->recv_counts[i])
+                AVS_NCCL(ncclRecv(d->recvbuf.p + d->recv_offs[i], (size_t)d->recv_counts[i], ncclDouble, d->peers[i], d->comm_p2p, stream));
+        }
+        AVS_NCCL(ncclGroupEnd());
+        if (d->n_halo)
+            hipLaunchKernelGGL(k_unpack_narrow, dim3((unsigned)((d->n_halo + 255) / 256)), dim3(256), 0, stream, (const double *)d->recvbuf.p,
+                               p_ext + d->n_own, d->n_halo);
+        AVS_HIP(hipGetLastError());
+        return AVS_OK;
+    }
+    avs_local_group *g = d->group;
+    AVS_REQUIRE(g, AVS_ESTATE, "multi-GPU layer not initialised");
+    AVS_HIP(hipStreamSynchronize(stream)); // my send buffer is packed
+    g->barrier();
+    for (size_t i = 0; i < d->peers.size(); ++i) {
+        if (!d->recv_counts[i]) continue;
+        PcgDist *peer = g->members[(size_t)d->peers[i]];
+        int64_t off = -1;
+        for (size_t j = 0; j < peer->peers.size(); ++j)
+            if (peer->peers[j] == d->rank) off = peer->send_offs[j];
+        AVS_REQUIRE(off >= 0, AVS_EINTERNAL, "peer %d has no send list for rank %d", d->peers[i], d->rank);
+        AVS_HIP(hipMemcpyAsync(d->recvbuf.p + d->recv_offs[i], peer->sendbuf.p + off, (size_t)d->recv_counts[i] * sizeof(double),
+                               hipMemcpyDeviceToDevice, stream));
+    }
+    if (d->n_halo)
+        hipLaunchKernelGGL(k_unpack_narrow, dim3((unsigned)((d->n_halo + 255) / 256)), dim3(256), 0, stream, (const double *)d->recvbuf.p,
+                           p_ext + d->n_own, d->n_halo);
+    AVS_HIP(hipGetLastError());
     AVS_HIP(hipStreamSynchronize(stream));
     g->barrier(); // nobody repacks before everybody has copied
     return AVS_OK;
@@ -562,6 +623,7 @@ bool dist_direct_args(PcgDist *d, DirectArgs *out)
     out->n_tiles_bnd = d->n_tiles_bnd;
     out->tile_flags = d->tile_flags.p;
     out->exclusive_device = d->exclusive_device;
+    out->paranoid = d->dd_host.paranoid != 0;
     return true;
 }
 
@@ -1225,11 +1287,13 @@ static avs_status dist_build_brick(avs_ctx *c, PcgDist *d)
         else {
             d->brick.view(d->brick_view, d->vi);
             d->brick_view.walk = fill >= kBrickEighthsFill ? 0 : 1;
+            d->brick_view.f32 = d->f32 ? 1 : 0; // the float-vector loop launches the float kernel: the walk is laid out for ITS grid
             if (c->opt.brick_plan) {
                 const int walk = d->brick_view.walk;
                 AVS_TRY(d->brick.plan_walk(brick_partial_count(d->brick_view), walk, c->opt.brick_cost, c->stream));
                 d->brick.view(d->brick_view, d->vi);
                 d->brick_view.walk = walk;
+                d->brick_view.f32 = d->f32 ? 1 : 0;
             }
             return AVS_OK;
         }
@@ -1947,6 +2011,7 @@ avs_status avs_dist_partition(avs_ctx *c, int32_t cut_axis)
     const bool ro = c->reordered;
     const double *g_rhs = ro ? c->p_rhs.p : c->rhs.p, *g_x0 = ro ? c->p_x0.p : c->x0.p;
     const bool host_plan = cur_opt().dist_host_plan != 0;
+    d->f32 = c->desc.precision == AVS_PRECISION_F32 && c->opt.dist_f32_vectors != 0;
     d->vi.clear();
     d->brick.clear();   // (the brick-structured form is built for distributed assemblies only: avs_dist_assemble)
     d->brick.view(d->brick_view, d->vi);
@@ -2028,6 +2093,7 @@ avs_status avs_dist_assemble(avs_ctx *c, int32_t cut_axis, avs_assembly_info *in
     t.start();
     c->system_ready = false; // no global matrix in this mode
     c->reordered = false;
+    d->f32 = c->desc.precision == AVS_PRECISION_F32 && c->opt.dist_f32_vectors != 0;
     d->vi.clear();
     if (c->slab.on) AVS_TRY(dist_assemble_window(c, d));
     else AVS_TRY(dist_assemble_device(c, d, cut_axis, extent));
@@ -2180,8 +2246,10 @@ avs_status avs_dist_solve(avs_ctx *c, double tol, int32_t max_iters, avs_solve_i
     d->vi.apply(A);
     A.no_precond = c->no_precond;
     A.brick = d->brick.ready ? &d->brick_view : nullptr;
+    A.f32_vectors = d->f32 ? 1 : 0;
     avs_solve_info local{};
     const avs_status rc = pcg_solve(d->pcg, A, d->rhs.p, d->x.p, tol, max_iters, c->stream, &local, d);
+    c->float_vectors = pcg_float_vectors(d->pcg);
     if (rc != AVS_OK) {
         // a peer's flag timed out: epochs / tickets of the comm blocks are no longer in step -- every rank sees the same fault
         // (it waits for the same peer) and leaves the direct transport for this plan; the next solve uses the fallback

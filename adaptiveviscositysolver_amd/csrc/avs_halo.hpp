@@ -110,7 +110,26 @@ __device__ __forceinline__ double wave_sum(double v)
 }
 
 
-enum ScalarOp { OP_NONE = 0, OP_INIT = 1, OP_RHO0 = 2, OP_ALPHA = 3, OP_BETA = 4, OP_SR_INIT = 5, OP_SR_STEP = 6, OP_ALPHA_ODD = 7 };
+enum ScalarOp { OP_NONE = 0, OP_INIT = 1, OP_RHO0 = 2, OP_ALPHA = 3, OP_BETA = 4, OP_SR_INIT = 5, OP_SR_STEP = 6, OP_ALPHA_ODD = 7,
+                OP_SR_INIT_F32 = 8, OP_SR_STEP_F32 = 9 };
+
+// The Chronopoulos-Gear step of the float-vector loops (avs_pcg_dist_f32.inl): the all-reduced double sums red = [r.u, r.r, w.u] rounded
+// to float, the scalars computed in float -- what Eigen's float CG holds -- and kept as doubles holding floats.  One function for the
+// finalizer, k_scalar and the step folded into k_sr_update_f32: every place computes the same bits.
+__device__ inline void sr_step_f32(const PcgScalars *in, double &rr, double &rho, double &alpha, double &beta, int &iter, int &done)
+{
+    if (done) return;
+    const float rrf = (float)in->red[1];
+    rr = (double)rrf;
+    if (rrf < (float)in->threshold) { done = 1; return; } // x is already updated: plain "converged"
+    const float gamma = (float)in->red[0], delta = (float)in->red[2];
+    const float b2 = gamma / (float)rho;
+    const float a = gamma / (delta - b2 * gamma / (float)alpha);
+    alpha = (double)a;
+    beta = (double)b2;
+    rho = (double)gamma;
+    iter += 1;
+}
 
 __device__ inline void apply_scalar_op(PcgScalars *sc, int op, double tol)
 {
@@ -177,6 +196,30 @@ __device__ inline void apply_scalar_op(PcgScalars *sc, int op, double tol)
             }
         }
         break;
+    case OP_SR_INIT_F32: { // red = [b.b, r.u, r.r, w.u]; Eigen's float threshold: tol^2 |b|^2 in float, at least the smallest normal float
+        const float bb = (float)sc->red[0], ru = (float)sc->red[1], rr = (float)sc->red[2], wu = (float)sc->red[3];
+        sc->rhs_norm2 = (double)bb;
+        sc->rr = (double)rr;
+        sc->iter = 0;
+        if (bb == 0.f) { sc->done = 3; sc->rr = 0.; break; }
+        const float t = (float)tol;
+        float thr = t * t * bb;
+        if (thr < 1.17549435e-38f) thr = 1.17549435e-38f;
+        sc->threshold = (double)thr;
+        if (rr < thr) { sc->done = 1; break; }
+        sc->done = 0;
+        sc->rho = (double)ru;
+        sc->alpha = (double)(ru / wu);
+        sc->beta = 0.;
+        break;
+    }
+    case OP_SR_STEP_F32: {
+        double rr = sc->rr, rho = sc->rho, alpha = sc->alpha, beta = sc->beta;
+        int iter = sc->iter, done = sc->done;
+        sr_step_f32(sc, rr, rho, alpha, beta, iter, done);
+        sc->rr = rr; sc->rho = rho; sc->alpha = alpha; sc->beta = beta; sc->iter = iter; sc->done = done;
+        break;
+    }
     default: break;
     }
 }

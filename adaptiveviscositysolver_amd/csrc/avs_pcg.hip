@@ -36,7 +36,7 @@ static constexpr int kSampleEvery = 4;       // SpMV launches bracketed by HIP e
 // What a captured chunk (PcgWork::graph) was recorded against: the loop, the buffers and sizes its launches read, its flags and the
 // tolerance.  It is replayed only while every field matches.  Each loop sets what it depends on and leaves the rest zero; the loop tag
 // keeps one loop from ever replaying another's graph on the same workspace.
-enum GraphLoop { kGraphF64 = 1, kGraphF32, kGraphDirect };
+enum GraphLoop { kGraphF64 = 1, kGraphF32, kGraphDirect, kGraphDirectF32 };
 struct GraphKey {
     int loop = 0;
     const void *row_ptr = nullptr, *col = nullptr, *val = nullptr, *codes = nullptr, *packed = nullptr, *table = nullptr;
@@ -60,6 +60,8 @@ struct PcgWork {
     DevBuf<uint16_t> dcode;  // value-indexed matrix: code of every row's diagonal entry ...
     DevBuf<double> invtab;   // ... into the table of inverted values (2 B instead of 8 B per row and vector pass)
     DevBuf<float> f_x, f_r, f_p, f_t, f_b, f_invd, f_invtab; // float-vector loop of AVS_PRECISION_F32 contexts (avs_pcg_f32.inl)
+    DevBuf<float> f_s, f_u;  // ... and s, u [owned | halo] of its partitioned single-reduction loops (avs_pcg_dist_f32.inl)
+    int float_vectors = 0;   // the last solve iterated on float vectors
     DevBuf<double> x_save;   // the initial guess while the CU-resident loop runs (restored if it faults)
     DevBuf<double> cancel_word; // partitioned solves: [0] this rank's avs_cancel request as the kernels / the all-reduce see it (0. / 1.)
     DevBuf<int> cancel_dev;     // ... and as an int for the finalizer of the direct transport
@@ -1921,10 +1923,17 @@ __device__ __forceinline__ void push_raise_flags(const DistDev *dd, const unsign
 // KEEP == false (round 5: the brick-structured form is small enough to stay in the Infinity Cache between two products -- but only
 // if the ~0.5 GB this kernel moves do not push it out): p, s, x, r -- read and written once per iteration, by this kernel only -- are
 // loaded and stored non-temporally; u (the next product's input) and w (the product's output, read here) stay cacheable.
-template <bool CODED, bool KEEP = true>
-__global__ __launch_bounds__(kBlock) void k_sr_update_push(int64_t n, double *__restrict__ x, double *__restrict__ r, double *__restrict__ p,
-                                                           double *__restrict__ s, double *__restrict__ u, const double *__restrict__ w,
-                                                           const double *__restrict__ invd, const uint16_t *__restrict__ dcode,
+// T (round 7): the vector type -- double, or float for the float-vector loop of AVS_PRECISION_F32 partitioned solves (avs_pcg_dist_f32.inl:
+// a thread's own sums in float, everything across threads in double; the pushed entries are widened to double, which is exact, so the
+// comm block, its 8-B slots and the checksums stay as they are).  Rows two at a time: 16-B (double) or 8-B (float) accesses.
+template <typename T> struct Pair;
+template <> struct Pair<double> { typedef d2_t type; };
+template <> struct Pair<float> { typedef float type __attribute__((ext_vector_type(2))); };
+
+template <bool CODED, bool KEEP = true, typename T = double>
+__global__ __launch_bounds__(kBlock) void k_sr_update_push(int64_t n, T *__restrict__ x, T *__restrict__ r, T *__restrict__ p,
+                                                           T *__restrict__ s, T *__restrict__ u, const T *__restrict__ w,
+                                                           const T *__restrict__ invd, const uint16_t *__restrict__ dcode,
                                                            const PcgScalars *sc, double *__restrict__ partial,
                                                            const DistDev *__restrict__ dd, const unsigned long long *__restrict__ epoch,
                                                            unsigned *__restrict__ ticket)
@@ -1937,63 +1946,64 @@ __global__ __launch_bounds__(kBlock) void k_sr_update_push(int64_t n, double *__
         return;
     }
     if (done) return;
-    const double alpha = sc->alpha, beta = sc->beta;
+    typedef typename Pair<T>::type v2_t;
+    const T alpha = (T)sc->alpha, beta = (T)sc->beta;
     __shared__ double red[4];
-    double ru = 0., rr = 0.;
+    T ru = 0, rr = 0;
     int64_t i = lo + 2 * (int64_t)threadIdx.x;
     for (; i + 1 < hi; i += 2 * kBlock) { // (lo is a multiple of kBlock: i is even, the 16-B accesses are aligned)
-        const d2_t pv = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(p + i));
-        const d2_t wv = *reinterpret_cast<const d2_t *>(w + i), sv = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(s + i));
-        const d2_t xv = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(x + i)), rv = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(r + i));
-        double id0, id1;
+        const v2_t pv = stream_load_k<KEEP>(reinterpret_cast<const v2_t *>(p + i));
+        const v2_t wv = *reinterpret_cast<const v2_t *>(w + i), sv = stream_load_k<KEEP>(reinterpret_cast<const v2_t *>(s + i));
+        const v2_t xv = stream_load_k<KEEP>(reinterpret_cast<const v2_t *>(x + i)), rv = stream_load_k<KEEP>(reinterpret_cast<const v2_t *>(r + i));
+        T id0, id1;
         if (CODED) {
             const unsigned cc = stream_load_k<KEEP>(reinterpret_cast<const unsigned *>(dcode + i));
             id0 = invd[cc & 0xffffu];
             id1 = invd[cc >> 16];
         } else {
-            const d2_t iv = *reinterpret_cast<const d2_t *>(invd + i);
+            const v2_t iv = *reinterpret_cast<const v2_t *>(invd + i);
             id0 = iv.x;
             id1 = iv.y;
         }
         // u is not read: what memory holds is inv(d) * r of the r just loaded (this kernel, or the set-up round, wrote exactly that product)
-        d2_t uv;
+        v2_t uv;
         uv.x = id0 * rv.x;
         uv.y = id1 * rv.y;
-        d2_t pn, sn, xn, rn, un;
+        v2_t pn, sn, xn, rn, un;
         pn.x = uv.x + beta * pv.x;  pn.y = uv.y + beta * pv.y;
         sn.x = wv.x + beta * sv.x;  sn.y = wv.y + beta * sv.y;
         xn.x = xv.x + alpha * pn.x; xn.y = xv.y + alpha * pn.y;
         rn.x = rv.x - alpha * sn.x; rn.y = rv.y - alpha * sn.y;
         un.x = id0 * rn.x;          un.y = id1 * rn.y;
-        stream_store_k<KEEP>(pn, reinterpret_cast<d2_t *>(p + i));
-        stream_store_k<KEEP>(sn, reinterpret_cast<d2_t *>(s + i));
-        stream_store_k<KEEP>(xn, reinterpret_cast<d2_t *>(x + i));
-        stream_store_k<KEEP>(rn, reinterpret_cast<d2_t *>(r + i));
-        *reinterpret_cast<d2_t *>(u + i) = un;
+        stream_store_k<KEEP>(pn, reinterpret_cast<v2_t *>(p + i));
+        stream_store_k<KEEP>(sn, reinterpret_cast<v2_t *>(s + i));
+        stream_store_k<KEEP>(xn, reinterpret_cast<v2_t *>(x + i));
+        stream_store_k<KEEP>(rn, reinterpret_cast<v2_t *>(r + i));
+        *reinterpret_cast<v2_t *>(u + i) = un;
         ru += rn.x * un.x;
         rr += rn.x * rn.x;
         ru += rn.y * un.y;
         rr += rn.y * rn.y;
     }
     if (i < hi) { // odd tail of the last range
-        const double idi = CODED ? invd[dcode[i]] : invd[i];
-        const double pi = idi * r[i] + beta * p[i]; // (u[i] == inv(d) r[i], see above)
-        const double si = w[i] + beta * s[i];
+        const T idi = CODED ? invd[dcode[i]] : invd[i];
+        const T pi = idi * r[i] + beta * p[i]; // (u[i] == inv(d) r[i], see above)
+        const T si = w[i] + beta * s[i];
         p[i] = pi;
         s[i] = si;
         x[i] += alpha * pi;
-        const double ri = r[i] - alpha * si;
+        const T ri = r[i] - alpha * si;
         r[i] = ri;
-        const double ui = idi * ri;
+        const T ui = idi * ri;
         u[i] = ui;
         ru += ri * ui;
         rr += ri * ri;
     }
-    ru = block_sum(ru, red); // (barriers inside: every u of this range is written before the push below reads it)
-    rr = block_sum(rr, red);
+    const double sru = block_sum((double)ru, red); // (barriers inside: every u of this range is written before the push below reads it)
+    const double srr = block_sum((double)rr, red);
     if (threadIdx.x == 0) {
-        partial[blockIdx.x] = ru;
-        partial[gridDim.x + blockIdx.x] = rr;
+        partial[blockIdx.x] = sru;
+        partial[gridDim.x + blockIdx.x] = srr;
     }
     const int np = dd->npeers, G = (int)gridDim.x, b = (int)blockIdx.x;
     const int paranoid = dd->paranoid;
@@ -2004,7 +2014,7 @@ __global__ __launch_bounds__(kBlock) void k_sr_update_push(int64_t n, double *__
         double *dst = dd->peer_halo_dst[i] - dd->send_off[i];
         unsigned long long cs = 0ull;
         for (int j = a + (int)threadIdx.x; j < e; j += kBlock) {
-            const double v = u[dd->send_idx[j]];
+            const double v = (double)u[dd->send_idx[j]];
             if (!(inject && j == 0)) __hip_atomic_store(dst + j, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             cs += (unsigned long long)__double_as_longlong(v);
         }
@@ -2085,8 +2095,10 @@ __global__ __launch_bounds__(512) void k_halo_finalize(HaloView hv)
 }
 // ... and in FRONT of it: wait for the peers' entries of this round (their epoch flags), then copy the comm block's halo area behind the
 // owned entries of the vector the product reads (system-scope loads: the entries were written by other GPUs), so that the brick kernel
-// itself is the plain one -- [owned | halo] is one array, as with the RCCL transport.
-__global__ __launch_bounds__(256) void k_halo_gather(HaloView hv, double *__restrict__ vec)
+// itself is the plain one -- [owned | halo] is one array, as with the RCCL transport.  T = float: the entries (floats widened by the
+// sender) are narrowed back, exactly.
+template <typename T>
+__global__ __launch_bounds__(256) void k_halo_gather(HaloView hv, T *__restrict__ vec)
 {
     if (hv.sc->done) return;
     halo_wait(hv);
@@ -2094,7 +2106,7 @@ __global__ __launch_bounds__(256) void k_halo_gather(HaloView hv, double *__rest
     int n_halo = 0;
     for (int i = 0; i < dd->npeers; ++i) n_halo += dd->recv_cnt[i];
     const long long n_own = dd->n_own;
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < n_halo; j += gridDim.x * 256) vec[n_own + j] = ld_sys_f64(dd->my_halo + j);
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < n_halo; j += gridDim.x * 256) vec[n_own + j] = (T)ld_sys_f64(dd->my_halo + j);
 }
 
 #include "avs_pcg_resident.inl"
@@ -2197,7 +2209,7 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
         if (brick) { // halo into the vector's tail, the plain persistent grid (partials into the stage slots), the finalizer: three launches
             if (da.npeers > 0) {
                 const int hg = n_halo_cols > 0 ? (n_halo_cols + 255) / 256 : 1;
-                hipLaunchKernelGGL(k_halo_gather, dim3(hg < 64 ? hg : 64), dim3(256), 0, stream, hv, const_cast<double *>(vec));
+                hipLaunchKernelGGL(k_halo_gather<double>, dim3(hg < 64 ? hg : 64), dim3(256), 0, stream, hv, const_cast<double *>(vec));
             }
             AVS_TRY(spmv_brick_launch(*A.brick, vec, wv, w->stage2.p, &sc->done, stream));
             hipLaunchKernelGGL(k_halo_finalize, dim3(nfin), dim3(512), 0, stream, hv);
@@ -2312,6 +2324,7 @@ avs_status pcg_create(PcgWork **out, int64_t n, int64_t n_ext, hipStream_t)
 }
 
 int64_t pcg_rows(const PcgWork *w) { return w ? w->n : -1; }
+int pcg_float_vectors(const PcgWork *w) { return w ? w->float_vectors : 0; }
 void pcg_fused_state(const PcgWork *w, int *used, int *faults)
 {
     if (used) *used = w ? w->fused_used : 0;
@@ -2395,6 +2408,7 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
 }
 
 #include "avs_pcg_f32.inl"
+#include "avs_pcg_dist_f32.inl"
 
 // (KEEP is a template parameter of the vector kernels: see stream_load_k)
 #define AVS_VEC_LAUNCH(KERNEL, C, F, ...)                                                                             \
@@ -2407,9 +2421,16 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
 {
     const int64_t n = A.n;
     AVS_REQUIRE(w && w->n == n, AVS_EINVAL, "pcg workspace does not match the system size");
+    w->float_vectors = 0; // (the float loops set it)
     if (dist) {
         DirectArgs da;
-        if (dist_direct_args(dist, &da)) return pcg_solve_direct(w, A, b, x, tol, max_iters, stream, info, da);
+        const bool direct = dist_direct_args(dist, &da);
+        // AVS_OPTION_DIST_F32_VECTORS: the single-reduction loops on float vectors; AVS_DIST_CG=standard and paranoid mode stay fp64
+        const bool paranoid = direct ? da.paranoid : cur_opt().paranoid != 0;
+        if (A.f32_vectors > 0 && !cur_opt().dist_standard_cg && !paranoid)
+            return direct ? pcg_solve_direct_f32(w, A, b, x, tol, max_iters, stream, info, da)
+                          : pcg_solve_sr_f32(w, A, b, x, tol, max_iters, stream, info, dist);
+        if (direct) return pcg_solve_direct(w, A, b, x, tol, max_iters, stream, info, da);
     }
     if (dist && dist_wants_single_reduction(dist))
         return pcg_solve_single_reduction(w, A, b, x, tol, max_iters, stream, info, dist);

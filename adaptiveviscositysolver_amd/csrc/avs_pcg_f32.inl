@@ -326,6 +326,7 @@ static avs_status pcg_solve_f32(PcgWork *w, const CsrView &A, const double *b, d
 {
     const int64_t n = A.n;
     const size_t na = (size_t)n + 8;
+    w->float_vectors = 1;
     if (!w->f_x.p) {
         AVS_TRY(w->f_x.alloc(na)); AVS_TRY(w->f_r.alloc(na)); AVS_TRY(w->f_p.alloc(na)); AVS_TRY(w->f_t.alloc(na)); AVS_TRY(w->f_b.alloc(na));
     }

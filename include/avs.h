@@ -96,7 +96,9 @@ typedef struct {
      * x0 are then float VALUES in the same fp64 arrays.  Single-GPU solves can iterate on FLOAT vectors with float scalars, as Eigen's
      * float CG does (round 5; dot products: a thread's terms in float, everything across threads in double -- Eigen's vectorised
      * reduction order is not reproduced): AVS_OPTION_F32_VECTORS = 1 always, -1 (default) for systems the CU-resident loop does not
-     * take; partitioned solves and the other cases iterate in fp64 on the float system (at least as accurate, same stopping rule).
+     * take.  Partitioned solves (avs_dist_solve) iterate on float vectors in their single-reduction loops with
+     * AVS_OPTION_DIST_F32_VECTORS = 1, over both transports; by default, and always with AVS_DIST_CG=standard, in paranoid mode and
+     * in the CU-resident loop between ranks, they iterate in fp64 on the float system (at least as accurate, same stopping rule).
      * The solution is a float vector either way (Eigen::VectorXf). */
     int32_t precision;
 } avs_desc;
@@ -205,12 +207,18 @@ typedef enum {
                                    * (the bandwidth of the vectors is what an iteration costs there), the resident fp64 loop where it fits the
                                    * chip (faster).  Takes effect at the next avs_assemble (the brick form's walk is laid out for the kernel
                                    * that will run). */
-    AVS_OPTION_FUSED_VECTOR_UPDATE = 9  /* single-GPU launch-per-phase loop: r -= alpha t and x += alpha p ; p = z + beta p as ONE launch with a grid barrier
+    AVS_OPTION_FUSED_VECTOR_UPDATE = 9, /* single-GPU launch-per-phase loop: r -= alpha t and x += alpha p ; p = z + beta p as ONE launch with a grid barrier
                                    * in between -- the new r stays in registers / LDS, 7.25 n instead of 8.5 n doubles per iteration; same sums in the
                                    * same order: iteration counts and solution bits do not depend on it.  0 never, 1 wherever a system qualifies
                                    * (>= 524,288 and <= 8,388,608 rows, a device with >= 256 CUs), -1 only systems larger than the Infinity Cache.
                                    * A barrier that is not passed within AVS_PCG_FUSED_TIMEOUT_MS (2000; the GPU shared with other work) redoes
                                    * the solve with the two launches.  Environment: AVS_PCG_FUSE_VECTORS. */
+    AVS_OPTION_DIST_F32_VECTORS = 10 /* AVS_PRECISION_F32 contexts, partitioned solves (avs_dist_solve): 1 = the single-reduction loops of both
+                                   * transports iterate on float vectors with float scalars, as the single-GPU AVS_OPTION_F32_VECTORS = 1 does (the
+                                   * CU-resident loop between ranks is then skipped); 0 (default) = fp64 iteration on the float system.  AVS_DIST_CG=standard
+                                   * and paranoid mode keep their fp64 loops.  No effect on AVS_PRECISION_F64 contexts.  Takes effect at the next
+                                   * avs_dist_partition / avs_dist_assemble (the local brick form's walk is laid out for the kernel that will run).
+                                   * Environment: AVS_DIST_F32_VECTORS. */
 } avs_solver_option;
 enum { AVS_USE_TRANSPORT_AUTO = 0, AVS_USE_TRANSPORT_RCCL = 1, AVS_USE_TRANSPORT_DIRECT = 2 };
 enum { AVS_BRICK_AUTO = -1, AVS_BRICK_NEVER = 0, AVS_BRICK_ALWAYS = 1, AVS_BRICK_TUNE = 2 };
@@ -248,6 +256,8 @@ typedef struct avs_matrix_format {
                                  * into a per-tile value table (round 5) */
     int32_t fused_vector_update; /* 1 = the last avs_solve ran the two vector kernels of an iteration as one launch (AVS_OPTION_FUSED_VECTOR_UPDATE, round 6) */
     int32_t fused_vector_faults; /* launches of it on this context whose grid barrier timed out (the solve was redone with the two launches) */
+    int32_t float_vectors;      /* 1 = the last avs_solve or avs_dist_solve on this context iterated on float vectors (AVS_OPTION_F32_VECTORS,
+                                 * AVS_OPTION_DIST_F32_VECTORS) */
 } avs_matrix_format;
 avs_status avs_get_matrix_format(avs_ctx *ctx, avs_matrix_format *fmt);
 avs_status avs_get_solution(avs_ctx *ctx, double *x, int64_t n, avs_memspace where);
