@@ -177,6 +177,48 @@ __global__ __launch_bounds__(256) void k_unpack_narrow(const double *__restrict_
     if (i < n) out[i] = (float)in[i];
 }
 
+// C1 after the pack: the peers' entries (doubles) land at `land` + recv_offs[i] -- through one NCCL group, or copied out of the peers'
+// send buffers between two barriers of the in-process group; `narrow` (nullptr: none) then receives them as floats
+static avs_status halo_transfer(PcgDist *d, double *land, float *narrow, hipStream_t stream)
+{
+    if (d->comm) {
+        AVS_NCCL(ncclGroupStart());
+        for (size_t i = 0; i < d->peers.size(); ++i) {
+            if (d->send_counts[i])
+                AVS_NCCL(ncclSend(d->sendbuf.p + d->send_offs[i], (size_t)d->send_counts[i], ncclDouble, d->peers[i], d->comm_p2p, stream));
+            if (d->recv_counts[i])
+                AVS_NCCL(ncclRecv(land + d->recv_offs[i], (size_t)d->recv_counts[i], ncclDouble, d->peers[i], d->comm_p2p, stream));
+        }
+        AVS_NCCL(ncclGroupEnd());
+    } else { // in-process transport
+        avs_local_group *g = d->group;
+        AVS_REQUIRE(g, AVS_ESTATE, "multi-GPU layer not initialised");
+        AVS_HIP(hipStreamSynchronize(stream)); // my send buffer is packed
+        g->barrier();
+        for (size_t i = 0; i < d->peers.size(); ++i) {
+            if (!d->recv_counts[i]) continue;
+            PcgDist *peer = g->members[(size_t)d->peers[i]];
+            // where does the peer keep what it sends to me?
+            int64_t off = -1;
+            for (size_t j = 0; j < peer->peers.size(); ++j)
+                if (peer->peers[j] == d->rank) off = peer->send_offs[j];
+            AVS_REQUIRE(off >= 0, AVS_EINTERNAL, "peer %d has no send list for rank %d", d->peers[i], d->rank);
+            AVS_HIP(hipMemcpyAsync(land + d->recv_offs[i], peer->sendbuf.p + off, (size_t)d->recv_counts[i] * sizeof(double),
+                                   hipMemcpyDeviceToDevice, stream));
+        }
+    }
+    if (narrow) {
+        if (d->n_halo)
+            hipLaunchKernelGGL(k_unpack_narrow, dim3((unsigned)((d->n_halo + 255) / 256)), dim3(256), 0, stream, (const double *)land, narrow,
+                               d->n_halo);
+        AVS_HIP(hipGetLastError());
+    }
+    if (d->comm) return AVS_OK;
+    AVS_HIP(hipStreamSynchronize(stream));
+    d->group->barrier(); // nobody repacks before everybody has copied
+    return AVS_OK;
+}
+
 // C1: p_ext = [owned | halo]; fills the halo tail from the peers' owned entries
 avs_status dist_halo_exchange(PcgDist *d, double *p_ext, hipStream_t stream)
 {
@@ -184,83 +226,19 @@ avs_status dist_halo_exchange(PcgDist *d, double *p_ext, hipStream_t stream)
     if (d->n_send)
         hipLaunchKernelGGL(k_pack, dim3((unsigned)((d->n_send + 255) / 256)), dim3(256), 0, stream, p_ext, d->send_idx.p,
                            d->sendbuf.p, d->n_send);
-    if (d->comm) {
-        AVS_NCCL(ncclGroupStart());
-        for (size_t i = 0; i < d->peers.size(); ++i) {
-            if (d->send_counts[i])
-                AVS_NCCL(ncclSend(d->sendbuf.p + d->send_offs[i], (size_t)d->send_counts[i], ncclDouble, d->peers[i], d->comm_p2p, stream));
-            if (d->recv_counts[i])
-                AVS_NCCL(ncclRecv(p_ext + d->n_own + d->recv_offs[i], (size_t)d->recv_counts[i], ncclDouble, d->peers[i], d->comm_p2p, stream));
-        }
-        AVS_NCCL(ncclGroupEnd());
-        return AVS_OK;
-    }
-    // in-process transport
-    avs_local_group *g = d->group;
-    AVS_REQUIRE(g, AVS_ESTATE, "multi-GPU layer not initialised");
-    AVS_HIP(hipStreamSynchronize(stream)); // my send buffer is packed
-    g->barrier();
-    for (size_t i = 0; i < d->peers.size(); ++i) {
-        if (!d->recv_counts[i]) continue;
-        PcgDist *peer = g->members[(size_t)d->peers[i]];
-        // where does the peer keep what it sends to me?
-        int64_t off = -1;
-        for (size_t j = 0; j < peer->peers.size(); ++j)
-            if (peer->peers[j] == d->rank) off = peer->send_offs[j];
-        AVS_REQUIRE(off >= 0, AVS_EINTERNAL, "peer %d has no send list for rank %d", d->peers[i], d->rank);
-        AVS_HIP(hipMemcpyAsync(p_ext + d->n_own + d->recv_offs[i], peer->sendbuf.p + off,
-                               (size_t)d->recv_counts[i] * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    }
-    AVS_HIP(hipStreamSynchronize(stream));
-    g->barrier(); // nobody repacks before everybody has copied
-    return AVS_OK;
+    return halo_transfer(d, p_ext + d->n_own, nullptr, stream);
 }
 
 // the same for a float vector [owned | halo]: the entries travel widened to double through the send buffer (exact: they are floats),
 // land in recvbuf and are narrowed into the tail
-avs_status dist_halo_exchange_f32(PcgDist *d, float *p_ext, hipStream_t stream)
+avs_status dist_halo_exchange(PcgDist *d, float *p_ext, hipStream_t stream)
 {
     if (d->world == 1) return AVS_OK;
     AVS_TRY(d->recvbuf.reserve((size_t)(d->n_halo > 0 ? d->n_halo : 1)));
     if (d->n_send)
         hipLaunchKernelGGL(k_pack_wide<float>, dim3((unsigned)((d->n_send + 255) / 256)), dim3(256), 0, stream, (const float *)p_ext, d->send_idx.p,
                            d->sendbuf.p, d->n_send);
-    if (d->comm) {
-        AVS_NCCL(ncclGroupStart());
-        for (size_t i = 0; i < d->peers.size(); ++i) {
-            if (d->send_counts[i])
-                AVS_NCCL(ncclSend(d->sendbuf.p + d->send_offs[i], (size_t)d->send_counts[i], ncclDouble, d->peers[i], d->comm_p2p, stream));
-            if (d->recv_counts[i])
-                AVS_NCCL(ncclRecv(d->recvbuf.p + d->recv_offs[i], (size_t)d->recv_counts[i], ncclDouble, d->peers[i], d->comm_p2p, stream));
-        }
-        AVS_NCCL(ncclGroupEnd());
-        if (d->n_halo)
-            hipLaunchKernelGGL(k_unpack_narrow, dim3((unsigned)((d->n_halo + 255) / 256)), dim3(256), 0, stream, (const double *)d->recvbuf.p,
-                               p_ext + d->n_own, d->n_halo);
-        AVS_HIP(hipGetLastError());
-        return AVS_OK;
-    }
-    avs_local_group *g = d->group;
-    AVS_REQUIRE(g, AVS_ESTATE, "multi-GPU layer not initialised");
-    AVS_HIP(hipStreamSynchronize(stream)); // my send buffer is packed
-    g->barrier();
-    for (size_t i = 0; i < d->peers.size(); ++i) {
-        if (!d->recv_counts[i]) continue;
-        PcgDist *peer = g->members[(size_t)d->peers[i]];
-        int64_t off = -1;
-        for (size_t j = 0; j < peer->peers.size(); ++j)
-            if (peer->peers[j] == d->rank) off = peer->send_offs[j];
-        AVS_REQUIRE(off >= 0, AVS_EINTERNAL, "peer %d has no send list for rank %d", d->peers[i], d->rank);
-        AVS_HIP(hipMemcpyAsync(d->recvbuf.p + d->recv_offs[i], peer->sendbuf.p + off, (size_t)d->recv_counts[i] * sizeof(double),
-                               hipMemcpyDeviceToDevice, stream));
-    }
-    if (d->n_halo)
-        hipLaunchKernelGGL(k_unpack_narrow, dim3((unsigned)((d->n_halo + 255) / 256)), dim3(256), 0, stream, (const double *)d->recvbuf.p,
-                           p_ext + d->n_own, d->n_halo);
-    AVS_HIP(hipGetLastError());
-    AVS_HIP(hipStreamSynchronize(stream));
-    g->barrier(); // nobody repacks before everybody has copied
-    return AVS_OK;
+    return halo_transfer(d, d->recvbuf.p, p_ext + d->n_own, stream);
 }
 
 bool dist_tile_lists(PcgDist *d, const int32_t **t_int, int *n_int, const int32_t **t_bnd, int *n_bnd)

@@ -113,18 +113,21 @@ __device__ __forceinline__ double wave_sum(double v)
 enum ScalarOp { OP_NONE = 0, OP_INIT = 1, OP_RHO0 = 2, OP_ALPHA = 3, OP_BETA = 4, OP_SR_INIT = 5, OP_SR_STEP = 6, OP_ALPHA_ODD = 7,
                 OP_SR_INIT_F32 = 8, OP_SR_STEP_F32 = 9 };
 
-// The Chronopoulos-Gear step of the float-vector loops (avs_pcg_dist_f32.inl): the all-reduced double sums red = [r.u, r.r, w.u] rounded
-// to float, the scalars computed in float -- what Eigen's float CG holds -- and kept as doubles holding floats.  One function for the
-// finalizer, k_scalar and the step folded into k_sr_update_f32: every place computes the same bits.
-__device__ inline void sr_step_f32(const PcgScalars *in, double &rr, double &rho, double &alpha, double &beta, int &iter, int &done)
+// The Chronopoulos-Gear step of the single-reduction loops on the all-reduced sums red = [r.u, r.r, w.u], computed in the scalar type S:
+// double, or float for the float-vector loops (the sums rounded to float, the scalars computed in float -- what Eigen's float CG holds --
+// and kept as doubles holding floats).  The step folded into k_sr_update and OP_SR_STEP_F32 (finalizer, k_scalar) share it: every place
+// computes the same bits.  OP_SR_STEP below is the same arithmetic written out on *sc (through sr_step<double> the compiler lays out
+// every kernel that inlines apply_scalar_op differently).
+template <typename S>
+__device__ inline void sr_step(const PcgScalars *in, double &rr, double &rho, double &alpha, double &beta, int &iter, int &done)
 {
     if (done) return;
-    const float rrf = (float)in->red[1];
-    rr = (double)rrf;
-    if (rrf < (float)in->threshold) { done = 1; return; } // x is already updated: plain "converged"
-    const float gamma = (float)in->red[0], delta = (float)in->red[2];
-    const float b2 = gamma / (float)rho;
-    const float a = gamma / (delta - b2 * gamma / (float)alpha);
+    const S rrs = (S)in->red[1];
+    rr = (double)rrs;
+    if (rrs < (S)in->threshold) { done = 1; return; } // x is already updated: plain "converged"
+    const S gamma = (S)in->red[0], delta = (S)in->red[2];
+    const S b2 = gamma / (S)rho;
+    const S a = gamma / (delta - b2 * gamma / (S)alpha);
     alpha = (double)a;
     beta = (double)b2;
     rho = (double)gamma;
@@ -216,7 +219,7 @@ __device__ inline void apply_scalar_op(PcgScalars *sc, int op, double tol)
     case OP_SR_STEP_F32: {
         double rr = sc->rr, rho = sc->rho, alpha = sc->alpha, beta = sc->beta;
         int iter = sc->iter, done = sc->done;
-        sr_step_f32(sc, rr, rho, alpha, beta, iter, done);
+        sr_step<float>(sc, rr, rho, alpha, beta, iter, done);
         sc->rr = rr; sc->rho = rho; sc->alpha = alpha; sc->beta = beta; sc->iter = iter; sc->done = done;
         break;
     }

@@ -114,7 +114,8 @@ struct Options {
                                  // CU-resident loop (there the vectors' bandwidth is what an iteration costs; a system that fits the chip is
                                  // solved faster by the resident fp64 loop: 128^3 beam 54 k against 29 k it/s)
     int dist_f32_vectors = 0;    // AVS_DIST_F32_VECTORS: AVS_PRECISION_F32 contexts' partitioned single-reduction loops iterate on float vectors
-                                 // (avs_pcg_dist_f32.inl); latched by the next avs_dist_partition / avs_dist_assemble (PcgDist::f32)
+                                 // (pcg_solve_single_reduction<float>, pcg_solve_direct<float>); latched by the next avs_dist_partition /
+                                 // avs_dist_assemble (PcgDist::f32)
     // CU-resident loop: tuning and test switches
     int resident_cus = 0, resident_equal_lanes = 0, resident_max_global = 3, resident_max_quads = 0, resident_no_stream = 0;
     long long resident_remap_chunk = 0;
@@ -586,7 +587,7 @@ avs_status pcg_create(PcgWork **w, int64_t n, int64_t n_ext, hipStream_t stream)
 void pcg_destroy(PcgWork *w);
 int64_t pcg_rows(const PcgWork *w); // rows the workspace was sized for (-1: none)
 void pcg_fused_state(const PcgWork *w, int *used, int *faults); // k_update_fused: the last solve ran it / launches whose barrier timed out
-int pcg_float_vectors(const PcgWork *w); // 1 = the last solve iterated on float vectors (avs_pcg_f32.inl, avs_pcg_dist_f32.inl)
+int pcg_float_vectors(const PcgWork *w); // 1 = the last solve iterated on float vectors (avs_pcg_f32.inl, the partitioned <float> loops)
 
 // Jacobi-PCG in Eigen's operation order; x holds the initial guess, returns the solution.
 // Optional halo hook (multi-GPU) is wired by avs_dist.hip through PcgDist.
@@ -690,7 +691,7 @@ avs_status crop_lattice_f32(const float *src, int rx, int ry, int rz, float *dst
 
 // multi-GPU hooks called from pcg_solve (implemented in avs_dist.hip)
 avs_status dist_halo_exchange(PcgDist *d, double *p_ext, hipStream_t stream);
-avs_status dist_halo_exchange_f32(PcgDist *d, float *p_ext, hipStream_t stream); // the same for a float vector (entries travel widened)
+avs_status dist_halo_exchange(PcgDist *d, float *p_ext, hipStream_t stream); // the same for a float vector (entries travel widened)
 avs_status dist_allreduce(PcgDist *d, double *dev_scalars, int count, hipStream_t stream);
 void dist_release(struct ::avs_ctx *c);
 bool dist_wants_single_reduction(PcgDist *d);

@@ -60,7 +60,7 @@ struct PcgWork {
     DevBuf<uint16_t> dcode;  // value-indexed matrix: code of every row's diagonal entry ...
     DevBuf<double> invtab;   // ... into the table of inverted values (2 B instead of 8 B per row and vector pass)
     DevBuf<float> f_x, f_r, f_p, f_t, f_b, f_invd, f_invtab; // float-vector loop of AVS_PRECISION_F32 contexts (avs_pcg_f32.inl)
-    DevBuf<float> f_s, f_u;  // ... and s, u [owned | halo] of its partitioned single-reduction loops (avs_pcg_dist_f32.inl)
+    DevBuf<float> f_s, f_u;  // ... and s, u [owned | halo] of the partitioned single-reduction loops on float vectors
     int float_vectors = 0;   // the last solve iterated on float vectors
     DevBuf<double> x_save;   // the initial guess while the CU-resident loop runs (restored if it faults)
     DevBuf<double> cancel_word; // partitioned solves: [0] this rank's avs_cancel request as the kernels / the all-reduce see it (0. / 1.)
@@ -1511,6 +1511,21 @@ static void reduce_launch(PcgWork *w, const double *partial, int nb, int nred, P
         hipLaunchKernelGGL(k_reduce, dim3(1), dim3(kRedBlock), 0, stream, partial, nb, nred, sc, op, tol, skip_if_done, red_off);
 }
 
+static avs_status reduce_stage(PcgWork *w, int nb, int nred, int op, double tol, int skip_if_done,
+                               hipStream_t stream, PcgDist *dist)
+{
+    if (!dist) {
+        reduce_launch(w, w->partial.p, nb, nred, w->sc.p, op, tol, skip_if_done, 0, stream);
+    } else {
+        // local sums -> RCCL all-reduce of sc->red[0..nred) -> scalar update
+        reduce_launch(w, w->partial.p, nb, nred, w->sc.p, (int)OP_NONE, tol, 0, 0, stream);
+        AVS_TRY(dist_allreduce(dist, reinterpret_cast<double *>(reinterpret_cast<char *>(w->sc.p) + offsetof(PcgScalars, red)), nred, stream));
+        hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, w->sc.p, op, tol);
+    }
+    AVS_HIP(hipGetLastError());
+    return AVS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Host side shared by the solve loops.  Every chunked loop has the same shape:
 //   for (;;) { poll_scalars; sample_spmv; done / max_iters / cancel -> break; enqueue_chunk; }   then finish_info
@@ -1674,6 +1689,8 @@ static avs_status finish_info(PcgWork *w, const CsrView &A, hipStream_t stream, 
 }
 
 
+#include "avs_pcg_f32.inl"
+
 // ---------------------------------------------------------------------------------------------
 // Single-reduction PCG (Chronopoulos & Gear 1989) -- used when the solve is partitioned over several
 // GPUs: the same Krylov iterates in exact arithmetic, but gamma = r.u, delta = w.u and |r|^2 are
@@ -1681,135 +1698,217 @@ static avs_status finish_info(PcgWork *w, const CsrView &A, hipStream_t stream, 
 // instead of two all-reduces + one exchange.  Costs one more vector (s = A p by recurrence): 12 n
 // doubles of vector traffic instead of 10 n -- irrelevant once the solve is latency-bound.
 //   u = M^-1 r ; w = A u ; p = u + beta p ; s = w + beta s ; x += alpha p ; r -= alpha s
+// T, the vector type: double, or float for partitioned AVS_PRECISION_F32 solves (AVS_OPTION_DIST_F32_VECTORS = 1), which get the
+// arithmetic of the single-GPU float loop (avs_pcg_f32.inl) over both transports:
+//   * x, r, p, s, w, u [owned | halo] and the inverse diagonal are float arrays;
+//   * sums: a thread's own terms in T, everything across threads and workgroups in double, across ranks in double in rank order
+//     (the finalizer of the direct transport / the all-reduce) -- every rank computes bit-identical scalars;
+//   * the scalar step (OP_SR_INIT_F32, OP_SR_STEP_F32, sr_step<float>) rounds the all-reduced sums to float and computes alpha, beta
+//     and the threshold in float;
+//   * the SpMV is the single-GPU float loop's (spmv_f32_dispatch);
+//   * halo entries travel as doubles (widened floats: exact) -- the direct transport's comm block, 8-B slots, self-test and checksums,
+//     and the RCCL / in-process exchange's buffers stay as they are.
+// What stays fp64: AVS_DIST_CG=standard, paranoid mode and the CU-resident loop between ranks.
+// CODED (float vectors only): the rows' 2-B diagonal codes and the table of inverted values instead of one inverse per row.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_sr_init(int64_t n, const double *__restrict__ b, const double *__restrict__ t,
-                                                    const double *__restrict__ invd, double *__restrict__ r,
-                                                    double *__restrict__ u, double *__restrict__ partial)
+// r = b - t, u = M^-1 r ; partials [0..g) b.b, [g..2g) r.u, [2g..3g) r.r
+template <typename T, bool CODED>
+__global__ __launch_bounds__(kBlock) void k_sr_init(int64_t n, const double *__restrict__ b, const T *__restrict__ t,
+                                                    const T *__restrict__ invd, const uint16_t *__restrict__ dcode, T *__restrict__ r,
+                                                    T *__restrict__ u, double *__restrict__ partial)
 {
     __shared__ double red[4];
-    double bb = 0., ru = 0., rr = 0.;
+    T bb = 0, ru = 0, rr = 0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const double bi = b[i];
-        const double ri = bi - t[i];
-        const double ui = invd[i] * ri;
+        const T bi = (T)b[i]; // (float: b holds float values)
+        const T ri = bi - t[i];
+        const T ui = (CODED ? invd[dcode[i]] : invd[i]) * ri;
         r[i] = ri;
         u[i] = ui;
         bb += bi * bi;
         ru += ri * ui;
         rr += ri * ri;
     }
-    bb = block_sum(bb, red);
-    ru = block_sum(ru, red);
-    rr = block_sum(rr, red);
+    const double sb = block_sum((double)bb, red);
+    const double su = block_sum((double)ru, red);
+    const double sr = block_sum((double)rr, red);
     if (threadIdx.x == 0) {
-        partial[blockIdx.x] = bb;
-        partial[gridDim.x + blockIdx.x] = ru;
-        partial[2 * gridDim.x + blockIdx.x] = rr;
+        partial[blockIdx.x] = sb;
+        partial[gridDim.x + blockIdx.x] = su;
+        partial[2 * gridDim.x + blockIdx.x] = sr;
     }
 }
 
-// The scalar step of the previous iteration (OP_SR_STEP on the all-reduced sums) is folded into the start of this
+// The scalar step of the previous iteration (OP_SR_STEP / OP_SR_STEP_F32 on the all-reduced sums) is folded into the start of this
 // kernel when `step` is set: every workgroup computes the same new scalars from state `in`, workgroup 0 stores them as
 // state `out` (a different PcgScalars: nobody reads what is being written) -- one launch less per iteration of a loop
 // that is launch-bound at 8 GPUs.  in == out and step == 0: scalars are used as they are.
-__global__ __launch_bounds__(kBlock) void k_sr_update(int64_t n, double *__restrict__ x, double *__restrict__ r,
-                                                      double *__restrict__ p, double *__restrict__ s,
-                                                      double *__restrict__ u, const double *__restrict__ w,
-                                                      const double *__restrict__ invd, const PcgScalars *in, PcgScalars *out,
-                                                      int step, double *__restrict__ partial)
+//   p = u + beta p, s = w + beta s, x += alpha p, r -= alpha s, u = M^-1 r ; partials r.u, r.r
+template <typename T, bool CODED>
+__global__ __launch_bounds__(kBlock) void k_sr_update(int64_t n, T *__restrict__ x, T *__restrict__ r, T *__restrict__ p,
+                                                      T *__restrict__ s, T *__restrict__ u, const T *__restrict__ w,
+                                                      const T *__restrict__ invd, const uint16_t *__restrict__ dcode,
+                                                      const PcgScalars *in, PcgScalars *out, int step, double *__restrict__ partial)
 {
     int done = in->done;
     double alpha = in->alpha, beta = in->beta;
     if (step) {
         double rr = in->rr, rho = in->rho;
         int iter = in->iter;
-        if (!done) { // OP_SR_STEP, red = [r.u, r.r, w.u]
-            rr = in->red[1];
-            if (in->red[1] < in->threshold) done = 1;
-            else {
-                const double gamma = in->red[0], delta = in->red[2];
-                const double b2 = gamma / rho;
-                alpha = gamma / (delta - b2 * gamma / alpha);
-                beta = b2;
-                rho = gamma;
-                iter += 1;
-            }
-        }
+        sr_step<T>(in, rr, rho, alpha, beta, iter, done);
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             PcgScalars o = *in;
             o.rr = rr; o.rho = rho; o.alpha = alpha; o.beta = beta; o.iter = iter; o.done = done;
             *out = o;
         }
     }
-    if (done == 3) {
-        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) x[i] = 0.;
-        return;
-    }
-    if (done) return;
+    if (done) return; // (rhs == 0, done == 3: the host zeroes x)
+    const T a = (T)alpha, bt = (T)beta;
     __shared__ double red[4];
-    double ru = 0., rr = 0.;
+    T ru = 0, rr = 0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const double pi = u[i] + beta * p[i];
-        const double si = w[i] + beta * s[i];
+        const T pi = u[i] + bt * p[i];
+        const T si = w[i] + bt * s[i];
         p[i] = pi;
         s[i] = si;
-        x[i] += alpha * pi;
-        const double ri = r[i] - alpha * si;
+        x[i] += a * pi;
+        const T ri = r[i] - a * si;
         r[i] = ri;
-        const double ui = invd[i] * ri;
+        const T ui = (CODED ? invd[dcode[i]] : invd[i]) * ri;
         u[i] = ui;
         ru += ri * ui;
         rr += ri * ri;
     }
-    ru = block_sum(ru, red);
-    rr = block_sum(rr, red);
+    const double su = block_sum((double)ru, red);
+    const double sr = block_sum((double)rr, red);
     if (threadIdx.x == 0) {
-        partial[blockIdx.x] = ru;
-        partial[gridDim.x + blockIdx.x] = rr;
+        partial[blockIdx.x] = su;
+        partial[gridDim.x + blockIdx.x] = sr;
     }
 }
 
-// Set-up of the single-reduction loops: r = b - A x (x staged through u for the halo), u = M^-1 r, w = A u, and the sums |b|^2, r.u,
-// |r|^2, w.u -> OP_SR_INIT in sc[0] (sc[1] zeroed).  dist == nullptr: one GPU, no exchange and no all-reduce.
-static avs_status sr_setup(PcgWork *w, const CsrView &A, const double *b, const double *x, double tol, bool coded, PcgDist *dist,
-                           hipStream_t stream)
+// k_sr_init / k_sr_update with (CODED) or without the diagonal codes; only the float loops read codes here (KERNEL<T, F32> keeps
+// KERNEL<double, true> from being instantiated)
+#define AVS_SR_LAUNCH(KERNEL, CODED, ...)                                                                       \
+    do {                                                                                                        \
+        if (CODED) hipLaunchKernelGGL((KERNEL<T, F32>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);         \
+        else hipLaunchKernelGGL((KERNEL<T, false>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);             \
+    } while (0)
+
+// The vectors of a single-reduction loop: fp64 -- the workspace's own (x: the caller's), float -- the f_* arrays (x narrowed)
+template <typename T> struct SrVecs {
+    T *x, *r, *p, *s, *w, *u;  // w = A u; u [owned | halo]
+    const T *invd;             // one inverse per row (float and coded: nullptr)
+    const T *invtab;           // coded: the table of inverted values, indexed by dcode (else nullptr)
+    const uint16_t *dcode;
+};
+
+// the SpMV of the set-up and of the RCCL loop: the fp64 dispatcher, or the float loop's
+template <bool DOT>
+static avs_status sr_spmv(const CsrView &A, const double *x, double *y, double *partial, const PcgScalars *sc, int variant,
+                          hipStream_t stream, int *nb)
 {
+    return spmv_dispatch<DOT>(A, x, y, partial, sc, variant, stream, nb);
+}
+template <bool DOT>
+static avs_status sr_spmv(const CsrView &A, const float *x, float *y, double *partial, const PcgScalars *sc, int, hipStream_t stream, int *nb)
+{
+    return spmv_f32_dispatch<DOT>(A, x, y, partial, sc, stream, nb);
+}
+
+// Set-up of the single-reduction loops: the vectors, zeroed recurrences, both scalar states and the diagonal (a `coded` matrix also
+// gets the rows' codes and the table of inverted values), then r = b - A x (x staged through u for the halo), u = M^-1 r, w = A u.
+// product(k): the transport's exchange of u and w = A u -- k = 0 of x, k = 1 of u, which also folds the sums |b|^2, r.u, |r|^2, w.u
+// (the first 3 * g vector partials) and applies OP_SR_INIT / OP_SR_INIT_F32 in sc[0].  g: the grid of the loop's vector kernels.
+template <typename T, typename F>
+static avs_status sr_setup(PcgWork *w, const CsrView &A, const double *b, double *x, bool coded, int g, SrVecs<T> *v, hipStream_t stream,
+                           F &&product)
+{
+    constexpr bool F32 = std::is_same<T, float>::value;
     const int64_t n = A.n;
-    const int g = vec_grid(n);
-    const int variant = spmv_default_variant(A);
-    AVS_TRY(w->s.alloc((size_t)n));
-    AVS_TRY(w->u.alloc((size_t)w->n_ext));
-    double *wv = w->t.p, *u = w->u.p;
-    double *pvec = w->partial.p, *pspmv = w->partial.p + 4 * (size_t)kVecGrid; // 3 * g vector-kernel partials, the SpMV's behind them
-    PcgScalars *sc = w->sc.p;
-    AVS_HIP(hipMemsetAsync(sc, 0, 2 * sizeof(PcgScalars), stream));
-    AVS_HIP(hipMemsetAsync(w->p.p, 0, (size_t)w->n_ext * sizeof(double), stream));
-    AVS_HIP(hipMemsetAsync(w->s.p, 0, (size_t)n * sizeof(double), stream));
-    AVS_TRY(prepare_diagonal(w, A, coded, w->invd.p, stream));
+    AVS_HIP(hipMemsetAsync(w->sc.p, 0, 2 * sizeof(PcgScalars), stream));
+    if constexpr (F32) { // as pcg_solve_f32 makes them
+        const size_t na = (size_t)n + 8, ne = (size_t)w->n_ext + 8;
+        AVS_TRY(w->f_x.alloc(na)); AVS_TRY(w->f_r.alloc(na)); AVS_TRY(w->f_p.alloc(na)); AVS_TRY(w->f_s.alloc(na)); AVS_TRY(w->f_t.alloc(na));
+        AVS_TRY(w->f_u.alloc(ne));
+        AVS_HIP(hipMemsetAsync(w->f_p.p, 0, na * sizeof(float), stream));
+        AVS_HIP(hipMemsetAsync(w->f_s.p, 0, na * sizeof(float), stream));
+        AVS_TRY(prepare_diagonal(w, A, coded, nullptr, stream));
+        *v = {w->f_x.p, w->f_r.p, w->f_p.p, w->f_s.p, w->f_t.p, w->f_u.p, nullptr, nullptr, nullptr};
+        if (coded) {
+            if (!w->f_invtab.p) AVS_TRY(w->f_invtab.alloc((size_t)kViLdsTable + 1));
+            hipLaunchKernelGGL(k_f32_invtab, dim3((A.table_size + kBlock) / kBlock), dim3(kBlock), 0, stream, A, w->f_invtab.p);
+            v->invtab = w->f_invtab.p;
+        } else {
+            AVS_TRY(w->f_invd.alloc(na));
+            hipLaunchKernelGGL(k_f32_inv_diag, dim3(row_grid(n)), dim3(kBlock), 0, stream, A, w->f_invd.p);
+            v->invd = w->f_invd.p;
+        }
+        w->float_vectors = 1;
+    } else {
+        AVS_TRY(w->s.alloc((size_t)n));
+        AVS_TRY(w->u.alloc((size_t)w->n_ext));
+        AVS_HIP(hipMemsetAsync(w->p.p, 0, (size_t)w->n_ext * sizeof(double), stream));
+        AVS_HIP(hipMemsetAsync(w->s.p, 0, (size_t)n * sizeof(double), stream));
+        AVS_TRY(prepare_diagonal(w, A, coded, w->invd.p, stream));
+        *v = {x, w->r.p, w->p.p, w->s.p, w->t.p, w->u.p, w->invd.p, coded ? w->invtab.p : nullptr, nullptr};
+    }
+    v->dcode = coded ? w->dcode.p : nullptr;
     AVS_HIP(hipEventRecord(w->ev0, stream));
-    AVS_HIP(hipMemcpyAsync(u, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    if (dist) AVS_TRY(dist_halo_exchange(dist, u, stream));
-    AVS_TRY(spmv_dispatch<false>(A, u, wv, nullptr, nullptr, variant, stream, nullptr));
-    hipLaunchKernelGGL(k_sr_init, dim3(g), dim3(kBlock), 0, stream, n, b, wv, w->invd.p, w->r.p, u, pvec);
-    if (dist) AVS_TRY(dist_halo_exchange(dist, u, stream));
-    int nb = 0;
-    AVS_TRY(spmv_dispatch<true>(A, u, wv, pspmv, nullptr, variant, stream, &nb));
-    reduce_launch(w, pvec, g, 3, sc, (int)OP_NONE, tol, 0, 0, stream);
-    reduce_launch(w, pspmv, nb, 1, sc, (int)OP_NONE, tol, 0, 3, stream);
-    if (dist) AVS_TRY(dist_allreduce(dist, sc->red, 4, stream));
-    hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc, (int)OP_SR_INIT, tol);
+    if constexpr (F32) {
+        hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, (const double *)x, v->x);
+        hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, (const double *)x, v->u);
+    } else {
+        AVS_HIP(hipMemcpyAsync(v->u, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    }
+    AVS_TRY(product(0));
+    const bool kc = F32 && coded; // (the fp64 set-up reads the per-row inverse)
+    AVS_SR_LAUNCH(k_sr_init, kc, n, b, (const T *)v->w, kc ? v->invtab : v->invd, v->dcode, v->r, v->u, w->partial.p);
+    AVS_TRY(product(1));
     AVS_HIP(hipGetLastError());
     return AVS_OK;
 }
 
+// sr_setup over the RCCL / in-process exchange; dist == nullptr: one GPU, no exchange and no all-reduce
+template <typename T>
+static avs_status sr_setup_exchange(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, bool coded, PcgDist *dist,
+                                    SrVecs<T> *v, hipStream_t stream)
+{
+    const int g = vec_grid(A.n);
+    const int variant = spmv_default_variant(A);
+    double *pvec = w->partial.p, *pspmv = w->partial.p + 4 * (size_t)kVecGrid; // 3 * g vector-kernel partials, the SpMV's behind them
+    PcgScalars *sc = w->sc.p;
+    return sr_setup(w, A, b, x, coded, g, v, stream, [&](int k) -> avs_status {
+        if (dist) AVS_TRY(dist_halo_exchange(dist, v->u, stream));
+        if (k == 0) return sr_spmv<false>(A, v->u, v->w, nullptr, nullptr, variant, stream, nullptr);
+        int nb = 0;
+        AVS_TRY(sr_spmv<true>(A, v->u, v->w, pspmv, nullptr, variant, stream, &nb));
+        reduce_launch(w, pvec, g, 3, sc, (int)OP_NONE, tol, 0, 0, stream);
+        reduce_launch(w, pspmv, nb, 1, sc, (int)OP_NONE, tol, 0, 3, stream);
+        if (dist) AVS_TRY(dist_allreduce(dist, sc->red, 4, stream));
+        hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc, std::is_same<T, float>::value ? (int)OP_SR_INIT_F32 : (int)OP_SR_INIT, tol);
+        return AVS_OK;
+    });
+}
+
+// Host-mediated transports (RCCL, in-process virtual ranks).  b, x: the rank's fp64 arrays (float vectors: holding float values); x
+// receives the solution.
+template <typename T>
 static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const double *b, double *x, double tol,
                                              int max_iters, hipStream_t stream, avs_solve_info *info, PcgDist *dist)
 {
+    constexpr bool F32 = std::is_same<T, float>::value;
     const int64_t n = A.n;
     const int g = vec_grid(n);
     const int variant = spmv_default_variant(A);
-    AVS_TRY(sr_setup(w, A, b, x, tol, false, dist, stream));
-    double *p = w->p.p, *r = w->r.p, *wv = w->t.p, *sv = w->s.p, *u = w->u.p, *invd = w->invd.p;
+    const bool coded = F32 && A.codes && !A.tab_ptr && A.table_size <= kViLdsTable; // (the fp64 loop reads the per-row inverse)
+    if (F32) { // the float SpMV's partials: one per persistent workgroup of the brick kernel, else one per 256 rows
+        const bool brick = A.brick && A.brick->ntiles > 0 && A.brick->pwords32;
+        const size_t nb_max = brick ? (size_t)brick_partial_count(*A.brick, 4) : (size_t)stream_grid(n);
+        AVS_TRY(ensure_partials(w, 4 * (size_t)kVecGrid + nb_max + 16));
+    }
+    SrVecs<T> v;
+    AVS_TRY(sr_setup_exchange(w, A, b, x, tol, coded, dist, &v, stream));
     double *pvec = w->partial.p;                        // 3 * g vector-kernel partials
     double *pspmv = w->partial.p + 4 * (size_t)kVecGrid; // SpMV partials behind them
     PcgScalars *sc = w->sc.p; // two states, ping-pong: sc[cur] is current, k_sr_update writes sc[cur ^ 1]
@@ -1819,26 +1918,32 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
         // first iteration of a chunk: scalars are final (SR_INIT or the explicit step after the chunk); afterwards the step of
         // the previous iteration rides in k_sr_update, which moves the state to the other slot
         const int step = c > 0 ? 1 : 0;
-        hipLaunchKernelGGL(k_sr_update, dim3(g), dim3(kBlock), 0, stream, n, x, r, p, sv, u, wv, invd, (const PcgScalars *)(sc + cur),
-                           sc + (step ? (cur ^ 1) : cur), step, pvec);
+        AVS_SR_LAUNCH(k_sr_update, coded, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w, coded ? v.invtab : v.invd, v.dcode,
+                      (const PcgScalars *)(sc + cur), sc + (step ? (cur ^ 1) : cur), step, pvec);
         if (step) cur ^= 1;
         const PcgScalars *now = sc + cur;
-        const int32_t *t_int = nullptr, *t_bnd = nullptr;
-        int n_int = 0, n_bnd = 0, nb = 0;
-        if (variant == 24 && !(A.brick && A.brick->ntiles > 0) && dist_tile_lists(dist, &t_int, &n_int, &t_bnd, &n_bnd)) {
-            // overlap: the exchange runs on the communication stream while the tiles that touch no halo
-            // column are multiplied; the halo-touching tiles follow once the halo has landed
-            AVS_TRY(dist_halo_begin(dist, u, stream));
+        int nb = 0;
+        bool overlapped = false;
+        if constexpr (!F32) {
+            const int32_t *t_int = nullptr, *t_bnd = nullptr;
+            int n_int = 0, n_bnd = 0;
+            if (variant == 24 && !(A.brick && A.brick->ntiles > 0) && dist_tile_lists(dist, &t_int, &n_int, &t_bnd, &n_bnd)) {
+                // overlap: the exchange runs on the communication stream while the tiles that touch no halo
+                // column are multiplied; the halo-touching tiles follow once the halo has landed
+                AVS_TRY(dist_halo_begin(dist, v.u, stream));
+                if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
+                AVS_TRY(spmv_dot_tiles(A, v.u, v.w, pspmv, now, t_int, n_int, stream));
+                AVS_TRY(dist_halo_end(dist, stream));
+                AVS_TRY(spmv_dot_tiles(A, v.u, v.w, pspmv + (size_t)n_int * (A.codes ? kTileRows / 64 : 1), now, t_bnd, n_bnd, stream));
+                if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
+                nb = (n_int + n_bnd) * (A.codes ? kTileRows / 64 : 1); // value-indexed kernel: one partial per wave
+                overlapped = true;
+            }
+        }
+        if (!overlapped) {
+            AVS_TRY(dist_halo_exchange(dist, v.u, stream));
             if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
-            AVS_TRY(spmv_dot_tiles(A, u, wv, pspmv, now, t_int, n_int, stream));
-            AVS_TRY(dist_halo_end(dist, stream));
-            AVS_TRY(spmv_dot_tiles(A, u, wv, pspmv + (size_t)n_int * (A.codes ? kTileRows / 64 : 1), now, t_bnd, n_bnd, stream));
-            if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
-            nb = (n_int + n_bnd) * (A.codes ? kTileRows / 64 : 1); // value-indexed kernel: one partial per wave
-        } else {
-            AVS_TRY(dist_halo_exchange(dist, u, stream));
-            if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
-            AVS_TRY(spmv_dispatch<true>(A, u, wv, pspmv, now, variant, stream, &nb));
+            AVS_TRY(sr_spmv<true>(A, v.u, v.w, pspmv, now, variant, stream, &nb));
             if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
         }
         if (nb < 16384) hipLaunchKernelGGL(k_reduce_pair, dim3(1), dim3(kRedBlock), 0, stream, pvec, g, 2, pspmv, nb, 1, sc + cur);
@@ -1863,15 +1968,15 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
         if (stop_h[1] != 0.) { (void)cancel_consume(); cancelled = true; break; }
         AVS_TRY(enqueue_chunk(w, stream, nullptr, max_iters, info != nullptr, enqueue_iteration, &cs)); // (no graph: RCCL calls inside)
         // the last iteration's step, explicitly: the host polls a final state
-        hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc + cur, (int)OP_SR_STEP, tol);
+        hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc + cur, F32 ? (int)OP_SR_STEP_F32 : (int)OP_SR_STEP, tol);
         AVS_HIP(hipGetLastError());
     }
-    if (w->host_sc->done == 3) { // rhs == 0: x := 0
-        hipLaunchKernelGGL(k_sr_update, dim3(g), dim3(kBlock), 0, stream, n, x, r, p, sv, u, wv, invd, (const PcgScalars *)(sc + cur), sc + cur, 0,
-                           pvec);
-    }
-    return finish_info(w, A, stream, info, &cs, cancelled, 0, false);
+    if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(v.x, 0, (size_t)n * sizeof(T), stream)); // rhs == 0: x := 0
+    if constexpr (F32) hipLaunchKernelGGL(k_f32_widen, dim3(g), dim3(kBlock), 0, stream, n, (const float *)v.x, x);
+    AVS_HIP(hipGetLastError());
+    return finish_info(w, A, stream, info, &cs, cancelled, 0, F32);
 }
+#undef AVS_SR_LAUNCH
 
 // ---------------------------------------------------------------------------------------------
 // Direct-transport loop (world >= 1): the single-reduction iteration above with NO RCCL call and no host work inside:
@@ -1923,9 +2028,9 @@ __device__ __forceinline__ void push_raise_flags(const DistDev *dd, const unsign
 // KEEP == false (round 5: the brick-structured form is small enough to stay in the Infinity Cache between two products -- but only
 // if the ~0.5 GB this kernel moves do not push it out): p, s, x, r -- read and written once per iteration, by this kernel only -- are
 // loaded and stored non-temporally; u (the next product's input) and w (the product's output, read here) stay cacheable.
-// T (round 7): the vector type -- double, or float for the float-vector loop of AVS_PRECISION_F32 partitioned solves (avs_pcg_dist_f32.inl:
-// a thread's own sums in float, everything across threads in double; the pushed entries are widened to double, which is exact, so the
-// comm block, its 8-B slots and the checksums stay as they are).  Rows two at a time: 16-B (double) or 8-B (float) accesses.
+// T (round 7): the vector type -- double, or float for the float-vector loop of AVS_PRECISION_F32 partitioned solves (see the
+// single-reduction section: a thread's own sums in float, everything across threads in double; the pushed entries are widened to double,
+// which is exact, so the comm block, its 8-B slots and the checksums stay as they are).  Rows two at a time: 16-B (double) or 8-B (float) accesses.
 template <typename T> struct Pair;
 template <> struct Pair<double> { typedef d2_t type; };
 template <> struct Pair<float> { typedef float type __attribute__((ext_vector_type(2))); };
@@ -2149,45 +2254,63 @@ avs_status direct_selftest(const DirectArgs &da, int rounds, hipStream_t stream,
     return AVS_OK;
 }
 
+// the message of a fault the direct transport's kernels left in the scalar state
+static avs_status direct_fault(const PcgScalars &h)
+{
+    if (h.fault == 4)
+        set_error("direct transport (paranoid mode): a halo segment does not add up to the checksum its sender left ahead of the flag "
+                  "-- stale or torn halo entries (iteration ~%d)", h.iter);
+    else
+        set_error("direct transport: %s did not arrive within the time limit (rank stalled or dead?)",
+                  h.fault == 1 ? "a peer's halo entries" : (h.fault == 2 ? "a peer's partial sums" : "a workgroup's partial sums"));
+    return AVS_ERCCL;
+}
+
+template <typename T>
 static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, int max_iters,
                                    hipStream_t stream, avs_solve_info *info, const DirectArgs &da)
 {
+    constexpr bool F32 = std::is_same<T, float>::value;
     const int64_t n = A.n;
     int g = 1, chunk_rows = kBlock; // every vector kernel of this loop uses the fused kernel's geometry (same partial layout)
     sr_update_geometry((long long)n, &g, &chunk_rows);
     AVS_REQUIRE(g == da.push_grid && chunk_rows == da.push_chunk, AVS_EINTERNAL, "push segments were built for another geometry");
-    AVS_TRY(w->s.alloc((size_t)n));
-    AVS_TRY(w->u.alloc((size_t)w->n_ext));
-    double *p = w->p.p, *r = w->r.p, *wv = w->t.p, *sv = w->s.p, *u = w->u.p, *invd = w->invd.p;
-    double *pvec = w->partial.p;                         // up to 3 * g vector-kernel partials
-    PcgScalars *sc = w->sc.p;
-    const bool brick = A.brick && A.brick->ntiles > 0;   // brick-structured form of the local rows: one partial per persistent workgroup
-    const int ntiles = brick ? brick_partial_count(*A.brick, 8) : da.n_tiles_int + da.n_tiles_bnd;  // (word stream: == ceil(n / kTileRows))
-    const int ppt = brick ? 1 : (A.codes ? kTileRows / 64 : 1); // value-indexed kernel: one partial per wave
+    // one dictionary of few values: the loop's vector kernel reads a 2-B diagonal code
+    const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable;
+    // brick-structured form of the local rows (float vectors: with its float walk): one partial per persistent workgroup
+    const bool brick = A.brick && A.brick->ntiles > 0 && (!F32 || A.brick->pwords32);
+    int ntiles = 0, ppt = 1; // the SpMV's partials: ntiles * ppt stage slots
+    if (F32) ntiles = n <= 0 ? 0 : (brick ? brick_partial_count(*A.brick, 4) : stream_grid(n)); // (k_f32_spmv_csr: one per 256 rows)
+    else {
+        ntiles = brick ? brick_partial_count(*A.brick, 8) : da.n_tiles_int + da.n_tiles_bnd; // (word stream: == ceil(n / kTileRows))
+        ppt = brick ? 1 : (A.codes ? kTileRows / 64 : 1); // value-indexed kernel: one partial per wave
+    }
     const int slots = ntiles * ppt;
     const int nfin = slots > 0 ? (slots + kFinShare - 1) / kFinShare : 1;
     AVS_TRY(w->stage2.alloc((size_t)(slots > 0 ? slots : 1) + (size_t)nfin));
     AVS_HIP(hipMemsetAsync(w->stage2.p, 0xFF, (size_t)(slots > 0 ? slots : 1) * sizeof(double), stream)); // arm: kSentinel in every slot
     const int push_blocks = da.n_send > 0 ? (da.n_send + 255) / 256 : 0;
     const int n_halo_cols = (int)(w->n_ext - n);
-
     AVS_TRY(w->cancel_dev.alloc(1));
     AVS_HIP(hipMemsetAsync(w->cancel_dev.p, 0, sizeof(int), stream));
-    AVS_HIP(hipMemsetAsync(sc, 0, 2 * sizeof(PcgScalars), stream));
-    AVS_HIP(hipMemsetAsync(p, 0, (size_t)w->n_ext * sizeof(double), stream));
-    AVS_HIP(hipMemsetAsync(sv, 0, (size_t)n * sizeof(double), stream));
-    // one dictionary of few values: the loop's vector kernel reads a 2-B diagonal code
-    const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable;
-    AVS_TRY(prepare_diagonal(w, A, coded, invd, stream));
-    AVS_HIP(hipEventRecord(w->ev0, stream));
+    double *pvec = w->partial.p; // up to 3 * g vector-kernel partials
+    PcgScalars *sc = w->sc.p;
+    SrVecs<T> v;
 
-    // one round: exchange `vec`, wv = A vec (+ partials of vec.wv), fold `nred_vec` vector partial arrays + that one, step `op`
-    auto round = [&](const double *vec, int nred_vec, int op, hipEvent_t ea, hipEvent_t eb, bool push = true) -> avs_status {
-        if (push && push_blocks) hipLaunchKernelGGL(k_push, dim3(push_blocks), dim3(256), 0, stream, da.dd, vec, (const unsigned long long *)da.epoch,
-                                            da.push_ticket, (const PcgScalars *)sc);
+    // one round: push `vec` to the peers, v.w = A vec (+ partials of vec.v.w), fold `nred_vec` vector partial arrays + those, step `op`
+    auto round = [&](T *vec, int nred_vec, int op, hipEvent_t ea, hipEvent_t eb, bool push) -> avs_status {
+        if (push && push_blocks) {
+            const double *pv = nullptr;
+            if constexpr (F32) { // k_push reads doubles: vec widened through w->t (the fp64 loop's w, unused here)
+                hipLaunchKernelGGL(k_f32_widen, dim3(g), dim3(kBlock), 0, stream, n, (const float *)vec, w->t.p);
+                pv = w->t.p;
+            } else {
+                pv = vec;
+            }
+            hipLaunchKernelGGL(k_push, dim3(push_blocks), dim3(256), 0, stream, da.dd, pv, (const unsigned long long *)da.epoch, da.push_ticket,
+                               (const PcgScalars *)sc);
+        }
         if (ea) AVS_HIP(hipEventRecord(ea, stream));
-        // ONE launch over all tiles + the finalizer block: tiles that read halo columns (flagged; the last ones of the [interior |
-        // halo-reading] row order) wait for the peers' flags, everything else multiplies while the halo travels
         HaloView hv;
         hv.dd = da.dd;
         hv.epoch = da.epoch;
@@ -2206,56 +2329,62 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
         hv.op = op;
         hv.tol = tol;
         hv.cancel = w->cancel_dev.p;
-        if (brick) { // halo into the vector's tail, the plain persistent grid (partials into the stage slots), the finalizer: three launches
+        if (!F32 && !brick) {
+            // fp64 word stream: ONE launch over all tiles + the finalizer block: tiles that read halo columns (flagged; the last ones of
+            // the [interior | halo-reading] row order) wait for the peers' flags, everything else multiplies while the halo travels
+            if constexpr (!F32) AVS_TRY(spmv_dot_tiles_halo(A, vec, v.w, nullptr, sc, nullptr, ntiles + nfin, hv, stream));
+        } else { // halo into the vector's tail, the SpMV (partials into the stage slots), the finalizer: three launches
             if (da.npeers > 0) {
                 const int hg = n_halo_cols > 0 ? (n_halo_cols + 255) / 256 : 1;
-                hipLaunchKernelGGL(k_halo_gather<double>, dim3(hg < 64 ? hg : 64), dim3(256), 0, stream, hv, const_cast<double *>(vec));
+                hipLaunchKernelGGL(k_halo_gather<T>, dim3(hg < 64 ? hg : 64), dim3(256), 0, stream, hv, vec);
             }
-            AVS_TRY(spmv_brick_launch(*A.brick, vec, wv, w->stage2.p, &sc->done, stream));
+            if constexpr (F32) AVS_TRY(spmv_f32_dispatch<true>(A, vec, v.w, w->stage2.p, sc, stream, nullptr));
+            else AVS_TRY(spmv_brick_launch(*A.brick, vec, v.w, w->stage2.p, &sc->done, stream));
             hipLaunchKernelGGL(k_halo_finalize, dim3(nfin), dim3(512), 0, stream, hv);
-        } else {
-            AVS_TRY(spmv_dot_tiles_halo(A, vec, wv, nullptr, sc, nullptr, ntiles + nfin, hv, stream));
         }
         if (eb) AVS_HIP(hipEventRecord(eb, stream));
+        AVS_HIP(hipGetLastError());
         return AVS_OK;
     };
-    // r = b - A x (x staged through u for the exchange), u = M^-1 r, w = A u
-    AVS_HIP(hipMemcpyAsync(u, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    AVS_TRY(round(u, 0, (int)OP_NONE, nullptr, nullptr));
-    hipLaunchKernelGGL(k_sr_init, dim3(g), dim3(kBlock), 0, stream, n, b, wv, invd, r, u, pvec);
-    AVS_TRY(round(u, 3, (int)OP_SR_INIT, nullptr, nullptr));
-    AVS_HIP(hipGetLastError());
+    AVS_TRY(sr_setup(w, A, b, x, coded, g, &v, stream, [&](int k) -> avs_status {
+        return k == 0 ? round(v.u, 0, (int)OP_NONE, nullptr, nullptr, true)
+                      : round(v.u, 3, F32 ? (int)OP_SR_INIT_F32 : (int)OP_SR_INIT, nullptr, nullptr, true);
+    }));
 
     // Systems that fit on the chip (<= ~1 M rows, packed single-dictionary form): the rest of the solve in ONE cooperative launch,
-    // matrix words in the register files, vector slices in LDS (avs_pcg_resident.inl).  Needs the GPU for itself.
+    // matrix words in the register files, vector slices in LDS (avs_pcg_resident.inl).  Needs the GPU for itself.  fp64 only.
     w->resident_used = 0;
-    if (coded && (da.exclusive_device || cur_opt().resident_cus > 0) && resident_wanted(true)) {
-        if (!w->resident) w->resident = new (std::nothrow) ResidentPlan();
-        if (w->resident && resident_prepare(w->resident, A, w->n_ext, &da, stream)) {
-            bool launched = false;
-            AVS_TRY(resident_run(w->resident, A, x, r, p, sv, u, wv, w->dcode.p, w->invtab.p, sc, max_iters, &da, stream, &launched));
-            w->resident_used = launched ? 1 : 0; // (refused: the loop below takes over from the same state)
+    if constexpr (!F32) {
+        if (coded && (da.exclusive_device || cur_opt().resident_cus > 0) && resident_wanted(true)) {
+            if (!w->resident) w->resident = new (std::nothrow) ResidentPlan();
+            if (w->resident && resident_prepare(w->resident, A, w->n_ext, &da, stream)) {
+                bool launched = false;
+                AVS_TRY(resident_run(w->resident, A, x, v.r, v.p, v.s, v.u, v.w, w->dcode.p, w->invtab.p, sc, max_iters, &da, stream, &launched));
+                w->resident_used = launched ? 1 : 0; // (refused: the loop below takes over from the same state)
+            }
         }
     }
 
     auto enqueue_iteration = [&](int c, bool timed) -> avs_status {
         // update and push in one launch (3 launches per iteration)
         if (coded && brick) // (the brick form serves single-dictionary matrices: coded)
-            hipLaunchKernelGGL((k_sr_update_push<true, false>), dim3(g), dim3(kBlock), 0, stream, n, x, r, p, sv, u, wv, (const double *)w->invtab.p,
-                               (const uint16_t *)w->dcode.p, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch, da.push_ticket);
+            hipLaunchKernelGGL((k_sr_update_push<true, false, T>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
+                               v.invtab, v.dcode, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch, da.push_ticket);
         else if (coded)
-            hipLaunchKernelGGL((k_sr_update_push<true, true>), dim3(g), dim3(kBlock), 0, stream, n, x, r, p, sv, u, wv, (const double *)w->invtab.p,
-                               (const uint16_t *)w->dcode.p, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch, da.push_ticket);
+            hipLaunchKernelGGL((k_sr_update_push<true, true, T>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
+                               v.invtab, v.dcode, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch, da.push_ticket);
         else
-            hipLaunchKernelGGL((k_sr_update_push<false, true>), dim3(g), dim3(kBlock), 0, stream, n, x, r, p, sv, u, wv, (const double *)invd,
-                               (const uint16_t *)nullptr, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch, da.push_ticket);
-        return round(u, 2, (int)OP_SR_STEP, timed ? w->evA[c] : nullptr, timed ? w->evB[c] : nullptr, false);
+            hipLaunchKernelGGL((k_sr_update_push<false, true, T>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
+                               v.invd, (const uint16_t *)nullptr, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch,
+                               da.push_ticket);
+        return round(v.u, 2, F32 ? (int)OP_SR_STEP_F32 : (int)OP_SR_STEP, timed ? w->evA[c] : nullptr, timed ? w->evB[c] : nullptr, false);
     };
-    GraphKey key = matrix_key(kGraphDirect, A, x, tol);
+    GraphKey key = matrix_key(F32 ? kGraphDirectF32 : kGraphDirect, A, v.x, tol);
     key.b = b;
     key.dd = da.dd;
     key.ntiles = ntiles;
     key.brick = brick;
+    key.coded = coded;
     const GraphKey *gkey = cur_opt().graph != 0 ? &key : nullptr;
     ChunkState cs;
     bool cancel_sent = false;
@@ -2263,13 +2392,7 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
         AVS_TRY(poll_scalars(w, sc, stream));
         if (w->host_sc->fault) {
             if (w->resident_used && w->resident) w->resident->ok = false; // the next distributed solve takes the launch-per-phase loop
-            if (w->host_sc->fault == 4)
-                set_error("direct transport (paranoid mode): a halo segment does not add up to the checksum its sender left ahead of the flag "
-                          "-- stale or torn halo entries (iteration ~%d)", w->host_sc->iter);
-            else
-                set_error("direct transport: %s did not arrive within the time limit (rank stalled or dead?)",
-                          w->host_sc->fault == 1 ? "a peer's halo entries" : (w->host_sc->fault == 2 ? "a peer's partial sums" : "a workgroup's partial sums"));
-            return AVS_ERCCL;
+            return direct_fault(*w->host_sc);
         }
         sample_spmv(w, info != nullptr, true, &cs);
         if (w->host_sc->done || cs.enqueued >= max_iters || w->resident_used) break;
@@ -2280,9 +2403,10 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
         }
         AVS_TRY(enqueue_chunk(w, stream, gkey, max_iters, info != nullptr, enqueue_iteration, &cs));
     }
-    if (w->host_sc->done == 3) // rhs == 0: x := 0
-        hipLaunchKernelGGL(k_sr_update, dim3(g), dim3(kBlock), 0, stream, n, x, r, p, sv, u, wv, invd, (const PcgScalars *)sc, sc, 0, pvec);
-    AVS_TRY(finish_info(w, A, stream, info, &cs, w->host_sc->cancelled != 0, w->resident_used, false));
+    if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(v.x, 0, (size_t)n * sizeof(T), stream)); // rhs == 0: x := 0
+    if constexpr (F32) hipLaunchKernelGGL(k_f32_widen, dim3(g), dim3(kBlock), 0, stream, n, (const float *)v.x, x);
+    AVS_HIP(hipGetLastError());
+    AVS_TRY(finish_info(w, A, stream, info, &cs, w->host_sc->cancelled != 0, w->resident_used, F32));
     if (w->host_sc->cancelled) (void)cancel_consume();
     return AVS_OK;
 }
@@ -2346,21 +2470,6 @@ void pcg_destroy(PcgWork *w)
     delete w;
 }
 
-static avs_status reduce_stage(PcgWork *w, int nb, int nred, int op, double tol, int skip_if_done,
-                               hipStream_t stream, PcgDist *dist)
-{
-    if (!dist) {
-        reduce_launch(w, w->partial.p, nb, nred, w->sc.p, op, tol, skip_if_done, 0, stream);
-    } else {
-        // local sums -> RCCL all-reduce of sc->red[0..nred) -> scalar update
-        reduce_launch(w, w->partial.p, nb, nred, w->sc.p, (int)OP_NONE, tol, 0, 0, stream);
-        AVS_TRY(dist_allreduce(dist, reinterpret_cast<double *>(reinterpret_cast<char *>(w->sc.p) + offsetof(PcgScalars, red)), nred, stream));
-        hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, w->sc.p, op, tol);
-    }
-    AVS_HIP(hipGetLastError());
-    return AVS_OK;
-}
-
 // Single GPU, no partition: the single-reduction iteration on the chip when the system qualifies (*ran = false otherwise, nothing
 // touched).  Set-up (r = b - A x, u = M^-1 r, w = A u, the three sums) with the launch-per-phase kernels, the loop resident.
 static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, int max_iters,
@@ -2373,7 +2482,8 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
     if (!w->resident) w->resident = new (std::nothrow) ResidentPlan();
     if (cancel_requested()) return AVS_OK; // (the launch-per-phase loop consumes the request at its first poll: 0 iterations, cancelled = 1)
     if (!w->resident || !resident_prepare(w->resident, A, A.n, nullptr, stream)) return AVS_OK;
-    AVS_TRY(sr_setup(w, A, b, x, tol, true, nullptr, stream));
+    SrVecs<double> v;
+    AVS_TRY(sr_setup_exchange(w, A, b, x, tol, true, nullptr, &v, stream));
     // the initial guess is kept: if a bounded wait inside the cooperative launch times out (the grid was not co-resident in time: a GPU
     // shared with a viewport or OpenCL work) the solve is redone from it by the launch-per-phase loop IN THIS CALL
     AVS_TRY(w->x_save.alloc((size_t)n));
@@ -2407,8 +2517,6 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
     return AVS_OK;
 }
 
-#include "avs_pcg_f32.inl"
-#include "avs_pcg_dist_f32.inl"
 
 // (KEEP is a template parameter of the vector kernels: see stream_load_k)
 #define AVS_VEC_LAUNCH(KERNEL, C, F, ...)                                                                             \
@@ -2428,12 +2536,12 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
         // AVS_OPTION_DIST_F32_VECTORS: the single-reduction loops on float vectors; AVS_DIST_CG=standard and paranoid mode stay fp64
         const bool paranoid = direct ? da.paranoid : cur_opt().paranoid != 0;
         if (A.f32_vectors > 0 && !cur_opt().dist_standard_cg && !paranoid)
-            return direct ? pcg_solve_direct_f32(w, A, b, x, tol, max_iters, stream, info, da)
-                          : pcg_solve_sr_f32(w, A, b, x, tol, max_iters, stream, info, dist);
-        if (direct) return pcg_solve_direct(w, A, b, x, tol, max_iters, stream, info, da);
+            return direct ? pcg_solve_direct<float>(w, A, b, x, tol, max_iters, stream, info, da)
+                          : pcg_solve_single_reduction<float>(w, A, b, x, tol, max_iters, stream, info, dist);
+        if (direct) return pcg_solve_direct<double>(w, A, b, x, tol, max_iters, stream, info, da);
     }
     if (dist && dist_wants_single_reduction(dist))
-        return pcg_solve_single_reduction(w, A, b, x, tol, max_iters, stream, info, dist);
+        return pcg_solve_single_reduction<double>(w, A, b, x, tol, max_iters, stream, info, dist);
     if (!dist && A.f32_vectors > 0) return pcg_solve_f32(w, A, b, x, tol, max_iters, stream, info); // AVS_PRECISION_F32: float vectors and scalars
     if (!dist && resident_wanted(false)) { // systems that fit on the chip (<= ~1 M rows, packed form): one cooperative launch
         bool ran = false;

@@ -1,4 +1,4 @@
-"""Partitioned solves of AVS_PRECISION_F32 contexts on float vectors (AVS_OPTION_DIST_F32_VECTORS = 1, csrc/avs_pcg_dist_f32.inl).
+"""Partitioned solves of AVS_PRECISION_F32 contexts on float vectors (AVS_OPTION_DIST_F32_VECTORS = 1, csrc/avs_pcg.hip).
 
 The single-GPU float loop (AVS_OPTION_F32_VECTORS = 1) iterates as Eigen's float CG does; with the option, the partitioned
 single-reduction loops do the same over both transports.  Checked here:

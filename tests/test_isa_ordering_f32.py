@@ -1,4 +1,4 @@
-"""The float instantiations of k_sr_update_push (the direct transport's float-vector loop, csrc/avs_pcg_dist_f32.inl) keep the
+"""The float instantiations of k_sr_update_push (the direct transport's float-vector loop, csrc/avs_pcg.hip) keep the
 ordering the protocol depends on: the halo entries leave with system-scope write-through stores, and an `s_waitcnt vmcnt(0)` sits
 between the last of them and the barrier / ticket / flag (tools/isa_check.py disassembles the shipped library; no GPU needed)."""
 import os
