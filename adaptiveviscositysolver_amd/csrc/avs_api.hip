@@ -111,6 +111,7 @@ Options options_from_env()
     o.fused_timeout_ms = env_int("AVS_PCG_FUSED_TIMEOUT_MS", 2000);
     { const int v = env_int("AVS_F32_VECTORS", -1); o.f32_vectors = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.dist_f32_vectors = env_int("AVS_DIST_F32_VECTORS", 0) != 0;
+    o.resident_f32 = env_int("AVS_RESIDENT_F32", 0) != 0;
     o.prepass_temporal = env_int("AVS_PREPASS_TEMPORAL", 1) != 0;
     { const int v = env_int("AVS_POST_DOF_SAMPLE", -1); o.post_dof_sample = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.resident_cus = env_int("AVS_CG_RESIDENT_CUS", 0);
@@ -634,6 +635,7 @@ static CsrView csr_of(avs_ctx *c)
     A.no_precond = c->no_precond;
     A.brick = (c->reordered && c->brick.ready) ? &c->brick_view : nullptr;
     A.f32_vectors = c->desc.precision == AVS_PRECISION_F32 ? c->opt.f32_vectors : 0;
+    A.resident_f32 = c->desc.precision == AVS_PRECISION_F32 ? c->opt.resident_f32 : 0;
     return A;
 }
 
@@ -669,6 +671,7 @@ avs_status avs_set_solver_option(avs_ctx *c, avs_solver_option option, int32_t v
     case AVS_OPTION_F32_VECTORS: c->opt.f32_vectors = value < 0 ? -1 : (value > 0 ? 1 : 0); return AVS_OK;
     case AVS_OPTION_FUSED_VECTOR_UPDATE: c->opt.fuse_vectors = value < 0 ? -1 : (value > 0 ? 1 : 0); return AVS_OK;
     case AVS_OPTION_DIST_F32_VECTORS: c->opt.dist_f32_vectors = value != 0; return AVS_OK;
+    case AVS_OPTION_RESIDENT_F32: c->opt.resident_f32 = value != 0; return AVS_OK;
     }
     set_error("unknown solver option %d", (int)option);
     return AVS_EINVAL;

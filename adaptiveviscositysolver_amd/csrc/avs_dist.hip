@@ -80,6 +80,7 @@ struct PcgDist {
     PcgWork *pcg = nullptr;
     bool partitioned = false, solved = false, reordered = false;
     bool f32 = false; // AVS_PRECISION_F32 + AVS_OPTION_DIST_F32_VECTORS when this plan was made: the single-reduction loops run on float vectors
+    bool resident_f32 = false; // ... + AVS_OPTION_RESIDENT_F32: the CU-resident loop between ranks runs on float vectors too
     DevBuf<double> recvbuf; // float halo exchange (RCCL / in-process): the peers' entries, widened, before they are narrowed into the vector
     // slab cuts along cut_axis (fine cells, world + 1 entries): the ones this assembly used, and the ones its per-plane weights suggest
     // for the next frame (slab-local assembly: the pre-pass needs the cuts BEFORE anything is counted)
@@ -1990,6 +1991,7 @@ avs_status avs_dist_partition(avs_ctx *c, int32_t cut_axis)
     const double *g_rhs = ro ? c->p_rhs.p : c->rhs.p, *g_x0 = ro ? c->p_x0.p : c->x0.p;
     const bool host_plan = cur_opt().dist_host_plan != 0;
     d->f32 = c->desc.precision == AVS_PRECISION_F32 && c->opt.dist_f32_vectors != 0;
+    d->resident_f32 = d->f32 && c->opt.resident_f32 != 0;
     d->vi.clear();
     d->brick.clear();   // (the brick-structured form is built for distributed assemblies only: avs_dist_assemble)
     d->brick.view(d->brick_view, d->vi);
@@ -2072,6 +2074,7 @@ avs_status avs_dist_assemble(avs_ctx *c, int32_t cut_axis, avs_assembly_info *in
     c->system_ready = false; // no global matrix in this mode
     c->reordered = false;
     d->f32 = c->desc.precision == AVS_PRECISION_F32 && c->opt.dist_f32_vectors != 0;
+    d->resident_f32 = d->f32 && c->opt.resident_f32 != 0;
     d->vi.clear();
     if (c->slab.on) AVS_TRY(dist_assemble_window(c, d));
     else AVS_TRY(dist_assemble_device(c, d, cut_axis, extent));
@@ -2225,6 +2228,7 @@ avs_status avs_dist_solve(avs_ctx *c, double tol, int32_t max_iters, avs_solve_i
     A.no_precond = c->no_precond;
     A.brick = d->brick.ready ? &d->brick_view : nullptr;
     A.f32_vectors = d->f32 ? 1 : 0;
+    A.resident_f32 = d->resident_f32 ? 1 : 0;
     avs_solve_info local{};
     const avs_status rc = pcg_solve(d->pcg, A, d->rhs.p, d->x.p, tol, max_iters, c->stream, &local, d);
     c->float_vectors = pcg_float_vectors(d->pcg);

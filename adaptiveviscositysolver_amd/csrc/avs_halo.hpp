@@ -117,21 +117,28 @@ enum ScalarOp { OP_NONE = 0, OP_INIT = 1, OP_RHO0 = 2, OP_ALPHA = 3, OP_BETA = 4
 // double, or float for the float-vector loops (the sums rounded to float, the scalars computed in float -- what Eigen's float CG holds --
 // and kept as doubles holding floats).  The step folded into k_sr_update and OP_SR_STEP_F32 (finalizer, k_scalar) share it: every place
 // computes the same bits.  OP_SR_STEP below is the same arithmetic written out on *sc (through sr_step<double> the compiler lays out
-// every kernel that inlines apply_scalar_op differently).
+// every kernel that inlines apply_scalar_op differently).  sr_step_sums: the step on sums and threshold wherever they are held (the
+// CU-resident loop's workgroup 0 has them in LDS and registers).
 template <typename S>
-__device__ inline void sr_step(const PcgScalars *in, double &rr, double &rho, double &alpha, double &beta, int &iter, int &done)
+__device__ inline void sr_step_sums(const double *red, const double *threshold, double &rr, double &rho, double &alpha, double &beta, int &iter,
+                                    int &done)
 {
     if (done) return;
-    const S rrs = (S)in->red[1];
+    const S rrs = (S)red[1];
     rr = (double)rrs;
-    if (rrs < (S)in->threshold) { done = 1; return; } // x is already updated: plain "converged"
-    const S gamma = (S)in->red[0], delta = (S)in->red[2];
+    if (rrs < (S)*threshold) { done = 1; return; } // x is already updated: plain "converged"
+    const S gamma = (S)red[0], delta = (S)red[2];
     const S b2 = gamma / (S)rho;
     const S a = gamma / (delta - b2 * gamma / (S)alpha);
     alpha = (double)a;
     beta = (double)b2;
     rho = (double)gamma;
     iter += 1;
+}
+template <typename S>
+__device__ inline void sr_step(const PcgScalars *in, double &rr, double &rho, double &alpha, double &beta, int &iter, int &done)
+{
+    sr_step_sums<S>(in->red, &in->threshold, rr, rho, alpha, beta, iter, done);
 }
 
 __device__ inline void apply_scalar_op(PcgScalars *sc, int op, double tol)

@@ -116,6 +116,9 @@ struct Options {
     int dist_f32_vectors = 0;    // AVS_DIST_F32_VECTORS: AVS_PRECISION_F32 contexts' partitioned single-reduction loops iterate on float vectors
                                  // (pcg_solve_single_reduction<float>, pcg_solve_direct<float>); latched by the next avs_dist_partition /
                                  // avs_dist_assemble (PcgDist::f32)
+    int resident_f32 = 0;        // AVS_RESIDENT_F32: the CU-resident loop iterates on float vectors where it takes a float-vector solve
+                                 // (k_cg_resident<.., float>): single GPU with f32_vectors != 0, partitioned with dist_f32_vectors (latched
+                                 // with it: PcgDist::resident_f32)
     // CU-resident loop: tuning and test switches
     int resident_cus = 0, resident_equal_lanes = 0, resident_max_global = 3, resident_max_quads = 0, resident_no_stream = 0;
     long long resident_remap_chunk = 0;
@@ -364,6 +367,8 @@ struct CsrView {
     const struct BrickView *brick = nullptr; // host pointer: the brick-structured form of this matrix (single-GPU launch-per-phase loop)
     int f32_vectors = 0; // AVS_PRECISION_F32: the values are floats; the single-GPU solve iterates on float vectors (avs_pcg_f32.inl): 1 always,
                          // -1 where the CU-resident loop does not take the system, 0 never
+    int resident_f32 = 0; // AVS_PRECISION_F32 + AVS_OPTION_RESIDENT_F32: a solve that iterates on float vectors (f32_vectors != 0) does so in the
+                          // CU-resident loop too, where the system qualifies
 };
 constexpr int kCwinOffBits = 14, kCwinSlotBits = 6, kCwinSlots = 1 << kCwinSlotBits, kCwinCodeBits = 32 - kCwinOffBits - kCwinSlotBits;
 

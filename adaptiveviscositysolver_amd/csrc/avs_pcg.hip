@@ -1708,7 +1708,7 @@ static avs_status finish_info(PcgWork *w, const CsrView &A, hipStream_t stream, 
 //   * the SpMV is the single-GPU float loop's (spmv_f32_dispatch);
 //   * halo entries travel as doubles (widened floats: exact) -- the direct transport's comm block, 8-B slots, self-test and checksums,
 //     and the RCCL / in-process exchange's buffers stay as they are.
-// What stays fp64: AVS_DIST_CG=standard, paranoid mode and the CU-resident loop between ranks.
+// What stays fp64: AVS_DIST_CG=standard and paranoid mode (the CU-resident loop between ranks: with AVS_OPTION_RESIDENT_F32 only).
 // CODED (float vectors only): the rows' 2-B diagonal codes and the table of inverted values instead of one inverse per row.
 // ---------------------------------------------------------------------------------------------
 // r = b - t, u = M^-1 r ; partials [0..g) b.b, [g..2g) r.u, [2g..3g) r.r
@@ -2352,14 +2352,15 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
     }));
 
     // Systems that fit on the chip (<= ~1 M rows, packed single-dictionary form): the rest of the solve in ONE cooperative launch,
-    // matrix words in the register files, vector slices in LDS (avs_pcg_resident.inl).  Needs the GPU for itself.  fp64 only.
+    // matrix words in the register files, vector slices in LDS (avs_pcg_resident.inl).  Needs the GPU for itself.  fp64, and float
+    // vectors with AVS_OPTION_RESIDENT_F32 (k_cg_resident<.., float>: the same state, the same scalar step as this loop).
     w->resident_used = 0;
-    if constexpr (!F32) {
+    if (!F32 || A.resident_f32) {
         if (coded && (da.exclusive_device || cur_opt().resident_cus > 0) && resident_wanted(true)) {
             if (!w->resident) w->resident = new (std::nothrow) ResidentPlan();
-            if (w->resident && resident_prepare(w->resident, A, w->n_ext, &da, stream)) {
+            if (w->resident && resident_prepare(w->resident, A, w->n_ext, &da, F32, stream)) {
                 bool launched = false;
-                AVS_TRY(resident_run(w->resident, A, x, v.r, v.p, v.s, v.u, v.w, w->dcode.p, w->invtab.p, sc, max_iters, &da, stream, &launched));
+                AVS_TRY(resident_run<T>(w->resident, A, v.x, v.r, v.p, v.s, v.u, v.w, v.dcode, v.invtab, sc, max_iters, &da, stream, &launched));
                 w->resident_used = launched ? 1 : 0; // (refused: the loop below takes over from the same state)
             }
         }
@@ -2391,7 +2392,7 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
     for (;;) {
         AVS_TRY(poll_scalars(w, sc, stream));
         if (w->host_sc->fault) {
-            if (w->resident_used && w->resident) w->resident->ok = false; // the next distributed solve takes the launch-per-phase loop
+            if (w->resident_used && w->resident) w->resident->ok = false; // the next distributed solve on this plan takes the launch-per-phase loop
             return direct_fault(*w->host_sc);
         }
         sample_spmv(w, info != nullptr, true, &cs);
@@ -2472,25 +2473,33 @@ void pcg_destroy(PcgWork *w)
 
 // Single GPU, no partition: the single-reduction iteration on the chip when the system qualifies (*ran = false otherwise, nothing
 // touched).  Set-up (r = b - A x, u = M^-1 r, w = A u, the three sums) with the launch-per-phase kernels, the loop resident.
+// T = float (AVS_OPTION_RESIDENT_F32): set-up and loop on float vectors, the solution widened into x at the end; a fault hands the
+// solve to the float launch-per-phase loop (pcg_solve_f32) instead of the fp64 one.
+template <typename T>
 static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, int max_iters,
                                             hipStream_t stream, avs_solve_info *info, bool *ran)
 {
+    constexpr bool F32 = std::is_same<T, float>::value;
     *ran = false;
     const int64_t n = A.n;
     const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable;
     if (!coded) return AVS_OK;
     if (!w->resident) w->resident = new (std::nothrow) ResidentPlan();
     if (cancel_requested()) return AVS_OK; // (the launch-per-phase loop consumes the request at its first poll: 0 iterations, cancelled = 1)
-    if (!w->resident || !resident_prepare(w->resident, A, A.n, nullptr, stream)) return AVS_OK;
-    SrVecs<double> v;
+    if (!w->resident || !resident_prepare(w->resident, A, A.n, nullptr, F32, stream)) return AVS_OK;
+    if (F32) { // the float set-up's SpMV partials (as pcg_solve_single_reduction<float> reserves them)
+        const bool brick = A.brick && A.brick->ntiles > 0 && A.brick->pwords32;
+        const size_t nb_max = brick ? (size_t)brick_partial_count(*A.brick, 4) : (size_t)stream_grid(n);
+        AVS_TRY(ensure_partials(w, 4 * (size_t)kVecGrid + nb_max + 16));
+    }
+    SrVecs<T> v;
     AVS_TRY(sr_setup_exchange(w, A, b, x, tol, true, nullptr, &v, stream));
     // the initial guess is kept: if a bounded wait inside the cooperative launch times out (the grid was not co-resident in time: a GPU
     // shared with a viewport or OpenCL work) the solve is redone from it by the launch-per-phase loop IN THIS CALL
     AVS_TRY(w->x_save.alloc((size_t)n));
     AVS_HIP(hipMemcpyAsync(w->x_save.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     bool launched = false;
-    AVS_TRY(resident_run(w->resident, A, x, w->r.p, w->p.p, w->s.p, w->u.p, w->t.p, w->dcode.p, w->invtab.p, w->sc.p, max_iters, nullptr,
-                         stream, &launched));
+    AVS_TRY(resident_run<T>(w->resident, A, v.x, v.r, v.p, v.s, v.u, v.w, v.dcode, v.invtab, w->sc.p, max_iters, nullptr, stream, &launched));
     if (!launched) return AVS_OK; // (x is untouched: the launch-per-phase loop starts over from it)
     AVS_TRY(poll_scalars(w, w->sc.p, stream));
     bool faulted = w->host_sc->fault != 0;
@@ -2498,15 +2507,17 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
     if (getenv("AVS_CG_RESIDENT_FAKE_FAULT")) faulted = true; // test hook of exactly this path (probe build only)
 #endif
     if (faulted) {
-        w->resident->ok = false; // not again on this context
+        w->resident->ok = false; // not again for this plan (until a new matrix or the other vector type re-plans)
         w->resident_faults++;
         AVS_HIP(hipMemcpyAsync(x, w->x_save.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
         return AVS_OK;           // *ran stays false: pcg_solve carries on with the launch-per-phase loop
     }
     *ran = true;
     w->resident_used = 1;
-    if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), stream)); // rhs == 0: x := 0
-    AVS_TRY(finish_info(w, A, stream, info, nullptr, false, 1, false)); // (spmv_ms = 0: no separate SpMV launch to time)
+    if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(v.x, 0, (size_t)n * sizeof(T), stream)); // rhs == 0: x := 0
+    if constexpr (F32) hipLaunchKernelGGL(k_f32_widen, dim3(vec_grid(n)), dim3(kBlock), 0, stream, n, (const float *)v.x, x);
+    AVS_HIP(hipGetLastError());
+    AVS_TRY(finish_info(w, A, stream, info, nullptr, false, 1, F32)); // (spmv_ms = 0: no separate SpMV launch to time)
     // avs_cancel during the cooperative launch: the launch cannot be interrupted, but the request ends HERE -- consumed, and reported when the
     // loop stopped at max_iterations without converging (a converged solve is a converged solve; the request is consumed either way, so that
     // it cannot hit the next solve on this context)
@@ -2542,13 +2553,16 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
     }
     if (dist && dist_wants_single_reduction(dist))
         return pcg_solve_single_reduction<double>(w, A, b, x, tol, max_iters, stream, info, dist);
-    if (!dist && A.f32_vectors > 0) return pcg_solve_f32(w, A, b, x, tol, max_iters, stream, info); // AVS_PRECISION_F32: float vectors and scalars
+    // AVS_OPTION_RESIDENT_F32: a float-vector solve (f32_vectors 1 or -1) tries the resident loop on float vectors first
+    const bool resident_f32 = !dist && A.resident_f32 && A.f32_vectors != 0;
+    if (!dist && A.f32_vectors > 0 && !resident_f32) return pcg_solve_f32(w, A, b, x, tol, max_iters, stream, info); // AVS_PRECISION_F32: float vectors and scalars
     if (!dist && resident_wanted(false)) { // systems that fit on the chip (<= ~1 M rows, packed form): one cooperative launch
         bool ran = false;
-        const avs_status rs = pcg_solve_resident_single(w, A, b, x, tol, max_iters, stream, info, &ran);
+        const avs_status rs = resident_f32 ? pcg_solve_resident_single<float>(w, A, b, x, tol, max_iters, stream, info, &ran)
+                                           : pcg_solve_resident_single<double>(w, A, b, x, tol, max_iters, stream, info, &ran);
         if (ran || rs != AVS_OK) return rs;
     }
-    if (!dist && A.f32_vectors < 0) return pcg_solve_f32(w, A, b, x, tol, max_iters, stream, info); // (auto: the resident loop did not take it)
+    if (!dist && A.f32_vectors != 0) return pcg_solve_f32(w, A, b, x, tol, max_iters, stream, info); // (auto, or a float resident loop that did not take it / faulted)
     if (A.brick && A.brick->ntiles > 0) // one partial per wave of every tile: tiles may be smaller than 512 rows
         AVS_TRY(ensure_partials(w, 2 * ((size_t)A.brick->ntiles * 8 + 16) + 4 * (size_t)kVecGrid + 16));
     const int g = vec_grid(n);

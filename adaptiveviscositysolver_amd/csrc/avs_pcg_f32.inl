@@ -327,7 +327,7 @@ static avs_status pcg_solve_f32(PcgWork *w, const CsrView &A, const double *b, d
     const int64_t n = A.n;
     const size_t na = (size_t)n + 8;
     w->float_vectors = 1;
-    if (!w->f_x.p) {
+    if (!w->f_x.p || !w->f_b.p) { // (the float set-up of the CU-resident loop allocates all but f_b)
         AVS_TRY(w->f_x.alloc(na)); AVS_TRY(w->f_r.alloc(na)); AVS_TRY(w->f_p.alloc(na)); AVS_TRY(w->f_t.alloc(na)); AVS_TRY(w->f_b.alloc(na));
     }
     const bool brick = A.brick && A.brick->ntiles > 0 && A.brick->pwords32;

@@ -17,6 +17,11 @@
 //
 // Same recurrences as k_sr_update_push + OP_SR_STEP (Chronopoulos-Gear), same left-to-right row sums (one lane per row), so the
 // iterates agree with the launch-per-phase loop up to the order of additions inside the three dot products.
+// T, the vector type: double, or float for AVS_PRECISION_F32 solves with AVS_OPTION_RESIDENT_F32 = 1 -- the partitioned float loop's
+// arithmetic (k_sr_update_push<.., float>): x, w, u and the slices / remote columns / tables in LDS are floats (the value table staged
+// as float: exact, the float system's values are floats; the inverse diagonal inverted in float, k_f32_invtab), float row sums, a
+// thread's own terms of the dot products in T and everything across threads, workgroups and ranks in double, the scalar step
+// sr_step_sums<float> on the float-rounded sums.  Halo entries travel widened to double (exact): the comm block is the same.
 // Every wait is bounded (wall_clock64): a missing workgroup / peer ends the kernel with sc->fault set, never a hung GPU.
 // Not used when two ranks share one physical GPU (two kernels that each need every CU cannot wait for each other).
 
@@ -47,10 +52,10 @@ static constexpr int kResUpd = AVS_RES_UPD; // rows per thread in flight in the 
 static constexpr int kResTimers = 8;   // phase time stamps per iteration (AVS_CG_RESIDENT_TIMERS=n)
 static constexpr int kResGens = 4;     // generations of the broadcast slots (a ring: re-armed two iterations ahead)
 
-struct ResidentArgs {
+template <typename T> struct ResidentArgs {
     // the local system (row pointers of the packed CSR; the words come re-encoded, see rwords)
     const int32_t *row_ptr;
-    const double *table;
+    const double *table;                  // (float system: float values, staged as T)
     int table_size;
     int n;     // own rows
     int G;     // workgroups (= CUs used)
@@ -73,9 +78,9 @@ struct ResidentArgs {
     int rem_stride;
     const int32_t *rem_count;             // G
     // vectors
-    double *x, *r, *p, *s, *u, *w;
+    T *x, *r, *p, *s, *u, *w;
     const uint16_t *dcode;                // diagonal's value code per row; invtab[code] = 1 / table[code]
-    const double *invtab;
+    const T *invtab;
     // synchronisation (device memory, agent scope)
     unsigned *bar_count;                  // [0]: pushing workgroups that have stored their boundary entries (the last raises the halo flags)
     unsigned long long *bar_flags;        // G: update phases workgroup g has completed (its u is in memory)
@@ -100,7 +105,7 @@ struct ResidentArgs {
 // Loop-body reads of the kernel arguments go through these: one scalar load from the kernarg segment AT THE USE.  Left to itself the
 // compiler loads all ~40 fields of ResidentArgs at entry, keeps the ~25 the loop touches live across it, runs out of SGPRs and spills
 // them to VGPR lanes: 817 v_readlane restores in a 4,000-instruction iteration (20 % of the VALU issue slots of a VALU-bound loop).
-// (the struct is the kernel's only parameter: it sits at offset 0 of the kernarg segment)
+// (the struct is the kernel's only parameter: it sits at offset 0 of the kernarg segment; the macros name the kernel's vector type T)
 template <int OFF> __device__ __forceinline__ unsigned long long res_karg64()
 {
     unsigned long long v;
@@ -113,13 +118,13 @@ template <int OFF> __device__ __forceinline__ unsigned res_karg32()
     asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(OFF));
     return v;
 }
-#define RES_P(f) (reinterpret_cast<decltype(ResidentArgs::f)>(res_karg64<(int)offsetof(ResidentArgs, f)>()))
-#define RES_I(f) ((int)res_karg32<(int)offsetof(ResidentArgs, f)>())
+#define RES_P(f) (reinterpret_cast<decltype(ResidentArgs<T>::f)>(res_karg64<(int)offsetof(ResidentArgs<T>, f)>()))
+#define RES_I(f) ((int)res_karg32<(int)offsetof(ResidentArgs<T>, f)>())
 // The same pointer, typed as GLOBAL memory.  The value comes out of an asm statement, so the compiler only knows a generic pointer and
 // emits flat_load / flat_store -- which tick the LDS counter (lgkmcnt) as well as vmcnt: every LDS wait then also waits for the
 // outstanding global loads, and nothing can be kept in flight across LDS work (the streamed quads, the update's x / w / s loads).
 template <class T> using res_gptr = T __attribute__((address_space(1))) *;
-#define RES_G(f) (reinterpret_cast<res_gptr<std::remove_pointer_t<decltype(ResidentArgs::f)>>>(res_karg64<(int)offsetof(ResidentArgs, f)>()))
+#define RES_G(f) (reinterpret_cast<res_gptr<std::remove_pointer_t<decltype(ResidentArgs<T>::f)>>>(res_karg64<(int)offsetof(ResidentArgs<T>, f)>()))
 
 __device__ __forceinline__ bool res_spin_u64(const unsigned long long *f, unsigned long long want, long long timeout)
 {
@@ -131,10 +136,11 @@ __device__ __forceinline__ bool res_spin_u64(const unsigned long long *f, unsign
     }
     return true;
 }
-// 16-B write-through store at agent scope (global_store_dwordx4 ... sc1): what two agent-scope atomic double stores would do, in one
-// fabric write.  The caller orders it with wait_own_stores() (s_waitcnt vmcnt(0)) like every other write-through store here.
-__device__ __forceinline__ void res_store_wt16(double *p, d2_t v)
+// 16-B write-through store at agent scope (global_store_dwordx4 ... sc1): what two agent-scope atomic double stores (four float ones)
+// would do, in one fabric write.  The caller orders it with wait_own_stores() (s_waitcnt vmcnt(0)) like every other write-through store here.
+template <typename V> __device__ __forceinline__ void res_store_wt16(void *p, V v)
 {
+    static_assert(sizeof(V) == 16, "one 16-B store");
     asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
 }
 // the same at system scope (sc0 sc1): boundary entries into a peer's halo area
@@ -326,22 +332,27 @@ __global__ __launch_bounds__(kResThreads) void k_resident_stream_layout(const in
 // boundaries: the inner loop is decode, two LDS reads and one FMA per word, and one end-of-row test per quad.  (Measured on the
 // 8-way partition of the 512^3 system, tools/probes/rowlen_local.py: rows of 2 / 12 / 15 / 17 / 18 / 20 / 26 words make up 97 %;
 // quads + <= 6 rows per lane need 0.89-0.92 of the chip's 262,144 lanes; slots of 15 or 18 words would need 1.06.)
-template <int NG, bool STREAM>
-__global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
+template <typename T> struct ResVec16;           // 16 B of T: the unit of the write-through stores of u
+template <> struct ResVec16<double> { typedef d2_t type; };
+template <> struct ResVec16<float> { typedef f4_t type; };
+
+template <int NG, bool STREAM, typename T>
+__global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
 {
     extern __shared__ __attribute__((aligned(16))) double rlds[];
     // u: the workgroup's slice, then its remote-column cache (one index space: a word's local column addresses both)
     // (the split is per workgroup -- its own row and remote-column counts: workgroups of coarse regions have few rows and many remote
     // columns, those of fine regions the opposite, and the sum is what has to fit)
+    // (even counts of T: the doubles behind the tables stay 8-B aligned)
     const int wrows_al = (a.wg_row0[blockIdx.x + 1] - a.wg_row0[blockIdx.x] + 1) & ~1, nrem_al = (a.rem_count[blockIdx.x] + 1) & ~1;
-    double *u_l = rlds;
-    double *r_l = u_l + wrows_al + nrem_al;
-    double *p_l = r_l + (NG < 3 ? wrows_al : 0);
-    double *s_l = p_l + (NG < 2 ? wrows_al : 0);
-    double *tbl = s_l + (NG < 1 ? wrows_al : 0); // table_size values + one zero (what the padding words multiply with)
-    double *itab = tbl + a.table_size + 1;          // table_size + 1 inverted values
-    double *fold = itab + a.table_size + 1;         // 3 x 16 wave sums
-    double *bc = fold + 48;                         // 4 rank sums + 4 broadcast scalars
+    T *u_l = reinterpret_cast<T *>(rlds);
+    T *r_l = u_l + wrows_al + nrem_al;
+    T *p_l = r_l + (NG < 3 ? wrows_al : 0);
+    T *s_l = p_l + (NG < 2 ? wrows_al : 0);
+    T *tbl = s_l + (NG < 1 ? wrows_al : 0); // table_size values + one zero (what the padding words multiply with)
+    T *itab = tbl + a.table_size + 1;          // table_size + 1 inverted values
+    double *fold = reinterpret_cast<double *>(itab + a.table_size + 1); // 3 x 16 wave sums
+    double *bc = fold + 48;                                              // 4 rank sums + 4 broadcast scalars
     __shared__ int sh_fail;
     __shared__ double rank_all[kMaxRanks * 4];
     const int tid = threadIdx.x, b = blockIdx.x, G = a.G;
@@ -404,7 +415,7 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
         if (NG < 1) s_l[i] = a.s[wrow0 + i];
     }
     for (int i = tid; i <= a.table_size; i += kResThreads) {
-        tbl[i] = i < a.table_size ? a.table[i] : 0.;
+        tbl[i] = i < a.table_size ? (T)a.table[i] : (T)0;
         itab[i] = a.invtab[i];
     }
     if (tid == 0) sh_fail = 0;
@@ -447,14 +458,15 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
         // x is touched every SECOND iteration: the update that computes p_new still holds p_old, which is all the skipped
         // x += alpha_prev p_old needs (16 of the 56-82 B per row of this phase, every other time)
         const bool skip_x = (it & 1) == 0;
-        double ru = 0., rr = 0.;
+        T ru = 0, rr = 0;
         {
-            const res_gptr<double> gx = RES_G(x) + wrow0, gp = NG >= 2 ? RES_G(p) + wrow0 : nullptr, gr = NG >= 3 ? RES_G(r) + wrow0 : nullptr;
-            const res_gptr<double> gs = NG >= 1 ? RES_G(s) + wrow0 : nullptr;
-            const res_gptr<const double> gw = RES_G(w) + wrow0;
+            const T al = (T)alpha, bt = (T)beta, al_pend = (T)alpha_pend; // (float: the scalars are floats held in doubles)
+            const res_gptr<T> gx = RES_G(x) + wrow0, gp = NG >= 2 ? RES_G(p) + wrow0 : nullptr, gr = NG >= 3 ? RES_G(r) + wrow0 : nullptr;
+            const res_gptr<T> gs = NG >= 1 ? RES_G(s) + wrow0 : nullptr;
+            const res_gptr<const T> gw = RES_G(w) + wrow0;
             const res_gptr<const uint16_t> gd = RES_G(dcode) + wrow0;
             for (int i0 = tid; i0 < wrows; i0 += kResUpd * kResThreads) {
-                double xv[kResUpd], wv[kResUpd], sv[kResUpd], pv[kResUpd], rv[kResUpd];
+                T xv[kResUpd], wv[kResUpd], sv[kResUpd], pv[kResUpd], rv[kResUpd];
                 unsigned dv[kResUpd];
 #pragma unroll
                 for (int j = 0; j < kResUpd; ++j) {
@@ -472,18 +484,18 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
                 for (int j = 0; j < kResUpd; ++j) {
                     const int i = i0 + j * kResThreads;
                     if (i < wrows) {
-                        const double p_old = NG >= 2 ? pv[j] : p_l[i];
-                        const double pi = u_l[i] + beta * p_old;
-                        const double si = wv[j] + beta * (NG >= 1 ? sv[j] : s_l[i]);
+                        const T p_old = NG >= 2 ? pv[j] : p_l[i];
+                        const T pi = u_l[i] + bt * p_old;
+                        const T si = wv[j] + bt * (NG >= 1 ? sv[j] : s_l[i]);
                         if (NG >= 2) gp[i] = pi;
                         else p_l[i] = pi;
                         if (NG >= 1) gs[i] = si;
                         else s_l[i] = si;
-                        if (!skip_x) gx[i] = (xv[j] + alpha_pend * p_old) + alpha * pi; // = the two sequential updates, bit for bit
-                        const double ri = (NG >= 3 ? rv[j] : r_l[i]) - alpha * si;
+                        if (!skip_x) gx[i] = (xv[j] + al_pend * p_old) + al * pi; // = the two sequential updates, bit for bit
+                        const T ri = (NG >= 3 ? rv[j] : r_l[i]) - al * si;
                         if (NG >= 3) gr[i] = ri;
                         else r_l[i] = ri;
-                        const double ui = itab[dv[j]] * ri;
+                        const T ui = itab[dv[j]] * ri;
                         u_l[i] = ui;
                         ru += ri * ui;
                         rr += ri * ri;
@@ -495,19 +507,30 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
         if (skip_x) alpha_pend = alpha;
         __syncthreads(); // the workgroup's u is complete in LDS
         // u to global for the other workgroups: write-through (other XCDs read it), coalesced, 16 B per lane where the slice allows
-        // (8-B sc1 stores cost 2.7x per byte, MI355X_MICROARCH.md)
+        // (8-B sc1 stores cost 2.7x per byte, MI355X_MICROARCH.md); K entries per store, the unaligned head and tail one entry per thread.
+        // Every store stays inside the workgroup's rows: the head is clamped to them (float: a workgroup of 1-2 rows can start 1-3 entries
+        // before a 16-B boundary -- small systems, one-row lanes), so groups >= 0 and head + K groups <= wrows
         {
-            double *const gu = RES_P(u);
-            const int head = (wrow0 & 1) && wrows > 0 ? 1 : 0; // 16-B alignment of the global address
-            if (tid == 0 && head) __hip_atomic_store(gu + wrow0, u_l[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int pairs = (wrows - head) >> 1;
-            for (int i = tid; i < pairs; i += kResThreads) {
-                d2_t v;
-                v.x = u_l[head + 2 * i];
-                v.y = u_l[head + 2 * i + 1];
-                res_store_wt16(gu + wrow0 + head + 2 * i, v);
+            constexpr int K = 16 / (int)sizeof(T);
+            T *const gu = RES_P(u);
+            const int align = (K - (wrow0 & (K - 1))) & (K - 1); // entries before the first 16-B boundary
+            const int head = K == 2 ? ((wrow0 & 1) && wrows > 0 ? 1 : 0) : (align < wrows ? align : wrows);
+            if (K == 2) { // (fp64: at most one entry each side, written out as before)
+                if (tid == 0 && head) __hip_atomic_store(gu + wrow0, u_l[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else if (tid < head)
+                __hip_atomic_store(gu + wrow0 + tid, u_l[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int groups = (wrows - head) >> (K == 2 ? 1 : 2);
+            for (int i = tid; i < groups; i += kResThreads) {
+                typename ResVec16<T>::type v;
+#pragma unroll
+                for (int k = 0; k < K; ++k) v[k] = u_l[head + K * i + k];
+                res_store_wt16(gu + wrow0 + head + K * i, v);
             }
-            if (tid == 0 && ((wrows - head) & 1)) __hip_atomic_store(gu + wrow0 + wrows - 1, u_l[wrows - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int rest = head + K * groups; // first entry of the tail (<= wrows)
+            if (K == 2) {
+                if (tid == 0 && ((wrows - head) & 1)) __hip_atomic_store(gu + wrow0 + wrows - 1, u_l[wrows - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else if (tid < wrows - rest)
+                __hip_atomic_store(gu + wrow0 + rest + tid, u_l[rest + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (dd && dd->npeers) {
             const int32_t *const pseg = RES_P(push_seg);
@@ -518,16 +541,16 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
                 // consecutive entries of the peer's halo area: two per fabric write where the address allows (an 8-B write-through store
                 // costs 2.7x per byte, MI355X_MICROARCH.md); the flag that orders them is raised after wait_own_stores()
                 const int head = (sa < se && (reinterpret_cast<uintptr_t>(dst + sa) & 15u)) ? 1 : 0;
-                if (tid == 0 && head) __hip_atomic_store(dst + sa, u_l[sidx[sa] - wrow0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if (tid == 0 && head) __hip_atomic_store(dst + sa, (double)u_l[sidx[sa] - wrow0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 const int pairs = (se - sa - head) >> 1;
                 for (int q = tid; q < pairs; q += kResThreads) {
                     const int j = sa + head + 2 * q;
                     d2_t v;
-                    v.x = u_l[sidx[j] - wrow0];
-                    v.y = u_l[sidx[j + 1] - wrow0];
+                    v.x = (double)u_l[sidx[j] - wrow0]; // (float: widened, exact; the reader narrows it back)
+                    v.y = (double)u_l[sidx[j + 1] - wrow0];
                     res_store_sys16(dst + j, v);
                 }
-                if (tid == 0 && ((se - sa - head) & 1)) __hip_atomic_store(dst + se - 1, u_l[sidx[se - 1] - wrow0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if (tid == 0 && ((se - sa - head) & 1)) __hip_atomic_store(dst + se - 1, (double)u_l[sidx[se - 1] - wrow0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
         wait_own_stores(); // u (agent scope) and the peers' entries (system scope) acknowledged before this wave reaches the barrier
@@ -562,18 +585,18 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
         // ---- C: w = A u for the lane's rows.  First the workgroup's remote columns -> LDS, ONE round trip for all of them (plain loads
         // of the global u: this CU's L1 / the XCD's L2 were invalidated behind the barrier; other ranks' entries: the halo area of the
         // comm block, fine-grained memory first touched after the flag); then every gather is an LDS read.
-        const res_gptr<const double> fu = RES_G(u);
+        const res_gptr<const T> fu = RES_G(u);
         const int fn = RES_I(n);
         for (int k0 = tid; k0 < nrem; k0 += kResFill * kResThreads) { // kResFill loads in flight per lane: a halo-reading workgroup fills 8-10 k slots
-            double v[kResFill];
+            T v[kResFill];
 #pragma unroll
             for (int j = 0; j < kResFill; ++j) {
                 const int k = k0 + j * kResThreads;
                 if (k < nrem) {
                     const int src = rem[k];
-                    if (!coherent) v[j] = (src < fn) ? fu[src] : halo[src - fn];
+                    if (!coherent) v[j] = (src < fn) ? fu[src] : (T)halo[src - fn]; // (halo entries: doubles; float: narrowed back, exact)
                     else if (src < fn) v[j] = __hip_atomic_load(fu + src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else v[j] = __hip_atomic_load(halo + (src - fn), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    else v[j] = (T)__hip_atomic_load(halo + (src - fn), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
             }
 #pragma unroll
@@ -585,10 +608,10 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
         __syncthreads();
         if (timed) ts[3] = wall_clock64();
         if (stamps && it == 20) RES_P(wg_times)[4 * b + 2] = wall_clock64();
-        double wu = 0.;
+        T wu = 0;
         {
-            const res_gptr<double> gw = RES_G(w);
-            double acc = 0.;
+            const res_gptr<T> gw = RES_G(w);
+            T acc = 0;
             int rk = 0; // row of the lane being summed
             unsigned em = endmask;
             int wnq = wave_nq;
@@ -607,8 +630,8 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
                     { // words 0, 1 (three groups with scheduling barriers between them: ten reads in flight at once need 20 more
                       // registers than the file has next to the 60 of the matrix, and the allocator then parks the MATRIX in scratch)
                         const unsigned t1 = __builtin_amdgcn_alignbit(mm.y, mm.x, 25);
-                        const double v0 = tbl[__builtin_amdgcn_ubfe(mm.x, (unsigned)cbits, kb)], x0 = u_l[mm.x & cmask];
-                        const double v1 = tbl[__builtin_amdgcn_ubfe(t1, (unsigned)cbits, kb)], x1 = u_l[t1 & cmask];
+                        const T v0 = tbl[__builtin_amdgcn_ubfe(mm.x, (unsigned)cbits, kb)], x0 = u_l[mm.x & cmask];
+                        const T v1 = tbl[__builtin_amdgcn_ubfe(t1, (unsigned)cbits, kb)], x1 = u_l[t1 & cmask];
                         acc += v0 * x0; // left to right inside the row, multiply then add (no FMA): the oracle's order and rounding, the same
                                         // row sums as the launch-per-phase kernels bit for bit (padding words add +0)
                         acc += v1 * x1;
@@ -617,20 +640,20 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
                     { // words 2, 3
                         const unsigned t2 = __builtin_amdgcn_alignbit(mm.z, mm.y, 18);
                         const unsigned t3 = __builtin_amdgcn_alignbit(mm.w, mm.z, 11);
-                        const double v2 = tbl[__builtin_amdgcn_ubfe(t2, (unsigned)cbits, kb)], x2 = u_l[t2 & cmask];
-                        const double v3 = tbl[__builtin_amdgcn_ubfe(t3, (unsigned)cbits, kb)], x3 = u_l[t3 & cmask];
+                        const T v2 = tbl[__builtin_amdgcn_ubfe(t2, (unsigned)cbits, kb)], x2 = u_l[t2 & cmask];
+                        const T v3 = tbl[__builtin_amdgcn_ubfe(t3, (unsigned)cbits, kb)], x3 = u_l[t3 & cmask];
                         acc += v2 * x2;
                         acc += v3 * x3;
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     { // word 4
-                        const double v4 = tbl[__builtin_amdgcn_ubfe(mm.w, 4u + (unsigned)cbits, kb)], x4 = u_l[__builtin_amdgcn_ubfe(mm.w, 4u, (unsigned)cbits)];
+                        const T v4 = tbl[__builtin_amdgcn_ubfe(mm.w, 4u + (unsigned)cbits, kb)], x4 = u_l[__builtin_amdgcn_ubfe(mm.w, 4u, (unsigned)cbits)];
                         acc += v4 * x4;
                     }
                     if ((em >> q) & 1u) {
                         gw[row0 + rk] = acc;
                         wu += acc * u_l[row0 + rk - wrow0];
-                        acc = 0.;
+                        acc = 0;
                         ++rk;
                     }
                 }
@@ -657,7 +680,7 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
                 const unsigned long long phi = ((unsigned long long)pw >> 14) | ((unsigned long long)pw << 11) | ((unsigned long long)pw << 36);
                 const u4_t padq = u4_t{(unsigned)plo, (unsigned)(plo >> 32), (unsigned)phi, (unsigned)(phi >> 32)};
                 int row = row0 + nrows;
-                double sacc = 0.;
+                T sacc = 0;
 #if AVS_RES_STREAM_DB
                 u4_t qn[kResStream]; // the batch in flight while the previous one is multiplied
 #pragma unroll
@@ -680,11 +703,11 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
                         const unsigned t1 = __builtin_amdgcn_alignbit(mm.y, mm.x, 25);
                         const unsigned t2 = __builtin_amdgcn_alignbit(mm.z, mm.y, 18);
                         const unsigned t3 = __builtin_amdgcn_alignbit(mm.w, mm.z, 11);
-                        const double v0 = tbl[__builtin_amdgcn_ubfe(mm.x, (unsigned)cbits, kb)], x0 = u_l[mm.x & cmask];
-                        const double v1 = tbl[__builtin_amdgcn_ubfe(t1, (unsigned)cbits, kb)], x1 = u_l[t1 & cmask];
-                        const double v2 = tbl[__builtin_amdgcn_ubfe(t2, (unsigned)cbits, kb)], x2 = u_l[t2 & cmask];
-                        const double v3 = tbl[__builtin_amdgcn_ubfe(t3, (unsigned)cbits, kb)], x3 = u_l[t3 & cmask];
-                        const double v4 = tbl[__builtin_amdgcn_ubfe(mm.w, 4u + (unsigned)cbits, kb)], x4 = u_l[__builtin_amdgcn_ubfe(mm.w, 4u, (unsigned)cbits)];
+                        const T v0 = tbl[__builtin_amdgcn_ubfe(mm.x, (unsigned)cbits, kb)], x0 = u_l[mm.x & cmask];
+                        const T v1 = tbl[__builtin_amdgcn_ubfe(t1, (unsigned)cbits, kb)], x1 = u_l[t1 & cmask];
+                        const T v2 = tbl[__builtin_amdgcn_ubfe(t2, (unsigned)cbits, kb)], x2 = u_l[t2 & cmask];
+                        const T v3 = tbl[__builtin_amdgcn_ubfe(t3, (unsigned)cbits, kb)], x3 = u_l[t3 & cmask];
+                        const T v4 = tbl[__builtin_amdgcn_ubfe(mm.w, 4u + (unsigned)cbits, kb)], x4 = u_l[__builtin_amdgcn_ubfe(mm.w, 4u, (unsigned)cbits)];
                         sacc += v0 * x0;
                         sacc += v1 * x1;
                         sacc += v2 * x2;
@@ -693,7 +716,7 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
                         if (mm.w >> 31) { // (bit 127) the row's last quad
                             gw[row] = sacc;
                             wu += sacc * u_l[row - wrow0];
-                            sacc = 0.;
+                            sacc = 0;
                             ++row;
                         }
                     }
@@ -703,7 +726,7 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
         // ---- D: one reduction of (r.u, |r|^2, w.u): every workgroup drops its three sums into sentinel-armed slots (fire and forget:
         // the value is its own arrival); workgroup 0 takes them in slot order, exchanges with the other ranks, applies the scalar step
         // and publishes it in the broadcast ring everybody polls ----
-        double s0 = ru, s1 = rr, s2 = wu;
+        double s0 = (double)ru, s1 = (double)rr, s2 = (double)wu; // (across threads, workgroups and ranks: double)
         res_block_fold3(s0, s1, s2, fold);
         if (tid == 0) {
             double *const sl = RES_P(slots) + 4 * b;
@@ -768,19 +791,13 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
                 __syncthreads();
             }
             if (tid == 0) {
-                // OP_SR_STEP on (gamma, |r|^2, delta)
+                // OP_SR_STEP (float: OP_SR_STEP_F32) on (gamma, |r|^2, delta)
                 const double gamma = bc[0], rr_all = bc[1], delta = bc[2];
-                int nd = 0;
-                double na = alpha, nb = beta, nrho = rho;
+                const double sums[3] = {gamma, rr_all, delta};
+                int nd = sh_fail ? 1 : 0;
+                double na = alpha, nb = beta, nrho = rho, nrr = (double)(T)rr_all;
                 int niter = iter;
-                if (sh_fail) nd = 1;
-                else if (rr_all < threshold) nd = 1;
-                else {
-                    nb = gamma / rho;
-                    na = gamma / (delta - nb * gamma / alpha);
-                    nrho = gamma;
-                    niter = iter + 1;
-                }
+                sr_step_sums<T>(sums, &threshold, nrr, nrho, na, nb, niter, nd);
                 // the ring: re-arm the generation two iterations ahead, publish this one
                 double *const ring = RES_P(bcast);
                 double *ahead = ring + 4 * ((it + 2) & (kResGens - 1)), *me = ring + 4 * gen;
@@ -797,7 +814,7 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
                 // the host's copy of the state (always written by this one thread: plain stores)
                 PcgScalars *const hs = RES_P(sc);
                 hs->red[0] = gamma; hs->red[1] = rr_all; hs->red[2] = delta;
-                hs->rr = rr_all; hs->alpha = na; hs->beta = nb; hs->rho = nrho; hs->iter = niter; hs->done = nd;
+                hs->rr = nrr; hs->alpha = na; hs->beta = nb; hs->rho = nrho; hs->iter = niter; hs->done = nd;
                 if (sh_fail && !hs->fault) hs->fault = 3;
             }
         }
@@ -819,7 +836,7 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs a)
     }
     // ---- write the vectors back (a later solve / the host reads them), close the round counter -----------------------------------
     if (x_pending) // the last update skipped x: x += alpha p with the p it left behind
-        for (int i = tid; i < wrows; i += kResThreads) a.x[wrow0 + i] += alpha_pend * (NG >= 2 ? a.p[wrow0 + i] : p_l[i]);
+        for (int i = tid; i < wrows; i += kResThreads) a.x[wrow0 + i] += (T)alpha_pend * (NG >= 2 ? a.p[wrow0 + i] : p_l[i]);
     for (int i = tid; i < wrows; i += kResThreads) {
         if (NG < 3) a.r[wrow0 + i] = r_l[i];
         if (NG < 2) a.p[wrow0 + i] = p_l[i];
@@ -849,6 +866,7 @@ struct ResidentPlan {
     DevBuf<long long> timers;
     int G = 0, max_timed = 0, lc_bits = 0, ng = 0, max_quads = kResQuads;
     size_t lds = 0;
+    bool f32 = false;                     // laid out (LDS split, kernel) for float vectors: only resident_run<float> runs it
     const void *key[4] = {};
     int64_t key_n = -1;
     uint64_t key_epoch = 0;
@@ -862,27 +880,35 @@ static bool resident_wanted(bool distributed)
     return cur_opt().resident != 0; // default for every system that qualifies (plan: 1.5-2 ms per new matrix; AVS_CG_RESIDENT=0 keeps the launch-per-phase loops)
 }
 
-static const void *resident_kernel(int ng, bool streams)
+template <typename T> static const void *resident_kernel(int ng, bool streams)
 {
     // (streamed rows are a template parameter: their code costs the plain kernels 15 more spilled registers otherwise)
     switch (ng) {
-    case 0: return streams ? (const void *)k_cg_resident<0, true> : (const void *)k_cg_resident<0, false>;
-    case 1: return streams ? (const void *)k_cg_resident<1, true> : (const void *)k_cg_resident<1, false>;
-    case 2: return streams ? (const void *)k_cg_resident<2, true> : (const void *)k_cg_resident<2, false>;
-    default: return streams ? (const void *)k_cg_resident<3, true> : (const void *)k_cg_resident<3, false>;
+    case 0: return streams ? (const void *)k_cg_resident<0, true, T> : (const void *)k_cg_resident<0, false, T>;
+    case 1: return streams ? (const void *)k_cg_resident<1, true, T> : (const void *)k_cg_resident<1, false, T>;
+    case 2: return streams ? (const void *)k_cg_resident<2, true, T> : (const void *)k_cg_resident<2, false, T>;
+    default: return streams ? (const void *)k_cg_resident<3, true, T> : (const void *)k_cg_resident<3, false, T>;
     }
 }
+static const void *resident_kernel(int ng, bool streams, bool f32)
+{
+    return f32 ? resident_kernel<float>(ng, streams) : resident_kernel<double>(ng, streams);
+}
 
-// Builds (or re-uses) the plan for A; returns false (with plan->why) when the system does not qualify.
-static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols, const DirectArgs *da, hipStream_t stream)
+// Builds (or re-uses) the plan for A; returns false (with plan->why) when the system does not qualify.  f32: for the float-vector
+// kernel -- the LDS holds T = float slices, remote columns and tables, so the split and the tier are chosen for 4-B entries.
+static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols, const DirectArgs *da, bool f32, hipStream_t stream)
 {
     const void *key[4] = {A.row_ptr, A.packed, A.table, da ? (const void *)da->dd : nullptr};
-    if (pl->tried && memcmp(key, pl->key, sizeof(key)) == 0 && pl->key_n == A.n && pl->key_epoch == A.epoch) return pl->ok;
+    if (pl->tried && memcmp(key, pl->key, sizeof(key)) == 0 && pl->key_n == A.n && pl->key_epoch == A.epoch && pl->f32 == f32) return pl->ok;
     pl->key_epoch = A.epoch; // (a re-assembly with the same DOF count rewrites the same buffers: the words of the plan would be stale)
     pl->tried = true;
     pl->ok = false;
+    pl->f32 = f32;          // (part of the key: a plan laid out for one vector type never runs the other's kernel; switching the option
+                            // re-plans, which also tries the resident loop again after a fault retired the other plan)
     memcpy(pl->key, key, sizeof(key));
     pl->key_n = A.n;
+    const size_t esz = f32 ? sizeof(float) : sizeof(double); // LDS entry of the vector slices, remote columns and tables
     const bool verbose = cur_opt().resident_verbose > 0;
     timespec plan_t0{};
     clock_gettime(CLOCK_MONOTONIC, &plan_t0);
@@ -912,7 +938,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     if (cur_opt().resident_cus > 0 && cur_opt().resident_cus < cus) G = cur_opt().resident_cus; // tests: two ranks on ONE GPU, each on a share of the CUs
     // Cheap refusals first (before the row pointers cross PCIe and the host walks them: 20-100 ms at 4-7 M rows, per new matrix):
     // every workgroup keeps its slice of u in LDS next to its remote columns (never less than about half as much again)
-    if ((size_t)(n / G) * sizeof(double) > (size_t)(160 * 1024) * 65 / 100) return no("the workgroups' slices of u leave no room for their remote columns in the LDS");
+    if ((size_t)(n / G) * esz > (size_t)(160 * 1024) * 65 / 100) return no("the workgroups' slices of u leave no room for their remote columns in the LDS");
     std::vector<int32_t> rp((size_t)n + 1);
     if (hipMemcpyAsync(rp.data(), A.row_ptr, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
         hipStreamSynchronize(stream) != hipSuccess) {
@@ -1017,6 +1043,8 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     while ((1 << code_bits) < A.table_size + 1) ++code_bits; // + the zero the padding words address
     if (code_bits >= kResWordBits - 8) return no("dictionary needs too many bits");
     const size_t lds_max = 160 * 1024 - 4096 - 1024;
+    // the two tables (values + zero, inverted values) in T, then the fold space (3 x 16 wave sums) and 4 + 4 scalars in double
+    const size_t lds_extra = 2 * ((size_t)A.table_size + 1) * esz + (48 + 8) * sizeof(double);
     const int cap = stream_T > 0. ? 32768 : 16384; // stride of the per-workgroup source lists (a workgroup with more remote columns does not qualify)
     const int64_t n_ext = n_cols > n ? n_cols : n;
     int64_t chunk_cols = std::min<int64_t>(n_ext, kRemapChunk);
@@ -1054,7 +1082,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     size_t lds = 0;
     const char *last_reason = "the vector slices + remote columns of a workgroup do not fit the LDS";
     for (int max_ng = std::min(1, max_ng_limit); max_ng <= max_ng_limit && ng < 0; ++max_ng) {
-    if ((size_t)(4 - max_ng) * (size_t)(n / G) * sizeof(double) > lds_max) continue; // (even the average workgroup's slices would not fit)
+    if ((size_t)(4 - max_ng) * (size_t)(n / G) * esz > lds_max) continue; // (even the average workgroup's slices would not fit)
     std::fill(lane_w.begin(), lane_w.end(), 1.0);
     std::fill(lane_extra.begin(), lane_extra.end(), 0.);
     bool give_up = false, reweighted = false, extras_active = false, extras_off = false;
@@ -1123,7 +1151,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
             // a tier whose TOTAL demand is close to the chip's LDS never fits (lanes, not LDS, bound the split; every further round is a
             // re-encoding pass: 10 ms of plan time on a 1.3 M-row system): next tier
             const int t = max_ng < 3 ? (max_ng < 0 ? 0 : max_ng) : 3;
-            const double limit0 = (double)(lds_max - (2 * ((size_t)A.table_size + 1) + 48 + 8) * sizeof(double)) / sizeof(double);
+            const double limit0 = (double)(lds_max - lds_extra) / (double)esz;
             double demand = 0.;
             for (int b = 0; b < G; ++b) demand += (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b];
             if (demand > 0.88 * limit0 * (double)G) { give_up = true; break; }
@@ -1141,7 +1169,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
         }
         // LDS split: every workgroup holds its slice of u + its remote-column cache, and as many of r, p, s as still fit (tiers: NG =
         // 0 .. 3 of them in global memory instead).  Footprint of workgroup b: (4 - NG) rows_b + remote_b doubles; the largest decides.
-        const size_t extra = (2 * ((size_t)A.table_size + 1) + 48 + 8) * sizeof(double);
+        const size_t extra = lds_extra;
         max_cols = 0;
         for (int t = 0; t <= 3 && t <= max_ng && ng < 0; ++t) {
             size_t worst = 0;
@@ -1150,7 +1178,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
                 worst = std::max(worst, (size_t)(4 - t) * rows_b + rem_b);
                 max_cols = std::max(max_cols, (int)(rows_b + rem_b));
             }
-            const size_t need = worst * sizeof(double) + extra;
+            const size_t need = worst * esz + extra;
             if (verbose) fprintf(stderr, "[avs resident] round %d, LDS tier %d: largest workgroup footprint %zu B (limit %zu)\n", round, t, need, lds_max);
             if (need <= lds_max) { ng = t; lds = need; }
         }
@@ -1160,7 +1188,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
         }
         if (ng < 0) { // shrink the offenders (at the largest tier allowed) and split again
             const int t = max_ng < 3 ? (max_ng < 0 ? 0 : max_ng) : 3;
-            const double limit = (double)(lds_max - extra) / sizeof(double);
+            const double limit = (double)(lds_max - extra) / (double)esz;
             { // ... unless the MEDIAN workgroup does not fit either: no re-split helps, go to the next tier
                 std::vector<double> fps((size_t)G);
                 for (int b = 0; b < G; ++b) fps[(size_t)b] = (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b];
@@ -1188,7 +1216,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     if ((1 << lc_bits) < max_cols) return no("rows + remote columns exceed the word's column bits");
     lpw = 0;
     for (int b = 0; b < G; ++b) lpw = std::max<int64_t>(lpw, wl[(size_t)b + 1] - wl[(size_t)b]);
-    const void *kern = resident_kernel(ng, stream_words > 0);
+    const void *kern = resident_kernel(ng, stream_words > 0, f32);
     if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess) {
         (void)hipGetLastError();
         return no("LDS opt-in refused");
@@ -1284,7 +1312,8 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     }
     if (verbose)
         fprintf(stderr, "[avs resident] plan: n = %lld, %lld lanes (%lld per workgroup), %d workgroups, <= %d rows per workgroup, %d-bit local columns, "
-                        "%d row-local vectors in global memory, LDS %zu B\n", (long long)n, (long long)L, (long long)lpw, G, max_rows, lc_bits, ng, lds);
+                        "%d row-local vectors in global memory, LDS %zu B, %s vectors\n", (long long)n, (long long)L, (long long)lpw, G, max_rows, lc_bits, ng, lds,
+                f32 ? "float" : "fp64");
     pl->G = G;
     pl->lc_bits = lc_bits;
     pl->max_quads = max_quads;
@@ -1298,12 +1327,15 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
 // Runs the rest of the solve (state in sc / the vectors, as the set-up rounds left it) in ONE cooperative launch.
 // *launched = false: the cooperative launch was refused (the grid is not co-resident on this device right now); nothing was
 // touched, the plan is retired and the caller carries on with the launch-per-phase loop.
-static avs_status resident_run(ResidentPlan *pl, const CsrView &A, double *x, double *r, double *p, double *s, double *u, double *wv,
-                               const uint16_t *dcode, const double *invtab, PcgScalars *sc, int max_iters, const DirectArgs *da,
-                               hipStream_t stream, bool *launched)
+// T: the plan's vector type (resident_prepare's f32).
+template <typename T>
+static avs_status resident_run(ResidentPlan *pl, const CsrView &A, T *x, T *r, T *p, T *s, T *u, T *wv, const uint16_t *dcode,
+                               const T *invtab, PcgScalars *sc, int max_iters, const DirectArgs *da, hipStream_t stream, bool *launched)
 {
     *launched = false;
-    ResidentArgs a{};
+    constexpr bool F32 = std::is_same<T, float>::value;
+    AVS_REQUIRE(pl->f32 == F32, AVS_EINTERNAL, "the resident plan was laid out for the other vector type");
+    ResidentArgs<T> a{};
     a.row_ptr = A.row_ptr;
     a.table = A.table;
     a.table_size = A.table_size;
@@ -1363,7 +1395,7 @@ static avs_status resident_run(ResidentPlan *pl, const CsrView &A, double *x, do
     AVS_HIP(hipMemsetAsync(pl->slots.p, 0xFF, (size_t)pl->G * 4 * sizeof(double), stream));   // armed: kSentinel in every slot
     AVS_HIP(hipMemsetAsync(pl->bcast.p, 0xFF, 4 * kResGens * sizeof(double), stream));
     void *args[] = {&a};
-    const hipError_t le = hipLaunchCooperativeKernel(resident_kernel(pl->ng, pl->streams), dim3((unsigned)pl->G), dim3(kResThreads), args, (unsigned)pl->lds, stream);
+    const hipError_t le = hipLaunchCooperativeKernel(resident_kernel<T>(pl->ng, pl->streams), dim3((unsigned)pl->G), dim3(kResThreads), args, (unsigned)pl->lds, stream);
     if (le != hipSuccess) {
         (void)hipGetLastError();
         pl->ok = false;

@@ -97,8 +97,9 @@ typedef struct {
      * float CG does (round 5; dot products: a thread's terms in float, everything across threads in double -- Eigen's vectorised
      * reduction order is not reproduced): AVS_OPTION_F32_VECTORS = 1 always, -1 (default) for systems the CU-resident loop does not
      * take.  Partitioned solves (avs_dist_solve) iterate on float vectors in their single-reduction loops with
-     * AVS_OPTION_DIST_F32_VECTORS = 1, over both transports; by default, and always with AVS_DIST_CG=standard, in paranoid mode and
-     * in the CU-resident loop between ranks, they iterate in fp64 on the float system (at least as accurate, same stopping rule).
+     * AVS_OPTION_DIST_F32_VECTORS = 1, over both transports; by default, and always with AVS_DIST_CG=standard and in paranoid mode,
+     * they iterate in fp64 on the float system (at least as accurate, same stopping rule).  The CU-resident loop (single GPU and between
+     * ranks) iterates on float vectors with AVS_OPTION_RESIDENT_F32 = 1, in fp64 otherwise.
      * The solution is a float vector either way (Eigen::VectorXf). */
     int32_t precision;
 } avs_desc;
@@ -205,7 +206,8 @@ typedef enum {
                                    * SolveType = fpreal32 through Eigen::ConjugateGradient (util.h:25-37, cpp:613-630) --; 0 = fp64 iteration on
                                    * the float system; -1 (default) = float vectors where the system is too large for the CU-resident loop
                                    * (the bandwidth of the vectors is what an iteration costs there), the resident fp64 loop where it fits the
-                                   * chip (faster).  Takes effect at the next avs_assemble (the brick form's walk is laid out for the kernel
+                                   * chip (faster).  With AVS_OPTION_RESIDENT_F32 = 1, -1 and 1 both run the resident loop on float vectors where
+                                   * it takes the system.  Takes effect at the next avs_assemble (the brick form's walk is laid out for the kernel
                                    * that will run). */
     AVS_OPTION_FUSED_VECTOR_UPDATE = 9, /* single-GPU launch-per-phase loop: r -= alpha t and x += alpha p ; p = z + beta p as ONE launch with a grid barrier
                                    * in between -- the new r stays in registers / LDS, 7.25 n instead of 8.5 n doubles per iteration; same sums in the
@@ -213,12 +215,21 @@ typedef enum {
                                    * (>= 524,288 and <= 8,388,608 rows, a device with >= 256 CUs), -1 only systems larger than the Infinity Cache.
                                    * A barrier that is not passed within AVS_PCG_FUSED_TIMEOUT_MS (2000; the GPU shared with other work) redoes
                                    * the solve with the two launches.  Environment: AVS_PCG_FUSE_VECTORS. */
-    AVS_OPTION_DIST_F32_VECTORS = 10 /* AVS_PRECISION_F32 contexts, partitioned solves (avs_dist_solve): 1 = the single-reduction loops of both
+    AVS_OPTION_DIST_F32_VECTORS = 10, /* AVS_PRECISION_F32 contexts, partitioned solves (avs_dist_solve): 1 = the single-reduction loops of both
                                    * transports iterate on float vectors with float scalars, as the single-GPU AVS_OPTION_F32_VECTORS = 1 does (the
-                                   * CU-resident loop between ranks is then skipped); 0 (default) = fp64 iteration on the float system.  AVS_DIST_CG=standard
-                                   * and paranoid mode keep their fp64 loops.  No effect on AVS_PRECISION_F64 contexts.  Takes effect at the next
-                                   * avs_dist_partition / avs_dist_assemble (the local brick form's walk is laid out for the kernel that will run).
-                                   * Environment: AVS_DIST_F32_VECTORS. */
+                                   * CU-resident loop between ranks is then skipped, unless AVS_OPTION_RESIDENT_F32 = 1 runs it on float vectors);
+                                   * 0 (default) = fp64 iteration on the float system.  AVS_DIST_CG=standard and paranoid mode keep their fp64 loops.
+                                   * No effect on AVS_PRECISION_F64 contexts.  Takes effect at the next avs_dist_partition / avs_dist_assemble (the
+                                   * local brick form's walk is laid out for the kernel that will run).  Environment: AVS_DIST_F32_VECTORS. */
+    AVS_OPTION_RESIDENT_F32 = 12  /* (11 is not assigned: avs_set_solver_option rejects it.)  AVS_PRECISION_F32 contexts: 1 = the CU-resident
+                                   * loop iterates on float vectors with float scalars (float vector slices, remote columns and tables in LDS, float row sums, a thread's terms summed in float, everything across
+                                   * threads / workgroups / ranks in double) where it takes a system that would otherwise iterate on float vectors:
+                                   * single-GPU solves with AVS_OPTION_F32_VECTORS = -1 or 1, partitioned solves with AVS_OPTION_DIST_F32_VECTORS = 1
+                                   * (the latter latched at the next avs_dist_partition / avs_dist_assemble).  0 (default) = as before: the resident
+                                   * loop stays fp64, and float-vector solves use the launch-per-phase / single-reduction loops.  With
+                                   * AVS_OPTION_F32_VECTORS = 0, AVS_DIST_CG=standard or paranoid mode nothing changes.  Reported through
+                                   * avs_solve_info.resident and avs_matrix_format.float_vectors.  No effect on AVS_PRECISION_F64 contexts.
+                                   * Environment: AVS_RESIDENT_F32. */
 } avs_solver_option;
 enum { AVS_USE_TRANSPORT_AUTO = 0, AVS_USE_TRANSPORT_RCCL = 1, AVS_USE_TRANSPORT_DIRECT = 2 };
 enum { AVS_BRICK_AUTO = -1, AVS_BRICK_NEVER = 0, AVS_BRICK_ALWAYS = 1, AVS_BRICK_TUNE = 2 };
