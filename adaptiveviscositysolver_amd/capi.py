@@ -30,6 +30,7 @@ PRECISION_F64, PRECISION_F32 = 0, 1   # avs_desc.precision (SolveType of the ref
  OPTION_FUSED_SCALAR_STEPS, OPTION_RELOAD_ENVIRONMENT, OPTION_F32_VECTORS, OPTION_FUSED_VECTOR_UPDATE,
  OPTION_DIST_F32_VECTORS) = range(11)  # avs_set_solver_option
 OPTION_RESIDENT_F32 = 12   # (11 is not assigned)
+OPTION_RESIDENT_LOCAL_TABLES = 13
 USE_TRANSPORT_AUTO, USE_TRANSPORT_RCCL, USE_TRANSPORT_DIRECT = 0, 1, 2
 BRICK_AUTO, BRICK_NEVER, BRICK_ALWAYS, BRICK_TUNE = -1, 0, 1, 2
 PRECONDITIONER_JACOBI, PRECONDITIONER_NONE = 0, 1

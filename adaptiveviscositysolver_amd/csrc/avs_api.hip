@@ -112,6 +112,7 @@ Options options_from_env()
     { const int v = env_int("AVS_F32_VECTORS", -1); o.f32_vectors = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.dist_f32_vectors = env_int("AVS_DIST_F32_VECTORS", 0) != 0;
     o.resident_f32 = env_int("AVS_RESIDENT_F32", 0) != 0;
+    o.resident_local_tables = env_int("AVS_RESIDENT_LOCAL_TABLES", 0) != 0;
     o.prepass_temporal = env_int("AVS_PREPASS_TEMPORAL", 1) != 0;
     { const int v = env_int("AVS_POST_DOF_SAMPLE", -1); o.post_dof_sample = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.resident_cus = env_int("AVS_CG_RESIDENT_CUS", 0);
@@ -672,6 +673,7 @@ avs_status avs_set_solver_option(avs_ctx *c, avs_solver_option option, int32_t v
     case AVS_OPTION_FUSED_VECTOR_UPDATE: c->opt.fuse_vectors = value < 0 ? -1 : (value > 0 ? 1 : 0); return AVS_OK;
     case AVS_OPTION_DIST_F32_VECTORS: c->opt.dist_f32_vectors = value != 0; return AVS_OK;
     case AVS_OPTION_RESIDENT_F32: c->opt.resident_f32 = value != 0; return AVS_OK;
+    case AVS_OPTION_RESIDENT_LOCAL_TABLES: c->opt.resident_local_tables = value != 0; return AVS_OK;
     }
     set_error("unknown solver option %d", (int)option);
     return AVS_EINVAL;

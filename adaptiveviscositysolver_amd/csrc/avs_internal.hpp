@@ -119,6 +119,8 @@ struct Options {
     int resident_f32 = 0;        // AVS_RESIDENT_F32: the CU-resident loop iterates on float vectors where it takes a float-vector solve
                                  // (k_cg_resident<.., float>): single GPU with f32_vectors != 0, partitioned with dist_f32_vectors (latched
                                  // with it: PcgDist::resident_f32)
+    int resident_local_tables = 0; // AVS_RESIDENT_LOCAL_TABLES: the CU-resident loop takes matrices without one small dictionary too, with a value
+                                 // table per workgroup / per wave built by the plan (k_resident_local_tables)
     // CU-resident loop: tuning and test switches
     int resident_cus = 0, resident_equal_lanes = 0, resident_max_global = 3, resident_max_quads = 0, resident_no_stream = 0;
     long long resident_remap_chunk = 0;

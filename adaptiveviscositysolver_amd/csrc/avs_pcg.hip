@@ -2356,11 +2356,15 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
     // vectors with AVS_OPTION_RESIDENT_F32 (k_cg_resident<.., float>: the same state, the same scalar step as this loop).
     w->resident_used = 0;
     if (!F32 || A.resident_f32) {
-        if (coded && (da.exclusive_device || cur_opt().resident_cus > 0) && resident_wanted(true)) {
+        // (AVS_OPTION_RESIDENT_LOCAL_TABLES: also a matrix without one small dictionary, with the per-row inverse this set-up made --
+        // the float set-up of a coded matrix makes none: no resident loop then)
+        const bool local = resident_local_tables_wanted(A);
+        if ((local ? v.invd != nullptr : coded) && (da.exclusive_device || cur_opt().resident_cus > 0) && resident_wanted(true)) {
             if (!w->resident) w->resident = new (std::nothrow) ResidentPlan();
             if (w->resident && resident_prepare(w->resident, A, w->n_ext, &da, F32, stream)) {
                 bool launched = false;
-                AVS_TRY(resident_run<T>(w->resident, A, v.x, v.r, v.p, v.s, v.u, v.w, v.dcode, v.invtab, sc, max_iters, &da, stream, &launched));
+                AVS_TRY(resident_run<T>(w->resident, A, v.x, v.r, v.p, v.s, v.u, v.w, v.dcode, w->resident->local ? v.invd : v.invtab, sc, max_iters, &da,
+                                        stream, &launched));
                 w->resident_used = launched ? 1 : 0; // (refused: the loop below takes over from the same state)
             }
         }
@@ -2483,7 +2487,10 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
     *ran = false;
     const int64_t n = A.n;
     const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable;
-    if (!coded) return AVS_OK;
+    // AVS_OPTION_RESIDENT_LOCAL_TABLES: a matrix without one small dictionary is planned with local value tables; its set-up is the
+    // uncoded one (one inverse per row, which the loop then reads)
+    const bool local = resident_local_tables_wanted(A);
+    if (!coded && !local) return AVS_OK;
     if (!w->resident) w->resident = new (std::nothrow) ResidentPlan();
     if (cancel_requested()) return AVS_OK; // (the launch-per-phase loop consumes the request at its first poll: 0 iterations, cancelled = 1)
     if (!w->resident || !resident_prepare(w->resident, A, A.n, nullptr, F32, stream)) return AVS_OK;
@@ -2493,13 +2500,14 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
         AVS_TRY(ensure_partials(w, 4 * (size_t)kVecGrid + nb_max + 16));
     }
     SrVecs<T> v;
-    AVS_TRY(sr_setup_exchange(w, A, b, x, tol, true, nullptr, &v, stream));
+    AVS_TRY(sr_setup_exchange(w, A, b, x, tol, !w->resident->local, nullptr, &v, stream));
     // the initial guess is kept: if a bounded wait inside the cooperative launch times out (the grid was not co-resident in time: a GPU
     // shared with a viewport or OpenCL work) the solve is redone from it by the launch-per-phase loop IN THIS CALL
     AVS_TRY(w->x_save.alloc((size_t)n));
     AVS_HIP(hipMemcpyAsync(w->x_save.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     bool launched = false;
-    AVS_TRY(resident_run<T>(w->resident, A, v.x, v.r, v.p, v.s, v.u, v.w, v.dcode, v.invtab, w->sc.p, max_iters, nullptr, stream, &launched));
+    AVS_TRY(resident_run<T>(w->resident, A, v.x, v.r, v.p, v.s, v.u, v.w, v.dcode, w->resident->local ? v.invd : v.invtab, w->sc.p, max_iters, nullptr,
+                            stream, &launched));
     if (!launched) return AVS_OK; // (x is untouched: the launch-per-phase loop starts over from it)
     AVS_TRY(poll_scalars(w, w->sc.p, stream));
     bool faulted = w->host_sc->fault != 0;

@@ -22,6 +22,10 @@
 // as float: exact, the float system's values are floats; the inverse diagonal inverted in float, k_f32_invtab), float row sums, a
 // thread's own terms of the dot products in T and everything across threads, workgroups and ranks in double, the scalar step
 // sr_step_sums<float> on the float-rounded sums.  Halo entries travel widened to double (exact): the comm block is the same.
+// LT, local value tables (AVS_OPTION_RESIDENT_LOCAL_TABLES, opt-in): a matrix without one dictionary of <= 1,023 values (a viscosity /
+// density field; tile-local tables, column windows, 6-B or 12-B words at the assembly) gets a value table per workgroup -- per wave where
+// a workgroup's code bits do not fit the 25-bit word -- built by the plan from the plain CSR values (k_resident_local_tables), and reads
+// one inverse of the diagonal per row (the launch-per-phase loops' array) instead of a code and a second table.  Same row sums.
 // Every wait is bounded (wall_clock64): a missing workgroup / peer ends the kernel with sc->fault set, never a hung GPU.
 // Not used when two ranks share one physical GPU (two kernels that each need every CU cannot wait for each other).
 
@@ -100,6 +104,14 @@ template <typename T> struct ResidentArgs {
     int max_timed;
     int coherent_fill;                    // 1: the remote columns are read with agent / system scope loads and L2 is NOT invalidated (see phase B)
     long long *wg_times;                  // optional: G x 4 stamps of every workgroup in iteration 20 (start, update done, fill done, SpMV done)
+    // LOCAL VALUE TABLES (the LT kernels, AVS_OPTION_RESIDENT_LOCAL_TABLES; appended: the offsets above are those of every other kernel):
+    // a word's code indexes the table of the GROUP its row belongs to -- the whole workgroup (ltab_gpw = 1) or the wave that sums the
+    // row (16) --, the distinct value bit patterns of the group's rows in ascending order, entry 0 = +0 (what the padding words
+    // multiply with: table_size is 0 there).  `table` then holds the groups' tables back to back, and `invtab` ONE INVERSE
+    // PER ROW (the launch-per-phase loops' k_inv_diag / k_f32_inv_diag array: no LDS at all; dcode is not read)
+    const int32_t *ltab_cnt;              // G x ltab_gpw: entries of every group's table
+    const int32_t *ltab_off;              // ... and where it starts in `table` (G x ltab_gpw + 1)
+    int ltab_gpw;
 };
 
 // Loop-body reads of the kernel arguments go through these: one scalar load from the kernarg segment AT THE USE.  Left to itself the
@@ -196,7 +208,11 @@ __device__ __forceinline__ void res_block_fold3(double &v0, double &v1, double &
 // per iteration on the workgroups that read 8 k halo entries) and the numbering is deterministic.
 static constexpr int kRemapBlock = 16; // bitmap words per prefix block
 static constexpr int kRemapChunk = 1 << 20; // columns per bitmap pass (128 KiB of LDS + 8 KiB of block prefixes): larger slabs take several passes
-__global__ __launch_bounds__(kResThreads) void k_resident_remap(const uint32_t *__restrict__ packed, const int32_t *__restrict__ row_ptr, int col_bits,
+// PLAIN (local value tables): the columns come from the plain CSR (`cols`; no packed words needed) and the code part is left 0 for
+// k_resident_local_tables to fill in.
+template <bool PLAIN>
+__global__ __launch_bounds__(kResThreads) void k_resident_remap(const uint32_t *__restrict__ packed, const int32_t *__restrict__ cols,
+                                                                const int32_t *__restrict__ row_ptr, int col_bits,
                                                                 int lc_bits, const int32_t *__restrict__ wg_row0, int rem_cap, int n_ext,
                                                                 uint32_t *__restrict__ rwords, int32_t *__restrict__ rem_list,
                                                                 int32_t *__restrict__ rem_count, int *__restrict__ fail, int n_own,
@@ -207,8 +223,14 @@ __global__ __launch_bounds__(kResThreads) void k_resident_remap(const uint32_t *
     const int b = blockIdx.x, tid = threadIdx.x;
     const int r0 = wg_row0[b], r1 = wg_row0[b + 1];
     const int k0 = row_ptr[r0], k1 = row_ptr[r1];
-    const unsigned cmask = (1u << col_bits) - 1u;
+    const unsigned cmask = PLAIN ? 0u : (1u << col_bits) - 1u;
     const int wrows = r1 - r0;
+    auto col_of = [&](int k, uint32_t *code) { // column of word k, its value code already at the local word's position
+        if (PLAIN) { *code = 0u; return (int)cols[k]; }
+        const uint32_t wd = packed[k];
+        *code = (wd >> col_bits) << lc_bits;
+        return (int)(wd & cmask);
+    };
     if (tid < 32) deps[tid] = 0u;
     int base = 0; // remote slots handed out by the chunks below this one (ascending columns overall)
     for (int c0 = 0; c0 < n_ext; c0 += chunk) {
@@ -218,7 +240,8 @@ __global__ __launch_bounds__(kResThreads) void k_resident_remap(const uint32_t *
         for (int i = tid; i < nb * kRemapBlock; i += kResThreads) bm[i] = 0u;
         __syncthreads();
         for (int k = k0 + tid; k < k1; k += kResThreads) {
-            const int col = (int)(packed[k] & cmask);
+            uint32_t code;
+            const int col = col_of(k, &code);
             if ((col < r0 || col >= r1) && col >= c0 && col < c1) atomicOr(&bm[(col - c0) >> 5], 1u << ((col - c0) & 31));
         }
         __syncthreads();
@@ -268,10 +291,9 @@ __global__ __launch_bounds__(kResThreads) void k_resident_remap(const uint32_t *
                 }
             }
         for (int k = k0 + tid; k < k1; k += kResThreads) {
-            const uint32_t wd = packed[k];
-            const int col = (int)(wd & cmask);
-            if ((col < r0 || col >= r1) && col >= c0 && col < c1)
-                rwords[k] = ((wd >> col_bits) << lc_bits) | (uint32_t)(wrows + base + slot_of(col - c0));
+            uint32_t code;
+            const int col = col_of(k, &code);
+            if ((col < r0 || col >= r1) && col >= c0 && col < c1) rwords[k] = code | (uint32_t)(wrows + base + slot_of(col - c0));
         }
         base += total;
         __syncthreads(); // the bitmap is cleared for the next chunk
@@ -282,11 +304,84 @@ __global__ __launch_bounds__(kResThreads) void k_resident_remap(const uint32_t *
     }
     if (tid < 32) dep_mask[(size_t)b * 32 + tid] = deps[tid];
     for (int k = k0 + tid; k < k1; k += kResThreads) { // the workgroup's own rows (and anything past the local columns: never read)
-        const uint32_t wd = packed[k];
-        const int col = (int)(wd & cmask);
-        if (col >= r0 && col < r1) rwords[k] = ((wd >> col_bits) << lc_bits) | (uint32_t)(col - r0);
-        else if (col >= n_ext) rwords[k] = (wd >> col_bits) << lc_bits;
+        uint32_t code;
+        const int col = col_of(k, &code);
+        if (col >= r0 && col < r1) rwords[k] = code | (uint32_t)(col - r0);
+        else if (col >= n_ext) rwords[k] = code;
     }
+}
+
+// Plan kernel of the local value tables, after k_resident_remap<true>: workgroup b collects, group by group (its whole row range, or
+// the rows of each of its 16 waves: tg_row0), the distinct BIT PATTERNS of the group's values -- an LDS hash set, so what it holds does
+// not depend on the order of arrival --, sorts them ascending as unsigned 64-bit integers (bitonic, in place: the empty slots, all
+// ones, end up last; +0 is always a member and therefore entry 0), writes the table and gives every word of the group its code by
+// binary search.  Deterministic: the same matrix and split give the same tables and words in every context.
+// ltab_cnt[group] > tcap: the group has more distinct values than a table holds (its words are left without codes).
+static constexpr unsigned long long kLtEmpty = ~0ull; // (a NaN: never a matrix value -- one that is counts as an overflow)
+__global__ __launch_bounds__(kResThreads) void k_resident_local_tables(const double *__restrict__ val, const int32_t *__restrict__ row_ptr,
+                                                                       const int32_t *__restrict__ tg_row0, int gpw, int tcap, int lc_bits,
+                                                                       uint32_t *__restrict__ rwords, double *__restrict__ ltab,
+                                                                       int32_t *__restrict__ ltab_cnt)
+{
+    extern __shared__ unsigned long long hs[]; // 2 * tcap slots (tcap >= 1024: the count may pass tcap by one insertion per thread)
+    __shared__ int cnt;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int slots = 2 * tcap;
+    const unsigned hmask = (unsigned)slots - 1u, cmask = (1u << lc_bits) - 1u;
+    for (int g = 0; g < gpw; ++g) {
+        const int grp = b * gpw + g;
+        const int k0 = row_ptr[tg_row0[grp]], k1 = row_ptr[tg_row0[grp + 1]];
+        for (int i = tid; i < slots; i += kResThreads) hs[i] = kLtEmpty;
+        if (tid == 0) { hs[0] = 0ull; cnt = 1; } // +0 hashes to slot 0
+        __syncthreads();
+        for (int k = k0 + tid; k < k1; k += kResThreads) {
+            if (*(volatile int *)&cnt > tcap) break; // overflow: reported below
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(val[k]);
+            if (bits == kLtEmpty) { atomicAdd(&cnt, slots); break; }
+            unsigned h = (unsigned)((bits * 0x9E3779B97F4A7C15ull) >> 40) & hmask;
+            for (int probe = 0; probe < slots; ++probe) {
+                const unsigned long long old = atomicCAS(&hs[h], kLtEmpty, bits);
+                if (old == kLtEmpty) { atomicAdd(&cnt, 1); break; }
+                if (old == bits) break;
+                h = (h + 1u) & hmask;
+            }
+        }
+        __syncthreads();
+        const int nv = cnt;
+        if (nv <= tcap) {
+            for (int k = 2; k <= slots; k <<= 1)
+                for (int j = k >> 1; j > 0; j >>= 1) {
+                    for (int i = tid; i < slots; i += kResThreads) {
+                        const int o = i ^ j;
+                        if (o > i) {
+                            const unsigned long long x = hs[i], y = hs[o];
+                            if ((x > y) == ((i & k) == 0)) { hs[i] = y; hs[o] = x; }
+                        }
+                    }
+                    __syncthreads();
+                }
+            for (int i = tid; i < nv; i += kResThreads) ltab[(size_t)grp * tcap + i] = __longlong_as_double((long long)hs[i]);
+            for (int k = k0 + tid; k < k1; k += kResThreads) {
+                const unsigned long long bits = (unsigned long long)__double_as_longlong(val[k]);
+                int lo = 0, hi = nv - 1; // hs[lo] <= bits <= hs[hi]
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (hs[mid] < bits) lo = mid + 1;
+                    else hi = mid;
+                }
+                rwords[k] = (rwords[k] & cmask) | ((uint32_t)lo << lc_bits);
+            }
+        }
+        if (tid == 0) ltab_cnt[grp] = nv;
+        __syncthreads(); // the set is cleared for the next group
+    }
+}
+// ... and of the accepted plan: the tables, tcap entries apart while their sizes were not known, back to back (block = group)
+__global__ __launch_bounds__(256) void k_resident_pack_tables(const double *__restrict__ src, int tcap, const int32_t *__restrict__ off,
+                                                              double *__restrict__ dst)
+{
+    const int grp = blockIdx.x, o = off[grp], c = off[grp + 1] - o;
+    for (int i = threadIdx.x; i < c; i += 256) dst[(size_t)o + i] = src[(size_t)grp * tcap + i];
 }
 
 // Plan kernel for STREAMED rows: thread = lane; packs the re-encoded words of the lane's streamed rows into quads (five 25-bit words, a
@@ -336,7 +431,8 @@ template <typename T> struct ResVec16;           // 16 B of T: the unit of the w
 template <> struct ResVec16<double> { typedef d2_t type; };
 template <> struct ResVec16<float> { typedef f4_t type; };
 
-template <int NG, bool STREAM, typename T>
+// LT: local value tables (ResidentArgs::ltab_cnt): every wave reads the table of its group, the inverse diagonal comes per row.
+template <int NG, bool STREAM, typename T, bool LT = false>
 __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
 {
     extern __shared__ __attribute__((aligned(16))) double rlds[];
@@ -351,7 +447,18 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
     T *s_l = p_l + (NG < 2 ? wrows_al : 0);
     T *tbl = s_l + (NG < 1 ? wrows_al : 0); // table_size values + one zero (what the padding words multiply with)
     T *itab = tbl + a.table_size + 1;          // table_size + 1 inverted values
-    double *fold = reinterpret_cast<double *>(itab + a.table_size + 1); // 3 x 16 wave sums
+    int lt_off = 0, lt_total = 0;              // LT: the wave's table inside the workgroup's (in entries), all of them (even)
+    if constexpr (LT) {
+        const int gpw = a.ltab_gpw, myg = (int)((threadIdx.x >> 6) * (unsigned)gpw) >> 4;
+        for (int g = 0; g < gpw; ++g) {
+            const int c = a.ltab_cnt[blockIdx.x * gpw + g];
+            if (g < myg) lt_off += c;
+            lt_total += c;
+        }
+        lt_off = __builtin_amdgcn_readfirstlane(lt_off);
+        lt_total = (lt_total + 1) & ~1;
+    }
+    double *fold = reinterpret_cast<double *>(LT ? tbl + lt_total : itab + a.table_size + 1); // 3 x 16 wave sums
     double *bc = fold + 48;                                              // 4 rank sums + 4 broadcast scalars
     __shared__ int sh_fail;
     __shared__ double rank_all[kMaxRanks * 4];
@@ -414,10 +521,20 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
         if (NG < 2) p_l[i] = a.p[wrow0 + i];
         if (NG < 1) s_l[i] = a.s[wrow0 + i];
     }
+    if constexpr (LT) { // the groups' tables, back to back (entry 0 of each: the zero)
+        int off = 0;
+        for (int g = 0; g < a.ltab_gpw; ++g) {
+            const int grp = b * a.ltab_gpw + g, c = a.ltab_cnt[grp];
+            const double *src = a.table + a.ltab_off[grp];
+            for (int i = tid; i < c; i += kResThreads) tbl[off + i] = (T)src[i];
+            off += c;
+        }
+    } else
     for (int i = tid; i <= a.table_size; i += kResThreads) {
         tbl[i] = i < a.table_size ? (T)a.table[i] : (T)0;
         itab[i] = a.invtab[i];
     }
+    const T *const tblw = LT ? tbl + lt_off : tbl; // the table this wave's words index
     if (tid == 0) sh_fail = 0;
     __syncthreads();
     const unsigned cmask = (1u << a.lc_bits) - 1u;
@@ -464,17 +581,20 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
             const res_gptr<T> gx = RES_G(x) + wrow0, gp = NG >= 2 ? RES_G(p) + wrow0 : nullptr, gr = NG >= 3 ? RES_G(r) + wrow0 : nullptr;
             const res_gptr<T> gs = NG >= 1 ? RES_G(s) + wrow0 : nullptr;
             const res_gptr<const T> gw = RES_G(w) + wrow0;
-            const res_gptr<const uint16_t> gd = RES_G(dcode) + wrow0;
+            const res_gptr<const uint16_t> gd = LT ? nullptr : RES_G(dcode) + wrow0;
+            const res_gptr<const T> gi = LT ? RES_G(invtab) + wrow0 : nullptr; // (LT: one inverse per row)
             for (int i0 = tid; i0 < wrows; i0 += kResUpd * kResThreads) {
                 T xv[kResUpd], wv[kResUpd], sv[kResUpd], pv[kResUpd], rv[kResUpd];
                 unsigned dv[kResUpd];
+                T iv[kResUpd];
 #pragma unroll
                 for (int j = 0; j < kResUpd; ++j) {
                     const int i = i0 + j * kResThreads;
                     if (i < wrows) {
                         if (!skip_x) xv[j] = gx[i];
                         wv[j] = gw[i];
-                        dv[j] = gd[i];
+                        if constexpr (LT) iv[j] = gi[i];
+                        else dv[j] = gd[i];
                         if (NG >= 1) sv[j] = gs[i];
                         if (NG >= 2) pv[j] = gp[i];
                         if (NG >= 3) rv[j] = gr[i];
@@ -495,7 +615,9 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
                         const T ri = (NG >= 3 ? rv[j] : r_l[i]) - al * si;
                         if (NG >= 3) gr[i] = ri;
                         else r_l[i] = ri;
-                        const T ui = itab[dv[j]] * ri;
+                        T ui;
+                        if constexpr (LT) ui = iv[j] * ri;
+                        else ui = itab[dv[j]] * ri;
                         u_l[i] = ui;
                         ru += ri * ui;
                         rr += ri * ri;
@@ -630,8 +752,8 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
                     { // words 0, 1 (three groups with scheduling barriers between them: ten reads in flight at once need 20 more
                       // registers than the file has next to the 60 of the matrix, and the allocator then parks the MATRIX in scratch)
                         const unsigned t1 = __builtin_amdgcn_alignbit(mm.y, mm.x, 25);
-                        const T v0 = tbl[__builtin_amdgcn_ubfe(mm.x, (unsigned)cbits, kb)], x0 = u_l[mm.x & cmask];
-                        const T v1 = tbl[__builtin_amdgcn_ubfe(t1, (unsigned)cbits, kb)], x1 = u_l[t1 & cmask];
+                        const T v0 = tblw[__builtin_amdgcn_ubfe(mm.x, (unsigned)cbits, kb)], x0 = u_l[mm.x & cmask];
+                        const T v1 = tblw[__builtin_amdgcn_ubfe(t1, (unsigned)cbits, kb)], x1 = u_l[t1 & cmask];
                         acc += v0 * x0; // left to right inside the row, multiply then add (no FMA): the oracle's order and rounding, the same
                                         // row sums as the launch-per-phase kernels bit for bit (padding words add +0)
                         acc += v1 * x1;
@@ -640,14 +762,14 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
                     { // words 2, 3
                         const unsigned t2 = __builtin_amdgcn_alignbit(mm.z, mm.y, 18);
                         const unsigned t3 = __builtin_amdgcn_alignbit(mm.w, mm.z, 11);
-                        const T v2 = tbl[__builtin_amdgcn_ubfe(t2, (unsigned)cbits, kb)], x2 = u_l[t2 & cmask];
-                        const T v3 = tbl[__builtin_amdgcn_ubfe(t3, (unsigned)cbits, kb)], x3 = u_l[t3 & cmask];
+                        const T v2 = tblw[__builtin_amdgcn_ubfe(t2, (unsigned)cbits, kb)], x2 = u_l[t2 & cmask];
+                        const T v3 = tblw[__builtin_amdgcn_ubfe(t3, (unsigned)cbits, kb)], x3 = u_l[t3 & cmask];
                         acc += v2 * x2;
                         acc += v3 * x3;
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     { // word 4
-                        const T v4 = tbl[__builtin_amdgcn_ubfe(mm.w, 4u + (unsigned)cbits, kb)], x4 = u_l[__builtin_amdgcn_ubfe(mm.w, 4u, (unsigned)cbits)];
+                        const T v4 = tblw[__builtin_amdgcn_ubfe(mm.w, 4u + (unsigned)cbits, kb)], x4 = u_l[__builtin_amdgcn_ubfe(mm.w, 4u, (unsigned)cbits)];
                         acc += v4 * x4;
                     }
                     if ((em >> q) & 1u) {
@@ -664,7 +786,7 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
                 const res_gptr<const uint32_t> twords = RES_G(rwords);
                 for (int k = kt; k < kt + tail; ++k) {
                     const uint32_t wd = twords[k];
-                    acc += tbl[wd >> cbits] * u_l[wd & cmask];
+                    acc += tblw[wd >> cbits] * u_l[wd & cmask];
                 }
                 gw[row0] = acc;
                 wu += acc * u_l[row0 - wrow0];
@@ -703,11 +825,11 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
                         const unsigned t1 = __builtin_amdgcn_alignbit(mm.y, mm.x, 25);
                         const unsigned t2 = __builtin_amdgcn_alignbit(mm.z, mm.y, 18);
                         const unsigned t3 = __builtin_amdgcn_alignbit(mm.w, mm.z, 11);
-                        const T v0 = tbl[__builtin_amdgcn_ubfe(mm.x, (unsigned)cbits, kb)], x0 = u_l[mm.x & cmask];
-                        const T v1 = tbl[__builtin_amdgcn_ubfe(t1, (unsigned)cbits, kb)], x1 = u_l[t1 & cmask];
-                        const T v2 = tbl[__builtin_amdgcn_ubfe(t2, (unsigned)cbits, kb)], x2 = u_l[t2 & cmask];
-                        const T v3 = tbl[__builtin_amdgcn_ubfe(t3, (unsigned)cbits, kb)], x3 = u_l[t3 & cmask];
-                        const T v4 = tbl[__builtin_amdgcn_ubfe(mm.w, 4u + (unsigned)cbits, kb)], x4 = u_l[__builtin_amdgcn_ubfe(mm.w, 4u, (unsigned)cbits)];
+                        const T v0 = tblw[__builtin_amdgcn_ubfe(mm.x, (unsigned)cbits, kb)], x0 = u_l[mm.x & cmask];
+                        const T v1 = tblw[__builtin_amdgcn_ubfe(t1, (unsigned)cbits, kb)], x1 = u_l[t1 & cmask];
+                        const T v2 = tblw[__builtin_amdgcn_ubfe(t2, (unsigned)cbits, kb)], x2 = u_l[t2 & cmask];
+                        const T v3 = tblw[__builtin_amdgcn_ubfe(t3, (unsigned)cbits, kb)], x3 = u_l[t3 & cmask];
+                        const T v4 = tblw[__builtin_amdgcn_ubfe(mm.w, 4u + (unsigned)cbits, kb)], x4 = u_l[__builtin_amdgcn_ubfe(mm.w, 4u, (unsigned)cbits)];
                         sacc += v0 * x0;
                         sacc += v1 * x1;
                         sacc += v2 * x2;
@@ -856,6 +978,11 @@ struct ResidentPlan {
     DevBuf<int32_t> lane_row0, wg_lane0, wg_row0, push_seg, rem_list, rem_count;
     DevBuf<uint32_t> lane_meta, rwords, swords;
     DevBuf<int32_t> wave_soff;
+    // local value tables (AVS_OPTION_RESIDENT_LOCAL_TABLES): the plan of a matrix without one small dictionary
+    bool local = false, key_local = false; // this plan uses them; the option it was built (or refused) under
+    DevBuf<double> ltab;                  // G x lt_gpw tables, back to back
+    DevBuf<int32_t> ltab_cnt, ltab_off, tg_row0; // entries per table, its offset in ltab; row boundaries of the groups (G x lt_gpw + 1)
+    int lt_gpw = 1;                       // tables per workgroup: 1, or 16 (one per wave)
     bool streams = false;
     DevBuf<unsigned long long> bar_flags;
     DevBuf<unsigned> dep_mask;
@@ -880,19 +1007,34 @@ static bool resident_wanted(bool distributed)
     return cur_opt().resident != 0; // default for every system that qualifies (plan: 1.5-2 ms per new matrix; AVS_CG_RESIDENT=0 keeps the launch-per-phase loops)
 }
 
-template <typename T> static const void *resident_kernel(int ng, bool streams)
+// the system is one the ordinary plan takes as far as its dictionary goes: the packed single-dictionary form, <= 1,023 values
+static bool resident_single_dictionary(const CsrView &A)
+{
+    return A.packed && A.codes && !A.tab_ptr && !A.cbase && A.col_bits > 0 && A.table_size <= 1023;
+}
+// ... or one that AVS_OPTION_RESIDENT_LOCAL_TABLES sends through the plan with local value tables (from the plain CSR)
+static bool resident_local_tables_wanted(const CsrView &A)
+{
+    return cur_opt().resident_local_tables != 0 && !resident_single_dictionary(A) && A.val && A.col;
+}
+
+template <typename T, bool LT> static const void *resident_kernel(int ng, bool streams)
 {
     // (streamed rows are a template parameter: their code costs the plain kernels 15 more spilled registers otherwise)
     switch (ng) {
-    case 0: return streams ? (const void *)k_cg_resident<0, true, T> : (const void *)k_cg_resident<0, false, T>;
-    case 1: return streams ? (const void *)k_cg_resident<1, true, T> : (const void *)k_cg_resident<1, false, T>;
-    case 2: return streams ? (const void *)k_cg_resident<2, true, T> : (const void *)k_cg_resident<2, false, T>;
-    default: return streams ? (const void *)k_cg_resident<3, true, T> : (const void *)k_cg_resident<3, false, T>;
+    case 0: return streams ? (const void *)k_cg_resident<0, true, T, LT> : (const void *)k_cg_resident<0, false, T, LT>;
+    case 1: return streams ? (const void *)k_cg_resident<1, true, T, LT> : (const void *)k_cg_resident<1, false, T, LT>;
+    case 2: return streams ? (const void *)k_cg_resident<2, true, T, LT> : (const void *)k_cg_resident<2, false, T, LT>;
+    default: return streams ? (const void *)k_cg_resident<3, true, T, LT> : (const void *)k_cg_resident<3, false, T, LT>;
     }
 }
-static const void *resident_kernel(int ng, bool streams, bool f32)
+template <typename T> static const void *resident_kernel(int ng, bool streams, bool local)
 {
-    return f32 ? resident_kernel<float>(ng, streams) : resident_kernel<double>(ng, streams);
+    return local ? resident_kernel<T, true>(ng, streams) : resident_kernel<T, false>(ng, streams);
+}
+static const void *resident_kernel(int ng, bool streams, bool f32, bool local)
+{
+    return f32 ? resident_kernel<float>(ng, streams, local) : resident_kernel<double>(ng, streams, local);
 }
 
 // Builds (or re-uses) the plan for A; returns false (with plan->why) when the system does not qualify.  f32: for the float-vector
@@ -900,7 +1042,12 @@ static const void *resident_kernel(int ng, bool streams, bool f32)
 static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols, const DirectArgs *da, bool f32, hipStream_t stream)
 {
     const void *key[4] = {A.row_ptr, A.packed, A.table, da ? (const void *)da->dd : nullptr};
-    if (pl->tried && memcmp(key, pl->key, sizeof(key)) == 0 && pl->key_n == A.n && pl->key_epoch == A.epoch && pl->f32 == f32) return pl->ok;
+    const bool opt_local = cur_opt().resident_local_tables != 0; // (part of the key, like the vector type: switching the option plans again)
+    if (pl->tried && memcmp(key, pl->key, sizeof(key)) == 0 && pl->key_n == A.n && pl->key_epoch == A.epoch && pl->f32 == f32 &&
+        pl->key_local == opt_local)
+        return pl->ok;
+    pl->key_local = opt_local;
+    pl->local = false;
     pl->key_epoch = A.epoch; // (a re-assembly with the same DOF count rewrites the same buffers: the words of the plan would be stale)
     pl->tried = true;
     pl->ok = false;
@@ -925,8 +1072,12 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
         if (verbose) fprintf(stderr, "[avs resident] not used: %s (n = %lld)\n", why, (long long)A.n);
         return false;
     };
-    if (!A.packed || !A.codes || A.tab_ptr || A.cbase || A.col_bits <= 0) return no("needs the packed single-dictionary form");
-    if (A.table_size > 1023 || A.n < 1 || A.n >= (1ll << 31)) return no("dictionary too large");
+    // lt: a matrix that fails only these two dictionary conditions is planned with local value tables when the option asks for it
+    const bool lt = resident_local_tables_wanted(A);
+    if (!lt && (!A.packed || !A.codes || A.tab_ptr || A.cbase || A.col_bits <= 0)) return no("needs the packed single-dictionary form");
+    if ((!lt && A.table_size > 1023) || A.n < 1 || A.n >= (1ll << 31)) return no("dictionary too large");
+    std::string lt_why; // the quantity of a local-table plan that did not fit
+    DevBuf<double> lt_strided; // the tables while the plan is being made: lt_cap entries apart
     int dev = 0, cus = 0, coop = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev) != hipSuccess || !coop || cus < 1) {
@@ -1040,11 +1191,14 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     std::vector<int32_t> wl((size_t)G + 1), wr((size_t)G + 1), rc((size_t)G);
     int max_rows = 0;
     int code_bits = 1;
-    while ((1 << code_bits) < A.table_size + 1) ++code_bits; // + the zero the padding words address
+    while (!lt && (1 << code_bits) < A.table_size + 1) ++code_bits; // + the zero the padding words address
     if (code_bits >= kResWordBits - 8) return no("dictionary needs too many bits");
     const size_t lds_max = 160 * 1024 - 4096 - 1024;
     // the two tables (values + zero, inverted values) in T, then the fold space (3 x 16 wave sums) and 4 + 4 scalars in double
-    const size_t lds_extra = 2 * ((size_t)A.table_size + 1) * esz + (48 + 8) * sizeof(double);
+    // (local tables: their entries are counted per workgroup, tabs[b] below, next to the remote columns; no inverted values in LDS)
+    const size_t lds_extra = (lt ? 0 : 2 * ((size_t)A.table_size + 1) * esz) + (48 + 8) * sizeof(double);
+    std::vector<int32_t> tabs((size_t)G, 0), tcnt, tgr; // LDS entries of workgroup b's tables (even); entries per group; group boundaries
+    int lt_gpw = 1, lt_cap = 0, lt_max = 0, lt_max_grp = 0;
     const int cap = stream_T > 0. ? 32768 : 16384; // stride of the per-workgroup source lists (a workgroup with more remote columns does not qualify)
     const int64_t n_ext = n_cols > n ? n_cols : n;
     int64_t chunk_cols = std::min<int64_t>(n_ext, kRemapChunk);
@@ -1054,7 +1208,10 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     DevBuf<int> fail;
     if (pl->wg_row0.alloc((size_t)G + 1) != AVS_OK || pl->rwords.alloc((size_t)A.nnz) != AVS_OK || pl->rem_count.alloc((size_t)G) != AVS_OK ||
         pl->rem_list.alloc((size_t)G * cap) != AVS_OK || fail.alloc(1) != AVS_OK || pl->dep_mask.alloc((size_t)G * 32) != AVS_OK || G > 1024 ||
-        hipFuncSetAttribute((const void *)k_resident_remap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)remap_lds) != hipSuccess) {
+        hipFuncSetAttribute(lt ? (const void *)k_resident_remap<true> : (const void *)k_resident_remap<false>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)remap_lds) != hipSuccess ||
+        (lt && (pl->ltab_cnt.alloc((size_t)G * 16) != AVS_OK || pl->tg_row0.alloc((size_t)G * 16 + 1) != AVS_OK ||
+                hipFuncSetAttribute((const void *)k_resident_local_tables, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4096 * 8) != hipSuccess))) {
         (void)hipGetLastError();
         return no("plan allocation failed");
     }
@@ -1125,10 +1282,69 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
             return no("plan upload failed");
         }
         // re-encode the words for this split (the plan kernel) and fetch the remote-column counts
-        auto remap = [&]() -> int { // 0 ok, 1 a source list overflowed, -1 failure
-            hipLaunchKernelGGL(k_resident_remap, dim3((unsigned)G), dim3(kResThreads), remap_lds, stream, A.packed, A.row_ptr, A.col_bits, lc_bits,
-                               (const int32_t *)pl->wg_row0.p, cap, (int)n_ext, pl->rwords.p, pl->rem_list.p, pl->rem_count.p, fail.p, (int)n,
-                               pl->dep_mask.p, (int)chunk_cols);
+        // Local tables, for the split and the columns just re-encoded: one table per workgroup where its code bits fit the word next to
+        // the REAL column bits (rows + remote columns of the largest workgroup, not the source lists' stride), else one per wave (the
+        // rows of the wave's 64 lanes: fewer values, 16 tables whose entries add up to more LDS).  0 ok, 2 declined (lt_why), -1 failure
+        auto local_tables = [&]() -> int {
+            int cols = 2;
+            for (int b = 0; b < G; ++b)
+                cols = std::max(cols, ((wr[(size_t)b + 1] - wr[(size_t)b] + 1) & ~1) + ((rc[(size_t)b] + 1) & ~1));
+            lc_bits = 1;
+            while ((1 << lc_bits) < cols) ++lc_bits;
+            for (lt_gpw = 1; lt_gpw <= 16; lt_gpw *= 16) {
+                lt_cap = lt_gpw == 1 ? 4096 : 2048;
+                const size_t ngrp = (size_t)G * (size_t)lt_gpw;
+                tgr.assign(ngrp + 1, (int32_t)n);
+                for (int b = 0; b < G; ++b)
+                    for (int g = 0; g < lt_gpw; ++g) { // (a wave's rows: from its first lane's first row to the next wave's)
+                        const int64_t l = std::min<int64_t>((int64_t)wl[(size_t)b] + 64 * g * (16 / lt_gpw), wl[(size_t)b + 1]);
+                        tgr[(size_t)b * lt_gpw + g] = l < L ? lrow[(size_t)l] : (int32_t)n;
+                    }
+                tcnt.assign(ngrp, 0);
+                if (lt_strided.alloc(ngrp * (size_t)lt_cap) != AVS_OK ||
+                    hipMemcpyAsync(pl->tg_row0.p, tgr.data(), tgr.size() * 4, hipMemcpyHostToDevice, stream) != hipSuccess)
+                    return -1;
+                hipLaunchKernelGGL(k_resident_local_tables, dim3((unsigned)G), dim3(kResThreads), (size_t)2 * lt_cap * 8, stream, A.val, A.row_ptr,
+                                   (const int32_t *)pl->tg_row0.p, lt_gpw, lt_cap, lc_bits, pl->rwords.p, lt_strided.p, pl->ltab_cnt.p);
+                if (hipMemcpyAsync(tcnt.data(), pl->ltab_cnt.p, ngrp * sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                    hipStreamSynchronize(stream) != hipSuccess)
+                    return -1;
+                lt_max = 0;
+                for (size_t g = 0; g < ngrp; ++g)
+                    if (tcnt[g] > lt_max) { lt_max = tcnt[g]; lt_max_grp = (int)g; }
+                code_bits = 1;
+                while ((1 << code_bits) < lt_max) ++code_bits;
+                char who[64];
+                if (lt_gpw == 1) snprintf(who, sizeof(who), "workgroup %d", lt_max_grp);
+                else snprintf(who, sizeof(who), "wave %d of workgroup %d", lt_max_grp % 16, lt_max_grp / 16);
+                char msg[256];
+                if (lt_max > lt_cap)
+                    snprintf(msg, sizeof(msg), "local table of %s has more than %d distinct values", who, lt_cap);
+                else if (code_bits + lc_bits > kResWordBits)
+                    snprintf(msg, sizeof(msg), "local table of %s (%d values) needs %d code bits, %d left by the %d column bits of the %d-bit word", who,
+                             lt_max, code_bits, kResWordBits - lc_bits, lc_bits, kResWordBits);
+                else {
+                    for (int b = 0; b < G; ++b) {
+                        int t = 0;
+                        for (int g = 0; g < lt_gpw; ++g) t += tcnt[(size_t)b * lt_gpw + g];
+                        tabs[(size_t)b] = (t + 1) & ~1;
+                    }
+                    return 0;
+                }
+                lt_why = msg;
+                if (verbose) fprintf(stderr, "[avs resident] local tables per %s: %s\n", lt_gpw == 1 ? "workgroup" : "wave", msg);
+            }
+            return 2;
+        };
+        auto remap = [&]() -> int { // 0 ok, 1 a source list overflowed, 2 the local tables do not fit the word, -1 failure
+            if (lt)
+                hipLaunchKernelGGL(k_resident_remap<true>, dim3((unsigned)G), dim3(kResThreads), remap_lds, stream, (const uint32_t *)nullptr, A.col,
+                                   A.row_ptr, 0, lc_bits, (const int32_t *)pl->wg_row0.p, cap, (int)n_ext, pl->rwords.p, pl->rem_list.p,
+                                   pl->rem_count.p, fail.p, (int)n, pl->dep_mask.p, (int)chunk_cols);
+            else
+                hipLaunchKernelGGL(k_resident_remap<false>, dim3((unsigned)G), dim3(kResThreads), remap_lds, stream, A.packed, (const int32_t *)nullptr,
+                                   A.row_ptr, A.col_bits, lc_bits, (const int32_t *)pl->wg_row0.p, cap, (int)n_ext, pl->rwords.p, pl->rem_list.p,
+                                   pl->rem_count.p, fail.p, (int)n, pl->dep_mask.p, (int)chunk_cols);
             int f = 0;
             if (hipMemcpyAsync(&f, fail.p, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
                 hipMemcpyAsync(rc.data(), pl->rem_count.p, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
@@ -1136,14 +1352,19 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
                 (void)hipGetLastError();
                 return -1;
             }
-            return f ? 1 : 0;
+            if (f) return 1;
+            if (!lt) return 0;
+            const int t = local_tables();
+            if (t < 0) (void)hipGetLastError();
+            return t;
         };
         // (round 0 of a later tier is the split of the first tier's round 0: its counts are re-used, the words re-encoded only if it is accepted)
-        reuse_round0 = round == 0 && round0_done && !cur_opt().resident_equal_lanes;
+        reuse_round0 = round == 0 && round0_done && !cur_opt().resident_equal_lanes && !lt; // (local tables belong to ONE split)
         if (reuse_round0) rc = rc_round0;
         else {
             const int rm = remap();
             if (rm < 0) return no("remap failed");
+            if (rm == 2) return no(lt_why.c_str());
             if (rm > 0) { last_reason = "a workgroup reads more remote columns than its source list holds"; give_up = true; break; }
         }
         if (round == 0) {
@@ -1153,7 +1374,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
             const int t = max_ng < 3 ? (max_ng < 0 ? 0 : max_ng) : 3;
             const double limit0 = (double)(lds_max - lds_extra) / (double)esz;
             double demand = 0.;
-            for (int b = 0; b < G; ++b) demand += (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b];
+            for (int b = 0; b < G; ++b) demand += (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b] + (double)tabs[(size_t)b];
             if (demand > 0.88 * limit0 * (double)G) { give_up = true; break; }
         }
         if (round == 0 && c_rem > 0. && !extras_off) { // the remote columns are known now: one more split that counts them
@@ -1175,7 +1396,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
             size_t worst = 0;
             for (int b = 0; b < G; ++b) {
                 const size_t rows_b = (size_t)((wr[(size_t)b + 1] - wr[(size_t)b] + 1) & ~1), rem_b = (size_t)((rc[(size_t)b] + 1) & ~1);
-                worst = std::max(worst, (size_t)(4 - t) * rows_b + rem_b);
+                worst = std::max(worst, (size_t)(4 - t) * rows_b + rem_b + (size_t)tabs[(size_t)b]);
                 max_cols = std::max(max_cols, (int)(rows_b + rem_b));
             }
             const size_t need = worst * esz + extra;
@@ -1184,6 +1405,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
         }
         if (ng >= 0 && reuse_round0) { // accepted on re-used counts: the words still hold another split's encoding
             const int rm = remap();
+            if (rm == 2) return no(lt_why.c_str());
             if (rm != 0) return no("remap failed");
         }
         if (ng < 0) { // shrink the offenders (at the largest tier allowed) and split again
@@ -1191,12 +1413,13 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
             const double limit = (double)(lds_max - extra) / (double)esz;
             { // ... unless the MEDIAN workgroup does not fit either: no re-split helps, go to the next tier
                 std::vector<double> fps((size_t)G);
-                for (int b = 0; b < G; ++b) fps[(size_t)b] = (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b];
+                for (int b = 0; b < G; ++b)
+                    fps[(size_t)b] = (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b] + (double)tabs[(size_t)b];
                 std::nth_element(fps.begin(), fps.begin() + G / 2, fps.end());
                 if (fps[(size_t)G / 2] > 0.98 * limit) { give_up = true; break; }
             }
             for (int b = 0; b < G; ++b) {
-                const double fp = (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b];
+                const double fp = (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b] + (double)tabs[(size_t)b];
                 if (fp > 0.97 * limit) {
                     reweighted = true;
                     for (int64_t l = wl[(size_t)b]; l < wl[(size_t)b + 1]; ++l) lane_w[(size_t)l] *= 1.12 * fp / limit;
@@ -1212,11 +1435,38 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
         fprintf(stderr, "[avs resident] remote columns per workgroup: min %d / median %d / 90 %% %d / max %d; rows per workgroup <= %d\n", srt[0],
                 srt[(size_t)G / 2], srt[(size_t)G * 9 / 10], srt[(size_t)G - 1], max_rows);
     }
-    if (ng < 0) return no(last_reason);
+    if (ng < 0) {
+        if (lt && lt_max > 0) { // the quantity that did not fit: the LDS, with the tables it would have had to hold
+            char msg[256];
+            snprintf(msg, sizeof(msg), "%s (local tables per %s, largest %d values, up to %d table entries per workgroup)", last_reason,
+                     lt_gpw == 1 ? "workgroup" : "wave", lt_max, *std::max_element(tabs.begin(), tabs.end()));
+            lt_why = msg;
+            return no(lt_why.c_str());
+        }
+        return no(last_reason);
+    }
+    if (lt && verbose)
+        fprintf(stderr, "[avs resident] local tables: one per %s, largest %d values (%s %d%s), %d code bits + %d column bits of %d, LDS tier %d, "
+                        "<= %d table entries per workgroup, inverse diagonal per row (no LDS)\n", lt_gpw == 1 ? "workgroup" : "wave", lt_max,
+                lt_gpw == 1 ? "workgroup" : "wave", lt_gpw == 1 ? lt_max_grp : lt_max_grp % 16,
+                lt_gpw == 1 ? "" : (" of workgroup " + std::to_string(lt_max_grp / 16)).c_str(), code_bits, lc_bits, kResWordBits, ng,
+                *std::max_element(tabs.begin(), tabs.end()));
     if ((1 << lc_bits) < max_cols) return no("rows + remote columns exceed the word's column bits");
+    if (lt) { // the tables of the accepted split, back to back
+        std::vector<int32_t> toff(tcnt.size() + 1, 0);
+        for (size_t g = 0; g < tcnt.size(); ++g) toff[g + 1] = toff[g] + tcnt[g];
+        if (pl->ltab_off.alloc(toff.size()) != AVS_OK || pl->ltab.alloc((size_t)toff.back()) != AVS_OK ||
+            hipMemcpy(pl->ltab_off.p, toff.data(), toff.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            return no("plan allocation failed");
+        }
+        hipLaunchKernelGGL(k_resident_pack_tables, dim3((unsigned)tcnt.size()), dim3(256), 0, stream, (const double *)lt_strided.p, lt_cap,
+                           (const int32_t *)pl->ltab_off.p, pl->ltab.p);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); return no("table layout failed"); }
+    }
     lpw = 0;
     for (int b = 0; b < G; ++b) lpw = std::max<int64_t>(lpw, wl[(size_t)b + 1] - wl[(size_t)b]);
-    const void *kern = resident_kernel(ng, stream_words > 0, f32);
+    const void *kern = resident_kernel(ng, stream_words > 0, f32, lt);
     if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess) {
         (void)hipGetLastError();
         return no("LDS opt-in refused");
@@ -1297,7 +1547,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
         }
         hipLaunchKernelGGL(k_resident_stream_layout, dim3((unsigned)G), dim3(kResThreads), 0, stream, A.row_ptr, (const uint32_t *)pl->rwords.p,
                            (const int32_t *)pl->lane_row0.p, (const uint32_t *)pl->lane_meta.p, (const int32_t *)pl->wg_lane0.p,
-                           (const int32_t *)pl->wave_soff.p, (uint32_t)A.table_size << lc_bits, reinterpret_cast<u4_t *>(pl->swords.p));
+                           (const int32_t *)pl->wave_soff.p, lt ? 0u : (uint32_t)A.table_size << lc_bits, reinterpret_cast<u4_t *>(pl->swords.p));
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); return no("stream layout failed"); }
         pl->streams = true;
         if (verbose)
@@ -1319,6 +1569,8 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     pl->max_quads = max_quads;
     pl->ng = ng;
     pl->lds = lds;
+    pl->local = lt;
+    pl->lt_gpw = lt_gpw;
     pl->ok = true;
     pl->why.clear();
     return true;
@@ -1327,7 +1579,8 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
 // Runs the rest of the solve (state in sc / the vectors, as the set-up rounds left it) in ONE cooperative launch.
 // *launched = false: the cooperative launch was refused (the grid is not co-resident on this device right now); nothing was
 // touched, the plan is retired and the caller carries on with the launch-per-phase loop.
-// T: the plan's vector type (resident_prepare's f32).
+// T: the plan's vector type (resident_prepare's f32).  A plan with local value tables (pl->local) takes ONE INVERSE PER ROW in `invtab`
+// (the launch-per-phase loops' array) and ignores dcode.
 template <typename T>
 static avs_status resident_run(ResidentPlan *pl, const CsrView &A, T *x, T *r, T *p, T *s, T *u, T *wv, const uint16_t *dcode,
                                const T *invtab, PcgScalars *sc, int max_iters, const DirectArgs *da, hipStream_t stream, bool *launched)
@@ -1337,8 +1590,11 @@ static avs_status resident_run(ResidentPlan *pl, const CsrView &A, T *x, T *r, T
     AVS_REQUIRE(pl->f32 == F32, AVS_EINTERNAL, "the resident plan was laid out for the other vector type");
     ResidentArgs<T> a{};
     a.row_ptr = A.row_ptr;
-    a.table = A.table;
-    a.table_size = A.table_size;
+    a.table = pl->local ? pl->ltab.p : A.table;
+    a.table_size = pl->local ? 0 : A.table_size; // (local tables: entry 0 of every table is the zero of the padding words)
+    a.ltab_cnt = pl->local ? pl->ltab_cnt.p : nullptr;
+    a.ltab_off = pl->local ? pl->ltab_off.p : nullptr;
+    a.ltab_gpw = pl->lt_gpw;
     a.n = (int)A.n;
     a.G = pl->G;
     a.lane_row0 = pl->lane_row0.p;
@@ -1395,7 +1651,7 @@ static avs_status resident_run(ResidentPlan *pl, const CsrView &A, T *x, T *r, T
     AVS_HIP(hipMemsetAsync(pl->slots.p, 0xFF, (size_t)pl->G * 4 * sizeof(double), stream));   // armed: kSentinel in every slot
     AVS_HIP(hipMemsetAsync(pl->bcast.p, 0xFF, 4 * kResGens * sizeof(double), stream));
     void *args[] = {&a};
-    const hipError_t le = hipLaunchCooperativeKernel(resident_kernel<T>(pl->ng, pl->streams), dim3((unsigned)pl->G), dim3(kResThreads), args, (unsigned)pl->lds, stream);
+    const hipError_t le = hipLaunchCooperativeKernel(resident_kernel<T>(pl->ng, pl->streams, pl->local), dim3((unsigned)pl->G), dim3(kResThreads), args, (unsigned)pl->lds, stream);
     if (le != hipSuccess) {
         (void)hipGetLastError();
         pl->ok = false;

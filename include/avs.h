@@ -221,7 +221,7 @@ typedef enum {
                                    * 0 (default) = fp64 iteration on the float system.  AVS_DIST_CG=standard and paranoid mode keep their fp64 loops.
                                    * No effect on AVS_PRECISION_F64 contexts.  Takes effect at the next avs_dist_partition / avs_dist_assemble (the
                                    * local brick form's walk is laid out for the kernel that will run).  Environment: AVS_DIST_F32_VECTORS. */
-    AVS_OPTION_RESIDENT_F32 = 12  /* (11 is not assigned: avs_set_solver_option rejects it.)  AVS_PRECISION_F32 contexts: 1 = the CU-resident
+    AVS_OPTION_RESIDENT_F32 = 12, /* (11 is not assigned: avs_set_solver_option rejects it.)  AVS_PRECISION_F32 contexts: 1 = the CU-resident
                                    * loop iterates on float vectors with float scalars (float vector slices, remote columns and tables in LDS, float row sums, a thread's terms summed in float, everything across
                                    * threads / workgroups / ranks in double) where it takes a system that would otherwise iterate on float vectors:
                                    * single-GPU solves with AVS_OPTION_F32_VECTORS = -1 or 1, partitioned solves with AVS_OPTION_DIST_F32_VECTORS = 1
@@ -230,6 +230,17 @@ typedef enum {
                                    * AVS_OPTION_F32_VECTORS = 0, AVS_DIST_CG=standard or paranoid mode nothing changes.  Reported through
                                    * avs_solve_info.resident and avs_matrix_format.float_vectors.  No effect on AVS_PRECISION_F64 contexts.
                                    * Environment: AVS_RESIDENT_F32. */
+    AVS_OPTION_RESIDENT_LOCAL_TABLES = 13 /* 1 = the CU-resident loop also takes a matrix WITHOUT one dictionary of <= 1,023 values (a viscosity or density
+                                   * field, a curved boundary: tile-local tables, column windows, 6-B or plain 12-B words at the assembly): the plan
+                                   * gives every workgroup -- or, where the 25-bit matrix word has no room for a workgroup's code bits, every wave --
+                                   * its own value table, the distinct bit patterns of the rows it holds in ascending order, taken from the plain CSR
+                                   * values; the inverse diagonal is read per row.  Same row sums and the same recurrences as the launch-per-phase
+                                   * loops.  Everything else that keeps a system off the chip (rows, LDS, a shared GPU, a pending cancel,
+                                   * AVS_OPTION_RESIDENT_LOOP = 0) still applies; a plan that does not fit says which quantity did not
+                                   * (AVS_CG_RESIDENT_VERBOSE=1) and the solve runs the launch-per-phase loop as before.  0 (default) = such systems
+                                   * are not planned at all.  Matrices the resident loop takes today run the ordinary plan either way.  Both vector
+                                   * types (float: with AVS_OPTION_RESIDENT_F32).  Reported through avs_solve_info.resident.  Read at the next
+                                   * solve: switching it plans again.  Environment: AVS_RESIDENT_LOCAL_TABLES. */
 } avs_solver_option;
 enum { AVS_USE_TRANSPORT_AUTO = 0, AVS_USE_TRANSPORT_RCCL = 1, AVS_USE_TRANSPORT_DIRECT = 2 };
 enum { AVS_BRICK_AUTO = -1, AVS_BRICK_NEVER = 0, AVS_BRICK_ALWAYS = 1, AVS_BRICK_TUNE = 2 };
