@@ -31,6 +31,7 @@ PRECISION_F64, PRECISION_F32 = 0, 1   # avs_desc.precision (SolveType of the ref
  OPTION_DIST_F32_VECTORS) = range(11)  # avs_set_solver_option
 OPTION_RESIDENT_F32 = 12   # (11 is not assigned)
 OPTION_RESIDENT_LOCAL_TABLES = 13
+OPTION_MIXED_PRECISION = 14
 USE_TRANSPORT_AUTO, USE_TRANSPORT_RCCL, USE_TRANSPORT_DIRECT = 0, 1, 2
 BRICK_AUTO, BRICK_NEVER, BRICK_ALWAYS, BRICK_TUNE = -1, 0, 1, 2
 PRECONDITIONER_JACOBI, PRECONDITIONER_NONE = 0, 1
@@ -121,7 +122,8 @@ class MatrixFormat(C.Structure):
                 ("bytes_per_nonzero", C.c_int32), ("tile_local_tables", C.c_int32),
                 ("column_windows", C.c_int32), ("brick_tiles", C.c_int32), ("brick_patterns", C.c_int32), ("_pad", C.c_int32),
                 ("brick_pattern_rows", C.c_int64), ("brick_bytes", C.c_int64), ("brick_walk", C.c_int32), ("brick_value_codes", C.c_int32),
-                ("fused_vector_update", C.c_int32), ("fused_vector_faults", C.c_int32), ("float_vectors", C.c_int32)]
+                ("fused_vector_update", C.c_int32), ("fused_vector_faults", C.c_int32), ("float_vectors", C.c_int32),
+                ("reliable_updates", C.c_int32)]
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)

@@ -113,6 +113,7 @@ Options options_from_env()
     o.dist_f32_vectors = env_int("AVS_DIST_F32_VECTORS", 0) != 0;
     o.resident_f32 = env_int("AVS_RESIDENT_F32", 0) != 0;
     o.resident_local_tables = env_int("AVS_RESIDENT_LOCAL_TABLES", 0) != 0;
+    o.mixed_precision = env_int("AVS_MIXED_PRECISION", 0) != 0;
     o.prepass_temporal = env_int("AVS_PREPASS_TEMPORAL", 1) != 0;
     { const int v = env_int("AVS_POST_DOF_SAMPLE", -1); o.post_dof_sample = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.resident_cus = env_int("AVS_CG_RESIDENT_CUS", 0);
@@ -558,6 +559,7 @@ avs_status avs_assemble(avs_ctx *c, avs_assembly_info *info)
         c->ainfo.system_ms = t.stop();
         t.start();
         c->reordered = false;
+        c->mixed = c->desc.precision == AVS_PRECISION_F64 && c->opt.mixed_precision != 0; // AVS_OPTION_MIXED_PRECISION: latched here
         c->brick_shift = c->opt.brick_shift;
         if (c->brick_shift >= 0) AVS_TRY(build_reordered_system(c, c->brick_shift));
         c->ainfo.csr_ms = t.stop();
@@ -590,6 +592,7 @@ avs_status avs_get_matrix_format(avs_ctx *c, avs_matrix_format *out)
         out->struct_size = size;
     };
     f.float_vectors = c->float_vectors;
+    f.reliable_updates = c->reliable_updates;
     if (!c->system_ready && dist_matrix_format(c, fmt)) { hand_over(); return AVS_OK; } // avs_dist_assemble: the rank's own rows
     AVS_REQUIRE(c->system_ready, AVS_ESTATE, "no system: call avs_assemble first");
     const bool vi = c->reordered && c->vi.table_size > 0;
@@ -637,6 +640,7 @@ static CsrView csr_of(avs_ctx *c)
     A.brick = (c->reordered && c->brick.ready) ? &c->brick_view : nullptr;
     A.f32_vectors = c->desc.precision == AVS_PRECISION_F32 ? c->opt.f32_vectors : 0;
     A.resident_f32 = c->desc.precision == AVS_PRECISION_F32 ? c->opt.resident_f32 : 0;
+    A.mixed = c->mixed ? 1 : 0;
     return A;
 }
 
@@ -674,6 +678,7 @@ avs_status avs_set_solver_option(avs_ctx *c, avs_solver_option option, int32_t v
     case AVS_OPTION_DIST_F32_VECTORS: c->opt.dist_f32_vectors = value != 0; return AVS_OK;
     case AVS_OPTION_RESIDENT_F32: c->opt.resident_f32 = value != 0; return AVS_OK;
     case AVS_OPTION_RESIDENT_LOCAL_TABLES: c->opt.resident_local_tables = value != 0; return AVS_OK;
+    case AVS_OPTION_MIXED_PRECISION: c->opt.mixed_precision = value != 0; return AVS_OK;
     }
     set_error("unknown solver option %d", (int)option);
     return AVS_EINVAL;
@@ -733,6 +738,7 @@ avs_status avs_solve(avs_ctx *c, double tol, int32_t max_iters, avs_solve_info *
     }
     narrow_solution_if_f32(c, c->x.p, n);
     c->float_vectors = pcg_float_vectors(c->pcg);
+    c->reliable_updates = pcg_reliable_updates(c->pcg);
     if (info) *info = local;
     c->solved = true;
     return AVS_OK;
@@ -1016,6 +1022,7 @@ namespace avs {
 avs_status probe_spmv_form(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st)
 {
     if (A.f32_vectors) return spmv_f32_probe(A, x, y, fused, dot_out, st); // AVS_PRECISION_F32: the float kernels the solve launches
+    if (A.mixed) return spmv_mixed_probe(A, x, y, fused, dot_out, st); // AVS_OPTION_MIXED_PRECISION: the loop's product (float x, fp64 values)
     if (!fused) return spmv_launch(A, x, y, 0, st);
     DevBuf<double> partial;
     size_t np = spmv_partial_elems(A.n);
@@ -1120,6 +1127,8 @@ avs_status avs_spmv_solver_form(avs_ctx *c, const double *x, double *y, int32_t 
     const int64_t n = c->n_vel;
     if (n == 0) return AVS_OK;
     CsrView A = csr_of(c);
+    if (fused_dot & 2) A.mixed = 0; // a mixed-precision context: the fp64 product of its reliable updates (on the walk laid out for the mixed kernel)
+    fused_dot &= 1;
     const unsigned g = (unsigned)((n + 255) / 256);
     if (!c->reordered) {
         AVS_TRY(probe_spmv_form(A, x, y, fused_dot != 0, dot_out, c->stream));

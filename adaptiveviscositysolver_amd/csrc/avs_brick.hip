@@ -106,6 +106,11 @@ __device__ __forceinline__ T lds_abs(unsigned byte_addr) { return *(const T __at
 constexpr unsigned kBrickBlockBytes = (unsigned)((kBrickPark - kBrickXSlots) * sizeof(double));
 template <typename T> constexpr unsigned brick_vals_byte() { return (unsigned)((kBrickSlotsPad + kBrickXSlots) * sizeof(T)) + kBrickBlockBytes; } // `vals` behind the lattice and `park`
 template <typename T> constexpr unsigned brick_vals_elems(int table_size) { return (unsigned)((table_size + 4) & ~3); } // keeps the pattern image 16-B aligned for both T
+// V, the type of the matrix values and of the row sums (default: T).  <float, double> is the mixed-precision loop's product
+// (avs_pcg_mixed.inl): lattice and x slots stay 4-byte, the value table in LDS holds doubles, every entry is (double)x * val added in
+// double left to right, and the row sum is rounded to float once, where y is stored (the fused dot uses the unrounded sum).  The
+// streamed rows' parked products are V as well -- the park area is sized in bytes of doubles for every T -- so that every row of y is
+// the correctly rounded double sum up to contraction.
 
 // element `idx` of an array whose base is workgroup-uniform: a 32-bit byte offset in a VGPR + the base in SGPRs (global_load ... saddr)
 // instead of 64-bit address arithmetic per lane
@@ -125,7 +130,7 @@ __device__ __forceinline__ T ld_u32(const T *base, unsigned idx)
 // The per-row arrays (rdesc: descriptor + position of every pattern row in execution order; ownslot) stay in global memory.
 constexpr int kBlkHdr = kBlkHdrWords;
 
-template <bool DOT, bool VC = false, typename T = double>
+template <bool DOT, bool VC = false, typename T = double, typename V = T>
 __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_spmv_brick(BrickView B, const T *__restrict__ x, T *__restrict__ y,
                                                          double *__restrict__ partial, const int *__restrict__ done_flag)
 {
@@ -137,8 +142,10 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
     T *park = xs + kBrickSlotsPad;                                       // right behind the lattice: [0, kBrickXSlots) extra x slots (off-lattice
                                                                         // columns), behind them kBrickBlockBytes: first the tile's descriptor
                                                                         // block, then the products of its streamed rows
-    T *vals = reinterpret_cast<T *>(smem_raw + kValsByte);               // table_size + 1 (the last entry is 0.0: padding words), padded to 16 B
-    uint32_t *pw = reinterpret_cast<uint32_t *>(vals + brick_vals_elems<T>(B.table_size)); // kBrickPatWords (VC: kBrickPatWordsVc) + 8
+    constexpr bool MIX = sizeof(V) != sizeof(T);                         // 8-B values next to 4-B vector elements
+    static_assert(sizeof(V) >= sizeof(T) && kValsByte % sizeof(V) == 0, "values at least as wide as the vectors, aligned behind the park area");
+    V *vals = reinterpret_cast<V *>(smem_raw + kValsByte);               // table_size + 1 (the last entry is 0.0: padding words), padded to 16 B
+    uint32_t *pw = reinterpret_cast<uint32_t *>(vals + brick_vals_elems<V>(B.table_size)); // kBrickPatWords (VC: kBrickPatWordsVc) + 8
     uint32_t *pinfo = pw + (VC ? kBrickPatWordsVc : kBrickPatWords) + 8; // kBrickPatMax: local start | quads << 16
     uint2 *rbt = reinterpret_cast<uint2 *>(pinfo + kBrickPatMax);       // kBrickRowBase entries: a row's bases on the four lattices, per axis
     const uint32_t *bw = reinterpret_cast<const uint32_t *>(park + kBrickXSlots);
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
     static_assert((kBrickPark - kBrickXSlots) * 2 <= kBrickBlk * 4, "one 16-B load per thread fetches a whole descriptor block");
 
     if (!VC)
-        for (int i = tid; i <= B.table_size; i += kBrickBlk) vals[i] = (i < B.table_size) ? (T)B.table[i] : (T)0; // once per workgroup (VC: a table per tile; float: the values ARE floats, AVS_PRECISION_F32)
+        for (int i = tid; i <= B.table_size; i += kBrickBlk) vals[i] = (i < B.table_size) ? (V)B.table[i] : (V)0; // once per workgroup (VC: a table per tile; float: the values ARE floats, AVS_PRECISION_F32)
     // A row of level lr at local cell (cx, cy, cz) has the byte offset 8 (kBrickLoff[lc] + 3 ((bz S + by) S + bx)) on lattice lc, with
     // b = ((c >> up) << down) + 1 per axis: the sum of one term per axis.  Table entry (axis d, lr, c + 1) = the four lattices' terms as
     // 16-bit fields {lattice 0 | lattice 1 << 16, lattice 2 | lattice 3 << 16} (the sums stay below 2^15: no carries between the fields);
@@ -214,7 +221,7 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
     int nsw_prev = 0;
 
     int iter = 0;
-    T dot = 0;                                                           // x.y of this lane's rows, all tiles of the workgroup
+    V dot = 0;                                                           // x.y of this lane's rows, all tiles of the workgroup
     for (;;) {
         BRICK_STAMP(0);
         if (nsw_prev > 0) __syncthreads();                               // the previous tile's streamed sums have read `park`
@@ -232,8 +239,8 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
         const int ntv = VC ? __builtin_amdgcn_readfirstlane((int)bw[14]) : 0;
         const int o_runs = kBlkHdr, o_pq = o_runs + 2 * nruns, o_pi = o_pq + npq; // (runs are 8 B)
         const bool emode = npat == 0;                 // no pattern rows: the products of the streamed rows may use the x lattice's LDS
-        T *prod = emode ? xs : park + kBrickXSlots;
-        const int cap = emode ? kBrickSlotsPad : kBrickPark - kBrickXSlots;
+        V *prod = reinterpret_cast<V *>(emode ? xs : park + kBrickXSlots);
+        const int cap = emode ? (int)(kBrickSlotsPad * sizeof(T) / sizeof(V)) : kBrickPark - kBrickXSlots; // (the park block holds kBrickPark - kBrickXSlots DOUBLES for every T)
         BRICK_STAMP(1);
         // Round 6: a CU runs three workgroups on the same SIMDs and the kernel is bound by instruction ISSUE (38 M VALU wave-instructions per
         // launch at 512^3, 80 % of them outside the row walk).  A wave in this phase -- descriptors, the tile's ONE round trip of loads, LDS
@@ -318,8 +325,8 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
             pqv[u] = uint4{0u, 0u, 0u, 0u};
             if (u * kBrickBlk < npq) pqv[u] = *reinterpret_cast<const uint4 *>(B.pwords + pqo[u]);
         }
-        T tval = 0;
-        if (VC && ntv > 0) tval = (T)ld_u32(B.ttab + tt0, (unsigned)(tid < ntv ? tid : 0));   // the tile's value table (<= kBrickTileVals entries)
+        V tval = 0;
+        if (VC && ntv > 0) tval = (V)ld_u32(B.ttab + tt0, (unsigned)(tid < ntv ? tid : 0));   // the tile's value table (<= kBrickTileVals entries)
         int cbo[RPT];                                  // VC: first quad of this wave's blocks of the code stream (read NOW: the streamed rows'
                                                        // products overwrite the block image while slower waves still walk their rows)
 #pragma unroll
@@ -347,12 +354,15 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
         for (int k = 0; k < kBrickMaxRows / kBrickBlk; ++k) sd[k] = uint2{0u, 0u};
         uint32_t w0[2] = {0u, 0u};
         T xv0[2] = {0, 0};
+        constexpr bool LATE_SD = MIX && VC; // (8-B values: the descriptors of the streamed rows are fetched behind the row walk instead of living across it)
         if (nsrows > 0) {
+            if (!LATE_SD) {
 #pragma unroll
             for (int k = 0; k < kBrickMaxRows / kBrickBlk; ++k) {
                 if (k * kBrickBlk >= nsrows) break;
                 const int i = brick_srow_of_thread(tid, k);
                 sd[k] = B.sdesc[srow0 + (i < nsrows ? i : 0)];
+            }
             }
             if (!emode && !wide) {
 #pragma unroll
@@ -368,7 +378,7 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
         const bool more = iter + 1 < cnt;
         const uint2 tbn = seq[(int64_t)(more ? iter + 1 : iter) * step];
         // ---- LDS writes
-        if (VC && tid <= ntv) vals[tid] = tid < ntv ? tval : (T)0;          // (entry ntv = 0.0: the code of the padding words)
+        if (VC && tid <= ntv) vals[tid] = tid < ntv ? tval : (V)0;          // (entry ntv = 0.0: the code of the padding words)
         if (tid < npat) pinfo[tid] = pinf;
 #pragma unroll
         for (int u = 0; u < PQ; ++u) {
@@ -398,8 +408,8 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
         if (!emode) {
             // products of the first streamed pass (the block in `park` is dead now)
             if (nsw > 0 && !wide) {
-                if (tid < nsw && tid < cap) prod[tid] = vals[w0[0] >> cbits] * xv0[0];
-                if (tid + kBrickBlk < nsw && tid + kBrickBlk < cap) prod[tid + kBrickBlk] = vals[w0[1] >> cbits] * xv0[1];
+                if (tid < nsw && tid < cap) prod[tid] = vals[w0[0] >> cbits] * (V)xv0[0];
+                if (tid + kBrickBlk < nsw && tid + kBrickBlk < cap) prod[tid + kBrickBlk] = vals[w0[1] >> cbits] * (V)xv0[1];
             }
             // pattern rows: one lane per row, everything from LDS
 #pragma unroll
@@ -431,72 +441,75 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
                 // the 4-B image of the table (BrickView::pwords32: delta << 18 | level << 14 | code << 2).  A pattern is padded to whole
                 // quads with words that repeat its first entry's slot with the code of 0.0: +-0.0 added to a sum that is never -0.0.
                 constexpr unsigned CM = ES == 8 ? 0x3ff8u : 0x1ffcu;       // the code field as a byte offset into `vals`
-                constexpr int VS = ES == 8 ? 0 : 1;                       // VC: the code stream holds byte offsets for 8-B values
+                constexpr int VS = sizeof(V) == 8 ? 0 : 1;                // VC: the code stream holds byte offsets for 8-B values
+                constexpr int CS = MIX ? 1 : 0;                           // 4-B pattern image, 8-B values: code << 2 -> code << 3
                 auto addr = [&](uint32_t w) -> unsigned {
                     const unsigned sel = ((w >> 14) & 3u) * 0x0202u + 0x0c0c0100u;
                     return (unsigned)((int)w >> 16) + __builtin_amdgcn_perm(P23, P01, sel); // + 16-bit field number `level` of P23:P01
                 };
-                T sum = 0;
+                V sum = 0;
                 // software pipeline: the words of quad q + 1 and the value / x reads of quad q are in flight while quad q - 1 is added
                 // (reading the words one quad past the pattern is harmless: the LDS image ends with spare quads; they are never decoded)
                 auto walk = [&](auto adr) {
-                    T v0, v1, v2, v3, x0, x1, x2, x3;
+                    V v0, v1, v2, v3;
+                    T x0, x1, x2, x3;
                     const uint4 w = wq[0];
                     uint4 wn = wq[1];
-                    v0 = lds_abs<T>(kValsByte + (w.x & CM)); x0 = lds_abs<T>(adr(w.x));
-                    v1 = lds_abs<T>(kValsByte + (w.y & CM)); x1 = lds_abs<T>(adr(w.y));
-                    v2 = lds_abs<T>(kValsByte + (w.z & CM)); x2 = lds_abs<T>(adr(w.z));
-                    v3 = lds_abs<T>(kValsByte + (w.w & CM)); x3 = lds_abs<T>(adr(w.w));
+                    v0 = lds_abs<V>(kValsByte + ((w.x & CM) << CS)); x0 = lds_abs<T>(adr(w.x));
+                    v1 = lds_abs<V>(kValsByte + ((w.y & CM) << CS)); x1 = lds_abs<T>(adr(w.y));
+                    v2 = lds_abs<V>(kValsByte + ((w.z & CM) << CS)); x2 = lds_abs<T>(adr(w.z));
+                    v3 = lds_abs<V>(kValsByte + ((w.w & CM) << CS)); x3 = lds_abs<T>(adr(w.w));
                     for (int q = 1; q < nq; ++q) {
                         const uint4 wnn = wq[q + 1];
-                        const T a0 = lds_abs<T>(kValsByte + (wn.x & CM)), c0 = lds_abs<T>(adr(wn.x));
-                        const T a1 = lds_abs<T>(kValsByte + (wn.y & CM)), c1 = lds_abs<T>(adr(wn.y));
-                        const T a2 = lds_abs<T>(kValsByte + (wn.z & CM)), c2 = lds_abs<T>(adr(wn.z));
-                        const T a3 = lds_abs<T>(kValsByte + (wn.w & CM)), c3 = lds_abs<T>(adr(wn.w));
-                        sum += v0 * x0;
-                        sum += v1 * x1;
-                        sum += v2 * x2;
-                        sum += v3 * x3;
+                        const V a0 = lds_abs<V>(kValsByte + ((wn.x & CM) << CS)); const T c0 = lds_abs<T>(adr(wn.x));
+                        const V a1 = lds_abs<V>(kValsByte + ((wn.y & CM) << CS)); const T c1 = lds_abs<T>(adr(wn.y));
+                        const V a2 = lds_abs<V>(kValsByte + ((wn.z & CM) << CS)); const T c2 = lds_abs<T>(adr(wn.z));
+                        const V a3 = lds_abs<V>(kValsByte + ((wn.w & CM) << CS)); const T c3 = lds_abs<T>(adr(wn.w));
+                        sum += v0 * (V)x0;
+                        sum += v1 * (V)x1;
+                        sum += v2 * (V)x2;
+                        sum += v3 * (V)x3;
                         v0 = a0; x0 = c0; v1 = a1; x1 = c1; v2 = a2; x2 = c2; v3 = a3; x3 = c3;
                         wn = wnn;
                     }
-                    sum += v0 * x0;
-                    sum += v1 * x1;
-                    sum += v2 * x2;
-                    sum += v3 * x3;
+                    sum += v0 * (V)x0;
+                    sum += v1 * (V)x1;
+                    sum += v2 * (V)x2;
+                    sum += v3 * (V)x3;
                 };
                 // VC: the value of an entry comes from the row's own code stream -- quad q of this lane at cp[64 q] (the wave's rows are
                 // interleaved, so a wave load is one 512-B run) -- instead of from the pattern word; same pipeline, same order of additions
                 auto walk_vc = [&](auto adr) {
                     const uint2 *cp = B.vcodes + (int64_t)cw0 + cbo[k] + lane;
-                    T v0, v1, v2, v3, x0, x1, x2, x3;
+                    V v0, v1, v2, v3;
+                    T x0, x1, x2, x3;
                     const uint4 w = wq[0];
                     uint4 wn = wq[1];
                     uint2 c = cp[0];
                     uint2 cn = cp[nq > 1 ? 64 : 0];
-                    v0 = lds_abs<T>(kValsByte + ((c.x & 0xffffu) >> VS)); x0 = lds_abs<T>(adr(w.x));
-                    v1 = lds_abs<T>(kValsByte + ((c.x >> 16) >> VS)); x1 = lds_abs<T>(adr(w.y));
-                    v2 = lds_abs<T>(kValsByte + ((c.y & 0xffffu) >> VS)); x2 = lds_abs<T>(adr(w.z));
-                    v3 = lds_abs<T>(kValsByte + ((c.y >> 16) >> VS)); x3 = lds_abs<T>(adr(w.w));
+                    v0 = lds_abs<V>(kValsByte + ((c.x & 0xffffu) >> VS)); x0 = lds_abs<T>(adr(w.x));
+                    v1 = lds_abs<V>(kValsByte + ((c.x >> 16) >> VS)); x1 = lds_abs<T>(adr(w.y));
+                    v2 = lds_abs<V>(kValsByte + ((c.y & 0xffffu) >> VS)); x2 = lds_abs<T>(adr(w.z));
+                    v3 = lds_abs<V>(kValsByte + ((c.y >> 16) >> VS)); x3 = lds_abs<T>(adr(w.w));
                     for (int q = 1; q < nq; ++q) {
                         const uint4 wnn = wq[q + 1];
                         const uint2 cnn = cp[(q + 1 < nq ? q + 1 : q) * 64];
-                        const T a0 = lds_abs<T>(kValsByte + ((cn.x & 0xffffu) >> VS)), c0 = lds_abs<T>(adr(wn.x));
-                        const T a1 = lds_abs<T>(kValsByte + ((cn.x >> 16) >> VS)), c1 = lds_abs<T>(adr(wn.y));
-                        const T a2 = lds_abs<T>(kValsByte + ((cn.y & 0xffffu) >> VS)), c2 = lds_abs<T>(adr(wn.z));
-                        const T a3 = lds_abs<T>(kValsByte + ((cn.y >> 16) >> VS)), c3 = lds_abs<T>(adr(wn.w));
-                        sum += v0 * x0;
-                        sum += v1 * x1;
-                        sum += v2 * x2;
-                        sum += v3 * x3;
+                        const V a0 = lds_abs<V>(kValsByte + ((cn.x & 0xffffu) >> VS)); const T c0 = lds_abs<T>(adr(wn.x));
+                        const V a1 = lds_abs<V>(kValsByte + ((cn.x >> 16) >> VS)); const T c1 = lds_abs<T>(adr(wn.y));
+                        const V a2 = lds_abs<V>(kValsByte + ((cn.y & 0xffffu) >> VS)); const T c2 = lds_abs<T>(adr(wn.z));
+                        const V a3 = lds_abs<V>(kValsByte + ((cn.y >> 16) >> VS)); const T c3 = lds_abs<T>(adr(wn.w));
+                        sum += v0 * (V)x0;
+                        sum += v1 * (V)x1;
+                        sum += v2 * (V)x2;
+                        sum += v3 * (V)x3;
                         v0 = a0; x0 = c0; v1 = a1; x1 = c1; v2 = a2; x2 = c2; v3 = a3; x3 = c3;
                         wn = wnn;
                         cn = cnn;
                     }
-                    sum += v0 * x0;
-                    sum += v1 * x1;
-                    sum += v2 * x2;
-                    sum += v3 * x3;
+                    sum += v0 * (V)x0;
+                    sum += v1 * (V)x1;
+                    sum += v2 * (V)x2;
+                    sum += v3 * (V)x3;
                 };
                 // (a queue of four code quads per lane, the first four loaded with the tile's other loads, was measured: 20 spilled registers, 288 us)
                 if (pi >> 31) { // every column of the pattern on the level-0 lattice (rows are executed sorted by pattern: waves rarely mix)
@@ -508,12 +521,12 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
                     else walk(addr);
                 }
 #ifdef AVS_EXP_YNT
-                __builtin_nontemporal_store(sum, reinterpret_cast<T *>(reinterpret_cast<char *>(y + row0) + (size_t)(unsigned)(ro * ES)));
+                __builtin_nontemporal_store((T)sum, reinterpret_cast<T *>(reinterpret_cast<char *>(y + row0) + (size_t)(unsigned)(ro * ES)));
 #else
-                *reinterpret_cast<T *>(reinterpret_cast<char *>(y + row0) + (size_t)(unsigned)(ro * ES)) = sum;
+                *reinterpret_cast<T *>(reinterpret_cast<char *>(y + row0) + (size_t)(unsigned)(ro * ES)) = (T)sum;
 #endif
                 if (AVS_BRICK_PRIO >= 2) __builtin_amdgcn_s_setprio(0);
-                if (DOT) dot += sum * lds_abs<T>(own8);
+                if (DOT) dot += sum * (V)lds_abs<T>(own8);
             }
             }
         }
@@ -523,7 +536,15 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
 #ifdef AVS_EXP_SPRIO
             __builtin_amdgcn_s_setprio(1);
 #endif
-            T ssum[kBrickMaxRows / kBrickBlk];
+            V ssum[kBrickMaxRows / kBrickBlk];
+            if (LATE_SD) {
+#pragma unroll
+                for (int k = 0; k < kBrickMaxRows / kBrickBlk; ++k) {
+                    if (k * kBrickBlk >= nsrows) break;
+                    const int i = brick_srow_of_thread(tid, k);
+                    sd[k] = B.sdesc[srow0 + (i < nsrows ? i : 0)];
+                }
+            }
 #pragma unroll
             for (int k = 0; k < kBrickMaxRows / kBrickBlk; ++k) ssum[k] = 0;
             for (int ts = 0; ts < nsw; ts += cap) {
@@ -533,7 +554,8 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
                     constexpr int SU = 4; // (8 entries per thread -- a whole pass of an E tile in one round of loads -- was measured SLOWER: 7.1 -> 7.7 us per E tile)
                     for (int e0 = ts + tid; e0 < te; e0 += SU * kBrickBlk) {
                         uint32_t w4[SU], c4[SU];
-                        T x4[SU], v4[SU];
+                        T x4[SU];
+                        V v4[SU];
 #pragma unroll
                         for (int u = 0; u < SU; ++u) {
                             const int e = e0 + u * kBrickBlk;
@@ -543,7 +565,7 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
                                 const uint32_t *w = B.swords + 3 * at;
                                 w4[u] = w[0];
                                 c4[u] = 0u;
-                                v4[u] = (T)__hiloint2double((int)w[2], (int)w[1]);
+                                v4[u] = (V)__hiloint2double((int)w[2], (int)w[1]);
                             } else if (wide) {
                                 const uint2 w = reinterpret_cast<const uint2 *>(B.swords)[at];
                                 w4[u] = w.x;
@@ -559,7 +581,7 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
 #pragma unroll
                         for (int u = 0; u < SU; ++u) {
                             const int e = e0 + u * kBrickBlk;
-                            if (e < te) prod[e - ts] = (VC ? v4[u] : vals[c4[u]]) * x4[u];
+                            if (e < te) prod[e - ts] = (VC ? v4[u] : vals[c4[u]]) * (V)x4[u];
                         }
                     }
                 }
@@ -575,8 +597,8 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
             for (int k = 0; k < kBrickMaxRows / kBrickBlk; ++k)
                 if (brick_srow_of_thread(tid, k) < nsrows && (sd[k].x >> 16) > 0) {
                     const int64_t row = (int64_t)row0 + (int)(sd[k].x & 0xffffu);
-                    y[row] = ssum[k];
-                    if (DOT) dot += ssum[k] * x[row];
+                    y[row] = (T)ssum[k];
+                    if (DOT) dot += ssum[k] * (V)x[row];
                 }
         }
 #ifdef AVS_EXP_SPRIO
@@ -604,32 +626,35 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
     }
 }
 
-size_t brick_lds_bytes(const BrickView &B, int elem_bytes)
+// elem_bytes: of a vector element; val_bytes: of a matrix value in LDS (0: as the vectors; 8 with 4-B vectors = the mixed-precision kernel)
+size_t brick_lds_bytes(const BrickView &B, int elem_bytes, int val_bytes)
 {
-    const size_t es = (size_t)elem_bytes;
+    const size_t es = (size_t)elem_bytes, vs = val_bytes > 0 ? (size_t)val_bytes : es;
     const size_t vals = elem_bytes == 4 ? brick_vals_elems<float>(B.table_size) : brick_vals_elems<double>(B.table_size);
-    return (size_t)(kBrickSlotsPad + kBrickXSlots) * es + kBrickBlockBytes + vals * es +
+    return (size_t)(kBrickSlotsPad + kBrickXSlots) * es + kBrickBlockBytes + vals * vs +
            (size_t)((B.vc ? kBrickPatWordsVc : kBrickPatWords) + 8 + kBrickPatMax + 2 * kBrickRowBase) * sizeof(uint32_t);
 }
-size_t brick_lds_bytes(const BrickView &B) { return brick_lds_bytes(B, B.f32 ? 4 : 8); }
+size_t brick_lds_bytes(const BrickView &B, int elem_bytes) { return brick_lds_bytes(B, elem_bytes, 0); }
+size_t brick_lds_bytes(const BrickView &B) { return brick_lds_bytes(B, B.f32 ? 4 : 8, B.f32 == 2 ? 8 : 0); }
 
 // LDS a workgroup may ask for on this device (the kernel opts in to more than the default 48 KiB, hipFuncSetAttribute below)
 constexpr size_t kBrickLdsLimit = 64 * 1024;
 bool brick_lds_fits(const BrickView &B) { return brick_lds_bytes(B, 8) <= kBrickLdsLimit; }
 
-template <typename T>
+template <typename T, typename V = T>
 static const void *brick_kernel(bool dot, bool vc)
 {
-    if (vc) return dot ? (const void *)k_spmv_brick<true, true, T> : (const void *)k_spmv_brick<false, true, T>;
-    return dot ? (const void *)k_spmv_brick<true, false, T> : (const void *)k_spmv_brick<false, false, T>;
+    if (vc) return dot ? (const void *)k_spmv_brick<true, true, T, V> : (const void *)k_spmv_brick<false, true, T, V>;
+    return dot ? (const void *)k_spmv_brick<true, false, T, V> : (const void *)k_spmv_brick<false, false, T, V>;
 }
 
 // persistent grid: as many workgroups as the device keeps resident for THIS LDS size (a larger value table costs a workgroup per CU;
 // the float kernel's lattice is half as large: four per CU); queried once per (device, LDS size, variant), guarded: contexts of several
 // host threads share the cache
-static int brick_grid(const BrickView &B, size_t lds, int elem_bytes)
+static int brick_grid(const BrickView &B, size_t lds, int elem_bytes, int val_bytes = 0)
 {
-    struct Entry { int dev; size_t lds; int vc, es; int grid; };
+    if (val_bytes == elem_bytes) val_bytes = 0;
+    struct Entry { int dev; size_t lds; int vc, es, vs; int grid; };
     static std::mutex mu;
     static std::vector<Entry> cache;
     int dev = 0;
@@ -638,16 +663,17 @@ static int brick_grid(const BrickView &B, size_t lds, int elem_bytes)
     {
         std::lock_guard<std::mutex> lk(mu);
         for (const Entry &e : cache)
-            if (e.dev == dev && e.lds == lds && e.vc == B.vc && e.es == elem_bytes) g = e.grid;
+            if (e.dev == dev && e.lds == lds && e.vc == B.vc && e.es == elem_bytes && e.vs == val_bytes) g = e.grid;
         if (!g) {
             int per_cu = 0, cus = 0;
-            const void *fn = elem_bytes == 4 ? brick_kernel<float>(true, B.vc != 0) : brick_kernel<double>(true, B.vc != 0);
+            const void *fn = elem_bytes == 4 ? (val_bytes == 8 ? brick_kernel<float, double>(true, B.vc != 0) : brick_kernel<float>(true, B.vc != 0))
+                                             : brick_kernel<double>(true, B.vc != 0);
             (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBrickBlk, lds);
             (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
             if (per_cu < 1) per_cu = 1;
             if (cus < 1) cus = 256;
             g = per_cu * cus;
-            cache.push_back(Entry{dev, lds, B.vc, elem_bytes, g});
+            cache.push_back(Entry{dev, lds, B.vc, elem_bytes, val_bytes, g});
         }
     }
 #ifdef AVS_PROBES
@@ -670,6 +696,7 @@ static avs_status brick_raise_lds_limit()
         for (int vc = 0; vc < 2; ++vc) {
             AVS_HIP(hipFuncSetAttribute(brick_kernel<double>(dot, vc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBrickLdsLimit));
             AVS_HIP(hipFuncSetAttribute(brick_kernel<float>(dot, vc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBrickLdsLimit));
+            AVS_HIP(hipFuncSetAttribute(brick_kernel<float, double>(dot, vc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBrickLdsLimit));
         }
     done[dev] = true;
     return AVS_OK;
@@ -710,8 +737,10 @@ static void brick_print_stamps()
 
 // partial sums of x.y the fused-dot launch writes: one per workgroup of the persistent grid (of the kernel the view is laid out for:
 // BrickView::f32 -- the planned walk and the partial arrays follow that grid)
+int brick_partial_count_mixed(const BrickView &B);
 int brick_partial_count(const BrickView &B)
 {
+    if (B.f32 == 2) return brick_partial_count_mixed(B);
     const int es = B.f32 ? 4 : 8;
     return B.ntiles > 0 ? brick_grid(B, brick_lds_bytes(B, es), es) : 0;
 }
@@ -719,17 +748,21 @@ int brick_partial_count(const BrickView &B, int elem_bytes)
 {
     return B.ntiles > 0 ? brick_grid(B, brick_lds_bytes(B, elem_bytes), elem_bytes) : 0;
 }
+int brick_partial_count_mixed(const BrickView &B) // of k_spmv_brick<.., float, double>
+{
+    return B.ntiles > 0 ? brick_grid(B, brick_lds_bytes(B, 4, 8), 4, 8) : 0;
+}
 
-template <typename T>
+template <typename T, typename V = T>
 static avs_status spmv_brick_launch_t(const BrickView &B0, const T *x, T *y, double *partial, const int *done_flag, hipStream_t stream)
 {
     if (B0.ntiles <= 0) return AVS_OK;
-    constexpr int es = (int)sizeof(T);
-    const size_t lds = brick_lds_bytes(B0, es);
+    constexpr int es = (int)sizeof(T), vs = (int)sizeof(V);
+    const size_t lds = brick_lds_bytes(B0, es, vs);
     AVS_REQUIRE(lds <= kBrickLdsLimit, AVS_EINTERNAL, "brick form: %zu bytes of LDS per workgroup exceed the limit (value table of %d entries)", lds,
                 B0.table_size);
     AVS_TRY(brick_raise_lds_limit());
-    const int grid = brick_grid(B0, lds, es);
+    const int grid = brick_grid(B0, lds, es, vs);
     BrickView B = B0;
     if (es == 4) {
         AVS_REQUIRE(B.pwords32, AVS_EINTERNAL, "brick form: no 4-byte pattern image for the float kernel");
@@ -740,10 +773,10 @@ static avs_status spmv_brick_launch_t(const BrickView &B0, const T *x, T *y, dou
     B.debug |= dbg;
 #endif
     if (B.vc) {
-        if (partial) hipLaunchKernelGGL((k_spmv_brick<true, true, T>), dim3(grid), dim3(kBrickBlk), lds, stream, B, x, y, partial, done_flag);
-        else hipLaunchKernelGGL((k_spmv_brick<false, true, T>), dim3(grid), dim3(kBrickBlk), lds, stream, B, x, y, partial, done_flag);
-    } else if (partial) hipLaunchKernelGGL((k_spmv_brick<true, false, T>), dim3(grid), dim3(kBrickBlk), lds, stream, B, x, y, partial, done_flag);
-    else hipLaunchKernelGGL((k_spmv_brick<false, false, T>), dim3(grid), dim3(kBrickBlk), lds, stream, B, x, y, partial, done_flag);
+        if (partial) hipLaunchKernelGGL((k_spmv_brick<true, true, T, V>), dim3(grid), dim3(kBrickBlk), lds, stream, B, x, y, partial, done_flag);
+        else hipLaunchKernelGGL((k_spmv_brick<false, true, T, V>), dim3(grid), dim3(kBrickBlk), lds, stream, B, x, y, partial, done_flag);
+    } else if (partial) hipLaunchKernelGGL((k_spmv_brick<true, false, T, V>), dim3(grid), dim3(kBrickBlk), lds, stream, B, x, y, partial, done_flag);
+    else hipLaunchKernelGGL((k_spmv_brick<false, false, T, V>), dim3(grid), dim3(kBrickBlk), lds, stream, B, x, y, partial, done_flag);
     AVS_HIP(hipGetLastError());
 #ifdef AVS_PROBES
     if (B.debug & 64) { // print the phase stamps of THIS launch (synchronises: not for timing loops)
@@ -760,6 +793,11 @@ avs_status spmv_brick_launch(const BrickView &B, const double *x, double *y, dou
 avs_status spmv_brick_launch_f32(const BrickView &B, const float *x, float *y, double *partial, const int *done_flag, hipStream_t stream)
 {
     return spmv_brick_launch_t<float>(B, x, y, partial, done_flag, stream);
+}
+// the mixed-precision loop's product (avs_pcg_mixed.inl): float x and y, the fp64 value table
+avs_status spmv_brick_launch_mixed(const BrickView &B, const float *x, float *y, double *partial, const int *done_flag, hipStream_t stream)
+{
+    return spmv_brick_launch_t<float, double>(B, x, y, partial, done_flag, stream);
 }
 
 } // namespace avs

@@ -119,6 +119,8 @@ struct Options {
     int resident_f32 = 0;        // AVS_RESIDENT_F32: the CU-resident loop iterates on float vectors where it takes a float-vector solve
                                  // (k_cg_resident<.., float>): single GPU with f32_vectors != 0, partitioned with dist_f32_vectors (latched
                                  // with it: PcgDist::resident_f32)
+    int mixed_precision = 0;     // AVS_MIXED_PRECISION: fp64 contexts' single-GPU launch-per-phase solves iterate on float vectors with fp64 residual
+                                 // updates (avs_pcg_mixed.inl); latched at avs_assemble (avs_ctx::mixed)
     int resident_local_tables = 0; // AVS_RESIDENT_LOCAL_TABLES: the CU-resident loop takes matrices without one small dictionary too, with a value
                                  // table per workgroup / per wave built by the plan (k_resident_local_tables)
     // CU-resident loop: tuning and test switches
@@ -371,6 +373,8 @@ struct CsrView {
                          // -1 where the CU-resident loop does not take the system, 0 never
     int resident_f32 = 0; // AVS_PRECISION_F32 + AVS_OPTION_RESIDENT_F32: a solve that iterates on float vectors (f32_vectors != 0) does so in the
                           // CU-resident loop too, where the system qualifies
+    int mixed = 0; // AVS_PRECISION_F64 + AVS_OPTION_MIXED_PRECISION (as of the last avs_assemble): a single-GPU solve the launch-per-phase loop
+                   // would run iterates on float vectors with fp64 residual updates (avs_pcg_mixed.inl)
 };
 constexpr int kCwinOffBits = 14, kCwinSlotBits = 6, kCwinSlots = 1 << kCwinSlotBits, kCwinCodeBits = 32 - kCwinOffBits - kCwinSlotBits;
 
@@ -436,6 +440,7 @@ struct BrickView {
     const double *ttab = nullptr;    // the tiles' value tables, one after the other
     // float-vector loop (AVS_PRECISION_F32, avs_pcg_f32.inl): the pattern table with byte offsets for 4-B elements; f32 = the planned walk
     // and the partial-sum count are those of the float kernel's grid
+    // f32 = 2: the mixed-precision loop of an fp64 context (avs_pcg_mixed.inl): the grid of k_spmv_brick<.., float, double>
     const uint32_t *pwords32 = nullptr;
     int f32 = 0;
 };
@@ -497,6 +502,9 @@ avs_status spmv_brick_launch(const BrickView &B, const double *x, double *y, dou
 int brick_partial_count(const BrickView &B);   // partial sums the fused-dot launch writes (one per persistent workgroup), kernel of B.f32
 int brick_partial_count(const BrickView &B, int elem_bytes);
 avs_status spmv_brick_launch_f32(const BrickView &B, const float *x, float *y, double *partial, const int *done_flag, hipStream_t stream);
+// float vectors, fp64 values and row sums (k_spmv_brick<.., float, double>): the mixed-precision loop's product
+avs_status spmv_brick_launch_mixed(const BrickView &B, const float *x, float *y, double *partial, const int *done_flag, hipStream_t stream);
+int brick_partial_count_mixed(const BrickView &B);
 
 // the lossless storage forms of one matrix's values (avs_reorder.hip), owned next to the CSR arrays
 constexpr int64_t kKeepCachedBytes = 200ll << 20; // what may stay in the 256 MB Infinity Cache across a PCG iteration
@@ -594,6 +602,7 @@ avs_status pcg_create(PcgWork **w, int64_t n, int64_t n_ext, hipStream_t stream)
 void pcg_destroy(PcgWork *w);
 int64_t pcg_rows(const PcgWork *w); // rows the workspace was sized for (-1: none)
 void pcg_fused_state(const PcgWork *w, int *used, int *faults); // k_update_fused: the last solve ran it / launches whose barrier timed out
+int pcg_reliable_updates(const PcgWork *w); // fp64 residual updates of the last solve (the mixed-precision loop; 0 otherwise)
 int pcg_float_vectors(const PcgWork *w); // 1 = the last solve iterated on float vectors (avs_pcg_f32.inl, the partitioned <float> loops)
 
 // Jacobi-PCG in Eigen's operation order; x holds the initial guess, returns the solution.
@@ -713,6 +722,7 @@ avs_status build_brick_form(struct ::avs_ctx *c); // avs_brick_build.hip
 // y = A x through the form the loops launch (+ the folded partial sums of x.y of the fused-dot instantiation); avs_api.hip
 avs_status probe_spmv_form(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st);
 avs_status spmv_f32_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st); // avs_pcg_f32.inl
+avs_status spmv_mixed_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st); // avs_pcg_mixed.inl
 #endif
 avs_status unpermute(struct ::avs_ctx *c, const double *xp, double *x);
 // builds the value dictionary of `val` (nnz entries); *table_size = 0 when there are more than 65536 distinct values
@@ -818,6 +828,8 @@ struct avs_ctx {
     avs::PcgWork *pcg = nullptr;
     avs::PcgDist *dist = nullptr;
     int float_vectors = 0; // the last avs_solve / avs_dist_solve iterated on float vectors (avs_matrix_format::float_vectors)
+    int reliable_updates = 0; // ... and its fp64 residual updates (the mixed-precision loop; avs_matrix_format::reliable_updates)
+    bool mixed = false;    // AVS_OPTION_MIXED_PRECISION as of the last avs_assemble (fp64 contexts): the brick walk is laid out for the mixed kernel
 
     avs::PyramidView view() const;
 };

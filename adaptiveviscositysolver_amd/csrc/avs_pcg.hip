@@ -36,7 +36,7 @@ static constexpr int kSampleEvery = 4;       // SpMV launches bracketed by HIP e
 // What a captured chunk (PcgWork::graph) was recorded against: the loop, the buffers and sizes its launches read, its flags and the
 // tolerance.  It is replayed only while every field matches.  Each loop sets what it depends on and leaves the rest zero; the loop tag
 // keeps one loop from ever replaying another's graph on the same workspace.
-enum GraphLoop { kGraphF64 = 1, kGraphF32, kGraphDirect, kGraphDirectF32 };
+enum GraphLoop { kGraphF64 = 1, kGraphF32, kGraphDirect, kGraphDirectF32, kGraphMixed };
 struct GraphKey {
     int loop = 0;
     const void *row_ptr = nullptr, *col = nullptr, *val = nullptr, *codes = nullptr, *packed = nullptr, *table = nullptr;
@@ -62,6 +62,7 @@ struct PcgWork {
     DevBuf<float> f_x, f_r, f_p, f_t, f_b, f_invd, f_invtab; // float-vector loop of AVS_PRECISION_F32 contexts (avs_pcg_f32.inl)
     DevBuf<float> f_s, f_u;  // ... and s, u [owned | halo] of the partitioned single-reduction loops on float vectors
     int float_vectors = 0;   // the last solve iterated on float vectors
+    int reliable_updates = 0; // ... and its fp64 residual updates (the mixed-precision loop, avs_pcg_mixed.inl)
     DevBuf<double> x_save;   // the initial guess while the CU-resident loop runs (restored if it faults)
     DevBuf<double> cancel_word; // partitioned solves: [0] this rank's avs_cancel request as the kernels / the all-reduce see it (0. / 1.)
     DevBuf<int> cancel_dev;     // ... and as an int for the finalizer of the direct transport
@@ -1690,6 +1691,7 @@ static avs_status finish_info(PcgWork *w, const CsrView &A, hipStream_t stream, 
 
 
 #include "avs_pcg_f32.inl"
+#include "avs_pcg_mixed.inl"
 
 // ---------------------------------------------------------------------------------------------
 // Single-reduction PCG (Chronopoulos & Gear 1989) -- used when the solve is partitioned over several
@@ -2454,6 +2456,7 @@ avs_status pcg_create(PcgWork **out, int64_t n, int64_t n_ext, hipStream_t)
 
 int64_t pcg_rows(const PcgWork *w) { return w ? w->n : -1; }
 int pcg_float_vectors(const PcgWork *w) { return w ? w->float_vectors : 0; }
+int pcg_reliable_updates(const PcgWork *w) { return w ? w->reliable_updates : 0; }
 void pcg_fused_state(const PcgWork *w, int *used, int *faults)
 {
     if (used) *used = w ? w->fused_used : 0;
@@ -2549,6 +2552,7 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
     const int64_t n = A.n;
     AVS_REQUIRE(w && w->n == n, AVS_EINVAL, "pcg workspace does not match the system size");
     w->float_vectors = 0; // (the float loops set it)
+    w->reliable_updates = 0;
     if (dist) {
         DirectArgs da;
         const bool direct = dist_direct_args(dist, &da);
@@ -2571,6 +2575,7 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
         if (ran || rs != AVS_OK) return rs;
     }
     if (!dist && A.f32_vectors != 0) return pcg_solve_f32(w, A, b, x, tol, max_iters, stream, info); // (auto, or a float resident loop that did not take it / faulted)
+    if (!dist && A.mixed) return pcg_solve_mixed(w, A, b, x, tol, max_iters, stream, info); // AVS_OPTION_MIXED_PRECISION: what the loop below would run
     if (A.brick && A.brick->ntiles > 0) // one partial per wave of every tile: tiles may be smaller than 512 rows
         AVS_TRY(ensure_partials(w, 2 * ((size_t)A.brick->ntiles * 8 + 16) + 4 * (size_t)kVecGrid + 16));
     const int g = vec_grid(n);

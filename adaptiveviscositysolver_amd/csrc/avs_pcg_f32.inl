@@ -66,12 +66,14 @@ __global__ void k_f32_threshold(PcgScalars *sc, double tol)
 // y = A x for any CsrView (8-B values, one dictionary, tile-local dictionaries): coalesced stream of (column, value) -> float products
 // parked in LDS -> every row adds its segment left to right.  256 rows per workgroup (a workgroup lies inside one 512-row tile: its
 // dictionary base is uniform).  The systems that land here are small (no brick form: < 2 M rows) and cache-resident.
-template <bool DOT>
+// V = double (the mixed-precision loop of fp64 contexts, avs_pcg_mixed.inl): the values are not narrowed, every product is
+// (double)x * val, the row sum is a double sum left to right and is rounded to float once, when y is stored.
+template <bool DOT, typename V = float>
 __global__ __launch_bounds__(kBlock) void k_f32_spmv_csr(CsrView A, const float *__restrict__ x, float *__restrict__ y,
                                                          double *__restrict__ partial, const PcgScalars *sc)
 {
     if (DOT && sc && sc->done) return;
-    __shared__ float prod[kStreamCap];
+    __shared__ V prod[kStreamCap];
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kBlock;
@@ -85,23 +87,24 @@ __global__ __launch_bounds__(kBlock) void k_f32_spmv_csr(CsrView A, const float 
         rs = A.row_ptr[row];
         re = A.row_ptr[row + 1];
     }
-    float sum = 0.f;
+    V sum = 0;
     for (int ts = s_blk; ts < e_blk; ts += kStreamCap) {
         const int te = (ts + kStreamCap < e_blk) ? ts + kStreamCap : e_blk;
         for (int k0 = ts + tid; k0 < te; k0 += 4 * kBlock) {
             int c[4];
-            float v[4], xv[4];
+            V v[4];
+            float xv[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int k = k0 + u * kBlock < te ? k0 + u * kBlock : ts;
                 c[u] = A.col[k];
-                v[u] = A.val && !A.codes ? (float)A.val[k] : (float)A.table[tbase + A.codes[k]];
+                v[u] = A.val && !A.codes ? (V)A.val[k] : (V)A.table[tbase + A.codes[k]];
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) xv[u] = x[c[u]];
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (k0 + u * kBlock < te) prod[k0 + u * kBlock - ts] = v[u] * xv[u];
+                if (k0 + u * kBlock < te) prod[k0 + u * kBlock - ts] = v[u] * (V)xv[u];
         }
         __syncthreads();
         const int a = rs > ts ? rs : ts;
@@ -109,9 +112,9 @@ __global__ __launch_bounds__(kBlock) void k_f32_spmv_csr(CsrView A, const float 
         for (int j = a; j < b; ++j) sum += prod[j - ts];
         __syncthreads();
     }
-    if (row < A.n) y[row] = sum;
+    if (row < A.n) y[row] = (float)sum;
     if (DOT) {
-        double d = (row < A.n) ? (double)(sum * x[row]) : 0.;
+        double d = (row < A.n) ? (double)(sum * (V)x[row]) : 0.;
         d = block_sum(d, red);
         if (tid == 0) partial[blockIdx.x] = d;
     }
@@ -161,8 +164,9 @@ __global__ __launch_bounds__(kBlock) void k_f32_init_p(int64_t n, const float *_
 
 // r -= alpha t ; partials r.r and r.(invd r).  Four rows per thread (16-B accesses).  FUSED: every workgroup folds the SpMV's `nb`
 // partial sums itself (the alpha step, as in k_update_r); else OP_ALPHA has left p.Ap in sc->pAp.  Either way alpha is the FLOAT
-// quotient of the float-rounded sums.
-template <bool CODED, bool FUSED, bool KEEP>
+// quotient of the float-rounded sums.  DS (the mixed-precision loop, avs_pcg_mixed.inl): the scalars are doubles -- alpha is the double
+// quotient of the unrounded sums, rounded to float only where it multiplies the float vector.
+template <bool CODED, bool FUSED, bool KEEP, bool DS = false>
 __global__ __launch_bounds__(kBlock) void k_f32_update_r(int64_t n, float *__restrict__ r, const float *__restrict__ t,
                                                          const float *__restrict__ invd, const uint16_t *__restrict__ dcode, PcgScalars *sc,
                                                          double *__restrict__ partial, const double *__restrict__ spmv_partial, int nb, int parity)
@@ -181,12 +185,15 @@ __global__ __launch_bounds__(kBlock) void k_f32_update_r(int64_t n, float *__res
         if (threadIdx.x == 0) tot = pap;
         __syncthreads();
         pap = tot;
-        alpha = (float)(parity ? sc->rho_alt : sc->rho) / (float)pap;
+        const double alpha_d = (parity ? sc->rho_alt : sc->rho) / pap;
+        alpha = DS ? (float)alpha_d : (float)(parity ? sc->rho_alt : sc->rho) / (float)pap;
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             sc->red[0] = pap;
-            sc->pAp = (double)(float)pap;
-            sc->alpha = (double)alpha;
+            sc->pAp = DS ? pap : (double)(float)pap;
+            sc->alpha = DS ? alpha_d : (double)alpha;
         }
+    } else if (DS) {
+        alpha = (float)sc->alpha; // (OP_ALPHA's double quotient)
     } else {
         alpha = (float)(parity ? sc->rho_alt : sc->rho) / (float)sc->pAp;
         if (blockIdx.x == 0 && threadIdx.x == 0) sc->alpha = (double)alpha; // (OP_ALPHA divided in double: k_f32_update_xp reads this one)
@@ -227,7 +234,9 @@ __global__ __launch_bounds__(kBlock) void k_f32_update_r(int64_t n, float *__res
 
 // x += alpha p (also in the iteration that converges: done == 2), then p = invd r + beta p.  The beta step -- fold of k_f32_update_r's
 // 2 g partials, convergence test, beta = absNew / absOld in float -- is done here by every workgroup for itself (as k_update_xp<FUSED>).
-template <bool CODED, bool KEEP>
+// DS (the mixed-precision loop): sums, threshold test and beta in double; the iteration that claims convergence leaves the r.z it started
+// from in sc->rho whatever its parity (the reliable update that follows reads it there).
+template <bool CODED, bool KEEP, bool DS = false>
 __global__ __launch_bounds__(kBlock) void k_f32_update_xp(int64_t n, float *__restrict__ x, float *__restrict__ p, const float *__restrict__ r,
                                                           const float *__restrict__ invd, const uint16_t *__restrict__ dcode, PcgScalars *sc,
                                                           const double *__restrict__ partial, int g, int parity)
@@ -247,20 +256,41 @@ __global__ __launch_bounds__(kBlock) void k_f32_update_xp(int64_t n, float *__re
         rz = block_sum(rz, red);
         if (threadIdx.x == 0) { tot[0] = rr; tot[1] = rz; }
         __syncthreads();
-        const float rrf = (float)tot[0], rzf = (float)tot[1];
-        const float absOld = (float)(parity ? sc->rho_alt : sc->rho);
-        if (rrf < (float)sc->threshold) done = 2; // Eigen: break before i++ (x += alpha p still pending)
-        else beta = rzf / absOld;
-        if (blockIdx.x == 0 && threadIdx.x == 0) { // what OP_BETA does
-            sc->red[0] = (double)rrf;
-            sc->red[1] = (double)rzf;
-            sc->rr = (double)rrf;
-            if (done == 2) sc->done = 2;
-            else {
-                if (parity) sc->rho = (double)rzf;
-                else sc->rho_alt = (double)rzf;
-                sc->beta = (double)beta;
-                sc->iter += 1;
+        if (DS) {
+            const double rrd = tot[0], rzd = tot[1];
+            const double absOld = parity ? sc->rho_alt : sc->rho;
+            if (rrd < sc->threshold) done = 2;
+            else beta = (float)(rzd / absOld);
+            if (blockIdx.x == 0 && threadIdx.x == 0) {
+                sc->red[0] = rrd;
+                sc->red[1] = rzd;
+                sc->rr = rrd;
+                if (done == 2) {
+                    sc->done = 2;
+                    if (parity) sc->rho = absOld; // (nobody reads sc->rho in an odd iteration: the slot this iteration would have written)
+                } else {
+                    if (parity) sc->rho = rzd;
+                    else sc->rho_alt = rzd;
+                    sc->beta = rzd / absOld;
+                    sc->iter += 1;
+                }
+            }
+        } else {
+            const float rrf = (float)tot[0], rzf = (float)tot[1];
+            const float absOld = (float)(parity ? sc->rho_alt : sc->rho);
+            if (rrf < (float)sc->threshold) done = 2; // Eigen: break before i++ (x += alpha p still pending)
+            else beta = rzf / absOld;
+            if (blockIdx.x == 0 && threadIdx.x == 0) { // what OP_BETA does
+                sc->red[0] = (double)rrf;
+                sc->red[1] = (double)rzf;
+                sc->rr = (double)rrf;
+                if (done == 2) sc->done = 2;
+                else {
+                    if (parity) sc->rho = (double)rzf;
+                    else sc->rho_alt = (double)rzf;
+                    sc->beta = (double)beta;
+                    sc->iter += 1;
+                }
             }
         }
     }

@@ -217,7 +217,9 @@ avs_status build_reordered_system(avs_ctx *c, int brick_shift)
         c->brick.view(c->brick_view, c->vi);
     }
     // AVS_PRECISION_F32 with float vectors: the loop launches the float kernel: the walk is laid out for ITS grid
-    const int view_f32 = (c->desc.precision == AVS_PRECISION_F32 && c->opt.f32_vectors != 0) ? 1 : 0;
+    // AVS_PRECISION_F64 with AVS_OPTION_MIXED_PRECISION: the mixed-precision loop launches k_spmv_brick<.., float, double> 32 times per fp64
+    // product: the walk is laid out for that grid (the fp64 kernel follows the plan where its grid is the same, else its strided walk)
+    const int view_f32 = c->mixed ? 2 : (c->desc.precision == AVS_PRECISION_F32 && c->opt.f32_vectors != 0) ? 1 : 0;
     c->brick_view.f32 = view_f32;
     if (c->brick.ready && c->opt.brick_plan) { // the persistent grid's walk, laid out from the tiles' estimated costs (BrickForm::plan_walk)
         AVS_TRY(c->brick.plan_walk(brick_partial_count(c->brick_view), c->brick_walk, c->opt.brick_cost, st));

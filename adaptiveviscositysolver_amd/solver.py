@@ -295,6 +295,12 @@ class ViscositySolve:
                 return (f"k_spmv_brick<DOT,{'VC,' if int(fmt.brick_value_codes) else ''}float> (brick-structured form, float vectors: {int(fmt.brick_tiles)} tiles, "
                         f"{int(fmt.brick_pattern_rows)} rows as {int(fmt.brick_patterns)} geometric row patterns, x of a brick + halo as floats in LDS; {tab}-entry dictionary; brick-major system)")
             return "k_f32_spmv_csr<DOT> (float vectors: column + value code streamed, float products parked in LDS; brick-major system)"
+        if int(getattr(fmt, "float_vectors", 0)) and int(getattr(fmt, "reliable_updates", 0)):   # the mixed-precision loop ran (avs_pcg_mixed.inl)
+            if int(getattr(fmt, "brick_tiles", 0)):
+                return (f"k_spmv_brick<DOT,{'VC,' if int(fmt.brick_value_codes) else ''}float,double> (brick-structured form, float vectors, fp64 values and row sums: "
+                        f"{int(fmt.brick_tiles)} tiles, {int(fmt.brick_pattern_rows)} rows as {int(fmt.brick_patterns)} geometric row patterns; {tab}-entry dictionary; "
+                        f"mixed-precision loop, {int(fmt.reliable_updates)} fp64 residual updates in the last solve; brick-major system)")
+            return "k_f32_spmv_csr<DOT,double> (float vectors, fp64 values and row sums; mixed-precision loop; brick-major system)"
         ltab = "LTAB" if 0 < tab <= 2048 else "GTAB"
         cw = int(fmt.column_windows)
         if int(getattr(fmt, "brick_tiles", 0)):

@@ -24,8 +24,10 @@ avs_status avs_bench_spmv(avs_ctx *ctx, int32_t variant, int32_t repeats, double
 
 /* y = A x with the storage form and kernel the solver's loop launches for the system owned by ctx (brick-structured form, word stream,
  * ...), for an ARBITRARY x: x and y are device vectors in the REFERENCE's DOF numbering (the entry permutes into the solver's brick-major
- * numbering and back).  fused_dot != 0 launches the fused-dot instantiation (what the PCG loop runs) and returns the folded x.y in
- * *dot_out.  The parity tests compare y with the CPU oracle's CSR product bit for bit. */
+ * numbering and back).  fused_dot & 1 launches the fused-dot instantiation (what the PCG loop runs) and returns the folded x.y in
+ * *dot_out.  The parity tests compare y with the CPU oracle's CSR product bit for bit.  A context assembled with
+ * AVS_OPTION_MIXED_PRECISION = 1 multiplies with the mixed-precision loop's product (x narrowed to float, fp64 values and row sums, y
+ * rounded to float); fused_dot & 2 asks such a context for the fp64 product of its reliable updates instead. */
 avs_status avs_spmv_solver_form(avs_ctx *ctx, const double *x, double *y, int32_t fused_dot, double *dot_out);
 /* the same for the LOCAL system of a partitioned solve (after avs_dist_assemble / avs_dist_partition): x_ext holds the rank's
  * [owned | halo] entries in local numbering (n_own + n_halo doubles, device), y its n_own rows */
