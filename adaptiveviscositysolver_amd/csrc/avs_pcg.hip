@@ -123,6 +123,23 @@ __device__ __forceinline__ double block_sum(double v, double *lds4)
     return s; // valid in thread 0
 }
 
+// two block sums through ONE barrier, each formed exactly as block_sum forms it (wave_sum, then ((w0 + w1) + w2) + w3); every thread adds
+// the four wave sums itself, so both totals are valid in EVERY thread and no broadcast barrier follows.  lds8 must be an array that
+// nothing else in the kernel touches: the barrier that block_sum takes before its stores only guards a reused array.
+__device__ __forceinline__ void block_sum2(double &a, double &b, double *lds8)
+{
+    a = wave_sum(a);
+    b = wave_sum(b);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        lds8[wave] = a;
+        lds8[4 + wave] = b;
+    }
+    __syncthreads();
+    a = ((lds8[0] + lds8[1]) + lds8[2]) + lds8[3];
+    b = ((lds8[4] + lds8[5]) + lds8[6]) + lds8[7];
+}
+
 // ---------------------------------------------------------------------------------------------
 // SpMV: stream variant
 // ---------------------------------------------------------------------------------------------
@@ -970,6 +987,77 @@ __global__ __launch_bounds__(kBlock) void k_inv_diag_coded(CsrView A, uint16_t *
     dcode[i] = (uint16_t)code;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The scalar prologue of the vector kernels of the launch-per-phase loops (k_update_r, k_update_xp and their float twins in
+// avs_pcg_f32.inl).  None of a kernel's stream loads depends on alpha or beta, and the scalar loads do not depend on each other, so at
+// kernel entry every thread requests, in this order and without waiting for anything:
+//   1. vec_request: the scalars (uniform loads; a kernel uses the ones its form needs, the others are never loaded) and its share of
+//      the partial sums of the launch before (up to kFoldBatch per array: all of them in the loops' own launches);
+//   2. the stream loads of its first kVecAhead grid-stride trips (a lane without such a trip reads *sc and drops the value: with no
+//      branch between the requests the compiler can wait for the partial sums alone -- loads return in order);
+//   3. vec_fold: folds the partial sums behind a single barrier while the streams are still in flight.
+// The chain this replaces ran, in every workgroup and before the first byte of a stream was requested: load done -> load the partials
+// -> two barriers per block_sum -> tot through LDS and a third barrier -> load rho / threshold -> divide -> first stream load at
+// cold-start latency.
+// The fold's arithmetic is the old one: thread t adds partial[t + 256 j] in ascending j (absent entries add +0.0, which changes no bit
+// of a sum that started from +0.0), wave_sum, ((w0 + w1) + w2) + w3 -- the same bits in every thread of every workgroup.
+// ---------------------------------------------------------------------------------------------
+static constexpr int kVecAhead = 1;  // trips whose loads leave before the fold (1 against 2: profiles/vector_prologue.md)
+static constexpr int kFoldBatch = 8; // partial sums per thread and array requested at once (k_update_xp at kVecGrid: 8 + 8)
+struct VecScalars {
+    int done;
+    double alpha, beta, pAp, rho_old, threshold; // sc as it was at kernel entry (rho_old: the slot of this iteration's parity)
+    double sum[2];                               // vec_fold: the folded partial sums
+    double va[kFoldBatch], vb[kFoldBatch];       // vec_request: the thread's first partial sums as loaded (entries beyond count: part[0])
+};
+// NS sums to fold: 0 (the scalar step was a launch of its own), 1 (part[0 .. count)), 2 (+ part[second .. second + count))
+template <int NS>
+__device__ __forceinline__ VecScalars vec_request(const PcgScalars *sc, int parity, const double *__restrict__ part, int count, int second)
+{
+    VecScalars s;
+    s.done = sc->done;
+    s.alpha = sc->alpha;
+    s.beta = sc->beta;
+    s.pAp = sc->pAp;
+    s.rho_old = *(parity ? &sc->rho_alt : &sc->rho);
+    s.threshold = sc->threshold;
+    s.sum[0] = s.sum[1] = 0.;
+#pragma unroll
+    for (int u = 0; u < kFoldBatch; ++u) {
+        const int k = u * kBlock + (int)threadIdx.x, kc = k < count ? k : 0;
+        s.va[u] = NS > 0 ? part[kc] : 0.;
+        s.vb[u] = NS > 1 ? part[second + kc] : 0.;
+    }
+    __builtin_amdgcn_sched_barrier(0); // (the streams' requests stay behind these: what returns first is what is needed first)
+    return s;
+}
+template <int NS>
+__device__ __forceinline__ void vec_fold(VecScalars &s, const double *__restrict__ part, int count, int second, double *lds8)
+{
+    if (NS == 0) return;
+    __builtin_amdgcn_sched_barrier(0);
+    double a = 0., b = 0.;
+#pragma unroll
+    for (int u = 0; u < kFoldBatch; ++u) {
+        const bool in = u * kBlock + (int)threadIdx.x < count;
+        a += in ? s.va[u] : 0.;
+        if (NS > 1) b += in ? s.vb[u] : 0.;
+    }
+    for (int k = kFoldBatch * kBlock + (int)threadIdx.x; k < count; k += kBlock) { // (k_update_r beyond 2048 partial sums)
+        a += part[k];
+        if (NS > 1) b += part[second + k];
+    }
+    block_sum2(a, b, lds8);
+    s.sum[0] = a;
+    s.sum[1] = b;
+}
+// the address a lane's stream load goes to: its rows, or *sc for a lane whose trip lies beyond the last row (value never used)
+template <typename V, typename E>
+__device__ __forceinline__ const V *vec_src(bool live, const E *rows, const PcgScalars *sc)
+{
+    return live ? reinterpret_cast<const V *>(rows) : reinterpret_cast<const V *>(sc);
+}
+
 // r -= alpha t ; partials: r.r and r.(invd r).  (x += alpha p rides along with the p update below:
 // one vector pass less per iteration -- 10 n instead of 11 n doubles of traffic.)
 // FUSED (single-GPU loop, small systems): the alpha step -- fold of the SpMV's `nb` partial sums, alpha = r.z / p.Ap -- is done
@@ -982,53 +1070,57 @@ __global__ __launch_bounds__(kBlock) void k_update_r(int64_t n, double *__restri
                                                      PcgScalars *sc, double *__restrict__ partial,
                                                      const double *__restrict__ spmv_partial = nullptr, int nb = 0, int parity = 0)
 {
-    if (sc->done) {
-        if (FUSED && blockIdx.x == 0 && threadIdx.x == 0 && sc->done == 2) sc->done = 1; // the pending x update has run (OP_ALPHA)
+    __shared__ double pro[8], red[8];
+    // t = A p is read for the last time here and r is next read one kernel later: the streams that nobody reads again before they
+    // are overwritten are loaded / stored NON-TEMPORALLY, so that they do not push the matrix out of the caches between two products
+    // (`keep`: matrix and vectors together fit the Infinity Cache -- then everything is left to it)
+    const int64_t n2 = n >> 1; // two rows per thread (16-B accesses), partial sums in the order (even row, odd row)
+    const int64_t j0 = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+    struct Trip { d2_t rv, tv, iv; unsigned cc; };
+    auto request = [&](int64_t j, bool live, Trip &q) {
+        const int64_t i = 2 * j;
+#ifndef AVS_EXP_NO_RNT
+        q.rv = stream_load_k<KEEP>(vec_src<d2_t>(live, r + i, sc));
+#else
+        q.rv = *vec_src<d2_t>(live, r + i, sc);
+#endif
+        q.tv = stream_load_k<KEEP>(vec_src<d2_t>(live, t + i, sc));
+        if (CODED) q.cc = stream_load_k<KEEP>(vec_src<unsigned>(live, dcode + i, sc));
+        else q.iv = *vec_src<d2_t>(live, invd + i, sc);
+    };
+    VecScalars s = vec_request<FUSED ? 1 : 0>(sc, parity, spmv_partial, nb, 0);
+    Trip ahead[kVecAhead];
+#pragma unroll
+    for (int u = 0; u < kVecAhead; ++u) request(j0 + u * stride, j0 + u * stride < n2, ahead[u]);
+    vec_fold<FUSED ? 1 : 0>(s, spmv_partial, nb, 0, pro);
+    if (s.done) {
+        if (FUSED && blockIdx.x == 0 && threadIdx.x == 0 && s.done == 2) sc->done = 1; // the pending x update has run (OP_ALPHA)
         return;
     }
-    __shared__ double red[4];
     double alpha;
     if (FUSED) {
-        __shared__ double tot;
-        double pap = 0.;
-        for (int k = threadIdx.x; k < nb; k += kBlock) pap += spmv_partial[k];
-        pap = block_sum(pap, red);
-        if (threadIdx.x == 0) tot = pap;
-        __syncthreads();
-        pap = tot;
-        alpha = (parity ? sc->rho_alt : sc->rho) / pap;
+        const double pap = s.sum[0];
+        alpha = s.rho_old / pap;
         if (blockIdx.x == 0 && threadIdx.x == 0) { // what OP_ALPHA does
             sc->red[0] = pap;
             sc->pAp = pap;
             sc->alpha = alpha;
         }
-    } else alpha = sc->alpha;
+    } else alpha = s.alpha;
     double rr = 0., rz = 0.;
-    // t = A p is read for the last time here and r is next read one kernel later: the streams that nobody reads again before they
-    // are overwritten are loaded / stored NON-TEMPORALLY, so that they do not push the matrix out of the caches between two products
-    // (`keep`: matrix and vectors together fit the Infinity Cache -- then everything is left to it)
-    const int64_t n2 = n >> 1; // two rows per thread (16-B accesses), partial sums in the order (even row, odd row)
-    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n2; j += (int64_t)gridDim.x * kBlock) {
+    auto row_pair = [&](int64_t j, const Trip &q) {
         const int64_t i = 2 * j;
-#ifndef AVS_EXP_NO_RNT
-        const d2_t rv = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(r + i));
-#else
-        const d2_t rv = *reinterpret_cast<const d2_t *>(r + i);
-#endif
-        const d2_t tv = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(t + i));
         double id0, id1;
         if (CODED) {
-            const unsigned cc = stream_load_k<KEEP>(reinterpret_cast<const unsigned *>(dcode + i));
-            id0 = invd[cc & 0xffffu];
-            id1 = invd[cc >> 16];
+            id0 = invd[q.cc & 0xffffu];
+            id1 = invd[q.cc >> 16];
         } else {
-            const d2_t iv = *reinterpret_cast<const d2_t *>(invd + i);
-            id0 = iv.x;
-            id1 = iv.y;
+            id0 = q.iv.x;
+            id1 = q.iv.y;
         }
         d2_t rn;
-        rn.x = rv.x - alpha * tv.x;
-        rn.y = rv.y - alpha * tv.y;
+        rn.x = q.rv.x - alpha * q.tv.x;
+        rn.y = q.rv.y - alpha * q.tv.y;
 #ifndef AVS_EXP_NO_RNT
         stream_store_k<KEEP>(rn, reinterpret_cast<d2_t *>(r + i));
 #else
@@ -1038,6 +1130,14 @@ __global__ __launch_bounds__(kBlock) void k_update_r(int64_t n, double *__restri
         rz += rn.x * (id0 * rn.x);
         rr += rn.y * rn.y;
         rz += rn.y * (id1 * rn.y);
+    };
+#pragma unroll
+    for (int u = 0; u < kVecAhead; ++u)
+        if (j0 + u * stride < n2) row_pair(j0 + u * stride, ahead[u]);
+    for (int64_t j = j0 + kVecAhead * stride; j < n2; j += stride) {
+        Trip q;
+        request(j, true, q);
+        row_pair(j, q);
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const int64_t i = n - 1;
@@ -1046,8 +1146,7 @@ __global__ __launch_bounds__(kBlock) void k_update_r(int64_t n, double *__restri
         rr += ri * ri;
         rz += ri * ((CODED ? invd[dcode[i]] : invd[i]) * ri);
     }
-    rr = block_sum(rr, red);
-    rz = block_sum(rz, red);
+    block_sum2(rr, rz, red);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = rr;
         partial[gridDim.x + blockIdx.x] = rz;
@@ -1068,25 +1167,32 @@ __global__ __launch_bounds__(kBlock) void k_update_xp(int64_t n, double *__restr
                                                       const uint16_t *__restrict__ dcode, PcgScalars *sc,
                                                       const double *__restrict__ partial = nullptr, int g = 0, int parity = 0)
 {
-    int done = sc->done;
+    __shared__ double pro[8];
+    // two rows per thread: 16-B loads / stores (the arrays are 16-B aligned; the odd last row goes alone)
+    const int64_t n2 = n >> 1;
+    const int64_t j0 = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+    struct Trip { d2_t pv, xv, rv, iv; unsigned cc; };
+    auto request = [&](int64_t j, bool live, Trip &q) {
+        const int64_t i = 2 * j;
+        q.pv = *vec_src<d2_t>(live, p + i, sc);
+        q.xv = stream_load_k<KEEP>(vec_src<d2_t>(live, x + i, sc));
+        q.rv = stream_load_k<KEEP>(vec_src<d2_t>(live, r + i, sc));
+        if (CODED) q.cc = stream_load_k<KEEP>(vec_src<unsigned>(live, dcode + i, sc));
+        else q.iv = *vec_src<d2_t>(live, invd + i, sc);
+    };
+    VecScalars s = vec_request<FUSED ? 2 : 0>(sc, parity, partial, g, g);
+    Trip ahead[kVecAhead];
+#pragma unroll
+    for (int u = 0; u < kVecAhead; ++u) request(j0 + u * stride, j0 + u * stride < n2, ahead[u]);
+    vec_fold<FUSED ? 2 : 0>(s, partial, g, g, pro);
+    int done = s.done;
     if (done == 1 || done == 3) return;
-    const double alpha = sc->alpha;
-    double beta = FUSED ? 0. : sc->beta;
+    const double alpha = s.alpha;
+    double beta = FUSED ? 0. : s.beta;
     if (FUSED && done == 0) {
-        __shared__ double red[4], tot[2];
-        double rr = 0., rz = 0.;
-        for (int i = threadIdx.x; i < g; i += kBlock) {
-            rr += partial[i];
-            rz += partial[g + i];
-        }
-        rr = block_sum(rr, red);
-        rz = block_sum(rz, red);
-        if (threadIdx.x == 0) { tot[0] = rr; tot[1] = rz; }
-        __syncthreads();
-        rr = tot[0];
-        rz = tot[1];
-        const double absOld = parity ? sc->rho_alt : sc->rho;
-        if (rr < sc->threshold) done = 2; // Eigen: break before i++ (x += alpha p still pending)
+        const double rr = s.sum[0], rz = s.sum[1];
+        const double absOld = s.rho_old;
+        if (rr < s.threshold) done = 2; // Eigen: break before i++ (x += alpha p still pending)
         else beta = rz / absOld;
         if (blockIdx.x == 0 && threadIdx.x == 0) { // what OP_BETA does
             sc->red[0] = rr;
@@ -1101,33 +1207,34 @@ __global__ __launch_bounds__(kBlock) void k_update_xp(int64_t n, double *__restr
             }
         }
     }
-    if (done == 2) {
+    if (done == 2) { // (the loads that went ahead are dropped)
         for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
             x[i] += alpha * p[i];
         return;
     }
-    // two rows per thread: 16-B loads / stores (the arrays are 16-B aligned; the odd last row goes alone)
-    const int64_t n2 = n >> 1;
-    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n2; j += (int64_t)gridDim.x * kBlock) {
+    auto row_pair = [&](int64_t j, const Trip &q) {
         const int64_t i = 2 * j;
-        const d2_t pv = *reinterpret_cast<const d2_t *>(p + i);
-        const d2_t xv = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(x + i));
-        const d2_t rv = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(r + i));
         double id0, id1;
         if (CODED) {
-            const unsigned cc = stream_load_k<KEEP>(reinterpret_cast<const unsigned *>(dcode + i));
-            id0 = invd[cc & 0xffffu];
-            id1 = invd[cc >> 16];
+            id0 = invd[q.cc & 0xffffu];
+            id1 = invd[q.cc >> 16];
         } else {
-            const d2_t iv = *reinterpret_cast<const d2_t *>(invd + i);
-            id0 = iv.x;
-            id1 = iv.y;
+            id0 = q.iv.x;
+            id1 = q.iv.y;
         }
         d2_t xn, pn;
-        xn.x = xv.x + alpha * pv.x;       xn.y = xv.y + alpha * pv.y;
-        pn.x = id0 * rv.x + beta * pv.x;  pn.y = id1 * rv.y + beta * pv.y;
+        xn.x = q.xv.x + alpha * q.pv.x;       xn.y = q.xv.y + alpha * q.pv.y;
+        pn.x = id0 * q.rv.x + beta * q.pv.x;  pn.y = id1 * q.rv.y + beta * q.pv.y;
         stream_store_k<KEEP>(xn, reinterpret_cast<d2_t *>(x + i)); // (x is touched once per iteration)
         *reinterpret_cast<d2_t *>(p + i) = pn;
+    };
+#pragma unroll
+    for (int u = 0; u < kVecAhead; ++u)
+        if (j0 + u * stride < n2) row_pair(j0 + u * stride, ahead[u]);
+    for (int64_t j = j0 + kVecAhead * stride; j < n2; j += stride) {
+        Trip q;
+        request(j, true, q);
+        row_pair(j, q);
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const int64_t i = n - 1;
@@ -2721,6 +2828,60 @@ avs_status spmv_sell_launch(int64_t nslices, const int64_t *slice_ptr, const int
     return AVS_OK;
 }
 
+// probe / test entry: one update_r launch followed by one update_xp launch of the launch-per-phase loops, any instantiation, on a grid
+// of `g` workgroups and a caller's PcgScalars image (the loops reach g < kVecGrid only with one trip per thread, and KEEP = false only
+// beyond the Infinity Cache)
+template <bool CODED, bool FUSED, bool KEEP>
+static void vector_probe_f64(int g, int64_t n, int nb, int parity, double *x, double *p, double *r, const double *t, const double *invd,
+                             const uint16_t *dcode, const double *spmv_partial, double *vpart, PcgScalars *sc, hipStream_t stream)
+{
+    // (the unfused form as pcg_solve launches it: OP_ALPHA / OP_BETA have left the scalars, no parity)
+    hipLaunchKernelGGL((k_update_r<CODED, FUSED, KEEP>), dim3(g), dim3(kBlock), 0, stream, n, r, t, invd, dcode, sc, vpart,
+                       FUSED ? spmv_partial : nullptr, FUSED ? nb : 0, FUSED ? parity : 0);
+    hipLaunchKernelGGL((k_update_xp<CODED, FUSED, KEEP>), dim3(g), dim3(kBlock), 0, stream, n, x, p, (const double *)r, invd, dcode, sc,
+                       FUSED ? (const double *)vpart : nullptr, FUSED ? g : 0, FUSED ? parity : 0);
+}
+template <bool CODED, bool FUSED, bool KEEP, bool DS>
+static void vector_probe_f32(int g, int64_t n, int nb, int parity, float *x, float *p, float *r, const float *t, const float *invd,
+                             const uint16_t *dcode, const double *spmv_partial, double *vpart, PcgScalars *sc, hipStream_t stream)
+{
+    // (the float loops have no unfused k_f32_update_xp: OP_ALPHA, then both kernels with the iteration's parity)
+    hipLaunchKernelGGL((k_f32_update_r<CODED, FUSED, KEEP, DS>), dim3(g), dim3(kBlock), 0, stream, n, r, t, invd, dcode, sc, vpart,
+                       FUSED ? spmv_partial : nullptr, FUSED ? nb : 0, parity);
+    hipLaunchKernelGGL((k_f32_update_xp<CODED, KEEP, DS>), dim3(g), dim3(kBlock), 0, stream, n, x, p, (const float *)r, invd, dcode, sc,
+                       (const double *)vpart, g, parity);
+}
+size_t vector_update_probe_scalars_size() { return sizeof(PcgScalars); }
+avs_status vector_update_probe(int flags, int g, int64_t n, int nb, int parity, void *x, void *p, void *r, const void *t, const void *invd,
+                               const uint16_t *dcode, const double *spmv_partial, double *vpart, void *scalars, hipStream_t stream)
+{
+    PcgScalars *sc = static_cast<PcgScalars *>(scalars);
+    const bool ds = (flags & AVS_VECTOR_PROBE_DS) != 0, f32 = ds || (flags & AVS_VECTOR_PROBE_F32) != 0;
+    const int sel = ((flags & AVS_VECTOR_PROBE_CODED) ? 4 : 0) | ((flags & AVS_VECTOR_PROBE_FUSED) ? 2 : 0) | ((flags & AVS_VECTOR_PROBE_KEEP) ? 1 : 0);
+#define AVS_PROBE_CASE(S, C, F, K)                                                                                                        \
+    case S:                                                                                                                               \
+        if (!f32) vector_probe_f64<C, F, K>(g, n, nb, parity, (double *)x, (double *)p, (double *)r, (const double *)t, (const double *)invd, \
+                                            dcode, spmv_partial, vpart, sc, stream);                                                      \
+        else if (ds) vector_probe_f32<C, F, K, true>(g, n, nb, parity, (float *)x, (float *)p, (float *)r, (const float *)t,              \
+                                                     (const float *)invd, dcode, spmv_partial, vpart, sc, stream);                        \
+        else vector_probe_f32<C, F, K, false>(g, n, nb, parity, (float *)x, (float *)p, (float *)r, (const float *)t, (const float *)invd, \
+                                              dcode, spmv_partial, vpart, sc, stream);                                                    \
+        break;
+    switch (sel) {
+        AVS_PROBE_CASE(0, false, false, false)
+        AVS_PROBE_CASE(1, false, false, true)
+        AVS_PROBE_CASE(2, false, true, false)
+        AVS_PROBE_CASE(3, false, true, true)
+        AVS_PROBE_CASE(4, true, false, false)
+        AVS_PROBE_CASE(5, true, false, true)
+        AVS_PROBE_CASE(6, true, true, false)
+        AVS_PROBE_CASE(7, true, true, true)
+    }
+#undef AVS_PROBE_CASE
+    AVS_HIP(hipGetLastError());
+    return AVS_OK;
+}
+
 #endif
 
 } // namespace avs
@@ -2738,5 +2899,17 @@ extern "C" avs_status avs_spmv_sell(int64_t nslices, const int64_t *slice_ptr, c
     const double ms = t.stop() / repeats;
     if (ms_per_launch) *ms_per_launch = ms;
     return AVS_OK;
+}
+
+extern "C" avs_status avs_vector_update_probe(int32_t flags, int32_t g, int64_t n, int32_t nb, int32_t parity, void *x, void *p, void *r,
+                                              const void *t, const void *invd, const uint16_t *dcode, const double *spmv_partial,
+                                              double *vpart, void *scalars, int32_t scalars_bytes, void *stream)
+{
+    AVS_REQUIRE(x && p && r && t && invd && vpart && scalars && n > 0 && g >= 1 && g <= 2048 && nb >= 0, AVS_EINVAL, "bad argument");
+    AVS_REQUIRE((parity == 0 || parity == 1) && (dcode || !(flags & AVS_VECTOR_PROBE_CODED)) && (spmv_partial || !(flags & AVS_VECTOR_PROBE_FUSED)),
+                AVS_EINVAL, "bad argument");
+    AVS_REQUIRE((size_t)scalars_bytes == avs::vector_update_probe_scalars_size(), AVS_EINVAL, "the scalars image has another size");
+    return avs::vector_update_probe(flags, g, n, nb, parity, x, p, r, t, invd, dcode, spmv_partial, vpart, scalars,
+                                    reinterpret_cast<hipStream_t>(stream));
 }
 #endif // AVS_PROBES

@@ -171,44 +171,51 @@ __global__ __launch_bounds__(kBlock) void k_f32_update_r(int64_t n, float *__res
                                                          const float *__restrict__ invd, const uint16_t *__restrict__ dcode, PcgScalars *sc,
                                                          double *__restrict__ partial, const double *__restrict__ spmv_partial, int nb, int parity)
 {
-    if (sc->done) {
-        if (FUSED && blockIdx.x == 0 && threadIdx.x == 0 && sc->done == 2) sc->done = 1; // the pending x update has run (OP_ALPHA)
+    __shared__ double pro[8], red[8];
+    // (the partial sums and the loads of the first kVecAhead trips are requested before anything is waited for: vec_request, avs_pcg.hip)
+    const int64_t n4 = n >> 2;
+    const int64_t j0 = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+    struct Trip { f4_t rv, tv, iv; u2_t cc; };
+    auto request = [&](int64_t j, bool live, Trip &q) {
+        const int64_t i = 4 * j;
+        q.rv = *vec_src<f4_t>(live, r + i, sc);
+        q.tv = stream_load_k<KEEP>(vec_src<f4_t>(live, t + i, sc));
+        if (CODED) q.cc = stream_load_k<KEEP>(vec_src<u2_t>(live, dcode + i, sc));
+        else q.iv = *vec_src<f4_t>(live, invd + i, sc);
+    };
+    VecScalars s = vec_request<FUSED ? 1 : 0>(sc, parity, spmv_partial, nb, 0);
+    Trip ahead[kVecAhead];
+#pragma unroll
+    for (int u = 0; u < kVecAhead; ++u) request(j0 + u * stride, j0 + u * stride < n4, ahead[u]);
+    vec_fold<FUSED ? 1 : 0>(s, spmv_partial, nb, 0, pro);
+    if (s.done) {
+        if (FUSED && blockIdx.x == 0 && threadIdx.x == 0 && s.done == 2) sc->done = 1; // the pending x update has run (OP_ALPHA)
         return;
     }
-    __shared__ double red[4];
     float alpha;
     if (FUSED) {
-        __shared__ double tot;
-        double pap = 0.;
-        for (int k = threadIdx.x; k < nb; k += kBlock) pap += spmv_partial[k];
-        pap = block_sum(pap, red);
-        if (threadIdx.x == 0) tot = pap;
-        __syncthreads();
-        pap = tot;
-        const double alpha_d = (parity ? sc->rho_alt : sc->rho) / pap;
-        alpha = DS ? (float)alpha_d : (float)(parity ? sc->rho_alt : sc->rho) / (float)pap;
+        const double pap = s.sum[0];
+        const double alpha_d = s.rho_old / pap;
+        alpha = DS ? (float)alpha_d : (float)s.rho_old / (float)pap;
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             sc->red[0] = pap;
             sc->pAp = DS ? pap : (double)(float)pap;
             sc->alpha = DS ? alpha_d : (double)alpha;
         }
     } else if (DS) {
-        alpha = (float)sc->alpha; // (OP_ALPHA's double quotient)
+        alpha = (float)s.alpha; // (OP_ALPHA's double quotient)
     } else {
-        alpha = (float)(parity ? sc->rho_alt : sc->rho) / (float)sc->pAp;
+        alpha = (float)s.rho_old / (float)s.pAp;
         if (blockIdx.x == 0 && threadIdx.x == 0) sc->alpha = (double)alpha; // (OP_ALPHA divided in double: k_f32_update_xp reads this one)
     }
     float rr = 0.f, rz = 0.f;
-    const int64_t n4 = n >> 2;
-    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n4; j += (int64_t)gridDim.x * kBlock) {
+    auto row_quad = [&](int64_t j, const Trip &q) {
         const int64_t i = 4 * j;
-        const f4_t rv = *reinterpret_cast<const f4_t *>(r + i);
-        const f4_t tv = stream_load_k<KEEP>(reinterpret_cast<const f4_t *>(t + i));
-        f4_t iv;
+        const f4_t rv = q.rv, tv = q.tv;
+        f4_t iv = q.iv;
         if (CODED) {
-            const u2_t cc = stream_load_k<KEEP>(reinterpret_cast<const u2_t *>(dcode + i));
-            iv.x = invd[cc.x & 0xffffu]; iv.y = invd[cc.x >> 16]; iv.z = invd[cc.y & 0xffffu]; iv.w = invd[cc.y >> 16];
-        } else iv = *reinterpret_cast<const f4_t *>(invd + i);
+            iv.x = invd[q.cc.x & 0xffffu]; iv.y = invd[q.cc.x >> 16]; iv.z = invd[q.cc.y & 0xffffu]; iv.w = invd[q.cc.y >> 16];
+        }
         f4_t rn;
         rn.x = rv.x - alpha * tv.x; rn.y = rv.y - alpha * tv.y; rn.z = rv.z - alpha * tv.z; rn.w = rv.w - alpha * tv.w;
         *reinterpret_cast<f4_t *>(r + i) = rn;
@@ -216,6 +223,14 @@ __global__ __launch_bounds__(kBlock) void k_f32_update_r(int64_t n, float *__res
         rr += rn.y * rn.y; rz += rn.y * (iv.y * rn.y);
         rr += rn.z * rn.z; rz += rn.z * (iv.z * rn.z);
         rr += rn.w * rn.w; rz += rn.w * (iv.w * rn.w);
+    };
+#pragma unroll
+    for (int u = 0; u < kVecAhead; ++u)
+        if (j0 + u * stride < n4) row_quad(j0 + u * stride, ahead[u]);
+    for (int64_t j = j0 + kVecAhead * stride; j < n4; j += stride) {
+        Trip q;
+        request(j, true, q);
+        row_quad(j, q);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
         for (int64_t i = n4 * 4; i < n; ++i) {
@@ -224,8 +239,8 @@ __global__ __launch_bounds__(kBlock) void k_f32_update_r(int64_t n, float *__res
             rr += ri * ri;
             rz += ri * ((CODED ? invd[dcode[i]] : invd[i]) * ri);
         }
-    const double srr = block_sum((double)rr, red);
-    const double srz = block_sum((double)rz, red);
+    double srr = (double)rr, srz = (double)rz;
+    block_sum2(srr, srz, red);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = srr;
         partial[gridDim.x + blockIdx.x] = srz;
@@ -241,25 +256,32 @@ __global__ __launch_bounds__(kBlock) void k_f32_update_xp(int64_t n, float *__re
                                                           const float *__restrict__ invd, const uint16_t *__restrict__ dcode, PcgScalars *sc,
                                                           const double *__restrict__ partial, int g, int parity)
 {
-    int done = sc->done;
+    __shared__ double pro[8];
+    const int64_t n4 = n >> 2;
+    const int64_t j0 = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
+    struct Trip { f4_t pv, xv, rv, iv; u2_t cc; };
+    auto request = [&](int64_t j, bool live, Trip &q) {
+        const int64_t i = 4 * j;
+        q.pv = *vec_src<f4_t>(live, p + i, sc);
+        q.xv = stream_load_k<KEEP>(vec_src<f4_t>(live, x + i, sc));
+        q.rv = stream_load_k<KEEP>(vec_src<f4_t>(live, r + i, sc));
+        if (CODED) q.cc = stream_load_k<KEEP>(vec_src<u2_t>(live, dcode + i, sc));
+        else q.iv = *vec_src<f4_t>(live, invd + i, sc);
+    };
+    VecScalars s = vec_request<2>(sc, parity, partial, g, g);
+    Trip ahead[kVecAhead];
+#pragma unroll
+    for (int u = 0; u < kVecAhead; ++u) request(j0 + u * stride, j0 + u * stride < n4, ahead[u]);
+    vec_fold<2>(s, partial, g, g, pro);
+    int done = s.done;
     if (done == 1 || done == 3) return;
-    const float alpha = (float)sc->alpha;
+    const float alpha = (float)s.alpha;
     float beta = 0.f;
     if (done == 0) {
-        __shared__ double red[4], tot[2];
-        double rr = 0., rz = 0.;
-        for (int i = threadIdx.x; i < g; i += kBlock) {
-            rr += partial[i];
-            rz += partial[g + i];
-        }
-        rr = block_sum(rr, red);
-        rz = block_sum(rz, red);
-        if (threadIdx.x == 0) { tot[0] = rr; tot[1] = rz; }
-        __syncthreads();
         if (DS) {
-            const double rrd = tot[0], rzd = tot[1];
-            const double absOld = parity ? sc->rho_alt : sc->rho;
-            if (rrd < sc->threshold) done = 2;
+            const double rrd = s.sum[0], rzd = s.sum[1];
+            const double absOld = s.rho_old;
+            if (rrd < s.threshold) done = 2;
             else beta = (float)(rzd / absOld);
             if (blockIdx.x == 0 && threadIdx.x == 0) {
                 sc->red[0] = rrd;
@@ -276,9 +298,9 @@ __global__ __launch_bounds__(kBlock) void k_f32_update_xp(int64_t n, float *__re
                 }
             }
         } else {
-            const float rrf = (float)tot[0], rzf = (float)tot[1];
-            const float absOld = (float)(parity ? sc->rho_alt : sc->rho);
-            if (rrf < (float)sc->threshold) done = 2; // Eigen: break before i++ (x += alpha p still pending)
+            const float rrf = (float)s.sum[0], rzf = (float)s.sum[1];
+            const float absOld = (float)s.rho_old;
+            if (rrf < (float)s.threshold) done = 2; // Eigen: break before i++ (x += alpha p still pending)
             else beta = rzf / absOld;
             if (blockIdx.x == 0 && threadIdx.x == 0) { // what OP_BETA does
                 sc->red[0] = (double)rrf;
@@ -294,26 +316,30 @@ __global__ __launch_bounds__(kBlock) void k_f32_update_xp(int64_t n, float *__re
             }
         }
     }
-    if (done == 2) {
+    if (done == 2) { // (the loads that went ahead are dropped)
         for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) x[i] += alpha * p[i];
         return;
     }
-    const int64_t n4 = n >> 2;
-    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n4; j += (int64_t)gridDim.x * kBlock) {
+    auto row_quad = [&](int64_t j, const Trip &q) {
         const int64_t i = 4 * j;
-        const f4_t pv = *reinterpret_cast<const f4_t *>(p + i);
-        const f4_t xv = stream_load_k<KEEP>(reinterpret_cast<const f4_t *>(x + i));
-        const f4_t rv = stream_load_k<KEEP>(reinterpret_cast<const f4_t *>(r + i));
-        f4_t iv;
+        const f4_t pv = q.pv, xv = q.xv, rv = q.rv;
+        f4_t iv = q.iv;
         if (CODED) {
-            const u2_t cc = stream_load_k<KEEP>(reinterpret_cast<const u2_t *>(dcode + i));
-            iv.x = invd[cc.x & 0xffffu]; iv.y = invd[cc.x >> 16]; iv.z = invd[cc.y & 0xffffu]; iv.w = invd[cc.y >> 16];
-        } else iv = *reinterpret_cast<const f4_t *>(invd + i);
+            iv.x = invd[q.cc.x & 0xffffu]; iv.y = invd[q.cc.x >> 16]; iv.z = invd[q.cc.y & 0xffffu]; iv.w = invd[q.cc.y >> 16];
+        }
         f4_t xn, pn;
         xn.x = xv.x + alpha * pv.x; xn.y = xv.y + alpha * pv.y; xn.z = xv.z + alpha * pv.z; xn.w = xv.w + alpha * pv.w;
         pn.x = iv.x * rv.x + beta * pv.x; pn.y = iv.y * rv.y + beta * pv.y; pn.z = iv.z * rv.z + beta * pv.z; pn.w = iv.w * rv.w + beta * pv.w;
         stream_store_k<KEEP>(xn, reinterpret_cast<f4_t *>(x + i));
         *reinterpret_cast<f4_t *>(p + i) = pn;
+    };
+#pragma unroll
+    for (int u = 0; u < kVecAhead; ++u)
+        if (j0 + u * stride < n4) row_quad(j0 + u * stride, ahead[u]);
+    for (int64_t j = j0 + kVecAhead * stride; j < n4; j += stride) {
+        Trip q;
+        request(j, true, q);
+        row_quad(j, q);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
         for (int64_t i = n4 * 4; i < n; ++i) {

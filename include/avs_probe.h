@@ -71,6 +71,26 @@ typedef struct {
 avs_status avs_brick_spmv_probe(const avs_brick_arrays *a, const double *x, double *y, double *partial, int32_t repeats, void *stream,
                                 double *ms_per_launch);
 
+/* The two vector kernels of one iteration of the launch-per-phase PCG loops -- update_r (r -= alpha A p, partial sums of r.r and r.z),
+ * then update_xp (x += alpha p ; p = z + beta p) -- launched once each on the caller's device arrays with `g` workgroups (1 .. 2048).  The
+ * product path reaches neither several trips per thread on a small grid nor the non-temporal instantiations below 200 MiB; this entry does.
+ * flags: AVS_VECTOR_PROBE_F32 float vectors and float scalars (AVS_PRECISION_F32), AVS_VECTOR_PROBE_DS float vectors and double scalars (the
+ * mixed-precision loop); neither: fp64.  AVS_VECTOR_PROBE_CODED: invd is the table of inverted values (as many entries as the codes reach)
+ * and dcode holds a 2-B code per row, else invd has an entry per row and dcode may be NULL.  AVS_VECTOR_PROBE_KEEP: plain loads and stores
+ * instead of non-temporal ones.  AVS_VECTOR_PROBE_FUSED: the kernels fold the partial sums and take the scalar steps themselves
+ * (spmv_partial: nb partial sums of p.Ap); without it the scalars image holds what OP_ALPHA / OP_BETA leave (the float loops have a fused
+ * update_xp only).  x, p, r, t and invd are arrays of the vector type (16-B aligned), vpart receives 2 g partial sums, `scalars` is a
+ * device image of the library's PcgScalars (scalars_bytes must be its size: seven doubles rho, pAp, rr, alpha, beta, threshold, rhs_norm2,
+ * four doubles of staging, the ints iter, done, fault, cancelled, the double rho_alt) and is updated in place. */
+#define AVS_VECTOR_PROBE_F32 1
+#define AVS_VECTOR_PROBE_DS 2
+#define AVS_VECTOR_PROBE_CODED 4
+#define AVS_VECTOR_PROBE_KEEP 8
+#define AVS_VECTOR_PROBE_FUSED 16
+avs_status avs_vector_update_probe(int32_t flags, int32_t g, int64_t n, int32_t nb, int32_t parity, void *x, void *p, void *r, const void *t,
+                                   const void *invd, const uint16_t *dcode, const double *spmv_partial, double *vpart, void *scalars,
+                                   int32_t scalars_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
