@@ -32,6 +32,7 @@ PRECISION_F64, PRECISION_F32 = 0, 1   # avs_desc.precision (SolveType of the ref
 OPTION_RESIDENT_F32 = 12   # (11 is not assigned)
 OPTION_RESIDENT_LOCAL_TABLES = 13
 OPTION_MIXED_PRECISION = 14
+OPTION_DIST_MIXED_PRECISION = 15
 USE_TRANSPORT_AUTO, USE_TRANSPORT_RCCL, USE_TRANSPORT_DIRECT = 0, 1, 2
 BRICK_AUTO, BRICK_NEVER, BRICK_ALWAYS, BRICK_TUNE = -1, 0, 1, 2
 PRECONDITIONER_JACOBI, PRECONDITIONER_NONE = 0, 1

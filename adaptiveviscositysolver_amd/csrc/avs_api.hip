@@ -114,6 +114,7 @@ Options options_from_env()
     o.resident_f32 = env_int("AVS_RESIDENT_F32", 0) != 0;
     o.resident_local_tables = env_int("AVS_RESIDENT_LOCAL_TABLES", 0) != 0;
     o.mixed_precision = env_int("AVS_MIXED_PRECISION", 0) != 0;
+    o.dist_mixed_precision = env_int("AVS_DIST_MIXED_PRECISION", 0) != 0;
     o.prepass_temporal = env_int("AVS_PREPASS_TEMPORAL", 1) != 0;
     { const int v = env_int("AVS_POST_DOF_SAMPLE", -1); o.post_dof_sample = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.resident_cus = env_int("AVS_CG_RESIDENT_CUS", 0);
@@ -679,6 +680,7 @@ avs_status avs_set_solver_option(avs_ctx *c, avs_solver_option option, int32_t v
     case AVS_OPTION_RESIDENT_F32: c->opt.resident_f32 = value != 0; return AVS_OK;
     case AVS_OPTION_RESIDENT_LOCAL_TABLES: c->opt.resident_local_tables = value != 0; return AVS_OK;
     case AVS_OPTION_MIXED_PRECISION: c->opt.mixed_precision = value != 0; return AVS_OK;
+    case AVS_OPTION_DIST_MIXED_PRECISION: c->opt.dist_mixed_precision = value != 0; return AVS_OK;
     }
     set_error("unknown solver option %d", (int)option);
     return AVS_EINVAL;

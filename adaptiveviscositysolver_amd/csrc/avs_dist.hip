@@ -81,6 +81,8 @@ struct PcgDist {
     bool partitioned = false, solved = false, reordered = false;
     bool f32 = false; // AVS_PRECISION_F32 + AVS_OPTION_DIST_F32_VECTORS when this plan was made: the single-reduction loops run on float vectors
     bool resident_f32 = false; // ... + AVS_OPTION_RESIDENT_F32: the CU-resident loop between ranks runs on float vectors too
+    bool mixed = false; // AVS_PRECISION_F64 + AVS_OPTION_DIST_MIXED_PRECISION when this plan was made: the single-reduction loops run on float
+                        // vectors with fp64 scalars and reliable updates (the brick walk is laid out for the mixed kernel)
     DevBuf<double> recvbuf; // float halo exchange (RCCL / in-process): the peers' entries, widened, before they are narrowed into the vector
     // slab cuts along cut_axis (fine cells, world + 1 entries): the ones this assembly used, and the ones its per-plane weights suggest
     // for the next frame (slab-local assembly: the pre-pass needs the cuts BEFORE anything is counted)
@@ -1266,13 +1268,16 @@ static avs_status dist_build_brick(avs_ctx *c, PcgDist *d)
         else {
             d->brick.view(d->brick_view, d->vi);
             d->brick_view.walk = fill >= kBrickEighthsFill ? 0 : 1;
-            d->brick_view.f32 = d->f32 ? 1 : 0; // the float-vector loop launches the float kernel: the walk is laid out for ITS grid
+            // the float-vector loop launches the float kernel, the mixed-precision loop k_spmv_brick<.., float, double>: the walk is laid out
+            // for ITS grid (the fp64 product of the reliable updates follows the plan where its grid is the same, else its strided walk)
+            const int view_f32 = d->mixed ? 2 : d->f32 ? 1 : 0;
+            d->brick_view.f32 = view_f32;
             if (c->opt.brick_plan) {
                 const int walk = d->brick_view.walk;
                 AVS_TRY(d->brick.plan_walk(brick_partial_count(d->brick_view), walk, c->opt.brick_cost, c->stream));
                 d->brick.view(d->brick_view, d->vi);
                 d->brick_view.walk = walk;
-                d->brick_view.f32 = d->f32 ? 1 : 0;
+                d->brick_view.f32 = view_f32;
             }
             return AVS_OK;
         }
@@ -1992,6 +1997,7 @@ avs_status avs_dist_partition(avs_ctx *c, int32_t cut_axis)
     const bool host_plan = cur_opt().dist_host_plan != 0;
     d->f32 = c->desc.precision == AVS_PRECISION_F32 && c->opt.dist_f32_vectors != 0;
     d->resident_f32 = d->f32 && c->opt.resident_f32 != 0;
+    d->mixed = c->desc.precision == AVS_PRECISION_F64 && c->opt.dist_mixed_precision != 0;
     d->vi.clear();
     d->brick.clear();   // (the brick-structured form is built for distributed assemblies only: avs_dist_assemble)
     d->brick.view(d->brick_view, d->vi);
@@ -2075,6 +2081,7 @@ avs_status avs_dist_assemble(avs_ctx *c, int32_t cut_axis, avs_assembly_info *in
     c->reordered = false;
     d->f32 = c->desc.precision == AVS_PRECISION_F32 && c->opt.dist_f32_vectors != 0;
     d->resident_f32 = d->f32 && c->opt.resident_f32 != 0;
+    d->mixed = c->desc.precision == AVS_PRECISION_F64 && c->opt.dist_mixed_precision != 0;
     d->vi.clear();
     if (c->slab.on) AVS_TRY(dist_assemble_window(c, d));
     else AVS_TRY(dist_assemble_device(c, d, cut_axis, extent));
@@ -2229,9 +2236,11 @@ avs_status avs_dist_solve(avs_ctx *c, double tol, int32_t max_iters, avs_solve_i
     A.brick = d->brick.ready ? &d->brick_view : nullptr;
     A.f32_vectors = d->f32 ? 1 : 0;
     A.resident_f32 = d->resident_f32 ? 1 : 0;
+    A.mixed = d->mixed ? 1 : 0; // (AVS_OPTION_DIST_MIXED_PRECISION; AVS_OPTION_MIXED_PRECISION has no effect here)
     avs_solve_info local{};
     const avs_status rc = pcg_solve(d->pcg, A, d->rhs.p, d->x.p, tol, max_iters, c->stream, &local, d);
     c->float_vectors = pcg_float_vectors(d->pcg);
+    c->reliable_updates = pcg_reliable_updates(d->pcg);
     if (rc != AVS_OK) {
         // a peer's flag timed out: epochs / tickets of the comm blocks are no longer in step -- every rank sees the same fault
         // (it waits for the same peer) and leaves the direct transport for this plan; the next solve uses the fallback
@@ -2266,6 +2275,13 @@ avs_status avs_dist_spmv_local_form(avs_ctx *c, const double *x_ext, double *y, 
     d->vi.apply(A);
     A.brick = d->brick.ready ? &d->brick_view : nullptr;
     if (A.n == 0) return AVS_OK;
+    // a plan latched with AVS_OPTION_DIST_MIXED_PRECISION: the mixed-precision loops' product on the float values of x_ext; fused_dot & 2
+    // asks for the fp64 product of its reliable updates instead (as avs_spmv_solver_form)
+    if (d->mixed && !(fused_dot & 2)) {
+        AVS_TRY(spmv_mixed_probe(A, x_ext, y, (fused_dot & 1) != 0, dot_out, c->stream, d->n_own + d->n_halo));
+        return AVS_OK;
+    }
+    fused_dot &= 1;
     AVS_TRY(probe_spmv_form(A, x_ext, y, fused_dot != 0, dot_out, c->stream));
     AVS_HIP(hipStreamSynchronize(c->stream));
     return AVS_OK;

@@ -121,6 +121,9 @@ struct Options {
                                  // with it: PcgDist::resident_f32)
     int mixed_precision = 0;     // AVS_MIXED_PRECISION: fp64 contexts' single-GPU launch-per-phase solves iterate on float vectors with fp64 residual
                                  // updates (avs_pcg_mixed.inl); latched at avs_assemble (avs_ctx::mixed)
+    int dist_mixed_precision = 0; // AVS_DIST_MIXED_PRECISION: fp64 contexts' partitioned single-reduction loops iterate on float vectors with fp64
+                                 // scalars and reliable updates (pcg_solve_single_reduction<float, true>, pcg_solve_direct<float, true>);
+                                 // latched by the next avs_dist_partition / avs_dist_assemble (PcgDist::mixed)
     int resident_local_tables = 0; // AVS_RESIDENT_LOCAL_TABLES: the CU-resident loop takes matrices without one small dictionary too, with a value
                                  // table per workgroup / per wave built by the plan (k_resident_local_tables)
     // CU-resident loop: tuning and test switches
@@ -374,7 +377,8 @@ struct CsrView {
     int resident_f32 = 0; // AVS_PRECISION_F32 + AVS_OPTION_RESIDENT_F32: a solve that iterates on float vectors (f32_vectors != 0) does so in the
                           // CU-resident loop too, where the system qualifies
     int mixed = 0; // AVS_PRECISION_F64 + AVS_OPTION_MIXED_PRECISION (as of the last avs_assemble): a single-GPU solve the launch-per-phase loop
-                   // would run iterates on float vectors with fp64 residual updates (avs_pcg_mixed.inl)
+                   // would run iterates on float vectors with fp64 residual updates (avs_pcg_mixed.inl); the local rows of a partitioned
+                   // plan: AVS_OPTION_DIST_MIXED_PRECISION as of that plan (the single-reduction loops' mixed-precision form)
 };
 constexpr int kCwinOffBits = 14, kCwinSlotBits = 6, kCwinSlots = 1 << kCwinSlotBits, kCwinCodeBits = 32 - kCwinOffBits - kCwinSlotBits;
 
@@ -722,7 +726,7 @@ avs_status build_brick_form(struct ::avs_ctx *c); // avs_brick_build.hip
 // y = A x through the form the loops launch (+ the folded partial sums of x.y of the fused-dot instantiation); avs_api.hip
 avs_status probe_spmv_form(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st);
 avs_status spmv_f32_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st); // avs_pcg_f32.inl
-avs_status spmv_mixed_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st); // avs_pcg_mixed.inl
+avs_status spmv_mixed_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st, int64_t n_cols = 0); // avs_pcg_mixed.inl
 #endif
 avs_status unpermute(struct ::avs_ctx *c, const double *xp, double *x);
 // builds the value dictionary of `val` (nnz entries); *table_size = 0 when there are more than 65536 distinct values

@@ -36,7 +36,7 @@ static constexpr int kSampleEvery = 4;       // SpMV launches bracketed by HIP e
 // What a captured chunk (PcgWork::graph) was recorded against: the loop, the buffers and sizes its launches read, its flags and the
 // tolerance.  It is replayed only while every field matches.  Each loop sets what it depends on and leaves the rest zero; the loop tag
 // keeps one loop from ever replaying another's graph on the same workspace.
-enum GraphLoop { kGraphF64 = 1, kGraphF32, kGraphDirect, kGraphDirectF32, kGraphMixed };
+enum GraphLoop { kGraphF64 = 1, kGraphF32, kGraphDirect, kGraphDirectF32, kGraphMixed, kGraphDirectMixed };
 struct GraphKey {
     int loop = 0;
     const void *row_ptr = nullptr, *col = nullptr, *val = nullptr, *codes = nullptr, *packed = nullptr, *table = nullptr;
@@ -1853,7 +1853,9 @@ __global__ __launch_bounds__(kBlock) void k_sr_init(int64_t n, const double *__r
 // state `out` (a different PcgScalars: nobody reads what is being written) -- one launch less per iteration of a loop
 // that is launch-bound at 8 GPUs.  in == out and step == 0: scalars are used as they are.
 //   p = u + beta p, s = w + beta s, x += alpha p, r -= alpha s, u = M^-1 r ; partials r.u, r.r
-template <typename T, bool CODED>
+// S, the scalar type: T, or double next to T = float (the mixed-precision loops, AVS_OPTION_DIST_MIXED_PRECISION): the step is
+// sr_step<double>, every dot term is widened before it is multiplied, and x is the correction xf.
+template <typename T, bool CODED, typename S = T>
 __global__ __launch_bounds__(kBlock) void k_sr_update(int64_t n, T *__restrict__ x, T *__restrict__ r, T *__restrict__ p,
                                                       T *__restrict__ s, T *__restrict__ u, const T *__restrict__ w,
                                                       const T *__restrict__ invd, const uint16_t *__restrict__ dcode,
@@ -1864,7 +1866,7 @@ __global__ __launch_bounds__(kBlock) void k_sr_update(int64_t n, T *__restrict__
     if (step) {
         double rr = in->rr, rho = in->rho;
         int iter = in->iter;
-        sr_step<T>(in, rr, rho, alpha, beta, iter, done);
+        sr_step<S>(in, rr, rho, alpha, beta, iter, done);
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             PcgScalars o = *in;
             o.rr = rr; o.rho = rho; o.alpha = alpha; o.beta = beta; o.iter = iter; o.done = done;
@@ -1874,7 +1876,7 @@ __global__ __launch_bounds__(kBlock) void k_sr_update(int64_t n, T *__restrict__
     if (done) return; // (rhs == 0, done == 3: the host zeroes x)
     const T a = (T)alpha, bt = (T)beta;
     __shared__ double red[4];
-    T ru = 0, rr = 0;
+    S ru = 0, rr = 0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         const T pi = u[i] + bt * p[i];
         const T si = w[i] + bt * s[i];
@@ -1885,8 +1887,8 @@ __global__ __launch_bounds__(kBlock) void k_sr_update(int64_t n, T *__restrict__
         r[i] = ri;
         const T ui = (CODED ? invd[dcode[i]] : invd[i]) * ri;
         u[i] = ui;
-        ru += ri * ui;
-        rr += ri * ri;
+        ru += (S)ri * (S)ui;
+        rr += (S)ri * (S)ri;
     }
     const double su = block_sum((double)ru, red);
     const double sr = block_sum((double)rr, red);
@@ -1894,6 +1896,72 @@ __global__ __launch_bounds__(kBlock) void k_sr_update(int64_t n, T *__restrict__
         partial[blockIdx.x] = su;
         partial[gridDim.x + blockIdx.x] = sr;
     }
+}
+
+// The mixed-precision form of the two loops (AVS_OPTION_DIST_MIXED_PRECISION; the scheme of avs_pcg_mixed.inl on the single-reduction
+// iteration): r, u, w, p, s and the correction xf are float, x, b, the matrix values, every row sum, every dot product and the scalars
+// stay fp64.  The reliable update runs behind every chunk, outside the captured graph: x += xf (k_mixed_fold), x exchanged in fp64,
+// t64 = A x with the rank's fp64 product, the kernel below, u exchanged, w = A u with w.u, and the Chronopoulos-Gear step on the TRUE
+// residual's sums (k_sr_mixed_step) IN PLACE OF the step of the chunk's last iteration -- which is therefore never taken on the
+// recurrence's sums: the RCCL loop drops its explicit k_scalar behind the chunk, the last round of a chunk of the direct loop folds its
+// sums with OP_NONE.  A chunk the recurrence froze (its r.r passed the threshold) left rho and alpha of the step it did not take: the
+// same update either confirms the claim on the fp64 residual or takes that step.
+//
+// r64 = b - t64 ; r = (float) r64 ; u = D^-1 r (stored: the next product's input).  partials: [0..g) r.u of the ROUNDED residual,
+// [g..2g) |r64|^2; INIT: [0..g) b.b, [g..2g) r.u, [2g..3g) |r64|^2 -- the layouts OP_SR_STEP / OP_SR_INIT read.  All sums in double.
+template <bool CODED, bool INIT>
+__global__ __launch_bounds__(kBlock) void k_sr_mixed_residual(int64_t n, const double *__restrict__ b, const double *__restrict__ t64,
+                                                              float *__restrict__ r, float *__restrict__ u, const float *__restrict__ invd,
+                                                              const uint16_t *__restrict__ dcode, double *__restrict__ partial,
+                                                              const PcgScalars *sc)
+{
+    __shared__ double red[4];
+    const bool skip = !INIT && sc->done != 0; // (done == 3, a transport fault: k_sr_mixed_begin left it set)
+    double rr = 0., ru = 0., bb = 0.;
+    if (!skip)
+        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+            const double bi = b[i];
+            const double ri = bi - t64[i];
+            const float rf = (float)ri;
+            const float ui = (CODED ? invd[dcode[i]] : invd[i]) * rf;
+            r[i] = rf;
+            u[i] = ui;
+            rr += ri * ri;
+            ru += (double)rf * (double)ui;
+            if (INIT) bb += bi * bi;
+        }
+    rr = block_sum(rr, red);
+    ru = block_sum(ru, red);
+    if (INIT) bb = block_sum(bb, red);
+    if (threadIdx.x == 0) {
+        if (INIT) partial[blockIdx.x] = bb;
+        partial[(INIT ? 1 : 0) * gridDim.x + blockIdx.x] = ru;
+        partial[(INIT ? 2 : 1) * gridDim.x + blockIdx.x] = rr;
+    }
+}
+
+// In front of a reliable update: the kernels of its two exchanges return while `done` is set, and a chunk the recurrence froze (or an
+// avs_cancel the direct transport's finalizer saw: sc->cancelled stays) left it set.  rhs == 0 and a transport fault keep it.
+__global__ void k_sr_mixed_begin(PcgScalars *sc)
+{
+    if (sc->done == 3 || sc->fault) return;
+    sc->done = 0;
+}
+
+// The scalar step of a reliable update on red = [r.u, |r64|^2, w.u] of the true residual (all-reduced / all-gathered in rank order):
+// the fp64 test, else OP_SR_STEP's arithmetic from rho and alpha of the last step taken; the iteration counts once, here.
+__global__ void k_sr_mixed_step(PcgScalars *sc)
+{
+    if (sc->done == 3 || sc->fault) return;
+    sc->rr = sc->red[1];
+    if (sc->cancelled || sc->red[1] < sc->threshold) { sc->done = 1; return; }
+    const double gamma_old = sc->rho, gamma = sc->red[0], delta = sc->red[2];
+    const double beta = gamma / gamma_old;
+    sc->alpha = gamma / (delta - beta * gamma / sc->alpha);
+    sc->beta = beta;
+    sc->rho = gamma;
+    sc->iter += 1;
+    sc->done = 0;
 }
 
 // k_sr_init / k_sr_update with (CODED) or without the diagonal codes; only the float loops read codes here (KERNEL<T, F32> keeps
@@ -1929,11 +1997,14 @@ static avs_status sr_spmv(const CsrView &A, const float *x, float *y, double *pa
 // gets the rows' codes and the table of inverted values), then r = b - A x (x staged through u for the halo), u = M^-1 r, w = A u.
 // product(k): the transport's exchange of u and w = A u -- k = 0 of x, k = 1 of u, which also folds the sums |b|^2, r.u, |r|^2, w.u
 // (the first 3 * g vector partials) and applies OP_SR_INIT / OP_SR_INIT_F32 in sc[0].  g: the grid of the loop's vector kernels.
-template <typename T, typename F>
+// MIXED (T = float): v->x is the correction xf = 0; product(0) stages x through w->p [owned | halo] and leaves the fp64 A x in w->t;
+// the sums are |b|^2, r.u of the rounded residual and |b - A x|^2 of the fp64 one.
+template <typename T, bool MIXED = false, typename F>
 static avs_status sr_setup(PcgWork *w, const CsrView &A, const double *b, double *x, bool coded, int g, SrVecs<T> *v, hipStream_t stream,
                            F &&product)
 {
     constexpr bool F32 = std::is_same<T, float>::value;
+    static_assert(F32 || !MIXED, "the mixed-precision loops iterate on float vectors");
     const int64_t n = A.n;
     AVS_HIP(hipMemsetAsync(w->sc.p, 0, 2 * sizeof(PcgScalars), stream));
     if constexpr (F32) { // as pcg_solve_f32 makes them
@@ -1964,7 +2035,10 @@ static avs_status sr_setup(PcgWork *w, const CsrView &A, const double *b, double
     }
     v->dcode = coded ? w->dcode.p : nullptr;
     AVS_HIP(hipEventRecord(w->ev0, stream));
-    if constexpr (F32) {
+    if constexpr (MIXED) {
+        AVS_HIP(hipMemsetAsync(v->x, 0, ((size_t)n + 8) * sizeof(float), stream));
+        AVS_HIP(hipMemcpyAsync(w->p.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    } else if constexpr (F32) {
         hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, (const double *)x, v->x);
         hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, (const double *)x, v->u);
     } else {
@@ -1972,14 +2046,19 @@ static avs_status sr_setup(PcgWork *w, const CsrView &A, const double *b, double
     }
     AVS_TRY(product(0));
     const bool kc = F32 && coded; // (the fp64 set-up reads the per-row inverse)
-    AVS_SR_LAUNCH(k_sr_init, kc, n, b, (const T *)v->w, kc ? v->invtab : v->invd, v->dcode, v->r, v->u, w->partial.p);
+    if constexpr (MIXED) {
+        if (coded) hipLaunchKernelGGL((k_sr_mixed_residual<true, true>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v->r, v->u, v->invtab, v->dcode, w->partial.p, (const PcgScalars *)w->sc.p);
+        else hipLaunchKernelGGL((k_sr_mixed_residual<false, true>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v->r, v->u, v->invd, v->dcode, w->partial.p, (const PcgScalars *)w->sc.p);
+    } else {
+        AVS_SR_LAUNCH(k_sr_init, kc, n, b, (const T *)v->w, kc ? v->invtab : v->invd, v->dcode, v->r, v->u, w->partial.p);
+    }
     AVS_TRY(product(1));
     AVS_HIP(hipGetLastError());
     return AVS_OK;
 }
 
 // sr_setup over the RCCL / in-process exchange; dist == nullptr: one GPU, no exchange and no all-reduce
-template <typename T>
+template <typename T, bool MIXED = false>
 static avs_status sr_setup_exchange(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, bool coded, PcgDist *dist,
                                     SrVecs<T> *v, hipStream_t stream)
 {
@@ -1987,22 +2066,30 @@ static avs_status sr_setup_exchange(PcgWork *w, const CsrView &A, const double *
     const int variant = spmv_default_variant(A);
     double *pvec = w->partial.p, *pspmv = w->partial.p + 4 * (size_t)kVecGrid; // 3 * g vector-kernel partials, the SpMV's behind them
     PcgScalars *sc = w->sc.p;
-    return sr_setup(w, A, b, x, coded, g, v, stream, [&](int k) -> avs_status {
+    return sr_setup<T, MIXED>(w, A, b, x, coded, g, v, stream, [&](int k) -> avs_status {
+        if constexpr (MIXED) {
+            if (k == 0) { // x exchanged in fp64, then the rank's fp64 product (as in the reliable updates)
+                if (dist) AVS_TRY(dist_halo_exchange(dist, w->p.p, stream));
+                return spmv_dispatch<false>(A, w->p.p, w->t.p, nullptr, nullptr, variant, stream, nullptr);
+            }
+        }
         if (dist) AVS_TRY(dist_halo_exchange(dist, v->u, stream));
         if (k == 0) return sr_spmv<false>(A, v->u, v->w, nullptr, nullptr, variant, stream, nullptr);
         int nb = 0;
-        AVS_TRY(sr_spmv<true>(A, v->u, v->w, pspmv, nullptr, variant, stream, &nb));
+        if constexpr (MIXED) AVS_TRY(spmv_mixed_dispatch<true>(A, v->u, v->w, pspmv, nullptr, stream, &nb));
+        else AVS_TRY(sr_spmv<true>(A, v->u, v->w, pspmv, nullptr, variant, stream, &nb));
         reduce_launch(w, pvec, g, 3, sc, (int)OP_NONE, tol, 0, 0, stream);
         reduce_launch(w, pspmv, nb, 1, sc, (int)OP_NONE, tol, 0, 3, stream);
         if (dist) AVS_TRY(dist_allreduce(dist, sc->red, 4, stream));
-        hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc, std::is_same<T, float>::value ? (int)OP_SR_INIT_F32 : (int)OP_SR_INIT, tol);
+        hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc, (std::is_same<T, float>::value && !MIXED) ? (int)OP_SR_INIT_F32 : (int)OP_SR_INIT, tol);
         return AVS_OK;
     });
 }
 
 // Host-mediated transports (RCCL, in-process virtual ranks).  b, x: the rank's fp64 arrays (float vectors: holding float values); x
 // receives the solution.
-template <typename T>
+// MIXED (T = float, AVS_OPTION_DIST_MIXED_PRECISION): x stays fp64 and receives the reliable updates (see k_sr_mixed_residual).
+template <typename T, bool MIXED = false>
 static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const double *b, double *x, double tol,
                                              int max_iters, hipStream_t stream, avs_solve_info *info, PcgDist *dist)
 {
@@ -2013,11 +2100,11 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
     const bool coded = F32 && A.codes && !A.tab_ptr && A.table_size <= kViLdsTable; // (the fp64 loop reads the per-row inverse)
     if (F32) { // the float SpMV's partials: one per persistent workgroup of the brick kernel, else one per 256 rows
         const bool brick = A.brick && A.brick->ntiles > 0 && A.brick->pwords32;
-        const size_t nb_max = brick ? (size_t)brick_partial_count(*A.brick, 4) : (size_t)stream_grid(n);
+        const size_t nb_max = brick ? (size_t)(MIXED ? brick_partial_count_mixed(*A.brick) : brick_partial_count(*A.brick, 4)) : (size_t)stream_grid(n);
         AVS_TRY(ensure_partials(w, 4 * (size_t)kVecGrid + nb_max + 16));
     }
     SrVecs<T> v;
-    AVS_TRY(sr_setup_exchange(w, A, b, x, tol, coded, dist, &v, stream));
+    AVS_TRY((sr_setup_exchange<T, MIXED>(w, A, b, x, tol, coded, dist, &v, stream)));
     double *pvec = w->partial.p;                        // 3 * g vector-kernel partials
     double *pspmv = w->partial.p + 4 * (size_t)kVecGrid; // SpMV partials behind them
     PcgScalars *sc = w->sc.p; // two states, ping-pong: sc[cur] is current, k_sr_update writes sc[cur ^ 1]
@@ -2027,8 +2114,15 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
         // first iteration of a chunk: scalars are final (SR_INIT or the explicit step after the chunk); afterwards the step of
         // the previous iteration rides in k_sr_update, which moves the state to the other slot
         const int step = c > 0 ? 1 : 0;
-        AVS_SR_LAUNCH(k_sr_update, coded, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w, coded ? v.invtab : v.invd, v.dcode,
-                      (const PcgScalars *)(sc + cur), sc + (step ? (cur ^ 1) : cur), step, pvec);
+        if constexpr (MIXED) {
+            if (coded) hipLaunchKernelGGL((k_sr_update<float, true, double>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const float *)v.w,
+                                          v.invtab, v.dcode, (const PcgScalars *)(sc + cur), sc + (step ? (cur ^ 1) : cur), step, pvec);
+            else hipLaunchKernelGGL((k_sr_update<float, false, double>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const float *)v.w,
+                                    v.invd, v.dcode, (const PcgScalars *)(sc + cur), sc + (step ? (cur ^ 1) : cur), step, pvec);
+        } else {
+            AVS_SR_LAUNCH(k_sr_update, coded, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w, coded ? v.invtab : v.invd, v.dcode,
+                          (const PcgScalars *)(sc + cur), sc + (step ? (cur ^ 1) : cur), step, pvec);
+        }
         if (step) cur ^= 1;
         const PcgScalars *now = sc + cur;
         int nb = 0;
@@ -2052,7 +2146,8 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
         if (!overlapped) {
             AVS_TRY(dist_halo_exchange(dist, v.u, stream));
             if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
-            AVS_TRY(sr_spmv<true>(A, v.u, v.w, pspmv, now, variant, stream, &nb));
+            if constexpr (MIXED) AVS_TRY(spmv_mixed_dispatch<true>(A, v.u, v.w, pspmv, now, stream, &nb));
+            else AVS_TRY(sr_spmv<true>(A, v.u, v.w, pspmv, now, variant, stream, &nb));
             if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
         }
         if (nb < 16384) hipLaunchKernelGGL(k_reduce_pair, dim3(1), dim3(kRedBlock), 0, stream, pvec, g, 2, pspmv, nb, 1, sc + cur);
@@ -2061,6 +2156,29 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
             reduce_launch(w, pspmv, nb, 1, sc + cur, (int)OP_NONE, tol, 0, 2, stream);
         }
         return dist_allreduce(dist, sc[cur].red, 3, stream);
+    };
+    // MIXED: the reliable update behind every chunk, on sc[cur] (every rank enqueues it: the exchanges are collective)
+    auto enqueue_update = [&]() -> avs_status {
+        if constexpr (MIXED) {
+            PcgScalars *now = sc + cur;
+            hipLaunchKernelGGL(k_sr_mixed_begin, dim3(1), dim3(1), 0, stream, now);
+            hipLaunchKernelGGL(k_mixed_fold, dim3(g), dim3(kBlock), 0, stream, n, x, v.x, (const PcgScalars *)now);
+            AVS_HIP(hipMemcpyAsync(w->p.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            AVS_TRY(dist_halo_exchange(dist, w->p.p, stream));
+            AVS_TRY(spmv_dispatch<false>(A, w->p.p, w->t.p, nullptr, nullptr, variant, stream, nullptr));
+            if (coded) hipLaunchKernelGGL((k_sr_mixed_residual<true, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u, v.invtab, v.dcode, pvec, (const PcgScalars *)now);
+            else hipLaunchKernelGGL((k_sr_mixed_residual<false, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u, v.invd, v.dcode, pvec, (const PcgScalars *)now);
+            AVS_TRY(dist_halo_exchange(dist, v.u, stream));
+            int nb = 0;
+            AVS_TRY(spmv_mixed_dispatch<true>(A, v.u, v.w, pspmv, now, stream, &nb));
+            reduce_launch(w, pvec, g, 2, now, (int)OP_NONE, tol, 0, 0, stream);
+            reduce_launch(w, pspmv, nb, 1, now, (int)OP_NONE, tol, 0, 2, stream);
+            AVS_TRY(dist_allreduce(dist, now->red, 3, stream));
+            hipLaunchKernelGGL(k_sr_mixed_step, dim3(1), dim3(1), 0, stream, now);
+            AVS_HIP(hipGetLastError());
+            w->reliable_updates++;
+        }
+        return AVS_OK;
     };
     ChunkState cs;
     bool cancelled = false;
@@ -2073,12 +2191,21 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
         AVS_HIP(hipMemcpyAsync(stop_h + 1, w->cancel_word.p, sizeof(double), hipMemcpyDeviceToHost, stream));
         AVS_TRY(poll_scalars(w, sc + cur, stream));
         sample_spmv(w, info != nullptr, true, &cs);
+        if (MIXED && w->host_sc->done == 0 && w->host_sc->iter < cs.enqueued) cs.enqueued = w->host_sc->iter; // a chunk the recurrence froze
         if (w->host_sc->done || cs.enqueued >= max_iters) break;
         if (stop_h[1] != 0.) { (void)cancel_consume(); cancelled = true; break; }
         AVS_TRY(enqueue_chunk(w, stream, nullptr, max_iters, info != nullptr, enqueue_iteration, &cs)); // (no graph: RCCL calls inside)
-        // the last iteration's step, explicitly: the host polls a final state
-        hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc + cur, F32 ? (int)OP_SR_STEP_F32 : (int)OP_SR_STEP, tol);
-        AVS_HIP(hipGetLastError());
+        if constexpr (MIXED) {
+            AVS_TRY(enqueue_update()); // x += xf and the step on the true residual before the host looks
+        } else {
+            // the last iteration's step, explicitly: the host polls a final state
+            hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc + cur, F32 ? (int)OP_SR_STEP_F32 : (int)OP_SR_STEP, tol);
+            AVS_HIP(hipGetLastError());
+        }
+    }
+    if constexpr (MIXED) {
+        if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), stream)); // rhs == 0: x := 0
+        return finish_info(w, A, stream, info, &cs, cancelled, 0, false);
     }
     if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(v.x, 0, (size_t)n * sizeof(T), stream)); // rhs == 0: x := 0
     if constexpr (F32) hipLaunchKernelGGL(k_f32_widen, dim3(g), dim3(kBlock), 0, stream, n, (const float *)v.x, x);
@@ -2144,7 +2271,9 @@ template <typename T> struct Pair;
 template <> struct Pair<double> { typedef d2_t type; };
 template <> struct Pair<float> { typedef float type __attribute__((ext_vector_type(2))); };
 
-template <bool CODED, bool KEEP = true, typename T = double>
+// S = double next to T = float: the mixed-precision loop's instantiation, as k_sr_update<float, .., double> -- dot terms widened, x is
+// the correction xf.
+template <bool CODED, bool KEEP = true, typename T = double, typename S = T>
 __global__ __launch_bounds__(kBlock) void k_sr_update_push(int64_t n, T *__restrict__ x, T *__restrict__ r, T *__restrict__ p,
                                                            T *__restrict__ s, T *__restrict__ u, const T *__restrict__ w,
                                                            const T *__restrict__ invd, const uint16_t *__restrict__ dcode,
@@ -2163,7 +2292,7 @@ __global__ __launch_bounds__(kBlock) void k_sr_update_push(int64_t n, T *__restr
     typedef typename Pair<T>::type v2_t;
     const T alpha = (T)sc->alpha, beta = (T)sc->beta;
     __shared__ double red[4];
-    T ru = 0, rr = 0;
+    S ru = 0, rr = 0;
     int64_t i = lo + 2 * (int64_t)threadIdx.x;
     for (; i + 1 < hi; i += 2 * kBlock) { // (lo is a multiple of kBlock: i is even, the 16-B accesses are aligned)
         const v2_t pv = stream_load_k<KEEP>(reinterpret_cast<const v2_t *>(p + i));
@@ -2194,10 +2323,10 @@ __global__ __launch_bounds__(kBlock) void k_sr_update_push(int64_t n, T *__restr
         stream_store_k<KEEP>(xn, reinterpret_cast<v2_t *>(x + i));
         stream_store_k<KEEP>(rn, reinterpret_cast<v2_t *>(r + i));
         *reinterpret_cast<v2_t *>(u + i) = un;
-        ru += rn.x * un.x;
-        rr += rn.x * rn.x;
-        ru += rn.y * un.y;
-        rr += rn.y * rn.y;
+        ru += (S)rn.x * (S)un.x;
+        rr += (S)rn.x * (S)rn.x;
+        ru += (S)rn.y * (S)un.y;
+        rr += (S)rn.y * (S)rn.y;
     }
     if (i < hi) { // odd tail of the last range
         const T idi = CODED ? invd[dcode[i]] : invd[i];
@@ -2210,8 +2339,8 @@ __global__ __launch_bounds__(kBlock) void k_sr_update_push(int64_t n, T *__restr
         r[i] = ri;
         const T ui = idi * ri;
         u[i] = ui;
-        ru += ri * ui;
-        rr += ri * ri;
+        ru += (S)ri * (S)ui;
+        rr += (S)ri * (S)ri;
     }
     const double sru = block_sum((double)ru, red); // (barriers inside: every u of this range is written before the push below reads it)
     const double srr = block_sum((double)rr, red);
@@ -2375,11 +2504,15 @@ static avs_status direct_fault(const PcgScalars &h)
     return AVS_ERCCL;
 }
 
-template <typename T>
+// MIXED (T = float, AVS_OPTION_DIST_MIXED_PRECISION): the float path's three-launch round with the double-scalar step ops; the last round
+// of a chunk folds its sums without a step (OP_NONE), and the reliable update behind the chunk -- a k_push round of x, the fp64 product,
+// k_sr_mixed_residual, a round of u -- takes it on the true residual's sums (k_sr_mixed_step).
+template <typename T, bool MIXED = false>
 static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, int max_iters,
                                    hipStream_t stream, avs_solve_info *info, const DirectArgs &da)
 {
     constexpr bool F32 = std::is_same<T, float>::value;
+    typedef typename std::conditional<MIXED, double, T>::type SS; // the scalar type of the update kernel
     const int64_t n = A.n;
     int g = 1, chunk_rows = kBlock; // every vector kernel of this loop uses the fused kernel's geometry (same partial layout)
     sr_update_geometry((long long)n, &g, &chunk_rows);
@@ -2389,7 +2522,7 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
     // brick-structured form of the local rows (float vectors: with its float walk): one partial per persistent workgroup
     const bool brick = A.brick && A.brick->ntiles > 0 && (!F32 || A.brick->pwords32);
     int ntiles = 0, ppt = 1; // the SpMV's partials: ntiles * ppt stage slots
-    if (F32) ntiles = n <= 0 ? 0 : (brick ? brick_partial_count(*A.brick, 4) : stream_grid(n)); // (k_f32_spmv_csr: one per 256 rows)
+    if (F32) ntiles = n <= 0 ? 0 : (brick ? (MIXED ? brick_partial_count_mixed(*A.brick) : brick_partial_count(*A.brick, 4)) : stream_grid(n)); // (k_f32_spmv_csr: one per 256 rows)
     else {
         ntiles = brick ? brick_partial_count(*A.brick, 8) : da.n_tiles_int + da.n_tiles_bnd; // (word stream: == ceil(n / kTileRows))
         ppt = brick ? 1 : (A.codes ? kTileRows / 64 : 1); // value-indexed kernel: one partial per wave
@@ -2405,6 +2538,37 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
     double *pvec = w->partial.p; // up to 3 * g vector-kernel partials
     PcgScalars *sc = w->sc.p;
     SrVecs<T> v;
+    const int variant = spmv_default_variant(A);
+    ChunkState cs;
+
+    // MIXED: x to the peers in fp64 and t64 = A x with the rank's fp64 product (the set-up and every reliable update): a round of its own
+    // -- push, wait + gather into the tail of the staging vector w->p, the product, and a finalizer without stage slots or sums, whose
+    // all-gather is the round's barrier (nobody pushes u into a halo area that is still being gathered) and advances the epoch
+    auto product_x = [&]() -> avs_status {
+        AVS_HIP(hipMemcpyAsync(w->p.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        if (push_blocks)
+            hipLaunchKernelGGL(k_push, dim3(push_blocks), dim3(256), 0, stream, da.dd, (const double *)x, (const unsigned long long *)da.epoch,
+                               da.push_ticket, (const PcgScalars *)sc);
+        HaloView hv;
+        hv.dd = da.dd;
+        hv.epoch = da.epoch;
+        hv.epoch_w = da.epoch;
+        hv.fin_ticket = da.fin_ticket;
+        hv.sc = sc;
+        hv.pvec = pvec;
+        hv.stage = w->stage2.p;
+        hv.stage2 = w->stage2.p + (slots > 0 ? slots : 1);
+        hv.g = g;
+        hv.tol = tol; // (ntiles = 0, nfin = 1, nred_vec = 0, op = OP_NONE, no cancel word: a request waits for the round of u)
+        if (da.npeers > 0) {
+            const int hg = n_halo_cols > 0 ? (n_halo_cols + 255) / 256 : 1;
+            hipLaunchKernelGGL(k_halo_gather<double>, dim3(hg < 64 ? hg : 64), dim3(256), 0, stream, hv, w->p.p);
+        }
+        AVS_TRY(spmv_dispatch<false>(A, w->p.p, w->t.p, nullptr, nullptr, variant, stream, nullptr));
+        hipLaunchKernelGGL(k_halo_finalize, dim3(1), dim3(512), 0, stream, hv);
+        AVS_HIP(hipGetLastError());
+        return AVS_OK;
+    };
 
     // one round: push `vec` to the peers, v.w = A vec (+ partials of vec.v.w), fold `nred_vec` vector partial arrays + those, step `op`
     auto round = [&](T *vec, int nred_vec, int op, hipEvent_t ea, hipEvent_t eb, bool push) -> avs_status {
@@ -2447,7 +2611,8 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
                 const int hg = n_halo_cols > 0 ? (n_halo_cols + 255) / 256 : 1;
                 hipLaunchKernelGGL(k_halo_gather<T>, dim3(hg < 64 ? hg : 64), dim3(256), 0, stream, hv, vec);
             }
-            if constexpr (F32) AVS_TRY(spmv_f32_dispatch<true>(A, vec, v.w, w->stage2.p, sc, stream, nullptr));
+            if constexpr (MIXED) AVS_TRY(spmv_mixed_dispatch<true>(A, vec, v.w, w->stage2.p, sc, stream, nullptr));
+            else if constexpr (F32) AVS_TRY(spmv_f32_dispatch<true>(A, vec, v.w, w->stage2.p, sc, stream, nullptr));
             else AVS_TRY(spmv_brick_launch(*A.brick, vec, v.w, w->stage2.p, &sc->done, stream));
             hipLaunchKernelGGL(k_halo_finalize, dim3(nfin), dim3(512), 0, stream, hv);
         }
@@ -2455,16 +2620,17 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
         AVS_HIP(hipGetLastError());
         return AVS_OK;
     };
-    AVS_TRY(sr_setup(w, A, b, x, coded, g, &v, stream, [&](int k) -> avs_status {
+    AVS_TRY((sr_setup<T, MIXED>(w, A, b, x, coded, g, &v, stream, [&](int k) -> avs_status {
+        if (MIXED && k == 0) return product_x();
         return k == 0 ? round(v.u, 0, (int)OP_NONE, nullptr, nullptr, true)
-                      : round(v.u, 3, F32 ? (int)OP_SR_INIT_F32 : (int)OP_SR_INIT, nullptr, nullptr, true);
-    }));
+                      : round(v.u, 3, (F32 && !MIXED) ? (int)OP_SR_INIT_F32 : (int)OP_SR_INIT, nullptr, nullptr, true);
+    })));
 
     // Systems that fit on the chip (<= ~1 M rows, packed single-dictionary form): the rest of the solve in ONE cooperative launch,
     // matrix words in the register files, vector slices in LDS (avs_pcg_resident.inl).  Needs the GPU for itself.  fp64, and float
     // vectors with AVS_OPTION_RESIDENT_F32 (k_cg_resident<.., float>: the same state, the same scalar step as this loop).
     w->resident_used = 0;
-    if (!F32 || A.resident_f32) {
+    if (!MIXED && (!F32 || A.resident_f32)) {
         // (AVS_OPTION_RESIDENT_LOCAL_TABLES: also a matrix without one small dictionary, with the per-row inverse this set-up made --
         // the float set-up of a coded matrix makes none: no resident loop then)
         const bool local = resident_local_tables_wanted(A);
@@ -2482,25 +2648,43 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
     auto enqueue_iteration = [&](int c, bool timed) -> avs_status {
         // update and push in one launch (3 launches per iteration)
         if (coded && brick) // (the brick form serves single-dictionary matrices: coded)
-            hipLaunchKernelGGL((k_sr_update_push<true, false, T>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
+            hipLaunchKernelGGL((k_sr_update_push<true, false, T, SS>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
                                v.invtab, v.dcode, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch, da.push_ticket);
         else if (coded)
-            hipLaunchKernelGGL((k_sr_update_push<true, true, T>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
+            hipLaunchKernelGGL((k_sr_update_push<true, true, T, SS>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
                                v.invtab, v.dcode, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch, da.push_ticket);
         else
-            hipLaunchKernelGGL((k_sr_update_push<false, true, T>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
+            hipLaunchKernelGGL((k_sr_update_push<false, true, T, SS>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
                                v.invd, (const uint16_t *)nullptr, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch,
                                da.push_ticket);
-        return round(v.u, 2, F32 ? (int)OP_SR_STEP_F32 : (int)OP_SR_STEP, timed ? w->evA[c] : nullptr, timed ? w->evB[c] : nullptr, false);
+        int op = F32 ? (int)OP_SR_STEP_F32 : (int)OP_SR_STEP;
+        if constexpr (MIXED) { // the chunk's last round leaves its step to the reliable update (cs.enqueued: iterations before this chunk)
+            const int len = (max_iters - cs.enqueued) < kChunk ? (max_iters - cs.enqueued) : kChunk;
+            op = c == len - 1 ? (int)OP_NONE : (int)OP_SR_STEP;
+        }
+        return round(v.u, 2, op, timed ? w->evA[c] : nullptr, timed ? w->evB[c] : nullptr, false);
     };
-    GraphKey key = matrix_key(F32 ? kGraphDirectF32 : kGraphDirect, A, v.x, tol);
+    auto enqueue_update = [&]() -> avs_status {
+        if constexpr (MIXED) {
+            hipLaunchKernelGGL(k_sr_mixed_begin, dim3(1), dim3(1), 0, stream, sc);
+            hipLaunchKernelGGL(k_mixed_fold, dim3(g), dim3(kBlock), 0, stream, n, x, v.x, (const PcgScalars *)sc);
+            AVS_TRY(product_x());
+            if (coded) hipLaunchKernelGGL((k_sr_mixed_residual<true, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u, v.invtab, v.dcode, pvec, (const PcgScalars *)sc);
+            else hipLaunchKernelGGL((k_sr_mixed_residual<false, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u, v.invd, v.dcode, pvec, (const PcgScalars *)sc);
+            AVS_TRY(round(v.u, 2, (int)OP_NONE, nullptr, nullptr, true));
+            hipLaunchKernelGGL(k_sr_mixed_step, dim3(1), dim3(1), 0, stream, sc);
+            AVS_HIP(hipGetLastError());
+            w->reliable_updates++;
+        }
+        return AVS_OK;
+    };
+    GraphKey key = matrix_key(MIXED ? kGraphDirectMixed : F32 ? kGraphDirectF32 : kGraphDirect, A, v.x, tol);
     key.b = b;
     key.dd = da.dd;
     key.ntiles = ntiles;
     key.brick = brick;
     key.coded = coded;
     const GraphKey *gkey = cur_opt().graph != 0 ? &key : nullptr;
-    ChunkState cs;
     bool cancel_sent = false;
     for (;;) {
         AVS_TRY(poll_scalars(w, sc, stream));
@@ -2509,6 +2693,7 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
             return direct_fault(*w->host_sc);
         }
         sample_spmv(w, info != nullptr, true, &cs);
+        if (MIXED && w->host_sc->done == 0 && w->host_sc->iter < cs.enqueued) cs.enqueued = w->host_sc->iter; // a chunk the recurrence froze
         if (w->host_sc->done || cs.enqueued >= max_iters || w->resident_used) break;
         if (cancel_requested() && !cancel_sent) { // avs_cancel: the request word the finalizer adds to the round's sums -- every rank stops in the same round
             static const int one = 1;
@@ -2516,11 +2701,16 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
             cancel_sent = true;
         }
         AVS_TRY(enqueue_chunk(w, stream, gkey, max_iters, info != nullptr, enqueue_iteration, &cs));
+        AVS_TRY(enqueue_update()); // (MIXED)
     }
-    if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(v.x, 0, (size_t)n * sizeof(T), stream)); // rhs == 0: x := 0
-    if constexpr (F32) hipLaunchKernelGGL(k_f32_widen, dim3(g), dim3(kBlock), 0, stream, n, (const float *)v.x, x);
+    if constexpr (MIXED) {
+        if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), stream)); // rhs == 0: x := 0
+    } else {
+        if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(v.x, 0, (size_t)n * sizeof(T), stream)); // rhs == 0: x := 0
+        if constexpr (F32) hipLaunchKernelGGL(k_f32_widen, dim3(g), dim3(kBlock), 0, stream, n, (const float *)v.x, x);
+    }
     AVS_HIP(hipGetLastError());
-    AVS_TRY(finish_info(w, A, stream, info, &cs, w->host_sc->cancelled != 0, w->resident_used, F32));
+    AVS_TRY(finish_info(w, A, stream, info, &cs, w->host_sc->cancelled != 0, w->resident_used, F32 && !MIXED));
     if (w->host_sc->cancelled) (void)cancel_consume();
     return AVS_OK;
 }
@@ -2668,6 +2858,11 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
         if (A.f32_vectors > 0 && !cur_opt().dist_standard_cg && !paranoid)
             return direct ? pcg_solve_direct<float>(w, A, b, x, tol, max_iters, stream, info, da)
                           : pcg_solve_single_reduction<float>(w, A, b, x, tol, max_iters, stream, info, dist);
+        // AVS_OPTION_DIST_MIXED_PRECISION (fp64 contexts; A.mixed is set from the plan's latch by avs_dist_solve only): the same loops on
+        // float vectors with fp64 scalars and reliable updates, under the same conditions
+        if (A.mixed && !cur_opt().dist_standard_cg && !paranoid && (direct || dist_wants_single_reduction(dist)))
+            return direct ? pcg_solve_direct<float, true>(w, A, b, x, tol, max_iters, stream, info, da)
+                          : pcg_solve_single_reduction<float, true>(w, A, b, x, tol, max_iters, stream, info, dist);
         if (direct) return pcg_solve_direct<double>(w, A, b, x, tol, max_iters, stream, info, da);
     }
     if (dist && dist_wants_single_reduction(dist))

@@ -275,15 +275,17 @@ static avs_status pcg_solve_mixed(PcgWork *w, const CsrView &A, const double *b,
 
 #ifdef AVS_PROBES
 // probe / test entry: y = A x through the mixed-precision loop's product (x holds float values; y is widened), + the folded partial sums
-avs_status spmv_mixed_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st)
+// n_cols (0: A.n): the entries of x -- [owned | halo] for the local rows of a partitioned plan
+avs_status spmv_mixed_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st, int64_t n_cols)
 {
     const int64_t n = A.n;
+    if (n_cols < n) n_cols = n;
     DevBuf<float> xf, yf;
     DevBuf<double> partial;
-    AVS_TRY(xf.alloc((size_t)n + 8));
+    AVS_TRY(xf.alloc((size_t)n_cols + 8));
     AVS_TRY(yf.alloc((size_t)n + 8));
     const int g = stream_grid(n) < kVecGrid ? stream_grid(n) : kVecGrid;
-    hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, st, n, x, xf.p);
+    hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, st, n_cols, x, xf.p);
     if (!fused) {
         AVS_TRY(spmv_mixed_dispatch<false>(A, xf.p, yf.p, nullptr, nullptr, st, nullptr));
     } else {

@@ -295,7 +295,9 @@ class ViscositySolve:
                 return (f"k_spmv_brick<DOT,{'VC,' if int(fmt.brick_value_codes) else ''}float> (brick-structured form, float vectors: {int(fmt.brick_tiles)} tiles, "
                         f"{int(fmt.brick_pattern_rows)} rows as {int(fmt.brick_patterns)} geometric row patterns, x of a brick + halo as floats in LDS; {tab}-entry dictionary; brick-major system)")
             return "k_f32_spmv_csr<DOT> (float vectors: column + value code streamed, float products parked in LDS; brick-major system)"
-        if int(getattr(fmt, "float_vectors", 0)) and int(getattr(fmt, "reliable_updates", 0)):   # the mixed-precision loop ran (avs_pcg_mixed.inl)
+        # a mixed-precision loop ran (avs_pcg_mixed.inl, or the partitioned loops with AVS_OPTION_DIST_MIXED_PRECISION): an fp64 context
+        # iterates on float vectors in no other way (a solve that converged before its first update reports no updates)
+        if int(getattr(fmt, "float_vectors", 0)) and (int(getattr(fmt, "reliable_updates", 0)) or getattr(self, "precision", 0) != capi.PRECISION_F32):
             if int(getattr(fmt, "brick_tiles", 0)):
                 return (f"k_spmv_brick<DOT,{'VC,' if int(fmt.brick_value_codes) else ''}float,double> (brick-structured form, float vectors, fp64 values and row sums: "
                         f"{int(fmt.brick_tiles)} tiles, {int(fmt.brick_pattern_rows)} rows as {int(fmt.brick_patterns)} geometric row patterns; {tab}-entry dictionary; "

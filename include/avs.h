@@ -241,7 +241,7 @@ typedef enum {
                                    * are not planned at all.  Matrices the resident loop takes today run the ordinary plan either way.  Both vector
                                    * types (float: with AVS_OPTION_RESIDENT_F32).  Reported through avs_solve_info.resident.  Read at the next
                                    * solve: switching it plans again.  Environment: AVS_RESIDENT_LOCAL_TABLES. */
-    AVS_OPTION_MIXED_PRECISION = 14 /* AVS_PRECISION_F64 contexts, single-GPU solves: 1 = a solve that would run the fp64 launch-per-phase loop iterates
+    AVS_OPTION_MIXED_PRECISION = 14, /* AVS_PRECISION_F64 contexts, single-GPU solves: 1 = a solve that would run the fp64 launch-per-phase loop iterates
                                    * on float vectors instead (r, p, A p and a correction xf: 4 B per row and stream; the matrix values and every
                                    * row sum stay fp64, the sum is rounded to float once; alpha, beta, the dot products and the threshold stay
                                    * fp64), and every 32 iterations -- and whenever the float recurrence claims convergence -- the correction is
@@ -252,6 +252,18 @@ typedef enum {
                                    * = nothing changes.  No effect on AVS_PRECISION_F32 contexts or on avs_dist_solve.  Reported through
                                    * avs_matrix_format.float_vectors and .reliable_updates.  Takes effect at the next avs_assemble (the brick form's
                                    * walk is laid out for the kernel that will run).  Environment: AVS_MIXED_PRECISION. */
+    AVS_OPTION_DIST_MIXED_PRECISION = 15 /* AVS_PRECISION_F64 contexts, partitioned solves (avs_dist_solve): 1 = the single-reduction loops of both
+                                   * transports iterate on float vectors (r, u, A u, p, s and a correction xf) with the scheme of
+                                   * AVS_OPTION_MIXED_PRECISION: matrix values, row sums (rounded to float once), dot products, alpha, beta and the
+                                   * threshold stay fp64, and behind every 32 iterations -- and whenever the float recurrence claims convergence --
+                                   * the correction is folded into the fp64 solution, x is exchanged in fp64 and the residual replaced by b - A x
+                                   * computed in fp64; the Chronopoulos-Gear step of that iteration is taken on the true residual's sums.
+                                   * avs_solve_info.error and .converged come from the last fp64 residual, .iterations counts the float
+                                   * iterations, .resident is 0 (the CU-resident loop between ranks is skipped).  AVS_DIST_CG=standard, paranoid
+                                   * mode, AVS_PRECISION_F32 contexts and avs_solve are not affected.  0 (default) = nothing changes.  Reported
+                                   * through avs_matrix_format.float_vectors and .reliable_updates.  Read at the next avs_dist_partition /
+                                   * avs_dist_assemble (the local brick form's walk is laid out for the kernel that will run).
+                                   * Environment: AVS_DIST_MIXED_PRECISION. */
 } avs_solver_option;
 enum { AVS_USE_TRANSPORT_AUTO = 0, AVS_USE_TRANSPORT_RCCL = 1, AVS_USE_TRANSPORT_DIRECT = 2 };
 enum { AVS_BRICK_AUTO = -1, AVS_BRICK_NEVER = 0, AVS_BRICK_ALWAYS = 1, AVS_BRICK_TUNE = 2 };
@@ -290,9 +302,9 @@ typedef struct avs_matrix_format {
     int32_t fused_vector_update; /* 1 = the last avs_solve ran the two vector kernels of an iteration as one launch (AVS_OPTION_FUSED_VECTOR_UPDATE, round 6) */
     int32_t fused_vector_faults; /* launches of it on this context whose grid barrier timed out (the solve was redone with the two launches) */
     int32_t float_vectors;      /* 1 = the last avs_solve or avs_dist_solve on this context iterated on float vectors (AVS_OPTION_F32_VECTORS,
-                                 * AVS_OPTION_DIST_F32_VECTORS, AVS_OPTION_MIXED_PRECISION) */
-    int32_t reliable_updates;   /* fp64 residual updates (x += xf, r = b - A x) of the last avs_solve: the mixed-precision loop
-                                 * (AVS_OPTION_MIXED_PRECISION); 0 for every other loop */
+                                 * AVS_OPTION_DIST_F32_VECTORS, AVS_OPTION_MIXED_PRECISION, AVS_OPTION_DIST_MIXED_PRECISION) */
+    int32_t reliable_updates;   /* fp64 residual updates (x += xf, r = b - A x) of the last avs_solve or avs_dist_solve: the mixed-precision
+                                 * loops (AVS_OPTION_MIXED_PRECISION, AVS_OPTION_DIST_MIXED_PRECISION); 0 for every other loop */
 } avs_matrix_format;
 avs_status avs_get_matrix_format(avs_ctx *ctx, avs_matrix_format *fmt);
 avs_status avs_get_solution(avs_ctx *ctx, double *x, int64_t n, avs_memspace where);

@@ -30,7 +30,9 @@ avs_status avs_bench_spmv(avs_ctx *ctx, int32_t variant, int32_t repeats, double
  * rounded to float); fused_dot & 2 asks such a context for the fp64 product of its reliable updates instead. */
 avs_status avs_spmv_solver_form(avs_ctx *ctx, const double *x, double *y, int32_t fused_dot, double *dot_out);
 /* the same for the LOCAL system of a partitioned solve (after avs_dist_assemble / avs_dist_partition): x_ext holds the rank's
- * [owned | halo] entries in local numbering (n_own + n_halo doubles, device), y its n_own rows */
+ * [owned | halo] entries in local numbering (n_own + n_halo doubles, device), y its n_own rows.  A plan made with
+ * AVS_OPTION_DIST_MIXED_PRECISION = 1 multiplies with the mixed-precision loops' product (all of x_ext narrowed to float, fp64 values and row
+ * sums, y rounded to float); fused_dot & 2 asks such a plan for the fp64 product of its reliable updates instead. */
 avs_status avs_dist_spmv_local_form(avs_ctx *ctx, const double *x_ext, double *y, int32_t fused_dot, double *dot_out);
 
 /* y = A x on a caller's device CSR (reference numbering kept) with the lossless storage form avs_pcg_csr builds for it -- chosen under the
