@@ -264,6 +264,7 @@ static void invalidate(avs_ctx *c, bool tables)
 {
     if (tables) c->tables_ready = false;
     c->stencils_ready = c->guess_ready = c->guess_partial = c->system_ready = c->solved = false;
+    ++c->solution_gen;
 }
 
 avs_status avs_set_labels(avs_ctx *c, int32_t level, const int8_t *labels, avs_memspace where)
@@ -743,6 +744,7 @@ avs_status avs_solve(avs_ctx *c, double tol, int32_t max_iters, avs_solve_info *
     c->reliable_updates = pcg_reliable_updates(c->pcg);
     if (info) *info = local;
     c->solved = true;
+    ++c->solution_gen;
     return AVS_OK;
 }
 
@@ -775,6 +777,7 @@ avs_status avs_set_solution(avs_ctx *c, const double *x, int64_t n, avs_memspace
     AVS_HIP(hipStreamSynchronize(c->stream));
     narrow_solution_if_f32(c, c->x.p, n);
     c->solved = true;
+    ++c->solution_gen;
     return AVS_OK;
 }
 

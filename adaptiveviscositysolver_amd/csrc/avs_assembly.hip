@@ -1145,6 +1145,7 @@ avs_status build_dof_tables(avs_ctx *c)
                        : (e == 2 ? "an index grid holds a value below AVS_OUTSIDE"
                                  : "declared DOF counts exceed the ids present in the index grids"));
     c->tables_ready = true;
+    ++c->solution_gen;
     return AVS_OK;
 }
 
@@ -1389,6 +1390,7 @@ avs_status build_system(avs_ctx *c)
     c->nraw = nraw;
     c->system_ready = true;
     c->solved = false;
+    ++c->solution_gen;
     return AVS_OK;
 }
 

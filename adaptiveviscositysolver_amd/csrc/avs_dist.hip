@@ -2368,6 +2368,7 @@ avs_status avs_dist_get_solution(avs_ctx *c, double *x, int64_t n, avs_memspace 
     else AVS_HIP(hipMemcpyAsync(c->x.p, full.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
     narrow_solution_if_f32(c, c->x.p, n);
     c->solved = true;
+    ++c->solution_gen;
     AVS_HIP(copy_out(x, c->x.p, (size_t)n * sizeof(double), where, st));
     AVS_HIP(hipStreamSynchronize(st));
     return AVS_OK;

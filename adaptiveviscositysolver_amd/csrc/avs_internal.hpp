@@ -801,6 +801,10 @@ struct avs_ctx {
     avs::DevBuf<unsigned> post_list_count;
     unsigned post_list_n[AVS_MAX_LEVELS] = {};
     bool post_lists_valid = false;
+    // solution generation: bumped wherever x, the pyramids or the dof tables are written (solve, avs_set_solution, avs_dist_get_solution,
+    // assemble, avs_prepass_apply, index and label setters).  post_nodes_gen: the generation the node grids (post_nval / post_nlab) were
+    // built for, 0 = none -- an interpolator build that finds them current skips the node passes (avs_post.hip, interp_build)
+    uint64_t solution_gen = 1, post_nodes_gen = 0;
 
     // brick-major copy of the system used by the solve (avs_reorder.hip); perm: new -> old
     avs::DevBuf<int32_t> perm, inv, p_row_ptr, p_col;

@@ -357,119 +357,160 @@ __global__ __launch_bounds__(kBlock) void k_nodes_distribute(PyramidView P, Post
     }
 }
 
-// interpSPGrid, interp.cpp:660-845; P2 = sample position in half fine cells -----------------------
-__device__ double interp_sp_grid(const PyramidView &P, const PostView &W, const I3 &P2, int axis)
+// interpSPGrid, interp.cpp:660-845 -----------------------------------------------------------------
+// One evaluator for every caller: the sample position is q, in level-0 cells (fp64).  Every index position the reference derives
+// (posToIndex on the cell, face and node lattices of a level) is q scaled by a power of two, minus the lattice's half-cell offset:
+// exact.  The transfer's lattice points are q = P2 * 0.5 (P2: half fine cells, an integer) -- exact as well, so the lattice form and the
+// point sampler (k_sample_points) run the same operations on the same values.
+//
+// Level of the ACTIVE cell over the level-0 cell c0 = floor(q), -1 = none.  The reference walks up from level 0 until it meets an
+// ACTIVE cell: up to `levels` DEPENDENT reads (all of them for a face deep inside a coarse cell -- most faces that come here).  All
+// candidate labels are requested at once instead and the lowest ACTIVE level is picked: same answer, one memory round trip.
+// (The walk does not depend on the axis: the point sampler does it once per point.)
+__device__ __forceinline__ int interp_find_level(const PyramidView &P, const I3 &c0)
 {
     const int L = P.levels;
-    // The reference walks up from level 0 until it meets an ACTIVE cell: up to `levels` DEPENDENT reads (all of them for a
-    // face deep inside a coarse cell -- most faces that come here).  All candidate labels are requested at once instead and
-    // the lowest ACTIVE level is picked: same answer, one memory round trip.
     int found = -1;
-    {
-        I3 c{{P2[0] >> 1, P2[1] >> 1, P2[2] >> 1}}; // floor(indexPoint) on the level-0 node lattice
-        int8_t lab[AVS_MAX_LEVELS];
+    I3 c = c0;
+    int8_t lab[AVS_MAX_LEVELS];
 #pragma unroll
-        for (int level = 0; level < AVS_MAX_LEVELS; ++level) {
-            lab[level] = 0;
-            if (level < L) {
-                const I3 cr = cell_res(P, level);
-                lab[level] = P.labels[level][lin(cr, clamp3(c, cr))];
-                c = half3(c);
+    for (int level = 0; level < AVS_MAX_LEVELS; ++level) {
+        lab[level] = 0;
+        if (level < L) {
+            const I3 cr = cell_res(P, level);
+            lab[level] = P.labels[level][lin(cr, clamp3(c, cr))];
+            c = half3(c);
+        }
+    }
+#pragma unroll
+    for (int level = AVS_MAX_LEVELS - 1; level >= 0; --level)
+        if (level < L && lab[level] == AVS_ACTIVE) found = level;
+    return found;
+}
+// q * 2^-k (k >= -1), exact
+__device__ __forceinline__ double scale_pow2(double q, int k) { return ldexp(q, -k); }
+
+// the interpolant of component `axis` at q, inside the ACTIVE cell of level `level` over c0 = floor(q) (interp_find_level)
+__device__ double interp_at_level(const PyramidView &P, const PostView &W, const double q[3], const I3 &c0, int level, int axis)
+{
+    const I3 cell{{c0[0] >> level, c0[1] >> level, c0[2] >> level}};
+    double ifp[3];
+    I3 face;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        ifp[a] = scale_pow2(q[a], level) - (a == axis ? 0. : .5); // posToIndex on the face lattice
+        face[a] = (int)floor(ifp[a]);
+    }
+    // HDKcellToNode(face, fi), interp.cpp:683-698: the eight faces around the sample.  Their indices (transition test) and
+    // their velocities (trilinear branch) are requested together, no early exit: one round trip instead of up to nine
+    bool transition = false;
+    float fv[8];
+#pragma unroll
+    for (int fi = 0; fi < 8; ++fi) {
+        const I3 nf{{face[0] + (fi & 1), face[1] + ((fi >> 1) & 1), face[2] + ((fi >> 2) & 1)}};
+        transition |= vidx_clamped(P, level, axis, nf) == AVS_UNASSIGNED;
+        fv[fi] = vel_clamped(P, W, level, axis, nf);
+    }
+    if (!transition) { // trilinear over the 8 faces, interp.cpp:700-728
+        double iw[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            iw[a] = ifp[a] - (double)face[a];
+            iw[a] = iw[a] < 0. ? 0. : (iw[a] > 1. ? 1. : iw[a]);
+        }
+        double v = 0.;
+#pragma unroll
+        for (int fi = 0; fi < 8; ++fi) {
+            const I3 nf{{face[0] + (fi & 1), face[1] + ((fi >> 1) & 1), face[2] + ((fi >> 2) & 1)}};
+            double wt = 1.;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) wt *= (nf[a] - face[a] == 0) ? (1. - iw[a]) : iw[a];
+            v += wt * (double)fv[fi];
+        }
+        return v;
+    }
+    // node-based interpolation with the bubble correction, interp.cpp:730-836
+    double ciw = scale_pow2(q[axis], level) - (double)cell[axis];
+    ciw = ciw < 0. ? 0. : (ciw > 1. ? 1. : ciw);
+    const int a1 = (axis + 1) % 3, a2 = (axis + 2) % 3;
+    double fiv[2] = {0., 0.};
+    for (int dir = 0; dir < 2; ++dir) {
+        I3 af = cell;
+        if (dir == 1) ++af[axis];
+        int fl = level;
+        if (vidx_clamped(P, level, axis, af) == AVS_UNASSIGNED && level > 0) { // project onto the child face
+            const double cip1 = scale_pow2(q[a1], level - 1), cip2 = scale_pow2(q[a2], level - 1);
+            for (int ci = 0; ci < 4; ++ci) {
+                const I3 cf = child_face(af, axis, ci);
+                if ((double)cf[a1] <= cip1 && (double)cf[a2] <= cip2 && (double)(cf[a1] + 1) >= cip1 && (double)(cf[a2] + 1) >= cip2) {
+                    fl = level - 1;
+                    af = cf;
+                    break;
+                }
             }
         }
-#pragma unroll
-        for (int level = AVS_MAX_LEVELS - 1; level >= 0; --level)
-            if (level < L && lab[level] == AVS_ACTIVE) found = level;
+        const double inp1 = scale_pow2(q[a1], fl), inp2 = scale_pow2(q[a2], fl);
+        const double fw0 = inp1 - floor(inp1), fw1 = inp2 - floor(inp2);
+        const double fvel = (double)vel_clamped(P, W, fl, axis, af);
+        const I3 nr = node_res(P, fl);
+        double avg = 0.;
+        for (int ni = 0; ni < 4; ++ni) { // HDKfaceToNode, util.h:133-149
+            I3 nd = af;
+            if (ni & 1) ++nd[a1];
+            if (ni & 2) ++nd[a2];
+            double wt = 1.;
+            wt *= (nd[a1] - af[a1] == 0) ? (1. - fw0) : fw0;
+            wt *= (nd[a2] - af[a2] == 0) ? (1. - fw1) : fw1;
+            const double nv = (double)W.nval[fl][axis][lin(nr, clamp3(nd, nr))];
+            avg += nv;
+            fiv[dir] += nv * wt;
+        }
+        const double m3 = 1. - fw0, m4 = 1. - fw1;
+        double mm = m3 < m4 ? m3 : m4;
+        mm = fw1 < mm ? fw1 : mm;
+        mm = fw0 < mm ? fw0 : mm;
+        fiv[dir] += 2. * (fvel - .25 * avg) * mm;
     }
+    return (1. - ciw) * fiv[0] + ciw * fiv[1];
+}
+
+// the lattice form (the transfer): P2 = sample position in half fine cells
+__device__ double interp_sp_grid(const PyramidView &P, const PostView &W, const I3 &P2, int axis)
+{
+    const I3 c0{{P2[0] >> 1, P2[1] >> 1, P2[2] >> 1}}; // floor(indexPoint) on the level-0 node lattice
+    const int found = interp_find_level(P, c0);
     if (found < 0) return 0.; // reference: assert(false)
-    I3 cell{{P2[0] >> 1, P2[1] >> 1, P2[2] >> 1}};
-    for (int l = 0; l < found; ++l) cell = half3(cell);
-    {
-        const int level = found;
-        {
-            const double scale = (double)(1 << (level + 1)); // half fine cells per cell of this level
-            double ifp[3];
-            I3 face;
+    const double q[3] = {(double)P2[0] * .5, (double)P2[1] * .5, (double)P2[2] * .5};
+    return interp_at_level(P, W, q, c0, found, axis);
+}
+
+// avs_sample_velocity: one lane per point, three components per lane, caller order.  pos / out: xyz interleaved.  A point outside the
+// grid (q NaN or outside [0, n]) or under no ACTIVE cell reads nothing further and gets 0, 0, 0 / inside = 0.
+__global__ __launch_bounds__(kBlock) void k_sample_points(PyramidView P, PostView W, int64_t n_points, const float *__restrict__ pos,
+                                                          double o0, double o1, double o2, double dx, float *__restrict__ out,
+                                                          uint8_t *__restrict__ inside)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_points) return;
+    const float p0 = pos[3 * i], p1 = pos[3 * i + 1], p2 = pos[3 * i + 2];
+    const double q[3] = {((double)p0 - o0) / dx, ((double)p1 - o1) / dx, ((double)p2 - o2) / dx};
+    bool in = true;
 #pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                ifp[a] = (double)P2[a] / scale - (a == axis ? 0. : .5); // posToIndex on the face lattice
-                face[a] = (int)floor(ifp[a]);
-            }
-            // HDKcellToNode(face, fi), interp.cpp:683-698: the eight faces around the sample.  Their indices (transition test) and
-            // their velocities (trilinear branch) are requested together, no early exit: one round trip instead of up to nine
-            bool transition = false;
-            float fv[8];
+    for (int a = 0; a < 3; ++a) in = in && q[a] >= 0. && q[a] <= (double)P.n[a]; // (false for a NaN)
+    float v[3] = {0.f, 0.f, 0.f};
+    int found = -1;
+    if (in) {
+        const I3 c0{{(int)floor(q[0]), (int)floor(q[1]), (int)floor(q[2])}};
+        found = interp_find_level(P, c0);
+        if (found >= 0) {
 #pragma unroll
-            for (int fi = 0; fi < 8; ++fi) {
-                const I3 nf{{face[0] + (fi & 1), face[1] + ((fi >> 1) & 1), face[2] + ((fi >> 2) & 1)}};
-                transition |= vidx_clamped(P, level, axis, nf) == AVS_UNASSIGNED;
-                fv[fi] = vel_clamped(P, W, level, axis, nf);
-            }
-            if (!transition) { // trilinear over the 8 faces, interp.cpp:700-728
-                double iw[3];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    iw[a] = ifp[a] - (double)face[a];
-                    iw[a] = iw[a] < 0. ? 0. : (iw[a] > 1. ? 1. : iw[a]);
-                }
-                double v = 0.;
-#pragma unroll
-                for (int fi = 0; fi < 8; ++fi) {
-                    const I3 nf{{face[0] + (fi & 1), face[1] + ((fi >> 1) & 1), face[2] + ((fi >> 2) & 1)}};
-                    double wt = 1.;
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) wt *= (nf[a] - face[a] == 0) ? (1. - iw[a]) : iw[a];
-                    v += wt * (double)fv[fi];
-                }
-                return v;
-            }
-            // node-based interpolation with the bubble correction, interp.cpp:730-836
-            double ciw = (double)P2[axis] / scale - (double)cell[axis];
-            ciw = ciw < 0. ? 0. : (ciw > 1. ? 1. : ciw);
-            const int a1 = (axis + 1) % 3, a2 = (axis + 2) % 3;
-            double fiv[2] = {0., 0.};
-            for (int dir = 0; dir < 2; ++dir) {
-                I3 af = cell;
-                if (dir == 1) ++af[axis];
-                int fl = level;
-                if (vidx_clamped(P, level, axis, af) == AVS_UNASSIGNED && level > 0) { // project onto the child face
-                    const double cs = (double)(1 << level);
-                    const double cip1 = (double)P2[a1] / cs, cip2 = (double)P2[a2] / cs;
-                    for (int ci = 0; ci < 4; ++ci) {
-                        const I3 cf = child_face(af, axis, ci);
-                        if ((double)cf[a1] <= cip1 && (double)cf[a2] <= cip2 && (double)(cf[a1] + 1) >= cip1 && (double)(cf[a2] + 1) >= cip2) {
-                            fl = level - 1;
-                            af = cf;
-                            break;
-                        }
-                    }
-                }
-                const double ns = (double)(1 << (fl + 1));
-                const double inp1 = (double)P2[a1] / ns, inp2 = (double)P2[a2] / ns;
-                const double fw0 = inp1 - floor(inp1), fw1 = inp2 - floor(inp2);
-                const double fvel = (double)vel_clamped(P, W, fl, axis, af);
-                const I3 nr = node_res(P, fl);
-                double avg = 0.;
-                for (int ni = 0; ni < 4; ++ni) { // HDKfaceToNode, util.h:133-149
-                    I3 nd = af;
-                    if (ni & 1) ++nd[a1];
-                    if (ni & 2) ++nd[a2];
-                    double wt = 1.;
-                    wt *= (nd[a1] - af[a1] == 0) ? (1. - fw0) : fw0;
-                    wt *= (nd[a2] - af[a2] == 0) ? (1. - fw1) : fw1;
-                    const double nv = (double)W.nval[fl][axis][lin(nr, clamp3(nd, nr))];
-                    avg += nv;
-                    fiv[dir] += nv * wt;
-                }
-                const double m3 = 1. - fw0, m4 = 1. - fw1;
-                double mm = m3 < m4 ? m3 : m4;
-                mm = fw1 < mm ? fw1 : mm;
-                mm = fw0 < mm ? fw0 : mm;
-                fiv[dir] += 2. * (fvel - .25 * avg) * mm;
-            }
-            return (1. - ciw) * fiv[0] + ciw * fiv[1];
+            for (int a = 0; a < 3; ++a) v[a] = (float)interp_at_level(P, W, q, c0, found, a);
         }
     }
+    out[3 * i] = v[0];
+    out[3 * i + 1] = v[1];
+    out[3 * i + 2] = v[2];
+    if (inside) inside[i] = found >= 0 ? 1 : 0;
 }
 
 // T7: cpp:2815-2894 -----------------------------------------------------------------------------
@@ -660,24 +701,45 @@ avs_status avs_transfer_to_regular_grid_in_place(avs_ctx *c, float *vel_x, float
 {
     return transfer_impl(c, vel_x, vel_y, vel_z, AVS_MEM_DEVICE, true);
 }
-static avs_status transfer_impl(avs_ctx *c, float *out_x, float *out_y, float *out_z, avs_memspace where, bool in_place)
+
+// The interpolator (HDK_OctreeVectorFieldInterpolator) between its build and its release: the transfer applies it to the regular grid
+// in between, avs_sample_velocity evaluates it at the caller's points.
+struct Interp {
+    PyramidView P;
+    PostView W;
+    bool slab = false;
+    const int32_t *ids = nullptr; // slab-local context: the DOFs of the rank's window
+    int64_t n = 0;                // DOFs scattered
+    bool lists = false;
+    unsigned hcount[AVS_MAX_LEVELS] = {};
+    uint64_t gen = 0;             // solution generation the node grids belong to
+};
+
+// Build: allocate and clear the staging grids, T1 scatter, node passes T2-T6.  Node grids that were built for the current solution
+// generation (same solution, pyramids and dof tables: nothing the node passes read has changed) are kept: only the scatter runs.
+static avs_status interp_build(avs_ctx *c, Interp &I)
 {
-    avs::OptScope opt_scope_(c);
-    AVS_REQUIRE(c && out_x && out_y && out_z, AVS_EINVAL, "null argument");
-    AVS_REQUIRE(c->solved, AVS_ESTATE, "no solution: call avs_solve first");
-    AVS_REQUIRE(c->have_ridx[0] && c->have_ridx[1] && c->have_ridx[2], AVS_ESTATE, "regular-grid index fields missing (avs_set_regular_index_field)");
-    AVS_REQUIRE(c->tables_ready, AVS_ESTATE, "dof tables missing");
-    AVS_HIP(hipSetDevice(c->desc.device));
-    Scope scope("Apply Octree Solution to Regular Grid"); // cpp:662
     hipStream_t st = c->stream;
     const int L = c->desc.levels;
-    PyramidView P = c->view();
-    PostView W{};
+    I.P = c->view();
+    PyramidView &P = I.P;
+    PostView &W = I.W;
+    W = PostView{};
     W.levels = L;
+    I.gen = c->solution_gen;
     // allocate + zero the per-level fields (makeConstant(0) / INACTIVENODE, interp.h:65-81, cpp:688)
     const bool temporal = c->opt.prepass_temporal != 0;
+    const bool slab = I.slab = c->slab.on;
+    auto nodes = [&](int l) { return (size_t)((c->desc.nx >> l) + 1) * ((c->desc.ny >> l) + 1) * ((c->desc.nz >> l) + 1); };
+    // (when in doubt, rebuild: a slab-local context, AVS_PREPASS_TEMPORAL=0 and any grid that is not the allocation the claim names)
+    bool current = temporal && !slab && c->post_ready && c->post_nodes_gen == c->solution_gen;
+    for (int l = 0; l < L && current; ++l) {
+        current = c->post_nodes_sparse[l] && c->post_nodes_sparse[l] == c->post_nlab[l].p && c->post_nlab[l].n == nodes(l);
+        for (int a = 0; a < 3 && current; ++a) current = c->post_nval[l][a].n == nodes(l);
+    }
+    if (!current) c->post_nodes_gen = 0;
     for (int l = 0; l < L; ++l) {
-        const size_t nn = (size_t)((c->desc.nx >> l) + 1) * ((c->desc.ny >> l) + 1) * ((c->desc.nz >> l) + 1);
+        const size_t nn = nodes(l);
         if (c->post_nlab[l].n != nn) c->post_nodes_sparse[l] = nullptr; // (a new allocation may get the old address)
         AVS_TRY(c->post_nlab[l].alloc(nn));
         AVS_TRY(c->post_nf[l].alloc(nn));
@@ -694,12 +756,13 @@ static avs_status transfer_impl(avs_ctx *c, float *out_x, float *out_y, float *o
             AVS_TRY(c->post_nval[l][a].alloc(nn));
             AVS_TRY(c->post_nw[l][a].alloc(nn));
             if (!(temporal && c->post_vel_zero[l][a] == c->post_vel[l][a].p)) AVS_HIP(hipMemsetAsync(c->post_vel[l][a].p, 0, nf * sizeof(float), st));
-            c->post_vel_zero[l][a] = nullptr; // (claimed again once this transfer has zeroed what it scatters)
+            c->post_vel_zero[l][a] = nullptr; // (claimed again once this build's release has zeroed what it scatters)
             W.vel[l][a] = c->post_vel[l][a].p;
             W.nval[l][a] = c->post_nval[l][a].p;
             W.nw[l][a] = c->post_nw[l][a].p;
         }
-        // node labels and values: the grids of the previous transfer are cleared where it labelled nodes; anything else is zero-filled
+        if (current) continue; // (the node grids stay as they are, and so do the claims on them)
+        // node labels and values: the grids of the previous build are cleared where it labelled nodes; anything else is zero-filled
         const bool sparse = temporal && c->post_nodes_sparse[l] == c->post_nlab[l].p;
         c->post_nodes_sparse[l] = nullptr;
         if (sparse && c->post_lists_valid && c->post_list[l].p) // ... by the list of the nodes it labelled
@@ -713,23 +776,21 @@ static avs_status transfer_impl(avs_ctx *c, float *out_x, float *out_y, float *o
     // Slab-local context (round 6): the DOFs of the rank's window are scattered and sampled, the faces of the rank's slab are written -- the
     // node values they read depend on faces <= 2 cells (of every level up to the top) away, well inside the window's 12-cell margin; the
     // solution is the whole vector (avs_dist_get_solution gathers it on every rank: n doubles, the one global-sized piece of the frame)
-    const bool slab = c->slab.on;
-    const int32_t *ids = slab ? (const int32_t *)c->wlist[0].p : nullptr;
-    const int64_t n = slab ? c->n_window[0] : c->n_vel;
+    const int32_t *ids = I.ids = slab ? (const int32_t *)c->wlist[0].p : nullptr;
+    const int64_t n = I.n = slab ? c->n_window[0] : c->n_vel;
     if (slab) AVS_REQUIRE(ids && c->x.n >= (size_t)c->n_vel, AVS_ESTATE, "slab-local transfer: gather the solution first (avs_dist_get_solution)");
-    int s_axis = -1, s_lo = 0, s_hi = 0;
-    if (slab) {
-        s_axis = c->slab.axis;
-        s_lo = c->slab.cuts[c->slab.rank];
-        s_hi = c->slab.rank == c->slab.world - 1 ? INT32_MAX : c->slab.cuts[c->slab.rank + 1]; // (the last rank takes the lattice's extra face)
-    }
     if (n) hipLaunchKernelGGL(k_scatter_velocity, dim3(grid_for((size_t)n)), dim3(kBlock), 0, st, P, W, c->vdof.p, n, c->x.p, ids);
-    auto nodes = [&](int l) { return (size_t)((c->desc.nx >> l) + 1) * ((c->desc.ny >> l) + 1) * ((c->desc.nz >> l) + 1); };
+    if (current) { // the lists and counts of the build that made the node grids hold as well
+        I.lists = c->post_lists_valid;
+        for (int l = 0; l < L; ++l) I.hcount[l] = c->post_list_n[l];
+        AVS_HIP(hipGetLastError());
+        return AVS_OK;
+    }
     // T2 lists the nodes it labels, per level, and the later passes walk the lists; sweeps over the node lattices remain for a context
     // without DOFs, node lattices beyond 2^32 entries, a list that overflows, or AVS_PREPASS_TEMPORAL=0
     bool lists = (temporal || slab) && n > 0 && nodes(0) < (1ull << 32);
     c->post_lists_valid = false;
-    unsigned hcount[AVS_MAX_LEVELS] = {};
+    unsigned *hcount = I.hcount;
     if (lists) {
         NodeLists NL{};
         AVS_TRY(c->post_list_count.alloc(AVS_MAX_LEVELS));
@@ -746,7 +807,7 @@ static avs_status transfer_impl(avs_ctx *c, float *out_x, float *out_y, float *o
             hipLaunchKernelGGL(k_nodes_sample_dofs, dim3(grid_for((size_t)(4 * n), 1u << 30)), dim3(kBlock), 0, st, P, W, c->vdof.p, n, NL, ids);
         else
             for (int l = 0; l < L; ++l) hipLaunchKernelGGL(k_nodes_sample, dim3(grid_for(nodes(l))), dim3(kBlock), 0, st, P, W, l, NL);
-        AVS_HIP(hipMemcpyAsync(hcount, c->post_list_count.p, sizeof(hcount), hipMemcpyDeviceToHost, st));
+        AVS_HIP(hipMemcpyAsync(hcount, c->post_list_count.p, sizeof(I.hcount), hipMemcpyDeviceToHost, st));
         AVS_HIP(hipStreamSynchronize(st));
         for (int l = 0; l < L; ++l) lists = lists && hcount[l] <= NL.cap[l];
         AVS_REQUIRE(lists || !slab, AVS_EINTERNAL, "slab-local transfer: a node list overflowed");
@@ -766,8 +827,43 @@ static avs_status transfer_impl(avs_ctx *c, float *out_x, float *out_y, float *o
         for (int l = 0; l < L; ++l) hipLaunchKernelGGL(k_nodes_normalize, dim3(grid_for(nodes(l))), dim3(kBlock), 0, st, P, W, l, (const uint32_t *)nullptr, (size_t)0);
         for (int l = L - 2; l >= 0; --l) hipLaunchKernelGGL(k_nodes_distribute, dim3(grid_for(nodes(l))), dim3(kBlock), 0, st, P, W, l, (const uint32_t *)nullptr, (size_t)0);
     }
+    I.lists = lists;
     AVS_HIP(hipGetLastError());
-    float *outs[3] = {out_x, out_y, out_z};
+    return AVS_OK;
+}
+
+// Release: the scattered face values are zeroed again, and the context records what the staging grids hold now.
+static avs_status interp_release(avs_ctx *c, Interp &I)
+{
+    hipStream_t st = c->stream;
+    const int L = c->desc.levels;
+    if (I.n) hipLaunchKernelGGL(k_unscatter_velocity, dim3(grid_for((size_t)I.n)), dim3(kBlock), 0, st, I.P, I.W, c->vdof.p, I.n, I.ids);
+    AVS_HIP(hipGetLastError());
+    AVS_HIP(hipStreamSynchronize(st));
+    c->post_lists_valid = I.lists; // (the lists name every node whose label / values are non-zero now)
+    for (int l = 0; l < L; ++l) { // what the staging grids hold now (see post_vel_zero / post_nodes_sparse)
+        c->post_list_n[l] = I.hcount[l];
+        c->post_nodes_sparse[l] = c->post_nlab[l].p;
+        for (int a = 0; a < 3; ++a) c->post_vel_zero[l][a] = c->post_vel[l][a].p;
+    }
+    c->post_ready = true;
+    c->post_nodes_gen = I.gen;
+    return AVS_OK;
+}
+
+// Apply (T7): the interpolator and the solution on the regular grid's faces
+static avs_status interp_apply_regular(avs_ctx *c, const Interp &I, float *const outs[3], avs_memspace where, bool in_place)
+{
+    hipStream_t st = c->stream;
+    const PyramidView &P = I.P;
+    const PostView &W = I.W;
+    const bool slab = I.slab;
+    int s_axis = -1, s_lo = 0, s_hi = 0;
+    if (slab) {
+        s_axis = c->slab.axis;
+        s_lo = c->slab.cuts[c->slab.rank];
+        s_hi = c->slab.rank == c->slab.world - 1 ? INT32_MAX : c->slab.cuts[c->slab.rank + 1]; // (the last rank takes the lattice's extra face)
+    }
     const bool padded = c->desc.field_nx != c->desc.nx || c->desc.field_ny != c->desc.ny || c->desc.field_nz != c->desc.nz;
     for (int a = 0; a < 3; ++a) {
         int fr[3] = {c->desc.nx, c->desc.ny, c->desc.nz};
@@ -808,17 +904,66 @@ static avs_status transfer_impl(avs_ctx *c, float *out_x, float *out_y, float *o
             }
         } else if (where == AVS_MEM_HOST) AVS_HIP(copy_out(outs[a], work, nf * sizeof(float), where, st));
     }
-    if (n) hipLaunchKernelGGL(k_unscatter_velocity, dim3(grid_for((size_t)n)), dim3(kBlock), 0, st, P, W, c->vdof.p, n, ids);
-    AVS_HIP(hipGetLastError());
-    AVS_HIP(hipStreamSynchronize(st));
-    c->post_lists_valid = lists; // (the lists name every node whose label / values are non-zero now)
-    for (int l = 0; l < L; ++l) { // what the staging grids hold now (see post_vel_zero / post_nodes_sparse)
-        c->post_list_n[l] = hcount[l];
-        c->post_nodes_sparse[l] = c->post_nlab[l].p;
-        for (int a = 0; a < 3; ++a) c->post_vel_zero[l][a] = c->post_vel[l][a].p;
-    }
-    c->post_ready = true;
     return AVS_OK;
+}
+
+static avs_status transfer_impl(avs_ctx *c, float *out_x, float *out_y, float *out_z, avs_memspace where, bool in_place)
+{
+    avs::OptScope opt_scope_(c);
+    AVS_REQUIRE(c && out_x && out_y && out_z, AVS_EINVAL, "null argument");
+    AVS_REQUIRE(c->solved, AVS_ESTATE, "no solution: call avs_solve first");
+    AVS_REQUIRE(c->have_ridx[0] && c->have_ridx[1] && c->have_ridx[2], AVS_ESTATE, "regular-grid index fields missing (avs_set_regular_index_field)");
+    AVS_REQUIRE(c->tables_ready, AVS_ESTATE, "dof tables missing");
+    AVS_HIP(hipSetDevice(c->desc.device));
+    Scope scope("Apply Octree Solution to Regular Grid"); // cpp:662
+    Interp I;
+    AVS_TRY(interp_build(c, I));
+    float *const outs[3] = {out_x, out_y, out_z};
+    AVS_TRY(interp_apply_regular(c, I, outs, where, in_place));
+    return interp_release(c, I);
+}
+
+// interpSPGrid (interp.cpp:660-845) at the caller's points: build -> k_sample_points -> release
+avs_status avs_sample_velocity(avs_ctx *c, int64_t n_points, const float *positions, const double *origin, float *velocity, uint8_t *inside,
+                               avs_memspace where)
+{
+    avs::OptScope opt_scope_(c);
+    AVS_REQUIRE(c, AVS_EINVAL, "null argument");
+    AVS_REQUIRE(n_points >= 0, AVS_EINVAL, "negative point count");
+    AVS_REQUIRE(n_points == 0 || (positions && velocity), AVS_EINVAL, "null argument");
+    AVS_REQUIRE(!c->slab.on, AVS_ESTATE, "avs_sample_velocity: the context holds a slab-local pre-pass (this rank's window only)");
+    AVS_REQUIRE(c->solved, AVS_ESTATE, "no solution: call avs_solve first");
+    AVS_REQUIRE(c->tables_ready, AVS_ESTATE, "dof tables missing");
+    if (n_points == 0) return AVS_OK;
+    AVS_REQUIRE((uint64_t)n_points < ((uint64_t)1 << 31) * kBlock, AVS_EINVAL, "too many points for one call");
+    AVS_HIP(hipSetDevice(c->desc.device));
+    hipStream_t st = c->stream;
+    const size_t np = (size_t)n_points;
+    DevBuf<float> dpos, dvel;
+    DevBuf<uint8_t> din;
+    const float *pos = positions;
+    float *vel = velocity;
+    uint8_t *in = inside;
+    if (where == AVS_MEM_HOST) {
+        AVS_TRY(dpos.alloc(3 * np));
+        AVS_TRY(dvel.alloc(3 * np));
+        if (inside) AVS_TRY(din.alloc(np));
+        AVS_HIP(copy_in(dpos.p, positions, 3 * np * sizeof(float), where, st));
+        pos = dpos.p;
+        vel = dvel.p;
+        in = inside ? din.p : nullptr;
+    }
+    Interp I;
+    AVS_TRY(interp_build(c, I));
+    const double o[3] = {origin ? origin[0] : 0., origin ? origin[1] : 0., origin ? origin[2] : 0.};
+    hipLaunchKernelGGL(k_sample_points, dim3((unsigned)((np + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, I.P, I.W, n_points, pos, o[0], o[1], o[2],
+                       (double)c->desc.dx, vel, in);
+    AVS_HIP(hipGetLastError());
+    if (where == AVS_MEM_HOST) {
+        AVS_HIP(copy_out(velocity, dvel.p, 3 * np * sizeof(float), where, st));
+        if (inside) AVS_HIP(copy_out(inside, din.p, np, where, st));
+    }
+    return interp_release(c, I); // (synchronises the stream: the host copies have landed)
 }
 
 // node grids after all passes (parity tests): labels int8, values fp32, (n+1)^3 per level

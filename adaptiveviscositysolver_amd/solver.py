@@ -393,6 +393,34 @@ class ViscositySolve:
                                               v[2].ctypes.data, capi.MEM_HOST))
         return lab, v
 
+    def sample_velocity(self, points, origin=None):
+        """The solved octree velocity at arbitrary points (avs_sample_velocity; interpSPGrid, interp.cpp:660-845).  `points`: (N, 3) float32,
+        world units -- a numpy array (host path) or a torch tensor on the context's device (device path); origin: world position of the
+        grid's lower corner (None = 0, 0, 0).  Returns (velocity (N, 3) float32, inside (N,) uint8) of the same kind; points outside the
+        grid or under no ACTIVE cell get velocity 0 and inside 0."""
+        org = None if origin is None else np.ascontiguousarray(origin, np.float64).reshape(3)
+        po = None if org is None else org.ctypes.data
+        if isinstance(points, np.ndarray):
+            pts = np.ascontiguousarray(points, np.float32)
+            if pts.ndim != 2 or pts.shape[1] != 3:
+                raise ValueError("points must have shape (N, 3)")
+            vel = np.empty(pts.shape, np.float32)
+            inside = np.empty(pts.shape[0], np.uint8)
+            capi.check(self.lib.avs_sample_velocity(self.h, pts.shape[0], pts.ctypes.data, po, vel.ctypes.data, inside.ctypes.data, capi.MEM_HOST))
+            return vel, inside
+        import torch
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError("points must have shape (N, 3)")
+        if not points.is_cuda:
+            raise ValueError("a torch tensor of points must live on the context's device (host points: pass a numpy array)")
+        pts = points.to(torch.float32).contiguous()
+        vel = torch.empty_like(pts)
+        inside = torch.empty(pts.shape[0], dtype=torch.uint8, device=pts.device)
+        # the library works on the context's stream: order it after the caller's work on torch's current stream, and torch's after it
+        torch.cuda.current_stream(pts.device).synchronize()
+        capi.check(self.lib.avs_sample_velocity(self.h, pts.shape[0], pts.data_ptr(), po, vel.data_ptr(), inside.data_ptr(), capi.MEM_DEVICE))
+        return vel, inside
+
     def edge_stencils(self):
         ne = self.info().n_edge
         return self._stencils(self.lib.avs_get_edge_stencils, ne, ne, capi.EDGE_STENCIL_CAP, capi.EDGE_BOUNDARY_CAP)

@@ -133,7 +133,8 @@ typedef struct avs_ctx avs_ctx;
 const char *avs_last_error(void);
 const char *avs_version(void);
 /* ABI revision of this header: bumped whenever a struct layout or the set of exported entries changes (2: round 5 -- avs_matrix_format
- * carries struct_size, avs_solve_info.cancelled, avs_cancel; the measurement entries moved to libavs_probe.so in round 4). */
+ * carries struct_size, avs_solve_info.cancelled, avs_cancel; the measurement entries moved to libavs_probe.so in round 4).
+ * Purely additive since (no revision): the entry avs_sample_velocity. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -343,6 +344,25 @@ avs_status avs_transfer_to_regular_grid(avs_ctx *ctx, float *out_x, float *out_y
 avs_status avs_transfer_to_regular_grid_in_place(avs_ctx *ctx, float *vel_x, float *vel_y, float *vel_z);
 /* interpolator node grids after all passes, (n+1)^3 per level: labels (0 inactive, 1 active), values fp32 */
 avs_status avs_get_node_grid(avs_ctx *ctx, int32_t level, int8_t *labels, float *vx, float *vy, float *vz, avs_memspace where);
+/* interpSPGrid (interp.h:140, interp.cpp:660-845) for arbitrary positions, all three components per point: the solved octree velocity
+ * anywhere in the grid (particle updates, markers, render grids of another resolution or offset, probes), by the same T-junction-aware
+ * trilinear / node-plus-bubble interpolation the transfer applies on the regular face lattice -- at a face position of that lattice
+ * component `axis` equals the transfer's value bit for bit.  A position becomes q[a] = ((double)p[a] - origin[a]) / dx in fp64 (level-0
+ * cells, dx of the avs_desc).  Positions are handled in exact index space (every index position the reference derives is q scaled by a
+ * power of two, minus the lattice's half-cell offset); HDK's fp32 posToIndex round trip is not reproduced; where it would decide a tie
+ * (a point lying exactly on a cell boundary) the forward cell is taken.  A point is outside when q is NaN or outside [0, n_a], or when no
+ * level holds an ACTIVE cell over it (the reference asserts there): velocity 0, 0, 0 and inside = 0; nothing is read out of bounds for it.
+ * Points are evaluated in caller order (no sorting); the result of a point does not depend on the others.
+ * Needs a solution (avs_solve, avs_set_solution, or avs_dist_get_solution on a context that is not slab-local) and the dof tables, else
+ * AVS_ESTATE; regular-grid index fields are NOT needed.  n_points == 0: AVS_OK, nothing is touched.  Slab-local contexts
+ * (avs_prepass_set_slab): AVS_ESTATE.  The interpolator's node grids are kept in the context and rebuilt only after the solution, the
+ * pyramids or the dof tables have changed -- sampling after a transfer of the same solution (or the reverse) runs no node pass. */
+avs_status avs_sample_velocity(avs_ctx *ctx, int64_t n_points,
+                               const float *positions,   /* n_points x 3, xyz interleaved, world units */
+                               const double *origin,     /* 3 doubles: world position of the grid's lower corner; NULL = 0,0,0 */
+                               float *velocity,          /* n_points x 3, xyz interleaved */
+                               uint8_t *inside,          /* n_points, may be NULL: 1 = an ACTIVE cell contains the point */
+                               avs_memspace where);
 
 /* ------------------------------------------------------------------------------------------
  * Seam A: only the solve (replaces cpp:611-643).  CSR with int32 row pointers/columns, fp64
