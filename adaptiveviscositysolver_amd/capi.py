@@ -64,7 +64,7 @@ EXPORTED_SYMBOLS = [
 ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 # include/avs_probe.h: exported by libavs_probe.so only (the -DAVS_PROBES build of the same sources)
 PROBE_SYMBOLS = ["avs_spmv_csr", "avs_bench_spmv", "avs_spmv_sell", "avs_bench_stream", "avs_brick_spmv_probe", "avs_spmv_solver_form",
-                 "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe"]
+                 "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe", "avs_pcg_csr_plan"]
 VECTOR_PROBE_F32, VECTOR_PROBE_DS, VECTOR_PROBE_CODED, VECTOR_PROBE_KEEP, VECTOR_PROBE_FUSED = 1, 2, 4, 8, 16   # avs_vector_update_probe flags
 SPMV_FORM_FUSED_DOT, SPMV_FORM_F32, SPMV_FORM_NO_CACHE_HINT = 1, 2, 4   # avs_spmv_csr_form flags (include/avs_probe.h)
 _VOID_RETURN = ("avs_last_error", "avs_version", "avs_destroy", "avs_plan_destroy", "avs_local_group_destroy",
@@ -131,6 +131,20 @@ class MatrixFormat(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(MatrixFormat)
+
+
+class ResidentPlanInfo(C.Structure):
+    """avs_resident_plan_info (include/avs_probe.h): the CU-resident loop's plan of an avs_pcg_csr_plan solve"""
+    _fields_ = [("struct_size", C.c_int32), ("used", C.c_int32), ("workgroups", C.c_int32), ("max_lanes_per_workgroup", C.c_int32),
+                ("lanes", C.c_int64), ("max_rows_per_workgroup", C.c_int32), ("lc_bits", C.c_int32), ("ng", C.c_int32),
+                ("lds_bytes", C.c_int32), ("max_quads", C.c_int32), ("long_row_lanes", C.c_int32), ("longest_tail", C.c_int32),
+                ("max_lane_streamed_rows", C.c_int32), ("streamed_rows", C.c_int64), ("streamed_words", C.c_int64),
+                ("max_remote", C.c_int32), ("remap_passes", C.c_int32), ("local_tables", C.c_int32),
+                ("tables_per_workgroup", C.c_int32), ("largest_table", C.c_int32), ("why", C.c_char * 128)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(ResidentPlanInfo)
 
 
 def source_fingerprint():
@@ -209,6 +223,7 @@ def load(probe=False):
         L.avs_brick_wave_stats.argtypes = [vp, C.POINTER(f64)]
         L.avs_spmv_csr_form.argtypes = [i64, vp, vp, vp, vp, vp, i32, C.POINTER(f64), C.POINTER(MatrixFormat), vp]
         L.avs_vector_update_probe.argtypes = [i32, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+        L.avs_pcg_csr_plan.argtypes = L.avs_pcg_csr.argtypes + [C.POINTER(ResidentPlanInfo)]
     L.avs_prepass_create.argtypes = [C.POINTER(PrepassDesc), C.POINTER(vp)]
     L.avs_prepass_destroy.argtypes = [vp]
     L.avs_prepass_destroy.restype = None

@@ -842,9 +842,10 @@ avs_status avs_get_center_stencils(avs_ctx *c, int32_t *cnt, int32_t *idx, doubl
 // ---------------------------------------------------------------------------------------------
 // seam A: solve only
 // ---------------------------------------------------------------------------------------------
-avs_status avs_pcg_csr(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val, const double *b,
-                       double *x, double tol, int32_t max_iters, avs_memspace where, int32_t device, void *stream,
-                       avs_solve_info *info)
+// (plan: avs_pcg_csr_plan of the probe build reports the CU-resident plan of the solve; the product entry passes NULL)
+static avs_status pcg_csr_entry(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val, const double *b,
+                                double *x, double tol, int32_t max_iters, avs_memspace where, int32_t device, void *stream,
+                                avs_solve_info *info, avs_resident_plan_info *plan)
 {
     avs::OptScope opt_scope_(nullptr); // context-free entry: the AVS_* environment of this call
     AVS_REQUIRE(n >= 0 && row_ptr && b && x && (n == 0 || (col && val)), AVS_EINVAL, "null argument");
@@ -916,12 +917,32 @@ avs_status avs_pcg_csr(int64_t n, const int32_t *row_ptr, const int32_t *col, co
         } while (0);
         (void)hipStreamSynchronize(s);
     }
+#ifdef AVS_PROBES
+    if (plan && w) pcg_resident_plan_info(w, plan);
+#else
+    (void)plan;
+#endif
     pcg_destroy(w);
     if (own) (void)hipStreamDestroy(s);
     return rc;
 }
 
+avs_status avs_pcg_csr(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val, const double *b,
+                       double *x, double tol, int32_t max_iters, avs_memspace where, int32_t device, void *stream,
+                       avs_solve_info *info)
+{
+    return pcg_csr_entry(n, row_ptr, col, val, b, x, tol, max_iters, where, device, stream, info, nullptr);
+}
+
 #ifdef AVS_PROBES // measurement / test entries (include/avs_probe.h): compiled into libavs_probe.so only
+avs_status avs_pcg_csr_plan(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val, const double *b, double *x,
+                            double tol, int32_t max_iters, avs_memspace where, int32_t device, void *stream, avs_solve_info *info,
+                            avs_resident_plan_info *plan)
+{
+    AVS_REQUIRE(plan && plan->struct_size >= 8, AVS_EINVAL, "plan: struct_size not set");
+    return pcg_csr_entry(n, row_ptr, col, val, b, x, tol, max_iters, where, device, stream, info, plan);
+}
+
 avs_status avs_spmv_csr(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val, const double *x,
                         double *y, int32_t variant, int32_t repeats, void *stream)
 {

@@ -725,6 +725,8 @@ avs_status build_brick_form(struct ::avs_ctx *c); // avs_brick_build.hip
 #ifdef AVS_PROBES
 // y = A x through the form the loops launch (+ the folded partial sums of x.y of the fused-dot instantiation); avs_api.hip
 avs_status probe_spmv_form(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st);
+// the CU-resident plan of the workspace's last solve (avs_pcg_csr_plan); avs_pcg.hip
+void pcg_resident_plan_info(const PcgWork *w, avs_resident_plan_info *out);
 avs_status spmv_f32_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st); // avs_pcg_f32.inl
 avs_status spmv_mixed_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st, int64_t n_cols = 0); // avs_pcg_mixed.inl
 #endif

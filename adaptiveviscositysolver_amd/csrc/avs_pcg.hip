@@ -2837,6 +2837,42 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
 }
 
 
+#ifdef AVS_PROBES
+// include/avs_probe.h, avs_pcg_csr_plan: what resident_prepare left on the plan of w's last solve, and whether the loop ran it
+void pcg_resident_plan_info(const PcgWork *w, avs_resident_plan_info *out)
+{
+    avs_resident_plan_info o{};
+    const size_t size = out->struct_size > 0 ? std::min((size_t)out->struct_size, sizeof(o)) : 0;
+    o.struct_size = (int32_t)size;
+    o.used = w->resident_used;
+    const char *why = "";
+    if (const ResidentPlan *pl = w->resident) {
+        o.workgroups = pl->G;
+        o.max_lanes_per_workgroup = pl->max_lanes;
+        o.lanes = pl->n_lanes;
+        o.max_rows_per_workgroup = pl->max_rows;
+        o.lc_bits = pl->lc_bits;
+        o.ng = pl->ng;
+        o.lds_bytes = (int32_t)pl->lds;
+        o.max_quads = pl->max_quads;
+        o.long_row_lanes = pl->long_lanes;
+        o.longest_tail = pl->longest_tail;
+        o.max_lane_streamed_rows = pl->max_lane_streamed;
+        o.streamed_rows = pl->streamed_rows;
+        o.streamed_words = pl->streamed_words;
+        o.max_remote = pl->max_remote;
+        o.remap_passes = pl->remap_passes;
+        o.local_tables = pl->local ? 1 : 0;
+        o.tables_per_workgroup = pl->local ? pl->lt_gpw : 0;
+        o.largest_table = pl->lt_max;
+        if (!o.used) why = !pl->why.empty() ? pl->why.c_str() : w->resident_faults ? "a bounded wait of the loop timed out" : "not tried";
+    } else if (!o.used)
+        why = "not planned (no dictionary-coded form, or the loop is switched off)";
+    snprintf(o.why, sizeof(o.why), "%s", why);
+    memcpy(out, &o, size);
+}
+#endif
+
 // (KEEP is a template parameter of the vector kernels: see stream_load_k)
 #define AVS_VEC_LAUNCH(KERNEL, C, F, ...)                                                                             \
     do {                                                                                                              \

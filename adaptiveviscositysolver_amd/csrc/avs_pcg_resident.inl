@@ -999,6 +999,10 @@ struct ResidentPlan {
     uint64_t key_epoch = 0;
     bool ok = false, tried = false;
     std::string why;
+    // what the plan turned out to be (reported by avs_pcg_csr_plan, include/avs_probe.h: a test names the edge it reached); the counts of
+    // a refused plan hold what was known when it stopped
+    int64_t n_lanes = 0, streamed_rows = 0, streamed_words = 0;
+    int max_lanes = 0, max_rows = 0, long_lanes = 0, longest_tail = 0, max_lane_streamed = 0, max_remote = 0, remap_passes = 0, lt_max = 0;
 };
 
 static bool resident_wanted(bool distributed)
@@ -1055,6 +1059,8 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
                             // re-plans, which also tries the resident loop again after a fault retired the other plan)
     memcpy(pl->key, key, sizeof(key));
     pl->key_n = A.n;
+    pl->n_lanes = pl->streamed_rows = pl->streamed_words = 0;
+    pl->max_lanes = pl->max_rows = pl->long_lanes = pl->longest_tail = pl->max_lane_streamed = pl->max_remote = pl->remap_passes = pl->lt_max = 0;
     const size_t esz = f32 ? sizeof(float) : sizeof(double); // LDS entry of the vector slices, remote columns and tables
     const bool verbose = cur_opt().resident_verbose > 0;
     timespec plan_t0{};
@@ -1180,14 +1186,23 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     // quads a lane streams per iteration (cost model, stream layout)
     std::vector<int32_t> lane_sw((size_t)L, 0);
     int64_t stream_words = 0;
+    pl->n_lanes = L;
     for (int64_t l = 0; l < L; ++l) {
         const int m = (int)((lmeta[(size_t)l] >> 3) & 127u);
+        if (lmeta[(size_t)l] >> 10) { // (a long row's lane: one register row, no streamed rows, the tail's words above bit 10)
+            pl->long_lanes++;
+            pl->longest_tail = std::max(pl->longest_tail, (int)(lmeta[(size_t)l] >> 10));
+            continue;
+        }
+        pl->streamed_rows += m;
+        pl->max_lane_streamed = std::max(pl->max_lane_streamed, m);
         if (m) {
             const int64_t r = (int64_t)lrow[(size_t)l] + (int64_t)(lmeta[(size_t)l] & 7u);
             for (int64_t q = r; q < r + m; ++q) lane_sw[(size_t)l] += (rp[(size_t)q + 1] - rp[(size_t)q] + kResQuadWords - 1) / kResQuadWords; // quads
             stream_words += rp[(size_t)(r + m)] - rp[(size_t)r];
         }
     }
+    pl->streamed_words = stream_words;
     std::vector<int32_t> wl((size_t)G + 1), wr((size_t)G + 1), rc((size_t)G);
     int max_rows = 0;
     int code_bits = 1;
@@ -1204,6 +1219,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     int64_t chunk_cols = std::min<int64_t>(n_ext, kRemapChunk);
     if (cur_opt().resident_remap_chunk >= 512) // tests: several bitmap passes on a small system
         chunk_cols = std::min<int64_t>(chunk_cols, (cur_opt().resident_remap_chunk + 511) / 512 * 512);
+    pl->remap_passes = (int)((n_ext + chunk_cols - 1) / chunk_cols);
     const size_t remap_lds = ((size_t)(((chunk_cols + 31) / 32 + kRemapBlock - 1) / kRemapBlock) * (kRemapBlock + 1) + 2) * sizeof(unsigned);
     DevBuf<int> fail;
     if (pl->wg_row0.alloc((size_t)G + 1) != AVS_OK || pl->rwords.alloc((size_t)A.nnz) != AVS_OK || pl->rem_count.alloc((size_t)G) != AVS_OK ||
@@ -1429,6 +1445,9 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     }
     }
     stage("split + re-encoding rounds");
+    pl->max_rows = max_rows;
+    pl->max_remote = *std::max_element(rc.begin(), rc.end());
+    pl->lt_max = lt_max;
     if (verbose) {
         std::vector<int32_t> srt(rc);
         std::sort(srt.begin(), srt.end());
@@ -1565,6 +1584,7 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
                         "%d row-local vectors in global memory, LDS %zu B, %s vectors\n", (long long)n, (long long)L, (long long)lpw, G, max_rows, lc_bits, ng, lds,
                 f32 ? "float" : "fp64");
     pl->G = G;
+    pl->max_lanes = (int)lpw;
     pl->lc_bits = lc_bits;
     pl->max_quads = max_quads;
     pl->ng = ng;

@@ -47,6 +47,37 @@ avs_status avs_dist_spmv_local_form(avs_ctx *ctx, const double *x_ext, double *y
 avs_status avs_spmv_csr_form(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val, const double *x, double *y,
                              int32_t flags, double *dot_out, avs_matrix_format *fmt, void *stream);
 
+/* avs_pcg_csr (same arguments, same solve, same AVS_* environment) + the CU-resident loop's plan for the caller's matrix: which of the
+ * plan's edges the solve reached.  The caller sets struct_size; fields past it are not written.  `used`: the resident loop ran the solve
+ * (= info->resident); otherwise `why` holds the reason (the plan's refusal, a refused cooperative launch, a timed-out wait) and the
+ * counts hold what the plan had worked out before it stopped (0 where it had not got that far). */
+typedef struct {
+    int32_t struct_size;
+    int32_t used;
+    int32_t workgroups;             /* G: CUs the loop runs on (AVS_CG_RESIDENT_CUS) */
+    int32_t max_lanes_per_workgroup;
+    int64_t lanes;
+    int32_t max_rows_per_workgroup;
+    int32_t lc_bits;                /* workgroup-local column bits of the 25-bit word */
+    int32_t ng;                     /* tier: row-local vectors kept in global memory (k_cg_resident<NG, ...>) */
+    int32_t lds_bytes;
+    int32_t max_quads;              /* register quads a lane uses (AVS_CG_RESIDENT_MAX_QUADS) */
+    int32_t long_row_lanes;         /* lanes that hold one row longer than 5 max_quads words ... */
+    int32_t longest_tail;           /* ... and the most words such a row leaves in memory */
+    int32_t max_lane_streamed_rows; /* most streamed rows of one lane */
+    int64_t streamed_rows;          /* > 0: the STREAM instantiation */
+    int64_t streamed_words;
+    int32_t max_remote;             /* most remote columns of a workgroup (its cache fill takes ceil(max_remote / 4096) trips) */
+    int32_t remap_passes;           /* bitmap passes of the re-encoding kernel (AVS_CG_RESIDENT_REMAP_CHUNK) */
+    int32_t local_tables;           /* the LT instantiation (AVS_RESIDENT_LOCAL_TABLES) */
+    int32_t tables_per_workgroup;   /* 1, or 16: one per wave */
+    int32_t largest_table;
+    char why[128];
+} avs_resident_plan_info;
+avs_status avs_pcg_csr_plan(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val, const double *b, double *x,
+                            double tol, int32_t max_iters, avs_memspace where, int32_t device, void *stream, avs_solve_info *info,
+                            avs_resident_plan_info *plan);
+
 /* Measurement: load balance of the brick kernel's row walk -- per G tile the quads of the slowest of the eight waves against the mean wave
  * (printed to stderr; out6 = {tiles, rows per tile, quads per row, slowest-wave quads, mean-wave quads, 0}) */
 avs_status avs_brick_wave_stats(avs_ctx *ctx, double *out6);

@@ -112,8 +112,10 @@ def test_resident_direct_transport_world_1(built_lib):
 
 
 def test_resident_long_row_path(resident_env, built_lib):
-    """Rows that do not fit a lane's registers keep their first words there and read the rest from memory.  No scene here has a row
-    of more than 75 merged entries, so the test lowers the quads a lane may use to 4 (20 words): every transition row takes the path."""
+    """Rows that do not fit a lane's registers keep their first words there and read the rest from memory.  No octree scene here has a
+    row of more than 75 merged entries, so this test lowers the quads a lane may use to 4 (20 words): every transition row takes the
+    path.  Rows that are naturally longer than 75 words, at the real 15 quads (tails of 1, 2, 5, 75 and 925 words), are the long_arrows
+    and tier_ng3_stream cases of tests/resident_edges.py, checked iterate by iterate in tests/test_gpu_resident_edges.py."""
     os.environ["AVS_CG_RESIDENT_MAX_QUADS"] = "4"
     try:
         sc = scenes.sphere(64, 4)
