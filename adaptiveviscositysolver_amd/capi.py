@@ -58,7 +58,7 @@ EXPORTED_SYMBOLS = [
     "avs_spmv_tile_rows", "avs_dist_assemble", "avs_dist_get_plan_sizes", "avs_dist_get_overlap_tiles", "avs_dist_get_plan_arrays", "avs_dist_solve", "avs_dist_get_solution",
     "avs_dist_get_info", "avs_dist_init_hosted", "avs_dist_export_blob", "avs_dist_import_blobs",
     "avs_prepass_set_slab", "avs_prepass_get_window", "avs_dist_bind_prepass", "avs_dist_get_cuts", "avs_set_solution",
-    "avs_sample_velocity",
+    "avs_sample_velocity", "avs_get_octree_cells", "avs_prepass_get_octree_cells",
 ]
 # avs_allreduce_i32_fn: avs_status (*)(int32_t *device_data, int64_t count, void *stream, void *user)
 ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -240,6 +240,8 @@ def load(probe=False):
     L.avs_transfer_to_regular_grid_in_place.argtypes = [vp, vp, vp, vp]
     L.avs_get_node_grid.argtypes = [vp, i32, vp, vp, vp, vp, i32]
     L.avs_sample_velocity.argtypes = [vp, i64, vp, vp, vp, vp, i32]
+    L.avs_get_octree_cells.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i32]
+    L.avs_prepass_get_octree_cells.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i32]
     L.avs_get_dof_table.argtypes = [vp, i32, vp, i32]
     L.avs_plan_owners.argtypes = [i64, vp, vp, i32, i32, i32, i32, vp]
     L.avs_plan_create.argtypes = [i64, vp, vp, vp, i32, i32, C.POINTER(vp)]

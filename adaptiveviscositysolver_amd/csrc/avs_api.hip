@@ -116,6 +116,7 @@ Options options_from_env()
     o.mixed_precision = env_int("AVS_MIXED_PRECISION", 0) != 0;
     o.dist_mixed_precision = env_int("AVS_DIST_MIXED_PRECISION", 0) != 0;
     o.prepass_temporal = env_int("AVS_PREPASS_TEMPORAL", 1) != 0;
+    o.cells_grid_cap = env_int("AVS_CELLS_GRID_CAP", 0);
     { const int v = env_int("AVS_POST_DOF_SAMPLE", -1); o.post_dof_sample = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.resident_cus = env_int("AVS_CG_RESIDENT_CUS", 0);
     o.resident_equal_lanes = getenv("AVS_CG_RESIDENT_EQUAL_LANES") != nullptr;

@@ -108,6 +108,7 @@ struct Options {
     int fused_timeout_ms = 2000; // AVS_PCG_FUSED_TIMEOUT_MS: bound of that barrier's wait
     int post_dof_sample = -1;    // AVS_POST_DOF_SAMPLE: the transfer samples its nodes from the velocity DOFs (1) / by a sweep over the node lattices (0);
                                  // -1: from the DOFs when the level-0 node lattice has more than 32 x as many nodes as there are DOFs
+    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) at that many workgroups (tests: the walks wrap on small lattices)
     int prepass_temporal = 1;    // AVS_PREPASS_TEMPORAL: the device pre-pass skips what its allocations already hold from their last filling (0: every run fills everything)
     int f32_vectors = -1;        // AVS_F32_VECTORS: AVS_PRECISION_F32 contexts iterate on float vectors with float scalars (what Eigen's float CG does):
                                  // 1 always, 0 never (fp64 iteration on the float system), -1 auto: where the system is too large for the
@@ -596,6 +597,23 @@ avs_status adopt_prepass_lattices(avs_ctx *c, const PrepassLoan &loan);         
 avs_status adopt_regular_index_lattice(avs_ctx *c, int32_t axis, std::shared_ptr<DevBuf<int32_t>> handle, const uint8_t *occ16,
                                        const int occ16_tiles[3]);                                          // avs_post.hip
 
+// Octree cell export (avs_cells.hip): avs_get_octree_cells / avs_prepass_get_octree_cells over one implementation.  The scratch lives in
+// the object that is asked (tile counts, their scan, the list of non-empty tiles, staging of host-bound records) and is reused across calls.
+struct CellsScratch {
+    DevBuf<int32_t> counts, offsets, scan_tmp, list, level, ijk;
+    DevBuf<long long> sums;
+    DevBuf<float> pos, pscale;
+};
+struct CellsSource {
+    const int8_t *labels[AVS_MAX_LEVELS];
+    int levels, n[3]; // levels present, level-0 cells per axis
+    double dx;
+    int grid_cap;     // Options::cells_grid_cap as of the object's creation
+};
+avs_status octree_cells_check_args(int64_t capacity, const int64_t *n_cells, avs_memspace where);
+avs_status export_octree_cells(CellsScratch &S, const CellsSource &src, hipStream_t st, const double *origin, int64_t capacity, float *position,
+                               float *pscale, int32_t *level, int32_t *ijk, int64_t *n_cells, int64_t *per_level, avs_memspace where);
+
 // avs_desc::precision == AVS_PRECISION_F32: the solution as the reference's Eigen::VectorXf holds it (avs_api.hip)
 void narrow_solution_if_f32(avs_ctx *c, double *x, int64_t n);
 
@@ -807,6 +825,8 @@ struct avs_ctx {
     // assemble, avs_prepass_apply, index and label setters).  post_nodes_gen: the generation the node grids (post_nval / post_nlab) were
     // built for, 0 = none -- an interpolator build that finds them current skips the node passes (avs_post.hip, interp_build)
     uint64_t solution_gen = 1, post_nodes_gen = 0;
+
+    avs::CellsScratch cells; // avs_get_octree_cells (avs_cells.hip)
 
     // brick-major copy of the system used by the solve (avs_reorder.hip); perm: new -> old
     avs::DevBuf<int32_t> perm, inv, p_row_ptr, p_col;

@@ -1067,6 +1067,7 @@ struct avs_prepass {
     long long dof_cap[3] = {0, 0, 0};          // ... sized from the previous run's counts (0: none this run)
     bool dof_valid[3] = {false, false, false}; // ... and complete (the count did not outgrow the capacity)
     int64_t prev_counts[3] = {0, 0, 0};
+    int cells_grid_cap = 0; // AVS_CELLS_GRID_CAP as of avs_prepass_create (avs_cells.hip)
     bool temporal = true; // AVS_PREPASS_TEMPORAL=0: every run fills everything (measurement / tests)
     // slab-local mode (avs_prepass_set_slab)
     avs::SlabWindow slab;
@@ -1077,6 +1078,7 @@ struct avs_prepass {
     int64_t n_window[3] = {0, 0, 0};
     const float *liq = nullptr, *sol = nullptr; // the SDFs of the running call (the caller's device arrays in slab mode, else the copies above)
     int64_t counts[4] = {0, 0, 0, 0}; // velocity, edge, centre, regular
+    avs::CellsScratch cells; // avs_prepass_get_octree_cells (avs_cells.hip)
     double ms[4] = {0, 0, 0, 0};
     bool ready = false;
 };
@@ -1248,7 +1250,9 @@ avs_status avs_prepass_create(const avs_prepass_desc *d, avs_prepass **out)
         if (lg < L) L = lg;
     }
     p->max_levels = L < 1 ? 1 : L;
-    p->temporal = avs::options_from_env().prepass_temporal != 0;
+    const avs::Options env_opt = avs::options_from_env();
+    p->temporal = env_opt.prepass_temporal != 0;
+    p->cells_grid_cap = env_opt.cells_grid_cap;
     *out = p;
     return AVS_OK;
 }
@@ -1910,6 +1914,28 @@ avs_status avs_prepass_get_weights(avs_prepass *p, avs_field_kind kind, int32_t 
     AVS_HIP(copy_out(out, src, g3(r).vol() * sizeof(float), where, p->stream));
     AVS_HIP(hipStreamSynchronize(p->stream));
     return AVS_OK;
+}
+
+// the ACTIVE cells of the label pyramid as points (oct.cpp:245-308): protocol in include/avs.h, kernels in avs_cells.hip
+avs_status avs_prepass_get_octree_cells(avs_prepass *p, const double *origin, int64_t capacity, float *position, float *pscale, int32_t *level,
+                                        int32_t *ijk, int64_t *n_cells, int64_t *per_level, avs_memspace where)
+{
+    (void)hipGetLastError(); // (a stale error of the host application's own HIP calls on this thread is not ours: see OptScope)
+    AVS_REQUIRE(p, AVS_EINVAL, "null argument");
+    AVS_TRY(avs::octree_cells_check_args(capacity, n_cells, where));
+    AVS_REQUIRE(!p->slab.on, AVS_ESTATE, "avs_prepass_get_octree_cells: the pre-pass is slab-local (labels inside this rank's window only)");
+    AVS_REQUIRE(p->ready, AVS_ESTATE, "call avs_prepass_run first");
+    avs::CellsSource src{};
+    for (int l = 0; l < p->levels; ++l) src.labels[l] = p->labels[l].p;
+    src.levels = p->levels;
+    src.n[0] = p->desc.nx;
+    src.n[1] = p->desc.ny;
+    src.n[2] = p->desc.nz;
+    src.dx = p->desc.dx;
+    src.grid_cap = p->cells_grid_cap;
+    AVS_HIP(hipSetDevice(p->desc.device));
+    Scope scope("Output Octree Geometry"); // oct.cpp:245
+    return avs::export_octree_cells(p->cells, src, p->stream, origin, capacity, position, pscale, level, ijk, n_cells, per_level, where);
 }
 
 avs_status avs_prepass_apply(avs_prepass *p, avs_ctx *ctx)

@@ -39,6 +39,7 @@ class ViscositySolve:
         self.h = h
         self.levels = int(levels)
         self.precision = int(precision)
+        self.device = int(device)
         self.counts = None
         self.field_res = tuple(fr[a] or self.res[a] for a in range(3))
 
@@ -421,6 +422,14 @@ class ViscositySolve:
         capi.check(self.lib.avs_sample_velocity(self.h, pts.shape[0], pts.data_ptr(), po, vel.data_ptr(), inside.data_ptr(), capi.MEM_DEVICE))
         return vel, inside
 
+    def octree_cells(self, origin=None, device_arrays=False):
+        """The ACTIVE cells of the label pyramid as points (avs_get_octree_cells; outputOctreeGeometry, oct.cpp:245-308), in the reference's
+        sweep order.  Returns position (n, 3) float32 (cell centres, world units; origin: the grid's lower corner, None = 0, 0, 0),
+        pscale (n,) float32 (the level's voxel size), level (n,) int32, ijk (n, 3) int32 and per_level (MAX_LEVELS,) int64: NumPy arrays,
+        or with device_arrays=True torch tensors on the context's device, written there by the kernel (they go straight into
+        sample_velocity).  Needs labels only: no assembly, no solve."""
+        return _octree_cells(self.lib.avs_get_octree_cells, self.h, origin, device_arrays, self.device)
+
     def edge_stencils(self):
         ne = self.info().n_edge
         return self._stencils(self.lib.avs_get_edge_stencils, ne, ne, capi.EDGE_STENCIL_CAP, capi.EDGE_BOUNDARY_CAP)
@@ -429,6 +438,35 @@ class ViscositySolve:
         nc = self.info().n_center
         return self._stencils(self.lib.avs_get_center_stencils, 3 * nc, nc, capi.CENTER_STENCIL_CAP,
                               capi.CENTER_BOUNDARY_CAP)
+
+
+def _octree_cells(fn, handle, origin, device_arrays, device):
+    """count query, allocate, fill -- shared by ViscositySolve.octree_cells and DevicePrepass.octree_cells"""
+    org = None if origin is None else np.ascontiguousarray(origin, np.float64).reshape(3)
+    po = None if org is None else org.ctypes.data
+    n = C.c_int64()
+    per_level = np.zeros(capi.MAX_LEVELS, np.int64)
+    capi.check(fn(handle, po, 0, None, None, None, None, C.byref(n), per_level.ctypes.data, capi.MEM_HOST))
+    n = int(n.value)
+    got = C.c_int64()
+    if not device_arrays:
+        out = (np.empty((n, 3), np.float32), np.empty(n, np.float32), np.empty(n, np.int32), np.empty((n, 3), np.int32))
+        if n:
+            capi.check(fn(handle, po, n, *[a.ctypes.data for a in out], C.byref(got), None, capi.MEM_HOST))
+        return (*out, per_level)
+    import torch
+    dev = torch.device("cuda", int(device))
+    out = (torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+           torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3), dtype=torch.int32, device=dev))
+    if n:
+        # the library writes on the object's stream: it must not start before torch's current stream is done with the memory the
+        # caching allocator has just handed out (as sample_velocity does) ...
+        torch.cuda.current_stream(dev).synchronize()
+        capi.check(fn(handle, po, n, *[a.data_ptr() for a in out], C.byref(got), None, capi.MEM_DEVICE))
+        # ... and the records are complete in order of the object's stream only (a stream the library may have created itself, which
+        # torch cannot name): torch's streams may read them once the device has drained
+        torch.cuda.synchronize(dev)
+    return (*out, per_level)
 
 
 def pcg_csr(row_ptr, col, val, b, x0, tol=1e-3, max_iters=2500, device=0):
@@ -461,6 +499,7 @@ class DevicePrepass:
         h = C.c_void_p()
         capi.check(self.lib.avs_prepass_create(C.byref(d), C.byref(h)))
         self.h = h
+        self.device = int(device)
         self.info = None
 
     def close(self):
@@ -515,6 +554,11 @@ class DevicePrepass:
     def apply(self, solver):
         capi.check(self.lib.avs_prepass_apply(self.h, solver.h))
         solver.counts = (self.info.n_velocity, self.info.n_edge, self.info.n_center)
+
+    def octree_cells(self, origin=None, device_arrays=False):
+        """The ACTIVE cells of the last run's label pyramid as points (avs_prepass_get_octree_cells): what ViscositySolve.octree_cells
+        returns, without a solve context ("Only Output Octree")."""
+        return _octree_cells(self.lib.avs_prepass_get_octree_cells, self.h, origin, device_arrays, self.device)
 
     def _shape(self, kind, level, axis):
         r = [self.res[0] >> level, self.res[1] >> level, self.res[2] >> level]

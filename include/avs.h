@@ -134,7 +134,8 @@ const char *avs_last_error(void);
 const char *avs_version(void);
 /* ABI revision of this header: bumped whenever a struct layout or the set of exported entries changes (2: round 5 -- avs_matrix_format
  * carries struct_size, avs_solve_info.cancelled, avs_cancel; the measurement entries moved to libavs_probe.so in round 4).
- * Purely additive since (no revision): the entry avs_sample_velocity. */
+ * Purely additive since (no revision): the entry avs_sample_velocity.
+ * Purely additive since (no revision): the entries avs_get_octree_cells and avs_prepass_get_octree_cells. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -364,6 +365,34 @@ avs_status avs_sample_velocity(avs_ctx *ctx, int64_t n_points,
                                uint8_t *inside,          /* n_points, may be NULL: 1 = an ACTIVE cell contains the point */
                                avs_memspace where);
 
+/* The octree's ACTIVE cells as points (HDK_OctreeGrid::outputOctreeGeometry, oct.cpp:245-308: the "Output Octree Geometry" / "Only Output
+ * Octree" toggles, cpp:78-79, 283-294), computed on the device from the label pyramid the context holds -- labels set by avs_set_labels
+ * or lent by avs_prepass_apply.  avs_prepass_get_octree_cells (below, with the pre-pass) is the same call on a pre-pass object.
+ * Which cells: every cell labelled AVS_ACTIVE at every level 0 .. levels-1; whether the pyramid is a valid octree is not judged.  On a
+ *   padded grid (field_n*) the cells outside the simulation grid are INACTIVE (oct.cpp:375-379) and never appear.
+ * Order: the reference's sweep -- levels ascending; inside a level UT_VoxelArray tile order (16^3 tiles, x fastest, then y, then z); inside
+ *   a tile x fastest, then y, then z; a lattice extent that is no multiple of 16 ends in a partial tile of the voxels that exist.
+ * Values of record r: level[r] = l; ijk[3r ..] = the cell's index on its level's lattice; pscale[r] = (float)(dx * 2^l), the level's voxel
+ *   size; position[3r + a] = (float)(origin[a] + (i_a + 0.5) * dx * 2^l), evaluated in fp64 and rounded once -- the convention of
+ *   avs_sample_velocity (q = (p - origin) / dx).  HDK's own fp32 indexToPos arithmetic is closed source and is not reproduced.
+ * Capacity protocol: *n_cells is always written, per_level[0 .. AVS_MAX_LEVELS) when non-NULL (the count per level).  capacity == 0 is a
+ *   count query: the array pointers are ignored and may be NULL.  capacity >= *n_cells: exactly *n_cells records are written and nothing
+ *   behind them is touched.  0 < capacity < *n_cells: AVS_EINVAL, no array element is written.  No ACTIVE cell: AVS_OK, *n_cells = 0.
+ *   position, pscale, level or ijk == NULL skips that array.  The count is 64-bit; one call emits at most 2^31 - 1 cells (tile offsets
+ *   are 32-bit): beyond that a count query still answers, a call with capacity > 0 returns AVS_EINVAL.
+ * Memory: AVS_MEM_DEVICE arrays are written by the kernel directly (no staging copy) on the object's stream, and the call returns once the
+ *   count is known -- the records are complete in stream order, so they can go straight into avs_sample_velocity on the same context;
+ *   work on another stream is ordered behind the object's stream by the caller (hipDeviceSynchronize for a stream the library created).
+ *   AVS_MEM_HOST arrays are staged and complete on return.  Scratch (tile counts, offsets, tile list, staging) stays in the object.
+ * State: labels of every level, else AVS_ESTATE; no assembly, solve or index pyramid is needed.  Slab-local contexts and pre-passes
+ *   (avs_prepass_set_slab: labels inside the rank's window only): AVS_ESTATE.  The pre-pass entry needs a completed avs_prepass_run
+ *   (AVS_ESTATE otherwise); a run that found no liquid (levels == 0) gives AVS_OK and *n_cells = 0.
+ * The same labels give the same bytes on every call and in every fresh object. */
+avs_status avs_get_octree_cells(avs_ctx *ctx, const double *origin /* 3, NULL = 0,0,0 */, int64_t capacity,
+                                float *position /* capacity x 3, xyz interleaved, world units */, float *pscale /* capacity */,
+                                int32_t *level /* capacity */, int32_t *ijk /* capacity x 3; may be NULL */,
+                                int64_t *n_cells, int64_t *per_level /* AVS_MAX_LEVELS, may be NULL */, avs_memspace where);
+
 /* ------------------------------------------------------------------------------------------
  * Seam A: only the solve (replaces cpp:611-643).  CSR with int32 row pointers/columns, fp64
  * values; x_inout holds the initial guess on entry and the solution on return.
@@ -429,6 +458,11 @@ avs_status avs_prepass_get_index(avs_prepass *pp, avs_index_kind kind, int32_t l
 avs_status avs_prepass_get_regular_index(avs_prepass *pp, int32_t axis, int32_t *out, avs_memspace where);
 avs_status avs_prepass_get_weights(avs_prepass *pp, avs_field_kind kind /* CENTER / EDGE / FACE weights */, int32_t axis, float *out,
                                    avs_memspace where);
+/* the ACTIVE cells of the label pyramid of the last run as points: avs_get_octree_cells (above) on the pre-pass object -- same order,
+ * values, capacity protocol and memory rules; enqueued on the pre-pass's stream.  No solve context is needed ("Only Output Octree"). */
+avs_status avs_prepass_get_octree_cells(avs_prepass *pp, const double *origin /* 3, NULL = 0,0,0 */, int64_t capacity,
+                                        float *position, float *pscale, int32_t *level, int32_t *ijk /* may be NULL */,
+                                        int64_t *n_cells, int64_t *per_level /* AVS_MAX_LEVELS, may be NULL */, avs_memspace where);
 /* hands labels, index pyramids, DOF counts, regular-grid indices and the three weight fields to a solve context created with
  * levels == info.levels on the same device.  BY REFERENCE (round 5; it used to copy ~12 full-size lattices per level set: 78 GB at
  * 1024^3): the context holds the pre-pass's allocations; the pre-pass keeps two per lattice and its next avs_prepass_run fills the set no

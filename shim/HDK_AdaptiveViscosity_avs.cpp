@@ -9,10 +9,15 @@
 // the GPU: integration weights, refinement mask, octree, classification + numbering (avs_prepass_*), stencils, assembly,
 // Jacobi-PCG (avs_assemble / avs_solve), octree -> regular grid transfer (avs_transfer_to_regular_grid).
 //
-// Not carried over (out of scope): outputOctreeGeometry / "doPrintOctree", the debug unit tests of the octree.
+// The "Output Octree Geometry" / "Only Output Octree" toggles (cpp:78-79, 283-294) are served from the device: the ACTIVE cells come back
+// as host arrays of avs_prepass_get_octree_cells and fill the "octreeGeometry" detail (writeCellPoints below).
+// Not carried over (out of scope): the debug unit tests of the octree.
 #include "HDK_AdaptiveViscosity.h" // the reference's own header, unchanged
 
+#include <GA/GA_Handle.h>
 #include <GAS/GAS_SubSolver.h>
+#include <GU/GU_Detail.h>
+#include <SIM/SIM_GeometryCopy.h>
 #include <SIM/SIM_Object.h>
 #include <SIM/SIM_RawField.h>
 #include <SIM/SIM_ScalarField.h>
@@ -211,6 +216,28 @@ bool write_dump(const char *path, avs_prepass *pp, const avs_prepass_info &info,
     return std::fclose(f) == 0 && ok;
 }
 
+// The "octreeGeometry" detail from the arrays of avs_prepass_get_octree_cells: a point cloud of n cell centres with the per-point
+// attributes the reference's output carries, "pscale" (float) and "octreeLevel" (int).  The library already emits the cells in the
+// reference's sweep order, so point r of the block is record r.
+void writeCellPoints(GU_Detail &gdp, int64_t n, const float *centre, const float *size, const int32_t *depth)
+{
+    gdp.clear(); // no points, no attributes: both are created afresh below
+    GA_RWHandleF pscale(gdp.addFloatTuple(GA_ATTRIB_POINT, "pscale", 1));
+    GA_RWHandleI cellLevel(gdp.addIntTuple(GA_ATTRIB_POINT, "octreeLevel", 1));
+    if (n > 0) {
+        const GA_Offset block = gdp.appendPointBlock((GA_Size)n); // one allocation; offsets block .. block + n - 1
+        UTparallelFor(UT_BlockedRange<int64_t>(0, n), [&](const UT_BlockedRange<int64_t> &range) {
+            for (int64_t r = range.begin(); r != range.end(); ++r) {
+                const GA_Offset pt = block + (GA_Offset)r;
+                gdp.setPos3(pt, centre[3 * r], centre[3 * r + 1], centre[3 * r + 2]);
+                pscale.set(pt, size[r]);
+                cellLevel.set(pt, depth[r]);
+            }
+        });
+    }
+    gdp.bumpDataIdsForAddOrRemove(true, false, false); // points and their attributes are new
+}
+
 } // namespace
 
 bool HDK_AdaptiveViscosity::solveGasSubclass(SIM_Engine &engine, SIM_Object *obj, SIM_Time time, SIM_Time timestep)
@@ -282,8 +309,29 @@ bool HDK_AdaptiveViscosity::solveGasSubclass(SIM_Engine &engine, SIM_Object *obj
         };
         if (!check(avs_prepass_run(h.pp, dense(liquid_sdf, liquid_dense), dense(solid_sdf, solid_dense), AVS_MEM_HOST))) return false;
         if (!check(avs_prepass_get_info(h.pp, &pinfo))) return false;
-        if (pinfo.levels == 0) return true; // no liquid in the refinement band: nothing to do this step
     }
+
+    // ---- "Output Octree Geometry" (cpp:283-294): the ACTIVE cells of the label pyramid, swept on the device ------------------
+    if (getDoPrintOctree()) {
+        UT_PerfMonAutoSolveEvent event(this, "Output Octree Geometry (GPU)");
+        const UT_Vector3 orig = liquid.getOrig(); // lower corner of the simulation grid = of the (padded) octree grid, oct.cpp:13-24
+        const double origin[3] = {orig.x(), orig.y(), orig.z()};
+        int64_t n_cells = 0;
+        if (!check(avs_prepass_get_octree_cells(h.pp, origin, 0, nullptr, nullptr, nullptr, nullptr, &n_cells, nullptr, AVS_MEM_HOST))) return false;
+        std::vector<float> position((size_t)n_cells * 3), pscale((size_t)n_cells);
+        std::vector<int32_t> level((size_t)n_cells);
+        if (n_cells > 0 && !check(avs_prepass_get_octree_cells(h.pp, origin, n_cells, position.data(), pscale.data(), level.data(), nullptr, &n_cells,
+                                                              nullptr, AVS_MEM_HOST)))
+            return false;
+        SIM_GeometryCopy *cells = getOrCreateGeometry(obj, "octreeGeometry"); // the data name the reference's DOP network reads
+        if (!cells) return fail("avs: cannot create the octreeGeometry data");
+        {
+            SIM_GeometryAutoWriteLock lock(cells);
+            writeCellPoints(lock.getGdp(), n_cells, position.data(), pscale.data(), level.data());
+        }
+        if (getOnlyPrintOctree()) return true; // the toggle exists to look at the refinement without paying for a solve
+    }
+    if (pinfo.levels == 0) return true; // no liquid in the refinement band: nothing to do this step
 
     // ---- context + the scalar fields of this frame -----------------------------------------------------------------------
     avs_desc d;
