@@ -64,7 +64,8 @@ EXPORTED_SYMBOLS = [
 ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 # include/avs_probe.h: exported by libavs_probe.so only (the -DAVS_PROBES build of the same sources)
 PROBE_SYMBOLS = ["avs_spmv_csr", "avs_bench_spmv", "avs_spmv_sell", "avs_bench_stream", "avs_brick_spmv_probe", "avs_spmv_solver_form",
-                 "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe", "avs_pcg_csr_plan"]
+                 "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe", "avs_pcg_csr_plan",
+                 "avs_merge_triplets_probe", "avs_exclusive_scan_probe"]
 VECTOR_PROBE_F32, VECTOR_PROBE_DS, VECTOR_PROBE_CODED, VECTOR_PROBE_KEEP, VECTOR_PROBE_FUSED = 1, 2, 4, 8, 16   # avs_vector_update_probe flags
 SPMV_FORM_FUSED_DOT, SPMV_FORM_F32, SPMV_FORM_NO_CACHE_HINT = 1, 2, 4   # avs_spmv_csr_form flags (include/avs_probe.h)
 _VOID_RETURN = ("avs_last_error", "avs_version", "avs_destroy", "avs_plan_destroy", "avs_local_group_destroy",
@@ -147,6 +148,17 @@ class ResidentPlanInfo(C.Structure):
         self.struct_size = C.sizeof(ResidentPlanInfo)
 
 
+class TripletMergeInfo(C.Structure):
+    """avs_triplet_merge_info (include/avs_probe.h): the limits of the device triplet merge and what an avs_merge_triplets_probe run reached"""
+    _fields_ = [("struct_size", C.c_int32), ("fast_limit", C.c_int32), ("wave_limit", C.c_int32), ("merge_lds", C.c_int32),
+                ("scan_tile", C.c_int32), ("long_grid_waves", C.c_int32), ("long_rows", C.c_int32), ("reserved", C.c_int32),
+                ("raw_slots", C.c_int64)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TripletMergeInfo)
+
+
 def source_fingerprint():
     """sha256 (16 hex digits) over the library's sources: kernels, internal headers, the public header.  Counter records under
     profiles/ carry the fingerprint of the tree they were taken with; bench.py only quotes a record whose fingerprint is the running one."""
@@ -224,6 +236,8 @@ def load(probe=False):
         L.avs_spmv_csr_form.argtypes = [i64, vp, vp, vp, vp, vp, i32, C.POINTER(f64), C.POINTER(MatrixFormat), vp]
         L.avs_vector_update_probe.argtypes = [i32, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
         L.avs_pcg_csr_plan.argtypes = L.avs_pcg_csr.argtypes + [C.POINTER(ResidentPlanInfo)]
+        L.avs_merge_triplets_probe.argtypes = [i64, vp, vp, vp, i32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(TripletMergeInfo), vp]
+        L.avs_exclusive_scan_probe.argtypes = [vp, vp, i64, vp]
     L.avs_prepass_create.argtypes = [C.POINTER(PrepassDesc), C.POINTER(vp)]
     L.avs_prepass_destroy.argtypes = [vp]
     L.avs_prepass_destroy.restype = None

@@ -1275,6 +1275,67 @@ avs_status build_initial_guess_rows(avs_ctx *c, const int32_t *ids, int64_t m)
     return AVS_OK;
 }
 
+// The wave-transposed raw layout of n rows of S.row_count[] raw entries: a wave of 64 rows gets 64 x its longest row, S.rawptr[w] = first slot
+// of wave w (entry k of lane l at S.rawptr[w] + 64 k + l).  *nraw: the raw total, *nslots: slots of all waves.  Synchronises.
+static avs_status raw_layout(avs_ctx::AsmScratch &S, int64_t n, hipStream_t st, int32_t *nraw, int32_t *nslots)
+{
+    DevBuf<int32_t> &row_count = S.row_count, &rawptr = S.rawptr, &scan_tmp = S.scan_tmp;
+    AVS_TRY(exclusive_scan_i32(row_count.p, rawptr.p, n, scan_tmp.p, scan_tmp.n, st));
+    *nraw = 0;
+    AVS_HIP(hipMemcpyAsync(nraw, rawptr.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    const int64_t nwaves = (n + 63) >> 6;
+    DevBuf<int32_t> &wslots = S.wave_slots;
+    AVS_TRY(wslots.reserve((size_t)nwaves + 1));
+    hipLaunchKernelGGL(k_wave_slots, dim3(grid_for(nwaves + 1)), dim3(kBlock), 0, st, n, (const int32_t *)row_count.p, wslots.p);
+    AVS_TRY(exclusive_scan_i32(wslots.p, rawptr.p, nwaves, scan_tmp.p, scan_tmp.n, st)); // rawptr now: first slot of every wave
+    *nslots = 0;
+    AVS_HIP(hipMemcpyAsync(nslots, rawptr.p + nwaves, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AVS_HIP(hipStreamSynchronize(st));
+    return AVS_OK;
+}
+
+// K6b + K7 on the raw layout (S.row_count, S.rawptr, S.raw_col, S.raw_val): first-occurrence masks -> unique counts -> row_ptr[n + 1] by scan,
+// then rank, fold and write the final CSR.  Between the two, out(nnz, col, val) names the arrays of >= nnz entries the merge writes: nnz is a
+// REFERENCE to where row_ptr[n] (-1 above INT32_MAX) is being copied -- it holds the count once out() has synchronised the stream; a status
+// other than AVS_OK from out() ends the step there.  The merge launches are left in flight.
+template <class Out>
+static avs_status merge_raw(avs_ctx::AsmScratch &S, int64_t n, bool f32, int32_t *row_ptr, hipStream_t st, Out &&out)
+{
+    DevBuf<int32_t> &row_count = S.row_count, &rawptr = S.rawptr, &scan_tmp = S.scan_tmp, &raw_col = S.raw_col, &ucount = S.ucount;
+    DevBuf<double> &raw_val = S.raw_val;
+    AVS_TRY(ucount.reserve((size_t)n + 1));
+    if (n) {
+        DevBuf<int32_t> &long_rows = S.long_rows;
+        AVS_TRY(long_rows.reserve((size_t)n + 1));
+        AVS_HIP(hipMemsetAsync(long_rows.p, 0, sizeof(int32_t), st));
+        hipLaunchKernelGGL(k_unique_rows, dim3(grid_for(n + 1)), dim3(kBlock), 0, st, n, (const int32_t *)rawptr.p, (int32_t *)raw_col.p,
+                           (const int32_t *)row_count.p, ucount.p, long_rows.p);
+        hipLaunchKernelGGL(k_unique_long, dim3(kLongGrid), dim3(kBlock), 0, st, (const int32_t *)rawptr.p, (int32_t *)raw_col.p, (const int32_t *)row_count.p,
+                           ucount.p, (const int32_t *)long_rows.p);
+    }
+    AVS_TRY(exclusive_scan_i32(ucount.p, row_ptr, n, scan_tmp.p, scan_tmp.n, st));
+    int32_t nnz = 0;
+    AVS_HIP(hipMemcpyAsync(&nnz, row_ptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    int32_t *col = nullptr;
+    double *val = nullptr;
+    AVS_TRY(out(nnz, col, val));
+    // K6b + K7: rank, fold, write the final CSR
+    if (n && f32)
+        hipLaunchKernelGGL(k_merge_rows<true>, dim3(grid_for(n)), dim3(kBlock), 0, st, n, (const int32_t *)rawptr.p, (const int32_t *)raw_col.p,
+                           (const double *)raw_val.p, (const int32_t *)row_count.p, (const int32_t *)row_ptr, col, val);
+    else if (n)
+        hipLaunchKernelGGL(k_merge_rows<false>, dim3(grid_for(n)), dim3(kBlock), 0, st, n, (const int32_t *)rawptr.p, (const int32_t *)raw_col.p,
+                           (const double *)raw_val.p, (const int32_t *)row_count.p, (const int32_t *)row_ptr, col, val);
+    if (n && f32)
+        hipLaunchKernelGGL(k_merge_long<true>, dim3(kLongGrid), dim3(kBlock), 0, st, (const int32_t *)rawptr.p, (const int32_t *)raw_col.p, (const double *)raw_val.p,
+                           (const int32_t *)row_count.p, (const int32_t *)row_ptr, col, val, (const int32_t *)S.long_rows.p);
+    else if (n)
+        hipLaunchKernelGGL(k_merge_long<false>, dim3(kLongGrid), dim3(kBlock), 0, st, (const int32_t *)rawptr.p, (const int32_t *)raw_col.p, (const double *)raw_val.p,
+                           (const int32_t *)row_count.p, (const int32_t *)row_ptr, col, val, (const int32_t *)S.long_rows.p);
+    AVS_HIP(hipGetLastError());
+    return AVS_OK;
+}
+
 // rows `ids[0..m)` (velocity DOFs; nullptr = all, in order) -> CSR with reference-numbered columns + rhs.
 // Row-local work: a rank of a multi-GPU solve assembles only the rows it owns.
 avs_status assemble_rows(avs_ctx *c, const int32_t *ids, int64_t m, DevBuf<int32_t> &row_ptr, DevBuf<int32_t> &col, DevBuf<double> &val,
@@ -1303,61 +1364,30 @@ avs_status assemble_rows(avs_ctx *c, const int32_t *ids, int64_t m, DevBuf<int32
     if (n) hipLaunchKernelGGL((k_rows<false>), dim3(grid_for(n)), dim3(kBlock), 0, st, P, c->vdof.p, n, E, C, c->x0.p,
                               (const int32_t *)nullptr, (int32_t *)nullptr, (double *)nullptr, row_count.p, (double *)nullptr, err.p, ids);
     // raw total (reported) and the wave-transposed layout: a wave of 64 rows gets 64 x its longest row
-    AVS_TRY(exclusive_scan_i32(row_count.p, rawptr.p, n, scan_tmp.p, scan_tmp.n, st));
-    int32_t nraw = 0;
-    AVS_HIP(hipMemcpyAsync(&nraw, rawptr.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    const int64_t nwaves = (n + 63) >> 6;
-    DevBuf<int32_t> &wslots = c->scratch.wave_slots;
-    AVS_TRY(wslots.reserve((size_t)nwaves + 1));
-    hipLaunchKernelGGL(k_wave_slots, dim3(grid_for(nwaves + 1)), dim3(kBlock), 0, st, n, (const int32_t *)row_count.p, wslots.p);
-    AVS_TRY(exclusive_scan_i32(wslots.p, rawptr.p, nwaves, scan_tmp.p, scan_tmp.n, st)); // rawptr now: first slot of every wave
-    int32_t nslots = 0;
-    AVS_HIP(hipMemcpyAsync(&nslots, rawptr.p + nwaves, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    AVS_HIP(hipStreamSynchronize(st));
+    int32_t nraw = 0, nslots = 0;
+    AVS_TRY(raw_layout(c->scratch, n, st, &nraw, &nslots));
     tr.mark("dry run, scans");
     AVS_REQUIRE(nraw >= 0 && nslots >= 0, AVS_EINVAL, "raw triplet count exceeds int32 (the scan reports -1 for any total above INT32_MAX)");
     if (nraw_out) *nraw_out = nraw;
     AVS_TRY(raw_col.reserve((size_t)nslots));
     AVS_TRY(raw_val.reserve((size_t)nslots));
-    // K6 emit (wave-transposed raw triplets), K6b first-occurrence masks -> unique counts
-    DevBuf<int32_t> &ucount = c->scratch.ucount;
-    AVS_TRY(ucount.reserve((size_t)n + 1));
-    if (n) {
+    // K6 emit (wave-transposed raw triplets), then the merge: K6b first-occurrence masks -> unique counts -> row pointers, K7
+    if (n)
         hipLaunchKernelGGL((k_rows<true>), dim3(grid_for(n)), dim3(kBlock), 0, st, P, c->vdof.p, n, E, C, c->x0.p,
                            (const int32_t *)rawptr.p, raw_col.p, raw_val.p, row_count.p, rhs.p, err.p, ids);
-        DevBuf<int32_t> &long_rows = c->scratch.long_rows;
-        AVS_TRY(long_rows.reserve((size_t)n + 1));
-        AVS_HIP(hipMemsetAsync(long_rows.p, 0, sizeof(int32_t), st));
-        hipLaunchKernelGGL(k_unique_rows, dim3(grid_for(n + 1)), dim3(kBlock), 0, st, n, (const int32_t *)rawptr.p, (int32_t *)raw_col.p,
-                           (const int32_t *)row_count.p, ucount.p, long_rows.p);
-        hipLaunchKernelGGL(k_unique_long, dim3(kLongGrid), dim3(kBlock), 0, st, (const int32_t *)rawptr.p, (int32_t *)raw_col.p, (const int32_t *)row_count.p,
-                           ucount.p, (const int32_t *)long_rows.p);
-    }
-    AVS_TRY(exclusive_scan_i32(ucount.p, row_ptr.p, n, scan_tmp.p, scan_tmp.n, st));
-    int32_t nnz = 0;
-    AVS_HIP(hipMemcpyAsync(&nnz, row_ptr.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    int e = 0;
-    AVS_TRY(read_err(err.p, st, &e));
-    tr.mark("emit, unique, scan");
-    AVS_REQUIRE(e == 0, AVS_EINTERNAL, "row assembly hit a reference assert (code %d): stencils and index pyramids disagree", e);
-    AVS_REQUIRE(nnz >= 0, AVS_EINVAL, "non-zero count exceeds int32");
-    if (nnz_out) *nnz_out = nnz;
-    AVS_TRY(col.reserve((size_t)nnz));
-    AVS_TRY(val.reserve((size_t)nnz));
-    // K6b + K7: rank, fold, write the final CSR
-    if (n && c->desc.precision == AVS_PRECISION_F32)
-        hipLaunchKernelGGL(k_merge_rows<true>, dim3(grid_for(n)), dim3(kBlock), 0, st, n, (const int32_t *)rawptr.p, (const int32_t *)raw_col.p,
-                           (const double *)raw_val.p, (const int32_t *)row_count.p, (const int32_t *)row_ptr.p, col.p, val.p);
-    else if (n)
-        hipLaunchKernelGGL(k_merge_rows<false>, dim3(grid_for(n)), dim3(kBlock), 0, st, n, (const int32_t *)rawptr.p, (const int32_t *)raw_col.p,
-                           (const double *)raw_val.p, (const int32_t *)row_count.p, (const int32_t *)row_ptr.p, col.p, val.p);
-    if (n && c->desc.precision == AVS_PRECISION_F32)
-        hipLaunchKernelGGL(k_merge_long<true>, dim3(kLongGrid), dim3(kBlock), 0, st, (const int32_t *)rawptr.p, (const int32_t *)raw_col.p, (const double *)raw_val.p,
-                           (const int32_t *)row_count.p, (const int32_t *)row_ptr.p, col.p, val.p, (const int32_t *)c->scratch.long_rows.p);
-    else if (n)
-        hipLaunchKernelGGL(k_merge_long<false>, dim3(kLongGrid), dim3(kBlock), 0, st, (const int32_t *)rawptr.p, (const int32_t *)raw_col.p, (const double *)raw_val.p,
-                           (const int32_t *)row_count.p, (const int32_t *)row_ptr.p, col.p, val.p, (const int32_t *)c->scratch.long_rows.p);
-    AVS_HIP(hipGetLastError());
+    AVS_TRY(merge_raw(c->scratch, n, c->desc.precision == AVS_PRECISION_F32, row_ptr.p, st, [&](const int32_t &nnz, int32_t *&ocol, double *&oval) -> avs_status {
+        int e = 0;
+        AVS_TRY(read_err(err.p, st, &e)); // (synchronises: nnz is there)
+        tr.mark("emit, unique, scan");
+        AVS_REQUIRE(e == 0, AVS_EINTERNAL, "row assembly hit a reference assert (code %d): stencils and index pyramids disagree", e);
+        AVS_REQUIRE(nnz >= 0, AVS_EINVAL, "non-zero count exceeds int32");
+        if (nnz_out) *nnz_out = nnz;
+        AVS_TRY(col.reserve((size_t)nnz));
+        AVS_TRY(val.reserve((size_t)nnz));
+        ocol = col.p;
+        oval = val.p;
+        return AVS_OK;
+    }));
     AVS_HIP(hipStreamSynchronize(st)); // the caller may read nnz-sized results right away; the raw buffers stay in the context
     tr.mark("merge");
     return AVS_OK;
@@ -1394,4 +1424,104 @@ avs_status build_system(avs_ctx *c)
     return AVS_OK;
 }
 
+#ifdef AVS_PROBES
+// avs_merge_triplets_probe: the caller's row-grouped triplets -> the wave-transposed raw layout k_rows<true> leaves.  fill == 0: the rows' raw
+// counts.  fill == 1: one thread per lane of every wave walks ALL of its slots; those past its row's length are poisoned with a column of that
+// very row (0 where the row is empty or beyond n) and a quiet NaN, so that a kernel reading past R folds the NaN into an entry it writes.
+__global__ __launch_bounds__(kBlock) void k_probe_raw_rows(int64_t n, const int32_t *__restrict__ in_ptr, const int32_t *__restrict__ in_col,
+                                                           const double *__restrict__ in_val, int32_t *__restrict__ row_count,
+                                                           const int32_t *__restrict__ rawptr, int32_t *__restrict__ raw_col,
+                                                           double *__restrict__ raw_val, int fill)
+{
+    const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t nwaves = (n + 63) >> 6;
+    if (!fill) {
+        if (row < n) row_count[row] = in_ptr[row + 1] - in_ptr[row];
+        return;
+    }
+    if (row >= nwaves * 64) return;
+    const int64_t w = row >> 6;
+    const size_t base = (size_t)rawptr[w] + (size_t)(row & 63);
+    const int depth = (rawptr[w + 1] - rawptr[w]) / kRawStride; // slots of every lane of this wave = its longest row
+    const int32_t src = row < n ? in_ptr[row] : 0;
+    const int R = row < n ? in_ptr[row + 1] - src : 0;
+    for (int k = 0; k < depth; ++k) {
+        const size_t at = base + (size_t)k * kRawStride;
+        if (k < R) {
+            raw_col[at] = in_col[src + k];
+            raw_val[at] = in_val[src + k];
+        } else {
+            raw_col[at] = R ? in_col[src + k % R] : 0;
+            raw_val[at] = __longlong_as_double(0x7ff8000000000000ll);
+        }
+    }
+}
+#endif
+
 } // namespace avs
+
+#ifdef AVS_PROBES // test entries (include/avs_probe.h): compiled into libavs_probe.so only
+extern "C" avs_status avs_merge_triplets_probe(int64_t n, const int32_t *raw_ptr, const int32_t *raw_col, const double *raw_val, int32_t f32,
+                                               int32_t *row_ptr, int32_t *col, double *val, int64_t capacity, int64_t *nnz_out,
+                                               avs_triplet_merge_info *info, void *stream)
+{
+    using namespace avs;
+    AVS_REQUIRE(info && info->struct_size >= (int32_t)sizeof(avs_triplet_merge_info), AVS_EINVAL, "info: struct_size not set");
+    info->fast_limit = kFast;
+    info->wave_limit = 64;
+    info->merge_lds = kMergeLds;
+    info->scan_tile = kScanTile;
+    info->long_grid_waves = (int32_t)(kLongGrid * (kBlock / 64));
+    info->long_rows = 0;
+    info->raw_slots = 0;
+    if (n == 0 && !raw_ptr && !row_ptr) return AVS_OK; // the limits alone: nothing touches the device
+    AVS_REQUIRE(n >= 0 && n < (int64_t)INT32_MAX && raw_ptr && row_ptr && nnz_out && capacity >= 0, AVS_EINVAL, "bad argument");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    std::vector<int32_t> hptr((size_t)n + 1);
+    AVS_HIP(hipMemcpyAsync(hptr.data(), raw_ptr, hptr.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AVS_HIP(hipStreamSynchronize(st));
+    AVS_REQUIRE(hptr[0] == 0, AVS_EINVAL, "raw_ptr[0] must be 0");
+    for (int64_t i = 0; i < n; ++i) AVS_REQUIRE(hptr[i + 1] >= hptr[i], AVS_EINVAL, "raw_ptr decreases at row %lld", (long long)i);
+    AVS_REQUIRE(hptr[n] == 0 || (raw_col && raw_val), AVS_EINVAL, "null triplet arrays");
+    avs_ctx::AsmScratch S;
+    AVS_TRY(S.row_count.reserve((size_t)n + 1));
+    AVS_TRY(S.rawptr.reserve((size_t)n + 1));
+    AVS_TRY(S.scan_tmp.reserve(scan_tmp_elems(n)));
+    if (n) hipLaunchKernelGGL(k_probe_raw_rows, dim3(grid_for(n)), dim3(kBlock), 0, st, n, raw_ptr, raw_col, raw_val, S.row_count.p,
+                              (const int32_t *)nullptr, (int32_t *)nullptr, (double *)nullptr, 0);
+    int32_t nraw = 0, nslots = 0;
+    AVS_TRY(raw_layout(S, n, st, &nraw, &nslots));
+    AVS_REQUIRE(nraw == hptr[n] && nslots >= 0, AVS_EINVAL, "raw slots exceed int32");
+    info->raw_slots = nslots;
+    AVS_TRY(S.raw_col.reserve((size_t)nslots));
+    AVS_TRY(S.raw_val.reserve((size_t)nslots));
+    if (n) hipLaunchKernelGGL(k_probe_raw_rows, dim3(grid_for(((n + 63) >> 6) * 64)), dim3(kBlock), 0, st, n, raw_ptr, raw_col, raw_val, S.row_count.p,
+                              (const int32_t *)S.rawptr.p, S.raw_col.p, S.raw_val.p, 1);
+    *nnz_out = 0;
+    AVS_TRY(merge_raw(S, n, f32 != 0, row_ptr, st, [&](const int32_t &nnz, int32_t *&ocol, double *&oval) -> avs_status {
+        AVS_HIP(hipStreamSynchronize(st));
+        AVS_REQUIRE(nnz >= 0, AVS_EINVAL, "non-zero count exceeds int32");
+        *nnz_out = nnz;
+        AVS_REQUIRE((int64_t)nnz <= capacity, AVS_EINVAL, "capacity %lld is below the %d merged entries", (long long)capacity, nnz);
+        AVS_REQUIRE(nnz == 0 || (col && val), AVS_EINVAL, "null output arrays");
+        ocol = col;
+        oval = val;
+        return AVS_OK;
+    }));
+    if (n) AVS_HIP(hipMemcpyAsync(&info->long_rows, S.long_rows.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AVS_HIP(hipStreamSynchronize(st)); // the raw arrays die here
+    return AVS_OK;
+}
+
+extern "C" avs_status avs_exclusive_scan_probe(const int32_t *in, int32_t *out, int64_t n, void *stream)
+{
+    using namespace avs;
+    AVS_REQUIRE(n >= 0 && out && (in || n == 0), AVS_EINVAL, "bad argument");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    DevBuf<int32_t> tmp;
+    AVS_TRY(tmp.reserve(scan_tmp_elems(n)));
+    AVS_TRY(exclusive_scan_i32(in, out, n, tmp.p, tmp.n, st));
+    AVS_HIP(hipStreamSynchronize(st)); // the scratch dies here
+    return AVS_OK;
+}
+#endif // AVS_PROBES

@@ -640,7 +640,9 @@ avs_status spmv_dot_launch(const CsrView &A, const double *x, double *y, double 
 size_t spmv_partial_elems(int64_t n);
 avs_status stream_probe(int mode, const double *a, double *b, int64_t n, double *sink, int grid, hipStream_t st);
 
-// scan (exclusive, int32 -> int32, n+1 outputs: out[n] = total)
+// scan (exclusive, int32 -> int32, n+1 outputs: out[n] = total).  A total above INT32_MAX is reported as out[n] == -1 (however often it would
+// have wrapped), and then ONLY out[n] is defined: callers check it before they read a prefix.  A single tile's sum (2048 inputs) must stay below
+// 2^31.  (tests/test_gpu_scan.py pins both, through avs_exclusive_scan_probe)
 avs_status exclusive_scan_i32(const int32_t *in, int32_t *out, int64_t n, int32_t *block_tmp, size_t block_tmp_elems,
                               hipStream_t stream);
 size_t scan_tmp_elems(int64_t n);

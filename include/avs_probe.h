@@ -124,6 +124,35 @@ avs_status avs_vector_update_probe(int32_t flags, int32_t g, int64_t n, int32_t 
                                    const void *invd, const uint16_t *dcode, const double *spmv_partial, double *vpart, void *scalars,
                                    int32_t scalars_bytes, void *stream);
 
+/* The device setFromTriplets (csrc/avs_assembly.hip: k_wave_slots, k_unique_rows, k_unique_long, k_merge_rows, k_merge_long and the scans
+ * between them) on the CALLER's triplets: n rows, raw_ptr[n + 1] plain row offsets (raw_ptr[0] == 0), raw_col / raw_val the triplets grouped
+ * by row in emission order; all device pointers.  The entry lays them out the way the row sweep emits them -- a wave of 64 rows gets 64 x its
+ * longest row, entry k of lane l at the wave's base + 64 k + l; the slots past a row's length are poisoned with a column of that row (0 for
+ * an empty row) and a quiet NaN -- and then runs the functions avs_assemble runs on that layout: unique, scan, merge, merge-long.  f32 != 0:
+ * duplicates are folded in float steps (AVS_PRECISION_F32; the values must be float values).  Columns are any int32 in [0, INT32_MAX - 1].
+ * Results: row_ptr[n + 1], *nnz, and col / val when nnz <= capacity -- otherwise AVS_EINVAL, *nnz set, col / val untouched.
+ * *info (struct_size set by the caller) gets the limits the kernels were compiled with and what the run reached.  With n == 0 and raw_ptr ==
+ * row_ptr == NULL only the limits are filled in, and nothing touches the device (the CPU tests place their cases from them). */
+typedef struct {
+    int32_t struct_size;
+    int32_t fast_limit;       /* kFast: rows up to here are merged in registers by their own thread */
+    int32_t wave_limit;       /* rows up to here by their whole wave; longer ones go on the list of long rows */
+    int32_t merge_lds;        /* kMergeLds: a wave's 64 merged rows are staged in LDS up to this many entries */
+    int32_t scan_tile;        /* elements per workgroup of exclusive_scan_i32 (its top pass loops beyond 256 tiles) */
+    int32_t long_grid_waves;  /* waves of the grids that walk the list of long rows */
+    int32_t long_rows;        /* rows k_unique_rows listed */
+    int32_t reserved;
+    int64_t raw_slots;        /* slots of the wave-transposed raw arrays */
+} avs_triplet_merge_info;
+avs_status avs_merge_triplets_probe(int64_t n, const int32_t *raw_ptr, const int32_t *raw_col, const double *raw_val, int32_t f32,
+                                    int32_t *row_ptr, int32_t *col, double *val, int64_t capacity, int64_t *nnz,
+                                    avs_triplet_merge_info *info, void *stream);
+/* exclusive_scan_i32 (the scan behind the assembly, the renumbering, the brick build, the pre-pass, the octree cells and the partition
+ * plan) on device arrays: out[i] = in[0] + .. + in[i - 1] for i <= n.  A total above INT32_MAX comes back as out[n] == -1, and then only
+ * out[n] is defined. */
+avs_status avs_exclusive_scan_probe(const int32_t *in, int32_t *out /* n + 1 */, int64_t n, void *stream);
+
+
 #ifdef __cplusplus
 }
 #endif
