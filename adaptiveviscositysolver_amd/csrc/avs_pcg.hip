@@ -846,7 +846,11 @@ static avs_status spmv_dispatch(const CsrView &A, const double *x, double *y, do
     return AVS_OK;
 }
 
-static size_t max_partials(int64_t n);
+static size_t max_partials(int64_t n)
+{
+    size_t a = (size_t)((n + 63) / 64) + 16, b = (size_t)kVecGrid * 4; // up to one partial per wave of rows
+    return 2 * (a > b ? a : b) + 4 * (size_t)kVecGrid + 16;
+}
 
 avs_status spmv_launch(const CsrView &A, const double *x, double *y, int variant, hipStream_t stream)
 {
@@ -906,13 +910,6 @@ avs_status spmv_dot_launch(const CsrView &A, const double *x, double *y, double 
     return spmv_dispatch<true>(A, x, y, partial, nullptr, variant, stream, nullptr);
 }
 size_t spmv_partial_elems(int64_t n) { return max_partials(n); }
-
-static size_t max_partials(int64_t n);
-static size_t max_partials(int64_t n)
-{
-    size_t a = (size_t)((n + 63) / 64) + 16, b = (size_t)kVecGrid * 4; // up to one partial per wave of rows
-    return 2 * (a > b ? a : b) + 4 * (size_t)kVecGrid + 16;
-}
 
 // ---------------------------------------------------------------------------------------------
 // vector kernels
@@ -1637,7 +1634,35 @@ static avs_status reduce_stage(PcgWork *w, int nb, int nred, int op, double tol,
 // ---------------------------------------------------------------------------------------------
 // Host side shared by the solve loops.  Every chunked loop has the same shape:
 //   for (;;) { poll_scalars; sample_spmv; done / max_iters / cancel -> break; enqueue_chunk; }   then finish_info
+// One body per loop, the precisions as template arguments: pcg_solve_phases<T, MIXED> (single GPU and the RCCL standard-CG path; the
+// table in front of it lists what differs between fp64, float and mixed), pcg_solve_single_reduction<T, MIXED>, pcg_solve_direct<T, MIXED>.
 // ---------------------------------------------------------------------------------------------
+// Run-time flags -> template arguments: with_flags(f, a, b, ..) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ..), so that a
+// generic lambda names the instantiation once -- k<C.value, K.value> -- instead of one launch per branch of an if-ladder.  Plain
+// branches, inlined: nothing per launch.  A combination that must not exist is folded inside the lambda (k_sr_update<T, F32 && C.value>).
+template <typename F> static auto with_flags(F &&f) { return f(); }
+template <typename F, typename... Bs> static auto with_flags(F &&f, bool b, Bs... rest)
+{
+    if (b) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+    return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
+// one dictionary of few values: the vector kernels read the rows' 2-B diagonal codes and the table of inverted values instead of one
+// inverse per row (tile-local codes are not indices into one table)
+static bool diag_coded(const CsrView &A) { return A.codes && !A.tab_ptr && A.table_size <= kViLdsTable; }
+
+// doubles of partial sums a launch-per-phase loop needs when its SpMV leaves up to `nb`: the SpMV's in the lower half, the vector
+// kernels' in the upper one (they are written while the SpMV's are still being read)
+static size_t phase_partials(size_t nb) { return 2 * (nb + 16) + 4 * (size_t)kVecGrid + 16; }
+
+// partial sums of the float product (spmv_f32_dispatch; mixed: spmv_mixed_dispatch): one per persistent workgroup of the brick kernel,
+// else one per 256 rows of the streaming kernel
+static size_t f32_spmv_partials(const CsrView &A, bool mixed)
+{
+    if (!(A.brick && A.brick->ntiles > 0 && A.brick->pwords32)) return (size_t)stream_grid(A.n);
+    return (size_t)(mixed ? brick_partial_count_mixed(*A.brick) : brick_partial_count(*A.brick, 4));
+}
+
 static int vec_grid(int64_t n) // grid-stride vector kernels
 {
     const int64_t g = (n + kBlock - 1) / kBlock;
@@ -1964,14 +1989,8 @@ __global__ void k_sr_mixed_step(PcgScalars *sc)
     sc->done = 0;
 }
 
-// k_sr_init / k_sr_update with (CODED) or without the diagonal codes; only the float loops read codes here (KERNEL<T, F32> keeps
+// (k_sr_init / k_sr_update read diagonal codes in the float loops only: they are launched as KERNEL<T, F32 && CODED>, which keeps
 // KERNEL<double, true> from being instantiated)
-#define AVS_SR_LAUNCH(KERNEL, CODED, ...)                                                                       \
-    do {                                                                                                        \
-        if (CODED) hipLaunchKernelGGL((KERNEL<T, F32>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);         \
-        else hipLaunchKernelGGL((KERNEL<T, false>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);             \
-    } while (0)
-
 // The vectors of a single-reduction loop: fp64 -- the workspace's own (x: the caller's), float -- the f_* arrays (x narrowed)
 template <typename T> struct SrVecs {
     T *x, *r, *p, *s, *w, *u;  // w = A u; u [owned | halo]
@@ -2007,23 +2026,16 @@ static avs_status sr_setup(PcgWork *w, const CsrView &A, const double *b, double
     static_assert(F32 || !MIXED, "the mixed-precision loops iterate on float vectors");
     const int64_t n = A.n;
     AVS_HIP(hipMemsetAsync(w->sc.p, 0, 2 * sizeof(PcgScalars), stream));
-    if constexpr (F32) { // as pcg_solve_f32 makes them
+    if constexpr (F32) { // as pcg_solve_phases<float> makes them
         const size_t na = (size_t)n + 8, ne = (size_t)w->n_ext + 8;
         AVS_TRY(w->f_x.alloc(na)); AVS_TRY(w->f_r.alloc(na)); AVS_TRY(w->f_p.alloc(na)); AVS_TRY(w->f_s.alloc(na)); AVS_TRY(w->f_t.alloc(na));
         AVS_TRY(w->f_u.alloc(ne));
         AVS_HIP(hipMemsetAsync(w->f_p.p, 0, na * sizeof(float), stream));
         AVS_HIP(hipMemsetAsync(w->f_s.p, 0, na * sizeof(float), stream));
-        AVS_TRY(prepare_diagonal(w, A, coded, nullptr, stream));
-        *v = {w->f_x.p, w->f_r.p, w->f_p.p, w->f_s.p, w->f_t.p, w->f_u.p, nullptr, nullptr, nullptr};
-        if (coded) {
-            if (!w->f_invtab.p) AVS_TRY(w->f_invtab.alloc((size_t)kViLdsTable + 1));
-            hipLaunchKernelGGL(k_f32_invtab, dim3((A.table_size + kBlock) / kBlock), dim3(kBlock), 0, stream, A, w->f_invtab.p);
-            v->invtab = w->f_invtab.p;
-        } else {
-            AVS_TRY(w->f_invd.alloc(na));
-            hipLaunchKernelGGL(k_f32_inv_diag, dim3(row_grid(n)), dim3(kBlock), 0, stream, A, w->f_invd.p);
-            v->invd = w->f_invd.p;
-        }
+        float *inv = nullptr;
+        const uint16_t *dcode = nullptr;
+        AVS_TRY(prepare_diagonal_f32(w, A, coded, &inv, &dcode, stream));
+        *v = {w->f_x.p, w->f_r.p, w->f_p.p, w->f_s.p, w->f_t.p, w->f_u.p, coded ? nullptr : inv, coded ? inv : nullptr, nullptr};
         w->float_vectors = 1;
     } else {
         AVS_TRY(w->s.alloc((size_t)n));
@@ -2046,12 +2058,14 @@ static avs_status sr_setup(PcgWork *w, const CsrView &A, const double *b, double
     }
     AVS_TRY(product(0));
     const bool kc = F32 && coded; // (the fp64 set-up reads the per-row inverse)
-    if constexpr (MIXED) {
-        if (coded) hipLaunchKernelGGL((k_sr_mixed_residual<true, true>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v->r, v->u, v->invtab, v->dcode, w->partial.p, (const PcgScalars *)w->sc.p);
-        else hipLaunchKernelGGL((k_sr_mixed_residual<false, true>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v->r, v->u, v->invd, v->dcode, w->partial.p, (const PcgScalars *)w->sc.p);
-    } else {
-        AVS_SR_LAUNCH(k_sr_init, kc, n, b, (const T *)v->w, kc ? v->invtab : v->invd, v->dcode, v->r, v->u, w->partial.p);
-    }
+    with_flags([&](auto C) {
+        if constexpr (MIXED)
+            hipLaunchKernelGGL((k_sr_mixed_residual<C.value, true>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v->r, v->u,
+                               kc ? v->invtab : v->invd, v->dcode, w->partial.p, (const PcgScalars *)w->sc.p);
+        else
+            hipLaunchKernelGGL((k_sr_init<T, F32 && C.value>), dim3(g), dim3(kBlock), 0, stream, n, b, (const T *)v->w, kc ? v->invtab : v->invd,
+                               v->dcode, v->r, v->u, w->partial.p);
+    }, kc);
     AVS_TRY(product(1));
     AVS_HIP(hipGetLastError());
     return AVS_OK;
@@ -2094,15 +2108,12 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
                                              int max_iters, hipStream_t stream, avs_solve_info *info, PcgDist *dist)
 {
     constexpr bool F32 = std::is_same<T, float>::value;
+    typedef typename std::conditional<MIXED, double, T>::type SS; // the scalar type of the update kernel
     const int64_t n = A.n;
     const int g = vec_grid(n);
     const int variant = spmv_default_variant(A);
-    const bool coded = F32 && A.codes && !A.tab_ptr && A.table_size <= kViLdsTable; // (the fp64 loop reads the per-row inverse)
-    if (F32) { // the float SpMV's partials: one per persistent workgroup of the brick kernel, else one per 256 rows
-        const bool brick = A.brick && A.brick->ntiles > 0 && A.brick->pwords32;
-        const size_t nb_max = brick ? (size_t)(MIXED ? brick_partial_count_mixed(*A.brick) : brick_partial_count(*A.brick, 4)) : (size_t)stream_grid(n);
-        AVS_TRY(ensure_partials(w, 4 * (size_t)kVecGrid + nb_max + 16));
-    }
+    const bool coded = F32 && diag_coded(A); // (the fp64 loop reads the per-row inverse)
+    if (F32) AVS_TRY(ensure_partials(w, 4 * (size_t)kVecGrid + f32_spmv_partials(A, MIXED) + 16)); // (the float SpMV's behind the vector kernels')
     SrVecs<T> v;
     AVS_TRY((sr_setup_exchange<T, MIXED>(w, A, b, x, tol, coded, dist, &v, stream)));
     double *pvec = w->partial.p;                        // 3 * g vector-kernel partials
@@ -2114,15 +2125,10 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
         // first iteration of a chunk: scalars are final (SR_INIT or the explicit step after the chunk); afterwards the step of
         // the previous iteration rides in k_sr_update, which moves the state to the other slot
         const int step = c > 0 ? 1 : 0;
-        if constexpr (MIXED) {
-            if (coded) hipLaunchKernelGGL((k_sr_update<float, true, double>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const float *)v.w,
-                                          v.invtab, v.dcode, (const PcgScalars *)(sc + cur), sc + (step ? (cur ^ 1) : cur), step, pvec);
-            else hipLaunchKernelGGL((k_sr_update<float, false, double>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const float *)v.w,
-                                    v.invd, v.dcode, (const PcgScalars *)(sc + cur), sc + (step ? (cur ^ 1) : cur), step, pvec);
-        } else {
-            AVS_SR_LAUNCH(k_sr_update, coded, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w, coded ? v.invtab : v.invd, v.dcode,
-                          (const PcgScalars *)(sc + cur), sc + (step ? (cur ^ 1) : cur), step, pvec);
-        }
+        with_flags([&](auto C) {
+            hipLaunchKernelGGL((k_sr_update<T, F32 && C.value, SS>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
+                               coded ? v.invtab : v.invd, v.dcode, (const PcgScalars *)(sc + cur), sc + (step ? (cur ^ 1) : cur), step, pvec);
+        }, coded);
         if (step) cur ^= 1;
         const PcgScalars *now = sc + cur;
         int nb = 0;
@@ -2166,8 +2172,10 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
             AVS_HIP(hipMemcpyAsync(w->p.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
             AVS_TRY(dist_halo_exchange(dist, w->p.p, stream));
             AVS_TRY(spmv_dispatch<false>(A, w->p.p, w->t.p, nullptr, nullptr, variant, stream, nullptr));
-            if (coded) hipLaunchKernelGGL((k_sr_mixed_residual<true, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u, v.invtab, v.dcode, pvec, (const PcgScalars *)now);
-            else hipLaunchKernelGGL((k_sr_mixed_residual<false, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u, v.invd, v.dcode, pvec, (const PcgScalars *)now);
+            with_flags([&](auto C) {
+                hipLaunchKernelGGL((k_sr_mixed_residual<C.value, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u,
+                                   coded ? v.invtab : v.invd, v.dcode, pvec, (const PcgScalars *)now);
+            }, coded);
             AVS_TRY(dist_halo_exchange(dist, v.u, stream));
             int nb = 0;
             AVS_TRY(spmv_mixed_dispatch<true>(A, v.u, v.w, pspmv, now, stream, &nb));
@@ -2212,7 +2220,6 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
     AVS_HIP(hipGetLastError());
     return finish_info(w, A, stream, info, &cs, cancelled, 0, F32);
 }
-#undef AVS_SR_LAUNCH
 
 // ---------------------------------------------------------------------------------------------
 // Direct-transport loop (world >= 1): the single-reduction iteration above with NO RCCL call and no host work inside:
@@ -2518,11 +2525,11 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
     sr_update_geometry((long long)n, &g, &chunk_rows);
     AVS_REQUIRE(g == da.push_grid && chunk_rows == da.push_chunk, AVS_EINTERNAL, "push segments were built for another geometry");
     // one dictionary of few values: the loop's vector kernel reads a 2-B diagonal code
-    const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable;
+    const bool coded = diag_coded(A);
     // brick-structured form of the local rows (float vectors: with its float walk): one partial per persistent workgroup
     const bool brick = A.brick && A.brick->ntiles > 0 && (!F32 || A.brick->pwords32);
     int ntiles = 0, ppt = 1; // the SpMV's partials: ntiles * ppt stage slots
-    if (F32) ntiles = n <= 0 ? 0 : (brick ? (MIXED ? brick_partial_count_mixed(*A.brick) : brick_partial_count(*A.brick, 4)) : stream_grid(n)); // (k_f32_spmv_csr: one per 256 rows)
+    if (F32) ntiles = n <= 0 ? 0 : (int)f32_spmv_partials(A, MIXED);
     else {
         ntiles = brick ? brick_partial_count(*A.brick, 8) : da.n_tiles_int + da.n_tiles_bnd; // (word stream: == ceil(n / kTileRows))
         ppt = brick ? 1 : (A.codes ? kTileRows / 64 : 1); // value-indexed kernel: one partial per wave
@@ -2647,16 +2654,12 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
 
     auto enqueue_iteration = [&](int c, bool timed) -> avs_status {
         // update and push in one launch (3 launches per iteration)
-        if (coded && brick) // (the brick form serves single-dictionary matrices: coded)
-            hipLaunchKernelGGL((k_sr_update_push<true, false, T, SS>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
-                               v.invtab, v.dcode, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch, da.push_ticket);
-        else if (coded)
-            hipLaunchKernelGGL((k_sr_update_push<true, true, T, SS>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
-                               v.invtab, v.dcode, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch, da.push_ticket);
-        else
-            hipLaunchKernelGGL((k_sr_update_push<false, true, T, SS>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s, v.u, (const T *)v.w,
-                               v.invd, (const uint16_t *)nullptr, (const PcgScalars *)sc, pvec, da.dd, (const unsigned long long *)da.epoch,
-                               da.push_ticket);
+        // (KEEP = false only with the brick form, which serves single-dictionary matrices: coded)
+        with_flags([&](auto C, auto B) {
+            hipLaunchKernelGGL((k_sr_update_push<C.value, !(C.value && B.value), T, SS>), dim3(g), dim3(kBlock), 0, stream, n, v.x, v.r, v.p, v.s,
+                               v.u, (const T *)v.w, coded ? v.invtab : v.invd, v.dcode, (const PcgScalars *)sc, pvec, da.dd,
+                               (const unsigned long long *)da.epoch, da.push_ticket);
+        }, coded, brick);
         int op = F32 ? (int)OP_SR_STEP_F32 : (int)OP_SR_STEP;
         if constexpr (MIXED) { // the chunk's last round leaves its step to the reliable update (cs.enqueued: iterations before this chunk)
             const int len = (max_iters - cs.enqueued) < kChunk ? (max_iters - cs.enqueued) : kChunk;
@@ -2669,8 +2672,10 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
             hipLaunchKernelGGL(k_sr_mixed_begin, dim3(1), dim3(1), 0, stream, sc);
             hipLaunchKernelGGL(k_mixed_fold, dim3(g), dim3(kBlock), 0, stream, n, x, v.x, (const PcgScalars *)sc);
             AVS_TRY(product_x());
-            if (coded) hipLaunchKernelGGL((k_sr_mixed_residual<true, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u, v.invtab, v.dcode, pvec, (const PcgScalars *)sc);
-            else hipLaunchKernelGGL((k_sr_mixed_residual<false, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u, v.invd, v.dcode, pvec, (const PcgScalars *)sc);
+            with_flags([&](auto C) {
+                hipLaunchKernelGGL((k_sr_mixed_residual<C.value, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u,
+                                   coded ? v.invtab : v.invd, v.dcode, pvec, (const PcgScalars *)sc);
+            }, coded);
             AVS_TRY(round(v.u, 2, (int)OP_NONE, nullptr, nullptr, true));
             hipLaunchKernelGGL(k_sr_mixed_step, dim3(1), dim3(1), 0, stream, sc);
             AVS_HIP(hipGetLastError());
@@ -2778,7 +2783,7 @@ void pcg_destroy(PcgWork *w)
 // Single GPU, no partition: the single-reduction iteration on the chip when the system qualifies (*ran = false otherwise, nothing
 // touched).  Set-up (r = b - A x, u = M^-1 r, w = A u, the three sums) with the launch-per-phase kernels, the loop resident.
 // T = float (AVS_OPTION_RESIDENT_F32): set-up and loop on float vectors, the solution widened into x at the end; a fault hands the
-// solve to the float launch-per-phase loop (pcg_solve_f32) instead of the fp64 one.
+// solve to the float launch-per-phase loop (pcg_solve_phases<float>) instead of the fp64 one.
 template <typename T>
 static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, int max_iters,
                                             hipStream_t stream, avs_solve_info *info, bool *ran)
@@ -2786,7 +2791,7 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
     constexpr bool F32 = std::is_same<T, float>::value;
     *ran = false;
     const int64_t n = A.n;
-    const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable;
+    const bool coded = diag_coded(A);
     // AVS_OPTION_RESIDENT_LOCAL_TABLES: a matrix without one small dictionary is planned with local value tables; its set-up is the
     // uncoded one (one inverse per row, which the loop then reads)
     const bool local = resident_local_tables_wanted(A);
@@ -2794,11 +2799,7 @@ static avs_status pcg_solve_resident_single(PcgWork *w, const CsrView &A, const 
     if (!w->resident) w->resident = new (std::nothrow) ResidentPlan();
     if (cancel_requested()) return AVS_OK; // (the launch-per-phase loop consumes the request at its first poll: 0 iterations, cancelled = 1)
     if (!w->resident || !resident_prepare(w->resident, A, A.n, nullptr, F32, stream)) return AVS_OK;
-    if (F32) { // the float set-up's SpMV partials (as pcg_solve_single_reduction<float> reserves them)
-        const bool brick = A.brick && A.brick->ntiles > 0 && A.brick->pwords32;
-        const size_t nb_max = brick ? (size_t)brick_partial_count(*A.brick, 4) : (size_t)stream_grid(n);
-        AVS_TRY(ensure_partials(w, 4 * (size_t)kVecGrid + nb_max + 16));
-    }
+    if (F32) AVS_TRY(ensure_partials(w, 4 * (size_t)kVecGrid + f32_spmv_partials(A, false) + 16)); // (as pcg_solve_single_reduction<float>)
     SrVecs<T> v;
     AVS_TRY(sr_setup_exchange(w, A, b, x, tol, !w->resident->local, nullptr, &v, stream));
     // the initial guess is kept: if a bounded wait inside the cooperative launch times out (the grid was not co-resident in time: a GPU
@@ -2873,12 +2874,253 @@ void pcg_resident_plan_info(const PcgWork *w, avs_resident_plan_info *out)
 }
 #endif
 
-// (KEEP is a template parameter of the vector kernels: see stream_load_k)
-#define AVS_VEC_LAUNCH(KERNEL, C, F, ...)                                                                             \
-    do {                                                                                                              \
-        if (keep) hipLaunchKernelGGL((KERNEL<C, F, true>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);            \
-        else hipLaunchKernelGGL((KERNEL<C, F, false>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);                \
-    } while (0)
+// One fused launch for the two vector kernels of the fp64 launch-per-phase loop (k_update_fused): HBM-sized single-GPU systems whose
+// rows fit its registers, a device with one CU per workgroup of its grid.  *on: this solve uses it; then the initial guess is kept, so
+// that a timed-out barrier costs a redo, not a wrong answer.  fuse_beta: the loop's (never with a partition).
+static avs_status fused_vectors_setup(PcgWork *w, const CsrView &A, const double *x, int g, bool fuse_beta, bool keep, hipStream_t stream, bool *on)
+{
+    const int64_t n = A.n;
+    bool fuse_vec = false;
+    if (fuse_beta && cur_opt().fuse_vectors != 0 && !w->fused_off && g == kVecGrid && n <= (int64_t)2 * kFusedPairs * kVecGrid * kBlock &&
+        n < ((int64_t)1 << 28) && (cur_opt().fuse_vectors > 0 || !keep)) {
+        int dev = 0, cus = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        fuse_vec = cus >= kVecGrid / 8;
+    }
+    if (fuse_vec) {
+        static std::atomic<unsigned long long> raised{0}; // the kernel's dynamic LDS limit: once per device
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (dev >= 0 && dev < 64 && !((raised.load() >> dev) & 1ull)) {
+            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
+            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
+            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
+            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
+            raised.fetch_or(1ull << dev);
+        }
+        if (!w->fused_bar.p) {
+            AVS_TRY(w->fused_bar.alloc(2));
+            AVS_HIP(hipMemsetAsync(w->fused_bar.p, 0, 2 * sizeof(unsigned long long), stream));
+        }
+        AVS_TRY(w->x_save.alloc((size_t)n));
+        AVS_HIP(hipMemcpyAsync(w->x_save.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    }
+    w->fused_used = fuse_vec ? 1 : 0;
+    *on = fuse_vec;
+    return AVS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The launch-per-phase loop: single-GPU solves in fp64 (T = double), on float vectors (T = float: AVS_PRECISION_F32, avs_pcg_f32.inl)
+// and in mixed precision (T = float, MIXED: AVS_OPTION_MIXED_PRECISION, avs_pcg_mixed.inl), and the RCCL standard-CG path (dist, fp64
+// only).  One iteration: SpMV with the fused dot, update_r, update_xp; chunks of kChunk iterations, replayed from a captured graph.
+//                 fp64                                   float                                  mixed
+//   vectors       caller's x, w->p/r/t, fp64 diagonal    f_x = narrowed x, f_b = narrowed b,    f_x = the correction, zeroed; f_p/r/t;
+//                                                        f_p/r/t, float diagonal                t64 = w->t; float diagonal
+//   partials      grown only for a brick form            max(stream, brick)                     that, and >= 6 kVecGrid + 64
+//   start         spmv_dispatch, k_init_residual,        float SpMV, k_f32_init_residual,       fp64 SpMV into t64, k_mixed_residual<., true>
+//                 OP_INIT, k_init_p, OP_RHO0             OP_INIT, k_f32_threshold,              into vpart, k_mixed_finish<true>,
+//                                                        k_f32_init_p, OP_RHO0                  k_f32_init_p (no reduction)
+//   vpart         upper half only with fuse_alpha        always the upper half                  as float
+//   unfused       update_r: parity 0                     the iteration's parity                 as float
+//   beta step     fuse_beta option, off with dist        always in update_xp                    as float
+//   graph         !dist; kGraphF64, key x, key.brick =   kGraphF32, key f_x, key.brick = the    kGraphMixed, else as float
+//                 A.brick != nullptr, key.fuse_vec       form has its float walk
+//   behind chunk  --                                     --                                     the reliable update (enqueue_update)
+//   end           fused-barrier redo                     k_f32_widen, float error               done == 3: x := 0
+// ---------------------------------------------------------------------------------------------
+// b, x: the context's fp64 arrays (float: holding float values); x holds the initial guess and receives the solution
+template <typename T, bool MIXED = false>
+static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, int max_iters, hipStream_t stream,
+                                   avs_solve_info *info, PcgDist *dist)
+{
+    constexpr bool F32 = std::is_same<T, float>::value;
+    static_assert(F32 || !MIXED, "the mixed-precision loop iterates on float vectors");
+    static_assert(kChunk % 2 == 0, "the parity of an iteration is taken from its position in the chunk");
+    const int64_t n = A.n;
+    const size_t na = (size_t)n + 8;
+    const int g = vec_grid(n);
+    const int variant = spmv_default_variant(A);
+    const bool coded = diag_coded(A);
+    // the brick form of the matrix (float vectors: with its float walk) -- one partial per wave of every tile: tiles may be smaller than 512 rows
+    const bool brick = A.brick && A.brick->ntiles > 0 && (!F32 || A.brick->pwords32);
+    {
+        size_t need = F32 ? phase_partials((size_t)stream_grid(n)) : 0; // the streaming kernel: one partial per 256 rows
+        if (brick) need = std::max(need, phase_partials((size_t)A.brick->ntiles * 8));
+        if (MIXED) need = std::max(need, 6 * (size_t)kVecGrid + 64); // k_mixed_residual<.., INIT>: three sums of g partials in the upper half
+        AVS_TRY(ensure_partials(w, need));
+    }
+    T *xv = nullptr, *p = nullptr, *r = nullptr, *t = nullptr, *inv = nullptr; // inv: indexed by dcode[i] (coded) or by i
+    const uint16_t *dcode = nullptr;
+    if constexpr (F32) { // (the float set-up of the CU-resident loop allocates all but f_b)
+        w->float_vectors = 1;
+        AVS_TRY(w->f_x.alloc(na)); AVS_TRY(w->f_r.alloc(na)); AVS_TRY(w->f_p.alloc(na)); AVS_TRY(w->f_t.alloc(na));
+        if (!MIXED) AVS_TRY(w->f_b.alloc(na));
+        xv = w->f_x.p, p = w->f_p.p, r = w->f_r.p, t = w->f_t.p;
+    } else {
+        xv = x, p = w->p.p, r = w->r.p, t = w->t.p;
+    }
+    double *const partial = w->partial.p, *const t64 = w->t.p;
+    double *const upper = partial + (w->npartial / 2); // the vector kernels' partial sums while the SpMV's are still being read
+    PcgScalars *sc = w->sc.p;
+    auto product = [&](auto DOT, const T *in, T *out, int *nb) -> avs_status { // out = A in (DOT: + the partials of in.out)
+        if constexpr (MIXED) return spmv_mixed_dispatch<DOT.value>(A, in, out, DOT.value ? partial : nullptr, DOT.value ? sc : nullptr, stream, nb);
+        else return sr_spmv<DOT.value>(A, in, out, DOT.value ? partial : nullptr, DOT.value ? sc : nullptr, variant, stream, nb);
+    };
+
+    AVS_HIP(hipMemsetAsync(sc, 0, sizeof(PcgScalars), stream));
+    if constexpr (MIXED) {
+        AVS_HIP(hipMemsetAsync(xv, 0, na * sizeof(float), stream));
+    } else if constexpr (F32) {
+        hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, b, w->f_b.p);
+        hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, (const double *)x, xv);
+    }
+    if constexpr (F32) {
+        AVS_TRY(prepare_diagonal_f32(w, A, coded, &inv, &dcode, stream));
+    } else {
+        AVS_TRY(prepare_diagonal(w, A, coded, w->invd.p, stream));
+        inv = coded ? w->invtab.p : w->invd.p;
+        dcode = coded ? w->dcode.p : nullptr;
+    }
+    AVS_HIP(hipEventRecord(w->ev0, stream));
+
+    // residual = rhs - mat * x ; p = z = D^-1 r ; |b|^2, |r|^2, rho
+    if constexpr (MIXED) { // in fp64, r rounded to float; rho is the fp64 sum (k_f32_init_p's own r.z partials are not used)
+        AVS_TRY(spmv_dispatch<false>(A, x, t64, nullptr, nullptr, variant, stream, nullptr));
+        with_flags([&](auto C) {
+            hipLaunchKernelGGL((k_mixed_residual<C.value, true>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)t64, r, (const float *)inv,
+                               dcode, upper, (const PcgScalars *)sc);
+        }, coded);
+        hipLaunchKernelGGL(k_mixed_finish<true>, dim3(1), dim3(kRedBlock), 0, stream, (const double *)upper, g, sc, tol);
+    } else if constexpr (F32) {
+        AVS_TRY(product(std::false_type{}, xv, t, nullptr));
+        hipLaunchKernelGGL(k_f32_init_residual, dim3(g), dim3(kBlock), 0, stream, n, w->f_b.p, t, r, partial);
+        AVS_TRY(reduce_stage(w, g, 2, OP_INIT, tol, 0, stream, nullptr));
+        hipLaunchKernelGGL(k_f32_threshold, dim3(1), dim3(1), 0, stream, sc, tol);
+    } else {
+        if (dist) { // x must be visible in its extended form for the product: stage it through p
+            AVS_HIP(hipMemcpyAsync(p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            AVS_TRY(dist_halo_exchange(dist, p, stream));
+        }
+        AVS_TRY(product(std::false_type{}, dist ? p : x, t, nullptr));
+        hipLaunchKernelGGL(k_init_residual, dim3(g), dim3(kBlock), 0, stream, n, b, t, r, partial);
+        AVS_TRY(reduce_stage(w, g, 2, OP_INIT, tol, 0, stream, dist));
+        hipLaunchKernelGGL(k_init_p, dim3(g), dim3(kBlock), 0, stream, n, r, w->invd.p, p, x, partial, sc);
+    }
+    if constexpr (F32)
+        with_flags([&](auto C) { hipLaunchKernelGGL(k_f32_init_p<C.value>, dim3(g), dim3(kBlock), 0, stream, n, r, inv, dcode, p, xv, partial, sc); },
+                   coded);
+    if constexpr (!MIXED) AVS_TRY(reduce_stage(w, g, 1, OP_RHO0, tol, 0, stream, dist));
+    AVS_HIP(hipGetLastError());
+
+    const bool use_graph = !dist && cur_opt().graph != 0;
+    // the beta step rides in update_xp.  fp64: an option, and not with the RCCL transport (the sums are all-reduced between the two kernels)
+    const bool fuse_beta = F32 || (!dist && cur_opt().fuse_beta != 0);
+    // matrix + vectors fit the Infinity Cache (float vectors, half as large, more often): no non-temporal hints in the vector kernels
+    const bool keep = A.keep_cached != 0;
+    bool fuse_vec = false; // fp64: one launch for the two vector kernels (k_update_fused)
+    if constexpr (!F32) AVS_TRY(fused_vectors_setup(w, A, x, g, fuse_beta, keep, stream, &fuse_vec));
+    const long long fused_timeout = (long long)cur_opt().fused_timeout_ms * 100000ll; // wall_clock64: 100 MHz
+    auto enqueue_iteration = [&](int c, bool timed) -> avs_status {
+        int nb = 0;
+        if constexpr (!F32)
+            if (dist) AVS_TRY(dist_halo_exchange(dist, p, stream));
+        if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
+        AVS_TRY(product(std::true_type{}, p, t, &nb)); // tmp = A p ; p.tmp
+        if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
+        // r.z alternates between two slots by the parity of the iteration -- every chunk starts at a multiple of kChunk (even; the
+        // reliable update leaves r.z where position 0 reads it), so c & 1 IS that parity
+        const int parity = fuse_beta ? (c & 1) : 0;
+        const bool fuse_alpha = fuse_beta && nb <= kFuseAlphaMax; // few SpMV partials: every workgroup of update_r folds them itself
+        double *vpart = (F32 || fuse_alpha) ? upper : partial;
+        if constexpr (!F32)
+            if (fuse_vec && fuse_alpha) {
+                with_flags([&](auto C, auto K) {
+                    hipLaunchKernelGGL((k_update_fused<C.value, K.value>), dim3(kVecGrid / 8), dim3(kFusedBlock), kFusedLds + (C.value ? kFusedTabBytes : 0),
+                                       stream, n, x, p, r, t, inv, dcode, sc, vpart, partial, nb, parity, w->fused_bar.p, fused_timeout, A.table_size + 1);
+                }, coded, keep);
+                return AVS_OK;
+            }
+        if (!fuse_alpha) AVS_TRY(reduce_stage(w, nb, 1, parity ? OP_ALPHA_ODD : OP_ALPHA, tol, 1, stream, dist));
+        const int r_parity = (F32 || fuse_alpha) ? parity : 0; // (the unfused fp64 kernel reads what OP_ALPHA left: no parity)
+        with_flags([&](auto C, auto FA, auto K) {
+            const double *spart = FA.value ? partial : nullptr;
+            if constexpr (F32)
+                hipLaunchKernelGGL((k_f32_update_r<C.value, FA.value, K.value, MIXED>), dim3(g), dim3(kBlock), 0, stream, n, r, t, inv, dcode, sc, vpart,
+                                   spart, FA.value ? nb : 0, r_parity);
+            else
+                hipLaunchKernelGGL((k_update_r<C.value, FA.value, K.value>), dim3(g), dim3(kBlock), 0, stream, n, r, t, inv, dcode, sc, vpart, spart,
+                                   FA.value ? nb : 0, r_parity);
+        }, coded, fuse_alpha, keep);
+        if (!fuse_beta) AVS_TRY(reduce_stage(w, g, 2, OP_BETA, tol, 1, stream, dist));
+        with_flags([&](auto C, auto FB, auto K) {
+            if constexpr (F32)
+                hipLaunchKernelGGL((k_f32_update_xp<C.value, K.value, MIXED>), dim3(g), dim3(kBlock), 0, stream, n, xv, p, r, inv, dcode, sc, vpart, g, parity);
+            else
+                hipLaunchKernelGGL((k_update_xp<C.value, FB.value, K.value>), dim3(g), dim3(kBlock), 0, stream, n, xv, p, r, inv, dcode, sc,
+                                   FB.value ? vpart : nullptr, FB.value ? g : 0, parity);
+        }, coded, fuse_beta, keep);
+        return AVS_OK;
+    };
+    // MIXED: the reliable update, behind every chunk (plain launches: the fp64 product is not part of the captured chunk)
+    auto enqueue_update = [&]() -> avs_status {
+        if constexpr (MIXED) {
+            hipLaunchKernelGGL(k_mixed_fold, dim3(g), dim3(kBlock), 0, stream, n, x, xv, (const PcgScalars *)sc);
+            AVS_TRY(spmv_dispatch<false>(A, x, t64, nullptr, nullptr, variant, stream, nullptr));
+            with_flags([&](auto C) {
+                hipLaunchKernelGGL((k_mixed_residual<C.value, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)t64, r, (const float *)inv,
+                                   dcode, upper, (const PcgScalars *)sc);
+            }, coded);
+            hipLaunchKernelGGL(k_mixed_finish<false>, dim3(1), dim3(kRedBlock), 0, stream, (const double *)upper, g, sc, tol);
+            with_flags([&](auto C) {
+                hipLaunchKernelGGL(k_mixed_pstep<C.value>, dim3(g), dim3(kBlock), 0, stream, n, p, (const float *)r, (const float *)inv, dcode,
+                                   (const PcgScalars *)sc);
+            }, coded);
+            AVS_HIP(hipGetLastError());
+            w->reliable_updates++;
+        }
+        return AVS_OK;
+    };
+    GraphKey key = matrix_key(MIXED ? kGraphMixed : F32 ? kGraphF32 : kGraphF64, A, xv, tol);
+    key.val = A.val;
+    key.coded = coded;
+    key.fuse_beta = fuse_beta;
+    key.fuse_vec = fuse_vec;
+    key.brick = F32 ? brick : A.brick != nullptr;
+    ChunkState cs;
+    bool cancelled = false;
+    for (;;) {
+        AVS_TRY(poll_scalars(w, sc, stream));
+        sample_spmv(w, info != nullptr, false, &cs);
+        const PcgScalars &h = *w->host_sc;
+        if (MIXED && h.done == 0 && h.iter < cs.enqueued) cs.enqueued = h.iter; // a chunk the recurrence froze: its remaining iterations did not run
+        if (h.done || cs.enqueued >= max_iters) break;
+        // avs_cancel (single GPU: the host's poll is the only party to agree with).  Known gap: the RCCL standard-CG path (dist)
+        // ignores it -- there is no all-rank vote here, so the request is neither consumed nor acted on
+        if (!dist && cancel_consume()) { cancelled = true; break; }
+        AVS_TRY(enqueue_chunk(w, stream, use_graph ? &key : nullptr, max_iters, info != nullptr, enqueue_iteration, &cs));
+        AVS_TRY(enqueue_update()); // (MIXED) x += xf before the host looks: whatever ends the loop, x holds the last iterate
+    }
+    if constexpr (MIXED) {
+        if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), stream)); // rhsNorm2 == 0 -> x.setZero()
+    } else if constexpr (F32) {
+        hipLaunchKernelGGL(k_f32_widen, dim3(g), dim3(kBlock), 0, stream, n, (const float *)xv, x);
+    } else {
+#ifdef AVS_PROBES
+        if (fuse_vec && getenv("AVS_PCG_FUSED_FAKE_FAULT")) w->host_sc->fault = 4; // test hook of exactly the path below (probe build only)
+#endif
+        if (fuse_vec && w->host_sc->fault == 4) { // the fused launch's grid barrier timed out (GPU shared with other work): the solve again, from
+            w->fused_off = true;                    // the initial guess, with the two vector launches -- on this workspace from now on
+            w->fused_faults++;
+            drop_graph(w);
+            AVS_HIP(hipMemcpyAsync(x, w->x_save.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            return pcg_solve(w, A, b, x, tol, max_iters, stream, info, dist);
+        }
+    }
+    return finish_info(w, A, stream, info, &cs, cancelled, 0, F32 && !MIXED);
+}
+
 avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, int max_iters,
                      hipStream_t stream, avs_solve_info *info, PcgDist *dist)
 {
@@ -2905,148 +3147,16 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
         return pcg_solve_single_reduction<double>(w, A, b, x, tol, max_iters, stream, info, dist);
     // AVS_OPTION_RESIDENT_F32: a float-vector solve (f32_vectors 1 or -1) tries the resident loop on float vectors first
     const bool resident_f32 = !dist && A.resident_f32 && A.f32_vectors != 0;
-    if (!dist && A.f32_vectors > 0 && !resident_f32) return pcg_solve_f32(w, A, b, x, tol, max_iters, stream, info); // AVS_PRECISION_F32: float vectors and scalars
+    if (!dist && A.f32_vectors > 0 && !resident_f32) return pcg_solve_phases<float>(w, A, b, x, tol, max_iters, stream, info, nullptr); // AVS_PRECISION_F32: float vectors and scalars
     if (!dist && resident_wanted(false)) { // systems that fit on the chip (<= ~1 M rows, packed form): one cooperative launch
         bool ran = false;
         const avs_status rs = resident_f32 ? pcg_solve_resident_single<float>(w, A, b, x, tol, max_iters, stream, info, &ran)
                                            : pcg_solve_resident_single<double>(w, A, b, x, tol, max_iters, stream, info, &ran);
         if (ran || rs != AVS_OK) return rs;
     }
-    if (!dist && A.f32_vectors != 0) return pcg_solve_f32(w, A, b, x, tol, max_iters, stream, info); // (auto, or a float resident loop that did not take it / faulted)
-    if (!dist && A.mixed) return pcg_solve_mixed(w, A, b, x, tol, max_iters, stream, info); // AVS_OPTION_MIXED_PRECISION: what the loop below would run
-    if (A.brick && A.brick->ntiles > 0) // one partial per wave of every tile: tiles may be smaller than 512 rows
-        AVS_TRY(ensure_partials(w, 2 * ((size_t)A.brick->ntiles * 8 + 16) + 4 * (size_t)kVecGrid + 16));
-    const int g = vec_grid(n);
-    const int variant = spmv_default_variant(A);
-    double *p = w->p.p, *r = w->r.p, *t = w->t.p, *invd = w->invd.p, *partial = w->partial.p;
-    PcgScalars *sc = w->sc.p;
-
-    AVS_HIP(hipMemsetAsync(sc, 0, sizeof(PcgScalars), stream));
-    // few distinct values: the two vector kernels of the loop read a 2-B diagonal code instead of the 8-B inverse
-    const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable; // (tile-local codes are not indices into one table)
-    AVS_TRY(prepare_diagonal(w, A, coded, invd, stream));
-    AVS_HIP(hipEventRecord(w->ev0, stream));
-
-    // residual = rhs - mat * x
-    if (dist) {
-        // x must be visible in its extended form for the product: stage it through p
-        AVS_HIP(hipMemcpyAsync(p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        AVS_TRY(dist_halo_exchange(dist, p, stream));
-        AVS_TRY(spmv_dispatch<false>(A, p, t, nullptr, nullptr, variant, stream, nullptr));
-    } else {
-        AVS_TRY(spmv_dispatch<false>(A, x, t, nullptr, nullptr, variant, stream, nullptr));
-    }
-    hipLaunchKernelGGL(k_init_residual, dim3(g), dim3(kBlock), 0, stream, n, b, t, r, partial);
-    AVS_TRY(reduce_stage(w, g, 2, OP_INIT, tol, 0, stream, dist));
-    hipLaunchKernelGGL(k_init_p, dim3(g), dim3(kBlock), 0, stream, n, r, invd, p, x, partial, sc);
-    AVS_TRY(reduce_stage(w, g, 1, OP_RHO0, tol, 0, stream, dist));
-    AVS_HIP(hipGetLastError());
-
-    const bool use_graph = !dist && cur_opt().graph != 0;
-    bool fuse_beta = !dist; // multi-GPU (RCCL transport): the sums are all-reduced between the two vector kernels
-    fuse_beta = fuse_beta && cur_opt().fuse_beta != 0;
-    static_assert(kChunk % 2 == 0, "the parity of an iteration is taken from its position in the chunk");
-    const int keep = A.keep_cached ? 1 : 0; // matrix + vectors fit the Infinity Cache: no non-temporal hints in the vector kernels
-    // one fused launch for the two vector kernels (k_update_fused): HBM-sized single-GPU systems whose rows fit its registers, a device
-    // with one CU per workgroup of its grid; the initial guess is kept so that a timed-out barrier costs a redo, not a wrong answer
-    bool fuse_vec = false;
-    if (!dist && fuse_beta && cur_opt().fuse_vectors != 0 && !w->fused_off && g == kVecGrid &&
-        n <= (int64_t)2 * kFusedPairs * kVecGrid * kBlock && n < ((int64_t)1 << 28) && (cur_opt().fuse_vectors > 0 || !keep)) {
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        fuse_vec = cus >= kVecGrid / 8;
-    }
-    if (fuse_vec) {
-        static std::atomic<unsigned long long> raised{0}; // the kernel's dynamic LDS limit: once per device
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev >= 0 && dev < 64 && !((raised.load() >> dev) & 1ull)) {
-            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
-            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
-            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
-            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
-            raised.fetch_or(1ull << dev);
-        }
-        if (!w->fused_bar.p) {
-            AVS_TRY(w->fused_bar.alloc(2));
-            AVS_HIP(hipMemsetAsync(w->fused_bar.p, 0, 2 * sizeof(unsigned long long), stream));
-        }
-        AVS_TRY(w->x_save.alloc((size_t)n));
-        AVS_HIP(hipMemcpyAsync(w->x_save.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    }
-    w->fused_used = fuse_vec ? 1 : 0;
-    const long long fused_timeout = (long long)cur_opt().fused_timeout_ms * 100000ll; // wall_clock64: 100 MHz
-    auto enqueue_iteration = [&](int c, bool timed) -> avs_status {
-        int nb = 0;
-        if (dist) AVS_TRY(dist_halo_exchange(dist, p, stream));
-        if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
-        AVS_TRY(spmv_dispatch<true>(A, p, t, partial, sc, variant, stream, &nb)); // tmp = A p ; p.tmp
-        if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
-        // single GPU: the beta step rides in k_update_xp (4 launches per iteration); r.z alternates between two slots by the
-        // parity of the iteration -- every chunk starts at a multiple of kChunk (even), so c & 1 IS that parity
-        const int parity = fuse_beta ? (c & 1) : 0;
-        const bool fuse_alpha = fuse_beta && nb <= kFuseAlphaMax; // few SpMV partials: every workgroup of k_update_r folds them itself
-        double *vpart = fuse_alpha ? partial + (w->npartial / 2) : partial; // (the SpMV's are still being read)
-        if (fuse_vec && fuse_alpha) {
-            const int fg = kVecGrid / 8;
-#define AVS_FUSED_LAUNCH(C, K, ...) hipLaunchKernelGGL((k_update_fused<C, K>), dim3(fg), dim3(kFusedBlock), kFusedLds + (C ? kFusedTabBytes : 0), stream, __VA_ARGS__, A.table_size + 1)
-            if (coded) {
-                if (keep) AVS_FUSED_LAUNCH(true, true, n, x, p, r, t, w->invtab.p, w->dcode.p, sc, vpart, partial, nb, parity, w->fused_bar.p, fused_timeout);
-                else AVS_FUSED_LAUNCH(true, false, n, x, p, r, t, w->invtab.p, w->dcode.p, sc, vpart, partial, nb, parity, w->fused_bar.p, fused_timeout);
-            } else {
-                if (keep) AVS_FUSED_LAUNCH(false, true, n, x, p, r, t, invd, nullptr, sc, vpart, partial, nb, parity, w->fused_bar.p, fused_timeout);
-                else AVS_FUSED_LAUNCH(false, false, n, x, p, r, t, invd, nullptr, sc, vpart, partial, nb, parity, w->fused_bar.p, fused_timeout);
-            }
-#undef AVS_FUSED_LAUNCH
-            return AVS_OK;
-        }
-        if (fuse_alpha) {
-            if (coded) AVS_VEC_LAUNCH(k_update_r, true, true, n, r, t, w->invtab.p, w->dcode.p, sc, vpart, partial, nb, parity);
-            else AVS_VEC_LAUNCH(k_update_r, false, true, n, r, t, invd, nullptr, sc, vpart, partial, nb, parity);
-        } else {
-            AVS_TRY(reduce_stage(w, nb, 1, parity ? OP_ALPHA_ODD : OP_ALPHA, tol, 1, stream, dist));
-            if (coded) AVS_VEC_LAUNCH(k_update_r, true, false, n, r, t, w->invtab.p, w->dcode.p, sc, partial, nullptr, 0, 0);
-            else AVS_VEC_LAUNCH(k_update_r, false, false, n, r, t, invd, nullptr, sc, partial, nullptr, 0, 0);
-        }
-        if (fuse_beta) {
-            if (coded) AVS_VEC_LAUNCH(k_update_xp, true, true, n, x, p, r, w->invtab.p, w->dcode.p, sc, vpart, g, parity);
-            else AVS_VEC_LAUNCH(k_update_xp, false, true, n, x, p, r, invd, nullptr, sc, vpart, g, parity);
-            return AVS_OK;
-        }
-        AVS_TRY(reduce_stage(w, g, 2, OP_BETA, tol, 1, stream, dist));
-        if (coded) AVS_VEC_LAUNCH(k_update_xp, true, false, n, x, p, r, w->invtab.p, w->dcode.p, sc, nullptr, 0, 0);
-        else AVS_VEC_LAUNCH(k_update_xp, false, false, n, x, p, r, invd, nullptr, sc, nullptr, 0, 0);
-        return AVS_OK;
-    };
-    GraphKey key = matrix_key(kGraphF64, A, x, tol);
-    key.val = A.val;
-    key.coded = coded;
-    key.fuse_beta = fuse_beta;
-    key.fuse_vec = fuse_vec;
-    key.brick = A.brick != nullptr;
-    ChunkState cs;
-    bool cancelled = false;
-    for (;;) {
-        AVS_TRY(poll_scalars(w, sc, stream));
-        sample_spmv(w, info != nullptr, false, &cs);
-        if (w->host_sc->done || cs.enqueued >= max_iters) break;
-        // avs_cancel (single GPU: the host's poll is the only party to agree with).  Known gap: the RCCL standard-CG path (dist)
-        // ignores it -- there is no all-rank vote here, so the request is neither consumed nor acted on
-        if (!dist && cancel_consume()) { cancelled = true; break; }
-        AVS_TRY(enqueue_chunk(w, stream, use_graph ? &key : nullptr, max_iters, info != nullptr, enqueue_iteration, &cs));
-    }
-#ifdef AVS_PROBES
-    if (fuse_vec && getenv("AVS_PCG_FUSED_FAKE_FAULT")) w->host_sc->fault = 4; // test hook of exactly the path below (probe build only)
-#endif
-    if (fuse_vec && w->host_sc->fault == 4) { // the fused launch's grid barrier timed out (GPU shared with other work): the solve again, from
-        w->fused_off = true;                    // the initial guess, with the two vector launches -- on this workspace from now on
-        w->fused_faults++;
-        drop_graph(w);
-        AVS_HIP(hipMemcpyAsync(x, w->x_save.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        return pcg_solve(w, A, b, x, tol, max_iters, stream, info, dist);
-    }
-    return finish_info(w, A, stream, info, &cs, cancelled, 0, false);
+    if (!dist && A.f32_vectors != 0) return pcg_solve_phases<float>(w, A, b, x, tol, max_iters, stream, info, nullptr); // (auto, or a float resident loop that did not take it / faulted)
+    if (!dist && A.mixed) return pcg_solve_phases<float, true>(w, A, b, x, tol, max_iters, stream, info, nullptr); // AVS_OPTION_MIXED_PRECISION: what the fp64 loop would run
+    return pcg_solve_phases<double>(w, A, b, x, tol, max_iters, stream, info, dist);
 }
 
 #ifdef AVS_PROBES
@@ -3088,27 +3198,14 @@ avs_status vector_update_probe(int flags, int g, int64_t n, int nb, int parity, 
 {
     PcgScalars *sc = static_cast<PcgScalars *>(scalars);
     const bool ds = (flags & AVS_VECTOR_PROBE_DS) != 0, f32 = ds || (flags & AVS_VECTOR_PROBE_F32) != 0;
-    const int sel = ((flags & AVS_VECTOR_PROBE_CODED) ? 4 : 0) | ((flags & AVS_VECTOR_PROBE_FUSED) ? 2 : 0) | ((flags & AVS_VECTOR_PROBE_KEEP) ? 1 : 0);
-#define AVS_PROBE_CASE(S, C, F, K)                                                                                                        \
-    case S:                                                                                                                               \
-        if (!f32) vector_probe_f64<C, F, K>(g, n, nb, parity, (double *)x, (double *)p, (double *)r, (const double *)t, (const double *)invd, \
-                                            dcode, spmv_partial, vpart, sc, stream);                                                      \
-        else if (ds) vector_probe_f32<C, F, K, true>(g, n, nb, parity, (float *)x, (float *)p, (float *)r, (const float *)t,              \
-                                                     (const float *)invd, dcode, spmv_partial, vpart, sc, stream);                        \
-        else vector_probe_f32<C, F, K, false>(g, n, nb, parity, (float *)x, (float *)p, (float *)r, (const float *)t, (const float *)invd, \
-                                              dcode, spmv_partial, vpart, sc, stream);                                                    \
-        break;
-    switch (sel) {
-        AVS_PROBE_CASE(0, false, false, false)
-        AVS_PROBE_CASE(1, false, false, true)
-        AVS_PROBE_CASE(2, false, true, false)
-        AVS_PROBE_CASE(3, false, true, true)
-        AVS_PROBE_CASE(4, true, false, false)
-        AVS_PROBE_CASE(5, true, false, true)
-        AVS_PROBE_CASE(6, true, true, false)
-        AVS_PROBE_CASE(7, true, true, true)
-    }
-#undef AVS_PROBE_CASE
+    with_flags([&](auto C, auto F, auto K) {
+        if (!f32) vector_probe_f64<C.value, F.value, K.value>(g, n, nb, parity, (double *)x, (double *)p, (double *)r, (const double *)t,
+                                                                (const double *)invd, dcode, spmv_partial, vpart, sc, stream);
+        else if (ds) vector_probe_f32<C.value, F.value, K.value, true>(g, n, nb, parity, (float *)x, (float *)p, (float *)r, (const float *)t,
+                                                                       (const float *)invd, dcode, spmv_partial, vpart, sc, stream);
+        else vector_probe_f32<C.value, F.value, K.value, false>(g, n, nb, parity, (float *)x, (float *)p, (float *)r, (const float *)t,
+                                                                (const float *)invd, dcode, spmv_partial, vpart, sc, stream);
+    }, (flags & AVS_VECTOR_PROBE_CODED) != 0, (flags & AVS_VECTOR_PROBE_FUSED) != 0, (flags & AVS_VECTOR_PROBE_KEEP) != 0);
     AVS_HIP(hipGetLastError());
     return AVS_OK;
 }

@@ -1,4 +1,5 @@
-// avs_pcg_f32.inl -- the float-vector PCG loop of AVS_PRECISION_F32 contexts (included by avs_pcg.hip, inside namespace avs).
+// avs_pcg_f32.inl -- kernels, SpMV dispatcher and diagonal set-up of the float-vector PCG loops of AVS_PRECISION_F32 contexts (included by
+// avs_pcg.hip, inside namespace avs).  The host loop is pcg_solve_phases<float> (avs_pcg.hip), shared with the fp64 and mixed solves.
 //
 // The reference built with USESINGLEPRECISION (HDK_Utilities.h:25-37: SolveType = fpreal32, Vector = Eigen::VectorXf) hands a
 // SparseMatrix<float> to Eigen::ConjugateGradient (HDK_AdaptiveViscosity.cpp:613-630): matrix values, vectors AND scalars are floats.
@@ -15,8 +16,8 @@
 //     to a few per cent and the solution to the accuracy float CG reaches, not bit for bit.
 // The SpMV is the brick kernel instantiated for float vectors where the matrix has the form (k_spmv_brick<DOT, VC, float>: the lattice
 // in LDS is half as large), else a plain streaming kernel over the CSR arrays (value index or 8-B values).
-// Same control flow as the fp64 launch-per-phase loop (pcg_solve): three launches per iteration with the scalar steps fused into the
-// vector kernels, chunks of kChunk iterations replayed from a captured hipGraph, avs_cancel polled between chunks.
+// Control flow: pcg_solve_phases -- three launches per iteration with the scalar steps fused into the vector kernels, chunks of kChunk
+// iterations replayed from a captured hipGraph, avs_cancel polled between chunks.
 
 typedef float f4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u2_t __attribute__((ext_vector_type(2)));
@@ -364,128 +365,45 @@ static avs_status spmv_f32_dispatch(const CsrView &A, const float *x, float *y, 
     return AVS_OK;
 }
 
-// (KEEP is a template parameter of the vector kernels: see stream_load_k)
-#define AVS_F32_LAUNCH_R(C, F, ...)                                                                                   \
-    do {                                                                                                              \
-        if (keep) hipLaunchKernelGGL((k_f32_update_r<C, F, true>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);   \
-        else hipLaunchKernelGGL((k_f32_update_r<C, F, false>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);       \
-    } while (0)
-#define AVS_F32_LAUNCH_XP(C, ...)                                                                                     \
-    do {                                                                                                              \
-        if (keep) hipLaunchKernelGGL((k_f32_update_xp<C, true>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);     \
-        else hipLaunchKernelGGL((k_f32_update_xp<C, false>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);         \
-    } while (0)
-
-// b, x: the context's fp64 arrays (float values); x holds the initial guess and receives the solution (float values again)
-static avs_status pcg_solve_f32(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, int max_iters, hipStream_t stream,
-                                avs_solve_info *info)
+// The float loops' diagonal (coded: diag_coded(A)): the rows' codes and the table inverted in float, else one float inverse per row.
+// *inv: what the vector kernels index -- by dcode[i] (coded) or by i.
+static avs_status prepare_diagonal_f32(PcgWork *w, const CsrView &A, bool coded, float **inv, const uint16_t **dcode, hipStream_t stream)
 {
-    const int64_t n = A.n;
-    const size_t na = (size_t)n + 8;
-    w->float_vectors = 1;
-    if (!w->f_x.p || !w->f_b.p) { // (the float set-up of the CU-resident loop allocates all but f_b)
-        AVS_TRY(w->f_x.alloc(na)); AVS_TRY(w->f_r.alloc(na)); AVS_TRY(w->f_p.alloc(na)); AVS_TRY(w->f_t.alloc(na)); AVS_TRY(w->f_b.alloc(na));
-    }
-    const bool brick = A.brick && A.brick->ntiles > 0 && A.brick->pwords32;
-    {
-        size_t need = 2 * ((size_t)((n + kBlock - 1) / kBlock) + 16) + 4 * (size_t)kVecGrid + 16; // the streaming kernel: one partial per 256 rows
-        if (brick) { const size_t nb = 2 * ((size_t)A.brick->ntiles * 8 + 16) + 4 * (size_t)kVecGrid + 16; need = nb > need ? nb : need; }
-        AVS_TRY(ensure_partials(w, need));
-    }
-    const int g = vec_grid(n);
-    float *xf = w->f_x.p, *p = w->f_p.p, *r = w->f_r.p, *t = w->f_t.p, *bf = w->f_b.p;
-    double *partial = w->partial.p;
-    PcgScalars *sc = w->sc.p;
-
-    AVS_HIP(hipMemsetAsync(sc, 0, sizeof(PcgScalars), stream));
-    hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, b, bf);
-    hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, (const double *)x, xf);
-    const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable;
-    float *invd = nullptr;
     AVS_TRY(prepare_diagonal(w, A, coded, nullptr, stream));
     if (coded) {
-        if (!w->f_invtab.p) AVS_TRY(w->f_invtab.alloc((size_t)kViLdsTable + 1));
+        AVS_TRY(w->f_invtab.alloc((size_t)kViLdsTable + 1));
         hipLaunchKernelGGL(k_f32_invtab, dim3((A.table_size + kBlock) / kBlock), dim3(kBlock), 0, stream, A, w->f_invtab.p);
-        invd = w->f_invtab.p;
     } else {
-        if (!w->f_invd.p) AVS_TRY(w->f_invd.alloc(na));
-        hipLaunchKernelGGL(k_f32_inv_diag, dim3(row_grid(n)), dim3(kBlock), 0, stream, A, w->f_invd.p);
-        invd = w->f_invd.p;
+        AVS_TRY(w->f_invd.alloc((size_t)A.n + 8));
+        hipLaunchKernelGGL(k_f32_inv_diag, dim3(row_grid(A.n)), dim3(kBlock), 0, stream, A, w->f_invd.p);
     }
-    const uint16_t *dcode = coded ? w->dcode.p : nullptr;
-    AVS_HIP(hipEventRecord(w->ev0, stream));
-
-    AVS_TRY(spmv_f32_dispatch<false>(A, xf, t, nullptr, nullptr, stream, nullptr));
-    hipLaunchKernelGGL(k_f32_init_residual, dim3(g), dim3(kBlock), 0, stream, n, bf, t, r, partial);
-    AVS_TRY(reduce_stage(w, g, 2, OP_INIT, tol, 0, stream, nullptr));
-    hipLaunchKernelGGL(k_f32_threshold, dim3(1), dim3(1), 0, stream, sc, tol);
-    if (coded) hipLaunchKernelGGL(k_f32_init_p<true>, dim3(g), dim3(kBlock), 0, stream, n, r, invd, dcode, p, xf, partial, sc);
-    else hipLaunchKernelGGL(k_f32_init_p<false>, dim3(g), dim3(kBlock), 0, stream, n, r, invd, dcode, p, xf, partial, sc);
-    AVS_TRY(reduce_stage(w, g, 1, OP_RHO0, tol, 0, stream, nullptr));
-    AVS_HIP(hipGetLastError());
-
-    const bool use_graph = cur_opt().graph != 0;
-    // float vectors are half as large: matrix + vectors fit the Infinity Cache more often (same rule, half the vector bytes)
-    const int keep = A.keep_cached ? 1 : 0;
-    auto enqueue_iteration = [&](int c, bool timed) -> avs_status {
-        int nb = 0;
-        if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
-        AVS_TRY(spmv_f32_dispatch<true>(A, p, t, partial, sc, stream, &nb)); // tmp = A p ; p.tmp
-        if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
-        const int parity = c & 1; // (every chunk starts at an even iteration)
-        const bool fuse_alpha = nb <= kFuseAlphaMax;
-        double *vpart = partial + (w->npartial / 2); // (the SpMV's partials are still being read)
-        if (fuse_alpha) {
-            if (coded) AVS_F32_LAUNCH_R(true, true, n, r, t, invd, dcode, sc, vpart, partial, nb, parity);
-            else AVS_F32_LAUNCH_R(false, true, n, r, t, invd, dcode, sc, vpart, partial, nb, parity);
-        } else {
-            AVS_TRY(reduce_stage(w, nb, 1, parity ? OP_ALPHA_ODD : OP_ALPHA, tol, 1, stream, nullptr));
-            if (coded) AVS_F32_LAUNCH_R(true, false, n, r, t, invd, dcode, sc, vpart, (const double *)nullptr, 0, parity);
-            else AVS_F32_LAUNCH_R(false, false, n, r, t, invd, dcode, sc, vpart, (const double *)nullptr, 0, parity);
-        }
-        if (coded) AVS_F32_LAUNCH_XP(true, n, xf, p, r, invd, dcode, sc, vpart, g, parity);
-        else AVS_F32_LAUNCH_XP(false, n, xf, p, r, invd, dcode, sc, vpart, g, parity);
-        return AVS_OK;
-    };
-    GraphKey key = matrix_key(kGraphF32, A, xf, tol);
-    key.val = A.val;
-    key.coded = coded;
-    key.fuse_beta = true;
-    key.brick = brick;
-    ChunkState cs;
-    bool cancelled = false;
-    for (;;) {
-        AVS_TRY(poll_scalars(w, sc, stream));
-        sample_spmv(w, info != nullptr, false, &cs);
-        if (w->host_sc->done || cs.enqueued >= max_iters) break;
-        if (cancel_consume()) { cancelled = true; break; }
-        AVS_TRY(enqueue_chunk(w, stream, use_graph ? &key : nullptr, max_iters, info != nullptr, enqueue_iteration, &cs));
-    }
-    hipLaunchKernelGGL(k_f32_widen, dim3(g), dim3(kBlock), 0, stream, n, (const float *)xf, x);
-    return finish_info(w, A, stream, info, &cs, cancelled, 0, true);
+    *inv = coded ? w->f_invtab.p : w->f_invd.p;
+    *dcode = coded ? w->dcode.p : nullptr;
+    return AVS_OK;
 }
-#undef AVS_F32_LAUNCH_R
-#undef AVS_F32_LAUNCH_XP
 
 #ifdef AVS_PROBES
-// probe / test entry: y = A x through the float forms (x holds float values; y is widened), + the folded partial sums of the fused dot
-avs_status spmv_f32_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st)
+// probe / test entry of a float loop's product: y = A x (x holds float values; y is widened), + the folded partial sums of the fused dot.
+// product(DOT, x, y, partial): the loop's dispatcher; n_cols: the entries of x; brick_partials: what the brick form's fused dot writes
+template <typename P>
+static avs_status spmv_float_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st, int64_t n_cols,
+                                   size_t brick_partials, P &&product)
 {
     const int64_t n = A.n;
     DevBuf<float> xf, yf;
     DevBuf<double> partial;
-    AVS_TRY(xf.alloc((size_t)n + 8));
+    AVS_TRY(xf.alloc((size_t)n_cols + 8));
     AVS_TRY(yf.alloc((size_t)n + 8));
     const int g = stream_grid(n) < kVecGrid ? stream_grid(n) : kVecGrid;
-    hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, st, n, x, xf.p);
+    hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, st, n_cols, x, xf.p);
     if (!fused) {
-        AVS_TRY(spmv_f32_dispatch<false>(A, xf.p, yf.p, nullptr, nullptr, st, nullptr));
+        AVS_TRY(product(std::false_type{}, xf.p, yf.p, nullptr));
     } else {
         size_t np = (size_t)stream_grid(n) + 16;
-        if (A.brick && A.brick->ntiles > 0 && (size_t)brick_partial_count(*A.brick, 4) > np) np = (size_t)brick_partial_count(*A.brick, 4);
+        if (brick_partials > np) np = brick_partials;
         AVS_TRY(partial.alloc(np));
         AVS_HIP(hipMemsetAsync(partial.p, 0, np * sizeof(double), st));
-        AVS_TRY(spmv_f32_dispatch<true>(A, xf.p, yf.p, partial.p, nullptr, st, nullptr));
+        AVS_TRY(product(std::true_type{}, xf.p, yf.p, partial.p));
         if (dot_out) {
             std::vector<double> h(np);
             AVS_HIP(hipMemcpyAsync(h.data(), partial.p, np * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -499,5 +417,12 @@ avs_status spmv_f32_probe(const CsrView &A, const double *x, double *y, bool fus
     AVS_HIP(hipGetLastError());
     AVS_HIP(hipStreamSynchronize(st));
     return AVS_OK;
+}
+avs_status spmv_f32_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st)
+{
+    return spmv_float_probe(A, x, y, fused, dot_out, st, A.n, A.brick ? (size_t)brick_partial_count(*A.brick, 4) : 0,
+                            [&](auto DOT, const float *xf, float *yf, double *partial) {
+                                return spmv_f32_dispatch<DOT.value>(A, xf, yf, partial, nullptr, st, nullptr);
+                            });
 }
 #endif // AVS_PROBES

@@ -1,8 +1,9 @@
-// avs_pcg_mixed.inl -- the mixed-precision PCG loop of AVS_PRECISION_F64 contexts (AVS_OPTION_MIXED_PRECISION; included by avs_pcg.hip
-// behind avs_pcg_f32.inl, inside namespace avs).
+// avs_pcg_mixed.inl -- kernels and SpMV dispatcher of the mixed-precision PCG loop of AVS_PRECISION_F64 contexts
+// (AVS_OPTION_MIXED_PRECISION; included by avs_pcg.hip behind avs_pcg_f32.inl, inside namespace avs).  The host loop is
+// pcg_solve_phases<float, true> (avs_pcg.hip), shared with the fp64 and float solves; this is the scheme it runs.
 //
-// The fp64 launch-per-phase loop is bound by the bytes of its vectors.  This loop iterates on 4-byte vectors and keeps the answer and
-// the stopping test in fp64 ("reliable updates" / residual replacement):
+// The fp64 launch-per-phase loop is bound by the bytes of its vectors.  The mixed loop iterates on 4-byte vectors and keeps the answer
+// and the stopping test in fp64 ("reliable updates" / residual replacement):
 //   fp64:  the solution x and the right-hand side b (the context's arrays), one scratch vector t64, the matrix values, every row sum of
 //          A p (rounded to float once, when it is stored), every dot product across threads / workgroups / launches, alpha, beta, rho,
 //          the threshold tol^2 |b|^2 and the residual norm the solve reports;
@@ -154,158 +155,14 @@ __global__ __launch_bounds__(kBlock) void k_mixed_pstep(int64_t n, float *__rest
         p[i] = (CODED ? invd[dcode[i]] : invd[i]) * r[i] + beta * p[i];
 }
 
-// (KEEP is a template parameter of the vector kernels: see stream_load_k)
-#define AVS_MIXED_LAUNCH_R(C, F, ...)                                                                                       \
-    do {                                                                                                                    \
-        if (keep) hipLaunchKernelGGL((k_f32_update_r<C, F, true, true>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);   \
-        else hipLaunchKernelGGL((k_f32_update_r<C, F, false, true>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);       \
-    } while (0)
-#define AVS_MIXED_LAUNCH_XP(C, ...)                                                                                         \
-    do {                                                                                                                    \
-        if (keep) hipLaunchKernelGGL((k_f32_update_xp<C, true, true>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);     \
-        else hipLaunchKernelGGL((k_f32_update_xp<C, false, true>), dim3(g), dim3(kBlock), 0, stream, __VA_ARGS__);         \
-    } while (0)
-
-// b, x: the context's fp64 arrays; x holds the initial guess and receives the solution
-static avs_status pcg_solve_mixed(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, int max_iters, hipStream_t stream,
-                                  avs_solve_info *info)
-{
-    const int64_t n = A.n;
-    const size_t na = (size_t)n + 8;
-    w->float_vectors = 1;
-    if (!w->f_x.p) { AVS_TRY(w->f_x.alloc(na)); AVS_TRY(w->f_r.alloc(na)); AVS_TRY(w->f_p.alloc(na)); AVS_TRY(w->f_t.alloc(na)); }
-    const bool brick = A.brick && A.brick->ntiles > 0 && A.brick->pwords32;
-    {
-        size_t need = 2 * ((size_t)((n + kBlock - 1) / kBlock) + 16) + 4 * (size_t)kVecGrid + 16; // the streaming kernel: one partial per 256 rows
-        if (brick) { const size_t nb = 2 * ((size_t)A.brick->ntiles * 8 + 16) + 4 * (size_t)kVecGrid + 16; need = nb > need ? nb : need; }
-        const size_t upd = 6 * (size_t)kVecGrid + 64; // k_mixed_residual<.., INIT>: three sums of g partials in the upper half
-        AVS_TRY(ensure_partials(w, need > upd ? need : upd));
-    }
-    const int g = vec_grid(n);
-    float *xf = w->f_x.p, *p = w->f_p.p, *r = w->f_r.p, *t = w->f_t.p;
-    double *t64 = w->t.p, *partial = w->partial.p;
-    double *vpart = partial + (w->npartial / 2); // the vector kernels' partial sums (the SpMV's are still being read)
-    PcgScalars *sc = w->sc.p;
-    const int variant = spmv_default_variant(A);
-
-    AVS_HIP(hipMemsetAsync(sc, 0, sizeof(PcgScalars), stream));
-    AVS_HIP(hipMemsetAsync(xf, 0, na * sizeof(float), stream));
-    const bool coded = A.codes && !A.tab_ptr && A.table_size <= kViLdsTable;
-    float *invd = nullptr;
-    AVS_TRY(prepare_diagonal(w, A, coded, nullptr, stream));
-    if (coded) {
-        if (!w->f_invtab.p) AVS_TRY(w->f_invtab.alloc((size_t)kViLdsTable + 1));
-        hipLaunchKernelGGL(k_f32_invtab, dim3((A.table_size + kBlock) / kBlock), dim3(kBlock), 0, stream, A, w->f_invtab.p);
-        invd = w->f_invtab.p;
-    } else {
-        if (!w->f_invd.p) AVS_TRY(w->f_invd.alloc(na));
-        hipLaunchKernelGGL(k_f32_inv_diag, dim3(row_grid(n)), dim3(kBlock), 0, stream, A, w->f_invd.p);
-        invd = w->f_invd.p;
-    }
-    const uint16_t *dcode = coded ? w->dcode.p : nullptr;
-    AVS_HIP(hipEventRecord(w->ev0, stream));
-
-    // r64 = b - A x in fp64; |b|^2, |r64|^2, rho; r = (float) r64; p = z = D^-1 r
-    AVS_TRY(spmv_dispatch<false>(A, x, t64, nullptr, nullptr, variant, stream, nullptr));
-    if (coded) hipLaunchKernelGGL((k_mixed_residual<true, true>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)t64, r, (const float *)invd, dcode, vpart, (const PcgScalars *)sc);
-    else hipLaunchKernelGGL((k_mixed_residual<false, true>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)t64, r, (const float *)invd, dcode, vpart, (const PcgScalars *)sc);
-    hipLaunchKernelGGL(k_mixed_finish<true>, dim3(1), dim3(kRedBlock), 0, stream, (const double *)vpart, g, sc, tol);
-    // (k_f32_init_p's own r.z partials are not used: rho is the fp64 sum above)
-    if (coded) hipLaunchKernelGGL(k_f32_init_p<true>, dim3(g), dim3(kBlock), 0, stream, n, r, invd, dcode, p, xf, partial, sc);
-    else hipLaunchKernelGGL(k_f32_init_p<false>, dim3(g), dim3(kBlock), 0, stream, n, r, invd, dcode, p, xf, partial, sc);
-    AVS_HIP(hipGetLastError());
-
-    const bool use_graph = cur_opt().graph != 0;
-    // the footprint is the float loop's (plus x, b, t64 touched once per kChunk iterations): the float loop's rule
-    const int keep = A.keep_cached ? 1 : 0;
-    auto enqueue_iteration = [&](int c, bool timed) -> avs_status {
-        int nb = 0;
-        if (timed) AVS_HIP(hipEventRecord(w->evA[c], stream));
-        AVS_TRY(spmv_mixed_dispatch<true>(A, p, t, partial, sc, stream, &nb)); // t = A p ; p.t
-        if (timed) AVS_HIP(hipEventRecord(w->evB[c], stream));
-        const int parity = c & 1; // (the position in the chunk: the update leaves r.z where position 0 reads it)
-        const bool fuse_alpha = nb <= kFuseAlphaMax;
-        if (fuse_alpha) {
-            if (coded) AVS_MIXED_LAUNCH_R(true, true, n, r, t, invd, dcode, sc, vpart, partial, nb, parity);
-            else AVS_MIXED_LAUNCH_R(false, true, n, r, t, invd, dcode, sc, vpart, partial, nb, parity);
-        } else {
-            AVS_TRY(reduce_stage(w, nb, 1, parity ? OP_ALPHA_ODD : OP_ALPHA, tol, 1, stream, nullptr));
-            if (coded) AVS_MIXED_LAUNCH_R(true, false, n, r, t, invd, dcode, sc, vpart, (const double *)nullptr, 0, parity);
-            else AVS_MIXED_LAUNCH_R(false, false, n, r, t, invd, dcode, sc, vpart, (const double *)nullptr, 0, parity);
-        }
-        if (coded) AVS_MIXED_LAUNCH_XP(true, n, xf, p, r, invd, dcode, sc, vpart, g, parity);
-        else AVS_MIXED_LAUNCH_XP(false, n, xf, p, r, invd, dcode, sc, vpart, g, parity);
-        return AVS_OK;
-    };
-    // the reliable update, behind every chunk (plain launches: the fp64 product is not part of the captured chunk)
-    auto enqueue_update = [&]() -> avs_status {
-        hipLaunchKernelGGL(k_mixed_fold, dim3(g), dim3(kBlock), 0, stream, n, x, xf, (const PcgScalars *)sc);
-        AVS_TRY(spmv_dispatch<false>(A, x, t64, nullptr, nullptr, variant, stream, nullptr));
-        if (coded) hipLaunchKernelGGL((k_mixed_residual<true, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)t64, r, (const float *)invd, dcode, vpart, (const PcgScalars *)sc);
-        else hipLaunchKernelGGL((k_mixed_residual<false, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)t64, r, (const float *)invd, dcode, vpart, (const PcgScalars *)sc);
-        hipLaunchKernelGGL(k_mixed_finish<false>, dim3(1), dim3(kRedBlock), 0, stream, (const double *)vpart, g, sc, tol);
-        if (coded) hipLaunchKernelGGL(k_mixed_pstep<true>, dim3(g), dim3(kBlock), 0, stream, n, p, (const float *)r, (const float *)invd, dcode, (const PcgScalars *)sc);
-        else hipLaunchKernelGGL(k_mixed_pstep<false>, dim3(g), dim3(kBlock), 0, stream, n, p, (const float *)r, (const float *)invd, dcode, (const PcgScalars *)sc);
-        AVS_HIP(hipGetLastError());
-        w->reliable_updates++;
-        return AVS_OK;
-    };
-    GraphKey key = matrix_key(kGraphMixed, A, xf, tol);
-    key.val = A.val;
-    key.coded = coded;
-    key.fuse_beta = true;
-    key.brick = brick;
-    ChunkState cs;
-    bool cancelled = false;
-    for (;;) {
-        AVS_TRY(poll_scalars(w, sc, stream));
-        sample_spmv(w, info != nullptr, false, &cs);
-        const PcgScalars &h = *w->host_sc;
-        if (h.done == 0 && h.iter < cs.enqueued) cs.enqueued = h.iter; // a chunk the recurrence froze: its remaining iterations did not run
-        if (h.done || cs.enqueued >= max_iters) break;
-        if (cancel_consume()) { cancelled = true; break; }
-        AVS_TRY(enqueue_chunk(w, stream, use_graph ? &key : nullptr, max_iters, info != nullptr, enqueue_iteration, &cs));
-        AVS_TRY(enqueue_update()); // x += xf before the host looks: whatever ends the loop, x holds the last iterate
-    }
-    if (w->host_sc->done == 3) AVS_HIP(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), stream)); // rhsNorm2 == 0 -> x.setZero()
-    return finish_info(w, A, stream, info, &cs, cancelled, 0, false);
-}
-#undef AVS_MIXED_LAUNCH_R
-#undef AVS_MIXED_LAUNCH_XP
-
 #ifdef AVS_PROBES
-// probe / test entry: y = A x through the mixed-precision loop's product (x holds float values; y is widened), + the folded partial sums
+// probe / test entry: y = A x through the mixed-precision loop's product (spmv_float_probe)
 // n_cols (0: A.n): the entries of x -- [owned | halo] for the local rows of a partitioned plan
 avs_status spmv_mixed_probe(const CsrView &A, const double *x, double *y, bool fused, double *dot_out, hipStream_t st, int64_t n_cols)
 {
-    const int64_t n = A.n;
-    if (n_cols < n) n_cols = n;
-    DevBuf<float> xf, yf;
-    DevBuf<double> partial;
-    AVS_TRY(xf.alloc((size_t)n_cols + 8));
-    AVS_TRY(yf.alloc((size_t)n + 8));
-    const int g = stream_grid(n) < kVecGrid ? stream_grid(n) : kVecGrid;
-    hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, st, n_cols, x, xf.p);
-    if (!fused) {
-        AVS_TRY(spmv_mixed_dispatch<false>(A, xf.p, yf.p, nullptr, nullptr, st, nullptr));
-    } else {
-        size_t np = (size_t)stream_grid(n) + 16;
-        if (A.brick && A.brick->ntiles > 0 && (size_t)brick_partial_count_mixed(*A.brick) > np) np = (size_t)brick_partial_count_mixed(*A.brick);
-        AVS_TRY(partial.alloc(np));
-        AVS_HIP(hipMemsetAsync(partial.p, 0, np * sizeof(double), st));
-        AVS_TRY(spmv_mixed_dispatch<true>(A, xf.p, yf.p, partial.p, nullptr, st, nullptr));
-        if (dot_out) {
-            std::vector<double> h(np);
-            AVS_HIP(hipMemcpyAsync(h.data(), partial.p, np * sizeof(double), hipMemcpyDeviceToHost, st));
-            AVS_HIP(hipStreamSynchronize(st));
-            double s = 0.;
-            for (double v : h) s += v;
-            *dot_out = s;
-        }
-    }
-    hipLaunchKernelGGL(k_f32_widen, dim3(g), dim3(kBlock), 0, st, n, (const float *)yf.p, y);
-    AVS_HIP(hipGetLastError());
-    AVS_HIP(hipStreamSynchronize(st));
-    return AVS_OK;
+    return spmv_float_probe(A, x, y, fused, dot_out, st, n_cols < A.n ? A.n : n_cols, A.brick ? (size_t)brick_partial_count_mixed(*A.brick) : 0,
+                            [&](auto DOT, const float *xf, float *yf, double *partial) {
+                                return spmv_mixed_dispatch<DOT.value>(A, xf, yf, partial, nullptr, st, nullptr);
+                            });
 }
 #endif // AVS_PROBES

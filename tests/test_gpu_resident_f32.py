@@ -198,7 +198,7 @@ def test_option_switch_on_one_context(built_lib):
 
 def test_fault_is_redone_by_the_float_launch_per_phase_loop(monkeypatch, built_lib):
     """AVS_CG_RESIDENT_FAKE_FAULT (probe build): the float resident launch counts as faulted, the same call restores the initial guess and
-    solves with pcg_solve_f32 -- exactly what F32_VECTORS = 1 without the option computes"""
+    solves with pcg_solve_phases<float> -- exactly what F32_VECTORS = 1 without the option computes"""
     sc = scenes.fat_beam(64, 3)
     s, _ = _context(sc, probe=True, resident_f32=1)
     good = s.solve(TOL, 5000)          # the float plan is built and its kernel launched on this very context ...
