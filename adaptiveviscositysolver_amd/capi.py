@@ -65,7 +65,7 @@ ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_v
 # include/avs_probe.h: exported by libavs_probe.so only (the -DAVS_PROBES build of the same sources)
 PROBE_SYMBOLS = ["avs_spmv_csr", "avs_bench_spmv", "avs_spmv_sell", "avs_bench_stream", "avs_brick_spmv_probe", "avs_spmv_solver_form",
                  "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe", "avs_pcg_csr_plan",
-                 "avs_merge_triplets_probe", "avs_exclusive_scan_probe"]
+                 "avs_merge_triplets_probe", "avs_exclusive_scan_probe", "avs_resident_plan_host"]
 VECTOR_PROBE_F32, VECTOR_PROBE_DS, VECTOR_PROBE_CODED, VECTOR_PROBE_KEEP, VECTOR_PROBE_FUSED = 1, 2, 4, 8, 16   # avs_vector_update_probe flags
 SPMV_FORM_FUSED_DOT, SPMV_FORM_F32, SPMV_FORM_NO_CACHE_HINT = 1, 2, 4   # avs_spmv_csr_form flags (include/avs_probe.h)
 _VOID_RETURN = ("avs_last_error", "avs_version", "avs_destroy", "avs_plan_destroy", "avs_local_group_destroy",
@@ -146,6 +146,17 @@ class ResidentPlanInfo(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(ResidentPlanInfo)
+
+
+class ResidentHostPlanInfo(C.Structure):
+    """avs_resident_host_plan_info (include/avs_probe.h): what the host-only planner of the CU-resident loop made of a row-pointer array"""
+    _fields_ = [("struct_size", C.c_int32), ("refused", C.c_int32), ("lanes", C.c_int64), ("long_row_lanes", C.c_int32),
+                ("longest_tail", C.c_int32), ("max_lane_streamed_rows", C.c_int32), ("max_rows_per_workgroup", C.c_int32),
+                ("streamed_rows", C.c_int64), ("streamed_words", C.c_int64), ("stream_T", C.c_double), ("why", C.c_char * 128)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(ResidentHostPlanInfo)
 
 
 class TripletMergeInfo(C.Structure):
@@ -238,6 +249,7 @@ def load(probe=False):
         L.avs_pcg_csr_plan.argtypes = L.avs_pcg_csr.argtypes + [C.POINTER(ResidentPlanInfo)]
         L.avs_merge_triplets_probe.argtypes = [i64, vp, vp, vp, i32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(TripletMergeInfo), vp]
         L.avs_exclusive_scan_probe.argtypes = [vp, vp, i64, vp]
+        L.avs_resident_plan_host.argtypes = [i64, vp, i32, i32, f64, i32, f64, vp, vp, vp, vp, vp, C.POINTER(ResidentHostPlanInfo)]
     L.avs_prepass_create.argtypes = [C.POINTER(PrepassDesc), C.POINTER(vp)]
     L.avs_prepass_destroy.argtypes = [vp]
     L.avs_prepass_destroy.restype = None
@@ -295,6 +307,22 @@ def load(probe=False):
     else:
         _lib = L
     return L
+
+
+def resident_plan_host(row_ptr, workgroups, max_quads=15, lane_fill=0.90, no_stream=False, stream_cost=1.5):
+    """avs_resident_plan_host (libavs_probe.so, no GPU): the CU-resident loop's lanes and first workgroup split for host row pointers.
+    Returns (info, lanes) -- lanes: dict of row0, meta, stream_quads (info.lanes entries each), wl, wr (workgroups + 1); None when refused."""
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int32)
+    n = len(rp) - 1
+    row0, meta, quads = np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.int32)
+    wl, wr = np.zeros(workgroups + 1, np.int32), np.zeros(workgroups + 1, np.int32)
+    info = ResidentHostPlanInfo()
+    check(load_probe().avs_resident_plan_host(n, rp.ctypes.data, workgroups, max_quads, lane_fill, int(no_stream), stream_cost, row0.ctypes.data,
+                                              meta.ctypes.data, quads.ctypes.data, wl.ctypes.data, wr.ctypes.data, C.byref(info)))
+    if info.refused:
+        return info, None
+    L = int(info.lanes)
+    return info, {"row0": row0[:L], "meta": meta[:L], "stream_quads": quads[:L], "wl": wl, "wr": wr}
 
 
 def check(status):

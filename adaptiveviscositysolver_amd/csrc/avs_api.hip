@@ -8,6 +8,7 @@
 #include <new>
 
 #include "avs_internal.hpp"
+#include "avs_resident_plan.hpp"
 
 namespace avs {
 
@@ -942,6 +943,49 @@ avs_status avs_pcg_csr_plan(int64_t n, const int32_t *row_ptr, const int32_t *co
 {
     AVS_REQUIRE(plan && plan->struct_size >= 8, AVS_EINVAL, "plan: struct_size not set");
     return pcg_csr_entry(n, row_ptr, col, val, b, x, tol, max_iters, where, device, stream, info, plan);
+}
+
+avs_status avs_resident_plan_host(int64_t n, const int32_t *row_ptr, int32_t workgroups, int32_t max_quads, double lane_fill, int32_t no_stream,
+                                  double stream_cost, int32_t *lane_row0, uint32_t *lane_meta, int32_t *lane_stream_quads, int32_t *wg_lane0,
+                                  int32_t *wg_row0, avs_resident_host_plan_info *info)
+{
+    AVS_REQUIRE(n >= 1 && n < (1ll << 31) && row_ptr && lane_row0 && lane_meta && lane_stream_quads && wg_lane0 && wg_row0, AVS_EINVAL, "null argument");
+    AVS_REQUIRE(workgroups >= 1 && workgroups <= 1024 && max_quads >= 1 && max_quads <= kResQuads, AVS_EINVAL, "workgroups / max_quads out of range");
+    AVS_REQUIRE(info && info->struct_size == (int32_t)sizeof(*info), AVS_EINVAL, "info: struct_size not set");
+    avs_resident_host_plan_info o{};
+    o.struct_size = (int32_t)sizeof(o);
+    ResidentLanes lanes;
+    int64_t q_total = 0;
+    const char *why = lanes_in_registers(row_ptr, n, workgroups, max_quads, &lanes, &q_total);
+    if (!why) why = lanes_with_streams(row_ptr, n, workgroups, max_quads, lane_fill, no_stream != 0, q_total, &lanes, &o.stream_T);
+    if (why) {
+        o.refused = 1;
+        snprintf(o.why, sizeof(o.why), "%s", why);
+        *info = o;
+        return AVS_OK;
+    }
+    const size_t L = (size_t)lanes.size(), G = (size_t)workgroups;
+    ResidentSplit split;
+    split.lane_w.assign(L, 1.0);
+    split.lane_extra.assign(L, 0.);
+    split.cum.assign(L + 1, 0.);
+    split.wl.resize(G + 1);
+    split.wr.resize(G + 1);
+    if (!split_by_cost(lanes, workgroups, stream_cost, &split)) split_equal_lanes((int64_t)L, workgroups, &split.wl);
+    o.max_rows_per_workgroup = workgroup_rows(split.wl, lanes, n, &split.wr);
+    o.lanes = lanes.size();
+    o.long_row_lanes = lanes.long_lanes;
+    o.longest_tail = lanes.longest_tail;
+    o.max_lane_streamed_rows = lanes.max_lane_streamed;
+    o.streamed_rows = lanes.streamed_rows;
+    o.streamed_words = lanes.streamed_words;
+    memcpy(lane_row0, lanes.row0.data(), L * sizeof(int32_t));
+    memcpy(lane_meta, lanes.meta.data(), L * sizeof(uint32_t));
+    memcpy(lane_stream_quads, lanes.stream_quads.data(), L * sizeof(int32_t));
+    memcpy(wg_lane0, split.wl.data(), (G + 1) * sizeof(int32_t));
+    memcpy(wg_row0, split.wr.data(), (G + 1) * sizeof(int32_t));
+    *info = o;
+    return AVS_OK;
 }
 
 avs_status avs_spmv_csr(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val, const double *x,

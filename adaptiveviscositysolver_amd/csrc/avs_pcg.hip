@@ -21,6 +21,7 @@
 // the iteration count and the solution are exactly those of the sequential algorithm.
 #include "avs_internal.hpp"
 #include "avs_halo.hpp"
+#include "avs_resident_plan.hpp"
 
 namespace avs {
 

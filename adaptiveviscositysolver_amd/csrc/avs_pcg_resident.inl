@@ -31,11 +31,7 @@
 
 #include <time.h>
 
-static constexpr int kResThreads = 1024;
-static constexpr int kResQuads = 15;     // 128-bit register quads of matrix words per lane (60 VGPRs)
-static constexpr int kResQuadWords = 5;  // 25-bit words per quad; a row takes ceil(len / 5) consecutive quads of ONE lane
-static constexpr int kResRowsMax = 6;    // rows per lane
-static constexpr int kResWordBits = 25;  // value code | workgroup-local column
+// (kResThreads, kResQuads, kResQuadWords, kResRowsMax, kResWordBits and the lane_meta layout: avs_resident_plan.hpp, shared with the planner)
 #ifndef AVS_RES_UPD
 #define AVS_RES_UPD 4
 #endif
@@ -405,8 +401,8 @@ __global__ __launch_bounds__(kResThreads) void k_resident_stream_layout(const in
     int j = 0;
     if (lane < wg_lane0[b + 1]) {
         const uint32_t meta = lane_meta[lane];
-        const int m = (int)((meta >> 3) & 127u);
-        const int r = lane_row0[lane] + (int)(meta & 7u);
+        const int m = (int)((meta >> kLaneStreamedShift) & kLaneStreamedMask);
+        const int r = lane_row0[lane] + (int)(meta & kLaneRowsMask);
         for (int rr = r; rr < r + m; ++rr) {
             const int ks = row_ptr[rr], ke = row_ptr[rr + 1];
             for (int k = ks; k < ke && j < wcnt; k += kResQuadWords, ++j) {
@@ -472,8 +468,8 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
     if (have) {
         row0_c = a.lane_row0[lane];
         const uint32_t meta = a.lane_meta[lane];
-        nrows = (int)(meta & 7u);
-        tail = (int)(meta >> 10);
+        nrows = (int)(meta & kLaneRowsMask);
+        tail = (int)(meta >> kLaneTailShift);
     }
     // ---- one-time loads: matrix words -> registers, vectors -> LDS, tables -> LDS -------------------------------------------
     u4_t m[kResQuads];
@@ -1041,15 +1037,365 @@ static const void *resident_kernel(int ng, bool streams, bool f32, bool local)
     return f32 ? resident_kernel<float>(ng, streams, local) : resident_kernel<double>(ng, streams, local);
 }
 
-// Builds (or re-uses) the plan for A; returns false (with plan->why) when the system does not qualify.  f32: for the float-vector
-// kernel -- the LDS holds T = float slices, remote columns and tables, so the split and the tier are chosen for 4-B entries.
-static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols, const DirectArgs *da, bool f32, hipStream_t stream)
+// ---- resident_prepare: the driver of the plan.  The integer planning is avs_resident_plan.cpp (host only); here are its device steps ----
+static bool resident_refuse(ResidentPlan *pl, const char *why, int64_t n)
+{
+    pl->why = why;
+    if (cur_opt().resident_verbose > 0) fprintf(stderr, "[avs resident] not used: %s (n = %lld)\n", why, (long long)n);
+    return false;
+}
+// a failed HIP step of the plan: the error is cleared, the caller refuses the plan and the solve keeps the launch-per-phase loop
+static bool plan_failed(bool failed)
+{
+    if (failed) (void)hipGetLastError();
+    return failed;
+}
+struct PlanClock { // (verbose: where the plan's milliseconds go)
+    bool verbose;
+    timespec t0{}, last{};
+    explicit PlanClock(bool v) : verbose(v)
+    {
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        last = t0;
+    }
+    static double ms(const timespec &a, const timespec &b) { return (b.tv_sec - a.tv_sec) * 1e3 + (b.tv_nsec - a.tv_nsec) * 1e-6; }
+    void stage(const char *what)
+    {
+        if (!verbose) return;
+        timespec t{};
+        clock_gettime(CLOCK_MONOTONIC, &t);
+        fprintf(stderr, "[avs resident]   plan stage %-28s %.2f ms\n", what, ms(last, t));
+        last = t;
+    }
+    double total() const
+    {
+        timespec t{};
+        clock_gettime(CLOCK_MONOTONIC, &t);
+        return ms(t0, t);
+    }
+};
+
+// One split of the lanes into workgroups and what the device steps worked out for it: shared by the rounds and the accepted-plan work
+struct ResidentSplitState {
+    ResidentPlan *pl = nullptr;
+    const CsrView *A = nullptr;
+    const ResidentLanes *lanes = nullptr;
+    hipStream_t stream = nullptr;
+    bool lt = false, verbose = false;
+    int G = 0, cap = 0;                         // workgroups; stride of the per-workgroup source lists
+    int64_t n = 0, n_ext = 0, chunk_cols = 0;   // rows, columns, columns per bitmap pass of the re-encoding
+    size_t remap_lds = 0;
+    ResidentSplit split;
+    std::vector<int32_t> rc, tabs, tcnt, tgr;   // per workgroup: remote columns, LDS entries of its tables (even); entries per group; group boundaries
+    int lc_bits = 0, code_bits = 1;
+    int lt_gpw = 1, lt_cap = 0, lt_max = 0, lt_max_grp = 0;
+    std::string lt_why;                         // the quantity of a local-table plan that did not fit
+    DevBuf<double> lt_strided;                  // the tables while the plan is being made: lt_cap entries apart
+    DevBuf<int> fail;
+    ResidentCounts counts() const { return ResidentCounts{split.wr, rc, tabs}; }
+};
+
+// Local tables, for the split and the columns just re-encoded: one table per workgroup where its code bits fit the word next to
+// the REAL column bits (rows + remote columns of the largest workgroup, not the source lists' stride), else one per wave (the
+// rows of the wave's 64 lanes: fewer values, 16 tables whose entries add up to more LDS).  0 ok, 2 declined (lt_why), -1 failure
+static int resident_local_tables(ResidentSplitState &s)
+{
+    const int G = s.G;
+    const int64_t L = s.lanes->size();
+    const std::vector<int32_t> &wl = s.split.wl;
+    const int cols = std::max(2, max_local_columns(s.counts()));
+    s.lc_bits = 1;
+    while ((1 << s.lc_bits) < cols) ++s.lc_bits;
+    for (s.lt_gpw = 1; s.lt_gpw <= 16; s.lt_gpw *= 16) {
+        const int gpw = s.lt_gpw;
+        s.lt_cap = gpw == 1 ? 4096 : 2048;
+        const size_t ngrp = (size_t)G * (size_t)gpw;
+        s.tgr.assign(ngrp + 1, (int32_t)s.n);
+        for (int b = 0; b < G; ++b)
+            for (int g = 0; g < gpw; ++g) { // (a wave's rows: from its first lane's first row to the next wave's)
+                const int64_t l = std::min<int64_t>((int64_t)wl[(size_t)b] + 64 * g * (16 / gpw), wl[(size_t)b + 1]);
+                s.tgr[(size_t)b * gpw + g] = l < L ? s.lanes->row0[(size_t)l] : (int32_t)s.n;
+            }
+        s.tcnt.assign(ngrp, 0);
+        if (s.lt_strided.alloc(ngrp * (size_t)s.lt_cap) != AVS_OK ||
+            hipMemcpyAsync(s.pl->tg_row0.p, s.tgr.data(), s.tgr.size() * 4, hipMemcpyHostToDevice, s.stream) != hipSuccess)
+            return -1;
+        hipLaunchKernelGGL(k_resident_local_tables, dim3((unsigned)G), dim3(kResThreads), (size_t)2 * s.lt_cap * 8, s.stream, s.A->val, s.A->row_ptr,
+                           (const int32_t *)s.pl->tg_row0.p, gpw, s.lt_cap, s.lc_bits, s.pl->rwords.p, s.lt_strided.p, s.pl->ltab_cnt.p);
+        if (hipMemcpyAsync(s.tcnt.data(), s.pl->ltab_cnt.p, ngrp * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream) != hipSuccess ||
+            hipStreamSynchronize(s.stream) != hipSuccess)
+            return -1;
+        s.lt_max = 0;
+        for (size_t g = 0; g < ngrp; ++g)
+            if (s.tcnt[g] > s.lt_max) { s.lt_max = s.tcnt[g]; s.lt_max_grp = (int)g; }
+        s.code_bits = 1;
+        while ((1 << s.code_bits) < s.lt_max) ++s.code_bits;
+        char who[64];
+        if (gpw == 1) snprintf(who, sizeof(who), "workgroup %d", s.lt_max_grp);
+        else snprintf(who, sizeof(who), "wave %d of workgroup %d", s.lt_max_grp % 16, s.lt_max_grp / 16);
+        char msg[256];
+        if (s.lt_max > s.lt_cap)
+            snprintf(msg, sizeof(msg), "local table of %s has more than %d distinct values", who, s.lt_cap);
+        else if (s.code_bits + s.lc_bits > kResWordBits)
+            snprintf(msg, sizeof(msg), "local table of %s (%d values) needs %d code bits, %d left by the %d column bits of the %d-bit word", who,
+                     s.lt_max, s.code_bits, kResWordBits - s.lc_bits, s.lc_bits, kResWordBits);
+        else {
+            for (int b = 0; b < G; ++b) {
+                int t = 0;
+                for (int g = 0; g < gpw; ++g) t += s.tcnt[(size_t)b * gpw + g];
+                s.tabs[(size_t)b] = (t + 1) & ~1;
+            }
+            return 0;
+        }
+        s.lt_why = msg;
+        if (s.verbose) fprintf(stderr, "[avs resident] local tables per %s: %s\n", gpw == 1 ? "workgroup" : "wave", msg);
+    }
+    return 2;
+}
+
+// re-encodes the words for the split in s (the plan kernel) and fetches the remote-column counts; with local tables, builds them too.
+// 0 ok, 1 a source list overflowed, 2 the local tables do not fit the word, -1 failure
+static int resident_remap(ResidentSplitState &s)
+{
+    const CsrView &A = *s.A;
+    ResidentPlan *pl = s.pl;
+    if (s.lt)
+        hipLaunchKernelGGL(k_resident_remap<true>, dim3((unsigned)s.G), dim3(kResThreads), s.remap_lds, s.stream, (const uint32_t *)nullptr, A.col,
+                           A.row_ptr, 0, s.lc_bits, (const int32_t *)pl->wg_row0.p, s.cap, (int)s.n_ext, pl->rwords.p, pl->rem_list.p,
+                           pl->rem_count.p, s.fail.p, (int)s.n, pl->dep_mask.p, (int)s.chunk_cols);
+    else
+        hipLaunchKernelGGL(k_resident_remap<false>, dim3((unsigned)s.G), dim3(kResThreads), s.remap_lds, s.stream, A.packed, (const int32_t *)nullptr,
+                           A.row_ptr, A.col_bits, s.lc_bits, (const int32_t *)pl->wg_row0.p, s.cap, (int)s.n_ext, pl->rwords.p, pl->rem_list.p,
+                           pl->rem_count.p, s.fail.p, (int)s.n, pl->dep_mask.p, (int)s.chunk_cols);
+    int f = 0;
+    if (plan_failed(hipMemcpyAsync(&f, s.fail.p, sizeof(int), hipMemcpyDeviceToHost, s.stream) != hipSuccess ||
+                    hipMemcpyAsync(s.rc.data(), pl->rem_count.p, (size_t)s.G * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream) != hipSuccess ||
+                    hipStreamSynchronize(s.stream) != hipSuccess))
+        return -1;
+    if (f) return 1;
+    if (!s.lt) return 0;
+    const int t = resident_local_tables(s);
+    plan_failed(t < 0);
+    return t;
+}
+
+// the sizes of the split's arrays and of the re-encoding passes, the plan's device buffers, the plan kernels' LDS opt-in
+static const char *resident_split_setup(ResidentSplitState &s, int64_t n_cols, double stream_T)
+{
+    ResidentPlan *pl = s.pl;
+    const CsrView &A = *s.A;
+    const int G = s.G;
+    const int64_t n = s.n, L = s.lanes->size();
+    while (!s.lt && (1 << s.code_bits) < A.table_size + 1) ++s.code_bits; // + the zero the padding words address
+    if (s.code_bits >= kResWordBits - 8) return "dictionary needs too many bits";
+    s.cap = stream_T > 0. ? 32768 : 16384; // (a workgroup with more remote columns than its source list holds does not qualify)
+    s.n_ext = n_cols > n ? n_cols : n;
+    s.chunk_cols = std::min<int64_t>(s.n_ext, kRemapChunk);
+    if (cur_opt().resident_remap_chunk >= 512) // tests: several bitmap passes on a small system
+        s.chunk_cols = std::min<int64_t>(s.chunk_cols, (cur_opt().resident_remap_chunk + 511) / 512 * 512);
+    pl->remap_passes = (int)((s.n_ext + s.chunk_cols - 1) / s.chunk_cols);
+    s.remap_lds = ((size_t)(((s.chunk_cols + 31) / 32 + kRemapBlock - 1) / kRemapBlock) * (kRemapBlock + 1) + 2) * sizeof(unsigned);
+    s.split.wl.resize((size_t)G + 1);
+    s.split.wr.resize((size_t)G + 1);
+    s.rc.resize((size_t)G);
+    s.tabs.assign((size_t)G, 0);
+    s.split.lane_w.assign((size_t)L, 1.0);
+    s.split.cum.assign((size_t)L + 1, 0.);
+    s.split.lane_extra.assign((size_t)L, 0.);
+    if (plan_failed(pl->wg_row0.alloc((size_t)G + 1) != AVS_OK || pl->rwords.alloc((size_t)A.nnz) != AVS_OK || pl->rem_count.alloc((size_t)G) != AVS_OK ||
+                    pl->rem_list.alloc((size_t)G * s.cap) != AVS_OK || s.fail.alloc(1) != AVS_OK || pl->dep_mask.alloc((size_t)G * 32) != AVS_OK || G > 1024 ||
+                    hipFuncSetAttribute(s.lt ? (const void *)k_resident_remap<true> : (const void *)k_resident_remap<false>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.remap_lds) != hipSuccess ||
+                    (s.lt && (pl->ltab_cnt.alloc((size_t)G * 16) != AVS_OK || pl->tg_row0.alloc((size_t)G * 16 + 1) != AVS_OK ||
+                            hipFuncSetAttribute((const void *)k_resident_local_tables, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4096 * 8) != hipSuccess))))
+        return "plan allocation failed";
+    return nullptr;
+}
+
+struct ResidentTier {
+    int ng = -1, max_cols = 0; // row-local vectors in global memory (-1: no tier fits); most rows + remote columns of a workgroup
+    size_t lds = 0;
+    const char *last_reason = "the vector slices + remote columns of a workgroup do not fit the LDS";
+};
+
+// Tiers: the fewest row-local vectors in global memory that fit.  Tier 1 (s) is tried with re-balancing first; tiers 2 and 3 (p, r
+// too) only when that fails -- larger slabs (streamed rows: the 2- and 4-way partitions) -- since their vector traffic is back in
+// the update phase (coalesced since the second pass of round 3, which is what makes them worth it).
+// Rounds of a tier: workgroup boundaries by estimated time (split_by_cost), then the words are re-encoded (k_resident_remap) and the
+// LDS footprints checked: a workgroup whose slices + remote columns do not fit (the ones that read the halo: up to 10 k remote
+// columns) gets its lanes re-weighted and the split is redone -- a few rounds.  Remote columns cost their workgroup a fill (the
+// halo-reading workgroups fill 8-10 k and finished 5 us after the median one).  Known only after a first split: round 0 measures
+// them, round 1 splits with them spread over the workgroup's lanes.  Per slot, in the units of c_lane / c_row: 0 / 1.1 / 2 / 3 / 4.5
+// -> 8-way loop-back (ranks 0 / 3) 33.8 / 35.9, 32.6 / 35.0, 31.6 / 33.0, 30.0 / 32.1, 30.4 / 32.3 us per iteration.
+// Returns the refusal of a step that ends the plan, else nullptr with tier->ng >= 0 (s holds the accepted split) or < 0 (none fits).
+static const char *resident_split_rounds(ResidentSplitState &s, double stream_T, size_t esz, size_t lds_max, size_t lds_extra, ResidentTier *tier)
+{
+    const int G = s.G;
+    const int64_t L = s.lanes->size();
+    const int max_ng_limit = cur_opt().resident_max_global;
+    const bool equal_lanes = cur_opt().resident_equal_lanes != 0;
+    const double c_rem = cur_opt().resident_remote_cost;
+    const double limit = (double)(lds_max - lds_extra) / (double)esz; // entries of the vector type a workgroup may hold
+    ResidentSplit &sp = s.split;
+    std::vector<int32_t> rc_round0;
+    bool round0_done = false;
+    for (int max_ng = std::min(1, max_ng_limit); max_ng <= max_ng_limit && tier->ng < 0; ++max_ng) {
+        if ((size_t)(4 - max_ng) * (size_t)(s.n / G) * esz > lds_max) continue; // (even the average workgroup's slices would not fit)
+        const int t_max = max_ng < 3 ? (max_ng < 0 ? 0 : max_ng) : 3;           // the largest tier allowed here: its footprints steer the split
+        std::fill(sp.lane_w.begin(), sp.lane_w.end(), 1.0);
+        std::fill(sp.lane_extra.begin(), sp.lane_extra.end(), 0.);
+        bool reweighted = false, extras_active = false, extras_off = false;
+        for (int round = 0; round < (stream_T > 0. ? 9 : 5) && tier->ng < 0; ++round) { // (large slabs: a lower tier is worth more rounds)
+            bool whole = split_by_cost(*s.lanes, G, cur_opt().resident_stream_cost, &sp);
+            if (!whole && extras_active && !reweighted) { // the remote-column term alone pushed a workgroup past 1024 lanes: split without it
+                std::fill(sp.lane_extra.begin(), sp.lane_extra.end(), 0.);
+                extras_active = false;
+                extras_off = true;
+                whole = split_by_cost(*s.lanes, G, cur_opt().resident_stream_cost, &sp);
+            }
+            if (!whole || equal_lanes) {
+                if (reweighted) break; // (re-weighting pushed a workgroup past 1024 lanes: next tier)
+                split_equal_lanes(L, G, &sp.wl);
+            }
+            sp.max_rows = workgroup_rows(sp.wl, *s.lanes, s.n, &sp.wr);
+            s.lc_bits = 1;
+            while ((1 << s.lc_bits) < sp.max_rows + s.cap + 2) ++s.lc_bits;
+            if (s.lc_bits + s.code_bits > kResWordBits) s.lc_bits = kResWordBits - s.code_bits; // (checked against the real counts below)
+            if (plan_failed(hipMemcpy(s.pl->wg_row0.p, sp.wr.data(), sp.wr.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                            hipMemsetAsync(s.fail.p, 0, sizeof(int), s.stream) != hipSuccess))
+                return "plan upload failed";
+            // (round 0 of a later tier is the split of the first tier's round 0: its counts are re-used, the words re-encoded only if it is accepted)
+            const bool reuse_round0 = round == 0 && round0_done && !equal_lanes && !s.lt; // (local tables belong to ONE split)
+            if (reuse_round0) s.rc = rc_round0;
+            else {
+                const int rm = resident_remap(s);
+                if (rm < 0) return "remap failed";
+                if (rm == 2) return s.lt_why.c_str();
+                if (rm > 0) {
+                    tier->last_reason = "a workgroup reads more remote columns than its source list holds";
+                    break;
+                }
+            }
+            const ResidentCounts counts = s.counts();
+            if (round == 0) {
+                if (!reuse_round0) {
+                    rc_round0 = s.rc;
+                    round0_done = true;
+                }
+                // a tier whose TOTAL demand is close to the chip's LDS never fits (lanes, not LDS, bound the split; every further round is a
+                // re-encoding pass: 10 ms of plan time on a 1.3 M-row system): next tier
+                if (total_demand(counts, t_max) > 0.88 * limit * (double)G) break;
+                // the remote columns are known now: one more split that counts them
+                if (c_rem > 0. && !extras_off && spread_remote_cost(s.rc, c_rem, &sp)) {
+                    extras_active = true;
+                    continue;
+                }
+            }
+            // LDS split: every workgroup holds its slice of u + its remote-column cache, and as many of r, p, s as still fit (tiers: NG =
+            // 0 .. 3 of them in global memory instead).  Footprint of workgroup b: (4 - NG) rows_b + remote_b entries; the largest decides.
+            tier->max_cols = max_local_columns(counts);
+            for (int t = 0; t <= 3 && t <= max_ng && tier->ng < 0; ++t) {
+                const size_t need = (size_t)largest_footprint(counts, t) * esz + lds_extra;
+                if (s.verbose) fprintf(stderr, "[avs resident] round %d, LDS tier %d: largest workgroup footprint %zu B (limit %zu)\n", round, t, need, lds_max);
+                if (need <= lds_max) {
+                    tier->ng = t;
+                    tier->lds = need;
+                }
+            }
+            if (tier->ng >= 0) {
+                if (reuse_round0) { // accepted on re-used counts: the words still hold another split's encoding
+                    const int rm = resident_remap(s);
+                    if (rm == 2) return s.lt_why.c_str();
+                    if (rm != 0) return "remap failed";
+                }
+                continue;
+            }
+            // shrink the offenders (at the largest tier allowed) and split again ... unless the MEDIAN workgroup does not fit either:
+            // no re-split helps, go to the next tier
+            if (median_footprint(counts, t_max) > 0.98 * limit) break;
+            if (reweight_offenders(counts, t_max, limit, &sp)) reweighted = true;
+        }
+    }
+    return nullptr;
+}
+
+// the tables of the accepted split, back to back
+static const char *resident_pack_tables(ResidentSplitState &s)
+{
+    ResidentPlan *pl = s.pl;
+    std::vector<int32_t> toff(s.tcnt.size() + 1, 0);
+    for (size_t g = 0; g < s.tcnt.size(); ++g) toff[g + 1] = toff[g] + s.tcnt[g];
+    if (plan_failed(pl->ltab_off.alloc(toff.size()) != AVS_OK || pl->ltab.alloc((size_t)toff.back()) != AVS_OK ||
+                    hipMemcpy(pl->ltab_off.p, toff.data(), toff.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
+        return "plan allocation failed";
+    hipLaunchKernelGGL(k_resident_pack_tables, dim3((unsigned)s.tcnt.size()), dim3(256), 0, s.stream, (const double *)s.lt_strided.p, s.lt_cap,
+                       (const int32_t *)pl->ltab_off.p, pl->ltab.p);
+    if (plan_failed(hipGetLastError() != hipSuccess || hipStreamSynchronize(s.stream) != hipSuccess)) return "table layout failed";
+    return nullptr;
+}
+
+// a partitioned plan: the push segments of every peer's send list and the workgroups that wait for the peers' flags (every workgroup
+// overlapping a halo-reading 512-row tile of the plan)
+static const char *resident_partition_arrays(ResidentPlan *pl, const DirectArgs *da, const std::vector<int32_t> &wr, int64_t n,
+                                             std::vector<int32_t> *seg, std::vector<uint8_t> *whalo)
+{
+    DistDev h;
+    if (plan_failed(hipMemcpy(&h, da->dd, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess)) return "DistDev download failed";
+    if (h.paranoid) return "paranoid mode keeps the launch-per-phase loop";
+    std::vector<int32_t> sidx((size_t)(da->n_send > 0 ? da->n_send : 1));
+    if (plan_failed(da->n_send && hipMemcpy(sidx.data(), h.send_idx, (size_t)da->n_send * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess))
+        return "send list download failed";
+    pl->n_push_wgs = push_segments(h.send_off, h.npeers, sidx.data(), wr, seg);
+    std::vector<int32_t> tb((size_t)(da->n_tiles_bnd > 0 ? da->n_tiles_bnd : 1));
+    if (plan_failed(da->n_tiles_bnd &&
+                    hipMemcpy(tb.data(), da->tiles_bnd, (size_t)da->n_tiles_bnd * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess))
+        return "tile list download failed";
+    halo_workgroups(tb.data(), da->n_tiles_bnd, kTileRows, n, wr, whalo);
+    return nullptr;
+}
+
+static const char *resident_upload(ResidentPlan *pl, const ResidentLanes &lanes, const std::vector<int32_t> &wl, const std::vector<int32_t> &seg,
+                                   const std::vector<uint8_t> &whalo)
+{
+    const size_t L = (size_t)lanes.size(), G = whalo.size();
+    if (!(pl->lane_row0.alloc(L) == AVS_OK && pl->lane_meta.alloc(L) == AVS_OK && pl->wg_lane0.alloc(G + 1) == AVS_OK &&
+          pl->push_seg.alloc(seg.size()) == AVS_OK && pl->wg_halo.alloc(G) == AVS_OK && pl->bar_count.alloc(2) == AVS_OK &&
+          pl->bar_flags.alloc(G) == AVS_OK && pl->slots.alloc(G * 4) == AVS_OK && pl->bcast.alloc(4 * kResGens) == AVS_OK))
+        return "plan allocation failed";
+    if (plan_failed(!(hipMemcpy(pl->lane_row0.p, lanes.row0.data(), L * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                      hipMemcpy(pl->lane_meta.p, lanes.meta.data(), L * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                      hipMemcpy(pl->wg_lane0.p, wl.data(), wl.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                      hipMemcpy(pl->push_seg.p, seg.data(), seg.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                      hipMemcpy(pl->wg_halo.p, whalo.data(), whalo.size(), hipMemcpyHostToDevice) == hipSuccess)))
+        return "plan upload failed";
+    return nullptr;
+}
+
+// the waves' lane-interleaved streams of the rows that do not fit the registers; *run = their quads, padding included
+static const char *resident_stream_layout(ResidentSplitState &s, uint32_t padword, int64_t *run)
+{
+    ResidentPlan *pl = s.pl;
+    std::vector<int32_t> soff;
+    *run = wave_stream_offsets(s.split.wl, *s.lanes, &soff);
+    if (*run >= (1ll << 29)) return "streamed quads exceed 32-bit offsets";
+    if (plan_failed(pl->swords.alloc((size_t)*run * 4) != AVS_OK || pl->wave_soff.alloc(soff.size()) != AVS_OK ||
+                    hipMemcpy(pl->wave_soff.p, soff.data(), soff.size() * 4, hipMemcpyHostToDevice) != hipSuccess))
+        return "stream allocation failed";
+    hipLaunchKernelGGL(k_resident_stream_layout, dim3((unsigned)s.G), dim3(kResThreads), 0, s.stream, s.A->row_ptr, (const uint32_t *)pl->rwords.p,
+                       (const int32_t *)pl->lane_row0.p, (const uint32_t *)pl->lane_meta.p, (const int32_t *)pl->wg_lane0.p,
+                       (const int32_t *)pl->wave_soff.p, padword, reinterpret_cast<u4_t *>(pl->swords.p));
+    if (plan_failed(hipGetLastError() != hipSuccess || hipStreamSynchronize(s.stream) != hipSuccess)) return "stream layout failed";
+    return nullptr;
+}
+
+// The plan of this matrix, vector type and option is kept; otherwise the plan is reset for a new attempt under the new key.
+static bool resident_plan_is_current(ResidentPlan *pl, const CsrView &A, const DirectArgs *da, bool f32)
 {
     const void *key[4] = {A.row_ptr, A.packed, A.table, da ? (const void *)da->dd : nullptr};
     const bool opt_local = cur_opt().resident_local_tables != 0; // (part of the key, like the vector type: switching the option plans again)
     if (pl->tried && memcmp(key, pl->key, sizeof(key)) == 0 && pl->key_n == A.n && pl->key_epoch == A.epoch && pl->f32 == f32 &&
         pl->key_local == opt_local)
-        return pl->ok;
+        return true;
     pl->key_local = opt_local;
     pl->local = false;
     pl->key_epoch = A.epoch; // (a re-assembly with the same DOF count rewrites the same buffers: the words of the plan would be stale)
@@ -1061,539 +1407,220 @@ static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols,
     pl->key_n = A.n;
     pl->n_lanes = pl->streamed_rows = pl->streamed_words = 0;
     pl->max_lanes = pl->max_rows = pl->long_lanes = pl->longest_tail = pl->max_lane_streamed = pl->max_remote = pl->remap_passes = pl->lt_max = 0;
+    return false;
+}
+
+// Builds (or re-uses) the plan for A; returns false (with plan->why) when the system does not qualify.  f32: for the float-vector
+// kernel -- the LDS holds T = float slices, remote columns and tables, so the split and the tier are chosen for 4-B entries.
+static bool resident_prepare(ResidentPlan *pl, const CsrView &A, int64_t n_cols, const DirectArgs *da, bool f32, hipStream_t stream)
+{
+    if (resident_plan_is_current(pl, A, da, f32)) return pl->ok; // 1. the key
     const size_t esz = f32 ? sizeof(float) : sizeof(double); // LDS entry of the vector slices, remote columns and tables
     const bool verbose = cur_opt().resident_verbose > 0;
-    timespec plan_t0{};
-    clock_gettime(CLOCK_MONOTONIC, &plan_t0);
-    timespec stage_t = plan_t0;
-    auto stage = [&](const char *what) { // (verbose: where the plan's milliseconds go)
-        if (!verbose) return;
-        timespec t{};
-        clock_gettime(CLOCK_MONOTONIC, &t);
-        fprintf(stderr, "[avs resident]   plan stage %-28s %.2f ms\n", what, (t.tv_sec - stage_t.tv_sec) * 1e3 + (t.tv_nsec - stage_t.tv_nsec) * 1e-6);
-        stage_t = t;
-    };
-    auto no = [&](const char *why) {
-        pl->why = why;
-        if (verbose) fprintf(stderr, "[avs resident] not used: %s (n = %lld)\n", why, (long long)A.n);
-        return false;
-    };
+    PlanClock clock(verbose);
+    const int64_t n = A.n;
+    auto no = [&](const char *why) { return resident_refuse(pl, why, n); };
+
+    // ---- 2. cheap refusals (before the row pointers cross PCIe and the host walks them: 20-100 ms at 4-7 M rows, per new matrix) ----
     // lt: a matrix that fails only these two dictionary conditions is planned with local value tables when the option asks for it
     const bool lt = resident_local_tables_wanted(A);
     if (!lt && (!A.packed || !A.codes || A.tab_ptr || A.cbase || A.col_bits <= 0)) return no("needs the packed single-dictionary form");
     if ((!lt && A.table_size > 1023) || A.n < 1 || A.n >= (1ll << 31)) return no("dictionary too large");
-    std::string lt_why; // the quantity of a local-table plan that did not fit
-    DevBuf<double> lt_strided; // the tables while the plan is being made: lt_cap entries apart
     int dev = 0, cus = 0, coop = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev) != hipSuccess || !coop || cus < 1) {
-        (void)hipGetLastError();
+    if (plan_failed(hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+                    hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev) != hipSuccess || !coop || cus < 1))
         return no("no cooperative launch");
-    }
-    const int64_t n = A.n;
     int G = cus;
     if (cur_opt().resident_cus > 0 && cur_opt().resident_cus < cus) G = cur_opt().resident_cus; // tests: two ranks on ONE GPU, each on a share of the CUs
-    // Cheap refusals first (before the row pointers cross PCIe and the host walks them: 20-100 ms at 4-7 M rows, per new matrix):
     // every workgroup keeps its slice of u in LDS next to its remote columns (never less than about half as much again)
     if ((size_t)(n / G) * esz > (size_t)(160 * 1024) * 65 / 100) return no("the workgroups' slices of u leave no room for their remote columns in the LDS");
+
+    // ---- 3. the row pointers ----
     std::vector<int32_t> rp((size_t)n + 1);
-    if (hipMemcpyAsync(rp.data(), A.row_ptr, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess) {
-        (void)hipGetLastError();
+    if (plan_failed(hipMemcpyAsync(rp.data(), A.row_ptr, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                    hipStreamSynchronize(stream) != hipSuccess))
         return no("row pointer download failed");
-    }
-    // ---- lanes: consecutive rows, each in ceil(len / 5) of the lane's 15 quads, at most 6 rows; a row of more than 75 words sits
-    // alone, the rest of it is read from memory ----
+    clock.stage("row pointers to the host");
+
+    // ---- 4. lanes (avs_resident_plan.cpp) ----
     int max_quads = kResQuads;
     if (cur_opt().resident_max_quads >= 1 && cur_opt().resident_max_quads <= kResQuads) max_quads = cur_opt().resident_max_quads; // tests: long-row path
-    const int W = max_quads * kResQuadWords;
-    std::vector<int32_t> lrow;
-    std::vector<uint32_t> lmeta;
-    lrow.reserve((size_t)n / 4 + 16);
-    lmeta.reserve((size_t)n / 4 + 16);
-    // T: streamed QUADS per lane.  0 while the slab fits the register files; otherwise every lane takes, after its register rows, rows
-    // worth about T quads (error diffusion keeps the average; equal quads per lane, not equal rows: a wave walks its longest lane's
-    // stream, and with rows of 3-6 quads an equal-rows split padded the streams by 64 %); at most 127 rows per lane
-    const char *lane_fail = nullptr;
-    auto quads_of = [&](int64_t row) { return (rp[(size_t)row + 1] - rp[(size_t)row] + kResQuadWords - 1) / kResQuadWords; };
-    auto form_lanes = [&](double T) {
-        lrow.clear();
-        lmeta.clear();
-        double debt = 0.;
-        for (int64_t i = 0; i < n;) {
-            const int Lr = rp[(size_t)i + 1] - rp[(size_t)i];
-            if (Lr <= 0) { lane_fail = "empty row"; return; } // (every row of this system carries its diagonal, cpp:2768)
-            if (Lr > W) {
-                if (Lr - W >= (1 << 22)) { lane_fail = "row too long"; return; }
-                lrow.push_back((int32_t)i);
-                lmeta.push_back(1u | ((unsigned)(Lr - W) << 10));
-                ++i;
-                continue;
-            }
-            int rows = 0, used = 0;
-            const int64_t first = i;
-            while (i < n && rows < kResRowsMax) {
-                const int Li = rp[(size_t)i + 1] - rp[(size_t)i];
-                if (Li <= 0 || Li > W) break;
-                const int k = (Li + kResQuadWords - 1) / kResQuadWords;
-                if (used + k > max_quads) break;
-                used += k;
-                ++rows;
-                ++i;
-            }
-            debt += T;
-            int m = 0;
-            while (i < n && m < 127) {
-                if (rp[(size_t)i + 1] - rp[(size_t)i] <= 0) { lane_fail = "empty row"; return; }
-                const int k = quads_of(i);
-                if ((double)k > debt + 0.5 * (double)k) break; // (take the row when at least half of it is owed)
-                debt -= (double)k;
-                ++m;
-                ++i;
-            }
-            lrow.push_back((int32_t)first);
-            lmeta.push_back((unsigned)rows | ((unsigned)m << 3));
-        }
-    };
-    stage("row pointers to the host");
-    const int64_t lane_cap = (int64_t)G * kResThreads;
+    ResidentLanes lanes;
     int64_t q_total = 0;
-    for (int64_t i = 0; i < n; ++i) q_total += quads_of(i);
-    // (a slab whose quads exceed what the lanes could hold even at 14 of 15 quads each needs streamed rows for certain: the
-    // registers-only pass -- 2 ns per row on the host -- is skipped)
-    const bool surely_streams = (double)q_total > 14. * 0.93 * (double)lane_cap;
-    if (!surely_streams) form_lanes(0.);
-    if (lane_fail) return no(lane_fail);
-    stage("lanes (registers only)");
     double stream_T = 0.;
-    if (surely_streams || (int64_t)lrow.size() > lane_cap * 93 / 100) {
-        if (cur_opt().resident_no_stream) return no("too many rows for the register files of this GPU");
-        // register quads an average lane holds: measured when the registers-only pass ran, else 12.8 (4-way slab 12.9, 256^3 beam 12.7)
-        const double q_lane = surely_streams ? 12.8 : (double)q_total / (double)lrow.size();
-        double Lt = cur_opt().resident_lane_fill * (double)lane_cap;
-        for (int attempt = 0; attempt < 8; ++attempt, Lt *= 0.97) {
-            stream_T = ((double)q_total - Lt * q_lane) / Lt;
-            form_lanes(stream_T);
-            if (lane_fail) return no(lane_fail);
-            if ((int64_t)lrow.size() <= lane_cap * 96 / 100) break;
-        }
-        if ((int64_t)lrow.size() > lane_cap * 97 / 100) return no("too many rows for the register files of this GPU, even with streamed rows");
-    }
-    const int64_t L = (int64_t)lrow.size();
-    int64_t lpw = (L + G - 1) / G;
-    if (lpw > kResThreads) return no("too many rows for the register files of this GPU");
-    stage("lanes with streamed rows");
-    // quads a lane streams per iteration (cost model, stream layout)
-    std::vector<int32_t> lane_sw((size_t)L, 0);
-    int64_t stream_words = 0;
+    if (const char *why = lanes_in_registers(rp.data(), n, G, max_quads, &lanes, &q_total)) return no(why);
+    clock.stage("lanes (registers only)");
+    if (const char *why = lanes_with_streams(rp.data(), n, G, max_quads, cur_opt().resident_lane_fill, cur_opt().resident_no_stream != 0, q_total,
+                                             &lanes, &stream_T))
+        return no(why);
+    clock.stage("lanes with streamed rows");
+    const int64_t L = lanes.size();
     pl->n_lanes = L;
-    for (int64_t l = 0; l < L; ++l) {
-        const int m = (int)((lmeta[(size_t)l] >> 3) & 127u);
-        if (lmeta[(size_t)l] >> 10) { // (a long row's lane: one register row, no streamed rows, the tail's words above bit 10)
-            pl->long_lanes++;
-            pl->longest_tail = std::max(pl->longest_tail, (int)(lmeta[(size_t)l] >> 10));
-            continue;
-        }
-        pl->streamed_rows += m;
-        pl->max_lane_streamed = std::max(pl->max_lane_streamed, m);
-        if (m) {
-            const int64_t r = (int64_t)lrow[(size_t)l] + (int64_t)(lmeta[(size_t)l] & 7u);
-            for (int64_t q = r; q < r + m; ++q) lane_sw[(size_t)l] += (rp[(size_t)q + 1] - rp[(size_t)q] + kResQuadWords - 1) / kResQuadWords; // quads
-            stream_words += rp[(size_t)(r + m)] - rp[(size_t)r];
-        }
-    }
-    pl->streamed_words = stream_words;
-    std::vector<int32_t> wl((size_t)G + 1), wr((size_t)G + 1), rc((size_t)G);
-    int max_rows = 0;
-    int code_bits = 1;
-    while (!lt && (1 << code_bits) < A.table_size + 1) ++code_bits; // + the zero the padding words address
-    if (code_bits >= kResWordBits - 8) return no("dictionary needs too many bits");
+    pl->long_lanes = lanes.long_lanes;
+    pl->longest_tail = lanes.longest_tail;
+    pl->streamed_rows = lanes.streamed_rows;
+    pl->max_lane_streamed = lanes.max_lane_streamed;
+    pl->streamed_words = lanes.streamed_words;
+
+    // ---- 5. the split: tiers and rounds ----
+    ResidentSplitState s;
+    s.pl = pl;
+    s.A = &A;
+    s.lanes = &lanes;
+    s.stream = stream;
+    s.lt = lt;
+    s.verbose = verbose;
+    s.G = G;
+    s.n = n;
     const size_t lds_max = 160 * 1024 - 4096 - 1024;
     // the two tables (values + zero, inverted values) in T, then the fold space (3 x 16 wave sums) and 4 + 4 scalars in double
-    // (local tables: their entries are counted per workgroup, tabs[b] below, next to the remote columns; no inverted values in LDS)
+    // (local tables: their entries are counted per workgroup, tabs[b], next to the remote columns; no inverted values in LDS)
     const size_t lds_extra = (lt ? 0 : 2 * ((size_t)A.table_size + 1) * esz) + (48 + 8) * sizeof(double);
-    std::vector<int32_t> tabs((size_t)G, 0), tcnt, tgr; // LDS entries of workgroup b's tables (even); entries per group; group boundaries
-    int lt_gpw = 1, lt_cap = 0, lt_max = 0, lt_max_grp = 0;
-    const int cap = stream_T > 0. ? 32768 : 16384; // stride of the per-workgroup source lists (a workgroup with more remote columns does not qualify)
-    const int64_t n_ext = n_cols > n ? n_cols : n;
-    int64_t chunk_cols = std::min<int64_t>(n_ext, kRemapChunk);
-    if (cur_opt().resident_remap_chunk >= 512) // tests: several bitmap passes on a small system
-        chunk_cols = std::min<int64_t>(chunk_cols, (cur_opt().resident_remap_chunk + 511) / 512 * 512);
-    pl->remap_passes = (int)((n_ext + chunk_cols - 1) / chunk_cols);
-    const size_t remap_lds = ((size_t)(((chunk_cols + 31) / 32 + kRemapBlock - 1) / kRemapBlock) * (kRemapBlock + 1) + 2) * sizeof(unsigned);
-    DevBuf<int> fail;
-    if (pl->wg_row0.alloc((size_t)G + 1) != AVS_OK || pl->rwords.alloc((size_t)A.nnz) != AVS_OK || pl->rem_count.alloc((size_t)G) != AVS_OK ||
-        pl->rem_list.alloc((size_t)G * cap) != AVS_OK || fail.alloc(1) != AVS_OK || pl->dep_mask.alloc((size_t)G * 32) != AVS_OK || G > 1024 ||
-        hipFuncSetAttribute(lt ? (const void *)k_resident_remap<true> : (const void *)k_resident_remap<false>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)remap_lds) != hipSuccess ||
-        (lt && (pl->ltab_cnt.alloc((size_t)G * 16) != AVS_OK || pl->tg_row0.alloc((size_t)G * 16 + 1) != AVS_OK ||
-                hipFuncSetAttribute((const void *)k_resident_local_tables, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4096 * 8) != hipSuccess))) {
-        (void)hipGetLastError();
-        return no("plan allocation failed");
-    }
-    // Tiers: the fewest row-local vectors in global memory that fit.  Tier 1 (s) is tried with re-balancing first; tiers 2 and 3 (p, r
-    // too) only when that fails -- larger slabs (streamed rows: the 2- and 4-way partitions) -- since their vector traffic is back in
-    // the update phase (coalesced since the second pass of round 3, which is what makes them worth it).
-    int max_ng_limit = 3;
-    max_ng_limit = cur_opt().resident_max_global;
-    // Workgroup boundaries by estimated time, not by lanes: the SpMV phase costs per lane (every lane walks its quads), the vector
-    // update per row (measured: ~12.7 ns per lane, ~3.6 ns per row of a workgroup) -- workgroups of fine regions have 2x the rows
-    // of those in coarse regions at equal lanes.  Then the words are re-encoded (k_resident_remap) and the LDS footprints checked:
-    // a workgroup whose slices + remote columns do not fit (the ones that read the halo: up to 10 k remote columns) gets its lanes
-    // re-weighted and the split is redone -- a few rounds.
-    std::vector<double> lane_w((size_t)L, 1.0), cum((size_t)L + 1, 0.), lane_extra((size_t)L, 0.);
-    // remote columns cost their workgroup a fill (the halo-reading workgroups fill 8-10 k and finished 5 us after the
-    // median one).  Known only after a first split: round 0 measures them, round 1 splits with them spread over the workgroup's lanes.
-    // Per slot, in the units of c_lane / c_row: 0 / 1.1 / 2 / 3 / 4.5 -> 8-way loop-back (ranks 0 / 3) 33.8 / 35.9, 32.6 / 35.0, 31.6 / 33.0,
-    // 30.0 / 32.1, 30.4 / 32.3 us per iteration.
-    std::vector<int32_t> rc_round0;
-    bool round0_done = false, reuse_round0 = false;
-    const double c_rem = cur_opt().resident_remote_cost;
-    const double c_lane = 12.7, c_row = 3.6;
-    const double kStreamCost = cur_opt().resident_stream_cost;
-    int ng = -1, lc_bits = 0, max_cols = 0;
-    size_t lds = 0;
-    const char *last_reason = "the vector slices + remote columns of a workgroup do not fit the LDS";
-    for (int max_ng = std::min(1, max_ng_limit); max_ng <= max_ng_limit && ng < 0; ++max_ng) {
-    if ((size_t)(4 - max_ng) * (size_t)(n / G) * esz > lds_max) continue; // (even the average workgroup's slices would not fit)
-    std::fill(lane_w.begin(), lane_w.end(), 1.0);
-    std::fill(lane_extra.begin(), lane_extra.end(), 0.);
-    bool give_up = false, reweighted = false, extras_active = false, extras_off = false;
-    for (int round = 0; round < (stream_T > 0. ? 9 : 5) && ng < 0 && !give_up; ++round) { // (large slabs: a lower tier is worth more rounds)
-        for (int64_t l = 0; l < L; ++l) // (a streamed quad costs what a register quad does plus its load; 15 quads = one lane's walk)
-            cum[(size_t)l + 1] = cum[(size_t)l] + lane_w[(size_t)l] * (c_lane * (1. + kStreamCost * (double)lane_sw[(size_t)l] / (double)kResQuads) +
-                                                                      c_row * (double)((lmeta[(size_t)l] & 7u) + ((lmeta[(size_t)l] >> 3) & 127u)) +
-                                                                      lane_extra[(size_t)l]);
-        int64_t l0 = 0;
-        wl[0] = 0;
-        for (int b = 1; b <= G; ++b) {
-            // equal shares of what is LEFT (a workgroup clipped at 1024 lanes hands its surplus to the following ones)
-            const double target = cum[(size_t)l0] + (cum[(size_t)L] - cum[(size_t)l0]) / (double)(G - b + 1);
-            int64_t l1 = std::lower_bound(cum.begin() + l0, cum.end(), target) - cum.begin();
-            if (b == G) l1 = L;
-            l1 = std::min<int64_t>(std::max(l1, l0), std::min<int64_t>(L, l0 + kResThreads));
-            wl[(size_t)b] = (int32_t)l1;
-            l0 = l1;
-        }
-        if (l0 != L && extras_active && !reweighted) { // the remote-column term alone pushed a workgroup past 1024 lanes: split without it
-            std::fill(lane_extra.begin(), lane_extra.end(), 0.);
-            extras_active = false;
-            extras_off = true;
-            --round;
-            continue;
-        }
-        if (l0 != L || cur_opt().resident_equal_lanes) {
-            if (reweighted) { give_up = true; break; } // (re-weighting pushed a workgroup past 1024 lanes: give up)
-            for (int b = 0; b <= G; ++b) wl[(size_t)b] = (int32_t)std::min<int64_t>((int64_t)b * lpw, L);
-        }
-        max_rows = 0;
-        for (int b = 0; b <= G; ++b) wr[(size_t)b] = wl[(size_t)b] < L ? lrow[(size_t)wl[(size_t)b]] : (int32_t)n;
-        for (int b = 0; b < G; ++b) max_rows = std::max(max_rows, wr[(size_t)b + 1] - wr[(size_t)b]);
-        lc_bits = 1;
-        while ((1 << lc_bits) < max_rows + cap + 2) ++lc_bits;
-        if (lc_bits + code_bits > kResWordBits) lc_bits = kResWordBits - code_bits; // (checked against the real counts below)
-        if (hipMemcpy(pl->wg_row0.p, wr.data(), wr.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemsetAsync(fail.p, 0, sizeof(int), stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return no("plan upload failed");
-        }
-        // re-encode the words for this split (the plan kernel) and fetch the remote-column counts
-        // Local tables, for the split and the columns just re-encoded: one table per workgroup where its code bits fit the word next to
-        // the REAL column bits (rows + remote columns of the largest workgroup, not the source lists' stride), else one per wave (the
-        // rows of the wave's 64 lanes: fewer values, 16 tables whose entries add up to more LDS).  0 ok, 2 declined (lt_why), -1 failure
-        auto local_tables = [&]() -> int {
-            int cols = 2;
-            for (int b = 0; b < G; ++b)
-                cols = std::max(cols, ((wr[(size_t)b + 1] - wr[(size_t)b] + 1) & ~1) + ((rc[(size_t)b] + 1) & ~1));
-            lc_bits = 1;
-            while ((1 << lc_bits) < cols) ++lc_bits;
-            for (lt_gpw = 1; lt_gpw <= 16; lt_gpw *= 16) {
-                lt_cap = lt_gpw == 1 ? 4096 : 2048;
-                const size_t ngrp = (size_t)G * (size_t)lt_gpw;
-                tgr.assign(ngrp + 1, (int32_t)n);
-                for (int b = 0; b < G; ++b)
-                    for (int g = 0; g < lt_gpw; ++g) { // (a wave's rows: from its first lane's first row to the next wave's)
-                        const int64_t l = std::min<int64_t>((int64_t)wl[(size_t)b] + 64 * g * (16 / lt_gpw), wl[(size_t)b + 1]);
-                        tgr[(size_t)b * lt_gpw + g] = l < L ? lrow[(size_t)l] : (int32_t)n;
-                    }
-                tcnt.assign(ngrp, 0);
-                if (lt_strided.alloc(ngrp * (size_t)lt_cap) != AVS_OK ||
-                    hipMemcpyAsync(pl->tg_row0.p, tgr.data(), tgr.size() * 4, hipMemcpyHostToDevice, stream) != hipSuccess)
-                    return -1;
-                hipLaunchKernelGGL(k_resident_local_tables, dim3((unsigned)G), dim3(kResThreads), (size_t)2 * lt_cap * 8, stream, A.val, A.row_ptr,
-                                   (const int32_t *)pl->tg_row0.p, lt_gpw, lt_cap, lc_bits, pl->rwords.p, lt_strided.p, pl->ltab_cnt.p);
-                if (hipMemcpyAsync(tcnt.data(), pl->ltab_cnt.p, ngrp * sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                    hipStreamSynchronize(stream) != hipSuccess)
-                    return -1;
-                lt_max = 0;
-                for (size_t g = 0; g < ngrp; ++g)
-                    if (tcnt[g] > lt_max) { lt_max = tcnt[g]; lt_max_grp = (int)g; }
-                code_bits = 1;
-                while ((1 << code_bits) < lt_max) ++code_bits;
-                char who[64];
-                if (lt_gpw == 1) snprintf(who, sizeof(who), "workgroup %d", lt_max_grp);
-                else snprintf(who, sizeof(who), "wave %d of workgroup %d", lt_max_grp % 16, lt_max_grp / 16);
-                char msg[256];
-                if (lt_max > lt_cap)
-                    snprintf(msg, sizeof(msg), "local table of %s has more than %d distinct values", who, lt_cap);
-                else if (code_bits + lc_bits > kResWordBits)
-                    snprintf(msg, sizeof(msg), "local table of %s (%d values) needs %d code bits, %d left by the %d column bits of the %d-bit word", who,
-                             lt_max, code_bits, kResWordBits - lc_bits, lc_bits, kResWordBits);
-                else {
-                    for (int b = 0; b < G; ++b) {
-                        int t = 0;
-                        for (int g = 0; g < lt_gpw; ++g) t += tcnt[(size_t)b * lt_gpw + g];
-                        tabs[(size_t)b] = (t + 1) & ~1;
-                    }
-                    return 0;
-                }
-                lt_why = msg;
-                if (verbose) fprintf(stderr, "[avs resident] local tables per %s: %s\n", lt_gpw == 1 ? "workgroup" : "wave", msg);
-            }
-            return 2;
-        };
-        auto remap = [&]() -> int { // 0 ok, 1 a source list overflowed, 2 the local tables do not fit the word, -1 failure
-            if (lt)
-                hipLaunchKernelGGL(k_resident_remap<true>, dim3((unsigned)G), dim3(kResThreads), remap_lds, stream, (const uint32_t *)nullptr, A.col,
-                                   A.row_ptr, 0, lc_bits, (const int32_t *)pl->wg_row0.p, cap, (int)n_ext, pl->rwords.p, pl->rem_list.p,
-                                   pl->rem_count.p, fail.p, (int)n, pl->dep_mask.p, (int)chunk_cols);
-            else
-                hipLaunchKernelGGL(k_resident_remap<false>, dim3((unsigned)G), dim3(kResThreads), remap_lds, stream, A.packed, (const int32_t *)nullptr,
-                                   A.row_ptr, A.col_bits, lc_bits, (const int32_t *)pl->wg_row0.p, cap, (int)n_ext, pl->rwords.p, pl->rem_list.p,
-                                   pl->rem_count.p, fail.p, (int)n, pl->dep_mask.p, (int)chunk_cols);
-            int f = 0;
-            if (hipMemcpyAsync(&f, fail.p, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                hipMemcpyAsync(rc.data(), pl->rem_count.p, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                hipStreamSynchronize(stream) != hipSuccess) {
-                (void)hipGetLastError();
-                return -1;
-            }
-            if (f) return 1;
-            if (!lt) return 0;
-            const int t = local_tables();
-            if (t < 0) (void)hipGetLastError();
-            return t;
-        };
-        // (round 0 of a later tier is the split of the first tier's round 0: its counts are re-used, the words re-encoded only if it is accepted)
-        reuse_round0 = round == 0 && round0_done && !cur_opt().resident_equal_lanes && !lt; // (local tables belong to ONE split)
-        if (reuse_round0) rc = rc_round0;
-        else {
-            const int rm = remap();
-            if (rm < 0) return no("remap failed");
-            if (rm == 2) return no(lt_why.c_str());
-            if (rm > 0) { last_reason = "a workgroup reads more remote columns than its source list holds"; give_up = true; break; }
-        }
-        if (round == 0) {
-            if (!reuse_round0) { rc_round0 = rc; round0_done = true; }
-            // a tier whose TOTAL demand is close to the chip's LDS never fits (lanes, not LDS, bound the split; every further round is a
-            // re-encoding pass: 10 ms of plan time on a 1.3 M-row system): next tier
-            const int t = max_ng < 3 ? (max_ng < 0 ? 0 : max_ng) : 3;
-            const double limit0 = (double)(lds_max - lds_extra) / (double)esz;
-            double demand = 0.;
-            for (int b = 0; b < G; ++b) demand += (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b] + (double)tabs[(size_t)b];
-            if (demand > 0.88 * limit0 * (double)G) { give_up = true; break; }
-        }
-        if (round == 0 && c_rem > 0. && !extras_off) { // the remote columns are known now: one more split that counts them
-            bool any = false;
-            for (int b = 0; b < G; ++b) {
-                const int64_t lanes_b = wl[(size_t)b + 1] - wl[(size_t)b];
-                for (int64_t l = wl[(size_t)b]; l < wl[(size_t)b + 1]; ++l) {
-                    any = any || lane_extra[(size_t)l] == 0.;
-                    lane_extra[(size_t)l] = c_rem * (double)rc[(size_t)b] / (double)(lanes_b > 0 ? lanes_b : 1);
-                }
-            }
-            if (any) { extras_active = true; continue; }
-        }
-        // LDS split: every workgroup holds its slice of u + its remote-column cache, and as many of r, p, s as still fit (tiers: NG =
-        // 0 .. 3 of them in global memory instead).  Footprint of workgroup b: (4 - NG) rows_b + remote_b doubles; the largest decides.
-        const size_t extra = lds_extra;
-        max_cols = 0;
-        for (int t = 0; t <= 3 && t <= max_ng && ng < 0; ++t) {
-            size_t worst = 0;
-            for (int b = 0; b < G; ++b) {
-                const size_t rows_b = (size_t)((wr[(size_t)b + 1] - wr[(size_t)b] + 1) & ~1), rem_b = (size_t)((rc[(size_t)b] + 1) & ~1);
-                worst = std::max(worst, (size_t)(4 - t) * rows_b + rem_b + (size_t)tabs[(size_t)b]);
-                max_cols = std::max(max_cols, (int)(rows_b + rem_b));
-            }
-            const size_t need = worst * esz + extra;
-            if (verbose) fprintf(stderr, "[avs resident] round %d, LDS tier %d: largest workgroup footprint %zu B (limit %zu)\n", round, t, need, lds_max);
-            if (need <= lds_max) { ng = t; lds = need; }
-        }
-        if (ng >= 0 && reuse_round0) { // accepted on re-used counts: the words still hold another split's encoding
-            const int rm = remap();
-            if (rm == 2) return no(lt_why.c_str());
-            if (rm != 0) return no("remap failed");
-        }
-        if (ng < 0) { // shrink the offenders (at the largest tier allowed) and split again
-            const int t = max_ng < 3 ? (max_ng < 0 ? 0 : max_ng) : 3;
-            const double limit = (double)(lds_max - extra) / (double)esz;
-            { // ... unless the MEDIAN workgroup does not fit either: no re-split helps, go to the next tier
-                std::vector<double> fps((size_t)G);
-                for (int b = 0; b < G; ++b)
-                    fps[(size_t)b] = (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b] + (double)tabs[(size_t)b];
-                std::nth_element(fps.begin(), fps.begin() + G / 2, fps.end());
-                if (fps[(size_t)G / 2] > 0.98 * limit) { give_up = true; break; }
-            }
-            for (int b = 0; b < G; ++b) {
-                const double fp = (double)(4 - t) * (double)(wr[(size_t)b + 1] - wr[(size_t)b]) + (double)rc[(size_t)b] + (double)tabs[(size_t)b];
-                if (fp > 0.97 * limit) {
-                    reweighted = true;
-                    for (int64_t l = wl[(size_t)b]; l < wl[(size_t)b + 1]; ++l) lane_w[(size_t)l] *= 1.12 * fp / limit;
-                }
-            }
-        }
-    }
-    }
-    stage("split + re-encoding rounds");
+    if (const char *why = resident_split_setup(s, n_cols, stream_T)) return no(why);
+    ResidentTier tier;
+    if (const char *why = resident_split_rounds(s, stream_T, esz, lds_max, lds_extra, &tier)) return no(why);
+    clock.stage("split + re-encoding rounds");
+    const int ng = tier.ng, max_rows = s.split.max_rows;
     pl->max_rows = max_rows;
-    pl->max_remote = *std::max_element(rc.begin(), rc.end());
-    pl->lt_max = lt_max;
+    pl->max_remote = *std::max_element(s.rc.begin(), s.rc.end());
+    pl->lt_max = s.lt_max;
     if (verbose) {
-        std::vector<int32_t> srt(rc);
+        std::vector<int32_t> srt(s.rc);
         std::sort(srt.begin(), srt.end());
         fprintf(stderr, "[avs resident] remote columns per workgroup: min %d / median %d / 90 %% %d / max %d; rows per workgroup <= %d\n", srt[0],
                 srt[(size_t)G / 2], srt[(size_t)G * 9 / 10], srt[(size_t)G - 1], max_rows);
     }
     if (ng < 0) {
-        if (lt && lt_max > 0) { // the quantity that did not fit: the LDS, with the tables it would have had to hold
+        if (lt && s.lt_max > 0) { // the quantity that did not fit: the LDS, with the tables it would have had to hold
             char msg[256];
-            snprintf(msg, sizeof(msg), "%s (local tables per %s, largest %d values, up to %d table entries per workgroup)", last_reason,
-                     lt_gpw == 1 ? "workgroup" : "wave", lt_max, *std::max_element(tabs.begin(), tabs.end()));
-            lt_why = msg;
-            return no(lt_why.c_str());
+            snprintf(msg, sizeof(msg), "%s (local tables per %s, largest %d values, up to %d table entries per workgroup)", tier.last_reason,
+                     s.lt_gpw == 1 ? "workgroup" : "wave", s.lt_max, *std::max_element(s.tabs.begin(), s.tabs.end()));
+            return no(msg);
         }
-        return no(last_reason);
+        return no(tier.last_reason);
     }
+
+    // ---- 6. the accepted plan: tables, kernel, partition arrays, uploads, streams ----
     if (lt && verbose)
         fprintf(stderr, "[avs resident] local tables: one per %s, largest %d values (%s %d%s), %d code bits + %d column bits of %d, LDS tier %d, "
-                        "<= %d table entries per workgroup, inverse diagonal per row (no LDS)\n", lt_gpw == 1 ? "workgroup" : "wave", lt_max,
-                lt_gpw == 1 ? "workgroup" : "wave", lt_gpw == 1 ? lt_max_grp : lt_max_grp % 16,
-                lt_gpw == 1 ? "" : (" of workgroup " + std::to_string(lt_max_grp / 16)).c_str(), code_bits, lc_bits, kResWordBits, ng,
-                *std::max_element(tabs.begin(), tabs.end()));
-    if ((1 << lc_bits) < max_cols) return no("rows + remote columns exceed the word's column bits");
-    if (lt) { // the tables of the accepted split, back to back
-        std::vector<int32_t> toff(tcnt.size() + 1, 0);
-        for (size_t g = 0; g < tcnt.size(); ++g) toff[g + 1] = toff[g] + tcnt[g];
-        if (pl->ltab_off.alloc(toff.size()) != AVS_OK || pl->ltab.alloc((size_t)toff.back()) != AVS_OK ||
-            hipMemcpy(pl->ltab_off.p, toff.data(), toff.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            return no("plan allocation failed");
-        }
-        hipLaunchKernelGGL(k_resident_pack_tables, dim3((unsigned)tcnt.size()), dim3(256), 0, stream, (const double *)lt_strided.p, lt_cap,
-                           (const int32_t *)pl->ltab_off.p, pl->ltab.p);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); return no("table layout failed"); }
-    }
-    lpw = 0;
+                        "<= %d table entries per workgroup, inverse diagonal per row (no LDS)\n", s.lt_gpw == 1 ? "workgroup" : "wave", s.lt_max,
+                s.lt_gpw == 1 ? "workgroup" : "wave", s.lt_gpw == 1 ? s.lt_max_grp : s.lt_max_grp % 16,
+                s.lt_gpw == 1 ? "" : (" of workgroup " + std::to_string(s.lt_max_grp / 16)).c_str(), s.code_bits, s.lc_bits, kResWordBits, ng,
+                *std::max_element(s.tabs.begin(), s.tabs.end()));
+    if ((1 << s.lc_bits) < tier.max_cols) return no("rows + remote columns exceed the word's column bits");
+    if (lt)
+        if (const char *why = resident_pack_tables(s)) return no(why);
+    const std::vector<int32_t> &wl = s.split.wl;
+    int64_t lpw = 0;
     for (int b = 0; b < G; ++b) lpw = std::max<int64_t>(lpw, wl[(size_t)b + 1] - wl[(size_t)b]);
-    const void *kern = resident_kernel(ng, stream_words > 0, f32, lt);
-    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess) {
-        (void)hipGetLastError();
-        return no("LDS opt-in refused");
-    }
+    const void *kern = resident_kernel(ng, lanes.streamed_words > 0, f32, lt);
+    if (plan_failed(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)) return no("LDS opt-in refused");
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kResThreads, lds) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
+    if (plan_failed(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kResThreads, tier.lds) != hipSuccess || per_cu < 1))
         return no("kernel does not fit a CU (registers / LDS)");
-    }
     std::vector<uint8_t> whalo((size_t)G, 0);
     std::vector<int32_t> seg(1, 0);
-    if (da && da->dd) {
-        DistDev h;
-        if (hipMemcpy(&h, da->dd, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return no("DistDev download failed"); }
-        if (h.paranoid) return no("paranoid mode keeps the launch-per-phase loop");
-        const int np = h.npeers;
-        std::vector<int32_t> sidx((size_t)(da->n_send > 0 ? da->n_send : 1));
-        if (da->n_send && hipMemcpy(sidx.data(), h.send_idx, (size_t)da->n_send * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) {
-            (void)hipGetLastError();
-            return no("send list download failed");
-        }
-        seg.assign((size_t)(np > 0 ? np : 1) * (size_t)(G + 1), 0);
-        for (int i = 0; i < np; ++i) {
-            const int32_t *lo = sidx.data() + h.send_off[i], *hi = sidx.data() + h.send_off[i + 1];
-            for (int b = 0; b <= G; ++b) {
-                const int32_t *itp = std::lower_bound(lo, hi, wr[(size_t)b]);
-                seg[(size_t)i * (G + 1) + b] = (int32_t)(itp - sidx.data());
-            }
-        }
-        pl->n_push_wgs = 0;
-        for (int b = 0; b < G; ++b) {
-            bool any = false;
-            for (int i = 0; i < np; ++i) any = any || seg[(size_t)i * (G + 1) + b + 1] > seg[(size_t)i * (G + 1) + b];
-            pl->n_push_wgs += any ? 1 : 0;
-        }
-        // workgroups that read halo columns wait for the peers' flags: every workgroup overlapping a halo-reading 512-row tile of the plan
-        std::vector<int32_t> tb((size_t)(da->n_tiles_bnd > 0 ? da->n_tiles_bnd : 1));
-        if (da->n_tiles_bnd && hipMemcpy(tb.data(), da->tiles_bnd, (size_t)da->n_tiles_bnd * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) {
-            (void)hipGetLastError();
-            return no("tile list download failed");
-        }
-        for (int t = 0; t < da->n_tiles_bnd; ++t) {
-            const int64_t r0 = (int64_t)tb[(size_t)t] * kTileRows, r1 = std::min<int64_t>(r0 + kTileRows, n);
-            for (int b = 0; b < G; ++b)
-                if (wr[(size_t)b] < r1 && wr[(size_t)b + 1] > r0) whalo[(size_t)b] = 1;
-        }
-    }
-    bool up = pl->lane_row0.alloc((size_t)L) == AVS_OK && pl->lane_meta.alloc((size_t)L) == AVS_OK && pl->wg_lane0.alloc((size_t)G + 1) == AVS_OK &&
-              pl->push_seg.alloc(seg.size()) == AVS_OK && pl->wg_halo.alloc((size_t)G) == AVS_OK && pl->bar_count.alloc(2) == AVS_OK &&
-              pl->bar_flags.alloc((size_t)G) == AVS_OK && pl->slots.alloc((size_t)G * 4) == AVS_OK && pl->bcast.alloc(4 * kResGens) == AVS_OK;
-    if (!up) return no("plan allocation failed");
-    up = hipMemcpy(pl->lane_row0.p, lrow.data(), (size_t)L * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(pl->lane_meta.p, lmeta.data(), (size_t)L * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(pl->wg_lane0.p, wl.data(), wl.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(pl->push_seg.p, seg.data(), seg.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(pl->wg_halo.p, whalo.data(), whalo.size(), hipMemcpyHostToDevice) == hipSuccess;
-    if (!up) { (void)hipGetLastError(); return no("plan upload failed"); }
-    stage("push segments, uploads");
+    if (da && da->dd)
+        if (const char *why = resident_partition_arrays(pl, da, s.split.wr, n, &seg, &whalo)) return no(why);
+    if (const char *why = resident_upload(pl, lanes, wl, seg, whalo)) return no(why);
+    clock.stage("push segments, uploads");
     pl->streams = false;
-    if (stream_words > 0) { // the waves' lane-interleaved streams of the rows that do not fit the registers
-        const int wpg = kResThreads / 64;
-        std::vector<int32_t> soff((size_t)G * wpg + 1, 0);
+    if (lanes.streamed_words > 0) {
         int64_t run = 0;
-        for (int b = 0; b < G; ++b)
-            for (int w = 0; w < wpg; ++w) {
-                int mx = 0;
-                for (int64_t l = (int64_t)wl[(size_t)b] + 64 * w; l < std::min<int64_t>((int64_t)wl[(size_t)b] + 64 * (w + 1), wl[(size_t)b + 1]); ++l)
-                    mx = std::max(mx, lane_sw[(size_t)l]);
-                soff[(size_t)b * wpg + w] = (int32_t)run;
-                run += 64 * (int64_t)mx;
-            }
-        soff[(size_t)G * wpg] = (int32_t)run;
-        if (run >= (1ll << 29)) return no("streamed quads exceed 32-bit offsets");
-        if (pl->swords.alloc((size_t)run * 4) != AVS_OK || pl->wave_soff.alloc(soff.size()) != AVS_OK ||
-            hipMemcpy(pl->wave_soff.p, soff.data(), soff.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            return no("stream allocation failed");
-        }
-        hipLaunchKernelGGL(k_resident_stream_layout, dim3((unsigned)G), dim3(kResThreads), 0, stream, A.row_ptr, (const uint32_t *)pl->rwords.p,
-                           (const int32_t *)pl->lane_row0.p, (const uint32_t *)pl->lane_meta.p, (const int32_t *)pl->wg_lane0.p,
-                           (const int32_t *)pl->wave_soff.p, lt ? 0u : (uint32_t)A.table_size << lc_bits, reinterpret_cast<u4_t *>(pl->swords.p));
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipGetLastError(); return no("stream layout failed"); }
+        if (const char *why = resident_stream_layout(s, lt ? 0u : (uint32_t)A.table_size << s.lc_bits, &run)) return no(why);
         pl->streams = true;
         if (verbose)
             fprintf(stderr, "[avs resident] streamed rows: %.1f %% of the words (%lld of %lld), %.1f MB per iteration incl. padding, %.1f streamed quads per lane\n",
-                    100. * (double)stream_words / (double)A.nnz, (long long)stream_words, (long long)A.nnz, (double)run * 16e-6, stream_T);
+                    100. * (double)lanes.streamed_words / (double)A.nnz, (long long)lanes.streamed_words, (long long)A.nnz, (double)run * 16e-6, stream_T);
     }
     if (verbose) {
-        timespec t1{};
-        clock_gettime(CLOCK_MONOTONIC, &t1);
-        fprintf(stderr, "[avs resident] plan built in %.2f ms (host: lanes + split; device: re-encoding)\n",
-                (t1.tv_sec - plan_t0.tv_sec) * 1e3 + (t1.tv_nsec - plan_t0.tv_nsec) * 1e-6);
-    }
-    if (verbose)
+        fprintf(stderr, "[avs resident] plan built in %.2f ms (host: lanes + split; device: re-encoding)\n", clock.total());
         fprintf(stderr, "[avs resident] plan: n = %lld, %lld lanes (%lld per workgroup), %d workgroups, <= %d rows per workgroup, %d-bit local columns, "
-                        "%d row-local vectors in global memory, LDS %zu B, %s vectors\n", (long long)n, (long long)L, (long long)lpw, G, max_rows, lc_bits, ng, lds,
-                f32 ? "float" : "fp64");
+                        "%d row-local vectors in global memory, LDS %zu B, %s vectors\n", (long long)n, (long long)L, (long long)lpw, G, max_rows, s.lc_bits, ng,
+                tier.lds, f32 ? "float" : "fp64");
+    }
+
+    // ---- 7. the plan ----
     pl->G = G;
     pl->max_lanes = (int)lpw;
-    pl->lc_bits = lc_bits;
+    pl->lc_bits = s.lc_bits;
     pl->max_quads = max_quads;
     pl->ng = ng;
-    pl->lds = lds;
+    pl->lds = tier.lds;
     pl->local = lt;
-    pl->lt_gpw = lt_gpw;
+    pl->lt_gpw = s.lt_gpw;
     pl->ok = true;
     pl->why.clear();
     return true;
+}
+
+// per-phase averages of workgroup 0 (tuning aid, AVS_CG_RESIDENT_TIMERS) after a launch with a.timers set
+static avs_status resident_report_timers(ResidentPlan *pl, int khz, hipStream_t stream)
+{
+    std::vector<long long> t((size_t)pl->max_timed * kResTimers + (size_t)pl->G * 4);
+    AVS_HIP(hipMemcpyAsync(t.data(), pl->timers.p, t.size() * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    AVS_HIP(hipStreamSynchronize(stream));
+    {
+        const long long *wt = t.data() + (size_t)pl->max_timed * kResTimers;
+        std::vector<double> ua, sp, tot;
+        long long first = 0;
+        for (int b = 0; b < pl->G; ++b)
+            if (wt[4 * b + 3]) {
+                if (!first || wt[4 * b] < first) first = wt[4 * b];
+            }
+        for (int b = 0; b < pl->G; ++b)
+            if (wt[4 * b + 3]) {
+                ua.push_back((double)(wt[4 * b + 1] - wt[4 * b]) * 1e3 / khz);
+                sp.push_back((double)(wt[4 * b + 3] - wt[4 * b + 2]) * 1e3 / khz);
+                tot.push_back((double)(wt[4 * b + 3] - first) * 1e3 / khz);
+            }
+        if (!tot.empty() && cur_opt().resident_verbose > 0) {
+            std::vector<int32_t> wl2((size_t)pl->G + 1), wr2((size_t)pl->G + 1), rc2((size_t)pl->G);
+            (void)hipMemcpy(wl2.data(), pl->wg_lane0.p, wl2.size() * 4, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(wr2.data(), pl->wg_row0.p, wr2.size() * 4, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(rc2.data(), pl->rem_count.p, rc2.size() * 4, hipMemcpyDeviceToHost);
+            std::vector<int> order((size_t)pl->G);
+            for (int b = 0; b < pl->G; ++b) order[(size_t)b] = b;
+            std::sort(order.begin(), order.end(), [&](int x, int y) { return wt[4 * x + 3] > wt[4 * y + 3]; });
+            for (int i = 0; i < 4; ++i) {
+                const int b = order[(size_t)i];
+                fprintf(stderr, "[avs resident]   slow workgroup %d: %d lanes, %d rows, %d remote; update %.2f, barrier+fill %.2f, spmv %.2f us\n", b,
+                        wl2[(size_t)b + 1] - wl2[(size_t)b], wr2[(size_t)b + 1] - wr2[(size_t)b], rc2[(size_t)b], (double)(wt[4 * b + 1] - wt[4 * b]) * 1e3 / khz,
+                        (double)(wt[4 * b + 2] - wt[4 * b + 1]) * 1e3 / khz, (double)(wt[4 * b + 3] - wt[4 * b + 2]) * 1e3 / khz);
+            }
+            const int b = order[(size_t)pl->G / 2];
+            fprintf(stderr, "[avs resident]   median workgroup %d: %d lanes, %d rows, %d remote; update %.2f, barrier+fill %.2f, spmv %.2f us\n", b,
+                    wl2[(size_t)b + 1] - wl2[(size_t)b], wr2[(size_t)b + 1] - wr2[(size_t)b], rc2[(size_t)b], (double)(wt[4 * b + 1] - wt[4 * b]) * 1e3 / khz,
+                    (double)(wt[4 * b + 2] - wt[4 * b + 1]) * 1e3 / khz, (double)(wt[4 * b + 3] - wt[4 * b + 2]) * 1e3 / khz);
+        }
+        if (!ua.empty()) {
+            auto q = [](std::vector<double> v, double f) { std::sort(v.begin(), v.end()); return v[(size_t)((v.size() - 1) * f)]; };
+            fprintf(stderr, "[avs resident] iteration 20, all workgroups, us (min / median / max): update %.2f / %.2f / %.2f | spmv %.2f / %.2f / %.2f | "
+                            "SpMV done after the first workgroup started %.2f / %.2f / %.2f\n", q(ua, 0), q(ua, .5), q(ua, 1), q(sp, 0), q(sp, .5), q(sp, 1),
+                    q(tot, 0), q(tot, .5), q(tot, 1));
+        }
+    }
+    double sum[5] = {0, 0, 0, 0, 0};
+    int cnt = 0;
+    for (int i = 0; i < pl->max_timed; ++i) {
+        const long long *q = t.data() + (size_t)i * kResTimers;
+        if (!q[5]) break;
+        for (int k = 0; k < 5; ++k) sum[k] += (double)(q[k + 1] - q[k]);
+        ++cnt;
+    }
+    if (cur_opt().resident_verbose >= 2)
+        for (int i = 0; i < pl->max_timed && i < 80; ++i) {
+            const long long *q = t.data() + (size_t)i * kResTimers;
+            double rr, den;
+            memcpy(&rr, q + 6, 8);
+            memcpy(&den, q + 7, 8);
+            fprintf(stderr, "[avs resident]   it %d: |r|^2 %.6e  alpha denominator %.6e\n", i, rr, den);
+        }
+    if (cnt)
+        fprintf(stderr, "[avs resident] %d iterations of workgroup 0, us: update+push %.2f | barrier+inv+flags %.2f | remote fill %.2f | spmv+fold %.2f | "
+                        "reduce+broadcast %.2f\n", cnt, sum[0] / cnt * 1e3 / khz, sum[1] / cnt * 1e3 / khz, sum[2] / cnt * 1e3 / khz,
+                sum[3] / cnt * 1e3 / khz, sum[4] / cnt * 1e3 / khz);
+    return AVS_OK;
 }
 
 // Runs the rest of the solve (state in sc / the vectors, as the set-up rounds left it) in ONE cooperative launch.
@@ -1680,70 +1707,6 @@ static avs_status resident_run(ResidentPlan *pl, const CsrView &A, T *x, T *r, T
         return AVS_OK;
     }
     *launched = true;
-    if (a.timers) { // per-phase averages of workgroup 0 (tuning aid)
-        std::vector<long long> t((size_t)pl->max_timed * kResTimers + (size_t)pl->G * 4);
-        AVS_HIP(hipMemcpyAsync(t.data(), pl->timers.p, t.size() * sizeof(long long), hipMemcpyDeviceToHost, stream));
-        AVS_HIP(hipStreamSynchronize(stream));
-        {
-            const long long *wt = t.data() + (size_t)pl->max_timed * kResTimers;
-            std::vector<double> ua, sp, tot;
-            long long first = 0;
-            for (int b = 0; b < pl->G; ++b)
-                if (wt[4 * b + 3]) {
-                    if (!first || wt[4 * b] < first) first = wt[4 * b];
-                }
-            for (int b = 0; b < pl->G; ++b)
-                if (wt[4 * b + 3]) {
-                    ua.push_back((double)(wt[4 * b + 1] - wt[4 * b]) * 1e3 / khz);
-                    sp.push_back((double)(wt[4 * b + 3] - wt[4 * b + 2]) * 1e3 / khz);
-                    tot.push_back((double)(wt[4 * b + 3] - first) * 1e3 / khz);
-                }
-            if (!tot.empty() && cur_opt().resident_verbose > 0) {
-                std::vector<int32_t> wl2((size_t)pl->G + 1), wr2((size_t)pl->G + 1), rc2((size_t)pl->G);
-                (void)hipMemcpy(wl2.data(), pl->wg_lane0.p, wl2.size() * 4, hipMemcpyDeviceToHost);
-                (void)hipMemcpy(wr2.data(), pl->wg_row0.p, wr2.size() * 4, hipMemcpyDeviceToHost);
-                (void)hipMemcpy(rc2.data(), pl->rem_count.p, rc2.size() * 4, hipMemcpyDeviceToHost);
-                std::vector<int> order((size_t)pl->G);
-                for (int b = 0; b < pl->G; ++b) order[(size_t)b] = b;
-                std::sort(order.begin(), order.end(), [&](int x, int y) { return wt[4 * x + 3] > wt[4 * y + 3]; });
-                for (int i = 0; i < 4; ++i) {
-                    const int b = order[(size_t)i];
-                    fprintf(stderr, "[avs resident]   slow workgroup %d: %d lanes, %d rows, %d remote; update %.2f, barrier+fill %.2f, spmv %.2f us\n", b,
-                            wl2[(size_t)b + 1] - wl2[(size_t)b], wr2[(size_t)b + 1] - wr2[(size_t)b], rc2[(size_t)b], (double)(wt[4 * b + 1] - wt[4 * b]) * 1e3 / khz,
-                            (double)(wt[4 * b + 2] - wt[4 * b + 1]) * 1e3 / khz, (double)(wt[4 * b + 3] - wt[4 * b + 2]) * 1e3 / khz);
-                }
-                const int b = order[(size_t)pl->G / 2];
-                fprintf(stderr, "[avs resident]   median workgroup %d: %d lanes, %d rows, %d remote; update %.2f, barrier+fill %.2f, spmv %.2f us\n", b,
-                        wl2[(size_t)b + 1] - wl2[(size_t)b], wr2[(size_t)b + 1] - wr2[(size_t)b], rc2[(size_t)b], (double)(wt[4 * b + 1] - wt[4 * b]) * 1e3 / khz,
-                        (double)(wt[4 * b + 2] - wt[4 * b + 1]) * 1e3 / khz, (double)(wt[4 * b + 3] - wt[4 * b + 2]) * 1e3 / khz);
-            }
-            if (!ua.empty()) {
-                auto q = [](std::vector<double> v, double f) { std::sort(v.begin(), v.end()); return v[(size_t)((v.size() - 1) * f)]; };
-                fprintf(stderr, "[avs resident] iteration 20, all workgroups, us (min / median / max): update %.2f / %.2f / %.2f | spmv %.2f / %.2f / %.2f | "
-                                "SpMV done after the first workgroup started %.2f / %.2f / %.2f\n", q(ua, 0), q(ua, .5), q(ua, 1), q(sp, 0), q(sp, .5), q(sp, 1),
-                        q(tot, 0), q(tot, .5), q(tot, 1));
-            }
-        }
-        double sum[5] = {0, 0, 0, 0, 0};
-        int cnt = 0;
-        for (int i = 0; i < pl->max_timed; ++i) {
-            const long long *q = t.data() + (size_t)i * kResTimers;
-            if (!q[5]) break;
-            for (int k = 0; k < 5; ++k) sum[k] += (double)(q[k + 1] - q[k]);
-            ++cnt;
-        }
-        if (cur_opt().resident_verbose >= 2)
-            for (int i = 0; i < pl->max_timed && i < 80; ++i) {
-                const long long *q = t.data() + (size_t)i * kResTimers;
-                double rr, den;
-                memcpy(&rr, q + 6, 8);
-                memcpy(&den, q + 7, 8);
-                fprintf(stderr, "[avs resident]   it %d: |r|^2 %.6e  alpha denominator %.6e\n", i, rr, den);
-            }
-        if (cnt)
-            fprintf(stderr, "[avs resident] %d iterations of workgroup 0, us: update+push %.2f | barrier+inv+flags %.2f | remote fill %.2f | spmv+fold %.2f | "
-                            "reduce+broadcast %.2f\n", cnt, sum[0] / cnt * 1e3 / khz, sum[1] / cnt * 1e3 / khz, sum[2] / cnt * 1e3 / khz,
-                    sum[3] / cnt * 1e3 / khz, sum[4] / cnt * 1e3 / khz);
-    }
+    if (a.timers) AVS_TRY(resident_report_timers(pl, khz, stream));
     return AVS_OK;
 }

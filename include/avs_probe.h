@@ -78,6 +78,30 @@ avs_status avs_pcg_csr_plan(int64_t n, const int32_t *row_ptr, const int32_t *co
                             double tol, int32_t max_iters, avs_memspace where, int32_t device, void *stream, avs_solve_info *info,
                             avs_resident_plan_info *plan);
 
+/* The host half of that plan (csrc/avs_resident_plan.cpp) on HOST row pointers, without a device and without a HIP call: the lanes of the
+ * n rows for `workgroups` workgroups with max_quads register quads per lane (1 .. 15), lane_fill and no_stream as AVS_CG_RESIDENT_LANE_FILL
+ * (default 0.90) and AVS_CG_RESIDENT_NO_STREAM give them, then the plan's first split of the lanes into workgroups: by estimated time with
+ * stream_cost (AVS_CG_RESIDENT_STREAM_COST, default 1.5) and no remote-column term, equal lanes where the clip at 1,024 lanes leaves some over.
+ * lane_row0, lane_meta (register rows | streamed rows << 3 | a long row's words left in memory << 10) and lane_stream_quads have room for
+ * n lanes, the first info->lanes are written; wg_lane0 and wg_row0 have workgroups + 1 entries.  A refusal of the planner is AVS_OK with
+ * info->refused = 1 and its text in info->why; the arrays are not written then. */
+typedef struct {
+    int32_t struct_size;
+    int32_t refused;
+    int64_t lanes;
+    int32_t long_row_lanes;
+    int32_t longest_tail;
+    int32_t max_lane_streamed_rows;
+    int32_t max_rows_per_workgroup;
+    int64_t streamed_rows;
+    int64_t streamed_words;
+    double stream_T;                /* streamed quads per lane the lanes were formed with (0: registers only) */
+    char why[128];
+} avs_resident_host_plan_info;
+avs_status avs_resident_plan_host(int64_t n, const int32_t *row_ptr, int32_t workgroups, int32_t max_quads, double lane_fill, int32_t no_stream,
+                                  double stream_cost, int32_t *lane_row0, uint32_t *lane_meta, int32_t *lane_stream_quads, int32_t *wg_lane0,
+                                  int32_t *wg_row0, avs_resident_host_plan_info *info);
+
 /* Measurement: load balance of the brick kernel's row walk -- per G tile the quads of the slowest of the eight waves against the mean wave
  * (printed to stderr; out6 = {tiles, rows per tile, quads per row, slowest-wave quads, mean-wave quads, 0}) */
 avs_status avs_brick_wave_stats(avs_ctx *ctx, double *out6);

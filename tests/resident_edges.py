@@ -1,4 +1,5 @@
-"""Named small systems at the edges of the CU-resident PCG plan (resident_prepare, csrc/avs_pcg_resident.inl), for seam A.
+"""Named small systems at the edges of the CU-resident PCG plan (resident_prepare, csrc/avs_pcg_resident.inl, driving the host planner
+csrc/avs_resident_plan.cpp), for seam A.
 
 The plan gives every lane of a 1024-lane workgroup up to 6 consecutive rows in 15 register quads of 5 words (a row takes whole quads; a
 row of more than W = 75 words sits alone and leaves its tail in memory), streams the rows that do not fit once the lanes exceed 93 % of
@@ -139,7 +140,8 @@ def row_lengths(case_or_rp):
 
 
 def lanes_in_registers(lens, max_quads=QUADS):
-    """(lanes, long-row lanes, longest tail) of a plan without streamed rows: form_lanes(0.) of resident_prepare restated"""
+    """(lanes, long-row lanes, longest tail) of a plan without streamed rows: form_lanes(T = 0) of csrc/avs_resident_plan.cpp restated
+    (tests/test_resident_plan_host.py compares the two without a GPU)"""
     w = max_quads * QUAD_WORDS
     lanes = long_lanes = tail = 0
     i, n = 0, len(lens)
