@@ -65,7 +65,8 @@ ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_v
 # include/avs_probe.h: exported by libavs_probe.so only (the -DAVS_PROBES build of the same sources)
 PROBE_SYMBOLS = ["avs_spmv_csr", "avs_bench_spmv", "avs_spmv_sell", "avs_bench_stream", "avs_brick_spmv_probe", "avs_spmv_solver_form",
                  "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe", "avs_pcg_csr_plan",
-                 "avs_merge_triplets_probe", "avs_exclusive_scan_probe", "avs_resident_plan_host"]
+                 "avs_merge_triplets_probe", "avs_exclusive_scan_probe", "avs_resident_plan_host", "avs_brick_form_probe"]
+BRICK_PROBE_FUSED_DOT, BRICK_PROBE_F32, BRICK_PROBE_MIXED, BRICK_PROBE_VALUE_CODES, BRICK_PROBE_DONE = 1, 2, 4, 8, 16   # avs_brick_form_probe flags
 VECTOR_PROBE_F32, VECTOR_PROBE_DS, VECTOR_PROBE_CODED, VECTOR_PROBE_KEEP, VECTOR_PROBE_FUSED = 1, 2, 4, 8, 16   # avs_vector_update_probe flags
 SPMV_FORM_FUSED_DOT, SPMV_FORM_F32, SPMV_FORM_NO_CACHE_HINT = 1, 2, 4   # avs_spmv_csr_form flags (include/avs_probe.h)
 _VOID_RETURN = ("avs_last_error", "avs_version", "avs_destroy", "avs_plan_destroy", "avs_local_group_destroy",
@@ -170,6 +171,19 @@ class TripletMergeInfo(C.Structure):
         self.struct_size = C.sizeof(TripletMergeInfo)
 
 
+class BrickFormInfo(C.Structure):
+    """avs_brick_form_info (include/avs_probe.h): the limits of the brick-structured SpMV form and what an avs_brick_form_probe build made"""
+    _fields_ = [("struct_size", C.c_int32)] + [(k, C.c_int32) for k in (
+        "run_len", "max_runs", "fast_runs", "pat_max", "pat_words", "pat_words_vc", "pat_len", "x_slots", "park_words", "emode_words",
+        "emode_words_mixed", "min_rows", "max_rows", "etile_rows", "tile_vals", "table_max", "block_words", "header_words",
+        "ready", "vc", "wide", "col_bits", "tiles", "patterns", "halo_tiles", "grid", "max_walk", "planned", "table_size", "reserved")] + [
+        ("pattern_rows", C.c_int64), ("streamed_rows", C.c_int64), ("streamed_words", C.c_int64)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(BrickFormInfo)
+
+
 def source_fingerprint():
     """sha256 (16 hex digits) over the library's sources: kernels, internal headers, the public header.  Counter records under
     profiles/ carry the fingerprint of the tree they were taken with; bench.py only quotes a record whose fingerprint is the running one."""
@@ -250,6 +264,8 @@ def load(probe=False):
         L.avs_merge_triplets_probe.argtypes = [i64, vp, vp, vp, i32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(TripletMergeInfo), vp]
         L.avs_exclusive_scan_probe.argtypes = [vp, vp, i64, vp]
         L.avs_resident_plan_host.argtypes = [i64, vp, i32, i32, f64, i32, f64, vp, vp, vp, vp, vp, C.POINTER(ResidentHostPlanInfo)]
+        L.avs_brick_form_probe.argtypes = [i64, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(f64), vp, i32,
+                                           C.POINTER(BrickFormInfo), vp, i32, vp]
     L.avs_prepass_create.argtypes = [C.POINTER(PrepassDesc), C.POINTER(vp)]
     L.avs_prepass_destroy.argtypes = [vp]
     L.avs_prepass_destroy.restype = None
@@ -323,6 +339,13 @@ def resident_plan_host(row_ptr, workgroups, max_quads=15, lane_fill=0.90, no_str
         return info, None
     L = int(info.lanes)
     return info, {"row0": row0[:L], "meta": meta[:L], "stream_quads": quads[:L], "wl": wl, "wr": wr}
+
+
+def brick_form_limits():
+    """avs_brick_form_probe's limits-only call (libavs_probe.so, no GPU): the constants the brick form and its kernel were compiled with"""
+    info = BrickFormInfo()
+    check(load_probe().avs_brick_form_probe(0, 0, None, None, None, None, 0, 0, 0, 0, None, None, 0, 0, 0, None, None, 0, C.byref(info), None, 0, None))
+    return info
 
 
 def check(status):

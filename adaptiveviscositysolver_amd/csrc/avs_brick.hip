@@ -651,6 +651,9 @@ static const void *brick_kernel(bool dot, bool vc)
 // persistent grid: as many workgroups as the device keeps resident for THIS LDS size (a larger value table costs a workgroup per CU;
 // the float kernel's lattice is half as large: four per CU); queried once per (device, LDS size, variant), guarded: contexts of several
 // host threads share the cache
+#ifdef AVS_PROBES
+static thread_local int tl_probe_grid = 0;
+#endif
 static int brick_grid(const BrickView &B, size_t lds, int elem_bytes, int val_bytes = 0)
 {
     if (val_bytes == elem_bytes) val_bytes = 0;
@@ -678,6 +681,7 @@ static int brick_grid(const BrickView &B, size_t lds, int elem_bytes, int val_by
     }
 #ifdef AVS_PROBES
     if (const char *e = getenv("AVS_BRICK_GRID")) g = atoi(e) > 0 ? atoi(e) : g;
+    if (tl_probe_grid > 0) g = tl_probe_grid; // avs_brick_form_probe: the persistent grid as an argument
 #endif
     return g < B.ntiles ? g : B.ntiles;
 }
@@ -831,6 +835,241 @@ extern "C" avs_status avs_brick_spmv_probe(const avs_brick_arrays *a, const doub
     const double ms = t.stop() / repeats;
     if (ms_per_launch) *ms_per_launch = ms;
     if (B.debug & 16) avs::brick_print_stamps();
+    return AVS_OK;
+}
+
+namespace avs {
+namespace {
+__global__ void k_bfp_narrow(int64_t n, const double *__restrict__ src, float *__restrict__ dst)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = (float)src[i];
+}
+__global__ void k_bfp_widen(int64_t n, const float *__restrict__ src, double *__restrict__ dst)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = (double)src[i];
+}
+__global__ void k_bfp_iota(int64_t n, int32_t *__restrict__ dst)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = (int32_t)i;
+}
+struct ProbeGridScope { // the persistent grid of avs_brick_form_probe, for the launches and counts of this call
+    explicit ProbeGridScope(int g) { tl_probe_grid = g; }
+    ~ProbeGridScope() { tl_probe_grid = 0; }
+};
+// most tiles a workgroup of the strided walks takes: the kernel's tile -> workgroup rule, on the host
+int brick_probe_max_walk(int ntiles, int grid, int walk)
+{
+    int most = 0;
+    for (int b = 0; b < grid; ++b) {
+        int tile = b, tstep = grid, tend = ntiles;
+        if ((grid & 7) == 0 && ntiles >= grid) {
+            const int c = b & 7, gx = grid >> 3;
+            tile = c * gx + (b >> 3);
+            if (walk == 0) {
+                tstep = gx;
+                tile = (int)(((int64_t)ntiles * c) >> 3) + (b >> 3);
+                tend = (int)(((int64_t)ntiles * (c + 1)) >> 3);
+            }
+        }
+        const int cnt = tile < tend ? (tend - tile + tstep - 1) / tstep : 0;
+        most = std::max(most, cnt);
+    }
+    return most;
+}
+} // namespace
+} // namespace avs
+
+extern "C" avs_status avs_brick_form_probe(int64_t n_rows, int64_t n_cols, const int32_t *row_ptr, const int32_t *col, const double *val,
+                                           const int32_t *dof, int32_t nx, int32_t ny, int32_t nz, int32_t levels, const double *x, double *y,
+                                           int32_t flags, int32_t grid, int32_t walk, double *dot_out, double *partials,
+                                           int32_t partial_capacity, avs_brick_form_info *info, int32_t *headers, int32_t header_capacity,
+                                           void *stream)
+{
+    using namespace avs;
+    OptScope opt_scope_(nullptr); // context-free entry: the environment as it is now
+    AVS_REQUIRE(info && info->struct_size >= (int32_t)sizeof(avs_brick_form_info), AVS_EINVAL,
+                "avs_brick_form_info.struct_size must be set to sizeof(avs_brick_form_info) before the call");
+    {
+        constexpr int RL = kBrickRunLen;
+        const int32_t size = info->struct_size;
+        memset(info, 0, sizeof(*info));
+        info->struct_size = size;
+        info->run_len = kBrickRunLen;
+        info->max_runs = kBrickMaxRuns;
+        info->fast_runs = (AVS_BRICK_RUFAST) * (kBrickBlk / RL);
+        info->pat_max = kBrickPatMax;
+        info->pat_words = kBrickPatWords;
+        info->pat_words_vc = kBrickPatWordsVc;
+        info->pat_len = kBrickPatLen;
+        info->x_slots = kBrickXSlots;
+        info->park_words = kBrickPark - kBrickXSlots;
+        info->emode_words = kBrickSlotsPad;
+        info->emode_words_mixed = (int32_t)(kBrickSlotsPad * sizeof(float) / sizeof(double));
+        info->min_rows = kBrickMinRows;
+        info->max_rows = kBrickMaxRows;
+        info->etile_rows = kBrickETileRows;
+        info->tile_vals = kBrickTileVals;
+        info->table_max = kBrickTableMax;
+        info->block_words = kBrickBlockStride;
+        info->header_words = kBlkHdrWords;
+    }
+    if (n_rows == 0 && !row_ptr) return AVS_OK; // the limits only: no device
+    AVS_REQUIRE(n_rows > 0 && n_cols >= n_rows && n_cols < (1ll << 31) - 64 && row_ptr && col && val && dof && x && y, AVS_EINVAL, "bad argument");
+    AVS_REQUIRE(nx > 0 && ny > 0 && nz > 0 && nx <= 1024 && ny <= 1024 && nz <= 1024 && levels >= 1 && levels <= 8, AVS_EINVAL, "bad grid");
+    constexpr int kAll = AVS_BRICK_PROBE_FUSED_DOT | AVS_BRICK_PROBE_F32 | AVS_BRICK_PROBE_MIXED | AVS_BRICK_PROBE_VALUE_CODES | AVS_BRICK_PROBE_DONE;
+    AVS_REQUIRE((flags & ~kAll) == 0, AVS_EINVAL, "unknown flags 0x%x", (unsigned)flags);
+    AVS_REQUIRE(!((flags & AVS_BRICK_PROBE_F32) && (flags & AVS_BRICK_PROBE_MIXED)), AVS_EINVAL, "F32 and MIXED exclude each other");
+    AVS_REQUIRE(!(flags & AVS_BRICK_PROBE_DONE) || (flags & AVS_BRICK_PROBE_FUSED_DOT), AVS_EINVAL, "DONE needs FUSED_DOT: only that instantiation reads the flag");
+    AVS_REQUIRE(grid >= 0 && grid <= 4096 && walk >= 0 && walk <= 2, AVS_EINVAL, "grid %d or walk %d out of range", grid, walk);
+    AVS_REQUIRE(!partials || partial_capacity > 0, AVS_EINVAL, "partials without a capacity");
+    const bool fused = (flags & AVS_BRICK_PROBE_FUSED_DOT) != 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // ---- the input is checked on the host before anything is launched on it
+    std::vector<int32_t> hrp((size_t)n_rows + 1), hdof((size_t)n_cols * 4);
+    AVS_HIP(hipMemcpyAsync(hrp.data(), row_ptr, hrp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AVS_HIP(hipMemcpyAsync(hdof.data(), dof, hdof.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AVS_HIP(hipStreamSynchronize(st));
+    AVS_REQUIRE(hrp[0] == 0, AVS_EINVAL, "row_ptr[0] must be 0");
+    for (int64_t r = 0; r < n_rows; ++r)
+        AVS_REQUIRE(hrp[(size_t)r + 1] > hrp[(size_t)r], AVS_EINVAL, "row %lld is empty (or row_ptr decreases): the brick kernel does not write y for it", (long long)r);
+    const int64_t nnz = hrp[(size_t)n_rows];
+    {
+        std::vector<int32_t> hcol((size_t)nnz);
+        AVS_HIP(hipMemcpyAsync(hcol.data(), col, hcol.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        AVS_HIP(hipStreamSynchronize(st));
+        for (int64_t k = 0; k < nnz; ++k)
+            AVS_REQUIRE(hcol[(size_t)k] >= 0 && hcol[(size_t)k] < n_cols, AVS_EINVAL, "entry %lld: column %d outside [0, %lld)", (long long)k, hcol[(size_t)k], (long long)n_cols);
+    }
+    {
+        const uint32_t nbx = (uint32_t)((nx + 7) >> 3), nby = (uint32_t)((ny + 7) >> 3);
+        uint32_t prev = 0;
+        for (int64_t c = 0; c < n_cols; ++c) {
+            const int32_t *rec = &hdof[(size_t)c * 4];
+            const int level = rec[0] & 0xff, axis = (rec[0] >> 8) & 0xff;
+            AVS_REQUIRE((rec[0] >> 16) == 0 && level <= 7 && level < levels && axis <= 2 && rec[1] >= 0 && rec[1] < 2048 && rec[2] >= 0 && rec[2] < 2048 && rec[3] >= 0 && rec[3] < 2048,
+                        AVS_EINVAL, "dof record %lld (level %d, axis %d, cell %d %d %d) does not fit the geometry key", (long long)c, level, axis, rec[1], rec[2], rec[3]);
+            if (c >= n_rows) continue;
+            int px = rec[1] << level, py = rec[2] << level, pz = rec[3] << level; // (the key of k_bk_geo)
+            px = px < nx ? px : nx - 1;
+            py = py < ny ? py : ny - 1;
+            pz = pz < nz ? pz : nz - 1;
+            const uint32_t brick = ((uint32_t)(pz >> 3) * nby + (uint32_t)(py >> 3)) * nbx + (uint32_t)(px >> 3);
+            AVS_REQUIRE(c == 0 || brick >= prev, AVS_EINVAL, "row %lld (brick %u) follows a row of brick %u: the rows are not brick-major", (long long)c, brick, prev);
+            prev = brick;
+        }
+    }
+    // ---- value index, form
+    ValueIndex vi, no_vi;
+    AVS_TRY(build_matrix_index(row_ptr, col, val, n_rows, nnz, n_cols, vi, st));
+    const ValueIndex &use_vi = (flags & AVS_BRICK_PROBE_VALUE_CODES) ? no_vi : vi; // no dictionary: the value-code variant
+    DevBuf<int32_t> ref_id;
+    AVS_TRY(ref_id.alloc((size_t)n_cols));
+    hipLaunchKernelGGL(k_bfp_iota, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, n_cols, ref_id.p);
+    BrickSource src;
+    src.n_rows = n_rows;
+    src.n_cols = n_cols;
+    src.nnz = nnz;
+    src.row_ptr = row_ptr;
+    src.col = col;
+    src.vi = &use_vi;
+    src.val = val;
+    src.vdof = dof;
+    src.ref_id = ref_id.p;
+    src.nx = nx; src.ny = ny; src.nz = nz;
+    src.levels = levels;
+    src.brick_shift = 3;
+    BrickForm bf;
+    const Options opt = cur_opt();
+    AVS_TRY(build_brick_form(bf, src, opt, st));
+    AVS_HIP(hipStreamSynchronize(st));
+    info->ready = bf.ready ? 1 : 0;
+    info->vc = bf.vc ? 1 : 0;
+    info->wide = bf.wide ? 1 : 0;
+    info->col_bits = use_vi.col_bits;
+    info->table_size = use_vi.table_size;
+    info->tiles = bf.ntiles;
+    info->patterns = bf.patterns;
+    info->halo_tiles = bf.halo_tiles;
+    info->pattern_rows = bf.regular_rows;
+    info->streamed_rows = bf.streamed_rows;
+    info->streamed_words = bf.streamed_words;
+    if (headers && bf.ntiles > 0 && bf.ntiles <= header_capacity) {
+        std::vector<uint2> tb((size_t)bf.ntiles);
+        AVS_HIP(hipMemcpy(tb.data(), bf.tile_blk.p, tb.size() * sizeof(uint2), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> hb((size_t)bf.ntiles * kBrickBlockStride);
+        AVS_HIP(hipMemcpy(hb.data(), bf.blocks.p, hb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int t = 0; t < bf.ntiles; ++t)
+            memcpy(headers + 16 * (size_t)t, &hb[(size_t)tb[(size_t)t].x * 4], 16 * sizeof(uint32_t));
+    }
+    if (dot_out) *dot_out = 0.;
+    if (!bf.ready) { bf.release(); return AVS_OK; }
+    // ---- the launch
+    BrickView B;
+    bf.view(B, use_vi);
+    B.walk = walk == 0 ? 0 : 1;
+    const int es = (flags & (AVS_BRICK_PROBE_F32 | AVS_BRICK_PROBE_MIXED)) ? 4 : 8;
+    B.f32 = (flags & AVS_BRICK_PROBE_F32) ? 1 : ((flags & AVS_BRICK_PROBE_MIXED) ? 2 : 0);
+    ProbeGridScope grid_scope(grid);
+    const int g = brick_partial_count(B);
+    info->grid = g;
+    info->max_walk = brick_probe_max_walk(bf.ntiles, g, B.walk);
+    if (walk == 2) {
+        AVS_TRY(bf.plan_walk(g, 1, opt.brick_cost, st));
+        if (bf.wgrid > 0) {
+            bf.view(B, use_vi);
+            B.walk = 1;
+            B.f32 = (flags & AVS_BRICK_PROBE_F32) ? 1 : ((flags & AVS_BRICK_PROBE_MIXED) ? 2 : 0);
+            info->planned = 1;
+            std::vector<int32_t> hp((size_t)g + 1);
+            AVS_HIP(hipMemcpy(hp.data(), bf.wptr.p, hp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            int most = 0;
+            for (int b = 0; b < g; ++b) most = std::max(most, hp[(size_t)b + 1] - hp[(size_t)b]);
+            info->max_walk = most;
+        }
+    }
+    DevBuf<double> dpart;
+    DevBuf<int> dflag;
+    std::vector<double> hpart;
+    if (fused) {
+        const size_t np = std::max((size_t)g, (size_t)(partials ? partial_capacity : 0));
+        AVS_REQUIRE(!partials || partial_capacity >= g, AVS_EINVAL, "%d partials do not fit a capacity of %d", g, partial_capacity);
+        hpart.assign(np, 0.);
+        if (partials) std::copy(partials, partials + partial_capacity, hpart.begin());
+        AVS_TRY(dpart.alloc(np));
+        AVS_HIP(hipMemcpyAsync(dpart.p, hpart.data(), np * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (flags & AVS_BRICK_PROBE_DONE) {
+        AVS_TRY(dflag.alloc(1));
+        const int one = 1;
+        AVS_HIP(hipMemcpyAsync(dflag.p, &one, sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    AVS_HIP(hipStreamSynchronize(st)); // (pageable sources)
+    if (es == 8) {
+        AVS_TRY(spmv_brick_launch(B, x, y, fused ? dpart.p : nullptr, dflag.p, st));
+    } else {
+        DevBuf<float> xf, yf;
+        AVS_TRY(xf.alloc((size_t)n_cols));
+        AVS_TRY(yf.alloc((size_t)n_rows));
+        hipLaunchKernelGGL(k_bfp_narrow, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, n_cols, x, xf.p);
+        hipLaunchKernelGGL(k_bfp_narrow, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, n_rows, (const double *)y, yf.p); // (DONE: y must come back as it went in)
+        if (flags & AVS_BRICK_PROBE_MIXED) AVS_TRY(spmv_brick_launch_mixed(B, xf.p, yf.p, fused ? dpart.p : nullptr, dflag.p, st));
+        else AVS_TRY(spmv_brick_launch_f32(B, xf.p, yf.p, fused ? dpart.p : nullptr, dflag.p, st));
+        hipLaunchKernelGGL(k_bfp_widen, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, n_rows, (const float *)yf.p, y);
+        AVS_HIP(hipGetLastError());
+        AVS_HIP(hipStreamSynchronize(st)); // xf, yf die here
+    }
+    if (fused) {
+        AVS_HIP(hipMemcpyAsync(hpart.data(), dpart.p, hpart.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        AVS_HIP(hipStreamSynchronize(st));
+        double s = 0.;
+        for (int b = 0; b < g; ++b) s += hpart[(size_t)b];
+        if (dot_out && !(flags & AVS_BRICK_PROBE_DONE)) *dot_out = s;
+        if (partials) std::copy(hpart.begin(), hpart.begin() + partial_capacity, partials);
+    }
+    AVS_HIP(hipStreamSynchronize(st)); // the form's arrays die here
     return AVS_OK;
 }
 #endif // AVS_PROBES

@@ -30,7 +30,7 @@ constexpr int kBlk = 256;
 constexpr int kTileBlk = 512;
 constexpr int kHashBitsPat = 21;                 // pattern hash table: 2 M slots
 constexpr int kMaxPatterns = 1 << 19;            // more distinct patterns: the scene is not regular, the form is not built
-constexpr int kBlockStride = 1728;               // words reserved per descriptor block (48 + 2 x 320 + 640 + 384 = 1712 at the limits)
+constexpr int kBlockStride = kBrickBlockStride;  // words reserved per descriptor block
 constexpr int kXsRows = kBrickXSlots;
 
 struct TileInfo {                                // built on the device from the brick starts
@@ -571,7 +571,9 @@ __global__ __launch_bounds__(kTileBlk) void k_bk_tile(const TileInfo *__restrict
             const int row = row0 + tid + k * kTileBlk;
             for (int e = row_ptr[row]; e < row_ptr[row + 1]; ++e) {
                 const int c = col[e];
-                if (c >= row0 && c < row0 + nrows) continue;
+                // the tile's own rows reach the lattice through their own slots -- except a row WITHOUT one (a face of level 4 or coarser),
+                // which another row of the tile reads through an extra slot: that slot is filled like any halo column
+                if (c >= row0 && c < row0 + nrows && eslot[e] < kBrickSlotsPad) continue;
                 smap[eslot[e]] = c; // (a slot has one column: every writer stores the same value)
             }
         }

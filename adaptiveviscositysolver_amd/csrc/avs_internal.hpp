@@ -389,6 +389,7 @@ constexpr int kCwinOffBits = 14, kCwinSlotBits = 6, kCwinSlots = 1 << kCwinSlotB
 struct ValueIndex;
 struct BrickForm;
 constexpr int kBlkHdrWords = 48;         // header of a tile's descriptor block (avs_brick.hip)
+constexpr int kBrickBlockStride = 1728;  // words reserved per descriptor block (48 + 2 x 320 + 640 + 384 = 1712 at the limits)
 constexpr int kBrickLoff[5] = {0, 3000, 3648, 3840, 3921}; // slot offsets of the level-0..3 lattices: (8>>l)+2 cells per axis, 3 faces per cell
 constexpr int kBrickSlots = 3921, kBrickSlotsPad = 3936;
 constexpr int kBrickMaxRows = 1024;   // rows per tile, two per thread (a fuller brick is cut into two tiles with one lattice origin)

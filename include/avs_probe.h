@@ -176,6 +176,70 @@ avs_status avs_merge_triplets_probe(int64_t n, const int32_t *raw_ptr, const int
  * out[n] is defined. */
 avs_status avs_exclusive_scan_probe(const int32_t *in, int32_t *out /* n + 1 */, int64_t n, void *stream);
 
+/* The brick-structured SpMV form (csrc/avs_brick_build.hip: build_brick_form(BrickForm &, const BrickSource &, ...), the function the solver
+ * and the partitioned plan call) and its kernel (csrc/avs_brick.hip: k_spmv_brick) on the CALLER's system: a device CSR of n_rows rows and
+ * n_cols >= n_rows columns (columns >= n_rows are halo columns, as in a partitioned rank's local system), one dof record per COLUMN in the
+ * int4 layout k_bk_geo reads (level | axis << 8, i, j, k; device, 4 n_cols int32), the grid nx, ny, nz (<= 1024 each) and its levels.  The
+ * rows must already be brick-major (brick ids non-decreasing): the entry uses an identity ref_id and reorders nothing.  It builds the value
+ * index as avs_spmv_csr_form does (build_matrix_index under the AVS_* environment of the call), the form under the Options of that
+ * environment (AVS_BRICK, AVS_BRICK_MIN_REGULAR, ...), and launches the kernel the loops launch: y = A x for device vectors x (n_cols
+ * doubles) and y (n_rows doubles).
+ * flags: FUSED_DOT the fused-dot instantiation (x.y folded in partial order in *dot_out; the per-workgroup partials in `partials`, a HOST
+ * array of partial_capacity doubles, may be NULL: the device array is initialised from it and copied back, so slots the launch does not
+ * write keep the caller's values); F32 the float kernel (x narrowed to float, y widened; the matrix values must be float values); MIXED
+ * k_spmv_brick<.., float, double> (x narrowed, y widened); VALUE_CODES forces the value-code variant (the form is built without a value
+ * dictionary); DONE (with FUSED_DOT only: the plain instantiation has no flag) hands the launch a device flag set to 1 -- it must leave y
+ * and the partials untouched.
+ * grid: 0 the library's default, otherwise the persistent grid (the library clamps either to the number of tiles).  walk: 0 contiguous
+ * eighths, 1 dealt chunks, 2 the planned walk (BrickForm::plan_walk for that grid over dealt chunks; it plans nothing unless the grid is a
+ * multiple of 8, at most the tiles, and every workgroup gets a tile -- info->planned says whether it did).
+ * *info (struct_size set by the caller) gets the limits the code was compiled with and what the build made; `headers` (HOST, may be NULL)
+ * the first 16 header words of every tile's descriptor block in tile-list order when tiles <= header_capacity.  With n_rows == 0 and
+ * row_ptr == NULL only the limits are filled in and nothing touches the device (the CPU tests place their cases from them).
+ * Refused with AVS_EINVAL on the host, before any launch: an empty row (the assembled systems always hold a diagonal, and the kernel does
+ * not write y for a streamed row of length 0), rows not in brick order, a column outside [0, n_cols), a dof record the geometry key cannot
+ * hold.  A form that is not ready is AVS_OK with info->ready == 0, no product, and the counts that were worked out. */
+#define AVS_BRICK_PROBE_FUSED_DOT 1
+#define AVS_BRICK_PROBE_F32 2
+#define AVS_BRICK_PROBE_MIXED 4
+#define AVS_BRICK_PROBE_VALUE_CODES 8
+#define AVS_BRICK_PROBE_DONE 16
+typedef struct {
+    int32_t struct_size;
+    /* limits */
+    int32_t run_len;          /* kBrickRunLen */
+    int32_t max_runs;         /* kBrickMaxRuns */
+    int32_t fast_runs;        /* kRuFast * QW: fill runs held in registers */
+    int32_t pat_max;          /* kBrickPatMax */
+    int32_t pat_words;        /* kBrickPatWords */
+    int32_t pat_words_vc;     /* kBrickPatWordsVc */
+    int32_t pat_len;          /* kBrickPatLen */
+    int32_t x_slots;          /* kBrickXSlots */
+    int32_t park_words;       /* kBrickPark - kBrickXSlots: streamed products per pass of a G tile */
+    int32_t emode_words;      /* ... of a tile without patterns (fp64 and float kernels) */
+    int32_t emode_words_mixed;/* ... in the mixed kernel */
+    int32_t min_rows;         /* kBrickMinRows */
+    int32_t max_rows;         /* kBrickMaxRows */
+    int32_t etile_rows;       /* kBrickETileRows */
+    int32_t tile_vals;        /* kBrickTileVals */
+    int32_t table_max;        /* kBrickTableMax */
+    int32_t block_words;      /* words reserved per descriptor block */
+    int32_t header_words;     /* kBlkHdrWords */
+    /* the build */
+    int32_t ready, vc, wide, col_bits;
+    int32_t tiles, patterns, halo_tiles;
+    int32_t grid;             /* workgroups launched */
+    int32_t max_walk;         /* most tiles any workgroup walks */
+    int32_t planned;          /* walk 2: plan_walk laid the walk out */
+    int32_t table_size;       /* of the value dictionary (0: value-code variant) */
+    int32_t reserved;
+    int64_t pattern_rows, streamed_rows, streamed_words;
+} avs_brick_form_info;
+avs_status avs_brick_form_probe(int64_t n_rows, int64_t n_cols, const int32_t *row_ptr, const int32_t *col, const double *val,
+                                const int32_t *dof, int32_t nx, int32_t ny, int32_t nz, int32_t levels, const double *x, double *y,
+                                int32_t flags, int32_t grid, int32_t walk, double *dot_out, double *partials, int32_t partial_capacity,
+                                avs_brick_form_info *info, int32_t *headers, int32_t header_capacity, void *stream);
+
 
 #ifdef __cplusplus
 }
