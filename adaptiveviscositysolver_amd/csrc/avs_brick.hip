@@ -37,6 +37,7 @@
 #include <mutex>
 
 #include "avs_internal.hpp"
+#include "avs_wave.hpp" // wave_sum_dpp: lane 63 holds the sum (fixed order)
 
 namespace avs {
 
@@ -70,24 +71,6 @@ __device__ long long g_brick_stamps[kStampWgs * kStampTiles * 8];
 #define BRICK_DBG(bit) 0
 #define BRICK_STAMP(slot) do { } while (0)
 #endif
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double brick_dpp_add(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return v + __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double brick_wave_sum_dpp(double v) // lane 63 holds the sum (fixed order)
-{
-    v = brick_dpp_add<0x111, 0xf>(v);
-    v = brick_dpp_add<0x112, 0xf>(v);
-    v = brick_dpp_add<0x114, 0xf>(v);
-    v = brick_dpp_add<0x118, 0xf>(v);
-    v = brick_dpp_add<0x142, 0xa>(v);
-    v = brick_dpp_add<0x143, 0xc>(v);
-    return v;
-}
 
 // i-th streamed row of a tile -> thread: consecutive rows go to different waves (a handful of rows per tile: every wave gets a few lanes)
 __device__ __forceinline__ int brick_srow_of_thread(int tid, int k) { return k * kBrickBlk + ((tid & 63) << 3) + (tid >> 6); }
@@ -612,7 +595,7 @@ __global__ __launch_bounds__(kBrickBlk) __attribute__((amdgpu_waves_per_eu(6, 8)
     }
     if (DOT) { // ONE partial per workgroup (fixed order: the tile walk is static, the waves' sums are added in wave order): few enough
                // for the vector kernel that follows to fold them itself instead of a reduction launch in between
-        const double dsum = brick_wave_sum_dpp((double)dot);            // (float: a lane's few rows in float, everything across lanes in double)
+        const double dsum = wave_sum_dpp((double)dot);                  // (float: a lane's few rows in float, everything across lanes in double)
         double *wsum = reinterpret_cast<double *>(park + kBrickXSlots);
         __syncthreads();                                                 // (the last tile's streamed sums may still be reading `park`)
         if (lane == 63) wsum[tid >> 6] = dsum;

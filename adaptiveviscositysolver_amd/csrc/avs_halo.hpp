@@ -1,11 +1,12 @@
-// avs_halo.hpp -- device code shared by the SpMV kernels of the partitioned solve (avs_pcg.hip: word-stream kernels, avs_brick.hip: the
-// brick-structured form): the CG scalars, the direct transport's flag / slot protocol and the finalizer blocks that
-// fold a round's partial sums, all-gather them with the other ranks through the comm blocks and apply the scalar step.
+// avs_halo.hpp -- device code shared by the word-stream SpMV kernels of the partitioned solve (avs_spmv.hip) and the loops of avs_pcg.hip:
+// the CG scalars, the direct transport's flag / slot protocol and the finalizer blocks that fold a round's partial
+// sums, all-gather them with the other ranks through the comm blocks and apply the scalar step.
 // Nothing here crosses the C ABI.  Reference: the all-reduce of the CG dot products north_star asks for, replacing Eigen's serial
 // p.dot(tmp) / squaredNorm inside ConjugateGradient (cpp:618-630).
 #pragma once
 
 #include "avs_internal.hpp"
+#include "avs_wave.hpp" // wave_sum
 
 namespace avs {
 
@@ -100,15 +101,6 @@ __device__ __forceinline__ unsigned long long selftest_pattern(unsigned long lon
 {
     return (E << 40) ^ ((unsigned long long)(from + 1) << 32) ^ (unsigned long long)(unsigned)k ^ 0x4000000000000000ull;
 }
-
-// wave64 sum by shuffles (fixed order)
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 
 enum ScalarOp { OP_NONE = 0, OP_INIT = 1, OP_RHO0 = 2, OP_ALPHA = 3, OP_BETA = 4, OP_SR_INIT = 5, OP_SR_STEP = 6, OP_ALPHA_ODD = 7,
                 OP_SR_INIT_F32 = 8, OP_SR_STEP_F32 = 9 };

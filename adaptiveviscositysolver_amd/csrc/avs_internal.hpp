@@ -634,10 +634,22 @@ struct PcgDist; // opaque: halo exchange + all-reduce
 avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, double tol, int max_iters,
                      hipStream_t stream, avs_solve_info *info, PcgDist *dist);
 
-// SpMV launchers (variant 0 = default)
+// SpMV launchers on the CSR and its compressed forms (avs_spmv.hip; variant 0 = default)
+struct PcgScalars; // avs_halo.hpp
+struct HaloView;
+constexpr int kTileRows = 512;    // rows per workgroup of the value-indexed kernel and of the dist tile lists
+constexpr int kViLdsTable = 2048; // dictionary entries staged in LDS (16 KiB)
 avs_status spmv_launch(const CsrView &A, const double *x, double *y, int variant, hipStream_t stream);
 int spmv_default_variant(const CsrView &A);
-avs_status spmv_dot_launch(const CsrView &A, const double *x, double *y, double *partial, int variant, hipStream_t stream);
+// + per-block partials of x.y (partial == nullptr: none).  The loops pass their scalars (sc->done: a launch enqueued past convergence
+// exits at once) and take the number of partials written
+avs_status spmv_dot_launch(const CsrView &A, const double *x, double *y, double *partial, int variant, hipStream_t stream,
+                           const PcgScalars *sc = nullptr, int *nblocks = nullptr);
+// the default kernel on a list of kTileRows-row tiles / on all tiles + the finalizer blocks of the direct transport
+avs_status spmv_dot_tiles(const CsrView &A, const double *x, double *y, double *partial, const PcgScalars *sc, const int32_t *tiles,
+                          int ntiles, hipStream_t stream);
+avs_status spmv_dot_tiles_halo(const CsrView &A, const double *x, double *y, double *partial, const PcgScalars *sc, const int32_t *tiles,
+                               int launch_blocks, const HaloView &hv, hipStream_t stream);
 size_t spmv_partial_elems(int64_t n);
 avs_status stream_probe(int mode, const double *a, double *b, int64_t n, double *sink, int grid, hipStream_t st);
 

@@ -1,20 +1,12 @@
-// avs_pcg.hip -- device-resident Jacobi-PCG + CSR SpMV for gfx950 (MI355X).
+// avs_pcg.hip -- device-resident Jacobi-PCG for gfx950 (MI355X): the loops and their vector, reduction and transport kernels.
+// (The matrix-vector products on the caller's CSR: avs_spmv.hip; the brick-structured form: avs_brick.hip.)
 //
 // Replaces cpp:611-643 of the reference (HDK_AdaptiveViscosity.cpp): Eigen's
 // ConjugateGradient<SparseMatrix<double>, Lower|Upper> with DiagonalPreconditioner and
 // solveWithGuess.  The iteration follows Eigen 3.3/3.4 ConjugateGradient.h operation by operation
 // (SURVEY.md 8(c)); only the order of additions inside dot products differs (block-wise tree).
 //
-// Roofline: every kernel here is HBM-bound.  Algorithmic bytes per SpMV launch:
-//   12*nnz + 4*(n+1) + 16*n      (fp64 values, int32 columns / row pointers)
-//
-// SpMV kernels
-//   variant 1  "stream": a 256-thread workgroup owns 256 consecutive rows.  Phase 1 streams the
-//              rows' (val, col) pairs with fully coalesced loads, gathers x[col] and parks the
-//              products in LDS; phase 2: one thread per row adds its LDS segment left to right
-//              (the same order as the CPU oracle => bit-identical y).  Row stride ~15 doubles is
-//              bank-conflict-free for ds_read_b64 (30*t mod 64 distinct for t < 32).
-//   variant 2-4 "vector": 4 / 8 / 16 lanes per row, shuffle reduction.
+// Roofline: every kernel here is HBM-bound.
 //
 // CG scalars never leave the device.  The host enqueues iterations in chunks and polls a
 // `done` flag once per chunk; kernels of iterations enqueued past convergence exit immediately, so
@@ -22,12 +14,10 @@
 #include "avs_internal.hpp"
 #include "avs_halo.hpp"
 #include "avs_resident_plan.hpp"
+#include "avs_wave.hpp"
 
 namespace avs {
 
-static constexpr int kBlock = 256;
-static constexpr int kVecGrid = 2048;        // grid-stride vector kernels: 8 blocks per CU
-static constexpr int kStreamCap = 4096;      // LDS products per tile (32 KiB)
 static constexpr int kChunk = 32;            // iterations enqueued between host polls
 static constexpr int kTimedChunkEvery = 8; // hipGraph replay: 1 chunk in 8 is enqueued launch by launch with timing events
 static constexpr int kFuseAlphaMax = 4096;   // single-GPU loop: SpMV partial sums that k_update_r's workgroups fold themselves (<= 262 k rows;
@@ -87,830 +77,6 @@ struct PcgWork {
     struct ResidentPlan *resident = nullptr; // CU-resident loop (avs_pcg_resident.inl): lane plan of the current matrix
     int resident_used = 0;                   // the last solve ran it
 };
-
-// ---------------------------------------------------------------------------------------------
-// block reduction helpers (wave64 shuffles, then LDS across the 4 waves of a 256-thread block)
-// ---------------------------------------------------------------------------------------------
-// wave64 sum without the LDS crossbar: inclusive scan inside every row of 16 lanes (row_shr 1, 2, 4, 8), then
-// row_bcast15 / row_bcast31 carry the row totals forward; lane 63 ends up with the sum of all 64 lanes (fixed order)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_add(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return v + __hiloint2double(hi, lo); // lanes without a source (or masked rows) add +0.0
-}
-
-__device__ __forceinline__ double wave_sum_dpp(double v) // result in lane 63
-{
-    v = dpp_add<0x111, 0xf>(v); // row_shr:1
-    v = dpp_add<0x112, 0xf>(v); // row_shr:2
-    v = dpp_add<0x114, 0xf>(v); // row_shr:4
-    v = dpp_add<0x118, 0xf>(v); // row_shr:8
-    v = dpp_add<0x142, 0xa>(v); // row_bcast:15 into rows 1 and 3
-    v = dpp_add<0x143, 0xc>(v); // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
-__device__ __forceinline__ double block_sum(double v, double *lds4)
-{
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) lds4[wave] = v;
-    __syncthreads();
-    double s = 0.;
-    if (threadIdx.x == 0) s = ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
-    return s; // valid in thread 0
-}
-
-// two block sums through ONE barrier, each formed exactly as block_sum forms it (wave_sum, then ((w0 + w1) + w2) + w3); every thread adds
-// the four wave sums itself, so both totals are valid in EVERY thread and no broadcast barrier follows.  lds8 must be an array that
-// nothing else in the kernel touches: the barrier that block_sum takes before its stores only guards a reused array.
-__device__ __forceinline__ void block_sum2(double &a, double &b, double *lds8)
-{
-    a = wave_sum(a);
-    b = wave_sum(b);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        lds8[wave] = a;
-        lds8[4 + wave] = b;
-    }
-    __syncthreads();
-    a = ((lds8[0] + lds8[1]) + lds8[2]) + lds8[3];
-    b = ((lds8[4] + lds8[5]) + lds8[6]) + lds8[7];
-}
-
-// ---------------------------------------------------------------------------------------------
-// SpMV: stream variant
-// ---------------------------------------------------------------------------------------------
-template <bool DOT>
-__global__ __launch_bounds__(kBlock) void k_spmv_stream(CsrView A, const double *__restrict__ x,
-                                                        double *__restrict__ y,
-                                                        double *__restrict__ partial,
-                                                        const PcgScalars *sc)
-{
-    if (DOT && sc && sc->done) return;
-    __shared__ double prod[kStreamCap];
-    __shared__ double red[4];
-    const int tid = threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * kBlock;
-    const int64_t row = row0 + tid;
-    const int64_t rlast = (row0 + kBlock < A.n) ? row0 + kBlock : A.n;
-    const int s_blk = A.row_ptr[row0];
-    const int e_blk = A.row_ptr[rlast];
-    int rs = 0, re = 0;
-    if (row < A.n) {
-        rs = A.row_ptr[row];
-        re = A.row_ptr[row + 1];
-    }
-    double sum = 0.;
-    for (int ts = s_blk; ts < e_blk; ts += kStreamCap) {
-        const int te = (ts + kStreamCap < e_blk) ? ts + kStreamCap : e_blk;
-        // phase 1: coalesced stream of (val, col), gather x, products to LDS.  4 independent
-        // loads per thread in flight per trip.
-        int k = ts + tid;
-        for (; k + 3 * kBlock < te; k += 4 * kBlock) {
-            const double v0 = A.val[k], v1 = A.val[k + kBlock], v2 = A.val[k + 2 * kBlock], v3 = A.val[k + 3 * kBlock];
-            const int c0 = A.col[k], c1 = A.col[k + kBlock], c2 = A.col[k + 2 * kBlock], c3 = A.col[k + 3 * kBlock];
-            const double x0 = x[c0], x1 = x[c1], x2 = x[c2], x3 = x[c3];
-            prod[k - ts] = v0 * x0;
-            prod[k - ts + kBlock] = v1 * x1;
-            prod[k - ts + 2 * kBlock] = v2 * x2;
-            prod[k - ts + 3 * kBlock] = v3 * x3;
-        }
-        for (; k < te; k += kBlock) prod[k - ts] = A.val[k] * x[A.col[k]];
-        __syncthreads();
-        // phase 2: each row adds its part of the tile, left to right
-        const int a = rs > ts ? rs : ts;
-        const int b = re < te ? re : te;
-        for (int j = a; j < b; ++j) sum += prod[j - ts];
-        __syncthreads();
-    }
-    if (row < A.n) y[row] = sum;
-    if (DOT) {
-        double d = (row < A.n) ? sum * x[row] : 0.;
-        d = block_sum(d, red);
-        if (tid == 0) partial[blockIdx.x] = d;
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// SpMV: generic tile kernel for tuning.  One block = BLK rows; knobs: LDS capacity CAP, 16-B/8-B
-// vector streaming (VEC), XCD-contiguous tile ownership (XCD: block b -> XCD b % 8 by the observed
-// dispatch rule; each XCD then owns a contiguous eighth of the rows so x gathers of neighbouring
-// tiles share one L2 -- used for speed only, never for correctness).
-// ---------------------------------------------------------------------------------------------
-typedef double d2_t __attribute__((ext_vector_type(2)));
-typedef int i2_t __attribute__((ext_vector_type(2)));
-
-// matrix words of the value-indexed kernels: non-temporal when the matrix is larger than the caches can hold between two products (the
-// read-once stream must not evict x from L2), plain when it may stay in the 256 MB Infinity Cache from one iteration to the next
-template <bool KEEP, typename T>
-__device__ __forceinline__ T stream_load_k(const T *p)
-{
-    if (KEEP) return *p;
-    return __builtin_nontemporal_load(p);
-}
-template <bool KEEP, typename T>
-__device__ __forceinline__ void stream_store_k(T v, T *p)
-{
-    if (KEEP) *p = v;
-    else __builtin_nontemporal_store(v, p);
-}
-// (the choice is a TEMPLATE parameter: with a run-time flag the optimiser merges the plain and the hinted load of one address into one
-// plain load and the hint is gone)
-template <bool NT, typename T>
-__device__ __forceinline__ T stream_load(const T *p)
-{
-    if (NT) return __builtin_nontemporal_load(p); // read once: do not let the stream evict x from L2
-    return *p;
-}
-
-template <int BLK, int CAP, bool DOT, bool VEC, bool XCD, bool NT, bool HALO = false>
-__global__ __launch_bounds__(BLK) void k_spmv_tile(CsrView A, const double *__restrict__ xin,
-                                                   double *__restrict__ y, double *__restrict__ partial,
-                                                   const PcgScalars *sc, int chunk, const int32_t *__restrict__ tiles = nullptr,
-                                                   HaloView hv = HaloView())
-{
-    if (DOT && sc && sc->done) return;
-    __shared__ double prod[CAP + 2];
-    __shared__ double red[BLK / 64];
-    const int tid = threadIdx.x;
-    // halo-touching launch of the direct transport: columns >= n_own live in the comm block's halo area
-    struct Gather {
-        const double *x, *hx;
-        int n_own;
-        __device__ __forceinline__ double operator[](int c) const { return (HALO && c >= n_own) ? ld_sys_f64(hx + (c - n_own)) : x[c]; }
-    };
-    const Gather x{xin, HALO ? hv.dd->my_halo : nullptr, HALO ? (int)hv.dd->n_own : 0};
-    if (HALO) {
-        if ((int)blockIdx.x >= hv.ntiles) { halo_finalizer<BLK>(hv, (int)blockIdx.x - hv.ntiles); return; }
-        if (hv.tile_bnd[blockIdx.x]) halo_wait(hv); // block-uniform
-    }
-    int64_t tile = tiles ? (int64_t)tiles[blockIdx.x] : (int64_t)blockIdx.x; // tile lists: interior / halo-touching subsets
-    if (XCD) {
-        const int64_t ntiles = gridDim.x;
-        if (chunk <= 0) { // each XCD owns one contiguous eighth
-            const int64_t per = ntiles >> 3, rem = ntiles & 7;
-            const int q = blockIdx.x & 7;
-            const int64_t slot = blockIdx.x >> 3;
-            tile = (int64_t)q * per + (q < rem ? q : rem) + slot;
-        } else { // XCDs take turns on chunks of `chunk` consecutive tiles (one moving window)
-            const int64_t super = (int64_t)chunk * 8;
-            const int64_t full = (ntiles / super) * super; // tail keeps the identity mapping
-            if (tile < full) {
-                const int64_t sb = tile / super, r = tile % super;
-                const int q = (int)(r & 7);
-                const int64_t slot = r >> 3;
-                tile = sb * super + (int64_t)q * chunk + slot;
-            }
-        }
-    }
-    const int64_t row0 = tile * BLK;
-    const int64_t row = row0 + tid;
-    const int64_t rlast = (row0 + BLK < A.n) ? row0 + BLK : A.n;
-    const int s_blk = A.row_ptr[row0];
-    const int e_blk = A.row_ptr[rlast];
-    int rs = 0, re = 0;
-    if (row < A.n) {
-        rs = A.row_ptr[row];
-        re = A.row_ptr[row + 1];
-    }
-    double sum = 0.;
-    for (int ts = s_blk; ts < e_blk; ts += CAP) {
-        const int te = (ts + CAP < e_blk) ? ts + CAP : e_blk;
-        int base;
-        if (VEC) {
-            base = ts & ~1;          // even => 16-B aligned doubles, 8-B aligned ints
-            const int te2 = te & ~1; // pairs fully below te
-            int k = base + 2 * tid;
-            for (; k + 2 * BLK < te2; k += 4 * BLK) {
-                const d2_t v0 = stream_load<NT>(reinterpret_cast<const d2_t *>(A.val + k));
-                const d2_t v1 = stream_load<NT>(reinterpret_cast<const d2_t *>(A.val + k + 2 * BLK));
-                const i2_t c0 = stream_load<NT>(reinterpret_cast<const i2_t *>(A.col + k));
-                const i2_t c1 = stream_load<NT>(reinterpret_cast<const i2_t *>(A.col + k + 2 * BLK));
-                const double x00 = x[c0.x], x01 = x[c0.y], x10 = x[c1.x], x11 = x[c1.y];
-                prod[k - base] = v0.x * x00;
-                prod[k - base + 1] = v0.y * x01;
-                prod[k - base + 2 * BLK] = v1.x * x10;
-                prod[k - base + 2 * BLK + 1] = v1.y * x11;
-            }
-            for (; k < te2; k += 2 * BLK) {
-                const d2_t v0 = stream_load<NT>(reinterpret_cast<const d2_t *>(A.val + k));
-                const i2_t c0 = stream_load<NT>(reinterpret_cast<const i2_t *>(A.col + k));
-                prod[k - base] = v0.x * x[c0.x];
-                prod[k - base + 1] = v0.y * x[c0.y];
-            }
-            if (tid == 0 && (te & 1)) prod[te - 1 - base] = A.val[te - 1] * x[A.col[te - 1]];
-        } else {
-            base = ts;
-            int k = ts + tid;
-            for (; k + 3 * BLK < te; k += 4 * BLK) {
-                const double v0 = stream_load<NT>(A.val + k), v1 = stream_load<NT>(A.val + k + BLK),
-                             v2 = stream_load<NT>(A.val + k + 2 * BLK), v3 = stream_load<NT>(A.val + k + 3 * BLK);
-                const int c0 = stream_load<NT>(A.col + k), c1 = stream_load<NT>(A.col + k + BLK),
-                          c2 = stream_load<NT>(A.col + k + 2 * BLK), c3 = stream_load<NT>(A.col + k + 3 * BLK);
-                const double x0 = x[c0], x1 = x[c1], x2 = x[c2], x3 = x[c3];
-                prod[k - ts] = v0 * x0;
-                prod[k - ts + BLK] = v1 * x1;
-                prod[k - ts + 2 * BLK] = v2 * x2;
-                prod[k - ts + 3 * BLK] = v3 * x3;
-            }
-            for (; k < te; k += BLK) prod[k - ts] = stream_load<NT>(A.val + k) * x[stream_load<NT>(A.col + k)];
-        }
-        __syncthreads();
-        const int a = rs > ts ? rs : ts;
-        const int b = re < te ? re : te;
-        for (int j = a; j < b; ++j) sum += prod[j - base];
-        __syncthreads();
-    }
-    if (row < A.n) {
-        if (NT) __builtin_nontemporal_store(sum, y + row);
-        else y[row] = sum;
-    }
-    if (DOT) {
-        double d = (row < A.n) ? sum * xin[row] : 0.;
-        d = wave_sum(d);
-        __syncthreads();
-        if ((tid & 63) == 0) red[tid >> 6] = d;
-        __syncthreads();
-        if (tid == 0) {
-            double t = 0.;
-            for (int w = 0; w < BLK / 64; ++w) t += red[w];
-            if (!HALO) partial[blockIdx.x] = t; // slot = position in the launch (== tile without a tile list)
-            else __hip_atomic_store(hv.stage + tile, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // fire and forget, see halo_finalizer
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// SpMV: vector variants (LPR lanes per row)
-// ---------------------------------------------------------------------------------------------
-template <int LPR, bool DOT>
-__global__ __launch_bounds__(kBlock) void k_spmv_vec(CsrView A, const double *__restrict__ x,
-                                                     double *__restrict__ y,
-                                                     double *__restrict__ partial,
-                                                     const PcgScalars *sc)
-{
-    if (DOT && sc && sc->done) return;
-    __shared__ double red[4];
-    const int sub = threadIdx.x % LPR;
-    const int64_t group = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LPR;
-    const int64_t ngroups = (int64_t)gridDim.x * kBlock / LPR;
-    double dot = 0.;
-    for (int64_t row = group; row < A.n; row += ngroups) {
-        const int s = A.row_ptr[row], e = A.row_ptr[row + 1];
-        double sum = 0.;
-        for (int k = s + sub; k < e; k += LPR) sum += A.val[k] * x[A.col[k]];
-#pragma unroll
-        for (int o = LPR / 2; o > 0; o >>= 1) sum += __shfl_down(sum, o, LPR);
-        if (sub == 0) {
-            y[row] = sum;
-            if (DOT) dot += sum * x[row];
-        }
-    }
-    if (DOT) {
-        dot = block_sum(dot, red);
-        if (threadIdx.x == 0) partial[blockIdx.x] = dot;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// SpMV on the value-indexed matrix (CsrView::codes / table): same tile structure as k_spmv_tile, but the
-// stream is (uint16 code, int32 col) = 6 B per non-zero instead of 12 B, and the value comes from the
-// dictionary -- staged in LDS when it has at most TBL entries (the uniform-coefficient case: ~100
-// entries), read through L1/L2 otherwise.  val == table[code] bit for bit, so products, their order and
-// the row sums are those of the plain kernel.
-// ---------------------------------------------------------------------------------------------
-// Every lane issues ALL of its quad loads for the pass (8-B code quad + 16-B column quad, or one 16-B quad of
-// packed words), then ALL 4*U gathers of x, before the first product is formed; products are parked with 16-B LDS
-// stores.  Row sums stay left-to-right (oracle order).  U = CAP / (4 BLK) = 2 with 32 waves per CU is the measured
-// optimum (profiles/r01_spmv_variants.md): U = 4 needs 70 VGPRs and twice the LDS, which halves the resident waves.
-typedef unsigned short us4_t __attribute__((ext_vector_type(4)));
-typedef int i4_t __attribute__((ext_vector_type(4)));
-
-typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
-
-// TLT > 0: tile-local dictionaries (CsrView::tab_ptr): the tile's own table is staged in LDS (its first TLT entries; a tile with
-// more distinct values takes a separate path that reads the rest through L1), codes are tile-local.
-// CWIN: windowed columns (CsrView::cbase): one 32-bit word per non-zero = code << 20 | window slot << 14 | offset.
-template <int BLK, int CAP, bool DOT, bool LTAB, bool PACK, int WIN = 0, int TLT = 0, bool HALO = false, bool CWIN = false, bool KEEPW = false>
-__global__ __launch_bounds__(BLK) void k_spmv_vi2(CsrView A, const double *__restrict__ x, double *__restrict__ y,
-                                                  double *__restrict__ partial, const PcgScalars *sc,
-                                                  const int32_t *__restrict__ tiles, HaloView hv = HaloView())
-{
-    if (DOT && sc && sc->done) return;
-    if (HALO) {
-        if ((int)blockIdx.x >= hv.ntiles) { halo_finalizer<BLK>(hv, (int)blockIdx.x - hv.ntiles); return; }
-        if (hv.tile_bnd[blockIdx.x]) halo_wait(hv); // block-uniform
-    }
-    const double *__restrict__ hx = HALO ? hv.dd->my_halo : nullptr;
-    const int n_own_cols = HALO ? (int)hv.dd->n_own : 0;
-    constexpr int U = CAP / (4 * BLK); // quads per lane per pass
-    static_assert(U >= 1 && U * 4 * BLK == CAP, "CAP must be a multiple of 4*BLK");
-    static_assert(TLT == 0 || (!LTAB && !PACK && BLK == 512), "tile tables: 512-row tiles, no plain packing");
-    static_assert(!CWIN || (!PACK && BLK == 512), "windowed columns: 512-row tiles");
-    constexpr bool WORDS = PACK || CWIN; // the stream is one 32-bit word per non-zero
-    constexpr bool PREF = WORDS;         // prefetch the next pass's words during this one (4 dwords per quad; the 6-B form would need 6)
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    static_assert(WIN == 0 || (WIN >= BLK && WIN % BLK == 0), "window = a whole number of tiles");
-    double *prod = smem;                 // CAP + 4
-    double *xs = smem + CAP + 4;                           // WIN entries of x around the tile's rows
-    int *cb = reinterpret_cast<int *>(smem + CAP + 4 + WIN); // CWIN: the tile's 64 window bases
-    double *tbl = smem + CAP + 4 + WIN + (CWIN ? kCwinSlots / 2 : 0); // table_size (LTAB) / TLT entries (tile tables)
-    const int tid = threadIdx.x;
-    const int64_t tile = tiles ? (int64_t)tiles[blockIdx.x] : (int64_t)blockIdx.x;
-    if (CWIN && tid < kCwinSlots) cb[tid] = A.cbase[tile * kCwinSlots + tid];
-    const double *__restrict__ gtab = A.table;
-    int tlen = A.table_size;
-    if (TLT > 0) {
-        const int t0 = A.tab_ptr[tile];
-        gtab = A.table + t0;
-        tlen = A.tab_ptr[tile + 1] - t0;
-        if (tlen > TLT) tlen = TLT;
-    }
-    // Tile tables: the first TLT entries are in LDS.  The rare tile with more distinct values reads the rest through L1 -- on a
-    // path of its own (`big`, wave-uniform), so that the common tile carries no global load (and no s_waitcnt on it) per product.
-    bool big = false;
-    if (TLT > 0) big = (A.tab_ptr[tile + 1] - A.tab_ptr[tile]) > TLT;
-    auto value = [&](unsigned code) -> double { return (LTAB || TLT > 0) ? tbl[code] : gtab[code]; };
-    auto value_big = [&](unsigned code) -> double { return code < (unsigned)TLT ? tbl[code] : gtab[code]; };
-    const int64_t row0 = tile * BLK;
-    const int64_t row = row0 + tid;
-    const int64_t rlast = (row0 + BLK < A.n) ? row0 + BLK : A.n;
-    // x window: 43 % (WIN = 256) / 58 % (512) of a tile's columns lie within WIN entries of its rows in the brick-major
-    // numbering; those gathers are served from LDS instead of one L1 access each
-    int w0 = 0;
-    unsigned wlen = 0;
-    if (WIN > 0) {
-        const int64_t lo = row0 - (WIN - BLK) / 2;
-        w0 = (int)(lo > 0 ? lo : 0);
-        const int64_t left = A.n - w0;
-        wlen = (unsigned)(left < WIN ? left : WIN);
-#pragma unroll
-        for (int i = 0; i < WIN / BLK; ++i) {
-            const unsigned o = (unsigned)(tid + i * BLK);
-            if (o < wlen) xs[o] = x[(int64_t)w0 + o];
-        }
-    }
-    auto gather = [&](int col) -> double {
-        if (WIN > 0 && !HALO) {
-            // Both reads are issued for every lane, from a clamped address, and the value is selected afterwards.  As two exec-masked
-            // branches writing ONE register the compiler put an `s_waitcnt lgkmcnt(0)` between the LDS read and the global load of every
-            // gather (write-after-write on the destination): the eight global gathers of a pass went out one LDS round trip apart.
-            const unsigned off = (unsigned)(col - w0);
-            const bool in = off < wlen;
-            const double a = xs[in ? off : 0u];
-            const double b = x[in ? w0 : col];
-            return in ? a : b;
-        }
-        if (WIN > 0) {
-            const unsigned off = (unsigned)(col - w0);
-            if (off < wlen) return xs[off];
-        }
-        if (HALO && col >= n_own_cols) return ld_sys_f64(hx + (col - n_own_cols)); // the comm block's halo area, written by the peers
-        return x[col];
-    };
-    // the matrix stream of a pass: every lane's quads are requested in one go ...
-    u4_t qn[U]; // value codes (WORDS: whole words, split at use)
-    i4_t cn[U];
-    auto request = [&](int ts, int e_blk) {
-        const int te = (ts + CAP < e_blk) ? ts + CAP : e_blk;
-        const int base = ts & ~3, te4 = te & ~3;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int kk = base + 4 * (tid + u * BLK);
-            qn[u] = u4_t{0, 0, 0, 0};
-            cn[u] = i4_t{0, 0, 0, 0};
-            if (kk < te4) {
-                if (WORDS) {
-                    qn[u] = stream_load_k<KEEPW>(reinterpret_cast<const u4_t *>(A.packed + kk));
-                } else {
-                    const us4_t h = stream_load_k<KEEPW>(reinterpret_cast<const us4_t *>(A.codes + kk));
-                    qn[u] = u4_t{h.x, h.y, h.z, h.w};
-                    cn[u] = stream_load_k<KEEPW>(reinterpret_cast<const i4_t *>(A.col + kk));
-                }
-            }
-        }
-    };
-    const int s_blk = A.row_ptr[row0];
-    const int e_blk = A.row_ptr[rlast];
-    // ... and the FIRST pass is requested before the tile's tables / x window are staged: their latency (two dependent global
-    // round trips for a tile-local dictionary) hides behind the stream instead of delaying it
-    request(s_blk, e_blk);
-    if (LTAB || TLT > 0)
-        for (int i = tid; i < tlen; i += BLK) tbl[i] = gtab[i];
-    int rs = 0, re = 0;
-    double xr = 0.;
-    if (row < A.n) {
-        rs = A.row_ptr[row];
-        re = A.row_ptr[row + 1];
-        if (DOT && WIN == 0) xr = x[row]; // early: its latency hides behind the passes
-    }
-    if (LTAB || WIN > 0 || TLT > 0 || CWIN) __syncthreads();
-    if (DOT && WIN > 0 && row < A.n) xr = xs[(int)(row - w0)]; // the tile's own rows are always inside the window
-    double sum = 0.;
-    for (int ts = s_blk; ts < e_blk; ts += CAP) {
-        const int te = (ts + CAP < e_blk) ? ts + CAP : e_blk;
-        const int base = ts & ~3; // 8-B aligned code quads, 16-B aligned column quads
-        const int te4 = te & ~3;  // quads fully below te
-        u4_t q[U];
-        i4_t c[U];
-        double xv[U][4];
-        const unsigned cmask = PACK ? ((1u << A.col_bits) - 1u) : 0u;
-        const int cbits = PACK ? A.col_bits : 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            q[u] = qn[u];
-            c[u] = cn[u];
-        }
-        if (PREF && te < e_blk) request(te, e_blk); // software pipeline: the next pass travels while this one is multiplied
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int kk = base + 4 * (tid + u * BLK);
-            if (kk < te4) {
-                if (PACK) {
-                    c[u] = i4_t{(int)(q[u].x & cmask), (int)(q[u].y & cmask), (int)(q[u].z & cmask), (int)(q[u].w & cmask)};
-                    q[u] = u4_t{q[u].x >> cbits, q[u].y >> cbits, q[u].z >> cbits, q[u].w >> cbits};
-                }
-                if (CWIN) {
-                    constexpr unsigned om = (1u << kCwinOffBits) - 1u, sm = kCwinSlots - 1u;
-                    c[u] = i4_t{cb[(q[u].x >> kCwinOffBits) & sm] + (int)(q[u].x & om), cb[(q[u].y >> kCwinOffBits) & sm] + (int)(q[u].y & om),
-                                cb[(q[u].z >> kCwinOffBits) & sm] + (int)(q[u].z & om), cb[(q[u].w >> kCwinOffBits) & sm] + (int)(q[u].w & om)};
-                    constexpr int sh = kCwinOffBits + kCwinSlotBits;
-                    q[u] = u4_t{q[u].x >> sh, q[u].y >> sh, q[u].z >> sh, q[u].w >> sh};
-                }
-                if ((CWIN || TLT > 0) && kk < ts) {
-                    // Head of the first pass: the aligned quad starts up to 3 entries BEFORE the tile's first non-zero.  Those
-                    // entries belong to the previous tile -- they are never summed, but their words are relative to THAT tile's
-                    // column windows / dictionary: decoded against this tile's they point anywhere (a gather up to 16 K entries
-                    // past the end of x: found as a GPU memory fault on a 3-rank distributed solve by tools/stress_parity.py).
-                    const int safe = (int)row0;
-                    if (kk + 0 < ts) { c[u].x = safe; q[u].x = 0u; }
-                    if (kk + 1 < ts) { c[u].y = safe; q[u].y = 0u; }
-                    if (kk + 2 < ts) { c[u].z = safe; q[u].z = 0u; }
-                }
-                xv[u][0] = gather(c[u].x);
-                xv[u][1] = gather(c[u].y);
-                xv[u][2] = gather(c[u].z);
-                xv[u][3] = gather(c[u].w);
-            }
-        }
-        auto products = [&](auto val) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int kk = base + 4 * (tid + u * BLK);
-                if (kk < te4) {
-                    d2_t lo, hi;
-                    lo.x = val(q[u].x) * xv[u][0];
-                    lo.y = val(q[u].y) * xv[u][1];
-                    hi.x = val(q[u].z) * xv[u][2];
-                    hi.y = val(q[u].w) * xv[u][3];
-                    *reinterpret_cast<d2_t *>(prod + (kk - base)) = lo;
-                    *reinterpret_cast<d2_t *>(prod + (kk - base) + 2) = hi;
-                }
-            }
-            if (tid < te - te4) { // ragged end of the pass (at most 3 entries; entries below ts are never summed)
-                const int kk = te4 + tid;
-                if (kk >= ts) prod[kk - base] = val(A.codes[kk]) * gather(A.col[kk]); // the unpacked arrays stay resident (an entry
-                                                                                       // below ts is the previous tile's: see above)
-            }
-        };
-        if (TLT > 0 && big) products(value_big);
-        else products(value);
-        if (!PREF && te < e_blk) request(te, e_blk);
-        __syncthreads();
-        const int a = rs > ts ? rs : ts;
-        const int b = re < te ? re : te;
-        for (int j = a; j < b; ++j) sum += prod[j - base];
-        __syncthreads();
-    }
-    if (DOT) {
-        // x.y: one partial per WAVE, reduced with DPP row shifts / broadcasts -- no LDS traffic, no barrier, no atomic.
-        // (Measured: parking the terms in LDS and letting the last-arriving wave fold them cost 9-10 us per launch, two
-        // dependent LDS round trips at the end of every wave's life while the LDS pipe is busy; a block barrier 15 us.)
-        const double d = wave_sum_dpp((row < A.n) ? sum * xr : 0.);
-        if ((tid & 63) == 63) {
-            if (!HALO) partial[(int64_t)blockIdx.x * (BLK / 64) + (tid >> 6)] = d; // slot = position in the launch
-            else // direct transport: write-through, fire and forget -- a finalizer block watches the slot (halo_finalizer)
-                __hip_atomic_store(hv.stage + tile * (BLK / 64) + (tid >> 6), d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (row < A.n) __builtin_nontemporal_store(sum, y + row);
-}
-
-static constexpr int kViLdsTable = 2048; // dictionary entries staged in LDS (16 KiB)
-static constexpr int kTileRows = 512;    // rows per workgroup of the value-indexed kernel and of the dist tile lists
-static constexpr int kTileCap = 4096;    // products parked per pass (U = 2 quads per lane)
-static constexpr int kTileWin = 512;     // x entries staged in LDS (the tile's own rows): 38 KiB per workgroup => 32 waves per CU
-
-template <int BLK, int CAP, bool DOT, bool LTAB, bool PACK, int WIN = 0, int TLT = 0, bool HALO = false, bool CWIN = false>
-static avs_status spmv_vi2_launch_t(const CsrView &A, const double *x, double *y, double *partial, const PcgScalars *sc,
-                                    const int32_t *tiles, int ntiles, size_t lds, hipStream_t stream, const HaloView &hv = HaloView())
-{
-    // > 48 KiB of dynamic LDS (value table of ~1.5 k+ entries) needs the opt-in; it is a per-device function attribute, so it
-    // is set on every such launch (cheap, rare path) rather than cached in a process-wide flag
-    if (A.keep_cached && !HALO) { // the words may stay in the Infinity Cache between two products: plain loads
-        if (lds > 48 * 1024)
-            AVS_HIP(hipFuncSetAttribute((const void *)k_spmv_vi2<BLK, CAP, DOT, LTAB, PACK, WIN, TLT, HALO, CWIN, !HALO>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
-        hipLaunchKernelGGL((k_spmv_vi2<BLK, CAP, DOT, LTAB, PACK, WIN, TLT, HALO, CWIN, !HALO>), dim3(ntiles), dim3(BLK), lds, stream, A, x, y,
-                           partial, sc, tiles, hv);
-        AVS_HIP(hipGetLastError());
-        return AVS_OK;
-    }
-    if (lds > 48 * 1024)
-        AVS_HIP(hipFuncSetAttribute((const void *)k_spmv_vi2<BLK, CAP, DOT, LTAB, PACK, WIN, TLT, HALO, CWIN>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
-    hipLaunchKernelGGL((k_spmv_vi2<BLK, CAP, DOT, LTAB, PACK, WIN, TLT, HALO, CWIN>), dim3(ntiles), dim3(BLK), lds, stream, A, x, y, partial,
-                       sc, tiles, hv);
-    AVS_HIP(hipGetLastError());
-    return AVS_OK;
-}
-
-static constexpr int kTltLds = 1024;   // tile-table entries staged in LDS (8 KiB; tiles rarely hold more distinct values)
-
-// tile-local dictionaries: 512-row tiles, CAP products per pass, the tile's table next to the x window
-template <int CAP, bool DOT, int TCAP>
-static avs_status spmv_tlt_launch(const CsrView &A, const double *x, double *y, double *partial, const PcgScalars *sc,
-                                  const int32_t *tiles, int ntiles, hipStream_t stream)
-{
-    if (ntiles <= 0) return AVS_OK;
-    const size_t lds = (size_t)(CAP + 4 + kTileWin + TCAP + (A.cbase ? kCwinSlots / 2 : 0)) * sizeof(double);
-    if (A.cbase) return spmv_vi2_launch_t<kTileRows, CAP, DOT, false, false, kTileWin, TCAP, false, true>(A, x, y, partial, sc, tiles, ntiles, lds, stream);
-    return spmv_vi2_launch_t<kTileRows, CAP, DOT, false, false, kTileWin, TCAP>(A, x, y, partial, sc, tiles, ntiles, lds, stream);
-}
-
-template <int BLK, int CAP, bool DOT, int WIN = 0>
-static avs_status spmv_vi2_launch(const CsrView &A, const double *x, double *y, double *partial, const PcgScalars *sc,
-                                  const int32_t *tiles, int ntiles, hipStream_t stream)
-{
-    if (ntiles <= 0) return AVS_OK;
-    if (A.tab_ptr) { // tile-local codes: only the tile-table kernel can decode them
-        if (BLK != kTileRows) { set_error("tile-local dictionaries need %d-row tiles", kTileRows); return AVS_EINVAL; }
-        return spmv_tlt_launch<kTileCap, DOT, kTltLds>(A, x, y, partial, sc, tiles, ntiles, stream);
-    }
-    const bool ltab = A.table_size <= kViLdsTable;
-    if (A.cbase) { // windowed columns with ONE dictionary (it has at most 2048 entries, see build_matrix_index)
-        if (BLK != kTileRows || WIN != kTileWin || !ltab) { set_error("windowed columns need the default tile geometry"); return AVS_EINVAL; }
-        const size_t ldsw = (size_t)(kTileCap + 4 + kTileWin + kCwinSlots / 2 + ((A.table_size + 1) & ~1)) * sizeof(double);
-        return spmv_vi2_launch_t<kTileRows, kTileCap, DOT, true, false, kTileWin, 0, false, true>(A, x, y, partial, sc, tiles, ntiles, ldsw, stream);
-    }
-    const bool pack = A.packed != nullptr;
-    const size_t lds = (size_t)(CAP + 4 + WIN + (ltab ? ((A.table_size + 1) & ~1) : 0)) * sizeof(double);
-    if (ltab && pack) return spmv_vi2_launch_t<BLK, CAP, DOT, true, true, WIN>(A, x, y, partial, sc, tiles, ntiles, lds, stream);
-    if (ltab) return spmv_vi2_launch_t<BLK, CAP, DOT, true, false, WIN>(A, x, y, partial, sc, tiles, ntiles, lds, stream);
-    if (pack) return spmv_vi2_launch_t<BLK, CAP, DOT, false, true, WIN>(A, x, y, partial, sc, tiles, ntiles, lds, stream);
-    return spmv_vi2_launch_t<BLK, CAP, DOT, false, false, WIN>(A, x, y, partial, sc, tiles, ntiles, lds, stream);
-}
-
-#ifdef AVS_PROBES
-// ---------------------------------------------------------------------------------------------
-// stream ceilings of this chip for the access widths the SpMV uses (measurement helpers)
-// ---------------------------------------------------------------------------------------------
-template <bool NT, int MODE>
-__global__ __launch_bounds__(kBlock) void k_stream_probe(const d2_t *__restrict__ a, d2_t *__restrict__ b, int64_t n2,
-                                                         double *__restrict__ sink)
-{
-    double acc = 0.;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    for (; i + 3 * stride < n2; i += 4 * stride) {
-        const d2_t v0 = stream_load<NT>(a + i), v1 = stream_load<NT>(a + i + stride), v2 = stream_load<NT>(a + i + 2 * stride),
-                   v3 = stream_load<NT>(a + i + 3 * stride);
-        if (MODE == 1) { b[i] = v0; b[i + stride] = v1; b[i + 2 * stride] = v2; b[i + 3 * stride] = v3; }
-        else acc += (v0.x + v0.y) + (v1.x + v1.y) + (v2.x + v2.y) + (v3.x + v3.y);
-    }
-    for (; i < n2; i += stride) {
-        const d2_t v0 = stream_load<NT>(a + i);
-        if (MODE == 1) b[i] = v0; else acc += v0.x + v0.y;
-    }
-    if (MODE == 0 && acc == 1.2345e300) sink[0] = acc; // keep the loads alive
-}
-
-avs_status stream_probe(int mode, const double *a, double *b, int64_t n, double *sink, int grid, hipStream_t st)
-{
-    const int64_t n2 = n / 2;
-    switch (mode) {
-    case 0: hipLaunchKernelGGL((k_stream_probe<false, 0>), dim3(grid), dim3(kBlock), 0, st, (const d2_t *)a, (d2_t *)b, n2, sink); break;
-    case 1: hipLaunchKernelGGL((k_stream_probe<true, 0>), dim3(grid), dim3(kBlock), 0, st, (const d2_t *)a, (d2_t *)b, n2, sink); break;
-    case 2: hipLaunchKernelGGL((k_stream_probe<false, 1>), dim3(grid), dim3(kBlock), 0, st, (const d2_t *)a, (d2_t *)b, n2, sink); break;
-    default: set_error("unknown stream probe mode %d", mode); return AVS_EINVAL;
-    }
-    AVS_HIP(hipGetLastError());
-    return AVS_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// SELL-C-sigma (C = 64 = one wavefront per slice) -- measurement only (BASELINE configs[4] asks for a blocked-ELL / SELL
-// experiment; tools/sell_experiment.py builds the layout and reports padding + time, profiles/r02_sell_experiment.md).
-// Slice s holds rows [64 s, 64 s + 64) of the sigma-sorted matrix, column-major: entry j of lane l at slice_ptr[s] + 64 j + l,
-// padded to the slice's longest row with (col 0, val 0.0).  Every load is a full coalesced 512-B / 256-B wave access.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_spmv_sell(int64_t nslices, const int64_t *__restrict__ slice_ptr, const int32_t *__restrict__ col,
-                                                   const double *__restrict__ val, const double *__restrict__ x, double *__restrict__ y)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (s >= nslices) return;
-    const int64_t b = slice_ptr[s], e = slice_ptr[s + 1];
-    double sum = 0.;
-    int64_t k = b + lane;
-    for (; k + 192 < e; k += 256) { // 4 entries per lane in flight
-        const double v0 = __builtin_nontemporal_load(val + k), v1 = __builtin_nontemporal_load(val + k + 64),
-                     v2 = __builtin_nontemporal_load(val + k + 128), v3 = __builtin_nontemporal_load(val + k + 192);
-        const int c0 = __builtin_nontemporal_load(col + k), c1 = __builtin_nontemporal_load(col + k + 64),
-                  c2 = __builtin_nontemporal_load(col + k + 128), c3 = __builtin_nontemporal_load(col + k + 192);
-        const double x0 = x[c0], x1 = x[c1], x2 = x[c2], x3 = x[c3];
-        sum += v0 * x0;
-        sum += v1 * x1;
-        sum += v2 * x2;
-        sum += v3 * x3;
-    }
-    for (; k < e; k += 64) sum += __builtin_nontemporal_load(val + k) * x[__builtin_nontemporal_load(col + k)];
-    y[s * 64 + lane] = sum;
-}
-
-#endif // AVS_PROBES
-
-static inline int stream_grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
-
-int spmv_default_variant(const CsrView &) { return 24; } // 512 rows/WG, 32 KiB LDS, 16-B vector + non-temporal stream (profiles/r01_spmv_variants.md)
-
-template <bool DOT>
-static avs_status spmv_dispatch(const CsrView &A, const double *x, double *y, double *partial,
-                                const PcgScalars *sc, int variant, hipStream_t stream, int *nblocks)
-{
-    if (A.n <= 0) { if (nblocks) *nblocks = 0; return AVS_OK; }
-    if (A.brick && A.brick->ntiles > 0 && (variant == 0 || variant == spmv_default_variant(A))) { // brick-structured form (avs_brick.hip)
-        if (nblocks) *nblocks = brick_partial_count(*A.brick, 8);
-        return spmv_brick_launch(*A.brick, x, y, DOT ? partial : nullptr, (DOT && sc) ? &sc->done : nullptr, stream);
-    }
-    if (A.codes && (variant == 0 || variant == spmv_default_variant(A))) { // value-indexed matrix: 6 or 4 B per non-zero
-        const int nt = (int)((A.n + kTileRows - 1) / kTileRows);
-        if (nblocks) *nblocks = nt * (kTileRows / 64);
-        return spmv_vi2_launch<kTileRows, kTileCap, DOT, kTileWin>(A, x, y, partial, sc, nullptr, nt, stream);
-    }
-#ifdef AVS_PROBES // geometry sweeps of the value-indexed kernels (profiles/r01_spmv_variants.md, r02_varvisc.md)
-    if (A.tab_ptr && variant >= 51 && variant <= 54) { // geometry sweep of the tile-table kernel (profiles/r02_varvisc.md)
-        const int nt = (int)((A.n + kTileRows - 1) / kTileRows);
-        if (nblocks) *nblocks = nt * (kTileRows / 64);
-        switch (variant) {
-        case 51: return spmv_tlt_launch<4096, DOT, 1024>(A, x, y, partial, sc, nullptr, nt, stream);
-        case 52: return spmv_tlt_launch<2048, DOT, 2048>(A, x, y, partial, sc, nullptr, nt, stream);
-        case 53: return spmv_tlt_launch<4096, DOT, 2048>(A, x, y, partial, sc, nullptr, nt, stream);
-        case 54: return spmv_tlt_launch<2048, DOT, 1024>(A, x, y, partial, sc, nullptr, nt, stream);
-        }
-    }
-    if (A.codes && !A.tab_ptr && !A.cbase && variant >= 31 && variant <= 46) {
-#define AVS_VI2_CASE(ID, BLK, CAP, ...)                                                                         \
-    case ID: {                                                                                                  \
-        const int nt = (int)((A.n + BLK - 1) / BLK);                                                            \
-        if (nblocks) *nblocks = nt * (BLK / 64);                                                                \
-        return spmv_vi2_launch<BLK, CAP, DOT, ##__VA_ARGS__>(A, x, y, partial, sc, nullptr, nt, stream);        \
-    }
-        switch (variant) { // geometry sweep of the value-indexed kernel (profiles/r01_spmv_variants.md)
-            AVS_VI2_CASE(31, 256, 4096)
-            AVS_VI2_CASE(32, 512, 8192)
-            AVS_VI2_CASE(33, 512, 4096)
-            AVS_VI2_CASE(34, 128, 2048)
-            AVS_VI2_CASE(36, 1024, 8192)
-            AVS_VI2_CASE(37, 256, 2048)
-            AVS_VI2_CASE(38, 512, 2048)
-            AVS_VI2_CASE(39, 256, 1024)
-            AVS_VI2_CASE(40, 128, 1024)
-            AVS_VI2_CASE(41, 256, 2048, 256)
-            AVS_VI2_CASE(42, 512, 4096, 512)
-            AVS_VI2_CASE(43, 256, 2048, 512)
-            AVS_VI2_CASE(44, 128, 1024, 128)
-            AVS_VI2_CASE(45, 128, 1024, 256)
-            AVS_VI2_CASE(46, 512, 4096, 1024)
-        }
-#undef AVS_VI2_CASE
-    }
-#endif
-    if (variant == 0) variant = spmv_default_variant(A);
-    int g;
-    switch (variant) { // the plain kernels below read A.val / A.col only
-#define AVS_TILE_CASE(ID, BLK, CAP, VEC, XCD, CHUNK, NT)                                                                  \
-    case ID:                                                                                                   \
-        g = (int)((A.n + BLK - 1) / BLK);                                                                      \
-        hipLaunchKernelGGL((k_spmv_tile<BLK, CAP, DOT, VEC, XCD, NT>), dim3(g), dim3(BLK), 0, stream, A, x, y, partial, sc, CHUNK); \
-        break;
-#ifdef AVS_PROBES // the round-1 kernel sweep (14 = the plain reference kernel avs_bench_spmv compares against)
-    case 1:
-        g = stream_grid(A.n);
-        hipLaunchKernelGGL((k_spmv_stream<DOT>), dim3(g), dim3(kBlock), 0, stream, A, x, y, partial, sc);
-        break;
-    case 2:
-        g = kVecGrid * 4;
-        hipLaunchKernelGGL((k_spmv_vec<4, DOT>), dim3(g), dim3(kBlock), 0, stream, A, x, y, partial, sc);
-        break;
-    case 3:
-        g = kVecGrid * 4;
-        hipLaunchKernelGGL((k_spmv_vec<8, DOT>), dim3(g), dim3(kBlock), 0, stream, A, x, y, partial, sc);
-        break;
-    case 4:
-        g = kVecGrid * 4;
-        hipLaunchKernelGGL((k_spmv_vec<16, DOT>), dim3(g), dim3(kBlock), 0, stream, A, x, y, partial, sc);
-        break;
-        AVS_TILE_CASE(5, 256, 4096, false, true, 0, false)
-        AVS_TILE_CASE(6, 256, 4096, true, false, 0, false)
-        AVS_TILE_CASE(7, 256, 2048, false, false, 0, false)
-        AVS_TILE_CASE(8, 128, 2048, false, false, 0, false)
-        AVS_TILE_CASE(9, 512, 8192, false, false, 0, false)
-        AVS_TILE_CASE(10, 256, 2048, true, false, 0, false)
-        AVS_TILE_CASE(11, 256, 2048, true, true, 2, false)
-        AVS_TILE_CASE(12, 256, 2048, true, true, 4, false)
-        AVS_TILE_CASE(13, 256, 2048, true, true, 16, false)
-        AVS_TILE_CASE(14, 256, 2048, true, false, 0, true)
-        AVS_TILE_CASE(15, 256, 2048, true, true, 4, true)
-        AVS_TILE_CASE(16, 256, 2048, true, true, 16, true)
-        AVS_TILE_CASE(17, 256, 2048, true, true, 64, true)
-        AVS_TILE_CASE(18, 256, 4096, true, true, 4, true)
-        AVS_TILE_CASE(19, 256, 2048, false, false, 0, true)
-        AVS_TILE_CASE(20, 256, 2048, true, true, 2, true)
-        AVS_TILE_CASE(21, 256, 2048, true, true, 8, true)
-        AVS_TILE_CASE(22, 128, 1024, true, false, 0, true)
-        AVS_TILE_CASE(23, 128, 2048, true, false, 0, true)
-#endif
-        AVS_TILE_CASE(24, 512, 4096, true, false, 0, true)
-#undef AVS_TILE_CASE
-    default:
-        set_error("unknown SpMV variant %d", variant);
-        return AVS_EINVAL;
-    }
-    if (nblocks) *nblocks = g;
-    AVS_HIP(hipGetLastError());
-    return AVS_OK;
-}
-
-static size_t max_partials(int64_t n)
-{
-    size_t a = (size_t)((n + 63) / 64) + 16, b = (size_t)kVecGrid * 4; // up to one partial per wave of rows
-    return 2 * (a > b ? a : b) + 4 * (size_t)kVecGrid + 16;
-}
-
-avs_status spmv_launch(const CsrView &A, const double *x, double *y, int variant, hipStream_t stream)
-{
-    return spmv_dispatch<false>(A, x, y, nullptr, nullptr, variant, stream, nullptr);
-}
-
-// default kernel restricted to a list of kTileRows-row tiles (multi-GPU overlap: interior tiles run while the halo
-// travels); partial[tile] receives the tile's share of x.y, so several launches fill one partial array
-int spmv_tile_rows() { return kTileRows; }
-avs_status spmv_dot_tiles(const CsrView &A, const double *x, double *y, double *partial, const PcgScalars *sc,
-                          const int32_t *tiles, int ntiles, hipStream_t stream)
-{
-    if (ntiles <= 0) return AVS_OK;
-    if (A.codes) return spmv_vi2_launch<kTileRows, kTileCap, true, kTileWin>(A, x, y, partial, sc, tiles, ntiles, stream);
-    hipLaunchKernelGGL((k_spmv_tile<kTileRows, 4096, true, true, false, true>), dim3(ntiles), dim3(kTileRows), 0, stream, A, x, y,
-                       partial, sc, 0, tiles);
-    AVS_HIP(hipGetLastError());
-    return AVS_OK;
-}
-
-// the SpMV launch of the direct transport: all tiles (those flagged in hv.tile_bnd wait for the peers' entries and gather halo
-// columns from the comm block) + the finalizer block; launch_blocks = ntiles + 1
-avs_status spmv_dot_tiles_halo(const CsrView &A, const double *x, double *y, double *partial, const PcgScalars *sc,
-                               const int32_t *tiles, int launch_blocks, const HaloView &hv, hipStream_t stream)
-{
-    if (A.codes) {
-        if (A.tab_ptr) {
-            const size_t lds = (size_t)(kTileCap + 4 + kTileWin + kTltLds + (A.cbase ? kCwinSlots / 2 : 0)) * sizeof(double);
-            if (A.cbase)
-                return spmv_vi2_launch_t<kTileRows, kTileCap, true, false, false, kTileWin, kTltLds, true, true>(A, x, y, partial, sc, tiles,
-                                                                                                             launch_blocks, lds, stream, hv);
-            return spmv_vi2_launch_t<kTileRows, kTileCap, true, false, false, kTileWin, kTltLds, true>(A, x, y, partial, sc, tiles, launch_blocks,
-                                                                                                   lds, stream, hv);
-        }
-        const bool ltab = A.table_size <= kViLdsTable;
-        if (A.cbase) {
-            const size_t ldsw = (size_t)(kTileCap + 4 + kTileWin + kCwinSlots / 2 + ((A.table_size + 1) & ~1)) * sizeof(double);
-            return spmv_vi2_launch_t<kTileRows, kTileCap, true, true, false, kTileWin, 0, true, true>(A, x, y, partial, sc, tiles, launch_blocks,
-                                                                                                  ldsw, stream, hv);
-        }
-        const bool pack = A.packed != nullptr;
-        const size_t lds = (size_t)(kTileCap + 4 + kTileWin + (ltab ? ((A.table_size + 1) & ~1) : 0)) * sizeof(double);
-        if (ltab && pack) return spmv_vi2_launch_t<kTileRows, kTileCap, true, true, true, kTileWin, 0, true>(A, x, y, partial, sc, tiles, launch_blocks, lds, stream, hv);
-        if (ltab) return spmv_vi2_launch_t<kTileRows, kTileCap, true, true, false, kTileWin, 0, true>(A, x, y, partial, sc, tiles, launch_blocks, lds, stream, hv);
-        if (pack) return spmv_vi2_launch_t<kTileRows, kTileCap, true, false, true, kTileWin, 0, true>(A, x, y, partial, sc, tiles, launch_blocks, lds, stream, hv);
-        return spmv_vi2_launch_t<kTileRows, kTileCap, true, false, false, kTileWin, 0, true>(A, x, y, partial, sc, tiles, launch_blocks, lds, stream, hv);
-    }
-    hipLaunchKernelGGL((k_spmv_tile<kTileRows, 4096, true, true, false, true, true>), dim3(launch_blocks), dim3(kTileRows), 0, stream, A, x, y,
-                       partial, sc, 0, tiles, hv);
-    AVS_HIP(hipGetLastError());
-    return AVS_OK;
-}
-
-// the form used inside the PCG loop: y = A x and per-block partials of x.y
-avs_status spmv_dot_launch(const CsrView &A, const double *x, double *y, double *partial, int variant, hipStream_t stream)
-{
-    return spmv_dispatch<true>(A, x, y, partial, nullptr, variant, stream, nullptr);
-}
-size_t spmv_partial_elems(int64_t n) { return max_partials(n); }
 
 // ---------------------------------------------------------------------------------------------
 // vector kernels
@@ -1255,7 +421,7 @@ __global__ __launch_bounds__(kBlock) void k_update_xp(int64_t n, double *__restr
 // not co-resident in time (the GPU shared with other work) sets sc->fault instead of hanging.  No L2 write-back fence anywhere: what
 // crosses the barrier is read with agent-scope loads.  Plain launch (a graph node like any other); needs every CU free, which holds behind the persistent SpMV.
 // ---------------------------------------------------------------------------------------------
-static constexpr size_t kFusedTabBytes = (size_t)(2048 + 1) * sizeof(double) + 8; // CODED: the inverted dictionary (kViLdsTable + 1 entries)
+static constexpr size_t kFusedTabBytes = (size_t)(kViLdsTable + 1) * sizeof(double) + 8; // CODED: the inverted dictionary
 static constexpr size_t kFusedLds = (size_t)8 * 1024 * 16; // the second emulated workgroup's new r: kFusedPairs x kFusedBlock pairs of doubles
 static constexpr unsigned kFusedStride = (unsigned)kVecGrid * kBlock * 16u; // bytes between two pairs of an emulated thread
 static constexpr int kFusedBlock = 1024, kFusedPairs = 8, kFusedBatch = 4; // (loads in flight per lane: kFusedBatch pairs of rows of each stream)
@@ -2000,12 +1166,12 @@ template <typename T> struct SrVecs {
     const uint16_t *dcode;
 };
 
-// the SpMV of the set-up and of the RCCL loop: the fp64 dispatcher, or the float loop's
+// the SpMV of the set-up and of the RCCL loop: the fp64 launcher (avs_spmv.hip; !DOT: partial is nullptr), or the float loop's
 template <bool DOT>
 static avs_status sr_spmv(const CsrView &A, const double *x, double *y, double *partial, const PcgScalars *sc, int variant,
                           hipStream_t stream, int *nb)
 {
-    return spmv_dispatch<DOT>(A, x, y, partial, sc, variant, stream, nb);
+    return spmv_dot_launch(A, x, y, DOT ? partial : nullptr, variant, stream, sc, nb);
 }
 template <bool DOT>
 static avs_status sr_spmv(const CsrView &A, const float *x, float *y, double *partial, const PcgScalars *sc, int, hipStream_t stream, int *nb)
@@ -2085,7 +1251,7 @@ static avs_status sr_setup_exchange(PcgWork *w, const CsrView &A, const double *
         if constexpr (MIXED) {
             if (k == 0) { // x exchanged in fp64, then the rank's fp64 product (as in the reliable updates)
                 if (dist) AVS_TRY(dist_halo_exchange(dist, w->p.p, stream));
-                return spmv_dispatch<false>(A, w->p.p, w->t.p, nullptr, nullptr, variant, stream, nullptr);
+                return spmv_launch(A, w->p.p, w->t.p, variant, stream);
             }
         }
         if (dist) AVS_TRY(dist_halo_exchange(dist, v->u, stream));
@@ -2172,7 +1338,7 @@ static avs_status pcg_solve_single_reduction(PcgWork *w, const CsrView &A, const
             hipLaunchKernelGGL(k_mixed_fold, dim3(g), dim3(kBlock), 0, stream, n, x, v.x, (const PcgScalars *)now);
             AVS_HIP(hipMemcpyAsync(w->p.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
             AVS_TRY(dist_halo_exchange(dist, w->p.p, stream));
-            AVS_TRY(spmv_dispatch<false>(A, w->p.p, w->t.p, nullptr, nullptr, variant, stream, nullptr));
+            AVS_TRY(spmv_launch(A, w->p.p, w->t.p, variant, stream));
             with_flags([&](auto C) {
                 hipLaunchKernelGGL((k_sr_mixed_residual<C.value, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)w->t.p, v.r, v.u,
                                    coded ? v.invtab : v.invd, v.dcode, pvec, (const PcgScalars *)now);
@@ -2433,9 +1599,6 @@ __global__ __launch_bounds__(256) void k_direct_selftest(HaloView hv, unsigned l
     dist_finalize<256>(hv, acc);
 }
 
-avs_status spmv_dot_tiles(const CsrView &A, const double *x, double *y, double *partial, const PcgScalars *sc, const int32_t *tiles,
-                          int ntiles, hipStream_t stream);
-
 // The finalizer of the direct transport as a launch of its own, behind the brick-structured form's SpMV (whose persistent workgroups
 // keep three per CU with the LDS they have: the finalizer's staging would cost the third): folds the round's stage slots and the
 // vector kernel's partials, all-gathers the sums with the other ranks and applies the scalar step (halo_finalizer, avs_halo.hpp).
@@ -2572,7 +1735,7 @@ static avs_status pcg_solve_direct(PcgWork *w, const CsrView &A, const double *b
             const int hg = n_halo_cols > 0 ? (n_halo_cols + 255) / 256 : 1;
             hipLaunchKernelGGL(k_halo_gather<double>, dim3(hg < 64 ? hg : 64), dim3(256), 0, stream, hv, w->p.p);
         }
-        AVS_TRY(spmv_dispatch<false>(A, w->p.p, w->t.p, nullptr, nullptr, variant, stream, nullptr));
+        AVS_TRY(spmv_launch(A, w->p.p, w->t.p, variant, stream));
         hipLaunchKernelGGL(k_halo_finalize, dim3(1), dim3(512), 0, stream, hv);
         AVS_HIP(hipGetLastError());
         return AVS_OK;
@@ -2728,7 +1891,7 @@ avs_status pcg_create(PcgWork **out, int64_t n, int64_t n_ext, hipStream_t)
     AVS_REQUIRE(w, AVS_ENOMEM, "out of host memory");
     w->n = n;
     w->n_ext = n_ext;
-    w->npartial = max_partials(n);
+    w->npartial = spmv_partial_elems(n);
     avs_status s;
     if ((s = w->r.alloc((size_t)n)) || (s = w->p.alloc((size_t)n_ext)) || (s = w->t.alloc((size_t)n)) ||
         (s = w->invd.alloc((size_t)n)) || (s = w->partial.alloc(w->npartial)) || (s = w->sc.alloc(2)) ||
@@ -2920,7 +2083,7 @@ static avs_status fused_vectors_setup(PcgWork *w, const CsrView &A, const double
 //   vectors       caller's x, w->p/r/t, fp64 diagonal    f_x = narrowed x, f_b = narrowed b,    f_x = the correction, zeroed; f_p/r/t;
 //                                                        f_p/r/t, float diagonal                t64 = w->t; float diagonal
 //   partials      grown only for a brick form            max(stream, brick)                     that, and >= 6 kVecGrid + 64
-//   start         spmv_dispatch, k_init_residual,        float SpMV, k_f32_init_residual,       fp64 SpMV into t64, k_mixed_residual<., true>
+//   start         spmv_launch, k_init_residual,          float SpMV, k_f32_init_residual,       fp64 SpMV into t64, k_mixed_residual<., true>
 //                 OP_INIT, k_init_p, OP_RHO0             OP_INIT, k_f32_threshold,              into vpart, k_mixed_finish<true>,
 //                                                        k_f32_init_p, OP_RHO0                  k_f32_init_p (no reduction)
 //   vpart         upper half only with fuse_alpha        always the upper half                  as float
@@ -2988,7 +2151,7 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
 
     // residual = rhs - mat * x ; p = z = D^-1 r ; |b|^2, |r|^2, rho
     if constexpr (MIXED) { // in fp64, r rounded to float; rho is the fp64 sum (k_f32_init_p's own r.z partials are not used)
-        AVS_TRY(spmv_dispatch<false>(A, x, t64, nullptr, nullptr, variant, stream, nullptr));
+        AVS_TRY(spmv_launch(A, x, t64, variant, stream));
         with_flags([&](auto C) {
             hipLaunchKernelGGL((k_mixed_residual<C.value, true>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)t64, r, (const float *)inv,
                                dcode, upper, (const PcgScalars *)sc);
@@ -3068,7 +2231,7 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
     auto enqueue_update = [&]() -> avs_status {
         if constexpr (MIXED) {
             hipLaunchKernelGGL(k_mixed_fold, dim3(g), dim3(kBlock), 0, stream, n, x, xv, (const PcgScalars *)sc);
-            AVS_TRY(spmv_dispatch<false>(A, x, t64, nullptr, nullptr, variant, stream, nullptr));
+            AVS_TRY(spmv_launch(A, x, t64, variant, stream));
             with_flags([&](auto C) {
                 hipLaunchKernelGGL((k_mixed_residual<C.value, false>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)t64, r, (const float *)inv,
                                    dcode, upper, (const PcgScalars *)sc);
@@ -3161,15 +2324,6 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
 }
 
 #ifdef AVS_PROBES
-avs_status spmv_sell_launch(int64_t nslices, const int64_t *slice_ptr, const int32_t *col, const double *val, const double *x, double *y,
-                            hipStream_t stream)
-{
-    if (nslices <= 0) return AVS_OK;
-    hipLaunchKernelGGL(k_spmv_sell, dim3((unsigned)((nslices + 3) / 4)), dim3(256), 0, stream, nslices, slice_ptr, col, val, x, y);
-    AVS_HIP(hipGetLastError());
-    return AVS_OK;
-}
-
 // probe / test entry: one update_r launch followed by one update_xp launch of the launch-per-phase loops, any instantiation, on a grid
 // of `g` workgroups and a caller's PcgScalars image (the loops reach g < kVecGrid only with one trip per thread, and KEEP = false only
 // beyond the Infinity Cache)
@@ -3216,20 +2370,6 @@ avs_status vector_update_probe(int flags, int g, int64_t n, int nb, int parity, 
 } // namespace avs
 
 #ifdef AVS_PROBES
-extern "C" avs_status avs_spmv_sell(int64_t nslices, const int64_t *slice_ptr, const int32_t *col, const double *val, const double *x,
-                                    double *y, int32_t repeats, void *stream, double *ms_per_launch)
-{
-    AVS_REQUIRE(slice_ptr && col && val && x && y && repeats > 0, AVS_EINVAL, "bad argument");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    AVS_TRY(avs::spmv_sell_launch(nslices, slice_ptr, col, val, x, y, st)); // warm-up
-    avs::Timer t(st);
-    t.start();
-    for (int i = 0; i < repeats; ++i) AVS_TRY(avs::spmv_sell_launch(nslices, slice_ptr, col, val, x, y, st));
-    const double ms = t.stop() / repeats;
-    if (ms_per_launch) *ms_per_launch = ms;
-    return AVS_OK;
-}
-
 extern "C" avs_status avs_vector_update_probe(int32_t flags, int32_t g, int64_t n, int32_t nb, int32_t parity, void *x, void *p, void *r,
                                               const void *t, const void *invd, const uint16_t *dcode, const double *spmv_partial,
                                               double *vpart, void *scalars, int32_t scalars_bytes, void *stream)

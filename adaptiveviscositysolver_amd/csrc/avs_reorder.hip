@@ -147,7 +147,7 @@ avs_status build_reordered_system(avs_ctx *c, int brick_shift)
     const int mode = c->opt.brick; // -1 auto, 0 never, 1 always, 2 tune
     // (matrices without one small dictionary -- variable viscosity: tile-local tables or > kViLdsTable values -- never run the CU-resident loop:
     //  the form serves them from kBrickMinSystemRowsVc rows on.  BASELINE configs[2], 256^3 mu(x), 1.27 M rows: 14.5 k -> 15.7 k it/s, round 6)
-    const bool resident_kind = c->vi.table_size > 0 && !c->vi.tile_tables && c->vi.table_size <= kBrickTableMax; // (= kViLdsTable of avs_pcg.hip: what the resident loop stages)
+    const bool resident_kind = c->vi.table_size > 0 && !c->vi.tile_tables && c->vi.table_size <= kBrickTableMax; // (= kViLdsTable: what the resident loop stages)
     const int64_t min_rows = resident_kind ? kBrickMinSystemRows : kBrickMinSystemRowsVc;
     int want = (mode == 0) ? 0 : (mode == 1 ? 1 : (n >= min_rows ? 1 : 0));
     // AUTO keeps the form where it multiplies faster than the word stream, and picks its tile walk (BrickView::walk).  Both follow from

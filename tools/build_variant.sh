@@ -6,7 +6,7 @@ TAG=$1; DEFS=$2
 cd "$(dirname "$0")/../adaptiveviscositysolver_amd/csrc"
 mkdir -p exp_$TAG ../exp
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I../../include -Wall -Wno-unused-function $DEFS"
-for f in avs_api avs_brick avs_brick_build avs_pcg avs_assembly avs_dist avs_reorder avs_prepass avs_post; do
+for f in avs_api avs_brick avs_brick_build avs_pcg avs_spmv avs_assembly avs_dist avs_reorder avs_prepass avs_post; do
   ( /opt/rocm/bin/hipcc $FLAGS -c $f.hip -o exp_$TAG/$f.o ) &
 done
 wait

@@ -1,6 +1,6 @@
 """Disassemble kernels of the SHIPPED libavs_hip.so and check instruction-level properties the protocol depends on.
 
-The direct multi-GPU transport (avs_pcg.hip) orders "halo data before flag" without L2 write-back fences: the writer waits for
+The direct multi-GPU transport (avs_pcg.hip; its SpMV launch: avs_spmv.hip) orders "halo data before flag" without L2 write-back fences: the writer waits for
 its own write-through stores to be acknowledged (`s_waitcnt vmcnt(0)`), then the workgroup barrier, then the ticket / flag.  The
 round-2 review found that the wait was not in the instruction stream (a workgroup-scope release fence lowers to lgkmcnt only).
 This module extracts the gfx950 code objects from the library's .hip_fatbin section (clang offload bundles, one per translation
