@@ -65,9 +65,14 @@ ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_v
 # include/avs_probe.h: exported by libavs_probe.so only (the -DAVS_PROBES build of the same sources)
 PROBE_SYMBOLS = ["avs_spmv_csr", "avs_bench_spmv", "avs_spmv_sell", "avs_bench_stream", "avs_brick_spmv_probe", "avs_spmv_solver_form",
                  "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe", "avs_pcg_csr_plan",
-                 "avs_merge_triplets_probe", "avs_exclusive_scan_probe", "avs_resident_plan_host", "avs_brick_form_probe"]
+                 "avs_merge_triplets_probe", "avs_exclusive_scan_probe", "avs_resident_plan_host", "avs_brick_form_probe", "avs_pcg_scalar_probe",
+                 "avs_sr_vector_probe"]
 BRICK_PROBE_FUSED_DOT, BRICK_PROBE_F32, BRICK_PROBE_MIXED, BRICK_PROBE_VALUE_CODES, BRICK_PROBE_DONE = 1, 2, 4, 8, 16   # avs_brick_form_probe flags
 VECTOR_PROBE_F32, VECTOR_PROBE_DS, VECTOR_PROBE_CODED, VECTOR_PROBE_KEEP, VECTOR_PROBE_FUSED = 1, 2, 4, 8, 16   # avs_vector_update_probe flags
+(SCALAR_PROBE_REDUCE_LAUNCH, SCALAR_PROBE_REDUCE, SCALAR_PROBE_REDUCE_MB, SCALAR_PROBE_REDUCE_PAIR, SCALAR_PROBE_SCALAR,
+ SCALAR_PROBE_MIXED_FINISH_INIT, SCALAR_PROBE_MIXED_FINISH, SCALAR_PROBE_SR_MIXED_BEGIN, SCALAR_PROBE_SR_MIXED_STEP) = range(9)   # avs_pcg_scalar_probe
+SCALAR_PROBE_STAGE_NAN = 0x7ff8a5a500000000
+SR_PROBE_INIT, SR_PROBE_UPDATE, SR_PROBE_MIXED_RESIDUAL, SR_PROBE_MIXED_RESIDUAL_INIT = range(4)   # avs_sr_vector_probe kernels
 SPMV_FORM_FUSED_DOT, SPMV_FORM_F32, SPMV_FORM_NO_CACHE_HINT = 1, 2, 4   # avs_spmv_csr_form flags (include/avs_probe.h)
 _VOID_RETURN = ("avs_last_error", "avs_version", "avs_destroy", "avs_plan_destroy", "avs_local_group_destroy",
                 "avs_prepass_destroy")
@@ -260,6 +265,8 @@ def load(probe=False):
         L.avs_brick_wave_stats.argtypes = [vp, C.POINTER(f64)]
         L.avs_spmv_csr_form.argtypes = [i64, vp, vp, vp, vp, vp, i32, C.POINTER(f64), C.POINTER(MatrixFormat), vp]
         L.avs_vector_update_probe.argtypes = [i32, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+        L.avs_pcg_scalar_probe.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, f64, i32, i32, i32, vp, i32, vp, vp, vp]
+        L.avs_sr_vector_probe.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
         L.avs_pcg_csr_plan.argtypes = L.avs_pcg_csr.argtypes + [C.POINTER(ResidentPlanInfo)]
         L.avs_merge_triplets_probe.argtypes = [i64, vp, vp, vp, i32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(TripletMergeInfo), vp]
         L.avs_exclusive_scan_probe.argtypes = [vp, vp, i64, vp]

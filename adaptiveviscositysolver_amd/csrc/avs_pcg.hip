@@ -1108,20 +1108,21 @@ __global__ __launch_bounds__(kBlock) void k_sr_mixed_residual(int64_t n, const d
                                                               const PcgScalars *sc)
 {
     __shared__ double red[4];
-    const bool skip = !INIT && sc->done != 0; // (done == 3, a transport fault: k_sr_mixed_begin left it set)
+    // done == 3, a transport fault: k_sr_mixed_begin left it set, and k_sr_mixed_step will not read the sums -- as k_sr_update, the launch
+    // leaves the vectors AND the partial sums as they are (it used to store zero sums)
+    if (!INIT && sc->done != 0) return;
     double rr = 0., ru = 0., bb = 0.;
-    if (!skip)
-        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-            const double bi = b[i];
-            const double ri = bi - t64[i];
-            const float rf = (float)ri;
-            const float ui = (CODED ? invd[dcode[i]] : invd[i]) * rf;
-            r[i] = rf;
-            u[i] = ui;
-            rr += ri * ri;
-            ru += (double)rf * (double)ui;
-            if (INIT) bb += bi * bi;
-        }
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const double bi = b[i];
+        const double ri = bi - t64[i];
+        const float rf = (float)ri;
+        const float ui = (CODED ? invd[dcode[i]] : invd[i]) * rf;
+        r[i] = rf;
+        u[i] = ui;
+        rr += ri * ri;
+        ru += (double)rf * (double)ui;
+        if (INIT) bb += bi * bi;
+    }
     rr = block_sum(rr, red);
     ru = block_sum(ru, red);
     if (INIT) bb = block_sum(bb, red);
@@ -2365,6 +2366,92 @@ avs_status vector_update_probe(int flags, int g, int64_t n, int nb, int parity, 
     return AVS_OK;
 }
 
+// probe / test entry: the scalar stages of the loops on a caller's partial sums and PcgScalars image.  The loops reach k_reduce_mb only
+// from 16,384 partial sums upward and the corners of apply_scalar_op only where a solve passes through them; this entry launches the same
+// kernels at any count and from any state.  k_reduce_mb gets a staging array and a ticket laid out as pcg_create lays them out.
+avs_status scalar_stage_probe(int which, const double *pa, int nb, int nred, const double *pb, int nbb, int nredb, int op, double tol,
+                              int skip_if_done, int red_off, int launches, void *scalars, double *stage_out, unsigned *ticket_out,
+                              hipStream_t stream)
+{
+    PcgScalars *sc = static_cast<PcgScalars *>(scalars);
+    PcgWork w; // (only what reduce_launch reads)
+    const bool multi = which == AVS_SCALAR_PROBE_REDUCE_LAUNCH || which == AVS_SCALAR_PROBE_REDUCE_MB;
+    if (multi) {
+        AVS_TRY(w.stage.alloc((size_t)kRedBlocks * 4));
+        AVS_TRY(w.ticket.alloc(1));
+        unsigned long long pattern[kRedBlocks * 4];
+        for (int i = 0; i < kRedBlocks * 4; ++i) pattern[i] = AVS_SCALAR_PROBE_STAGE_NAN | (unsigned long long)i;
+        AVS_HIP(hipMemcpyAsync(w.stage.p, pattern, sizeof(pattern), hipMemcpyHostToDevice, stream));
+        AVS_HIP(hipMemsetAsync(w.ticket.p, 0, sizeof(unsigned), stream));
+        AVS_HIP(hipStreamSynchronize(stream)); // (pattern leaves the stack)
+    }
+    for (int l = 0; l < launches; ++l) switch (which) {
+        case AVS_SCALAR_PROBE_REDUCE_LAUNCH: reduce_launch(&w, pa, nb, nred, sc, op, tol, skip_if_done, red_off, stream); break;
+        case AVS_SCALAR_PROBE_REDUCE:
+            hipLaunchKernelGGL(k_reduce, dim3(1), dim3(kRedBlock), 0, stream, pa, nb, nred, sc, op, tol, skip_if_done, red_off);
+            break;
+        case AVS_SCALAR_PROBE_REDUCE_MB:
+            hipLaunchKernelGGL(k_reduce_mb, dim3(kRedBlocks), dim3(kRedBlock), 0, stream, pa, nb, nred, sc, op, tol, skip_if_done, red_off, w.stage.p,
+                               w.ticket.p);
+            break;
+        case AVS_SCALAR_PROBE_REDUCE_PAIR:
+            hipLaunchKernelGGL(k_reduce_pair, dim3(1), dim3(kRedBlock), 0, stream, pa, nb, nred, pb, nbb, nredb, sc);
+            break;
+        case AVS_SCALAR_PROBE_SCALAR: hipLaunchKernelGGL(k_scalar, dim3(1), dim3(64), 0, stream, sc, op, tol); break;
+        case AVS_SCALAR_PROBE_MIXED_FINISH_INIT: hipLaunchKernelGGL(k_mixed_finish<true>, dim3(1), dim3(kRedBlock), 0, stream, pa, nb, sc, tol); break;
+        case AVS_SCALAR_PROBE_MIXED_FINISH: hipLaunchKernelGGL(k_mixed_finish<false>, dim3(1), dim3(kRedBlock), 0, stream, pa, nb, sc, tol); break;
+        case AVS_SCALAR_PROBE_SR_MIXED_BEGIN: hipLaunchKernelGGL(k_sr_mixed_begin, dim3(1), dim3(1), 0, stream, sc); break;
+        default: hipLaunchKernelGGL(k_sr_mixed_step, dim3(1), dim3(1), 0, stream, sc); break;
+        }
+    AVS_HIP(hipGetLastError());
+    if (ticket_out) *ticket_out = 0u;
+    if (multi) { // (the workspace goes with this call: wait for the launches either way)
+        if (stage_out) AVS_HIP(hipMemcpyAsync(stage_out, w.stage.p, (size_t)kRedBlocks * 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (ticket_out) AVS_HIP(hipMemcpyAsync(ticket_out, w.ticket.p, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        AVS_HIP(hipStreamSynchronize(stream));
+    }
+    return AVS_OK;
+}
+
+// probe / test entry: one launch of a vector kernel of the single-reduction loops, any instantiation the loops make, on `g` workgroups
+// (the loops reach a second trip per thread only above 524,288 rows, and never a workgroup without rows)
+template <typename T, bool CODED>
+static void sr_vector_probe_t(int kernel, bool ds, int g, int64_t n, const double *b, T *x, T *r, T *p, T *s, T *u, const T *wv, const T *invd,
+                              const uint16_t *dcode, const PcgScalars *in, PcgScalars *out, int step, double *partial, hipStream_t stream)
+{
+    constexpr bool F32 = std::is_same<T, float>::value;
+    if (kernel == AVS_SR_PROBE_INIT)
+        hipLaunchKernelGGL((k_sr_init<T, F32 && CODED>), dim3(g), dim3(kBlock), 0, stream, n, b, wv, invd, dcode, r, u, partial);
+    else if constexpr (F32) {
+        if (ds) hipLaunchKernelGGL((k_sr_update<float, CODED, double>), dim3(g), dim3(kBlock), 0, stream, n, x, r, p, s, u, wv, invd, dcode, in, out, step, partial);
+        else hipLaunchKernelGGL((k_sr_update<float, CODED, float>), dim3(g), dim3(kBlock), 0, stream, n, x, r, p, s, u, wv, invd, dcode, in, out, step, partial);
+    } else
+        hipLaunchKernelGGL((k_sr_update<double, false, double>), dim3(g), dim3(kBlock), 0, stream, n, x, r, p, s, u, wv, invd, dcode, in, out, step, partial);
+}
+avs_status sr_vector_probe(int kernel, int flags, int g, int64_t n, const double *b, void *x, void *r, void *p, void *s, void *u, const void *wv,
+                           const void *invd, const uint16_t *dcode, const void *scalars_in, void *scalars_out, int step, double *partial,
+                           hipStream_t stream)
+{
+    const PcgScalars *in = static_cast<const PcgScalars *>(scalars_in);
+    PcgScalars *out = static_cast<PcgScalars *>(scalars_out);
+    const bool ds = (flags & AVS_VECTOR_PROBE_DS) != 0, f32 = ds || (flags & AVS_VECTOR_PROBE_F32) != 0;
+    with_flags([&](auto C) {
+        if (kernel == AVS_SR_PROBE_MIXED_RESIDUAL || kernel == AVS_SR_PROBE_MIXED_RESIDUAL_INIT)
+            with_flags([&](auto I) {
+                hipLaunchKernelGGL((k_sr_mixed_residual<C.value, I.value>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)wv, (float *)r,
+                                   (float *)u, (const float *)invd, dcode, partial, in);
+            }, kernel == AVS_SR_PROBE_MIXED_RESIDUAL_INIT);
+        else if (f32)
+            sr_vector_probe_t<float, C.value>(kernel, ds, g, n, b, (float *)x, (float *)r, (float *)p, (float *)s, (float *)u, (const float *)wv,
+                                              (const float *)invd, dcode, in, out, step, partial, stream);
+        else
+            sr_vector_probe_t<double, false>(kernel, false, g, n, b, (double *)x, (double *)r, (double *)p, (double *)s, (double *)u,
+                                             (const double *)wv, (const double *)invd, dcode, in, out, step, partial, stream);
+    }, (flags & AVS_VECTOR_PROBE_CODED) != 0);
+    AVS_HIP(hipGetLastError());
+    return AVS_OK;
+}
+
 #endif
 
 } // namespace avs
@@ -2380,5 +2467,44 @@ extern "C" avs_status avs_vector_update_probe(int32_t flags, int32_t g, int64_t 
     AVS_REQUIRE((size_t)scalars_bytes == avs::vector_update_probe_scalars_size(), AVS_EINVAL, "the scalars image has another size");
     return avs::vector_update_probe(flags, g, n, nb, parity, x, p, r, t, invd, dcode, spmv_partial, vpart, scalars,
                                     reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" avs_status avs_pcg_scalar_probe(int32_t which, const double *partial, int32_t nb, int32_t nred, const double *partial_b, int32_t nb_b,
+                                           int32_t nred_b, int32_t op, double tol, int32_t skip_if_done, int32_t red_off, int32_t launches,
+                                           void *scalars, int32_t scalars_bytes, double *stage_out, uint32_t *ticket_out, void *stream)
+{
+    AVS_REQUIRE(which >= AVS_SCALAR_PROBE_REDUCE_LAUNCH && which <= AVS_SCALAR_PROBE_SR_MIXED_STEP && scalars && launches >= 1 && launches <= 16,
+                AVS_EINVAL, "bad argument");
+    AVS_REQUIRE((size_t)scalars_bytes == avs::vector_update_probe_scalars_size(), AVS_EINVAL, "the scalars image has another size");
+    AVS_REQUIRE(op >= 0 && op <= 9, AVS_EINVAL, "no such scalar op");
+    if (which <= AVS_SCALAR_PROBE_REDUCE_PAIR) {
+        const bool pair = which == AVS_SCALAR_PROBE_REDUCE_PAIR;
+        AVS_REQUIRE(partial && nb >= (which == AVS_SCALAR_PROBE_REDUCE_MB ? 1 : 0) && nred >= 0 && red_off >= 0, AVS_EINVAL, "bad partial sums");
+        AVS_REQUIRE(!pair || (partial_b && nb_b >= 0 && nred_b >= 0 && red_off == 0), AVS_EINVAL, "bad second set of partial sums");
+        AVS_REQUIRE(red_off + nred + (pair ? nred_b : 0) <= 4, AVS_EINVAL, "the sums do not fit red[4]");
+    } else if (which == AVS_SCALAR_PROBE_MIXED_FINISH_INIT || which == AVS_SCALAR_PROBE_MIXED_FINISH) {
+        AVS_REQUIRE(partial && nb >= 0, AVS_EINVAL, "bad partial sums");
+    }
+    return avs::scalar_stage_probe(which, partial, nb, nred, partial_b, nb_b, nred_b, op, tol, skip_if_done, red_off, launches, scalars, stage_out,
+                                   ticket_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" avs_status avs_sr_vector_probe(int32_t kernel, int32_t flags, int32_t g, int64_t n, const double *b, void *x, void *r, void *p, void *s,
+                                          void *u, const void *w, const void *invd, const uint16_t *dcode, const void *scalars_in,
+                                          void *scalars_out, int32_t scalars_bytes, int32_t step, double *partial, void *stream)
+{
+    const bool update = kernel == AVS_SR_PROBE_UPDATE, mixed = kernel == AVS_SR_PROBE_MIXED_RESIDUAL || kernel == AVS_SR_PROBE_MIXED_RESIDUAL_INIT;
+    const bool f32 = (flags & (AVS_VECTOR_PROBE_F32 | AVS_VECTOR_PROBE_DS)) != 0;
+    AVS_REQUIRE(kernel >= AVS_SR_PROBE_INIT && kernel <= AVS_SR_PROBE_MIXED_RESIDUAL_INIT && n > 0 && g >= 1 && g <= 2048, AVS_EINVAL, "bad argument");
+    AVS_REQUIRE((flags & ~(AVS_VECTOR_PROBE_F32 | AVS_VECTOR_PROBE_DS | AVS_VECTOR_PROBE_CODED)) == 0, AVS_EINVAL, "no such flag");
+    AVS_REQUIRE(!(flags & AVS_VECTOR_PROBE_DS) || update, AVS_EINVAL, "float vectors with double scalars: k_sr_update only");
+    AVS_REQUIRE(!(flags & AVS_VECTOR_PROBE_F32) || !mixed, AVS_EINVAL, "k_sr_mixed_residual has one type form");
+    AVS_REQUIRE(!(flags & AVS_VECTOR_PROBE_CODED) || ((f32 || mixed) && dcode), AVS_EINVAL, "diagonal codes: the float forms only");
+    AVS_REQUIRE(r && u && w && invd && partial && (update || b) && (!update || (x && p && s)), AVS_EINVAL, "bad argument");
+    AVS_REQUIRE(kernel == AVS_SR_PROBE_INIT || scalars_in, AVS_EINVAL, "bad argument");
+    AVS_REQUIRE(!update || (scalars_out && (step == 0 || (step == 1 && scalars_out != scalars_in))), AVS_EINVAL, "bad scalar states");
+    AVS_REQUIRE((size_t)scalars_bytes == avs::vector_update_probe_scalars_size(), AVS_EINVAL, "the scalars image has another size");
+    return avs::sr_vector_probe(kernel, flags, g, n, b, x, r, p, s, u, w, invd, dcode, scalars_in, scalars_out, step, partial,
+                                reinterpret_cast<hipStream_t>(stream));
 }
 #endif // AVS_PROBES

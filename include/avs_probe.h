@@ -148,6 +148,52 @@ avs_status avs_vector_update_probe(int32_t flags, int32_t g, int64_t n, int32_t 
                                    const void *invd, const uint16_t *dcode, const double *spmv_partial, double *vpart, void *scalars,
                                    int32_t scalars_bytes, void *stream);
 
+/* The scalar stages of the PCG loops (csrc/avs_pcg.hip, avs_halo.hpp, avs_pcg_mixed.inl) on the caller's device arrays: `launches` (1 .. 16)
+ * back-to-back launches of the kernel `which` selects, on a device image of PcgScalars (layout and scalars_bytes as for
+ * avs_vector_update_probe) that is updated in place.
+ *   REDUCE_LAUNCH       reduce_launch's own choice between k_reduce and k_reduce_mb (the latter from 16,384 partial sums upward)
+ *   REDUCE, REDUCE_MB   k_reduce at any nb >= 0, k_reduce_mb at any nb >= 1: `partial` holds nred arrays of nb sums, folded into
+ *                       red[red_off .. red_off + nred); then the scalar op `op` (ScalarOp of avs_halo.hpp, 0: none) with `tol`
+ *   REDUCE_PAIR         k_reduce_pair: red[0 .. nred) from `partial` (nb each), red[nred .. nred + nred_b) from partial_b (nb_b each)
+ *   SCALAR              k_scalar: `op` alone
+ *   MIXED_FINISH_INIT, MIXED_FINISH   k_mixed_finish<true> / <false> on 3 / 2 arrays of nb sums in `partial`
+ *   SR_MIXED_BEGIN, SR_MIXED_STEP     k_sr_mixed_begin, k_sr_mixed_step
+ * For REDUCE_LAUNCH and REDUCE_MB the entry owns the staging array and the ticket of k_reduce_mb, laid out as the solver's workspace lays
+ * them out (64 x 4 doubles, one unsigned set to 0); slot i of the staging array starts as the NaN AVS_SCALAR_PROBE_STAGE_NAN | i.  After the
+ * last launch the entry waits for the stream and returns the staging array in stage_out (HOST, 256 doubles, may be NULL) and the ticket in
+ * *ticket_out (HOST, may be NULL; 0 for the other selectors). */
+#define AVS_SCALAR_PROBE_REDUCE_LAUNCH 0
+#define AVS_SCALAR_PROBE_REDUCE 1
+#define AVS_SCALAR_PROBE_REDUCE_MB 2
+#define AVS_SCALAR_PROBE_REDUCE_PAIR 3
+#define AVS_SCALAR_PROBE_SCALAR 4
+#define AVS_SCALAR_PROBE_MIXED_FINISH_INIT 5
+#define AVS_SCALAR_PROBE_MIXED_FINISH 6
+#define AVS_SCALAR_PROBE_SR_MIXED_BEGIN 7
+#define AVS_SCALAR_PROBE_SR_MIXED_STEP 8
+#define AVS_SCALAR_PROBE_STAGE_NAN 0x7ff8a5a500000000ull
+avs_status avs_pcg_scalar_probe(int32_t which, const double *partial, int32_t nb, int32_t nred, const double *partial_b, int32_t nb_b,
+                                int32_t nred_b, int32_t op, double tol, int32_t skip_if_done, int32_t red_off, int32_t launches,
+                                void *scalars, int32_t scalars_bytes, double *stage_out, uint32_t *ticket_out, void *stream);
+
+/* One launch of a vector kernel of the single-reduction loops on `g` workgroups (1 .. 2048) and the caller's device arrays:
+ *   INIT                  k_sr_init: r = b - w, u = D^-1 r; partial: g sums each of b.b, r.u, r.r
+ *   UPDATE                k_sr_update: p, s, x, r, u from w, alpha and beta; partial: g sums each of r.u, r.r.  step 1: the kernel first takes
+ *                         the Chronopoulos-Gear step on scalars_in and workgroup 0 stores the new state in scalars_out (another image);
+ *                         step 0: the scalars are used as they are (scalars_out may be scalars_in, and is not written)
+ *   MIXED_RESIDUAL(_INIT) k_sr_mixed_residual<., false / true>: w holds the fp64 product t64 (doubles), r and u are float; partial: g sums
+ *                         each of (INIT: b.b,) r.u, |b - t64|^2; scalars_in: the state whose `done` the plain form reads
+ * flags (of avs_vector_update_probe): none fp64 vectors; F32 float vectors and scalars (INIT, UPDATE); DS float vectors, double scalars
+ * (UPDATE); CODED with the float forms and the mixed residual: invd is the table of inverted values, dcode a 2-B code per row.  b is fp64
+ * in every form; x, r, p, s, u, w (but for the mixed residual) and invd are arrays of the vector type; x, p, s are read by UPDATE only. */
+#define AVS_SR_PROBE_INIT 0
+#define AVS_SR_PROBE_UPDATE 1
+#define AVS_SR_PROBE_MIXED_RESIDUAL 2
+#define AVS_SR_PROBE_MIXED_RESIDUAL_INIT 3
+avs_status avs_sr_vector_probe(int32_t kernel, int32_t flags, int32_t g, int64_t n, const double *b, void *x, void *r, void *p, void *s,
+                               void *u, const void *w, const void *invd, const uint16_t *dcode, const void *scalars_in, void *scalars_out,
+                               int32_t scalars_bytes, int32_t step, double *partial, void *stream);
+
 /* The device setFromTriplets (csrc/avs_assembly.hip: k_wave_slots, k_unique_rows, k_unique_long, k_merge_rows, k_merge_long and the scans
  * between them) on the CALLER's triplets: n rows, raw_ptr[n + 1] plain row offsets (raw_ptr[0] == 0), raw_col / raw_val the triplets grouped
  * by row in emission order; all device pointers.  The entry lays them out the way the row sweep emits them -- a wave of 64 rows gets 64 x its

@@ -22,6 +22,7 @@ import pytest
 import torch
 
 from adaptiveviscositysolver_amd import capi, pcg_csr
+from pcg_scalar_model import SCALARS, block_sum        # (the record of PcgScalars, wave_sum and the 256-thread block_sum live there)
 from util import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -29,9 +30,6 @@ pytestmark = pytest.mark.gpu
 D = 1                      # kVecAhead of csrc/avs_pcg.hip: trips whose loads are issued before the prologue
 BLOCK = 256
 NB_MAX = 4096
-SCALARS = np.dtype([("rho", "f8"), ("pAp", "f8"), ("rr", "f8"), ("alpha", "f8"), ("beta", "f8"), ("threshold", "f8"), ("rhs_norm2", "f8"),
-                    ("red", "f8", 4), ("iter", "i4"), ("done", "i4"), ("fault", "i4"), ("cancelled", "i4"), ("rho_alt", "f8")])
-assert SCALARS.itemsize == 112
 TYPES = {"f64": (np.float64, 2, 0), "f32": (np.float32, 4, capi.VECTOR_PROBE_F32), "f32_ds": (np.float32, 4, capi.VECTOR_PROBE_DS)}
 GUARD = 64                 # bytes of 0xA5 between two arrays of the arena: a store beyond an array's end shows up in the comparison
 
@@ -44,19 +42,6 @@ def shapes(R, g):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # the model
 # ---------------------------------------------------------------------------------------------------------------------------------------
-def wave_sum(v):
-    """v[..., 64] -> lane 0 of wave_sum (csrc/avs_halo.hpp)"""
-    for o in (32, 16, 8, 4, 2, 1):
-        v = v[..., :o] + v[..., o:2 * o]
-    return v[..., 0]
-
-
-def block_sum(v):
-    """v[nblocks, 256] doubles -> thread 0's block_sum of every workgroup"""
-    w = wave_sum(v.reshape(-1, 4, 64))
-    return ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
-
-
 def fold(a, count):
     """what every workgroup makes of `count` partial sums of the launch before"""
     acc = np.zeros(BLOCK)
