@@ -39,6 +39,9 @@ PRECONDITIONER_JACOBI, PRECONDITIONER_NONE = 0, 1
 INACTIVE, ACTIVE, UP, DOWN = 0, 1, 2, 3
 UNASSIGNED, SOLIDBOUNDARY, OUTSIDE = -1, -2, -3
 INDEX_VELOCITY, INDEX_EDGE, INDEX_CENTER = 0, 1, 2
+CHECK_LABELS, CHECK_VELOCITY_INDICES = 1, 2   # bits of `what` of avs_check_octree
+(RULE_LABEL_VALUE, RULE_COLUMN, RULE_UP, RULE_ACTIVE, RULE_INDEX_VALUE, RULE_FACE, RULE_SENTINEL, RULE_NUMBERING) = range(8)
+OCTREE_RULES = 8
 (FIELD_CENTER_WEIGHTS, FIELD_EDGE_WEIGHTS, FIELD_FACE_WEIGHTS, FIELD_VISCOSITY, FIELD_DENSITY,
  FIELD_VELOCITY, FIELD_SOLID_VELOCITY) = range(7)
 
@@ -58,7 +61,7 @@ EXPORTED_SYMBOLS = [
     "avs_spmv_tile_rows", "avs_dist_assemble", "avs_dist_get_plan_sizes", "avs_dist_get_overlap_tiles", "avs_dist_get_plan_arrays", "avs_dist_solve", "avs_dist_get_solution",
     "avs_dist_get_info", "avs_dist_init_hosted", "avs_dist_export_blob", "avs_dist_import_blobs",
     "avs_prepass_set_slab", "avs_prepass_get_window", "avs_dist_bind_prepass", "avs_dist_get_cuts", "avs_set_solution",
-    "avs_sample_velocity", "avs_get_octree_cells", "avs_prepass_get_octree_cells",
+    "avs_sample_velocity", "avs_get_octree_cells", "avs_prepass_get_octree_cells", "avs_check_octree", "avs_prepass_check_octree",
 ]
 # avs_allreduce_i32_fn: avs_status (*)(int32_t *device_data, int64_t count, void *stream, void *user)
 ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -138,6 +141,16 @@ class MatrixFormat(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(MatrixFormat)
+
+
+class OctreeCheck(C.Structure):
+    """avs_octree_check: the report of avs_check_octree / avs_prepass_check_octree"""
+    _fields_ = [("struct_size", C.c_int32), ("passed", C.c_int32), ("violations", C.c_int64 * OCTREE_RULES), ("first_rule", C.c_int32),
+                ("first_level", C.c_int32), ("first_axis", C.c_int32), ("first_ijk", C.c_int32 * 3)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(OctreeCheck)
 
 
 class ResidentPlanInfo(C.Structure):
@@ -291,6 +304,8 @@ def load(probe=False):
     L.avs_sample_velocity.argtypes = [vp, i64, vp, vp, vp, vp, i32]
     L.avs_get_octree_cells.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i32]
     L.avs_prepass_get_octree_cells.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i32]
+    L.avs_check_octree.argtypes = [vp, C.c_uint32, C.POINTER(OctreeCheck)]
+    L.avs_prepass_check_octree.argtypes = [vp, C.c_uint32, C.POINTER(OctreeCheck)]
     L.avs_get_dof_table.argtypes = [vp, i32, vp, i32]
     L.avs_plan_owners.argtypes = [i64, vp, vp, i32, i32, i32, i32, vp]
     L.avs_plan_create.argtypes = [i64, vp, vp, vp, i32, i32, C.POINTER(vp)]

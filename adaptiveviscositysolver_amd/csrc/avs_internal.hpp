@@ -17,6 +17,7 @@
 
 #include "avs.h"
 #include "avs_probe.h"
+#include "avs_check_report.hpp"
 
 struct avs_ctx;
 namespace avs {
@@ -108,7 +109,7 @@ struct Options {
     int fused_timeout_ms = 2000; // AVS_PCG_FUSED_TIMEOUT_MS: bound of that barrier's wait
     int post_dof_sample = -1;    // AVS_POST_DOF_SAMPLE: the transfer samples its nodes from the velocity DOFs (1) / by a sweep over the node lattices (0);
                                  // -1: from the DOFs when the level-0 node lattice has more than 32 x as many nodes as there are DOFs
-    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) at that many workgroups (tests: the walks wrap on small lattices)
+    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) and of the octree check (avs_check.hip) at that many workgroups (tests: the walks wrap on small lattices)
     int prepass_temporal = 1;    // AVS_PREPASS_TEMPORAL: the device pre-pass skips what its allocations already hold from their last filling (0: every run fills everything)
     int f32_vectors = -1;        // AVS_F32_VECTORS: AVS_PRECISION_F32 contexts iterate on float vectors with float scalars (what Eigen's float CG does):
                                  // 1 always, 0 never (fp64 iteration on the float system), -1 auto: where the system is too large for the
@@ -615,6 +616,21 @@ avs_status octree_cells_check_args(int64_t capacity, const int64_t *n_cells, avs
 avs_status export_octree_cells(CellsScratch &S, const CellsSource &src, hipStream_t st, const double *origin, int64_t capacity, float *position,
                                float *pscale, int32_t *level, int32_t *ijk, int64_t *n_cells, int64_t *per_level, avs_memspace where);
 
+// Octree check (avs_check.hip): avs_check_octree / avs_prepass_check_octree over one implementation, as the cell export above.  Scratch:
+// one occurrence counter per velocity id and the raw report (a count per rule + the key of the first violation).
+struct CheckScratch {
+    DevBuf<int32_t> occ;
+    DevBuf<unsigned long long> raw;
+};
+struct CheckSource {
+    const int8_t *labels[AVS_MAX_LEVELS];
+    const int32_t *vidx[AVS_MAX_LEVELS][3]; // read with AVS_CHECK_VELOCITY_INDICES only
+    int levels, n[3];  // levels present, level-0 cells per axis
+    int64_t n_velocity;
+    int grid_cap;      // Options::cells_grid_cap as of the object's creation
+};
+avs_status check_octree(CheckScratch &S, const CheckSource &src, hipStream_t st, uint32_t what, avs_octree_check *report);
+
 // avs_desc::precision == AVS_PRECISION_F32: the solution as the reference's Eigen::VectorXf holds it (avs_api.hip)
 void narrow_solution_if_f32(avs_ctx *c, double *x, int64_t n);
 
@@ -842,6 +858,7 @@ struct avs_ctx {
     uint64_t solution_gen = 1, post_nodes_gen = 0;
 
     avs::CellsScratch cells; // avs_get_octree_cells (avs_cells.hip)
+    avs::CheckScratch check; // avs_check_octree (avs_check.hip)
 
     // brick-major copy of the system used by the solve (avs_reorder.hip); perm: new -> old
     avs::DevBuf<int32_t> perm, inv, p_row_ptr, p_col;

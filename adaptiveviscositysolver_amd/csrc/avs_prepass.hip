@@ -1079,6 +1079,7 @@ struct avs_prepass {
     const float *liq = nullptr, *sol = nullptr; // the SDFs of the running call (the caller's device arrays in slab mode, else the copies above)
     int64_t counts[4] = {0, 0, 0, 0}; // velocity, edge, centre, regular
     avs::CellsScratch cells; // avs_prepass_get_octree_cells (avs_cells.hip)
+    avs::CheckScratch check; // avs_prepass_check_octree (avs_check.hip)
     double ms[4] = {0, 0, 0, 0};
     bool ready = false;
 };
@@ -1936,6 +1937,34 @@ avs_status avs_prepass_get_octree_cells(avs_prepass *p, const double *origin, in
     AVS_HIP(hipSetDevice(p->desc.device));
     Scope scope("Output Octree Geometry"); // oct.cpp:245
     return avs::export_octree_cells(p->cells, src, p->stream, origin, capacity, position, pscale, level, ijk, n_cells, per_level, where);
+}
+
+// the invariants of the label and velocity index pyramids (oct.cpp:984-1304, cpp:2896-2999): rules in include/avs.h, kernels in avs_check.hip
+avs_status avs_prepass_check_octree(avs_prepass *p, uint32_t what, avs_octree_check *report)
+{
+    (void)hipGetLastError(); // (a stale error of the host application's own HIP calls on this thread is not ours: see OptScope)
+    AVS_REQUIRE(p, AVS_EINVAL, "null argument");
+    const char *why = nullptr;
+    if (avs::check_octree_args(what, report, &why) != AVS_OK) {
+        set_error("%s", why);
+        return AVS_EINVAL;
+    }
+    AVS_REQUIRE(!p->slab.on, AVS_ESTATE, "avs_prepass_check_octree: the pre-pass is slab-local (lattices inside this rank's window only)");
+    AVS_REQUIRE(p->ready, AVS_ESTATE, "call avs_prepass_run first");
+    avs::CheckSource src{};
+    for (int l = 0; l < p->levels; ++l) {
+        src.labels[l] = p->labels[l].p;
+        for (int a = 0; a < 3; ++a) src.vidx[l][a] = p->vidx[l][a].p;
+    }
+    src.levels = p->levels;
+    src.n[0] = p->desc.nx;
+    src.n[1] = p->desc.ny;
+    src.n[2] = p->desc.nz;
+    src.n_velocity = p->counts[0];
+    src.grid_cap = p->cells_grid_cap;
+    AVS_HIP(hipSetDevice(p->desc.device));
+    Scope scope("Octree Unit Test"); // cpp:881, cpp:411
+    return avs::check_octree(p->check, src, p->stream, what, report);
 }
 
 avs_status avs_prepass_apply(avs_prepass *p, avs_ctx *ctx)

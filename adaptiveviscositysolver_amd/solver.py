@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -430,6 +431,12 @@ class ViscositySolve:
         sample_velocity).  Needs labels only: no assembly, no solve."""
         return _octree_cells(self.lib.avs_get_octree_cells, self.h, origin, device_arrays, self.device)
 
+    def check_octree(self, what=capi.CHECK_LABELS | capi.CHECK_VELOCITY_INDICES):
+        """Is the pyramid the context holds one the hot path is defined for?  (avs_check_octree: the reference's debug invariants,
+        oct.cpp:984-1304 and cpp:2896-2999, on the device.)  what: capi.CHECK_LABELS (needs labels), capi.CHECK_VELOCITY_INDICES (needs
+        the velocity index pyramid and the dof counts too), or both.  Returns an OctreeCheck."""
+        return _check_octree(self.lib.avs_check_octree, self.h, what)
+
     def edge_stencils(self):
         ne = self.info().n_edge
         return self._stencils(self.lib.avs_get_edge_stencils, ne, ne, capi.EDGE_STENCIL_CAP, capi.EDGE_BOUNDARY_CAP)
@@ -438,6 +445,26 @@ class ViscositySolve:
         nc = self.info().n_center
         return self._stencils(self.lib.avs_get_center_stencils, 3 * nc, nc, capi.CENTER_STENCIL_CAP,
                               capi.CENTER_BOUNDARY_CAP)
+
+
+@dataclass(frozen=True)
+class OctreeCheck:
+    """report of check_octree: passed; violations[rule] = lattice entries (rule 7: ids) that break rule `rule` (capi.RULE_*); first =
+    (rule, level, axis, i, j, k) of the violating entry that comes first in that order, None when passed"""
+    passed: bool
+    violations: tuple
+    first: tuple | None
+
+    def __bool__(self):
+        return self.passed
+
+
+def _check_octree(fn, handle, what):
+    """shared by ViscositySolve.check_octree and DevicePrepass.check_octree"""
+    rep = capi.OctreeCheck()
+    capi.check(fn(handle, int(what), C.byref(rep)))
+    first = None if rep.passed else (rep.first_rule, rep.first_level, rep.first_axis, *rep.first_ijk)
+    return OctreeCheck(bool(rep.passed), tuple(int(v) for v in rep.violations), first)
 
 
 def _octree_cells(fn, handle, origin, device_arrays, device):
@@ -559,6 +586,11 @@ class DevicePrepass:
         """The ACTIVE cells of the last run's label pyramid as points (avs_prepass_get_octree_cells): what ViscositySolve.octree_cells
         returns, without a solve context ("Only Output Octree")."""
         return _octree_cells(self.lib.avs_prepass_get_octree_cells, self.h, origin, device_arrays, self.device)
+
+    def check_octree(self, what=capi.CHECK_LABELS | capi.CHECK_VELOCITY_INDICES):
+        """The invariants of the last run's label and velocity index pyramids (avs_prepass_check_octree): what
+        ViscositySolve.check_octree returns, without a solve context."""
+        return _check_octree(self.lib.avs_prepass_check_octree, self.h, what)
 
     def _shape(self, kind, level, axis):
         r = [self.res[0] >> level, self.res[1] >> level, self.res[2] >> level]

@@ -135,7 +135,8 @@ const char *avs_version(void);
 /* ABI revision of this header: bumped whenever a struct layout or the set of exported entries changes (2: round 5 -- avs_matrix_format
  * carries struct_size, avs_solve_info.cancelled, avs_cancel; the measurement entries moved to libavs_probe.so in round 4).
  * Purely additive since (no revision): the entry avs_sample_velocity.
- * Purely additive since (no revision): the entries avs_get_octree_cells and avs_prepass_get_octree_cells. */
+ * Purely additive since (no revision): the entries avs_get_octree_cells and avs_prepass_get_octree_cells.
+ * Purely additive since (no revision): the entries avs_check_octree and avs_prepass_check_octree. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -393,6 +394,50 @@ avs_status avs_get_octree_cells(avs_ctx *ctx, const double *origin /* 3, NULL = 
                                 int32_t *level /* capacity */, int32_t *ijk /* capacity x 3; may be NULL */,
                                 int64_t *n_cells, int64_t *per_level /* AVS_MAX_LEVELS, may be NULL */, avs_memspace where);
 
+/* Is the pyramid the context holds one the hot path is defined for?  The reference's debug invariants -- HDK_OctreeGrid::unitTest
+ * (oct.cpp:984-1304, called at cpp:881) and octreeVelocityUnitTest (cpp:2896-2999, called at cpp:411) -- evaluated on the device over the
+ * label pyramid and the velocity index pyramid as they lie there (set by avs_set_labels / avs_set_index_field or lent by
+ * avs_prepass_apply: checked in place).  avs_prepass_check_octree (below, with the pre-pass) is the same call on a pre-pass object.
+ * Nothing else in the library calls it, and it changes nothing: every other entry behaves as without it.
+ * L = levels, the lattices are n >> l; a cell outside its lattice counts as INACTIVE.  violations[r] = lattice entries that break rule r
+ * at least once (64-bit); every rule is evaluated independently of the others:
+ *   0 LABEL_VALUE  every label of every level is 0 .. 3.
+ *   1 COLUMN       (oct.cpp:984-1080) a level-0 cell and its ancestors at levels 1 .. L-1, ascending.  INACTIVE: every ancestor is
+ *                  INACTIVE or DOWN and no INACTIVE follows a DOWN.  ACTIVE: every ancestor is DOWN.  UP: the ancestors read UP* ACTIVE
+ *                  DOWN* with exactly one ACTIVE (an UP column without an ACTIVE ancestor violates; the reference lets it pass).  Any
+ *                  other level-0 label (DOWN) violates.  Entries: level-0 cells.
+ *   2 UP           (oct.cpp:1082-1160) an UP cell at level l: l < L-1, all eight cells of its sibling block are UP, every in-lattice face
+ *                  neighbour is ACTIVE or UP.
+ *   3 ACTIVE       (oct.cpp:1162-1248, as its comment states it: the reference's loop body never runs, its guard `!passed` is false on
+ *                  entry) an ACTIVE cell at level l and each in-lattice face neighbour.  Neighbour DOWN: l > 0 and the neighbour's four
+ *                  children on the shared face are ACTIVE.  Neighbour UP: l < L-1 and the neighbour's parent is ACTIVE.
+ *   4 INDEX_VALUE  every velocity index is >= AVS_OUTSIDE and < n_velocity.
+ *   5 FACE         (cpp:2925-2965) a face with id >= 0 at level l and the labels of its backward / forward cell: ACTIVE / ACTIVE, or
+ *                  ACTIVE / UP (or UP / ACTIVE) with l < L-1 and the UP cell's parent ACTIVE.
+ *   6 SENTINEL     (cpp:2966-2973) AVS_OUTSIDE and AVS_SOLIDBOUNDARY occur at level 0 only.
+ *   7 NUMBERING    every id in [0, n_velocity) occurs exactly once over all levels and axes (entries: the ids that occur 0 times or more
+ *                  than once; ids out of range are rule 4's).  The reference does not assert it; a repeated id corrupts the dof table.
+ * what: AVS_CHECK_LABELS = rules 0 .. 3, AVS_CHECK_VELOCITY_INDICES = rules 4 .. 7, or both; any other bit: AVS_EINVAL.  what == 0: AVS_OK,
+ *   passed = 1, nothing is launched.  Rules that were not asked for report 0 violations.
+ * first_*: the violating entry that comes first by (rule, level, axis, linear index "i + rx*(j + ry*k)" in its lattice); -1 everywhere when
+ *   passed.  Label rules report axis 0, rule 1 level 0; rule 7 reports level 0, axis 0 and first_ijk = (id, 0, 0).
+ * struct_size: IN, as in avs_matrix_format -- only that many bytes of the report are written.
+ * State: AVS_CHECK_LABELS needs the labels of every level; AVS_CHECK_VELOCITY_INDICES in addition the velocity lattices of every level and
+ *   axis and the dof counts (avs_set_dof_counts); anything missing: AVS_ESTATE.  Slab-local contexts and pre-passes: AVS_ESTATE.  The
+ *   pre-pass entry needs a completed avs_prepass_run; a run that found no liquid (levels == 0) gives passed = 1.
+ * The work is enqueued on the object's stream and the call returns once the report is on the host; scratch (one int32 per velocity id, the
+ *   raw report) stays in the object.  The same lattices give the same report on every call. */
+enum { AVS_CHECK_LABELS = 1, AVS_CHECK_VELOCITY_INDICES = 2 };
+enum { AVS_RULE_LABEL_VALUE = 0, AVS_RULE_COLUMN = 1, AVS_RULE_UP = 2, AVS_RULE_ACTIVE = 3,
+       AVS_RULE_INDEX_VALUE = 4, AVS_RULE_FACE = 5, AVS_RULE_SENTINEL = 6, AVS_RULE_NUMBERING = 7, AVS_OCTREE_RULES = 8 };
+typedef struct avs_octree_check {
+    int32_t struct_size;                   /* IN: sizeof(avs_octree_check) of the caller's header */
+    int32_t passed;                        /* 1 = no rule that was asked for is violated */
+    int64_t violations[AVS_OCTREE_RULES];
+    int32_t first_rule, first_level, first_axis, first_ijk[3];
+} avs_octree_check;
+avs_status avs_check_octree(avs_ctx *ctx, uint32_t what, avs_octree_check *report);
+
 /* ------------------------------------------------------------------------------------------
  * Seam A: only the solve (replaces cpp:611-643).  CSR with int32 row pointers/columns, fp64
  * values; x_inout holds the initial guess on entry and the solution on return.
@@ -463,6 +508,9 @@ avs_status avs_prepass_get_weights(avs_prepass *pp, avs_field_kind kind /* CENTE
 avs_status avs_prepass_get_octree_cells(avs_prepass *pp, const double *origin /* 3, NULL = 0,0,0 */, int64_t capacity,
                                         float *position, float *pscale, int32_t *level, int32_t *ijk /* may be NULL */,
                                         int64_t *n_cells, int64_t *per_level /* AVS_MAX_LEVELS, may be NULL */, avs_memspace where);
+/* the invariants of the pyramids of the last run: avs_check_octree (above) on the pre-pass object -- same rules, report and state errors;
+ * enqueued on the pre-pass's stream */
+avs_status avs_prepass_check_octree(avs_prepass *pp, uint32_t what, avs_octree_check *report);
 /* hands labels, index pyramids, DOF counts, regular-grid indices and the three weight fields to a solve context created with
  * levels == info.levels on the same device.  BY REFERENCE (round 5; it used to copy ~12 full-size lattices per level set: 78 GB at
  * 1024^3): the context holds the pre-pass's allocations; the pre-pass keeps two per lattice and its next avs_prepass_run fills the set no

@@ -309,6 +309,23 @@ bool HDK_AdaptiveViscosity::solveGasSubclass(SIM_Engine &engine, SIM_Object *obj
         };
         if (!check(avs_prepass_run(h.pp, dense(liquid_sdf, liquid_dense), dense(solid_sdf, solid_dense), AVS_MEM_HOST))) return false;
         if (!check(avs_prepass_get_info(h.pp, &pinfo))) return false;
+#ifndef NDEBUG
+        // where the reference asserts octreeLabels.unitTest() (cpp:881) and octreeVelocityUnitTest() (cpp:411): the same invariants,
+        // evaluated on the device over the pyramids the run has just left there
+        avs_octree_check octree_check;
+        std::memset(&octree_check, 0, sizeof(octree_check));
+        octree_check.struct_size = (int32_t)sizeof(octree_check);
+        if (!check(avs_prepass_check_octree(h.pp, AVS_CHECK_LABELS | AVS_CHECK_VELOCITY_INDICES, &octree_check))) return false;
+        if (!octree_check.passed) {
+            UT_WorkBuffer msg;
+            msg.sprintf("avs: the octree breaks rule %d of avs_check_octree first at level %d, axis %d, entry (%d, %d, %d)", (int)octree_check.first_rule,
+                        (int)octree_check.first_level, (int)octree_check.first_axis, (int)octree_check.first_ijk[0], (int)octree_check.first_ijk[1],
+                        (int)octree_check.first_ijk[2]);
+            addError(obj, SIM_MESSAGE, msg.buffer(), UT_ERROR_WARNING);
+            h.release();
+            return false;
+        }
+#endif
     }
 
     // ---- "Output Octree Geometry" (cpp:283-294): the ACTIVE cells of the label pyramid, swept on the device ------------------
