@@ -69,7 +69,8 @@ ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_v
 PROBE_SYMBOLS = ["avs_spmv_csr", "avs_bench_spmv", "avs_spmv_sell", "avs_bench_stream", "avs_brick_spmv_probe", "avs_spmv_solver_form",
                  "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe", "avs_pcg_csr_plan",
                  "avs_merge_triplets_probe", "avs_exclusive_scan_probe", "avs_resident_plan_host", "avs_brick_form_probe", "avs_pcg_scalar_probe",
-                 "avs_sr_vector_probe"]
+                 "avs_sr_vector_probe", "avs_dist_plan_probe"]
+DIST_PLAN_PROBE_PLAN, DIST_PLAN_PROBE_TAIL = 0, 1   # avs_dist_plan_probe modes
 BRICK_PROBE_FUSED_DOT, BRICK_PROBE_F32, BRICK_PROBE_MIXED, BRICK_PROBE_VALUE_CODES, BRICK_PROBE_DONE = 1, 2, 4, 8, 16   # avs_brick_form_probe flags
 VECTOR_PROBE_F32, VECTOR_PROBE_DS, VECTOR_PROBE_CODED, VECTOR_PROBE_KEEP, VECTOR_PROBE_FUSED = 1, 2, 4, 8, 16   # avs_vector_update_probe flags
 (SCALAR_PROBE_REDUCE_LAUNCH, SCALAR_PROBE_REDUCE, SCALAR_PROBE_REDUCE_MB, SCALAR_PROBE_REDUCE_PAIR, SCALAR_PROBE_SCALAR,
@@ -202,6 +203,31 @@ class BrickFormInfo(C.Structure):
         self.struct_size = C.sizeof(BrickFormInfo)
 
 
+class DistPlanInput(C.Structure):
+    """avs_dist_plan_input (include/avs_probe.h): the device arrays avs_dist_plan_probe runs a planner core on"""
+    _fields_ = [("n", C.c_int64), ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("val", C.c_void_p), ("dof", C.c_void_p), ("perm", C.c_void_p),
+                ("owner", C.c_void_p), ("dom", C.c_void_p), ("n_dom", C.c_int64), ("levels", C.c_int32), ("cut_axis", C.c_int32),
+                ("extent", C.c_int32), ("split", C.c_int32), ("rank", C.c_int32), ("world", C.c_int32)]
+
+
+class DistPlanOutput(C.Structure):
+    """avs_dist_plan_output: host arrays (and their capacities) the probe copies the plan to"""
+    _fields_ = [(k, C.c_int64) for k in ("row_capacity", "nnz_capacity", "send_capacity", "plane_capacity")] + [(k, C.c_void_p) for k in (
+        "weights", "plane_owner", "owner", "own_global", "halo_global", "row_ptr_local", "col_local", "val_local", "send_idx", "peers",
+        "send_counts", "recv_counts", "tiles_int", "tiles_bnd", "local_ref", "rhs_local")]
+
+
+class DistPlanInfo(C.Structure):
+    """avs_dist_plan_info: the limits the device planners were compiled with and the sizes of the plan an avs_dist_plan_probe run made"""
+    _fields_ = [("struct_size", C.c_int32)] + [(k, C.c_int32) for k in (
+        "lds_planes", "scan_tile", "spmv_tile_rows", "row_group", "max_world", "nplanes", "n_peers", "n_tiles_int", "n_tiles_bnd")] + [
+        (k, C.c_int64) for k in ("n_own", "n_halo", "n_send", "nnz_local", "n_interior", "guard_bytes_hit")]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(DistPlanInfo)
+
+
 def source_fingerprint():
     """sha256 (16 hex digits) over the library's sources: kernels, internal headers, the public header.  Counter records under
     profiles/ carry the fingerprint of the tree they were taken with; bench.py only quotes a record whose fingerprint is the running one."""
@@ -286,6 +312,7 @@ def load(probe=False):
         L.avs_resident_plan_host.argtypes = [i64, vp, i32, i32, f64, i32, f64, vp, vp, vp, vp, vp, C.POINTER(ResidentHostPlanInfo)]
         L.avs_brick_form_probe.argtypes = [i64, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(f64), vp, i32,
                                            C.POINTER(BrickFormInfo), vp, i32, vp]
+        L.avs_dist_plan_probe.argtypes = [i32, C.POINTER(DistPlanInput), C.POINTER(DistPlanOutput), C.POINTER(DistPlanInfo), vp]
     L.avs_prepass_create.argtypes = [C.POINTER(PrepassDesc), C.POINTER(vp)]
     L.avs_prepass_destroy.argtypes = [vp]
     L.avs_prepass_destroy.restype = None
@@ -368,6 +395,46 @@ def brick_form_limits():
     info = BrickFormInfo()
     check(load_probe().avs_brick_form_probe(0, 0, None, None, None, None, 0, 0, 0, 0, None, None, 0, 0, 0, None, None, 0, C.byref(info), None, 0, None))
     return info
+
+
+def dist_plan_limits():
+    """avs_dist_plan_probe's limits-only call (libavs_probe.so, no GPU): the constants the device partition planners were compiled with"""
+    info = DistPlanInfo()
+    check(load_probe().avs_dist_plan_probe(0, None, None, C.byref(info), None))
+    return info
+
+
+def dist_plan_probe(mode, row_ptr, col, val, rank, world, *, dof=None, perm=None, levels=1, cut_axis=0, extent=1, owner=None, dom=None,
+                    split=0, send_capacity=None):
+    """avs_dist_plan_probe on torch DEVICE tensors (int32 row_ptr / col / dof [n, 4] / perm / dom, float64 val, uint8 owner).  Returns
+    (info, arrays): the plan's arrays as numpy arrays cut to their sizes (weights / plane_owner / owner in PLAN mode, local_ref / rhs_local in
+    TAIL mode).  Raises AvsError on a refusal."""
+    n = int(row_ptr.numel()) - 1
+    nnz = int(col.numel())
+    extent_planes = 65535
+    send_capacity = (n * max(world - 1, 1) + 1) if send_capacity is None else send_capacity
+    a = dict(weights=np.zeros(extent_planes, np.int64), plane_owner=np.zeros(extent_planes, np.int32), owner=np.zeros(n + 1, np.uint8),
+             own_global=np.zeros(n + 1, np.int32), halo_global=np.zeros(n + 1, np.int32), row_ptr_local=np.zeros(n + 2, np.int32),
+             col_local=np.zeros(nnz + 1, np.int32), val_local=np.zeros(nnz + 1, np.float64), send_idx=np.zeros(send_capacity, np.int32),
+             peers=np.zeros(32, np.int32), send_counts=np.zeros(32, np.int32), recv_counts=np.zeros(32, np.int32),
+             tiles_int=np.zeros(n + 1, np.int32), tiles_bnd=np.zeros(n + 1, np.int32), local_ref=np.zeros(n + 1, np.int32),
+             rhs_local=np.zeros(n + 1, np.float64))
+    ptr = lambda t: None if t is None else t.data_ptr()
+    inp = DistPlanInput(n=n, row_ptr=ptr(row_ptr), col=ptr(col), val=ptr(val), dof=ptr(dof), perm=ptr(perm), owner=ptr(owner), dom=ptr(dom),
+                        n_dom=0 if dom is None else int(dom.numel()), levels=levels, cut_axis=cut_axis, extent=extent, split=int(split),
+                        rank=rank, world=world)
+    out = DistPlanOutput(row_capacity=n + 1, nnz_capacity=nnz + 1, send_capacity=send_capacity, plane_capacity=extent_planes,
+                         **{k: v.ctypes.data for k, v in a.items()})
+    info = DistPlanInfo()
+    check(load_probe().avs_dist_plan_probe(mode, C.byref(inp), C.byref(out), C.byref(info), None))
+    sizes = dict(weights=info.nplanes, plane_owner=info.nplanes, owner=n, own_global=info.n_own, halo_global=info.n_halo,
+                 row_ptr_local=info.n_own + 1, col_local=info.nnz_local, val_local=info.nnz_local, send_idx=info.n_send, peers=info.n_peers,
+                 send_counts=info.n_peers, recv_counts=info.n_peers, tiles_int=info.n_tiles_int, tiles_bnd=info.n_tiles_bnd,
+                 local_ref=info.n_own + info.n_halo, rhs_local=info.n_own)
+    res = {k: v[:sizes[k]].copy() for k, v in a.items()}
+    for k in (("local_ref", "rhs_local") if mode == DIST_PLAN_PROBE_PLAN else ("weights", "plane_owner", "owner")):
+        del res[k]
+    return info, res
 
 
 def check(status):

@@ -1068,6 +1068,9 @@ __global__ __launch_bounds__(kBlock) void k_scan_apply(const int32_t *__restrict
 }
 
 size_t scan_tmp_elems(int64_t n) { return (size_t)((n + kScanTile - 1) / kScanTile) + 2; }
+#ifdef AVS_PROBES
+int scan_tile_elems() { return kScanTile; }
+#endif
 
 avs_status exclusive_scan_i32(const int32_t *in, int32_t *out, int64_t n, int32_t *tmp, size_t tmp_elems,
                               hipStream_t stream)

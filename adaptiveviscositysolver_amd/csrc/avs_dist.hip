@@ -941,42 +941,131 @@ static avs_status scan_flags(const int32_t *f, int32_t *pos, int64_t n, DevBuf<i
     return AVS_OK;
 }
 
-// fills the plan and the local system of `d` from the context's (brick-major when `ro`) system
-static avs_status plan_on_device(avs_ctx *c, PcgDist *d, int cut_axis, int extent, bool ro)
+// Guard words behind the arrays the planners fill.  The probe build (avs_dist_plan_probe) hands the planner cores a PlanGuards: plan_buf then
+// allocates every array with kBytes of a known pattern behind its last entry, and the core counts the altered bytes before it returns.  The
+// product passes null: plan_buf is DevBuf::alloc / DevBuf::reserve and nothing else, so what the product allocates does not change.
+struct PlanGuards {
+#ifdef AVS_PROBES
+    static constexpr size_t kBytes = 64;
+    static constexpr int kPattern = 0xA5;
+    static constexpr int kMaxSpans = 96;
+    const uint8_t *at[kMaxSpans];
+    size_t bytes[kMaxSpans];
+    int spans = 0;
+    int64_t hit = 0;
+#endif
+};
+#ifdef AVS_PROBES
+static avs_status plan_guard_add(PlanGuards *g, const void *p, size_t bytes, hipStream_t st)
 {
-    hipStream_t st = c->stream;
-    const int64_t n = c->n_vel;
-    const int rank = d->rank, world = d->world;
+    AVS_REQUIRE(g->spans < PlanGuards::kMaxSpans, AVS_EINTERNAL, "too many guarded arrays");
+    AVS_HIP(hipMemsetAsync(const_cast<void *>(p), PlanGuards::kPattern, bytes, st));
+    g->at[g->spans] = static_cast<const uint8_t *>(p);
+    g->bytes[g->spans++] = bytes;
+    return AVS_OK;
+}
+// an array is about to be freed: its guard can no longer be read
+static void plan_guard_drop(PlanGuards *g, const void *p, size_t bytes)
+{
+    const uint8_t *lo = static_cast<const uint8_t *>(p);
+    int k = 0;
+    for (int i = 0; i < g->spans; ++i)
+        if (!p || g->at[i] < lo || g->at[i] >= lo + bytes) { g->at[k] = g->at[i]; g->bytes[k++] = g->bytes[i]; }
+    g->spans = k;
+}
+// counts the guard bytes that no longer hold the pattern (the stream is idle afterwards) and forgets the spans
+static avs_status plan_guard_check(PlanGuards *g, hipStream_t st)
+{
+    AVS_HIP(hipStreamSynchronize(st));
+    uint8_t h[PlanGuards::kBytes + 16];
+    for (int i = 0; i < g->spans; ++i) {
+        AVS_HIP(hipMemcpy(h, g->at[i], g->bytes[i], hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < g->bytes[i]; ++b) g->hit += h[b] != (uint8_t)PlanGuards::kPattern;
+    }
+    g->spans = 0;
+    return AVS_OK;
+}
+#endif
+// `count` entries of `b`: DevBuf::reserve (`keep`: scratch kept across frames) or DevBuf::alloc; with guards, exactly count entries + the guard
+template <typename T>
+static avs_status plan_buf(PlanGuards *g, DevBuf<T> &b, size_t count, bool keep, hipStream_t st)
+{
+#ifdef AVS_PROBES
+    if (g) {
+        const size_t extra = (PlanGuards::kBytes + sizeof(T) - 1) / sizeof(T);
+        if (b.p) plan_guard_drop(g, b.p, b.n * sizeof(T));
+        b.release();
+        AVS_TRY(b.alloc(count + extra));
+        return plan_guard_add(g, b.p + count, extra * sizeof(T), st);
+    }
+#endif
+    (void)g;
+    (void)st;
+    return keep ? b.reserve(count) : b.alloc(count);
+}
+
+// What the device planner reads, as plain arrays (device pointers): a CSR of n rows whose columns lie in [0, n), one dof record per DOF
+// (level | axis << 8, i, j, k), perm (row i stands for the DOF perm[i]; null: identity), the cut geometry and the rank.
+struct PlanKeep;
+struct PlanSource {
+    int64_t n = 0;
+    const int32_t *row_ptr = nullptr, *col = nullptr;
+    const double *val = nullptr;
+    const int32_t *vdof = nullptr, *perm = nullptr;
+    int levels = 1, cut_axis = 0, extent = 1;
+    int rank = 0, world = 1;
+    hipStream_t stream = nullptr;
+    PlanKeep *keep = nullptr; // null (the product): the intermediate results below are scratch
+};
+// intermediate results a caller may ask the cores to keep (avs_dist_plan_probe) + the guard words of that run
+struct PlanKeep {
+    std::vector<int64_t> weight;   // per plane
+    std::vector<int> plane_owner;
+    DevBuf<uint8_t> owner;         // per row
+    DevBuf<int32_t> halo;          // the halo ids, grouped by owner, ascending inside a group (n_halo entries)
+    int64_t n_interior = -1;       // the tail's row split: rows that read no other rank (-1: not split)
+    PlanGuards guards;
+};
+
+// fills the plan and the local system of `d` (rank and world from `s`) from the system in `s`
+static avs_status plan_from_source(PcgDist *d, const PlanSource &s)
+{
+    hipStream_t st = s.stream;
+    const int64_t n = s.n;
+    const int rank = s.rank, world = s.world;
     AVS_REQUIRE(world <= 32, AVS_EINVAL, "at most 32 ranks");
-    const int32_t *g_rp = ro ? c->p_row_ptr.p : c->row_ptr.p, *g_col = ro ? c->p_col.p : c->col.p;
-    const double *g_val = ro ? c->p_val.p : c->val.p;
-    const bool vi = false; // the local rows get their own dictionaries afterwards (build_matrix_index)
-    const int shift = c->desc.levels - 1;
+    const int32_t *g_rp = s.row_ptr, *g_col = s.col;
+    const double *g_val = s.val;
+    const int cut_axis = s.cut_axis, extent = s.extent;
+    const int shift = s.levels - 1;
     const int nplanes = (extent + (1 << shift) - 1) >> shift;
     AVS_REQUIRE(nplanes <= 65535, AVS_EINVAL, "too many cut planes");
+    PlanGuards *G = s.keep ? &s.keep->guards : nullptr;
 
     DevBuf<uint16_t> plane;
     DevBuf<unsigned long long> weight;
-    DevBuf<int32_t> plane_owner, flag, pos, g2l, scan_tmp, halo_tmp;
-    DevBuf<uint8_t> owner, is_halo;
+    DevBuf<int32_t> plane_owner, flag, pos, g2l, scan_tmp, halo_scratch;
+    DevBuf<uint8_t> owner_scratch, is_halo;
     DevBuf<uint32_t> needed_by;
-    AVS_TRY(plane.alloc((size_t)n));
-    AVS_TRY(weight.alloc((size_t)nplanes));
-    AVS_TRY(plane_owner.alloc((size_t)nplanes));
-    AVS_TRY(flag.alloc((size_t)n + 1));
-    AVS_TRY(pos.alloc((size_t)n + 1));
-    AVS_TRY(g2l.alloc((size_t)n));
-    AVS_TRY(scan_tmp.alloc(scan_tmp_elems(n + 1)));
-    AVS_TRY(owner.alloc((size_t)n));
-    AVS_TRY(is_halo.alloc((size_t)n));
-    AVS_TRY(needed_by.alloc((size_t)n));
+    DevBuf<uint8_t> &owner = s.keep ? s.keep->owner : owner_scratch;
+    DevBuf<int32_t> &halo_tmp = s.keep ? s.keep->halo : halo_scratch;
+    AVS_TRY(plan_buf(G, plane, (size_t)n, false, st));
+    AVS_TRY(plan_buf(G, weight, (size_t)nplanes, false, st));
+    AVS_TRY(plan_buf(G, plane_owner, (size_t)nplanes, false, st));
+    AVS_TRY(plan_buf(G, flag, (size_t)n + 1, false, st));
+    AVS_TRY(plan_buf(G, pos, (size_t)n + 1, false, st));
+    AVS_TRY(plan_buf(G, g2l, (size_t)n, false, st));
+    AVS_TRY(plan_buf(G, scan_tmp, scan_tmp_elems(n + 1), false, st));
+    AVS_TRY(plan_buf(G, owner, (size_t)n, false, st));
+    AVS_TRY(plan_buf(G, is_halo, (size_t)n, false, st));
+    AVS_TRY(plan_buf(G, needed_by, (size_t)n, false, st));
     AVS_HIP(hipMemsetAsync(weight.p, 0, (size_t)nplanes * sizeof(unsigned long long), st));
     AVS_HIP(hipMemsetAsync(is_halo.p, 0, (size_t)n, st));
     AVS_HIP(hipMemsetAsync(needed_by.p, 0, (size_t)n * sizeof(uint32_t), st));
     AVS_HIP(hipMemsetAsync(g2l.p, 0xFF, (size_t)n * sizeof(int32_t), st));
 
     // 1. slabs: per-plane weights -> (host, O(planes)) greedy cuts -> owner of every row
-    hipLaunchKernelGGL(k_plan_planes, dim3(2048), dim3(256), 0, st, n, c->vdof.p, ro ? c->perm.p : nullptr, g_rp, cut_axis, extent,
+    hipLaunchKernelGGL(k_plan_planes, dim3(2048), dim3(256), 0, st, n, s.vdof, s.perm, g_rp, cut_axis, extent,
                        shift, nplanes, plane.p, weight.p);
     std::vector<unsigned long long> h_w((size_t)nplanes);
     AVS_HIP(hipMemcpyAsync(h_w.data(), weight.p, h_w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -986,11 +1075,15 @@ static avs_status plan_on_device(avs_ctx *c, PcgDist *d, int cut_axis, int exten
     plane_owners_from_weights(h_w64.data(), nplanes, world, h_po.data());
     AVS_HIP(hipMemcpyAsync(plane_owner.p, h_po.data(), h_po.size() * sizeof(int), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_plan_owner, dim3(grid256(n)), dim3(256), 0, st, n, plane.p, plane_owner.p, rank, owner.p, flag.p);
+    if (s.keep) {
+        s.keep->weight = h_w64;
+        s.keep->plane_owner = h_po;
+    }
 
     // 2. owned rows, ascending
     int64_t n_own = 0;
     AVS_TRY(scan_flags(flag.p, pos.p, n, scan_tmp, &n_own, st));
-    AVS_TRY(d->own_global.alloc((size_t)n_own));
+    AVS_TRY(plan_buf(G, d->own_global, (size_t)n_own, false, st));
     hipLaunchKernelGGL(k_plan_scatter, dim3(grid256(n)), dim3(256), 0, st, n, flag.p, pos.p, (const int32_t *)nullptr, d->own_global.p,
                        g2l.p, 0);
 
@@ -999,7 +1092,8 @@ static avs_status plan_on_device(avs_ctx *c, PcgDist *d, int cut_axis, int exten
 
     // 4. halo numbering (grouped by owner) and send lists (ascending owned entries each peer reads)
     std::vector<int64_t> recv_cnt((size_t)world, 0), send_cnt((size_t)world, 0);
-    AVS_TRY(halo_tmp.alloc((size_t)n)); // halo ids are only needed to number them; the list itself is not kept
+    // halo ids are only needed to number them: every peer's scatter starts at 0 unless the caller keeps the list
+    AVS_TRY(plan_buf(G, halo_tmp, (size_t)n, false, st));
     int64_t n_halo = 0;
     for (int q = 0; q < world; ++q) {
         if (q == rank) continue;
@@ -1007,7 +1101,7 @@ static avs_status plan_on_device(avs_ctx *c, PcgDist *d, int cut_axis, int exten
         AVS_TRY(scan_flags(flag.p, pos.p, n, scan_tmp, &recv_cnt[(size_t)q], st));
         if (recv_cnt[(size_t)q])
             hipLaunchKernelGGL(k_plan_scatter, dim3(grid256(n)), dim3(256), 0, st, n, flag.p, pos.p, (const int32_t *)nullptr,
-                               halo_tmp.p, g2l.p, (int32_t)(n_own + n_halo));
+                               halo_tmp.p + (s.keep ? n_halo : 0), g2l.p, (int32_t)(n_own + n_halo));
         n_halo += recv_cnt[(size_t)q];
     }
     int64_t n_send = 0;
@@ -1017,8 +1111,8 @@ static avs_status plan_on_device(avs_ctx *c, PcgDist *d, int cut_axis, int exten
         AVS_TRY(scan_flags(flag.p, pos.p, n, scan_tmp, &send_cnt[(size_t)q], st));
         n_send += send_cnt[(size_t)q];
     }
-    AVS_TRY(d->send_idx.alloc((size_t)n_send));
-    AVS_TRY(d->sendbuf.alloc((size_t)n_send));
+    AVS_TRY(plan_buf(G, d->send_idx, (size_t)n_send, false, st));
+    AVS_TRY(plan_buf(G, d->sendbuf, (size_t)n_send, false, st));
     {
         int64_t off = 0;
         for (int q = 0; q < world; ++q) {
@@ -1040,42 +1134,45 @@ static avs_status plan_on_device(avs_ctx *c, PcgDist *d, int cut_axis, int exten
             d->recv_counts.push_back((int32_t)recv_cnt[(size_t)q]);
         }
 
-    // 5. local CSR
-    AVS_TRY(d->row_ptr.alloc((size_t)n_own + 1));
+    // 5. local CSR: k_plan_local_len leaves the n_own row lengths (and a 0 behind them); the scan of n_own inputs writes the n_own + 1 row
+    // pointers (out[n_own] = total)
+    AVS_TRY(plan_buf(G, d->row_ptr, (size_t)n_own + 1, false, st));
     hipLaunchKernelGGL(k_plan_local_len, dim3(grid256(n_own + 1)), dim3(256), 0, st, n_own, d->own_global.p, g_rp, flag.p);
-    AVS_TRY(exclusive_scan_i32(flag.p, d->row_ptr.p, n_own + 1, scan_tmp.p, scan_tmp.n, st));
+    AVS_TRY(exclusive_scan_i32(flag.p, d->row_ptr.p, n_own, scan_tmp.p, scan_tmp.n, st));
     int32_t nnz_local = 0;
     AVS_HIP(hipMemcpyAsync(&nnz_local, d->row_ptr.p + n_own, 4, hipMemcpyDeviceToHost, st));
     AVS_HIP(hipStreamSynchronize(st));
-    AVS_TRY(d->col.alloc((size_t)nnz_local));
-    AVS_TRY(d->val.alloc((size_t)nnz_local));
+    AVS_TRY(plan_buf(G, d->col, (size_t)nnz_local, false, st));
+    AVS_TRY(plan_buf(G, d->val, (size_t)nnz_local, false, st));
     const int T = spmv_tile_rows();
     const int64_t ntiles = (n_own + T - 1) / T;
     DevBuf<int32_t> tile_bnd, tile_int, tile_pos;
-    AVS_TRY(tile_bnd.alloc((size_t)ntiles + 1));
-    AVS_TRY(tile_int.alloc((size_t)ntiles + 1));
-    AVS_TRY(tile_pos.alloc((size_t)ntiles + 1));
+    AVS_TRY(plan_buf(G, tile_bnd, (size_t)ntiles + 1, false, st));
+    AVS_TRY(plan_buf(G, tile_int, (size_t)ntiles + 1, false, st));
+    AVS_TRY(plan_buf(G, tile_pos, (size_t)ntiles + 1, false, st));
     AVS_HIP(hipMemsetAsync(tile_bnd.p, 0, ((size_t)ntiles + 1) * 4, st));
     if (n_own)
         hipLaunchKernelGGL(k_plan_local_rows, dim3(8192), dim3(256), 0, st, n_own, d->own_global.p, g_rp, g_col, g_val,
                            (const uint16_t *)nullptr, g2l.p, d->row_ptr.p, d->col.p, d->val.p, (uint16_t *)nullptr, T, tile_bnd.p);
-    (void)vi;
 
     // 6. tile lists for the overlap of the exchange with the interior rows
     int64_t n_bnd = 0, n_int = 0;
     AVS_TRY(scan_flags(tile_bnd.p, tile_pos.p, ntiles, scan_tmp, &n_bnd, st));
-    AVS_TRY(d->tiles_bnd.alloc((size_t)n_bnd));
+    AVS_TRY(plan_buf(G, d->tiles_bnd, (size_t)n_bnd, false, st));
     if (n_bnd)
         hipLaunchKernelGGL(k_plan_scatter, dim3(grid256(ntiles)), dim3(256), 0, st, ntiles, tile_bnd.p, tile_pos.p, (const int32_t *)nullptr,
                            d->tiles_bnd.p, (int32_t *)nullptr, 0);
     if (ntiles) hipLaunchKernelGGL(k_plan_not, dim3(grid256(ntiles)), dim3(256), 0, st, ntiles, tile_bnd.p, tile_int.p);
     AVS_TRY(scan_flags(tile_int.p, tile_pos.p, ntiles, scan_tmp, &n_int, st));
-    AVS_TRY(d->tiles_int.alloc((size_t)n_int));
+    AVS_TRY(plan_buf(G, d->tiles_int, (size_t)n_int, false, st));
     if (n_int)
         hipLaunchKernelGGL(k_plan_scatter, dim3(grid256(ntiles)), dim3(256), 0, st, ntiles, tile_int.p, tile_pos.p, (const int32_t *)nullptr,
                            d->tiles_int.p, (int32_t *)nullptr, 0);
     AVS_HIP(hipGetLastError());
     AVS_HIP(hipStreamSynchronize(st)); // temporaries die here
+#ifdef AVS_PROBES
+    if (G) AVS_TRY(plan_guard_check(G, st));
+#endif
     d->n_tiles_int = (int)n_int;
     d->n_tiles_bnd = (int)n_bnd;
     d->n_own = n_own;
@@ -1083,6 +1180,25 @@ static avs_status plan_on_device(avs_ctx *c, PcgDist *d, int cut_axis, int exten
     d->n_send = n_send;
     d->nnz_local = nnz_local;
     return AVS_OK;
+}
+
+// the plan of the context's (brick-major when `ro`) system
+static avs_status plan_on_device(avs_ctx *c, PcgDist *d, int cut_axis, int extent, bool ro)
+{
+    PlanSource s;
+    s.n = c->n_vel;
+    s.row_ptr = ro ? c->p_row_ptr.p : c->row_ptr.p;
+    s.col = ro ? c->p_col.p : c->col.p;
+    s.val = ro ? c->p_val.p : c->val.p; // (the local rows get their own dictionaries afterwards: build_matrix_index)
+    s.vdof = c->vdof.p;
+    s.perm = ro ? c->perm.p : nullptr;
+    s.levels = c->desc.levels;
+    s.cut_axis = cut_axis;
+    s.extent = extent;
+    s.rank = d->rank;
+    s.world = d->world;
+    s.stream = c->stream;
+    return plan_from_source(d, s);
 }
 
 
@@ -1292,19 +1408,37 @@ static avs_status dist_build_brick(avs_ctx *c, PcgDist *d)
 // rows, halo numbering, send lists, local column ids, tile lists.  Ids live in an id space of `n_ids` entries (brick-major ids / the
 // reference's ids); `dom` (null: 0 .. n_dom) lists, in brick-major order, the ids a halo column can have; owner / is_halo / g2l are
 // indexed by id.  inv (reference id -> id, null: identity), perm (id -> reference id, null: identity).
+// dist_assemble_tail builds the rank's rows and its warm start; everything between the two is dist_tail_from_rows, a function of plain
+// arguments (avs_dist_plan_probe runs it on a caller's rows).
+//
+// The arguments of that core: the rank's n_own rows stand in d->row_ptr / col / val / rhs as assemble_rows leaves them
+// (nnz_local entries, columns still in the numbering `inv` reads), d->own_global holds their ids and *ids the reference DOFs behind them;
+// g2l already maps the owned ids to 0 .. n_own, is_halo is zero, owner[id] is the id's rank (0xFF: outside the rank's window).  The core
+// swaps *ids, like the rows, when it reorders them.  flag and pos hold max(n_own, n_dom) + 1 entries, scan_tmp enough for a scan of as many.
+struct TailSource {
+    DevBuf<int32_t> *ids = nullptr;
+    int64_t n_own = 0, nnz_local = 0;
+    const int32_t *dom = nullptr;
+    int64_t n_dom = 0;
+    const int32_t *inv = nullptr, *perm = nullptr;
+    const uint8_t *owner = nullptr;
+    uint8_t *is_halo = nullptr;
+    int32_t *g2l = nullptr, *flag = nullptr, *pos = nullptr;
+    DevBuf<int32_t> *scan_tmp = nullptr;
+    int rank = 0, world = 1;
+    bool split = false; // [interior | halo-reading] local row order
+    hipStream_t stream = nullptr;
+    PlanKeep *keep = nullptr; // null (the product): the halo id list is scratch
+};
+static avs_status dist_tail_from_rows(PcgDist *d, const TailSource &s);
+
 static avs_status dist_assemble_tail(avs_ctx *c, PcgDist *d, DevBuf<int32_t> &ids, int64_t n_own, int64_t n_ids, const int32_t *dom, int64_t n_dom,
                                      const int32_t *inv, const int32_t *perm, DevBuf<uint8_t> &owner, DevBuf<uint8_t> &is_halo, DevBuf<int32_t> &g2l,
                                      DevBuf<int32_t> &flag, DevBuf<int32_t> &pos, DevBuf<int32_t> &scan_tmp)
 {
     hipStream_t st = c->stream;
-    const int rank = d->rank, world = d->world;
-    const int64_t n = n_dom;
-    DevBuf<int32_t> &halo_tmp = d->ws.halo_tmp;
-    DevBuf<uint32_t> &needed_by = d->ws.needed_by;
-    DevBuf<int> &mark_err = d->ws.mark_err;
-    AVS_TRY(mark_err.reserve(1));
-    AVS_HIP(hipMemsetAsync(mark_err.p, 0, sizeof(int), st));
-    PhaseTrace tr(st, "tail", cur_opt().trace_phases != 0);
+    (void)n_ids;
+    PhaseTrace tr(st, "tail rows", cur_opt().trace_phases != 0);
     // restriction (warm start, also the mass term of the right-hand side) and rows of this rank only;
     // columns still in the reference numbering
     AVS_TRY(build_initial_guess_rows(c, ids.p, n_own));
@@ -1312,13 +1446,63 @@ static avs_status dist_assemble_tail(avs_ctx *c, PcgDist *d, DevBuf<int32_t> &id
     int64_t nnz_local = 0;
     AVS_TRY(assemble_rows(c, ids.p, n_own, d->row_ptr, d->col, d->val, d->rhs, &nnz_local, nullptr));
     tr.mark("assemble_rows");
-    AVS_TRY(needed_by.reserve((size_t)n_own));
-    if (n_own) hipLaunchKernelGGL(k_da_mark, dim3(8192), dim3(256), 0, st, n_own, d->row_ptr.p, d->col.p, inv, owner.p, rank, is_halo.p,
+    TailSource s;
+    s.ids = &ids;
+    s.n_own = n_own;
+    s.nnz_local = nnz_local;
+    s.dom = dom;
+    s.n_dom = n_dom;
+    s.inv = inv;
+    s.perm = perm;
+    s.owner = owner.p;
+    s.is_halo = is_halo.p;
+    s.g2l = g2l.p;
+    s.flag = flag.p;
+    s.pos = pos.p;
+    s.scan_tmp = &scan_tmp;
+    s.rank = d->rank;
+    s.world = d->world;
+    // A slab the brick-structured form will serve keeps the plain ascending (brick-major) row order: its tiles are whole bricks, and the
+    // ones that read halo columns are moved to the end of the WALK order instead (build_brick_form), which keeps them full.  With the
+    // [interior | halo-reading] split every brick next to a cut would fall into two part-filled tiles.
+    s.split = d->world > 1 && cur_opt().dist_split_rows != 0 && !dist_brick_wanted(c, n_own);
+    s.stream = st;
+    AVS_TRY(dist_tail_from_rows(d, s));
+    // warm start of the owned DOFs (in the order the core left the rows in)
+    AVS_TRY(d->x0.reserve((size_t)n_own));
+    AVS_TRY(d->x.reserve((size_t)n_own));
+    if (n_own) hipLaunchKernelGGL(k_gather_i<double>, dim3(grid256(n_own)), dim3(256), 0, st, c->x0.p, ids.p, d->x0.p, n_own);
+    AVS_HIP(hipGetLastError());
+    AVS_HIP(hipStreamSynchronize(st));
+    tr.mark("x0");
+    return AVS_OK;
+}
+
+// Everything from the rows' marks onward: peer mask, row split, halo numbering, send lists, local column ids, tile lists, local_ref
+static avs_status dist_tail_from_rows(PcgDist *d, const TailSource &s)
+{
+    hipStream_t st = s.stream;
+    const int rank = s.rank, world = s.world;
+    const int64_t n = s.n_dom, n_own = s.n_own, nnz_local = s.nnz_local;
+    const int32_t *dom = s.dom, *inv = s.inv, *perm = s.perm;
+    const uint8_t *owner = s.owner;
+    uint8_t *is_halo = s.is_halo;
+    int32_t *g2l = s.g2l, *flag = s.flag, *pos = s.pos;
+    DevBuf<int32_t> &ids = *s.ids, &scan_tmp = *s.scan_tmp;
+    PlanGuards *G = s.keep ? &s.keep->guards : nullptr;
+    DevBuf<int32_t> &halo_tmp = d->ws.halo_tmp;
+    DevBuf<uint32_t> &needed_by = d->ws.needed_by;
+    DevBuf<int> &mark_err = d->ws.mark_err;
+    AVS_TRY(plan_buf(G, mark_err, 1, true, st));
+    AVS_HIP(hipMemsetAsync(mark_err.p, 0, sizeof(int), st));
+    PhaseTrace tr(st, "tail", cur_opt().trace_phases != 0);
+    AVS_TRY(plan_buf(G, needed_by, (size_t)n_own, true, st));
+    if (n_own) hipLaunchKernelGGL(k_da_mark, dim3(8192), dim3(256), 0, st, n_own, d->row_ptr.p, d->col.p, inv, owner, rank, is_halo,
                                   needed_by.p, mark_err.p);
     uint32_t peer_mask = 0u; // (a slab talks to its neighbours: the per-rank scans below run for them only -- each is a scan + a host round trip)
     {
         DevBuf<uint32_t> &pm = d->ws.pm;
-        AVS_TRY(pm.reserve(1));
+        AVS_TRY(plan_buf(G, pm, 1, true, st));
         AVS_HIP(hipMemsetAsync(pm.p, 0, sizeof(uint32_t), st));
         if (n_own) hipLaunchKernelGGL(k_da_peer_mask, dim3(1024), dim3(256), 0, st, n_own, (const uint32_t *)needed_by.p, pm.p);
         int e = 0;
@@ -1328,29 +1512,24 @@ static avs_status dist_assemble_tail(avs_ctx *c, PcgDist *d, DevBuf<int32_t> &id
         AVS_REQUIRE(e == 0, AVS_EINTERNAL, "slab-local assembly: a row reads a column outside the rank's window (index margin too small)");
     }
     tr.mark("mark columns");
-    bool split = world > 1;
-    split = split && cur_opt().dist_split_rows != 0;
-    // A slab the brick-structured form will serve keeps the plain ascending (brick-major) row order: its tiles are whole bricks, and the
-    // ones that read halo columns are moved to the end of the WALK order instead (build_brick_form), which keeps them full.  With the
-    // [interior | halo-reading] split every brick next to a cut would fall into two part-filled tiles.
-    if (dist_brick_wanted(c, n_own)) split = false;
-    if (split && n_own) { // [interior | halo-reading] local row order (see k_da_new_index)
+    if (s.split && n_own) { // [interior | halo-reading] local row order (see k_da_new_index)
         DevBuf<int32_t> &new_of = d->alt_new_of, &len_new = d->alt_len, &rp2 = d->alt_row_ptr, &col2 = d->alt_col, &own2 = d->alt_own, &ids2 = d->alt_ids;
         DevBuf<double> &val2 = d->alt_val, &rhs2 = d->alt_rhs;
         DevBuf<uint32_t> &nb2 = d->alt_nb;
-        AVS_TRY(new_of.reserve((size_t)n_own));
-        AVS_TRY(len_new.reserve((size_t)n_own + 1));
-        AVS_TRY(rp2.reserve((size_t)n_own + 1));
-        AVS_TRY(col2.reserve((size_t)nnz_local));
-        AVS_TRY(val2.reserve((size_t)nnz_local));
-        AVS_TRY(own2.reserve((size_t)n_own));
-        AVS_TRY(ids2.reserve((size_t)n_own));
-        AVS_TRY(rhs2.reserve((size_t)n_own));
-        AVS_TRY(nb2.reserve((size_t)n_own));
-        hipLaunchKernelGGL(k_da_flag_send, dim3(grid256(n_own)), dim3(256), 0, st, n_own, (const uint32_t *)needed_by.p, -1, flag.p); // q = -1: "reads nobody"
+        AVS_TRY(plan_buf(G, new_of, (size_t)n_own, true, st));
+        AVS_TRY(plan_buf(G, len_new, (size_t)n_own + 1, true, st));
+        AVS_TRY(plan_buf(G, rp2, (size_t)n_own + 1, true, st));
+        AVS_TRY(plan_buf(G, col2, (size_t)nnz_local, true, st));
+        AVS_TRY(plan_buf(G, val2, (size_t)nnz_local, true, st));
+        AVS_TRY(plan_buf(G, own2, (size_t)n_own, true, st));
+        AVS_TRY(plan_buf(G, ids2, (size_t)n_own, true, st));
+        AVS_TRY(plan_buf(G, rhs2, (size_t)n_own, true, st));
+        AVS_TRY(plan_buf(G, nb2, (size_t)n_own, true, st));
+        hipLaunchKernelGGL(k_da_flag_send, dim3(grid256(n_own)), dim3(256), 0, st, n_own, (const uint32_t *)needed_by.p, -1, flag); // q = -1: "reads nobody"
         int64_t n_interior = 0;
-        AVS_TRY(scan_flags(flag.p, pos.p, n_own, scan_tmp, &n_interior, st));
-        hipLaunchKernelGGL(k_da_new_index, dim3(grid256(n_own + 1)), dim3(256), 0, st, n_own, (const uint32_t *)needed_by.p, (const int32_t *)pos.p,
+        AVS_TRY(scan_flags(flag, pos, n_own, scan_tmp, &n_interior, st));
+        if (s.keep) s.keep->n_interior = n_interior;
+        hipLaunchKernelGGL(k_da_new_index, dim3(grid256(n_own + 1)), dim3(256), 0, st, n_own, (const uint32_t *)needed_by.p, (const int32_t *)pos,
                            n_interior, (const int32_t *)d->row_ptr.p, new_of.p, len_new.p);
         AVS_TRY(exclusive_scan_i32(len_new.p, rp2.p, n_own, scan_tmp.p, scan_tmp.n, st));
         hipLaunchKernelGGL(k_da_move_rows, dim3(8192), dim3(256), 0, st, n_own, (const int32_t *)new_of.p, (const int32_t *)d->row_ptr.p,
@@ -1360,7 +1539,7 @@ static avs_status dist_assemble_tail(avs_ctx *c, PcgDist *d, DevBuf<int32_t> &id
         hipLaunchKernelGGL(k_da_move<int32_t>, dim3(g1), dim3(256), 0, st, n_own, (const int32_t *)new_of.p, (const int32_t *)ids.p, ids2.p);
         hipLaunchKernelGGL(k_da_move<double>, dim3(g1), dim3(256), 0, st, n_own, (const int32_t *)new_of.p, (const double *)d->rhs.p, rhs2.p);
         hipLaunchKernelGGL(k_da_move<uint32_t>, dim3(g1), dim3(256), 0, st, n_own, (const int32_t *)new_of.p, (const uint32_t *)needed_by.p, nb2.p);
-        hipLaunchKernelGGL(k_da_g2l_own, dim3(g1), dim3(256), 0, st, n_own, (const int32_t *)own2.p, g2l.p);
+        hipLaunchKernelGGL(k_da_g2l_own, dim3(g1), dim3(256), 0, st, n_own, (const int32_t *)own2.p, g2l);
         AVS_HIP(hipGetLastError());
         AVS_HIP(hipStreamSynchronize(st));
         auto swap_i = [](DevBuf<int32_t> &a, DevBuf<int32_t> &b) { std::swap(a.p, b.p); std::swap(a.n, b.n); };
@@ -1376,32 +1555,33 @@ static avs_status dist_assemble_tail(avs_ctx *c, PcgDist *d, DevBuf<int32_t> &id
     tr.mark("row order split");
     // halo numbering (grouped by owner, ascending) and send lists (ascending owned rows that read a DOF of q)
     std::vector<int64_t> recv_cnt((size_t)world, 0), send_cnt((size_t)world, 0);
-    AVS_TRY(halo_tmp.reserve((size_t)(n > 0 ? n : 1)));
+    // halo ids are only needed to number them: every peer's scatter starts at 0 unless the caller keeps the list
+    AVS_TRY(plan_buf(G, halo_tmp, (size_t)(n > 0 ? n : 1), true, st));
     int64_t n_halo = 0, n_send = 0;
     for (int q = 0; q < world; ++q) {
         if (q == rank || !((peer_mask >> q) & 1u)) continue;
-        hipLaunchKernelGGL(k_plan_flag_halo, dim3(grid256(n)), dim3(256), 0, st, n, is_halo.p, owner.p, q, flag.p, dom);
-        AVS_TRY(scan_flags(flag.p, pos.p, n, scan_tmp, &recv_cnt[(size_t)q], st));
+        hipLaunchKernelGGL(k_plan_flag_halo, dim3(grid256(n)), dim3(256), 0, st, n, is_halo, owner, q, flag, dom);
+        AVS_TRY(scan_flags(flag, pos, n, scan_tmp, &recv_cnt[(size_t)q], st));
         if (recv_cnt[(size_t)q])
-            hipLaunchKernelGGL(k_plan_scatter, dim3(grid256(n)), dim3(256), 0, st, n, flag.p, pos.p, (const int32_t *)nullptr,
-                               halo_tmp.p, g2l.p, (int32_t)(n_own + n_halo), dom);
+            hipLaunchKernelGGL(k_plan_scatter, dim3(grid256(n)), dim3(256), 0, st, n, flag, pos, (const int32_t *)nullptr,
+                               halo_tmp.p + (s.keep ? n_halo : 0), g2l, (int32_t)(n_own + n_halo), dom);
         n_halo += recv_cnt[(size_t)q];
     }
     for (int q = 0; q < world; ++q) {
         if (q == rank || !n_own || !((peer_mask >> q) & 1u)) continue;
-        hipLaunchKernelGGL(k_da_flag_send, dim3(grid256(n_own)), dim3(256), 0, st, n_own, needed_by.p, q, flag.p);
-        AVS_TRY(scan_flags(flag.p, pos.p, n_own, scan_tmp, &send_cnt[(size_t)q], st));
+        hipLaunchKernelGGL(k_da_flag_send, dim3(grid256(n_own)), dim3(256), 0, st, n_own, needed_by.p, q, flag);
+        AVS_TRY(scan_flags(flag, pos, n_own, scan_tmp, &send_cnt[(size_t)q], st));
         n_send += send_cnt[(size_t)q];
     }
-    AVS_TRY(d->send_idx.reserve((size_t)n_send));
-    AVS_TRY(d->sendbuf.reserve((size_t)n_send));
+    AVS_TRY(plan_buf(G, d->send_idx, (size_t)n_send, true, st));
+    AVS_TRY(plan_buf(G, d->sendbuf, (size_t)n_send, true, st));
     {
         int64_t off = 0;
         for (int q = 0; q < world; ++q) {
             if (q == rank || !send_cnt[(size_t)q]) continue;
-            hipLaunchKernelGGL(k_da_flag_send, dim3(grid256(n_own)), dim3(256), 0, st, n_own, needed_by.p, q, flag.p);
-            AVS_TRY(exclusive_scan_i32(flag.p, pos.p, n_own, scan_tmp.p, scan_tmp.n, st));
-            hipLaunchKernelGGL(k_plan_scatter, dim3(grid256(n_own)), dim3(256), 0, st, n_own, flag.p, pos.p, (const int32_t *)nullptr,
+            hipLaunchKernelGGL(k_da_flag_send, dim3(grid256(n_own)), dim3(256), 0, st, n_own, needed_by.p, q, flag);
+            AVS_TRY(exclusive_scan_i32(flag, pos, n_own, scan_tmp.p, scan_tmp.n, st));
+            hipLaunchKernelGGL(k_plan_scatter, dim3(grid256(n_own)), dim3(256), 0, st, n_own, flag, pos, (const int32_t *)nullptr,
                                d->send_idx.p + off, (int32_t *)nullptr, 0); // local row index == local DOF index
             off += send_cnt[(size_t)q];
         }
@@ -1421,35 +1601,34 @@ static avs_status dist_assemble_tail(avs_ctx *c, PcgDist *d, DevBuf<int32_t> &id
     const int T = spmv_tile_rows();
     const int64_t ntiles = (n_own + T - 1) / T;
     DevBuf<int32_t> &tile_bnd = d->ws.tile_bnd, &tile_int = d->ws.tile_int, &tile_pos = d->ws.tile_pos;
-    AVS_TRY(tile_bnd.reserve((size_t)ntiles + 1));
-    AVS_TRY(tile_int.reserve((size_t)ntiles + 1));
-    AVS_TRY(tile_pos.reserve((size_t)ntiles + 1));
+    AVS_TRY(plan_buf(G, tile_bnd, (size_t)ntiles + 1, true, st));
+    AVS_TRY(plan_buf(G, tile_int, (size_t)ntiles + 1, true, st));
+    AVS_TRY(plan_buf(G, tile_pos, (size_t)ntiles + 1, true, st));
     AVS_HIP(hipMemsetAsync(tile_bnd.p, 0, ((size_t)ntiles + 1) * 4, st));
-    if (n_own) hipLaunchKernelGGL(k_da_localize, dim3(8192), dim3(256), 0, st, n_own, d->row_ptr.p, d->col.p, g2l.p, T, tile_bnd.p);
+    if (n_own) hipLaunchKernelGGL(k_da_localize, dim3(8192), dim3(256), 0, st, n_own, d->row_ptr.p, d->col.p, g2l, T, tile_bnd.p);
     int64_t n_bnd = 0, n_int = 0;
     AVS_TRY(scan_flags(tile_bnd.p, tile_pos.p, ntiles, scan_tmp, &n_bnd, st));
-    AVS_TRY(d->tiles_bnd.reserve((size_t)n_bnd));
+    AVS_TRY(plan_buf(G, d->tiles_bnd, (size_t)n_bnd, true, st));
     if (n_bnd)
         hipLaunchKernelGGL(k_plan_scatter, dim3(grid256(ntiles)), dim3(256), 0, st, ntiles, tile_bnd.p, tile_pos.p, (const int32_t *)nullptr,
                            d->tiles_bnd.p, (int32_t *)nullptr, 0);
     if (ntiles) hipLaunchKernelGGL(k_plan_not, dim3(grid256(ntiles)), dim3(256), 0, st, ntiles, tile_bnd.p, tile_int.p);
     AVS_TRY(scan_flags(tile_int.p, tile_pos.p, ntiles, scan_tmp, &n_int, st));
-    AVS_TRY(d->tiles_int.reserve((size_t)n_int));
+    AVS_TRY(plan_buf(G, d->tiles_int, (size_t)n_int, true, st));
     if (n_int)
         hipLaunchKernelGGL(k_plan_scatter, dim3(grid256(ntiles)), dim3(256), 0, st, ntiles, tile_int.p, tile_pos.p, (const int32_t *)nullptr,
                            d->tiles_int.p, (int32_t *)nullptr, 0);
 
     // reference ids behind the local columns (owned: the assembled rows' DOFs; halo: through the brick-major permutation)
-    AVS_TRY(d->local_ref.reserve((size_t)(n_own + n_halo)));
+    AVS_TRY(plan_buf(G, d->local_ref, (size_t)(n_own + n_halo), true, st));
     if (n_own) AVS_HIP(hipMemcpyAsync(d->local_ref.p, ids.p, (size_t)n_own * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    if (n_halo) hipLaunchKernelGGL(k_da_halo_ref, dim3(grid256(n)), dim3(256), 0, st, n, (const int32_t *)g2l.p, perm, n_own, d->local_ref.p, dom);
-    // warm start of the owned DOFs
-    AVS_TRY(d->x0.reserve((size_t)n_own));
-    AVS_TRY(d->x.reserve((size_t)n_own));
-    if (n_own) hipLaunchKernelGGL(k_gather_i<double>, dim3(grid256(n_own)), dim3(256), 0, st, c->x0.p, ids.p, d->x0.p, n_own);
+    if (n_halo) hipLaunchKernelGGL(k_da_halo_ref, dim3(grid256(n)), dim3(256), 0, st, n, (const int32_t *)g2l, perm, n_own, d->local_ref.p, dom);
     AVS_HIP(hipGetLastError());
     AVS_HIP(hipStreamSynchronize(st)); // temporaries die here
-    tr.mark("localize, tiles, x0");
+    tr.mark("localize, tiles, local_ref");
+#ifdef AVS_PROBES
+    if (G) AVS_TRY(plan_guard_check(G, st));
+#endif
     d->n_tiles_int = (int)n_int;
     d->n_tiles_bnd = (int)n_bnd;
     d->n_own = n_own;
@@ -2284,6 +2463,222 @@ avs_status avs_dist_spmv_local_form(avs_ctx *c, const double *x_ext, double *y, 
     fused_dot &= 1;
     AVS_TRY(probe_spmv_form(A, x_ext, y, fused_dot != 0, dot_out, c->stream));
     AVS_HIP(hipStreamSynchronize(c->stream));
+    return AVS_OK;
+}
+
+// test entry (include/avs_probe.h): the planner cores -- plan_from_source, dist_tail_from_rows -- on the caller's device arrays
+extern "C++" {
+template <typename T>
+static avs_status plan_probe_out(T *dst, const T *src, int64_t count, int64_t capacity, const char *what)
+{
+    if (!dst || count == 0) return AVS_OK;
+    AVS_REQUIRE(count <= capacity, AVS_EINVAL, "%s: %lld entries exceed the capacity %lld", what, (long long)count, (long long)capacity);
+    AVS_HIP(hipMemcpy(dst, src, (size_t)count * sizeof(T), hipMemcpyDeviceToHost));
+    return AVS_OK;
+}
+template <typename T>
+static avs_status plan_probe_up(PlanGuards *G, DevBuf<T> &b, const std::vector<T> &h, hipStream_t st)
+{
+    AVS_TRY(plan_buf(G, b, h.size(), false, st));
+    if (!h.empty()) AVS_HIP(hipMemcpyAsync(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    AVS_HIP(hipStreamSynchronize(st)); // (h may die before the stream gets there)
+    return AVS_OK;
+}
+} // extern "C++"
+
+avs_status avs_dist_plan_probe(int32_t mode, const avs_dist_plan_input *in, const avs_dist_plan_output *out, avs_dist_plan_info *info,
+                               void *stream)
+{
+    AVS_REQUIRE(info && info->struct_size >= (int32_t)sizeof(avs_dist_plan_info), AVS_EINVAL, "info: struct_size not set");
+    info->lds_planes = kPlanLdsPlanes;
+    info->scan_tile = scan_tile_elems();
+    info->spmv_tile_rows = spmv_tile_rows();
+    info->row_group = 16;
+    info->max_world = kMaxRanks;
+    info->nplanes = info->n_peers = info->n_tiles_int = info->n_tiles_bnd = 0;
+    info->n_own = info->n_halo = info->n_send = info->nnz_local = 0;
+    info->n_interior = -1;
+    info->guard_bytes_hit = 0;
+    if (!in || (in->n == 0 && !in->row_ptr)) return AVS_OK; // the limits alone: nothing touches the device
+    AVS_REQUIRE(out, AVS_EINVAL, "null argument");
+    AVS_REQUIRE(mode == AVS_DIST_PLAN_PROBE_PLAN || mode == AVS_DIST_PLAN_PROBE_TAIL, AVS_EINVAL, "unknown mode %d", mode);
+    const bool tail = mode == AVS_DIST_PLAN_PROBE_TAIL;
+    const int64_t n = in->n;
+    const int rank = in->rank, world = in->world;
+    AVS_REQUIRE(n >= 0 && n < (int64_t)INT32_MAX && in->row_ptr, AVS_EINVAL, "bad argument");
+    AVS_REQUIRE(world >= 1 && world <= kMaxRanks && rank >= 0 && rank < world, AVS_EINVAL, "rank %d / world %d out of range", rank, world);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+
+    // host copies: everything is checked before the first launch
+    std::vector<int32_t> h_rp((size_t)n + 1);
+    AVS_HIP(hipMemcpy(h_rp.data(), in->row_ptr, h_rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    AVS_REQUIRE(h_rp[0] == 0, AVS_EINVAL, "row_ptr[0] must be 0");
+    for (int64_t i = 0; i < n; ++i) AVS_REQUIRE(h_rp[(size_t)i + 1] >= h_rp[(size_t)i], AVS_EINVAL, "row_ptr decreases at row %lld", (long long)i);
+    const int64_t nnz = h_rp[(size_t)n];
+    AVS_REQUIRE(nnz == 0 || (in->col && in->val), AVS_EINVAL, "null matrix arrays");
+    std::vector<int32_t> h_col((size_t)nnz);
+    if (nnz) AVS_HIP(hipMemcpy(h_col.data(), in->col, h_col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < nnz; ++k)
+        AVS_REQUIRE(h_col[(size_t)k] >= 0 && h_col[(size_t)k] < n, AVS_EINVAL, "column %d of entry %lld outside [0, %lld)", h_col[(size_t)k],
+                    (long long)k, (long long)n);
+
+    PcgDist d;
+    d.rank = rank;
+    d.world = world;
+    PlanKeep keep;
+    PlanGuards *G = &keep.guards;
+    G->spans = 0;
+    G->hit = 0;
+    if (!tail) {
+        AVS_REQUIRE(in->dof, AVS_EINVAL, "null dof records");
+        AVS_REQUIRE(in->levels >= 1 && in->levels <= AVS_MAX_LEVELS && in->cut_axis >= 0 && in->cut_axis <= 2 && in->extent >= 1, AVS_EINVAL,
+                    "levels %d / cut_axis %d / extent %d out of range", in->levels, in->cut_axis, in->extent);
+        const int shift = in->levels - 1;
+        const int64_t nplanes = ((int64_t)in->extent + (1 << shift) - 1) >> shift;
+        AVS_REQUIRE(nplanes <= 65535, AVS_EINVAL, "too many cut planes");
+        std::vector<int32_t> h_dof((size_t)n * 4), h_perm;
+        if (n) AVS_HIP(hipMemcpy(h_dof.data(), in->dof, h_dof.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < n; ++i) {
+            const int32_t *t = &h_dof[(size_t)i * 4];
+            AVS_REQUIRE((t[0] & 0xff) <= 30 && t[1] >= 0 && t[2] >= 0 && t[3] >= 0, AVS_EINVAL, "dof record %lld out of range", (long long)i);
+        }
+        if (in->perm) {
+            h_perm.resize((size_t)n);
+            if (n) AVS_HIP(hipMemcpy(h_perm.data(), in->perm, h_perm.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < n; ++i)
+                AVS_REQUIRE(h_perm[(size_t)i] >= 0 && h_perm[(size_t)i] < n, AVS_EINVAL, "perm[%lld] outside [0, %lld)", (long long)i, (long long)n);
+        }
+        PlanSource s;
+        s.n = n;
+        s.row_ptr = in->row_ptr;
+        s.col = in->col;
+        s.val = in->val;
+        s.vdof = in->dof;
+        s.perm = in->perm;
+        s.levels = in->levels;
+        s.cut_axis = in->cut_axis;
+        s.extent = in->extent;
+        s.rank = rank;
+        s.world = world;
+        s.stream = st;
+        s.keep = &keep;
+        const avs_status rc = plan_from_source(&d, s);
+        info->guard_bytes_hit = G->hit;
+        if (rc != AVS_OK) return rc;
+        info->nplanes = (int32_t)nplanes;
+        if (out->weights || out->plane_owner)
+            AVS_REQUIRE(nplanes <= out->plane_capacity, AVS_EINVAL, "%lld planes exceed the capacity %lld", (long long)nplanes, (long long)out->plane_capacity);
+        if (out->weights) std::copy(keep.weight.begin(), keep.weight.end(), out->weights);
+        if (out->plane_owner) std::copy(keep.plane_owner.begin(), keep.plane_owner.end(), out->plane_owner);
+        AVS_TRY(plan_probe_out(out->owner, (const uint8_t *)keep.owner.p, n, n, "owner"));
+    } else {
+        AVS_REQUIRE(in->owner, AVS_EINVAL, "null owner array");
+        AVS_REQUIRE(in->n_dom >= 0 && in->n_dom <= n && (in->dom || in->n_dom == 0), AVS_EINVAL, "dom: %lld entries for %lld ids", (long long)in->n_dom,
+                    (long long)n);
+        std::vector<uint8_t> h_owner((size_t)n);
+        if (n) AVS_HIP(hipMemcpy(h_owner.data(), in->owner, h_owner.size(), hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < n; ++i)
+            AVS_REQUIRE(h_owner[(size_t)i] < world || h_owner[(size_t)i] == 0xFF, AVS_EINVAL, "owner[%lld] = %d is no rank", (long long)i, h_owner[(size_t)i]);
+        const int64_t n_dom = in->dom ? in->n_dom : n;
+        if (in->dom) {
+            std::vector<int32_t> h_dom((size_t)n_dom);
+            std::vector<uint8_t> seen((size_t)n, 0);
+            if (n_dom) AVS_HIP(hipMemcpy(h_dom.data(), in->dom, h_dom.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < n_dom; ++i) {
+                const int32_t g = h_dom[(size_t)i];
+                AVS_REQUIRE(g >= 0 && g < n && !seen[(size_t)g], AVS_EINVAL, "dom[%lld] = %d outside [0, %lld) or listed twice", (long long)i, g, (long long)n);
+                seen[(size_t)g] = 1;
+            }
+        }
+        { // symmetric pattern: the sorted (row, column) pairs equal the sorted (column, row) pairs
+            std::vector<uint64_t> a((size_t)nnz), b((size_t)nnz);
+            for (int64_t r = 0; r < n; ++r)
+                for (int32_t k = h_rp[(size_t)r]; k < h_rp[(size_t)r + 1]; ++k) {
+                    a[(size_t)k] = ((uint64_t)r << 32) | (uint32_t)h_col[(size_t)k];
+                    b[(size_t)k] = ((uint64_t)(uint32_t)h_col[(size_t)k] << 32) | (uint64_t)r;
+                }
+            std::sort(a.begin(), a.end());
+            std::sort(b.begin(), b.end());
+            a.erase(std::unique(a.begin(), a.end()), a.end());
+            b.erase(std::unique(b.begin(), b.end()), b.end());
+            AVS_REQUIRE(a == b, AVS_EINVAL, "TAIL mode: the pattern is not symmetric");
+        }
+        // the state after assemble_rows: the rank's rows in ascending id order, columns still global
+        std::vector<double> h_val((size_t)nnz);
+        if (nnz) AVS_HIP(hipMemcpy(h_val.data(), in->val, h_val.size() * sizeof(double), hipMemcpyDeviceToHost));
+        std::vector<int32_t> ids, rp(1, 0), cl, g2l((size_t)n, -1);
+        std::vector<double> vl, rhs;
+        for (int64_t i = 0; i < n; ++i) {
+            if (h_owner[(size_t)i] != rank) continue;
+            g2l[(size_t)i] = (int32_t)ids.size();
+            ids.push_back((int32_t)i);
+            rhs.push_back((double)i);
+            cl.insert(cl.end(), h_col.begin() + h_rp[(size_t)i], h_col.begin() + h_rp[(size_t)i + 1]);
+            vl.insert(vl.end(), h_val.begin() + h_rp[(size_t)i], h_val.begin() + h_rp[(size_t)i + 1]);
+            rp.push_back((int32_t)cl.size());
+        }
+        const int64_t n_own = (int64_t)ids.size();
+        DevBuf<int32_t> d_ids, d_g2l, flag, pos, scan_tmp;
+        DevBuf<uint8_t> is_halo;
+        AVS_TRY(plan_probe_up(G, d_ids, ids, st));
+        AVS_TRY(plan_probe_up(G, d.own_global, ids, st));
+        AVS_TRY(plan_probe_up(G, d.row_ptr, rp, st));
+        AVS_TRY(plan_probe_up(G, d.col, cl, st));
+        AVS_TRY(plan_probe_up(G, d.val, vl, st));
+        AVS_TRY(plan_probe_up(G, d.rhs, rhs, st));
+        AVS_TRY(plan_probe_up(G, d_g2l, g2l, st));
+        const int64_t n_scan = std::max(n_own, n_dom);
+        AVS_TRY(plan_buf(G, flag, (size_t)n_scan + 1, false, st));
+        AVS_TRY(plan_buf(G, pos, (size_t)n_scan + 1, false, st));
+        AVS_TRY(plan_buf(G, scan_tmp, scan_tmp_elems(n_scan + 1), false, st));
+        AVS_TRY(plan_buf(G, is_halo, (size_t)n, false, st));
+        AVS_HIP(hipMemsetAsync(is_halo.p, 0, (size_t)n, st));
+        TailSource s;
+        s.ids = &d_ids;
+        s.n_own = n_own;
+        s.nnz_local = (int64_t)cl.size();
+        s.dom = in->dom;
+        s.n_dom = n_dom;
+        s.owner = in->owner;
+        s.is_halo = is_halo.p;
+        s.g2l = d_g2l.p;
+        s.flag = flag.p;
+        s.pos = pos.p;
+        s.scan_tmp = &scan_tmp;
+        s.rank = rank;
+        s.world = world;
+        s.split = in->split != 0;
+        s.stream = st;
+        s.keep = &keep;
+        const avs_status rc = dist_tail_from_rows(&d, s);
+        info->guard_bytes_hit = G->hit;
+        if (rc != AVS_OK) return rc;
+        info->n_interior = keep.n_interior;
+        AVS_TRY(plan_probe_out(out->local_ref, (const int32_t *)d.local_ref.p, d.n_own + d.n_halo, out->row_capacity, "local_ref"));
+        AVS_TRY(plan_probe_out(out->rhs_local, (const double *)d.rhs.p, d.n_own, out->row_capacity, "rhs_local"));
+    }
+    DevBuf<int32_t> &halo = tail ? d.ws.halo_tmp : keep.halo;
+    info->n_own = d.n_own;
+    info->n_halo = d.n_halo;
+    info->n_send = d.n_send;
+    info->nnz_local = d.nnz_local;
+    info->n_peers = (int32_t)d.peers.size();
+    info->n_tiles_int = d.n_tiles_int;
+    info->n_tiles_bnd = d.n_tiles_bnd;
+    AVS_TRY(plan_probe_out(out->own_global, (const int32_t *)d.own_global.p, d.n_own, out->row_capacity, "own_global"));
+    AVS_TRY(plan_probe_out(out->halo_global, (const int32_t *)halo.p, d.n_halo, out->row_capacity, "halo_global"));
+    if (out->row_ptr_local) {
+        AVS_REQUIRE(d.n_own <= out->row_capacity, AVS_EINVAL, "row_ptr_local: %lld rows exceed the capacity %lld", (long long)d.n_own, (long long)out->row_capacity);
+        AVS_HIP(hipMemcpy(out->row_ptr_local, d.row_ptr.p, ((size_t)d.n_own + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    AVS_TRY(plan_probe_out(out->col_local, (const int32_t *)d.col.p, d.nnz_local, out->nnz_capacity, "col_local"));
+    AVS_TRY(plan_probe_out(out->val_local, (const double *)d.val.p, d.nnz_local, out->nnz_capacity, "val_local"));
+    AVS_TRY(plan_probe_out(out->send_idx, (const int32_t *)d.send_idx.p, d.n_send, out->send_capacity, "send_idx"));
+    AVS_TRY(plan_probe_out(out->tiles_int, (const int32_t *)d.tiles_int.p, (int64_t)d.n_tiles_int, out->row_capacity, "tiles_int"));
+    AVS_TRY(plan_probe_out(out->tiles_bnd, (const int32_t *)d.tiles_bnd.p, (int64_t)d.n_tiles_bnd, out->row_capacity, "tiles_bnd"));
+    if (out->peers) std::copy(d.peers.begin(), d.peers.end(), out->peers);
+    if (out->send_counts) std::copy(d.send_counts.begin(), d.send_counts.end(), out->send_counts);
+    if (out->recv_counts) std::copy(d.recv_counts.begin(), d.recv_counts.end(), out->recv_counts);
     return AVS_OK;
 }
 #endif

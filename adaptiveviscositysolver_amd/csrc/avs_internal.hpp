@@ -675,6 +675,9 @@ avs_status stream_probe(int mode, const double *a, double *b, int64_t n, double 
 avs_status exclusive_scan_i32(const int32_t *in, int32_t *out, int64_t n, int32_t *block_tmp, size_t block_tmp_elems,
                               hipStream_t stream);
 size_t scan_tmp_elems(int64_t n);
+#ifdef AVS_PROBES
+int scan_tile_elems(); // elements per workgroup of the scan (the probes report it as a limit)
+#endif
 bool dist_matrix_format(avs_ctx *c, avs_matrix_format *fmt); // avs_dist.hip: local rows of a partitioned / distributed system
 avs_status build_stencils(avs_ctx *c);
 avs_status pad_stencils(avs_ctx *c, bool edge); // unused stencil slots := (-1, 0.0), before a read-back

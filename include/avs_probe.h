@@ -286,6 +286,72 @@ avs_status avs_brick_form_probe(int64_t n_rows, int64_t n_cols, const int32_t *r
                                 int32_t flags, int32_t grid, int32_t walk, double *dot_out, double *partials, int32_t partial_capacity,
                                 avs_brick_form_info *info, int32_t *headers, int32_t header_capacity, void *stream);
 
+/* The device partition planners (csrc/avs_dist.hip) on the CALLER's arrays: the functions avs_dist_partition and avs_dist_assemble call,
+ * without a context.  All inputs are device arrays, every result is copied to a HOST array of a stated capacity (any may be NULL).
+ *   PLAN  plan_from_source, the core of avs_dist_partition's device planner: a CSR of n rows (any columns in [0, n), any row lengths
+ *         including 0, duplicates allowed, the pattern need not be symmetric), its values, one int4 dof record per DOF (level | axis << 8,
+ *         i, j, k), perm (row i stands for the DOF perm[i]; NULL: identity), levels (1 .. 8), cut_axis, extent (>= 1, any value that gives
+ *         at most 65,535 planes of 2^(levels-1) cells -- not tied to the 1,024 limit of a grid), rank and world.
+ *   TAIL  dist_tail_from_rows, everything avs_dist_assemble does behind assemble_rows: a CSR over n ids whose PATTERN IS SYMMETRIC, `owner`
+ *         (one byte per id: its rank, 0xFF: outside the rank's window), rank, world, split (!= 0: [interior | halo-reading] local row order)
+ *         and dom (NULL: every id; else n_dom <= n distinct ids, the only ones a halo column may have, in the order halo ids are numbered
+ *         in).  The entry gathers the rows whose owner is `rank` in ascending id order -- the state after assemble_rows, the right-hand
+ *         side of row i being (double)i -- and calls the core with identity inv / perm.  A column whose owner is 0xFF comes back as the
+ *         core's AVS_EINTERNAL.
+ * Results (out): weights and plane_owner per plane and owner per row (PLAN only); own_global (TAIL: in the possibly reordered local order),
+ * halo_global, row_ptr_local (n_own + 1), col_local, val_local, send_idx (grouped by peer), peers / send_counts / recv_counts (room for 32
+ * each), tiles_int, tiles_bnd, and for TAIL local_ref (n_own + n_halo) and rhs_local.  row_capacity bounds n_own, n_halo, n_own + n_halo
+ * (local_ref) and the tile lists; nnz_capacity, send_capacity and plane_capacity the others: a result beyond its capacity is AVS_EINVAL with
+ * the sizes in *info.
+ * In the probe every array the planner fills is allocated with 64 guard bytes of a known pattern behind its last entry (the product's
+ * allocations are not changed: the cores allocate through one helper that is DevBuf::alloc / reserve without guards);
+ * info->guard_bytes_hit counts the guard bytes that were altered.
+ * *info (struct_size set by the caller) gets the limits the code was compiled with and the sizes of the plan.  With in == NULL, or in->n == 0
+ * and in->row_ptr == NULL, only the limits are filled in and nothing touches the device (the CPU tests place their cases from them).
+ * Refused with AVS_EINVAL on the host, before any launch: rank >= world, world > 32, levels / cut_axis / extent out of range, row pointers
+ * that do not start at 0 or decrease, a column outside [0, n), a dof record whose level exceeds 30 or whose coordinate is negative, a perm
+ * or dom entry outside [0, n), an owner byte that is neither < world nor 0xFF, and in TAIL mode an asymmetric pattern. */
+#define AVS_DIST_PLAN_PROBE_PLAN 0
+#define AVS_DIST_PLAN_PROBE_TAIL 1
+typedef struct {
+    int64_t n;
+    const int32_t *row_ptr, *col;
+    const double *val;
+    const int32_t *dof, *perm;      /* PLAN */
+    const uint8_t *owner;           /* TAIL */
+    const int32_t *dom;             /* TAIL */
+    int64_t n_dom;
+    int32_t levels, cut_axis, extent; /* PLAN */
+    int32_t split;                  /* TAIL */
+    int32_t rank, world;
+} avs_dist_plan_input;
+typedef struct {
+    int64_t row_capacity, nnz_capacity, send_capacity, plane_capacity;
+    int64_t *weights;
+    int32_t *plane_owner;
+    uint8_t *owner;                 /* n entries */
+    int32_t *own_global, *halo_global, *row_ptr_local, *col_local;
+    double *val_local;
+    int32_t *send_idx, *peers, *send_counts, *recv_counts, *tiles_int, *tiles_bnd, *local_ref;
+    double *rhs_local;
+} avs_dist_plan_output;
+typedef struct {
+    int32_t struct_size;
+    /* limits */
+    int32_t lds_planes;             /* kPlanLdsPlanes: more planes than this are weighed with global atomics */
+    int32_t scan_tile;              /* elements per workgroup of exclusive_scan_i32 */
+    int32_t spmv_tile_rows;         /* avs_spmv_tile_rows(): rows per entry of the tile lists */
+    int32_t row_group;              /* lanes that share a row in the mark / localize / move kernels */
+    int32_t max_world;
+    /* the plan */
+    int32_t nplanes, n_peers, n_tiles_int, n_tiles_bnd;
+    int64_t n_own, n_halo, n_send, nnz_local;
+    int64_t n_interior;             /* TAIL with a split: rows that read no other rank; else -1 */
+    int64_t guard_bytes_hit;
+} avs_dist_plan_info;
+avs_status avs_dist_plan_probe(int32_t mode, const avs_dist_plan_input *in, const avs_dist_plan_output *out, avs_dist_plan_info *info,
+                               void *stream);
+
 
 #ifdef __cplusplus
 }
