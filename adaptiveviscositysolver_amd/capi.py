@@ -42,6 +42,10 @@ INDEX_VELOCITY, INDEX_EDGE, INDEX_CENTER = 0, 1, 2
 CHECK_LABELS, CHECK_VELOCITY_INDICES = 1, 2   # bits of `what` of avs_check_octree
 (RULE_LABEL_VALUE, RULE_COLUMN, RULE_UP, RULE_ACTIVE, RULE_INDEX_VALUE, RULE_FACE, RULE_SENTINEL, RULE_NUMBERING) = range(8)
 OCTREE_RULES = 8
+CSR_CHECK_VALUES, CSR_CHECK_ORDER, CSR_CHECK_DIAGONAL, CSR_CHECK_SYMMETRY, CSR_CHECK_ALL = 1, 2, 4, 8, 15   # bits of `what` of avs_check_csr
+(CSR_RULE_ROW_PTR, CSR_RULE_COLUMN, CSR_RULE_VALUE, CSR_RULE_VECTOR, CSR_RULE_ORDER, CSR_RULE_DIAGONAL, CSR_RULE_PATTERN,
+ CSR_RULE_SYMMETRY) = range(8)
+CSR_RULES = 8
 (FIELD_CENTER_WEIGHTS, FIELD_EDGE_WEIGHTS, FIELD_FACE_WEIGHTS, FIELD_VISCOSITY, FIELD_DENSITY,
  FIELD_VELOCITY, FIELD_SOLID_VELOCITY) = range(7)
 
@@ -62,6 +66,7 @@ EXPORTED_SYMBOLS = [
     "avs_dist_get_info", "avs_dist_init_hosted", "avs_dist_export_blob", "avs_dist_import_blobs",
     "avs_prepass_set_slab", "avs_prepass_get_window", "avs_dist_bind_prepass", "avs_dist_get_cuts", "avs_set_solution",
     "avs_sample_velocity", "avs_get_octree_cells", "avs_prepass_get_octree_cells", "avs_check_octree", "avs_prepass_check_octree",
+    "avs_check_csr", "avs_check_system",
 ]
 # avs_allreduce_i32_fn: avs_status (*)(int32_t *device_data, int64_t count, void *stream, void *user)
 ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -152,6 +157,18 @@ class OctreeCheck(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(OctreeCheck)
+
+
+class CsrCheck(C.Structure):
+    """avs_csr_check: the report of avs_check_csr / avs_check_system"""
+    _fields_ = [("struct_size", C.c_int32), ("passed", C.c_int32), ("evaluated", C.c_int32), ("first_rule", C.c_int32),
+                ("first_index", C.c_int64), ("first_row", C.c_int32), ("first_col", C.c_int32), ("violations", C.c_int64 * CSR_RULES),
+                ("empty_rows", C.c_int64), ("longest_row", C.c_int64), ("asymmetric_entries", C.c_int64),
+                ("max_abs_value", C.c_double), ("max_abs_asymmetry", C.c_double)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(CsrCheck)
 
 
 class ResidentPlanInfo(C.Structure):
@@ -333,6 +350,8 @@ def load(probe=False):
     L.avs_prepass_get_octree_cells.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i32]
     L.avs_check_octree.argtypes = [vp, C.c_uint32, C.POINTER(OctreeCheck)]
     L.avs_prepass_check_octree.argtypes = [vp, C.c_uint32, C.POINTER(OctreeCheck)]
+    L.avs_check_csr.argtypes = [i64, i64, vp, vp, vp, vp, vp, C.c_uint32, f64, i32, i32, vp, C.POINTER(CsrCheck)]
+    L.avs_check_system.argtypes = [vp, C.c_uint32, f64, C.POINTER(CsrCheck)]
     L.avs_get_dof_table.argtypes = [vp, i32, vp, i32]
     L.avs_plan_owners.argtypes = [i64, vp, vp, i32, i32, i32, i32, vp]
     L.avs_plan_create.argtypes = [i64, vp, vp, vp, i32, i32, C.POINTER(vp)]

@@ -18,6 +18,7 @@
 #include "avs.h"
 #include "avs_probe.h"
 #include "avs_check_report.hpp"
+#include "avs_csr_check_report.hpp"
 
 struct avs_ctx;
 namespace avs {
@@ -631,6 +632,19 @@ struct CheckSource {
 };
 avs_status check_octree(CheckScratch &S, const CheckSource &src, hipStream_t st, uint32_t what, avs_octree_check *report);
 
+// CSR check (avs_csr_check.hip): avs_check_csr / avs_check_system over one implementation.  Scratch: the raw report and one byte per row
+// (1: the row's columns are strictly ascending, so the partner search of the symmetry pass may bisect it).
+struct CsrCheckScratch {
+    DevBuf<unsigned long long> raw;
+    DevBuf<uint8_t> ascending;
+};
+struct CsrCheckSource { // device pointers; b, x: may be null
+    int64_t n, nnz;
+    const int32_t *row_ptr, *col;
+    const double *val, *b, *x;
+};
+avs_status check_csr(CsrCheckScratch &S, const CsrCheckSource &src, hipStream_t st, uint32_t what, double symmetry_tolerance, avs_csr_check *report);
+
 // avs_desc::precision == AVS_PRECISION_F32: the solution as the reference's Eigen::VectorXf holds it (avs_api.hip)
 void narrow_solution_if_f32(avs_ctx *c, double *x, int64_t n);
 
@@ -862,6 +876,7 @@ struct avs_ctx {
 
     avs::CellsScratch cells; // avs_get_octree_cells (avs_cells.hip)
     avs::CheckScratch check; // avs_check_octree (avs_check.hip)
+    avs::CsrCheckScratch csr_check; // avs_check_system (avs_csr_check.hip)
 
     // brick-major copy of the system used by the solve (avs_reorder.hip); perm: new -> old
     avs::DevBuf<int32_t> perm, inv, p_row_ptr, p_col;

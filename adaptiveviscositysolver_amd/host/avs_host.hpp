@@ -88,6 +88,15 @@ public:
         check(avs_assemble(myCtx, &info), "avs_assemble");
         return info;
     }
+    // is the assembled system one the solve is defined for? (avs_check_system: pointers, columns, finite values, ascending rows, a
+    // positive diagonal, symmetry within an absolute tolerance; report.passed, and the measured asymmetry of A)
+    avs_csr_check checkLinearSystem(uint32_t what = AVS_CSR_CHECK_ALL, double symmetryTolerance = 0.)
+    {
+        avs_csr_check report{};
+        report.struct_size = (int32_t)sizeof(report);
+        check(avs_check_system(myCtx, what, symmetryTolerance, &report), "avs_check_system");
+        return report;
+    }
     SolveResult solveConjugateGradient(double solverTolerance = 1e-3, int maxSolverIterations = 2500)
     {
         avs_solve_info s{};

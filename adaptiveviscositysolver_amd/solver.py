@@ -437,6 +437,15 @@ class ViscositySolve:
         the velocity index pyramid and the dof counts too), or both.  Returns an OctreeCheck."""
         return _check_octree(self.lib.avs_check_octree, self.h, what)
 
+    def check_system(self, what=capi.CSR_CHECK_ALL, symmetry_tolerance=0.0):
+        """Is the assembled system one the solve is defined for?  (avs_check_system: the rules of avs_check_csr on the context's
+        reference-numbered matrix, its right-hand side and the initial guess, in place.)  Needs assemble(); changes nothing a later
+        solve reads.  Returns a CsrCheck: asymmetric_entries and max_abs_asymmetry say how far the assembled A is from bitwise
+        symmetric."""
+        rep = capi.CsrCheck()
+        capi.check(self.lib.avs_check_system(self.h, int(what), float(symmetry_tolerance), C.byref(rep)))
+        return _csr_check(rep)
+
     def edge_stencils(self):
         ne = self.info().n_edge
         return self._stencils(self.lib.avs_get_edge_stencils, ne, ne, capi.EDGE_STENCIL_CAP, capi.EDGE_BOUNDARY_CAP)
@@ -509,6 +518,53 @@ def pcg_csr(row_ptr, col, val, b, x0, tol=1e-3, max_iters=2500, device=0):
                                x.ctypes.data, float(tol), int(max_iters), capi.MEM_HOST, device, None,
                                C.byref(info)))
     return x, info
+
+
+@dataclass(frozen=True)
+class CsrCheck:
+    """report of check_csr / check_system: passed; evaluated = bit r: rule r (capi.CSR_RULE_*) was evaluated; violations[rule] = positions
+    that break the rule; first = (rule, index, row, col) of the violating position that comes first by (rule, index), None when passed;
+    empty_rows, longest_row; with capi.CSR_CHECK_SYMMETRY asymmetric_entries, max_abs_value and max_abs_asymmetry (0 otherwise)"""
+    passed: bool
+    evaluated: int
+    violations: tuple
+    first: tuple | None
+    empty_rows: int
+    longest_row: int
+    asymmetric_entries: int
+    max_abs_value: float
+    max_abs_asymmetry: float
+
+    def __bool__(self):
+        return self.passed
+
+
+def _csr_check(rep):
+    first = None if rep.passed else (rep.first_rule, rep.first_index, rep.first_row, rep.first_col)
+    return CsrCheck(bool(rep.passed), int(rep.evaluated), tuple(int(v) for v in rep.violations), first, int(rep.empty_rows),
+                    int(rep.longest_row), int(rep.asymmetric_entries), float(rep.max_abs_value), float(rep.max_abs_asymmetry))
+
+
+def check_csr(row_ptr, col, val, b=None, x=None, what=capi.CSR_CHECK_ALL, symmetry_tolerance=0.0, device=0):
+    """Is this CSR system one pcg_csr is defined for?  (avs_check_csr on host numpy arrays: eight rules evaluated on the device, see
+    include/avs.h.)  A caller checks once when wiring up seam A, not per solve.  Returns a CsrCheck."""
+    lib = capi.load()
+    rp = np.ascontiguousarray(row_ptr, np.int32)
+    cl = np.ascontiguousarray(col, np.int32)
+    vl = np.ascontiguousarray(val, np.float64)
+    bb = None if b is None else np.ascontiguousarray(b, np.float64)
+    xx = None if x is None else np.ascontiguousarray(x, np.float64)
+    n = len(rp) - 1
+    for name, v in (("b", bb), ("x", xx)):
+        if v is not None and len(v) != n:
+            raise ValueError(f"{name} has {len(v)} entries for {n} rows")
+    if len(cl) != len(vl):
+        raise ValueError(f"col has {len(cl)} entries, val {len(vl)}")
+    rep = capi.CsrCheck()
+    capi.check(lib.avs_check_csr(n, len(cl), rp.ctypes.data, cl.ctypes.data if len(cl) else None, vl.ctypes.data if len(vl) else None,
+                                 None if bb is None else bb.ctypes.data, None if xx is None else xx.ctypes.data, int(what),
+                                 float(symmetry_tolerance), capi.MEM_HOST, device, None, C.byref(rep)))
+    return _csr_check(rep)
 
 
 class DevicePrepass:

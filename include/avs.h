@@ -136,7 +136,8 @@ const char *avs_version(void);
  * carries struct_size, avs_solve_info.cancelled, avs_cancel; the measurement entries moved to libavs_probe.so in round 4).
  * Purely additive since (no revision): the entry avs_sample_velocity.
  * Purely additive since (no revision): the entries avs_get_octree_cells and avs_prepass_get_octree_cells.
- * Purely additive since (no revision): the entries avs_check_octree and avs_prepass_check_octree. */
+ * Purely additive since (no revision): the entries avs_check_octree and avs_prepass_check_octree.
+ * Purely additive since (no revision): the entries avs_check_csr and avs_check_system. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -445,6 +446,70 @@ avs_status avs_check_octree(avs_ctx *ctx, uint32_t what, avs_octree_check *repor
 avs_status avs_pcg_csr(int64_t n, const int32_t *row_ptr, const int32_t *col, const double *val,
                        const double *b, double *x_inout, double tolerance, int32_t max_iterations,
                        avs_memspace where, int32_t device, void *stream, avs_solve_info *info);
+
+/* Is this CSR system one avs_pcg_csr is defined for?  avs_pcg_csr hands row_ptr, col and val to its kernels unread: a column outside
+ * [0, n) or a row pointer that runs backwards is an out-of-bounds gather there, and a missing or non-positive diagonal, a NaN or an
+ * unsymmetric matrix is a solve that does not converge without saying why.  avs_check_csr evaluates eight rules on the device and reports
+ * a 64-bit count per rule, the first violating position and a few measurements.  Nothing else in the library calls it, it writes nothing
+ * the caller owns, and every other entry behaves as without it.  avs_check_system is the same check on the system a context assembled.
+ * n rows, row_ptr has n + 1 entries; nnz is the caller's statement of how long col and val are: entry nnz and anything beyond it is never
+ * read, whatever row_ptr says.  Every rule is evaluated independently, entry by entry; a position counts at most once per rule:
+ *   0 ROW_PTR   (always) index i in 0 .. n: row_ptr[i] < 0 or > nnz; i == 0 and row_ptr[0] != 0; i == n and row_ptr[n] != nnz; i < n and
+ *               row_ptr[i] > row_ptr[i + 1].  If rule 0 is violated nothing else is evaluated (the other rules walk rows through
+ *               row_ptr): evaluated = 1, every other count and every measurement is 0, first_row = first_col = -1.
+ *   1 COLUMN    (always, once rule 0 holds) entry k: col[k] < 0 or >= n.  Such entries are skipped by rules 5 .. 7; no value read from
+ *               the caller's arrays is used as an address without this test.
+ *   2 VALUE     (AVS_CSR_CHECK_VALUES) entry k: val[k] is NaN or +-Inf.
+ *   3 VECTOR    (AVS_CSR_CHECK_VALUES, and only if b or x is given) row i: b[i] or x[i] is NaN or +-Inf.
+ *   4 ORDER     (AVS_CSR_CHECK_ORDER) entry k that is not the first of its row: col[k] <= col[k - 1] -- rows strictly ascending, hence no
+ *               repeated column, as Eigen's compressed matrix (cpp:613-614) and the device triplet merge hold them.  The SpMV forms
+ *               accept unordered rows: a caller who knows its rows are unordered leaves this bit out.
+ *   5 DIAGONAL  (AVS_CSR_CHECK_DIAGONAL) row i: no entry with col == i, or the last such entry (the one the Jacobi preconditioner reads)
+ *               is not > 0 (NaN is not > 0).
+ *   6 PATTERN   (AVS_CSR_CHECK_SYMMETRY) entry k = (i, j) with j in range and j != i: row j has no entry with column i.
+ *   7 SYMMETRY  (AVS_CSR_CHECK_SYMMETRY) entry k = (i, j) as in rule 6 whose partner p -- the first entry of row j with column i -- exists:
+ *               val[k] and val[p] are finite and |val[k] - val[p]| > symmetry_tolerance (absolute, the caller's number, typically a
+ *               multiple of max_abs_value; one subtraction and one comparison).
+ * Measurements (rule 0 holding): empty_rows, longest_row (entries); with AVS_CSR_CHECK_SYMMETRY, else 0: max_abs_value = the largest
+ *   |val[k]| over the finite entries, and over the pairs (k, p) of rule 7 with both values finite asymmetric_entries = pairs with
+ *   val[k] != val[p] and max_abs_asymmetry = the largest |val[k] - val[p]|.
+ * what: any of the AVS_CSR_CHECK_* bits; 0 runs rules 0 and 1 only; any other bit: AVS_EINVAL.  A rule that was not asked for reports 0
+ *   and is not launched.  evaluated: bit r = rule r was evaluated.  n == 0: rule 0 on the single pointer, nothing else (evaluated = 1).
+ * first_*: the violating position that comes first by (rule, index); first_rule = first_index = first_row = first_col = -1 when passed.
+ *   first_index: the row_ptr index (rule 0), the entry k (rules 1, 2, 4, 6, 7), the row i (rules 3, 5).  first_row: the row that owns
+ *   entry k, or the row i (-1 for rule 0); first_col: col[k] as stored, even out of range (-1 for rules 0, 3, 5).
+ * Arguments: n, nnz in [0, 2^31); row_ptr non-NULL; col and val non-NULL when nnz > 0; b, x may be NULL (n entries each otherwise);
+ *   symmetry_tolerance finite and >= 0; device in range; report non-NULL with struct_size set (IN, as in avs_matrix_format: only that
+ *   many bytes are written).  Anything else: AVS_EINVAL with a message in avs_last_error.
+ * AVS_MEM_DEVICE arrays are read in place on `stream` (NULL: a stream of the library's own), AVS_MEM_HOST arrays are staged; the call
+ *   returns once the report is on the host (one more wait after the row_ptr pass: rule 0 decides whether the rest may run).
+ * avs_check_system: the context's reference-numbered row_ptr, col, val and rhs (what avs_get_csr hands out) as b, and the initial guess
+ *   as x.  Needs avs_assemble (AVS_ESTATE otherwise, and after avs_dist_assemble: no global matrix exists); scratch (the raw report, one
+ *   byte per row) stays in the context; nothing a later avs_solve reads is changed.
+ * The same arrays give the same report on every call.  The partner search of rules 6 / 7 is a binary search in rows that are strictly
+ *   ascending and a linear scan (row length probes per entry) in rows that are not. */
+enum { AVS_CSR_CHECK_VALUES = 1, AVS_CSR_CHECK_ORDER = 2, AVS_CSR_CHECK_DIAGONAL = 4, AVS_CSR_CHECK_SYMMETRY = 8,
+       AVS_CSR_CHECK_ALL = 15 };
+enum { AVS_CSR_RULE_ROW_PTR = 0, AVS_CSR_RULE_COLUMN = 1, AVS_CSR_RULE_VALUE = 2, AVS_CSR_RULE_VECTOR = 3,
+       AVS_CSR_RULE_ORDER = 4, AVS_CSR_RULE_DIAGONAL = 5, AVS_CSR_RULE_PATTERN = 6, AVS_CSR_RULE_SYMMETRY = 7,
+       AVS_CSR_RULES = 8 };
+typedef struct avs_csr_check {
+    int32_t struct_size;          /* IN: sizeof(avs_csr_check) of the caller's header */
+    int32_t passed;               /* 1 = no evaluated rule is violated */
+    int32_t evaluated;            /* bit r: rule r was evaluated */
+    int32_t first_rule;           /* -1 when passed */
+    int64_t first_index;          /* position in the rule's array: row_ptr index (rule 0), entry k (1, 2, 4, 6, 7), row i (3, 5) */
+    int32_t first_row, first_col; /* row owning the entry / the stored column (as stored, even out of range); -1 where not applicable */
+    int64_t violations[AVS_CSR_RULES];
+    int64_t empty_rows, longest_row;
+    int64_t asymmetric_entries;   /* measurements of the SYMMETRY bit; 0 when not asked */
+    double max_abs_value, max_abs_asymmetry;
+} avs_csr_check;
+avs_status avs_check_csr(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *col, const double *val,
+                         const double *b /* may be NULL */, const double *x /* may be NULL */,
+                         uint32_t what, double symmetry_tolerance, avs_memspace where, int32_t device, void *stream,
+                         avs_csr_check *report);
+avs_status avs_check_system(avs_ctx *ctx, uint32_t what, double symmetry_tolerance, avs_csr_check *report);
 
 /* (measurement / test entries -- single SpMV launches, kernel sweeps, stream probes -- live in include/avs_probe.h and libavs_probe.so) */
 
