@@ -78,6 +78,7 @@ PROBE_SYMBOLS = ["avs_spmv_csr", "avs_bench_spmv", "avs_spmv_sell", "avs_bench_s
 DIST_PLAN_PROBE_PLAN, DIST_PLAN_PROBE_TAIL = 0, 1   # avs_dist_plan_probe modes
 BRICK_PROBE_FUSED_DOT, BRICK_PROBE_F32, BRICK_PROBE_MIXED, BRICK_PROBE_VALUE_CODES, BRICK_PROBE_DONE = 1, 2, 4, 8, 16   # avs_brick_form_probe flags
 VECTOR_PROBE_F32, VECTOR_PROBE_DS, VECTOR_PROBE_CODED, VECTOR_PROBE_KEEP, VECTOR_PROBE_FUSED = 1, 2, 4, 8, 16   # avs_vector_update_probe flags
+VECTOR_PROBE_ONE_LAUNCH = 32                                                                                   # ... k_update_fused instead of the pair
 (SCALAR_PROBE_REDUCE_LAUNCH, SCALAR_PROBE_REDUCE, SCALAR_PROBE_REDUCE_MB, SCALAR_PROBE_REDUCE_PAIR, SCALAR_PROBE_SCALAR,
  SCALAR_PROBE_MIXED_FINISH_INIT, SCALAR_PROBE_MIXED_FINISH, SCALAR_PROBE_SR_MIXED_BEGIN, SCALAR_PROBE_SR_MIXED_STEP) = range(9)   # avs_pcg_scalar_probe
 SCALAR_PROBE_STAGE_NAN = 0x7ff8a5a500000000

@@ -108,7 +108,7 @@ Options options_from_env()
         (void)sscanf(e, "%lf,%lf,%lf,%lf,%lf,%lf", &k.tile, &k.row, &k.run, &k.word, &k.etile, &k.quad);
     }
     o.fuse_beta = env_int("AVS_PCG_FUSE_BETA", 1) != 0;
-    { const int v = env_int("AVS_PCG_FUSE_VECTORS", 0); o.fuse_vectors = v < 0 ? -1 : (v > 0 ? 1 : 0); }
+    { const int v = env_int("AVS_PCG_FUSE_VECTORS", -1); o.fuse_vectors = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.fused_timeout_ms = env_int("AVS_PCG_FUSED_TIMEOUT_MS", 2000);
     { const int v = env_int("AVS_F32_VECTORS", -1); o.f32_vectors = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     o.dist_f32_vectors = env_int("AVS_DIST_F32_VECTORS", 0) != 0;

@@ -105,8 +105,9 @@ struct Options {
     BrickCost brick_cost;        // AVS_BRICK_COST=tile,row,run,word,etile,quad
     // single-GPU loop
     int fuse_beta = 1;
-    int fuse_vectors = 0;        // AVS_PCG_FUSE_VECTORS: the two vector kernels of the single-GPU loop as one launch with a grid barrier (k_update_fused,
-                                 // avs_pcg.hip): 0 never, 1 wherever the system qualifies, -1 only systems larger than the Infinity Cache
+    int fuse_vectors = -1;       // AVS_PCG_FUSE_VECTORS: the two vector kernels of the single-GPU loop as one launch with a grid barrier (k_update_fused,
+                                 // avs_pcg.hip): 0 never, 1 wherever the system qualifies, -1 only systems larger than the Infinity Cache whose
+                                 // SpMV leaves few enough partial sums for the launch to fold them itself (profiles/fused_vectors.md)
     int fused_timeout_ms = 2000; // AVS_PCG_FUSED_TIMEOUT_MS: bound of that barrier's wait
     int post_dof_sample = -1;    // AVS_POST_DOF_SAMPLE: the transfer samples its nodes from the velocity DOFs (1) / by a sweep over the node lattices (0);
                                  // -1: from the DOFs when the level-0 node lattice has more than 32 x as many nodes as there are DOFs

@@ -61,6 +61,7 @@ struct PcgWork {
     DevBuf<unsigned long long> fused_bar; // k_update_fused: the grid barrier's ticket counter (monotonic)
     bool fused_off = false;  // ... a launch of it timed out at its barrier on this workspace: the two-launch form from then on
     int fused_faults = 0, fused_used = 0;
+    float fused_void_ms = 0.f; // a solve whose fused launch timed out: the time of the voided attempt (added to the redo's solve_ms)
     DevBuf<double> s, u; // single-reduction variant (multi-GPU): s = A p recurrence, u = M^-1 r with halo tail
     DevBuf<PcgScalars> sc;
     DevBuf<double> stage2;         // direct transport: per-workgroup SpMV sums of the halo-touching launch
@@ -409,23 +410,37 @@ __global__ __launch_bounds__(kBlock) void k_update_xp(int64_t n, double *__restr
 }
 
 // ---------------------------------------------------------------------------------------------
-// Round 6 (review r05 #3): k_update_r and k_update_xp as ONE launch for HBM-sized systems -- r -= alpha t with its two sums, a GRID
-// BARRIER, then x += alpha p ; p = invd r + beta p with the new r (and the diagonal codes) still in REGISTERS: 7.25 n instead of
-// 8.5 n doubles of traffic per iteration and one launch boundary less.  kFusedGrid workgroups of 1024 threads, one per CU (128 registers
-// per lane: 16 rows of r per lane x 2); every sum is formed in exactly the order of the two kernels it replaces -- thread T of
-// workgroup B plays the threads (T & 255) of the 256-thread workgroups 4 B + (T >> 8) and 1024 + 4 B + (T >> 8) of the
-// kVecGrid-workgroup launches (same rows, same order, the same wave / four-wave folds, the same partial-sum arrays, the same 256-lane
-// folds of them) -- so the iteration, its scalars and the solution are bit-identical with the option on or off.
-// The barrier: the partial sums leave with write-through stores (agent scope), one monotonic 64-bit counter (never reset: a launch's
-// target is the next multiple of the grid above its own ticket), relaxed polls with s_sleep, bounded by wall_clock64 -- a grid that is
-// not co-resident in time (the GPU shared with other work) sets sc->fault instead of hanging.  No L2 write-back fence anywhere: what
-// crosses the barrier is read with agent-scope loads.  Plain launch (a graph node like any other); needs every CU free, which holds behind the persistent SpMV.
+// k_update_r and k_update_xp as ONE launch for HBM-sized systems -- r -= alpha t with its two sums, a GRID BARRIER, then x += alpha p ;
+// p = invd r + beta p with the new r still in REGISTERS and LDS: 7.25 n instead of 8.5 n doubles of traffic per iteration and one launch
+// boundary less.  kVecGrid / 8 workgroups of 1024 threads, one per CU (128 registers per lane: 16 rows of r per lane x 2); every sum is
+// formed in exactly the order of the two kernels it replaces -- thread T of workgroup B plays the threads (T & 255) of the 256-thread
+// workgroups 4 B + (T >> 8) and 1024 + 4 B + (T >> 8) of the kVecGrid-workgroup launches (same rows, same order, the same wave /
+// four-wave folds, the same partial-sum arrays, the same 256-lane folds of them, which every quarter forms for itself) -- so the
+// iteration, its scalars and the solution are bit-identical with the option on or off.
+// Order of the requests (profiles/fused_vectors.md; the order of vec_request / vec_fold above):
+//   entry     done and the scalars, the thread's share of the SpMV's partial sums (branch-free), its share of the inverted dictionary,
+//             the first batch of r, t and codes -- all before anything is waited for; the fold and the dictionary's way into LDS share
+//             one workgroup barrier, with the streams in flight;
+//   phase 1   r, t, the codes and the store of r are NON-TEMPORAL unless KEEP (r is not read again before it is overwritten, and must
+//             not push the matrix and p out of the Infinity Cache in front of the SpMV); p stays plain, the SpMV reads it next;
+//   barrier   the first batch of phase 2 (p, x, codes: nothing of it depends on phase 1) is requested before the four sums of the
+//             workgroup's halves go through ONE workgroup barrier and are published; behind the last poll every thread requests its
+//             8 + 8 partial sums at once, folds them through one more workgroup barrier, and phase 2 starts on loads that have landed.
+// The barrier: the partial sums leave with write-through stores (agent scope), one monotonic 64-bit counter (a launch's target is the
+// next multiple of the grid above its own ticket), relaxed polls with s_sleep, bounded by wall_clock64 -- a grid that is not co-resident
+// in time (the GPU shared with other work) sets sc->fault instead of hanging.  No L2 write-back fence anywhere: what crosses the barrier
+// is read with agent-scope loads.  Plain launch (a graph node like any other); needs every CU free, which holds behind the persistent SpMV.
 // ---------------------------------------------------------------------------------------------
 static constexpr size_t kFusedTabBytes = (size_t)(kViLdsTable + 1) * sizeof(double) + 8; // CODED: the inverted dictionary
 static constexpr size_t kFusedLds = (size_t)8 * 1024 * 16; // the second emulated workgroup's new r: kFusedPairs x kFusedBlock pairs of doubles
 static constexpr unsigned kFusedStride = (unsigned)kVecGrid * kBlock * 16u; // bytes between two pairs of an emulated thread
 static constexpr int kFusedBlock = 1024, kFusedPairs = 8, kFusedBatch = 4; // (loads in flight per lane: kFusedBatch pairs of rows of each stream)
+static constexpr int kFusedTabAhead = (kViLdsTable + 1 + kFusedBlock - 1) / kFusedBlock; // dictionary entries a thread requests at entry
 // (kFusedPairs pairs of rows per emulated thread: n <= 2 * kFusedPairs * kVecGrid * kBlock rows)
+static_assert(kVecGrid == kFoldBatch * kBlock, "the beta fold requests all of a thread's partial sums in one batch");
+#ifndef AVS_EXP_FUSED_AHEAD // where phase 2's first batch is requested (the experiment of profiles/fused_vectors.md): 0 behind the beta fold,
+#define AVS_EXP_FUSED_AHEAD 2 // 1 in front of the partial sums' publication, 2 behind the ticket
+#endif
 // element at a 32-bit BYTE offset from a uniform base (global_load ... saddr: no 64-bit address per lane and stream kept in registers)
 template <class T> __device__ __forceinline__ T *at_off(T *base, unsigned byte_off)
 {
@@ -435,16 +450,11 @@ template <class T> __device__ __forceinline__ const T *at_off(const T *base, uns
 {
     return reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + (size_t)byte_off);
 }
-__device__ __forceinline__ double quarter_sum(double v, double *lds4, int t) // block_sum of the 256-thread workgroup this quarter plays (valid where t == 0)
-{
-    v = wave_sum(v);
-    __syncthreads();
-    if ((t & 63) == 0) lds4[t >> 6] = v;
-    __syncthreads();
-    double s = 0.;
-    if (t == 0) s = ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
-    return s;
-}
+// one batch of a phase's streams as loaded: u, v = (r, t) in phase 1 and (p, x) in phase 2; the codes or the inverse diagonal of the rows
+struct FusedBatch {
+    d2_t u[kFusedBatch], v[kFusedBatch], idv[kFusedBatch];
+    unsigned cc[kFusedBatch];
+};
 template <bool CODED, bool KEEP>
 __global__ __launch_bounds__(kFusedBlock) void k_update_fused(int64_t n, double *__restrict__ x, double *__restrict__ p, double *__restrict__ r,
                                                               const double *__restrict__ t, const double *__restrict__ invd,
@@ -452,82 +462,131 @@ __global__ __launch_bounds__(kFusedBlock) void k_update_fused(int64_t n, double 
                                                               const double *__restrict__ spmv_partial, int nb, int parity,
                                                               unsigned long long *__restrict__ bar, long long timeout_ticks, int tab_n)
 {
-    {
-        const int d = sc->done;
-        if (d) {
-            if (blockIdx.x == 0 && threadIdx.x == 0 && d == 2) sc->done = 1; // the pending x update has run
-            return;
-        }
-    }
-    __shared__ double red[4][4];
-    __shared__ double bc[4];
+    // (every array is written once per launch: no barrier guards a reuse)
+    __shared__ double fold_a[4][4];   // alpha fold: [quarter][wave]
+    __shared__ double sums[4][4][4];  // phase 1: [quarter][rr0, rz0, rr1, rz1][wave]
+    __shared__ double fold_b[4][8];   // beta fold: [quarter][rr waves | rz waves]
     __shared__ int sh_fail;
-    const int T = threadIdx.x, tq = T & 255, q = T >> 8;
-    constexpr int g = kVecGrid;
-    if (CODED) { // the inverted dictionary into LDS (a look-up per row and phase: from L1 it was a second, dependent round trip per batch)
-        extern __shared__ __attribute__((aligned(16))) unsigned char fused_lds0[];
-        double *tw = reinterpret_cast<double *>(fused_lds0 + kFusedLds);
-        for (int i = T; i < tab_n; i += kFusedBlock) tw[i] = invd[i];
-    }
-    // ---- alpha: the fold of the SpMV's partial sums as every workgroup of k_update_r<FUSED> does it (the barriers in it publish the table)
-    double pap = 0.;
-    if (q == 0)
-        for (int k = tq; k < nb; k += kBlock) pap += spmv_partial[k];
-    pap = quarter_sum(pap, red[q], tq);
-    if (T == 0) { bc[0] = pap; sh_fail = 0; }
-    __syncthreads();
-    pap = bc[0];
-    const double rho_old = parity ? sc->rho_alt : sc->rho;
-    const double alpha = rho_old / pap;
-    // ---- phase 1: r -= alpha t   (loads of a lane beyond the last pair are clamped to pair 0 and their results dropped: no branches
-    //      around the loads, one predicate per store and per sum)
- const int64_t n2 = n >> 1;
-    const unsigned lim = (unsigned)n2 * 16u;               // byte offset behind the last pair
-    d2_t rn[kFusedPairs];                                  // the new r of the first emulated workgroup's rows: registers ...
     extern __shared__ __attribute__((aligned(16))) unsigned char fused_lds[];
-    d2_t *rl = reinterpret_cast<d2_t *>(fused_lds);        // ... of the second one's: LDS, rl[m * kFusedBlock + T] (128 KiB)
-    const double *tab = reinterpret_cast<const double *>(fused_lds + kFusedLds); // CODED: the inverted dictionary (tab_n entries), staged below
-    double rr[2] = {0., 0.}, rz[2] = {0., 0.};
+    d2_t *rl = reinterpret_cast<d2_t *>(fused_lds);                  // the new r of the second emulated workgroup's rows: rl[m * kFusedBlock + T] (128 KiB)
+    double *tab = reinterpret_cast<double *>(fused_lds + kFusedLds); // CODED: the inverted dictionary (tab_n entries)
+    const int T = threadIdx.x, tq = T & 255, q = T >> 8, wv = tq >> 6;
+    constexpr int g = kVecGrid;
+    const int64_t n2 = n >> 1;
+    const unsigned lim = (unsigned)n2 * 16u; // byte offset behind the last pair (n < 2^28 rows: checked by the host)
+    // byte offset of pair m of the emulated thread of half h; the loads of a lane beyond the last pair are clamped to pair 0 and their
+    // results dropped: no branches around the loads, one predicate per store and per sum
+    // (opaque: an offset is formed again wherever it is used instead of being carried, spilled, through the kernel)
+    auto pair_off = [&](int h, int m) {
+        unsigned o = (unsigned)T;
+        asm volatile("" : "+v"(o));
+        return (((unsigned)blockIdx.x * 4u + (o >> 8) + (unsigned)(g / 2) * (unsigned)h) * kBlock + (o & 255u)) * 16u + (unsigned)m * kFusedStride;
+    };
+    auto request1 = [&](int h, int m0, FusedBatch &b) {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int b = (int)blockIdx.x * 4 + q + (g / 2) * h;
-        const unsigned o0 = ((unsigned)b * kBlock + (unsigned)tq) * 16u; // byte offset of this lane's first pair (n < 2^28 rows: checked by the host)
-#pragma unroll
-        for (int m0 = 0; m0 < kFusedPairs; m0 += kFusedBatch) {
-            d2_t rv[kFusedBatch], tv[kFusedBatch], idv[kFusedBatch];
-            unsigned cc[kFusedBatch];
-#pragma unroll
-            for (int u = 0; u < kFusedBatch; ++u) {
-                const unsigned oj = o0 + (unsigned)(m0 + u) * kFusedStride;
-                const unsigned o = oj < lim ? oj : 0u;
-                rv[u] = *reinterpret_cast<const d2_t *>(at_off(r, o));
-                tv[u] = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(at_off(t, o)));
-                if (CODED) cc[u] = *reinterpret_cast<const unsigned *>(at_off(dcode, o >> 2)); // (read again in phase 2: 0.25 n)
-                else idv[u] = *reinterpret_cast<const d2_t *>(at_off(invd, o));
-            }
-#pragma unroll
-            for (int u = 0; u < kFusedBatch; ++u) {
-                const int m = m0 + u;
-                const unsigned oj = o0 + (unsigned)m * kFusedStride;
-                double id0, id1;
-                if (CODED) { id0 = tab[cc[u] & 0xffffu]; id1 = tab[cc[u] >> 16]; }
-                else { id0 = idv[u].x; id1 = idv[u].y; }
-                d2_t v;
-                v.x = rv[u].x - alpha * tv[u].x;
-                v.y = rv[u].y - alpha * tv[u].y;
-                if (h == 0) rn[m] = v;
-                else rl[m * kFusedBlock + T] = v;
-                if (oj < lim) {
-                    *reinterpret_cast<d2_t *>(at_off(r, oj)) = v;
-                    rr[h] += v.x * v.x;
-                    rz[h] += v.x * (id0 * v.x);
-                    rr[h] += v.y * v.y;
-                    rz[h] += v.y * (id1 * v.y);
-                }
-            }
-            asm volatile("" ::: "memory"); // (the next batch's loads stay behind this batch: registers)
-            __builtin_amdgcn_sched_barrier(0);
+        for (int u = 0; u < kFusedBatch; ++u) {
+            const unsigned oj = pair_off(h, m0 + u), o = oj < lim ? oj : 0u;
+            b.u[u] = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(at_off(r, o)));
+            b.v[u] = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(at_off(t, o)));
+            if (CODED) b.cc[u] = stream_load_k<KEEP>(reinterpret_cast<const unsigned *>(at_off(dcode, o >> 2))); // (read again in phase 2: 0.25 n)
+            else b.idv[u] = *reinterpret_cast<const d2_t *>(at_off(invd, o));
         }
+    };
+    auto request2 = [&](int h, int m0, FusedBatch &b, bool px, bool id) { // px: p and x; id: the codes / the inverse diagonal
+#pragma unroll
+        for (int u = 0; u < kFusedBatch; ++u) {
+            const unsigned oj = pair_off(h, m0 + u), o = oj < lim ? oj : 0u;
+            if (px) {
+                b.u[u] = *reinterpret_cast<const d2_t *>(at_off(p, o));
+                b.v[u] = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(at_off(x, o)));
+            }
+            if (id) {
+                if (CODED) b.cc[u] = stream_load_k<KEEP>(reinterpret_cast<const unsigned *>(at_off(dcode, o >> 2)));
+                else b.idv[u] = *reinterpret_cast<const d2_t *>(at_off(invd, o));
+            }
+        }
+    };
+    // ---- entry: every request that depends on nothing, in the order in which the results are needed (loads return in order)
+    const int d = sc->done;
+    const double rho_old = parity ? sc->rho_alt : sc->rho, threshold = sc->threshold, alpha_in = sc->alpha;
+    double va[kFoldBatch], dv[kFusedTabAhead];
+#pragma unroll
+    for (int u = 0; u < kFoldBatch; ++u) {
+        const int k = u * kBlock + tq;
+        va[u] = spmv_partial[k < nb ? k : 0];
+    }
+    if (CODED) {
+#pragma unroll
+        for (int u = 0; u < kFusedTabAhead; ++u) {
+            const int i = u * kFusedBlock + T;
+            dv[u] = invd[i < tab_n ? i : 0];
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    FusedBatch cur;
+    request1(0, 0, cur);
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- alpha: the fold of the SpMV's partial sums as every workgroup of k_update_r<FUSED> does it, by every quarter for itself (the
+    //      barrier in it publishes the table)
+    double pap = 0.;
+#pragma unroll
+    for (int u = 0; u < kFoldBatch; ++u) pap += u * kBlock + tq < nb ? va[u] : 0.;
+    for (int k = kFoldBatch * kBlock + tq; k < nb; k += kBlock) pap += spmv_partial[k]; // (beyond 2048 partial sums)
+    pap = wave_sum(pap);
+    if ((T & 63) == 0) fold_a[q][wv] = pap;
+    if (CODED) {
+#pragma unroll
+        for (int u = 0; u < kFusedTabAhead; ++u) {
+            const int i = u * kFusedBlock + T;
+            if (i < tab_n) tab[i] = dv[u];
+        }
+    }
+    if (T == 0) sh_fail = 0;
+    __syncthreads();
+    if (d) { // (the loads that went ahead are dropped)
+        if (blockIdx.x == 0 && T == 0 && d == 2 && nb) sc->done = 1; // the pending x update has run (nb == 0: OP_ALPHA has said so)
+        return;
+    }
+    pap = ((fold_a[q][0] + fold_a[q][1]) + fold_a[q][2]) + fold_a[q][3];
+    const double alpha = nb ? rho_old / pap : alpha_in; // (nb == 0: the alpha step was a launch of its own, as in front of k_update_r<., false, .>)
+    // ---- phase 1: r -= alpha t
+    d2_t rn[kFusedPairs]; // the new r of the first emulated workgroup's rows: registers
+    double rr[2] = {0., 0.}, rz[2] = {0., 0.};
+    auto consume1 = [&](int h, int m0, const FusedBatch &b) {
+#pragma unroll
+        for (int u = 0; u < kFusedBatch; ++u) {
+            const int m = m0 + u;
+            const unsigned oj = pair_off(h, m);
+            // (opaque: used here, in front of the predicate -- the optimiser otherwise sinks a batch's first code load into the predicated
+            //  block, where it becomes a second, dependent round trip)
+            unsigned c = CODED ? b.cc[u] : 0u;
+            double id0 = CODED ? 0. : b.idv[u].x, id1 = CODED ? 0. : b.idv[u].y;
+            if (CODED) {
+                asm volatile("" : "+v"(c));
+                id0 = tab[c & 0xffffu];
+                id1 = tab[c >> 16];
+            } else asm volatile("" : "+v"(id0), "+v"(id1));
+            d2_t v;
+            v.x = b.u[u].x - alpha * b.v[u].x;
+            v.y = b.u[u].y - alpha * b.v[u].y;
+            if (h == 0) rn[m] = v;
+            else rl[m * kFusedBlock + T] = v;
+            if (oj < lim) {
+                stream_store_k<KEEP>(v, reinterpret_cast<d2_t *>(at_off(r, oj)));
+                rr[h] += v.x * v.x;
+                rz[h] += v.x * (id0 * v.x);
+                rr[h] += v.y * v.y;
+                rz[h] += v.y * (id1 * v.y);
+            }
+        }
+    };
+    constexpr int kBatches = 2 * kFusedPairs / kFusedBatch; // of a phase: the first half's, then the second half's
+#pragma unroll
+    for (int k = 0; k < kBatches; ++k) {
+        consume1(k / (kBatches / 2), k % (kBatches / 2) * kFusedBatch, cur);
+        __builtin_amdgcn_sched_barrier(0); // (the next batch's loads stay behind this batch: registers)
+        if (k + 1 < kBatches) request1((k + 1) / (kBatches / 2), (k + 1) % (kBatches / 2) * kFusedBatch, cur);
+        __builtin_amdgcn_sched_barrier(0);
     }
     double r_last = 0.;
     if ((n & 1) && blockIdx.x == 0 && T == 0) { // (the odd last row: thread 0 of workgroup 0 of k_update_r)
@@ -537,12 +596,26 @@ __global__ __launch_bounds__(kFusedBlock) void k_update_fused(int64_t n, double 
         rr[0] += r_last * r_last;
         rz[0] += r_last * ((CODED ? invd[dcode[i]] : invd[i]) * r_last);
     }
+#if AVS_EXP_FUSED_AHEAD == 1
+    request2(0, 0, cur, true, CODED);
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+    {
+        const double s0 = wave_sum(rr[0]), s1 = wave_sum(rz[0]), s2 = wave_sum(rr[1]), s3 = wave_sum(rz[1]);
+        if ((T & 63) == 0) {
+            sums[q][0][wv] = s0;
+            sums[q][1][wv] = s1;
+            sums[q][2][wv] = s2;
+            sums[q][3][wv] = s3;
+        }
+    }
+    __syncthreads();
+    if (tq == 0) { // write-through: the other workgroups read these behind the barrier
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const double srr = quarter_sum(rr[h], red[q], tq);
-        const double srz = quarter_sum(rz[h], red[q], tq);
-        if (tq == 0) { // write-through: the other workgroups read these behind the barrier
+        for (int h = 0; h < 2; ++h) {
             const int b = (int)blockIdx.x * 4 + q + (g / 2) * h;
+            const double srr = ((sums[q][2 * h][0] + sums[q][2 * h][1]) + sums[q][2 * h][2]) + sums[q][2 * h][3];
+            const double srz = ((sums[q][2 * h + 1][0] + sums[q][2 * h + 1][1]) + sums[q][2 * h + 1][2]) + sums[q][2 * h + 1][3];
             __hip_atomic_store(vpart + b, srr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(vpart + g + b, srz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -550,8 +623,17 @@ __global__ __launch_bounds__(kFusedBlock) void k_update_fused(int64_t n, double 
     // ---- grid barrier
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the partial sums are acknowledged before the ticket is drawn
     __syncthreads();
+    unsigned long long ticket = 0;
+    if (T == 0) ticket = __hip_atomic_fetch_add(bar, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#if AVS_EXP_FUSED_AHEAD == 2
+    // phase 2's first batch leaves here, behind the ticket: it is under way while the grid meets and the sums are folded, and it does not
+    // hold the ticket back (in front of it, it sat under the wait for the partial sums' acknowledgement: profiles/fused_vectors.md).
+    // The 8-B inverse diagonal of its rows follows when the partial sums' registers are free again (128 registers per lane)
+    __builtin_amdgcn_sched_barrier(0);
+    request2(0, 0, cur, true, CODED);
+    __builtin_amdgcn_sched_barrier(0);
+#endif
     if (T == 0) {
-        const unsigned long long ticket = __hip_atomic_fetch_add(bar, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long target = (ticket / gridDim.x + 1ull) * gridDim.x;
         const long long t0 = wall_clock64();
         while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
@@ -560,6 +642,15 @@ __global__ __launch_bounds__(kFusedBlock) void k_update_fused(int64_t n, double 
         }
     }
     __syncthreads();
+    // ---- beta: the fold of the 2 g partial sums as every workgroup of k_update_xp<FUSED> does it, by every quarter for itself; all
+    //      of a thread's 8 + 8 are requested before the first is waited for
+    double fa[kFoldBatch], fb[kFoldBatch];
+#pragma unroll
+    for (int u = 0; u < kFoldBatch; ++u) {
+        fa[u] = __hip_atomic_load(vpart + u * kBlock + tq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        fb[u] = __hip_atomic_load(vpart + g + u * kBlock + tq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __builtin_amdgcn_sched_barrier(0);
     if (sh_fail) { // not every workgroup arrived in time: the solve is void (the host reads sc->fault and redoes it with the two launches)
         if (T == 0) {
             __hip_atomic_store(&sc->fault, 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -567,26 +658,37 @@ __global__ __launch_bounds__(kFusedBlock) void k_update_fused(int64_t n, double 
         }
         return;
     }
-    // ---- beta: the fold of the 2 g partial sums as every workgroup of k_update_xp<FUSED> does it
     double frr = 0., frz = 0.;
-    if (q == 0)
-        for (int i = tq; i < g; i += kBlock) {
-            frr += __hip_atomic_load(vpart + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            frz += __hip_atomic_load(vpart + g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    frr = quarter_sum(frr, red[q], tq);
-    frz = quarter_sum(frz, red[q], tq);
-    if (T == 0) { bc[1] = frr; bc[2] = frz; }
+#pragma unroll
+    for (int u = 0; u < kFoldBatch; ++u) {
+        frr += fa[u];
+        frz += fb[u];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#if AVS_EXP_FUSED_AHEAD != 0
+    if (!CODED) request2(0, 0, cur, false, true);
+#else
+    request2(0, 0, cur, true, true);
+#endif
+    __builtin_amdgcn_sched_barrier(0);
+    frr = wave_sum(frr);
+    frz = wave_sum(frz);
+    if ((T & 63) == 0) {
+        fold_b[q][wv] = frr;
+        fold_b[q][4 + wv] = frz;
+    }
     __syncthreads();
-    frr = bc[1];
-    frz = bc[2];
+    frr = ((fold_b[q][0] + fold_b[q][1]) + fold_b[q][2]) + fold_b[q][3];
+    frz = ((fold_b[q][4] + fold_b[q][5]) + fold_b[q][6]) + fold_b[q][7];
     int done = 0;
     double beta = 0.;
-    if (frr < sc->threshold) done = 2; // Eigen: break before i++ (x += alpha p still runs)
+    if (frr < threshold) done = 2; // Eigen: break before i++ (x += alpha p still runs)
     else beta = frz / rho_old;
     if (blockIdx.x == 0 && T == 0) { // what OP_ALPHA and OP_BETA do
-        sc->pAp = pap;
-        sc->alpha = alpha;
+        if (nb) {
+            sc->pAp = pap;
+            sc->alpha = alpha;
+        }
         sc->red[0] = frr;
         sc->red[1] = frz;
         sc->rr = frr;
@@ -599,45 +701,40 @@ __global__ __launch_bounds__(kFusedBlock) void k_update_fused(int64_t n, double 
         }
     }
     // ---- phase 2: x += alpha p ; p = invd r + beta p
+    auto consume2 = [&](int h, int m0, const FusedBatch &b) {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int b = (int)blockIdx.x * 4 + q + (g / 2) * h;
-        unsigned o0 = ((unsigned)b * kBlock + (unsigned)tq) * 16u;
-        asm volatile("" : "+v"(o0)); // (opaque: the addresses are formed again here instead of being carried, spilled, across the barrier from phase 1)
-#pragma unroll
-        for (int m0 = 0; m0 < kFusedPairs; m0 += kFusedBatch) {
-            d2_t pv[kFusedBatch], xv[kFusedBatch], idv[kFusedBatch]; // (the diagonal codes / the inverse diagonal are read again, r stays in registers)
-            unsigned cc[kFusedBatch];
-#pragma unroll
-            for (int u = 0; u < kFusedBatch; ++u) {
-                const unsigned oj = o0 + (unsigned)(m0 + u) * kFusedStride;
-                const unsigned o = oj < lim ? oj : 0u;
-                pv[u] = *reinterpret_cast<const d2_t *>(at_off(p, o));
-                xv[u] = stream_load_k<KEEP>(reinterpret_cast<const d2_t *>(at_off(x, o)));
-                if (CODED) cc[u] = stream_load_k<KEEP>(reinterpret_cast<const unsigned *>(at_off(dcode, o >> 2)));
-                else idv[u] = *reinterpret_cast<const d2_t *>(at_off(invd, o));
+        for (int u = 0; u < kFusedBatch; ++u) {
+            const int m = m0 + u;
+            const unsigned oj = pair_off(h, m);
+            // (opaque: used here, in front of the predicate -- the optimiser otherwise sinks a batch's first code load into the predicated
+            //  block, where it becomes a second, dependent round trip)
+            unsigned c = CODED ? b.cc[u] : 0u;
+            double id0 = CODED ? 0. : b.idv[u].x, id1 = CODED ? 0. : b.idv[u].y;
+            if (CODED) {
+                asm volatile("" : "+v"(c));
+                id0 = tab[c & 0xffffu];
+                id1 = tab[c >> 16];
+            } else asm volatile("" : "+v"(id0), "+v"(id1));
+            const d2_t rv = h == 0 ? rn[m] : rl[m * kFusedBlock + T];
+            double p0 = b.u[u].x, p1 = b.u[u].y, x0 = b.v[u].x, x1 = b.v[u].y;
+            asm volatile("" : "+v"(p0), "+v"(p1), "+v"(x0), "+v"(x1)); // (as the codes: everything below is used behind the predicate only)
+            d2_t xn, pn;
+            xn.x = x0 + alpha * p0;
+            xn.y = x1 + alpha * p1;
+            pn.x = id0 * rv.x + beta * p0;
+            pn.y = id1 * rv.y + beta * p1;
+            if (oj < lim) {
+                stream_store_k<KEEP>(xn, reinterpret_cast<d2_t *>(at_off(x, oj)));
+                if (done != 2) *reinterpret_cast<d2_t *>(at_off(p, oj)) = pn;
             }
-#pragma unroll
-            for (int u = 0; u < kFusedBatch; ++u) {
-                const int m = m0 + u;
-                const unsigned oj = o0 + (unsigned)m * kFusedStride;
-                double id0, id1;
-                if (CODED) { id0 = tab[cc[u] & 0xffffu]; id1 = tab[cc[u] >> 16]; }
-                else { id0 = idv[u].x; id1 = idv[u].y; }
-                d2_t xn, pn;
-                const d2_t rv = h == 0 ? rn[m] : rl[m * kFusedBlock + T];
-                xn.x = xv[u].x + alpha * pv[u].x;
-                xn.y = xv[u].y + alpha * pv[u].y;
-                pn.x = id0 * rv.x + beta * pv[u].x;
-                pn.y = id1 * rv.y + beta * pv[u].y;
-                if (oj < lim) {
-                    stream_store_k<KEEP>(xn, reinterpret_cast<d2_t *>(at_off(x, oj)));
-                    if (done != 2) *reinterpret_cast<d2_t *>(at_off(p, oj)) = pn;
-                }
-            }
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
         }
+    };
+#pragma unroll
+    for (int k = 0; k < kBatches; ++k) {
+        consume2(k / (kBatches / 2), k % (kBatches / 2) * kFusedBatch, cur);
+        __builtin_amdgcn_sched_barrier(0);
+        if (k + 1 < kBatches) request2((k + 1) / (kBatches / 2), (k + 1) % (kBatches / 2) * kFusedBatch, cur, true, true);
+        __builtin_amdgcn_sched_barrier(0);
     }
     if ((n & 1) && blockIdx.x == 0 && T == 0) {
         const int64_t i = n - 1;
@@ -972,6 +1069,8 @@ static avs_status finish_info(PcgWork *w, const CsrView &A, hipStream_t stream, 
     AVS_HIP(hipEventSynchronize(w->ev1));
     float ms = 0.f;
     AVS_HIP(hipEventElapsedTime(&ms, w->ev0, w->ev1));
+    const float void_ms = w->fused_void_ms;
+    w->fused_void_ms = 0.f;
     if (!info) return AVS_OK;
     const PcgScalars &h = *w->host_sc;
     info->iterations = h.iter;
@@ -981,7 +1080,7 @@ static avs_status finish_info(PcgWork *w, const CsrView &A, hipStream_t stream, 
     else info->error = f32 ? (double)sqrtf((float)h.rr / (float)h.rhs_norm2) : sqrt(h.rr / h.rhs_norm2);
     info->n = A.n;
     info->nnz = A.nnz;
-    info->solve_ms = ms;
+    info->solve_ms = ms + void_ms; // (a redo behind a timed-out fused launch: the voided attempt counts)
     info->spmv_ms = (cs && cs->spmv_samples) ? cs->spmv_ms_sum / cs->spmv_samples : 0.;
     info->resident = resident;
     info->cancelled = cancelled ? 1 : 0;
@@ -2042,28 +2141,36 @@ void pcg_resident_plan_info(const PcgWork *w, avs_resident_plan_info *out)
 // One fused launch for the two vector kernels of the fp64 launch-per-phase loop (k_update_fused): HBM-sized single-GPU systems whose
 // rows fit its registers, a device with one CU per workgroup of its grid.  *on: this solve uses it; then the initial guess is kept, so
 // that a timed-out barrier costs a redo, not a wrong answer.  fuse_beta: the loop's (never with a partition).
+static avs_status fused_raise_lds() // the kernel's dynamic LDS limit: once per device
+{
+    static std::atomic<unsigned long long> raised{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev >= 0 && dev < 64 && !((raised.load() >> dev) & 1ull)) {
+        AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
+        AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
+        AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
+        AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
+        raised.fetch_or(1ull << dev);
+    }
+    return AVS_OK;
+}
+static bool fused_device_fits() // one CU per workgroup of the fused launch's grid
+{
+    int dev = 0, cus = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus >= kVecGrid / 8;
+}
 static avs_status fused_vectors_setup(PcgWork *w, const CsrView &A, const double *x, int g, bool fuse_beta, bool keep, hipStream_t stream, bool *on)
 {
     const int64_t n = A.n;
     bool fuse_vec = false;
     if (fuse_beta && cur_opt().fuse_vectors != 0 && !w->fused_off && g == kVecGrid && n <= (int64_t)2 * kFusedPairs * kVecGrid * kBlock &&
-        n < ((int64_t)1 << 28) && (cur_opt().fuse_vectors > 0 || !keep)) {
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        fuse_vec = cus >= kVecGrid / 8;
-    }
+        n < ((int64_t)1 << 28) && (cur_opt().fuse_vectors > 0 || !keep))
+        fuse_vec = fused_device_fits();
     if (fuse_vec) {
-        static std::atomic<unsigned long long> raised{0}; // the kernel's dynamic LDS limit: once per device
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev >= 0 && dev < 64 && !((raised.load() >> dev) & 1ull)) {
-            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
-            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
-            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
-            AVS_HIP(hipFuncSetAttribute((const void *)k_update_fused<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFusedLds + kFusedTabBytes)));
-            raised.fetch_or(1ull << dev);
-        }
+        AVS_TRY(fused_raise_lds());
         if (!w->fused_bar.p) {
             AVS_TRY(w->fused_bar.alloc(2));
             AVS_HIP(hipMemsetAsync(w->fused_bar.p, 0, 2 * sizeof(unsigned long long), stream));
@@ -2071,7 +2178,7 @@ static avs_status fused_vectors_setup(PcgWork *w, const CsrView &A, const double
         AVS_TRY(w->x_save.alloc((size_t)n));
         AVS_HIP(hipMemcpyAsync(w->x_save.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     }
-    w->fused_used = fuse_vec ? 1 : 0;
+    w->fused_used = 0; // (1 once a fused launch has been enqueued: the loop falls back to the two launches where the SpMV leaves many partial sums)
     *on = fuse_vec;
     return AVS_OK;
 }
@@ -2199,15 +2306,20 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
         const int parity = fuse_beta ? (c & 1) : 0;
         const bool fuse_alpha = fuse_beta && nb <= kFuseAlphaMax; // few SpMV partials: every workgroup of update_r folds them itself
         double *vpart = (F32 || fuse_alpha) ? upper : partial;
+        // the fused launch.  Where the SpMV leaves more partial sums than a workgroup folds for itself the alpha step stays a launch of
+        // its own in front of it (nb = 0): only when the option is 1 -- "auto" (-1) takes the form that was measured
+        const bool fused_launch = !F32 && fuse_vec && (fuse_alpha || cur_opt().fuse_vectors > 0);
+        if (!fuse_alpha) AVS_TRY(reduce_stage(w, nb, 1, parity ? OP_ALPHA_ODD : OP_ALPHA, tol, 1, stream, dist));
         if constexpr (!F32)
-            if (fuse_vec && fuse_alpha) {
+            if (fused_launch) {
+                w->fused_used = 1; // (every solve enqueues its first chunk launch by launch, so this runs in each that iterates)
                 with_flags([&](auto C, auto K) {
                     hipLaunchKernelGGL((k_update_fused<C.value, K.value>), dim3(kVecGrid / 8), dim3(kFusedBlock), kFusedLds + (C.value ? kFusedTabBytes : 0),
-                                       stream, n, x, p, r, t, inv, dcode, sc, vpart, partial, nb, parity, w->fused_bar.p, fused_timeout, A.table_size + 1);
+                                       stream, n, x, p, r, t, inv, dcode, sc, vpart, partial, fuse_alpha ? nb : 0, parity, w->fused_bar.p, fused_timeout,
+                                       A.table_size + 1);
                 }, coded, keep);
                 return AVS_OK;
             }
-        if (!fuse_alpha) AVS_TRY(reduce_stage(w, nb, 1, parity ? OP_ALPHA_ODD : OP_ALPHA, tol, 1, stream, dist));
         const int r_parity = (F32 || fuse_alpha) ? parity : 0; // (the unfused fp64 kernel reads what OP_ALPHA left: no parity)
         with_flags([&](auto C, auto FA, auto K) {
             const double *spart = FA.value ? partial : nullptr;
@@ -2278,7 +2390,15 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
         if (fuse_vec && w->host_sc->fault == 4) { // the fused launch's grid barrier timed out (GPU shared with other work): the solve again, from
             w->fused_off = true;                    // the initial guess, with the two vector launches -- on this workspace from now on
             w->fused_faults++;
+            w->fused_used = 0;
             drop_graph(w);
+            AVS_HIP(hipEventRecord(w->ev1, stream));
+            AVS_HIP(hipEventSynchronize(w->ev1));
+            float void_ms = 0.f;
+            AVS_HIP(hipEventElapsedTime(&void_ms, w->ev0, w->ev1));
+            w->fused_void_ms += void_ms;
+            // (workgroups that gave up have left the counter between two multiples of the grid)
+            AVS_HIP(hipMemsetAsync(w->fused_bar.p, 0, 2 * sizeof(unsigned long long), stream));
             AVS_HIP(hipMemcpyAsync(x, w->x_save.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
             return pcg_solve(w, A, b, x, tol, max_iters, stream, info, dist);
         }
@@ -2348,12 +2468,44 @@ static void vector_probe_f32(int g, int64_t n, int nb, int parity, float *x, flo
     hipLaunchKernelGGL((k_f32_update_xp<CODED, KEEP, DS>), dim3(g), dim3(kBlock), 0, stream, n, x, p, (const float *)r, invd, dcode, sc,
                        (const double *)vpart, g, parity);
 }
+__global__ __launch_bounds__(kBlock) void k_probe_max_code(int64_t n, const uint16_t *__restrict__ dcode, unsigned long long *__restrict__ top)
+{
+    unsigned long long m = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) m = m > dcode[i] ? m : dcode[i];
+    if (m) atomicMax(top, m);
+}
 size_t vector_update_probe_scalars_size() { return sizeof(PcgScalars); }
 avs_status vector_update_probe(int flags, int g, int64_t n, int nb, int parity, void *x, void *p, void *r, const void *t, const void *invd,
                                const uint16_t *dcode, const double *spmv_partial, double *vpart, void *scalars, hipStream_t stream)
 {
     PcgScalars *sc = static_cast<PcgScalars *>(scalars);
     const bool ds = (flags & AVS_VECTOR_PROBE_DS) != 0, f32 = ds || (flags & AVS_VECTOR_PROBE_F32) != 0;
+    if (flags & AVS_VECTOR_PROBE_ONE_LAUNCH) { // k_update_fused in place of the pair, as the fp64 loop launches it (the entry has checked the shape)
+        const bool coded = (flags & AVS_VECTOR_PROBE_CODED) != 0;
+        AVS_REQUIRE(fused_device_fits(), AVS_EINVAL, "the fused launch needs a CU per workgroup");
+        AVS_TRY(fused_raise_lds());
+        DevBuf<unsigned long long> bar; // [0] the barrier's counter, [1] the largest code
+        AVS_TRY(bar.alloc(2));
+        AVS_HIP(hipMemsetAsync(bar.p, 0, 2 * sizeof(unsigned long long), stream));
+        int tab_n = 1;
+        if (coded) { // the table has as many entries as the codes reach
+            hipLaunchKernelGGL(k_probe_max_code, dim3(kVecGrid), dim3(kBlock), 0, stream, n, dcode, bar.p + 1);
+            unsigned long long top = 0;
+            AVS_HIP(hipMemcpyAsync(&top, bar.p + 1, sizeof(top), hipMemcpyDeviceToHost, stream));
+            AVS_HIP(hipStreamSynchronize(stream));
+            AVS_REQUIRE(top <= (unsigned long long)kViLdsTable, AVS_EINVAL, "the fused launch keeps at most 2049 dictionary entries");
+            tab_n = (int)top + 1;
+        }
+        const long long timeout = (long long)cur_opt().fused_timeout_ms * 100000ll;
+        with_flags([&](auto C, auto K) {
+            hipLaunchKernelGGL((k_update_fused<C.value, K.value>), dim3(kVecGrid / 8), dim3(kFusedBlock), kFusedLds + (C.value ? kFusedTabBytes : 0),
+                               stream, n, (double *)x, (double *)p, (double *)r, (const double *)t, (const double *)invd, dcode, sc, vpart, spmv_partial,
+                               nb, parity, bar.p, timeout, tab_n);
+        }, coded, (flags & AVS_VECTOR_PROBE_KEEP) != 0);
+        AVS_HIP(hipGetLastError());
+        AVS_HIP(hipStreamSynchronize(stream)); // (the counter goes with this call)
+        return AVS_OK;
+    }
     with_flags([&](auto C, auto F, auto K) {
         if (!f32) vector_probe_f64<C.value, F.value, K.value>(g, n, nb, parity, (double *)x, (double *)p, (double *)r, (const double *)t,
                                                                 (const double *)invd, dcode, spmv_partial, vpart, sc, stream);
@@ -2465,6 +2617,12 @@ extern "C" avs_status avs_vector_update_probe(int32_t flags, int32_t g, int64_t 
     AVS_REQUIRE((parity == 0 || parity == 1) && (dcode || !(flags & AVS_VECTOR_PROBE_CODED)) && (spmv_partial || !(flags & AVS_VECTOR_PROBE_FUSED)),
                 AVS_EINVAL, "bad argument");
     AVS_REQUIRE((size_t)scalars_bytes == avs::vector_update_probe_scalars_size(), AVS_EINVAL, "the scalars image has another size");
+    if (flags & AVS_VECTOR_PROBE_ONE_LAUNCH) { // refused on the host, before any launch: what the loop's dispatch never hands the fused kernel
+        AVS_REQUIRE((flags & AVS_VECTOR_PROBE_FUSED) && !(flags & (AVS_VECTOR_PROBE_F32 | AVS_VECTOR_PROBE_DS)), AVS_EINVAL,
+                    "one launch: fp64 and the fused scalar steps only");
+        AVS_REQUIRE(g == 2048 && n >= 2 && n <= (int64_t)8388608 && nb >= 1 && nb <= 4096, AVS_EINVAL,
+                    "one launch: 2048 emulated workgroups, at most 8,388,608 rows, 1 .. 4096 partial sums");
+    }
     return avs::vector_update_probe(flags, g, n, nb, parity, x, p, r, t, invd, dcode, spmv_partial, vpart, scalars,
                                     reinterpret_cast<hipStream_t>(stream));
 }

@@ -216,7 +216,8 @@ typedef enum {
     AVS_OPTION_FUSED_VECTOR_UPDATE = 9, /* single-GPU launch-per-phase loop: r -= alpha t and x += alpha p ; p = z + beta p as ONE launch with a grid barrier
                                    * in between -- the new r stays in registers / LDS, 7.25 n instead of 8.5 n doubles per iteration; same sums in the
                                    * same order: iteration counts and solution bits do not depend on it.  0 never, 1 wherever a system qualifies
-                                   * (>= 524,288 and <= 8,388,608 rows, a device with >= 256 CUs), -1 only systems larger than the Infinity Cache.
+                                   * (>= 524,288 and <= 8,388,608 rows, a device with >= 256 CUs), -1 (the default) only systems larger than the
+                                   * Infinity Cache whose SpMV leaves at most 4096 partial sums (the launch then takes the alpha step as well).
                                    * A barrier that is not passed within AVS_PCG_FUSED_TIMEOUT_MS (2000; the GPU shared with other work) redoes
                                    * the solve with the two launches.  Environment: AVS_PCG_FUSE_VECTORS. */
     AVS_OPTION_DIST_F32_VECTORS = 10, /* AVS_PRECISION_F32 contexts, partitioned solves (avs_dist_solve): 1 = the single-reduction loops of both
@@ -303,7 +304,7 @@ typedef struct avs_matrix_format {
     int32_t brick_walk;         /* tile walk of the persistent workgroups: 0 one contiguous eighth of the tiles per XCD, 1 chunks dealt to the XCDs in turn */
     int32_t brick_value_codes;  /* 1 = variable-viscosity variant: the patterns carry the geometry only, every pattern row streams its own 2-B value codes
                                  * into a per-tile value table (round 5) */
-    int32_t fused_vector_update; /* 1 = the last avs_solve ran the two vector kernels of an iteration as one launch (AVS_OPTION_FUSED_VECTOR_UPDATE, round 6) */
+    int32_t fused_vector_update; /* 1 = the last avs_solve enqueued the two vector kernels of an iteration as one launch (AVS_OPTION_FUSED_VECTOR_UPDATE) */
     int32_t fused_vector_faults; /* launches of it on this context whose grid barrier timed out (the solve was redone with the two launches) */
     int32_t float_vectors;      /* 1 = the last avs_solve or avs_dist_solve on this context iterated on float vectors (AVS_OPTION_F32_VECTORS,
                                  * AVS_OPTION_DIST_F32_VECTORS, AVS_OPTION_MIXED_PRECISION, AVS_OPTION_DIST_MIXED_PRECISION) */

@@ -138,12 +138,16 @@ avs_status avs_brick_spmv_probe(const avs_brick_arrays *a, const double *x, doub
  * (spmv_partial: nb partial sums of p.Ap); without it the scalars image holds what OP_ALPHA / OP_BETA leave (the float loops have a fused
  * update_xp only).  x, p, r, t and invd are arrays of the vector type (16-B aligned), vpart receives 2 g partial sums, `scalars` is a
  * device image of the library's PcgScalars (scalars_bytes must be its size: seven doubles rho, pAp, rr, alpha, beta, threshold, rhs_norm2,
- * four doubles of staging, the ints iter, done, fault, cancelled, the double rho_alt) and is updated in place. */
+ * four doubles of staging, the ints iter, done, fault, cancelled, the double rho_alt) and is updated in place.
+ * AVS_VECTOR_PROBE_ONE_LAUNCH (with AVS_VECTOR_PROBE_FUSED, fp64 only): k_update_fused, the single launch with a grid barrier that
+ * AVS_OPTION_FUSED_VECTOR_UPDATE puts in place of the pair, on the same arguments -- g must be 2048 and n at most 8,388,608 rows (else
+ * AVS_EINVAL before anything is launched), nb 1 .. 4096, the device must have 256 CUs; the call returns when the launch has ended. */
 #define AVS_VECTOR_PROBE_F32 1
 #define AVS_VECTOR_PROBE_DS 2
 #define AVS_VECTOR_PROBE_CODED 4
 #define AVS_VECTOR_PROBE_KEEP 8
 #define AVS_VECTOR_PROBE_FUSED 16
+#define AVS_VECTOR_PROBE_ONE_LAUNCH 32
 avs_status avs_vector_update_probe(int32_t flags, int32_t g, int64_t n, int32_t nb, int32_t parity, void *x, void *p, void *r, const void *t,
                                    const void *invd, const uint16_t *dcode, const double *spmv_partial, double *vpart, void *scalars,
                                    int32_t scalars_bytes, void *stream);
