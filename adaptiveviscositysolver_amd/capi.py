@@ -42,6 +42,10 @@ INDEX_VELOCITY, INDEX_EDGE, INDEX_CENTER = 0, 1, 2
 CHECK_LABELS, CHECK_VELOCITY_INDICES = 1, 2   # bits of `what` of avs_check_octree
 (RULE_LABEL_VALUE, RULE_COLUMN, RULE_UP, RULE_ACTIVE, RULE_INDEX_VALUE, RULE_FACE, RULE_SENTINEL, RULE_NUMBERING) = range(8)
 OCTREE_RULES = 8
+CHECK_EDGE_INDICES, CHECK_CENTER_INDICES = 1, 2   # bits of `what` of avs_check_stress_indices
+(STRESS_RULE_EDGE_VALUE, STRESS_RULE_EDGE_CELLS, STRESS_RULE_EDGE_FACES, STRESS_RULE_EDGE_NUMBERING, STRESS_RULE_CENTER_VALUE,
+ STRESS_RULE_CENTER_LABEL, STRESS_RULE_CENTER_FACES, STRESS_RULE_CENTER_EDGES, STRESS_RULE_CENTER_NUMBERING) = range(9)
+STRESS_RULES = 9
 CSR_CHECK_VALUES, CSR_CHECK_ORDER, CSR_CHECK_DIAGONAL, CSR_CHECK_SYMMETRY, CSR_CHECK_ALL = 1, 2, 4, 8, 15   # bits of `what` of avs_check_csr
 (CSR_RULE_ROW_PTR, CSR_RULE_COLUMN, CSR_RULE_VALUE, CSR_RULE_VECTOR, CSR_RULE_ORDER, CSR_RULE_DIAGONAL, CSR_RULE_PATTERN,
  CSR_RULE_SYMMETRY) = range(8)
@@ -66,7 +70,7 @@ EXPORTED_SYMBOLS = [
     "avs_dist_get_info", "avs_dist_init_hosted", "avs_dist_export_blob", "avs_dist_import_blobs",
     "avs_prepass_set_slab", "avs_prepass_get_window", "avs_dist_bind_prepass", "avs_dist_get_cuts", "avs_set_solution",
     "avs_sample_velocity", "avs_get_octree_cells", "avs_prepass_get_octree_cells", "avs_check_octree", "avs_prepass_check_octree",
-    "avs_check_csr", "avs_check_system",
+    "avs_check_csr", "avs_check_system", "avs_check_stress_indices", "avs_prepass_check_stress_indices",
 ]
 # avs_allreduce_i32_fn: avs_status (*)(int32_t *device_data, int64_t count, void *stream, void *user)
 ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -158,6 +162,17 @@ class OctreeCheck(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(OctreeCheck)
+
+
+class StressCheck(C.Structure):
+    """avs_stress_check: the report of avs_check_stress_indices / avs_prepass_check_stress_indices"""
+    _fields_ = [("struct_size", C.c_int32), ("passed", C.c_int32), ("violations", C.c_int64 * STRESS_RULES), ("first_rule", C.c_int32),
+                ("first_level", C.c_int32), ("first_axis", C.c_int32), ("first_ijk", C.c_int32 * 3), ("active_edges", C.c_int64),
+                ("active_centers", C.c_int64)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(StressCheck)
 
 
 class CsrCheck(C.Structure):
@@ -351,6 +366,8 @@ def load(probe=False):
     L.avs_prepass_get_octree_cells.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i32]
     L.avs_check_octree.argtypes = [vp, C.c_uint32, C.POINTER(OctreeCheck)]
     L.avs_prepass_check_octree.argtypes = [vp, C.c_uint32, C.POINTER(OctreeCheck)]
+    L.avs_check_stress_indices.argtypes = [vp, C.c_uint32, C.POINTER(StressCheck)]
+    L.avs_prepass_check_stress_indices.argtypes = [vp, C.c_uint32, C.POINTER(StressCheck)]
     L.avs_check_csr.argtypes = [i64, i64, vp, vp, vp, vp, vp, C.c_uint32, f64, i32, i32, vp, C.POINTER(CsrCheck)]
     L.avs_check_system.argtypes = [vp, C.c_uint32, f64, C.POINTER(CsrCheck)]
     L.avs_get_dof_table.argtypes = [vp, i32, vp, i32]

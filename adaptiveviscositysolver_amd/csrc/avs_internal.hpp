@@ -19,6 +19,7 @@
 #include "avs_probe.h"
 #include "avs_check_report.hpp"
 #include "avs_csr_check_report.hpp"
+#include "avs_stress_check_report.hpp"
 
 struct avs_ctx;
 namespace avs {
@@ -111,7 +112,7 @@ struct Options {
     int fused_timeout_ms = 2000; // AVS_PCG_FUSED_TIMEOUT_MS: bound of that barrier's wait
     int post_dof_sample = -1;    // AVS_POST_DOF_SAMPLE: the transfer samples its nodes from the velocity DOFs (1) / by a sweep over the node lattices (0);
                                  // -1: from the DOFs when the level-0 node lattice has more than 32 x as many nodes as there are DOFs
-    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) and of the octree check (avs_check.hip) at that many workgroups (tests: the walks wrap on small lattices)
+    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) and of the octree and stress index checks (avs_check.hip, avs_stress_check.hip) at that many workgroups (tests: the walks wrap on small lattices)
     int prepass_temporal = 1;    // AVS_PREPASS_TEMPORAL: the device pre-pass skips what its allocations already hold from their last filling (0: every run fills everything)
     int f32_vectors = -1;        // AVS_F32_VECTORS: AVS_PRECISION_F32 contexts iterate on float vectors with float scalars (what Eigen's float CG does):
                                  // 1 always, 0 never (fp64 iteration on the float system), -1 auto: where the system is too large for the
@@ -633,6 +634,23 @@ struct CheckSource {
 };
 avs_status check_octree(CheckScratch &S, const CheckSource &src, hipStream_t st, uint32_t what, avs_octree_check *report);
 
+// Stress index check (avs_stress_check.hip): avs_check_stress_indices / avs_prepass_check_stress_indices over one implementation.  Scratch:
+// one occurrence counter per edge id and per centre id and the raw report (a count per rule, the key of the first violation, the two
+// active counts).
+struct StressCheckScratch {
+    DevBuf<int32_t> occ_edge, occ_center;
+    DevBuf<unsigned long long> raw;
+};
+struct StressCheckSource {
+    const int8_t *labels[AVS_MAX_LEVELS];
+    const int32_t *vidx[AVS_MAX_LEVELS][3], *eidx[AVS_MAX_LEVELS][3];
+    const int32_t *cidx[AVS_MAX_LEVELS];    // read with AVS_CHECK_CENTER_INDICES only
+    int levels, n[3];  // levels present, level-0 cells per axis
+    int64_t n_edge, n_center;
+    int grid_cap;      // Options::cells_grid_cap as of the object's creation
+};
+avs_status check_stress_indices(StressCheckScratch &S, const StressCheckSource &src, hipStream_t st, uint32_t what, avs_stress_check *report);
+
 // CSR check (avs_csr_check.hip): avs_check_csr / avs_check_system over one implementation.  Scratch: the raw report and one byte per row
 // (1: the row's columns are strictly ascending, so the partner search of the symmetry pass may bisect it).
 struct CsrCheckScratch {
@@ -878,6 +896,7 @@ struct avs_ctx {
     avs::CellsScratch cells; // avs_get_octree_cells (avs_cells.hip)
     avs::CheckScratch check; // avs_check_octree (avs_check.hip)
     avs::CsrCheckScratch csr_check; // avs_check_system (avs_csr_check.hip)
+    avs::StressCheckScratch stress_check; // avs_check_stress_indices (avs_stress_check.hip)
 
     // brick-major copy of the system used by the solve (avs_reorder.hip); perm: new -> old
     avs::DevBuf<int32_t> perm, inv, p_row_ptr, p_col;

@@ -1080,6 +1080,7 @@ struct avs_prepass {
     int64_t counts[4] = {0, 0, 0, 0}; // velocity, edge, centre, regular
     avs::CellsScratch cells; // avs_prepass_get_octree_cells (avs_cells.hip)
     avs::CheckScratch check; // avs_prepass_check_octree (avs_check.hip)
+    avs::StressCheckScratch stress_check; // avs_prepass_check_stress_indices (avs_stress_check.hip)
     double ms[4] = {0, 0, 0, 0};
     bool ready = false;
 };
@@ -1965,6 +1966,39 @@ avs_status avs_prepass_check_octree(avs_prepass *p, uint32_t what, avs_octree_ch
     AVS_HIP(hipSetDevice(p->desc.device));
     Scope scope("Octree Unit Test"); // cpp:881, cpp:411
     return avs::check_octree(p->check, src, p->stream, what, report);
+}
+
+// the invariants of the edge and centre stress index pyramids (cpp:3001-3298): rules in include/avs.h, kernels in avs_stress_check.hip
+avs_status avs_prepass_check_stress_indices(avs_prepass *p, uint32_t what, avs_stress_check *report)
+{
+    (void)hipGetLastError(); // (a stale error of the host application's own HIP calls on this thread is not ours: see OptScope)
+    AVS_REQUIRE(p, AVS_EINVAL, "null argument");
+    const char *why = nullptr;
+    if (avs::check_stress_args(what, report, &why) != AVS_OK) {
+        set_error("%s", why);
+        return AVS_EINVAL;
+    }
+    AVS_REQUIRE(!p->slab.on, AVS_ESTATE, "avs_prepass_check_stress_indices: the pre-pass is slab-local (lattices inside this rank's window only)");
+    AVS_REQUIRE(p->ready, AVS_ESTATE, "call avs_prepass_run first");
+    avs::StressCheckSource src{};
+    for (int l = 0; l < p->levels; ++l) {
+        src.labels[l] = p->labels[l].p;
+        src.cidx[l] = p->cidx[l].p;
+        for (int a = 0; a < 3; ++a) {
+            src.vidx[l][a] = p->vidx[l][a].p;
+            src.eidx[l][a] = p->eidx[l][a].p;
+        }
+    }
+    src.levels = p->levels;
+    src.n[0] = p->desc.nx;
+    src.n[1] = p->desc.ny;
+    src.n[2] = p->desc.nz;
+    src.n_edge = p->counts[1];
+    src.n_center = p->counts[2];
+    src.grid_cap = p->cells_grid_cap;
+    AVS_HIP(hipSetDevice(p->desc.device));
+    Scope scope("Stress Unit Tests"); // cpp:412-413
+    return avs::check_stress_indices(p->stress_check, src, p->stream, what, report);
 }
 
 avs_status avs_prepass_apply(avs_prepass *p, avs_ctx *ctx)

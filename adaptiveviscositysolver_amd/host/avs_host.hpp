@@ -97,6 +97,15 @@ public:
         check(avs_check_system(myCtx, what, symmetryTolerance, &report), "avs_check_system");
         return report;
     }
+    // are the edge and centre stress index pyramids ones the hot path is defined for? (avs_check_stress_indices: where the reference
+    // asserts edgeStressUnitTest and centerStresUnitTest, cpp:412-413; report.passed, a count per rule and the first violating entry)
+    avs_stress_check checkStressIndices(uint32_t what = AVS_CHECK_EDGE_INDICES | AVS_CHECK_CENTER_INDICES)
+    {
+        avs_stress_check report{};
+        report.struct_size = (int32_t)sizeof(report);
+        check(avs_check_stress_indices(myCtx, what, &report), "avs_check_stress_indices");
+        return report;
+    }
     SolveResult solveConjugateGradient(double solverTolerance = 1e-3, int maxSolverIterations = 2500)
     {
         avs_solve_info s{};

@@ -437,6 +437,13 @@ class ViscositySolve:
         the velocity index pyramid and the dof counts too), or both.  Returns an OctreeCheck."""
         return _check_octree(self.lib.avs_check_octree, self.h, what)
 
+    def check_stress_indices(self, what=capi.CHECK_EDGE_INDICES | capi.CHECK_CENTER_INDICES):
+        """Are the edge and centre stress index pyramids the context holds ones the hot path is defined for?  (avs_check_stress_indices:
+        the reference's debug invariants, cpp:3001-3298, on the device.)  what: capi.CHECK_EDGE_INDICES (needs labels, the velocity and
+        edge index pyramids and the dof counts), capi.CHECK_CENTER_INDICES (the centre index pyramid too), or both.  Returns a
+        StressCheck."""
+        return _check_stress_indices(self.lib.avs_check_stress_indices, self.h, what)
+
     def check_system(self, what=capi.CSR_CHECK_ALL, symmetry_tolerance=0.0):
         """Is the assembled system one the solve is defined for?  (avs_check_system: the rules of avs_check_csr on the context's
         reference-numbered matrix, its right-hand side and the initial guess, in place.)  Needs assemble(); changes nothing a later
@@ -474,6 +481,29 @@ def _check_octree(fn, handle, what):
     capi.check(fn(handle, int(what), C.byref(rep)))
     first = None if rep.passed else (rep.first_rule, rep.first_level, rep.first_axis, *rep.first_ijk)
     return OctreeCheck(bool(rep.passed), tuple(int(v) for v in rep.violations), first)
+
+
+@dataclass(frozen=True)
+class StressCheck:
+    """report of check_stress_indices: passed; violations[rule] = lattice entries (rules 3 and 8: ids) that break rule `rule`
+    (capi.STRESS_RULE_*); first = (rule, level, axis, i, j, k) of the violating entry that comes first in that order, None when passed;
+    active_edges / active_centers = entries that carry an id (0 for a kind that was not asked for)"""
+    passed: bool
+    violations: tuple
+    first: tuple | None
+    active_edges: int
+    active_centers: int
+
+    def __bool__(self):
+        return self.passed
+
+
+def _check_stress_indices(fn, handle, what):
+    """shared by ViscositySolve.check_stress_indices and DevicePrepass.check_stress_indices"""
+    rep = capi.StressCheck()
+    capi.check(fn(handle, int(what), C.byref(rep)))
+    first = None if rep.passed else (rep.first_rule, rep.first_level, rep.first_axis, *rep.first_ijk)
+    return StressCheck(bool(rep.passed), tuple(int(v) for v in rep.violations), first, int(rep.active_edges), int(rep.active_centers))
 
 
 def _octree_cells(fn, handle, origin, device_arrays, device):
@@ -647,6 +677,11 @@ class DevicePrepass:
         """The invariants of the last run's label and velocity index pyramids (avs_prepass_check_octree): what
         ViscositySolve.check_octree returns, without a solve context."""
         return _check_octree(self.lib.avs_prepass_check_octree, self.h, what)
+
+    def check_stress_indices(self, what=capi.CHECK_EDGE_INDICES | capi.CHECK_CENTER_INDICES):
+        """The invariants of the last run's edge and centre stress index pyramids (avs_prepass_check_stress_indices): what
+        ViscositySolve.check_stress_indices returns, without a solve context."""
+        return _check_stress_indices(self.lib.avs_prepass_check_stress_indices, self.h, what)
 
     def _shape(self, kind, level, axis):
         r = [self.res[0] >> level, self.res[1] >> level, self.res[2] >> level]

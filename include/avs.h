@@ -137,7 +137,8 @@ const char *avs_version(void);
  * Purely additive since (no revision): the entry avs_sample_velocity.
  * Purely additive since (no revision): the entries avs_get_octree_cells and avs_prepass_get_octree_cells.
  * Purely additive since (no revision): the entries avs_check_octree and avs_prepass_check_octree.
- * Purely additive since (no revision): the entries avs_check_csr and avs_check_system. */
+ * Purely additive since (no revision): the entries avs_check_csr and avs_check_system.
+ * Purely additive since (no revision): the entries avs_check_stress_indices and avs_prepass_check_stress_indices. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -440,6 +441,74 @@ typedef struct avs_octree_check {
 } avs_octree_check;
 avs_status avs_check_octree(avs_ctx *ctx, uint32_t what, avs_octree_check *report);
 
+/* The same question for the two stress index pyramids (AVS_INDEX_EDGE, AVS_INDEX_CENTER), which decide which stencils avs_assemble builds
+ * and where their records are stored.  The reference's debug invariants -- edgeStressUnitTest and centerStresUnitTest (cpp:3001-3298,
+ * called at cpp:412-413) -- evaluated on the device over the lattices as they lie there (set by avs_set_index_field or lent by
+ * avs_prepass_apply: checked in place).  avs_prepass_check_stress_indices (below, with the pre-pass) is the same call on a pre-pass object.
+ * Nothing else in the library calls it, and it changes nothing: every other entry behaves as without it.
+ * L = levels, cell lattices are n >> l; the edge lattice of axis a has one more entry on the two other axes b = (a+1)%3 and c = (a+2)%3, the
+ * face lattice of axis f one more on f.  A cell outside its lattice reads as INACTIVE, an index outside its lattice as AVS_UNASSIGNED.
+ * Values of the label and velocity pyramids are only compared with sentinels (check those with avs_check_octree).  violations[r] = lattice
+ * entries that break rule r at least once (64-bit); every rule is evaluated independently of the others:
+ *   0 EDGE_VALUE        every edge index is AVS_UNASSIGNED, AVS_OUTSIDE or in [0, n_edge).  AVS_SOLIDBOUNDARY violates: classification
+ *                       never writes it to a stress lattice.
+ *   1 EDGE_CELLS        (cpp:3037-3052) an edge e of axis a at level l with id >= 0 and the four cells around it, walked as the reference
+ *                       walks them: e - 1_b - 1_c, e - 1_c, e - 1_b, e, up to the first one outside the lattice.  Every cell reached is
+ *                       ACTIVE or UP.  (The reference's comment asks for all four.  Its loop, like the classification that writes the
+ *                       lattice, cpp:1361-1370, leaves at the first cell outside: on the upper border plane of b an edge is decided by
+ *                       its first cell alone, and liquid that reaches that border at a coarse level yields an edge with an id next
+ *                       to a DOWN cell the walk never sees.  The pre-pass yields such pyramids, so the rule asserts what the reference asserts.)
+ *   2 EDGE_FACES        (cpp:3054-3121) the same edges; for f in {b, c}, o the third axis, the two faces of axis f at e and e - 1_o; a face
+ *                       whose o coordinate is < 0 or >= (n_o >> l) is skipped.  The velocity index v of a face: v >= 0 is fine.
+ *                       AVS_SOLIDBOUNDARY or AVS_OUTSIDE: l == 0.  AVS_UNASSIGNED and e[f] odd (a T-junction inside a coarse cell): l < L-1
+ *                       and the level-(l+1) cell face >> 1 is ACTIVE.  AVS_UNASSIGNED and e[f] even: l < L-1 and the level-(l+1) velocity
+ *                       index of axis f at face >> 1 is not AVS_UNASSIGNED.  Any other negative value violates.
+ *                       Narrower than the reference on the border of the grid, where its assert rejects what its own classification
+ *                       (and the pre-pass here) writes once liquid reaches the border at a coarse level: a face on a border plane of
+ *                       its lattice (f coordinate 0 or n_f >> l; never numbered, cpp:1210-1215: AVS_OUTSIDE at level 0, untouched
+ *                       above) is skipped, and so is every face of an edge with e[b] == n_b >> l (rule 1's walk ends after its first
+ *                       cell, so the cells beside those faces were never looked at).
+ *   3 EDGE_NUMBERING    every id in [0, n_edge) occurs exactly once over all levels and axes (entries: the ids that occur 0 times or more
+ *                       than once; ids out of range are rule 0's).  The reference does not assert it.
+ *   4 CENTER_VALUE      rule 0 for the centre indices, against n_center.
+ *   5 CENTER_LABEL      (cpp:3184) a centre with id >= 0 lies on an ACTIVE cell.
+ *   6 CENTER_FACES      (cpp:3190-3231) the same centres at level l and their six faces cell + d 1_a, d in {0, 1}.  The velocity index v:
+ *                       AVS_UNASSIGNED: l > 0 and the four child faces 2 face + {0,1} 1_b + {0,1} 1_c of level l-1 are all >= 0.
+ *                       AVS_OUTSIDE or AVS_SOLIDBOUNDARY: l == 0.  Any other negative value violates.  A face on a border plane of its
+ *                       lattice (a coordinate 0 or n_a >> l) is skipped, as in rule 2: a coarse ACTIVE cell on the border of the grid
+ *                       has an UNASSIGNED face there with UNASSIGNED children, which the reference's assert rejects.
+ *   7 CENTER_EDGES      (cpp:3233-3266) the same centres and their twelve edges: axis a, cell + {0,1} 1_b + {0,1} 1_c.  Only an
+ *                       AVS_UNASSIGNED edge index is examined (AVS_OUTSIDE passes, as in the reference): l > 0, and for each of the two child
+ *                       edges 2 edge + {0,1} 1_a of level l-1 whose index is < 0: l >= 2 and both grandchildren 2 child + {0,1} 1_a of level
+ *                       l-2 are >= 0.  (Where this rule reports a violation at l == 0 or l == 1, the reference indexes level -1 or -2.)
+ *   8 CENTER_NUMBERING  rule 3 over [0, n_center).
+ * what: AVS_CHECK_EDGE_INDICES = rules 0 .. 3, AVS_CHECK_CENTER_INDICES = rules 4 .. 8, or both; any other bit: AVS_EINVAL.  what == 0:
+ *   AVS_OK, passed = 1, nothing is launched.  Rules that were not asked for report 0 violations and are not launched.
+ * first_*: the violating entry that comes first by (rule, level, axis, linear index "i + rx*(j + ry*k)" in its own lattice); -1 everywhere
+ *   when passed.  Centre rules report axis 0; rules 3 and 8 report level 0, axis 0 and first_ijk = (id, 0, 0).
+ * active_edges, active_centers: entries with a stored value >= 0, over all levels (and axes); 0 for a kind that was not asked for.
+ * struct_size: IN, as in avs_octree_check -- only that many bytes of the report are written; below offsetof(passed) + 4 or above 4096, a
+ *   NULL report: AVS_EINVAL.
+ * State: AVS_CHECK_EDGE_INDICES needs the labels of every level, the velocity and edge lattices of every level and axis and the dof counts
+ *   (avs_set_dof_counts); AVS_CHECK_CENTER_INDICES in addition the centre lattices; anything missing: AVS_ESTATE.  Slab-local contexts and
+ *   pre-passes: AVS_ESTATE.  The pre-pass entry needs a completed avs_prepass_run; a run that found no liquid (levels == 0) gives passed = 1.
+ * A pyramid that passes is one the pre-pass can have written; avs_assemble still reports on its own (AVS_EINTERNAL) the stencils the
+ *   reference cannot build, such as an UNASSIGNED face beside an edge of the top level on the border of the grid.
+ * The work is enqueued on the object's stream and the call returns once the report is on the host; scratch (one int32 per edge id and per
+ *   centre id, the raw report) stays in the object.  The same lattices give the same report on every call. */
+enum { AVS_CHECK_EDGE_INDICES = 1, AVS_CHECK_CENTER_INDICES = 2 };
+enum { AVS_STRESS_RULE_EDGE_VALUE = 0, AVS_STRESS_RULE_EDGE_CELLS = 1, AVS_STRESS_RULE_EDGE_FACES = 2, AVS_STRESS_RULE_EDGE_NUMBERING = 3,
+       AVS_STRESS_RULE_CENTER_VALUE = 4, AVS_STRESS_RULE_CENTER_LABEL = 5, AVS_STRESS_RULE_CENTER_FACES = 6, AVS_STRESS_RULE_CENTER_EDGES = 7,
+       AVS_STRESS_RULE_CENTER_NUMBERING = 8, AVS_STRESS_RULES = 9 };
+typedef struct avs_stress_check {
+    int32_t struct_size;                   /* IN: sizeof(avs_stress_check) of the caller's header */
+    int32_t passed;                        /* 1 = no rule that was asked for is violated */
+    int64_t violations[AVS_STRESS_RULES];
+    int32_t first_rule, first_level, first_axis, first_ijk[3];
+    int64_t active_edges, active_centers;
+} avs_stress_check;
+avs_status avs_check_stress_indices(avs_ctx *ctx, uint32_t what, avs_stress_check *report);
+
 /* ------------------------------------------------------------------------------------------
  * Seam A: only the solve (replaces cpp:611-643).  CSR with int32 row pointers/columns, fp64
  * values; x_inout holds the initial guess on entry and the solution on return.
@@ -577,6 +646,8 @@ avs_status avs_prepass_get_octree_cells(avs_prepass *pp, const double *origin /*
 /* the invariants of the pyramids of the last run: avs_check_octree (above) on the pre-pass object -- same rules, report and state errors;
  * enqueued on the pre-pass's stream */
 avs_status avs_prepass_check_octree(avs_prepass *pp, uint32_t what, avs_octree_check *report);
+/* the invariants of the edge and centre stress index pyramids of the last run: avs_check_stress_indices (above) on the pre-pass object */
+avs_status avs_prepass_check_stress_indices(avs_prepass *pp, uint32_t what, avs_stress_check *report);
 /* hands labels, index pyramids, DOF counts, regular-grid indices and the three weight fields to a solve context created with
  * levels == info.levels on the same device.  BY REFERENCE (round 5; it used to copy ~12 full-size lattices per level set: 78 GB at
  * 1024^3): the context holds the pre-pass's allocations; the pre-pass keeps two per lattice and its next avs_prepass_run fills the set no

@@ -325,6 +325,20 @@ bool HDK_AdaptiveViscosity::solveGasSubclass(SIM_Engine &engine, SIM_Object *obj
             h.release();
             return false;
         }
+        // ... and edgeStressUnitTest() / centerStresUnitTest() (cpp:412-413) over the two stress index pyramids
+        avs_stress_check stress_check;
+        std::memset(&stress_check, 0, sizeof(stress_check));
+        stress_check.struct_size = (int32_t)sizeof(stress_check);
+        if (!check(avs_prepass_check_stress_indices(h.pp, AVS_CHECK_EDGE_INDICES | AVS_CHECK_CENTER_INDICES, &stress_check))) return false;
+        if (!stress_check.passed) {
+            UT_WorkBuffer msg;
+            msg.sprintf("avs: the stress indices break rule %d of avs_check_stress_indices first at level %d, axis %d, entry (%d, %d, %d)",
+                        (int)stress_check.first_rule, (int)stress_check.first_level, (int)stress_check.first_axis, (int)stress_check.first_ijk[0],
+                        (int)stress_check.first_ijk[1], (int)stress_check.first_ijk[2]);
+            addError(obj, SIM_MESSAGE, msg.buffer(), UT_ERROR_WARNING);
+            h.release();
+            return false;
+        }
 #endif
     }
 
