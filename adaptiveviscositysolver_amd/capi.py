@@ -46,6 +46,8 @@ CHECK_EDGE_INDICES, CHECK_CENTER_INDICES = 1, 2   # bits of `what` of avs_check_
 (STRESS_RULE_EDGE_VALUE, STRESS_RULE_EDGE_CELLS, STRESS_RULE_EDGE_FACES, STRESS_RULE_EDGE_NUMBERING, STRESS_RULE_CENTER_VALUE,
  STRESS_RULE_CENTER_LABEL, STRESS_RULE_CENTER_FACES, STRESS_RULE_CENTER_EDGES, STRESS_RULE_CENTER_NUMBERING) = range(9)
 STRESS_RULES = 9
+RATES_OF_SOLUTION, RATES_OF_INITIAL_GUESS = 0, 1   # `which` of avs_get_strain_rates / avs_get_shear_rate_field
+EDGE_LOOKUP_OWN, EDGE_LOOKUP_CHILD, EDGE_LOOKUP_GRANDCHILD, EDGE_LOOKUP_SKIPPED = range(4)   # avs_strain_summary.edge_lookups
 CSR_CHECK_VALUES, CSR_CHECK_ORDER, CSR_CHECK_DIAGONAL, CSR_CHECK_SYMMETRY, CSR_CHECK_ALL = 1, 2, 4, 8, 15   # bits of `what` of avs_check_csr
 (CSR_RULE_ROW_PTR, CSR_RULE_COLUMN, CSR_RULE_VALUE, CSR_RULE_VECTOR, CSR_RULE_ORDER, CSR_RULE_DIAGONAL, CSR_RULE_PATTERN,
  CSR_RULE_SYMMETRY) = range(8)
@@ -71,6 +73,7 @@ EXPORTED_SYMBOLS = [
     "avs_prepass_set_slab", "avs_prepass_get_window", "avs_dist_bind_prepass", "avs_dist_get_cuts", "avs_set_solution",
     "avs_sample_velocity", "avs_get_octree_cells", "avs_prepass_get_octree_cells", "avs_check_octree", "avs_prepass_check_octree",
     "avs_check_csr", "avs_check_system", "avs_check_stress_indices", "avs_prepass_check_stress_indices",
+    "avs_get_strain_rates", "avs_get_shear_rate_field",
 ]
 # avs_allreduce_i32_fn: avs_status (*)(int32_t *device_data, int64_t count, void *stream, void *user)
 ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -173,6 +176,19 @@ class StressCheck(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(StressCheck)
+
+
+class StrainSummary(C.Structure):
+    """avs_strain_summary: the counters, dissipations and maxima of avs_get_strain_rates"""
+    _fields_ = [("struct_size", C.c_int32), ("which", C.c_int32), ("n_edge", C.c_int64), ("n_center", C.c_int64),
+                ("empty_edges", C.c_int64), ("empty_centers", C.c_int64), ("boundary_edges", C.c_int64), ("boundary_centers", C.c_int64),
+                ("nonfinite", C.c_int64), ("edge_lookups", C.c_int64 * 4), ("empty_pairs", C.c_int64),
+                ("dissipation_edge", C.c_double), ("dissipation_center", C.c_double), ("max_abs_edge_rate", C.c_double),
+                ("max_abs_center_rate", C.c_double), ("max_shear_rate", C.c_double)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(StrainSummary)
 
 
 class CsrCheck(C.Structure):
@@ -368,6 +384,8 @@ def load(probe=False):
     L.avs_prepass_check_octree.argtypes = [vp, C.c_uint32, C.POINTER(OctreeCheck)]
     L.avs_check_stress_indices.argtypes = [vp, C.c_uint32, C.POINTER(StressCheck)]
     L.avs_prepass_check_stress_indices.argtypes = [vp, C.c_uint32, C.POINTER(StressCheck)]
+    L.avs_get_strain_rates.argtypes = [vp, i32, vp, vp, vp, C.POINTER(StrainSummary), i32]
+    L.avs_get_shear_rate_field.argtypes = [vp, i32, vp, i32]
     L.avs_check_csr.argtypes = [i64, i64, vp, vp, vp, vp, vp, C.c_uint32, f64, i32, i32, vp, C.POINTER(CsrCheck)]
     L.avs_check_system.argtypes = [vp, C.c_uint32, f64, C.POINTER(CsrCheck)]
     L.avs_get_dof_table.argtypes = [vp, i32, vp, i32]

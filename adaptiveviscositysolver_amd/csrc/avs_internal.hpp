@@ -651,6 +651,15 @@ struct StressCheckSource {
 };
 avs_status check_stress_indices(StressCheckScratch &S, const StressCheckSource &src, hipStream_t st, uint32_t what, avs_stress_check *report);
 
+// Strain rates (avs_strain.hip): avs_get_strain_rates / avs_get_shear_rate_field.  Scratch kept across calls: the rates of the edge
+// stencils and of the centre lists, the cells' shear rates, one partial sum per 256 stencils (edges, then cells), the raw summary, and the
+// staging of a host-bound field.
+struct StrainScratch {
+    DevBuf<double> edge, center, cell, partial;
+    DevBuf<unsigned long long> raw;
+    DevBuf<float> field;
+};
+
 // CSR check (avs_csr_check.hip): avs_check_csr / avs_check_system over one implementation.  Scratch: the raw report and one byte per row
 // (1: the row's columns are strictly ascending, so the partner search of the symmetry pass may bisect it).
 struct CsrCheckScratch {
@@ -897,6 +906,7 @@ struct avs_ctx {
     avs::CheckScratch check; // avs_check_octree (avs_check.hip)
     avs::CsrCheckScratch csr_check; // avs_check_system (avs_csr_check.hip)
     avs::StressCheckScratch stress_check; // avs_check_stress_indices (avs_stress_check.hip)
+    avs::StrainScratch strain; // avs_get_strain_rates / avs_get_shear_rate_field (avs_strain.hip)
 
     // brick-major copy of the system used by the solve (avs_reorder.hip); perm: new -> old
     avs::DevBuf<int32_t> perm, inv, p_row_ptr, p_col;

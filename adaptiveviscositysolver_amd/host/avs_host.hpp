@@ -106,6 +106,30 @@ public:
         check(avs_check_stress_indices(myCtx, what, &report), "avs_check_stress_indices");
         return report;
     }
+    // the deformation of the solution (AVS_RATES_OF_SOLUTION) or of the restricted input velocity (AVS_RATES_OF_INITIAL_GUESS: after
+    // buildStressStencils + buildVelocityMapping, before any system exists): the rate of every edge stencil and centre list, the shear
+    // rate sqrt(2 eps:eps) of every ACTIVE cell by centre id, and the summary (avs_get_strain_rates; counters, dissipations, maxima)
+    struct StrainRates {
+        std::vector<double> edge, center, cell;
+        avs_strain_summary summary{};
+    };
+    StrainRates strainRates(int32_t which = AVS_RATES_OF_SOLUTION)
+    {
+        StrainRates r;
+        r.summary.struct_size = (int32_t)sizeof(r.summary);
+        check(avs_get_strain_rates(myCtx, which, nullptr, nullptr, nullptr, &r.summary, AVS_MEM_HOST), "avs_get_strain_rates");
+        r.edge.resize((size_t)r.summary.n_edge);
+        r.center.resize(3 * (size_t)r.summary.n_center);
+        r.cell.resize((size_t)r.summary.n_center);
+        check(avs_get_strain_rates(myCtx, which, r.edge.data(), r.center.data(), r.cell.data(), nullptr, AVS_MEM_HOST), "avs_get_strain_rates");
+        return r;
+    }
+    // the shear rate on the simulation grid (field_nx * field_ny * field_nz floats, x fastest: the lattice of AVS_FIELD_VISCOSITY), 0 where
+    // no ACTIVE cell covers a cell -- what a shear-dependent viscosity mu(gamma) is evaluated from
+    void shearRateField(float *field, int32_t which = AVS_RATES_OF_SOLUTION)
+    {
+        check(avs_get_shear_rate_field(myCtx, which, field, AVS_MEM_HOST), "avs_get_shear_rate_field");
+    }
     SolveResult solveConjugateGradient(double solverTolerance = 1e-3, int maxSolverIterations = 2500)
     {
         avs_solve_info s{};

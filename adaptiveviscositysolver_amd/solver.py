@@ -453,6 +453,45 @@ class ViscositySolve:
         capi.check(self.lib.avs_check_system(self.h, int(what), float(symmetry_tolerance), C.byref(rep)))
         return _csr_check(rep)
 
+    def strain_rates(self, which=capi.RATES_OF_SOLUTION, device_arrays=False):
+        """The deformation of a velocity (avs_get_strain_rates): the rate of every edge stencil (eps_bc at an edge of axis a) and of every
+        centre list (du_a/dx_a; list id = cell id + n_center * axis), the shear rate sqrt(2 eps:eps) of every ACTIVE cell (by centre id)
+        and the summary (counters, dissipations, maxima).  which: capi.RATES_OF_SOLUTION (needs solve / set_solution) or
+        capi.RATES_OF_INITIAL_GUESS (needs build_stencils + build_initial_guess only).  Returns a StrainRates of NumPy arrays, or with
+        device_arrays=True of torch tensors on the context's device, written there by the kernels."""
+        i = self.info()
+        ne, nc = int(i.n_edge), int(i.n_center)
+        summary = capi.StrainSummary()
+        if not device_arrays:
+            out = (np.empty(ne, np.float64), np.empty(3 * nc, np.float64), np.empty(nc, np.float64))
+            capi.check(self.lib.avs_get_strain_rates(self.h, int(which), *[a.ctypes.data for a in out], C.byref(summary), capi.MEM_HOST))
+            return StrainRates(*out, _strain_summary(summary))
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = tuple(torch.empty(n, dtype=torch.float64, device=dev) for n in (ne, 3 * nc, nc))
+        torch.cuda.current_stream(dev).synchronize()   # (the stream rules of octree_cells)
+        capi.check(self.lib.avs_get_strain_rates(self.h, int(which), *[a.data_ptr() for a in out], C.byref(summary), capi.MEM_DEVICE))
+        torch.cuda.synchronize(dev)
+        return StrainRates(*out, _strain_summary(summary))
+
+    def shear_rate_field(self, which=capi.RATES_OF_SOLUTION, device_array=False):
+        """The shear rate sqrt(2 eps:eps) on the simulation grid (avs_get_shear_rate_field), the lattice FIELD_VISCOSITY is given on:
+        float32 (nz, ny, nx), 0 where no ACTIVE cell covers a cell.  A NumPy array, or with device_array=True a torch tensor on the
+        context's device.  With which=capi.RATES_OF_INITIAL_GUESS it is what a shear-dependent viscosity is evaluated from before the
+        solve: build_stencils, build_initial_guess, shear_rate_field, set_field(FIELD_VISCOSITY, data=mu(gamma)), assemble, solve."""
+        nx, ny, nz = self.field_res
+        if not device_array:
+            out = np.empty((nz, ny, nx), np.float32)
+            capi.check(self.lib.avs_get_shear_rate_field(self.h, int(which), out.ctypes.data, capi.MEM_HOST))
+            return out
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        capi.check(self.lib.avs_get_shear_rate_field(self.h, int(which), out.data_ptr(), capi.MEM_DEVICE))
+        torch.cuda.synchronize(dev)
+        return out
+
     def edge_stencils(self):
         ne = self.info().n_edge
         return self._stencils(self.lib.avs_get_edge_stencils, ne, ne, capi.EDGE_STENCIL_CAP, capi.EDGE_BOUNDARY_CAP)
@@ -504,6 +543,44 @@ def _check_stress_indices(fn, handle, what):
     capi.check(fn(handle, int(what), C.byref(rep)))
     first = None if rep.passed else (rep.first_rule, rep.first_level, rep.first_axis, *rep.first_ijk)
     return StressCheck(bool(rep.passed), tuple(int(v) for v in rep.violations), first, int(rep.active_edges), int(rep.active_centers))
+
+
+@dataclass(frozen=True)
+class StrainSummary:
+    """avs_strain_summary: n_edge / n_center stencils evaluated; empty_* (cnt == 0) and boundary_* (bcnt > 0) stencils; nonfinite rates;
+    edge_lookups[capi.EDGE_LOOKUP_*] = how the cell pass resolved its 12 n_center edge slots; empty_pairs = (cell, edge axis) without an
+    edge; dissipation_edge = sum w_e eps_e^2, dissipation_center = sum w_c (exx^2 + eyy^2 + ezz^2); maxima over finite values"""
+    which: int
+    n_edge: int
+    n_center: int
+    empty_edges: int
+    empty_centers: int
+    boundary_edges: int
+    boundary_centers: int
+    nonfinite: int
+    edge_lookups: tuple
+    empty_pairs: int
+    dissipation_edge: float
+    dissipation_center: float
+    max_abs_edge_rate: float
+    max_abs_center_rate: float
+    max_shear_rate: float
+
+
+@dataclass(frozen=True)
+class StrainRates:
+    """result of ViscositySolve.strain_rates: edge (n_edge,), center (3 n_center,), cell (n_center,) float64 and the StrainSummary"""
+    edge: object
+    center: object
+    cell: object
+    summary: StrainSummary
+
+
+def _strain_summary(s):
+    return StrainSummary(int(s.which), int(s.n_edge), int(s.n_center), int(s.empty_edges), int(s.empty_centers), int(s.boundary_edges),
+                         int(s.boundary_centers), int(s.nonfinite), tuple(int(v) for v in s.edge_lookups), int(s.empty_pairs),
+                         float(s.dissipation_edge), float(s.dissipation_center), float(s.max_abs_edge_rate), float(s.max_abs_center_rate),
+                         float(s.max_shear_rate))
 
 
 def _octree_cells(fn, handle, origin, device_arrays, device):

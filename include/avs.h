@@ -138,7 +138,8 @@ const char *avs_version(void);
  * Purely additive since (no revision): the entries avs_get_octree_cells and avs_prepass_get_octree_cells.
  * Purely additive since (no revision): the entries avs_check_octree and avs_prepass_check_octree.
  * Purely additive since (no revision): the entries avs_check_csr and avs_check_system.
- * Purely additive since (no revision): the entries avs_check_stress_indices and avs_prepass_check_stress_indices. */
+ * Purely additive since (no revision): the entries avs_check_stress_indices and avs_prepass_check_stress_indices.
+ * Purely additive since (no revision): the entries avs_get_strain_rates and avs_get_shear_rate_field. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -508,6 +509,77 @@ typedef struct avs_stress_check {
     int64_t active_edges, active_centers;
 } avs_stress_check;
 avs_status avs_check_stress_indices(avs_ctx *ctx, uint32_t what, avs_stress_check *report);
+
+/* The deformation of a velocity: the rate of every stress stencil, a shear rate per ACTIVE cell, the dissipation of the step, and the shear
+ * rate gamma = sqrt(2 eps:eps) as a field on the simulation grid -- what a host needs to evaluate a shear-dependent viscosity mu(gamma)
+ * (Carreau, Bingham, a shear-thinning melt).  Every edge stencil of avs_build_stencils is a row of the deformation-rate operator (eps_bc
+ * at an edge of axis a, b = (a+1)%3, c = (a+2)%3), every centre stencil list du_a/dx_a at a cell (cpp:443-498).  Nothing else in the
+ * library calls these entries, and they write nothing a later assemble, solve or transfer reads.
+ * which: the velocity vector u the stencils are applied to (n_velocity entries, reference numbering).  AVS_RATES_OF_SOLUTION: the solution
+ *   (avs_solve, avs_set_solution, or avs_dist_get_solution on a context that is not slab-local).  AVS_RATES_OF_INITIAL_GUESS: the
+ *   restricted input velocity of avs_build_initial_guess / avs_assemble (not the partial one of avs_dist_assemble) -- what a viscosity model
+ *   uses BEFORE the solve: provisional fields, avs_build_stencils, avs_build_initial_guess, avs_get_shear_rate_field, mu(gamma),
+ *   avs_set_scalar_field(AVS_FIELD_VISCOSITY), avs_assemble, avs_solve.  No system has to be assembled for either.
+ * Rate of a stencil s (of `count` stencils, SoA as in avs_get_edge_stencils): fp64, one rounding per operation.  acc = 0; for k = 0 ..
+ *   cnt[s]-1 in stored order acc = acc + coef[k*count + s] * u[idx[k*count + s]]; then for k = 0 .. bcnt[s]-1 acc = acc + bval[k*count + s].
+ *   Slots at or behind cnt / bcnt are never read.  cnt == 0 gives the sum of the boundary terms.  AVS_PRECISION_F32 contexts are
+ *   evaluated the same way on the values they store.  edge_rate[e]: edge stress e; center_rate[cid + n_center*a] = eps_aa of centre cid.
+ * Shear rate of the cell with centre id cid, at level l, cell C (mirrors rule 7 CENTER_EDGES of avs_check_stress_indices, the reference's
+ *   statement of which edges an ACTIVE cell owns, cpp:3233-3266).  For edge axis a the four slots e = C + {0,1} 1_b + {0,1} 1_c of the
+ *   level-l edge lattice of axis a, the b offset fastest.  A slot is resolved by its edge index v:
+ *     v >= 0                         the rate of edge v (counted in edge_lookups[AVS_EDGE_LOOKUP_OWN]);
+ *     v == AVS_UNASSIGNED and l > 0  the two children 2 e + {0,1} 1_a of level l-1, in that order.  A child with id >= 0 contributes its
+ *                                    rate (..._CHILD, per child).  A child with a negative index contributes, if l >= 2, the mean of its
+ *                                    grandchildren 2 child + {0,1} 1_a of level l-2 that have an id >= 0 (..._GRANDCHILD, per grandchild
+ *                                    used; none: the child contributes nothing).  The slot's value is the sum of the contributing
+ *                                    children in order divided by their number; no contributing child: the slot is skipped;
+ *     anything else                  skipped (..._SKIPPED, per slot): AVS_OUTSIDE, AVS_UNASSIGNED at level 0, a slot without a descendant
+ *                                    -- a free surface has no stress sample there.  An index outside its lattice reads as AVS_UNASSIGNED,
+ *                                    an id >= n_edge as no id.
+ *   m_a = the sum of the contributing slots in slot order divided by their number; no contributing slot: m_a = 0 and the pair (cell, a)
+ *   is counted in empty_pairs.  A mean is (x) / 1, (x + y) / 2, ((x + y) + z) / 3, (((x + y) + z) + w) / 4.
+ *   gamma = sqrt(2 ((exx exx + eyy eyy) + ezz ezz) + 4 ((m_0 m_0 + m_1 m_1) + m_2 m_2)), eaa = center_rate[cid + n_center*a].
+ * Shear-rate field: one value per cell of the simulation grid (field_n*, the lattice AVS_FIELD_VISCOSITY is given on), x fastest.  From
+ *   the level-0 cell the label pyramid is climbed, as avs_sample_velocity does, to the lowest level whose cell over it is ACTIVE; that cell's
+ *   centre id cid gives (float)gamma[cid], the fp64 value rounded once.  No ACTIVE cell over it, or a centre index that is no id: 0.
+ *   Every entry of `field` is written.
+ * Summary (may be NULL; struct_size: IN, the protocol of avs_stress_check -- only that many bytes are written; below offsetof(which) + 4
+ *   or above 4096: AVS_EINVAL).  A summary always evaluates all three passes.  empty_*: stencils with cnt == 0 (centres: lists, three per
+ *   centre); boundary_*: stencils with bcnt > 0; nonfinite: edge and centre rates that are NaN or Inf.
+ *   dissipation_edge = sum_e w_e eps_e^2 and dissipation_center = sum_cells w_c ((exx^2 + eyy^2) + ezz^2), with the integration weights
+ *   of the stencils (avs_get_edge_stencils / avs_get_center_stencils: w_e = 4 dt mu V_e, w_c = 2 dt mu V_c, V in fine-voxel units): their
+ *   sum is dt / dx^3 times the integral of 2 mu eps:eps over the liquid, u^T (A - M_u) u of the system the solve inverts where no stencil
+ *   carries a boundary term.  An edge whose rate is not finite and a cell with a rate that is not finite are left out of the sums; maxima
+ *   are over finite values (max_shear_rate over the cells' gamma).  The sums are deterministic: a partial sum per 256 consecutive
+ *   stencils, the partial sums folded in a fixed order, no floating atomics -- the same inputs give the same bytes on every call, in
+ *   every fresh context and for every grid size.
+ * Outputs: any of edge_rate, center_rate, cell_shear_rate and summary may be NULL; only the passes the others need are run.  All four NULL:
+ *   AVS_OK, nothing is launched.  n_edge == n_center == 0: AVS_OK, the summary is zero, the field is zero.  AVS_MEM_DEVICE arrays are
+ *   written by the kernels directly on the context's stream (the memory rules of avs_get_octree_cells); the call returns once the summary,
+ *   if asked for, is on the host.  AVS_MEM_HOST arrays are staged and complete on return.  Scratch (rates, the cell array, partial sums,
+ *   the raw summary, staging) stays in the context.
+ * State: stencils (avs_build_stencils / avs_assemble) and the vector named by `which`, else AVS_ESTATE; slab-local contexts: AVS_ESTATE.
+ *   which not one of the two values, an unknown memory space, a NULL field: AVS_EINVAL. */
+enum { AVS_RATES_OF_SOLUTION = 0, AVS_RATES_OF_INITIAL_GUESS = 1 };
+enum { AVS_EDGE_LOOKUP_OWN = 0, AVS_EDGE_LOOKUP_CHILD = 1, AVS_EDGE_LOOKUP_GRANDCHILD = 2, AVS_EDGE_LOOKUP_SKIPPED = 3 };
+typedef struct avs_strain_summary {
+    int32_t struct_size;                 /* IN: sizeof(avs_strain_summary) of the caller's header */
+    int32_t which;
+    int64_t n_edge, n_center;            /* stencils evaluated: n_edge edge stencils, 3 n_center centre lists */
+    int64_t empty_edges, empty_centers;  /* cnt == 0 (lists: 3 per centre) */
+    int64_t boundary_edges, boundary_centers; /* bcnt > 0 */
+    int64_t nonfinite;                   /* rates that are NaN / Inf */
+    int64_t edge_lookups[4];             /* how the cell pass resolved its 12 n_center edge slots (AVS_EDGE_LOOKUP_*) */
+    int64_t empty_pairs;                 /* (cell, edge axis) with no contributing edge */
+    double dissipation_edge, dissipation_center;
+    double max_abs_edge_rate, max_abs_center_rate, max_shear_rate;   /* over finite values */
+} avs_strain_summary;
+avs_status avs_get_strain_rates(avs_ctx *ctx, int32_t which,
+                                double *edge_rate        /* n_edge,      may be NULL */,
+                                double *center_rate      /* 3*n_center, list id = cell id + n_center*axis, may be NULL */,
+                                double *cell_shear_rate  /* n_center,    may be NULL */,
+                                avs_strain_summary *summary /* may be NULL */, avs_memspace where);
+avs_status avs_get_shear_rate_field(avs_ctx *ctx, int32_t which, float *field /* field_nx*field_ny*field_nz, x fastest */, avs_memspace where);
 
 /* ------------------------------------------------------------------------------------------
  * Seam A: only the solve (replaces cpp:611-643).  CSR with int32 row pointers/columns, fp64

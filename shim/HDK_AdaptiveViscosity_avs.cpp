@@ -25,6 +25,7 @@
 #include <UT/UT_DSOVersion.h>
 #include <UT/UT_Interrupt.h>
 #include <UT/UT_ParallelUtil.h>
+#include <UT/UT_String.h>
 #include <UT/UT_PerfMonAutoEvent.h>
 #include <UT/UT_VoxelArray.h>
 #include <UT/UT_WorkBuffer.h>
@@ -435,6 +436,25 @@ bool HDK_AdaptiveViscosity::solveGasSubclass(SIM_Engine &engine, SIM_Object *obj
         extra.sprintf("iterations=%d, error=%.6f, octree DOFS=%d, regular DOFs=%d", (int)sinfo.iterations, sinfo.error, (int)sinfo.n,
                       (int)pinfo.n_regular);
         event.setExtraInfo(extra.buffer());
+    }
+
+    // ---- optional: the shear rate of the solution into a scalar field of the DOP network ---------------------------------------
+    // New string parameter "shearRateField" (a maintainer adds its PRM_Template next to the reference's, cpp:36-124): the name of a scalar
+    // field aligned with the surface field; empty = off.  gamma = sqrt(2 eps:eps) of the solved octree velocity on the simulation grid
+    // (avs_get_shear_rate_field), for a viscosity model evaluated in the network: mu(gamma) of this substep is the next one's "viscosity".
+    {
+        UT_String shear_name;
+        getOptions().getOptionS("shearRateField", shear_name);
+        if (shear_name.isstring()) {
+            SIM_ScalarField *shear = getScalarField(obj, shear_name.buffer());
+            if (!shear || !shear->getField()->isAligned(surface->getField()))
+                return fail("avs: the shear rate field must exist and be aligned with the surface field");
+            UT_PerfMonAutoSolveEvent event(this, "Shear Rate Field (GPU)");
+            std::vector<float> gamma((size_t)sim[0] * sim[1] * sim[2]);
+            if (!check(avs_get_shear_rate_field(h.ctx, AVS_RATES_OF_SOLUTION, gamma.data(), AVS_MEM_HOST))) return false;
+            unflatten(gamma, *shear->getField());
+            shear->pubHandleModification();
+        }
     }
 
     // ---- octree solution -> regular MAC grid, written back into "vel" (cpp:655-707) ------------------------------------------
