@@ -48,6 +48,7 @@ CHECK_EDGE_INDICES, CHECK_CENTER_INDICES = 1, 2   # bits of `what` of avs_check_
 STRESS_RULES = 9
 RATES_OF_SOLUTION, RATES_OF_INITIAL_GUESS = 0, 1   # `which` of avs_get_strain_rates / avs_get_shear_rate_field
 EDGE_LOOKUP_OWN, EDGE_LOOKUP_CHILD, EDGE_LOOKUP_GRANDCHILD, EDGE_LOOKUP_SKIPPED = range(4)   # avs_strain_summary.edge_lookups
+CHECK_OF_SOLUTION, CHECK_OF_INITIAL_GUESS = 0, 1   # `which` of avs_check_solution
 CSR_CHECK_VALUES, CSR_CHECK_ORDER, CSR_CHECK_DIAGONAL, CSR_CHECK_SYMMETRY, CSR_CHECK_ALL = 1, 2, 4, 8, 15   # bits of `what` of avs_check_csr
 (CSR_RULE_ROW_PTR, CSR_RULE_COLUMN, CSR_RULE_VALUE, CSR_RULE_VECTOR, CSR_RULE_ORDER, CSR_RULE_DIAGONAL, CSR_RULE_PATTERN,
  CSR_RULE_SYMMETRY) = range(8)
@@ -73,7 +74,7 @@ EXPORTED_SYMBOLS = [
     "avs_prepass_set_slab", "avs_prepass_get_window", "avs_dist_bind_prepass", "avs_dist_get_cuts", "avs_set_solution",
     "avs_sample_velocity", "avs_get_octree_cells", "avs_prepass_get_octree_cells", "avs_check_octree", "avs_prepass_check_octree",
     "avs_check_csr", "avs_check_system", "avs_check_stress_indices", "avs_prepass_check_stress_indices",
-    "avs_get_strain_rates", "avs_get_shear_rate_field",
+    "avs_get_strain_rates", "avs_get_shear_rate_field", "avs_check_solution", "avs_check_csr_solution",
 ]
 # avs_allreduce_i32_fn: avs_status (*)(int32_t *device_data, int64_t count, void *stream, void *user)
 ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -201,6 +202,21 @@ class CsrCheck(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(CsrCheck)
+
+
+class SolutionCheck(C.Structure):
+    """avs_solution_check: the report of avs_check_solution / avs_check_csr_solution"""
+    _fields_ = [("struct_size", C.c_int32), ("which", C.c_int32), ("evaluated", C.c_int32), ("claimed_converged", C.c_int32),
+                ("claimed_iterations", C.c_int32), ("reserved", C.c_int32), ("n", C.c_int64), ("nnz", C.c_int64),
+                ("nonfinite_x", C.c_int64), ("nonfinite_b", C.c_int64), ("nonfinite_residual", C.c_int64), ("rows_summed", C.c_int64),
+                ("rhs_norm2", C.c_double), ("residual_norm2", C.c_double), ("relative_residual", C.c_double),
+                ("max_abs_residual", C.c_double), ("max_residual_row", C.c_int64), ("max_abs_x", C.c_double),
+                ("x_dot_ax", C.c_double), ("x_dot_b", C.c_double), ("update_norm2", C.c_double), ("max_abs_update", C.c_double),
+                ("claimed_error", C.c_double)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(SolutionCheck)
 
 
 class ResidentPlanInfo(C.Structure):
@@ -388,6 +404,8 @@ def load(probe=False):
     L.avs_get_shear_rate_field.argtypes = [vp, i32, vp, i32]
     L.avs_check_csr.argtypes = [i64, i64, vp, vp, vp, vp, vp, C.c_uint32, f64, i32, i32, vp, C.POINTER(CsrCheck)]
     L.avs_check_system.argtypes = [vp, C.c_uint32, f64, C.POINTER(CsrCheck)]
+    L.avs_check_solution.argtypes = [vp, i32, vp, C.POINTER(SolutionCheck), i32]
+    L.avs_check_csr_solution.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(SolutionCheck)]
     L.avs_get_dof_table.argtypes = [vp, i32, vp, i32]
     L.avs_plan_owners.argtypes = [i64, vp, vp, i32, i32, i32, i32, vp]
     L.avs_plan_create.argtypes = [i64, vp, vp, vp, i32, i32, C.POINTER(vp)]

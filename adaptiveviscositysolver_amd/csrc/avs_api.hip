@@ -747,6 +747,8 @@ avs_status avs_solve(avs_ctx *c, double tol, int32_t max_iters, avs_solve_info *
     if (info) *info = local;
     c->solved = true;
     ++c->solution_gen;
+    c->claim = local; // (avs_check_solution: what this solve said of the x it left)
+    c->claim_gen = c->solution_gen;
     return AVS_OK;
 }
 

@@ -112,7 +112,7 @@ struct Options {
     int fused_timeout_ms = 2000; // AVS_PCG_FUSED_TIMEOUT_MS: bound of that barrier's wait
     int post_dof_sample = -1;    // AVS_POST_DOF_SAMPLE: the transfer samples its nodes from the velocity DOFs (1) / by a sweep over the node lattices (0);
                                  // -1: from the DOFs when the level-0 node lattice has more than 32 x as many nodes as there are DOFs
-    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) and of the octree and stress index checks (avs_check.hip, avs_stress_check.hip) at that many workgroups (tests: the walks wrap on small lattices)
+    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) and of the octree, stress index and solution checks (avs_check.hip, avs_stress_check.hip, avs_solution_check.hip) at that many workgroups (tests: the walks wrap on small lattices)
     int prepass_temporal = 1;    // AVS_PREPASS_TEMPORAL: the device pre-pass skips what its allocations already hold from their last filling (0: every run fills everything)
     int f32_vectors = -1;        // AVS_F32_VECTORS: AVS_PRECISION_F32 contexts iterate on float vectors with float scalars (what Eigen's float CG does):
                                  // 1 always, 0 never (fp64 iteration on the float system), -1 auto: where the system is too large for the
@@ -673,6 +673,14 @@ struct CsrCheckSource { // device pointers; b, x: may be null
 };
 avs_status check_csr(CsrCheckScratch &S, const CsrCheckSource &src, hipStream_t st, uint32_t what, double symmetry_tolerance, avs_csr_check *report);
 
+// Solution check (avs_solution_check.hip): avs_check_solution / avs_check_csr_solution over one implementation.  Scratch kept across
+// calls: five partial sums per 256 rows, the arg-max pair of every wave of the grid, the raw report, and the staging of a host-bound residual.
+struct SolutionCheckScratch {
+    DevBuf<double> partial, residual;
+    DevBuf<unsigned long long> wave_bits, raw;
+    DevBuf<unsigned> wave_row;
+};
+
 // avs_desc::precision == AVS_PRECISION_F32: the solution as the reference's Eigen::VectorXf holds it (avs_api.hip)
 void narrow_solution_if_f32(avs_ctx *c, double *x, int64_t n);
 
@@ -877,6 +885,10 @@ struct avs_ctx {
     int64_t nnz = 0, nraw = 0;
     bool guess_ready = false, system_ready = false, solved = false;
     bool guess_partial = false; // x0 holds the restriction of SOME rows only (avs_dist_assemble): never handed out
+    // what the last avs_solve claimed, for avs_check_solution: it holds while solution_gen == claim_gen, that is until x, the system or the
+    // pyramids are written again (avs_set_solution, avs_dist_get_solution, a re-assembly); 0 = no claim
+    uint64_t claim_gen = 0;
+    avs_solve_info claim{};
 
     // post-solve transfer (avs_post.hip): regular-grid classification + interpolator work fields
     avs::LatBuf<int32_t> ridx[3];
@@ -907,6 +919,7 @@ struct avs_ctx {
     avs::CsrCheckScratch csr_check; // avs_check_system (avs_csr_check.hip)
     avs::StressCheckScratch stress_check; // avs_check_stress_indices (avs_stress_check.hip)
     avs::StrainScratch strain; // avs_get_strain_rates / avs_get_shear_rate_field (avs_strain.hip)
+    avs::SolutionCheckScratch solution_check; // avs_check_solution (avs_solution_check.hip)
 
     // brick-major copy of the system used by the solve (avs_reorder.hip); perm: new -> old
     avs::DevBuf<int32_t> perm, inv, p_row_ptr, p_col;

@@ -130,6 +130,16 @@ public:
     {
         check(avs_get_shear_rate_field(myCtx, which, field, AVS_MEM_HOST), "avs_get_shear_rate_field");
     }
+    // did x solve the assembled system? (avs_check_solution: the true b - A x in fp64 from the plain CSR, whatever loop and storage form
+    // produced x; report.relative_residual next to report.claimed_error, the solve's own figure.)  residual: n doubles on the host, or
+    // null.  which = AVS_CHECK_OF_INITIAL_GUESS: the residual the solve starts from.
+    avs_solution_check checkSolution(int32_t which = AVS_CHECK_OF_SOLUTION, double *residual = nullptr)
+    {
+        avs_solution_check report{};
+        report.struct_size = (int32_t)sizeof(report);
+        check(avs_check_solution(myCtx, which, residual, &report, AVS_MEM_HOST), "avs_check_solution");
+        return report;
+    }
     SolveResult solveConjugateGradient(double solverTolerance = 1e-3, int maxSolverIterations = 2500)
     {
         avs_solve_info s{};

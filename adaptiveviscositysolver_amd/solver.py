@@ -453,6 +453,28 @@ class ViscositySolve:
         capi.check(self.lib.avs_check_system(self.h, int(what), float(symmetry_tolerance), C.byref(rep)))
         return _csr_check(rep)
 
+    def check_solution(self, which=capi.CHECK_OF_SOLUTION, residual=False, device_arrays=False):
+        """Did x solve the assembled system?  (avs_check_solution: the true residual b - A x in fp64 from the context's reference-numbered
+        CSR, in place, whatever loop and storage form produced x.)  which: capi.CHECK_OF_SOLUTION (needs solve / set_solution) or
+        capi.CHECK_OF_INITIAL_GUESS.  Returns a SolutionCheck; with residual=True its .residual holds every r_i (a NumPy array, or with
+        device_arrays=True a torch tensor on the context's device).  Changes nothing a later solve reads."""
+        rep = capi.SolutionCheck()
+        if not residual:
+            capi.check(self.lib.avs_check_solution(self.h, int(which), None, C.byref(rep), capi.MEM_HOST))
+            return _solution_check(rep, None)
+        n = int(self.info().n_velocity)
+        if not device_arrays:
+            out = np.empty(n, np.float64)
+            capi.check(self.lib.avs_check_solution(self.h, int(which), out.ctypes.data, C.byref(rep), capi.MEM_HOST))
+            return _solution_check(rep, out)
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = torch.empty(n, dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()   # (the stream rules of octree_cells)
+        capi.check(self.lib.avs_check_solution(self.h, int(which), out.data_ptr(), C.byref(rep), capi.MEM_DEVICE))
+        torch.cuda.synchronize(dev)
+        return _solution_check(rep, out)
+
     def strain_rates(self, which=capi.RATES_OF_SOLUTION, device_arrays=False):
         """The deformation of a velocity (avs_get_strain_rates): the rate of every edge stencil (eps_bc at an edge of axis a) and of every
         centre list (du_a/dx_a; list id = cell id + n_center * axis), the shear rate sqrt(2 eps:eps) of every ACTIVE cell (by centre id)
@@ -672,6 +694,73 @@ def check_csr(row_ptr, col, val, b=None, x=None, what=capi.CSR_CHECK_ALL, symmet
                                  None if bb is None else bb.ctypes.data, None if xx is None else xx.ctypes.data, int(what),
                                  float(symmetry_tolerance), capi.MEM_HOST, device, None, C.byref(rep)))
     return _csr_check(rep)
+
+
+@dataclass(frozen=True)
+class SolutionCheck:
+    """report of check_solution / check_csr_solution (avs_solution_check, include/avs.h): relative_residual = sqrt(residual_norm2 /
+    rhs_norm2) of the true r = b - A x over the rows_summed rows whose x_i, b_i and r_i are finite; claimed_error / claimed_converged /
+    claimed_iterations: what the solve that left x said of it (NaN / -1 when unknown); evaluated False: seam A found the row pointers or
+    columns out of range and walked nothing; residual: every r_i when it was asked for, else None"""
+    which: int
+    evaluated: bool
+    claimed_converged: int
+    claimed_iterations: int
+    claimed_error: float
+    n: int
+    nnz: int
+    nonfinite_x: int
+    nonfinite_b: int
+    nonfinite_residual: int
+    rows_summed: int
+    rhs_norm2: float
+    residual_norm2: float
+    relative_residual: float
+    max_abs_residual: float
+    max_residual_row: int
+    max_abs_x: float
+    x_dot_ax: float
+    x_dot_b: float
+    update_norm2: float
+    max_abs_update: float
+    residual: object = None
+
+    @property
+    def energy(self):
+        """0.5 x.Ax - x.b over the summed rows"""
+        return 0.5 * self.x_dot_ax - self.x_dot_b
+
+
+_SOLUTION_CHECK_FIELDS = [f for f in SolutionCheck.__dataclass_fields__ if f != "residual"]
+
+
+def _solution_check(rep, residual):
+    kinds = SolutionCheck.__annotations__
+    return SolutionCheck(**{f: {"int": int, "bool": bool, "float": float}[kinds[f]](getattr(rep, f)) for f in _SOLUTION_CHECK_FIELDS},
+                         residual=residual)
+
+
+def check_csr_solution(row_ptr, col, val, b, x, x0=None, residual=False, device=0):
+    """Did x solve this CSR system?  (avs_check_csr_solution on host numpy arrays: the true residual b - A x in fp64, rows added in stored
+    order; rules 0 and 1 of check_csr run first, and .evaluated is False if they fail.)  x0: the initial guess, for the update figures.
+    Returns a SolutionCheck, with residual=True its .residual filled."""
+    lib = capi.load()
+    rp = np.ascontiguousarray(row_ptr, np.int32)
+    cl = np.ascontiguousarray(col, np.int32)
+    vl = np.ascontiguousarray(val, np.float64)
+    n = len(rp) - 1
+    vecs = {k: None if v is None else np.ascontiguousarray(v, np.float64) for k, v in (("b", b), ("x", x), ("x0", x0))}
+    for name, v in vecs.items():
+        if v is not None and len(v) != n:
+            raise ValueError(f"{name} has {len(v)} entries for {n} rows")
+    if len(cl) != len(vl):
+        raise ValueError(f"col has {len(cl)} entries, val {len(vl)}")
+    out = np.empty(n, np.float64) if residual else None
+    ptr = lambda a: None if a is None or len(a) == 0 else a.ctypes.data
+    rep = capi.SolutionCheck()
+    capi.check(lib.avs_check_csr_solution(n, len(cl), rp.ctypes.data, ptr(cl), ptr(vl), ptr(vecs["b"]), ptr(vecs["x"]), ptr(vecs["x0"]),
+                                          ptr(out), capi.MEM_HOST, device, None, C.byref(rep)))
+    return _solution_check(rep, out)
 
 
 class DevicePrepass:

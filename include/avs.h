@@ -139,7 +139,8 @@ const char *avs_version(void);
  * Purely additive since (no revision): the entries avs_check_octree and avs_prepass_check_octree.
  * Purely additive since (no revision): the entries avs_check_csr and avs_check_system.
  * Purely additive since (no revision): the entries avs_check_stress_indices and avs_prepass_check_stress_indices.
- * Purely additive since (no revision): the entries avs_get_strain_rates and avs_get_shear_rate_field. */
+ * Purely additive since (no revision): the entries avs_get_strain_rates and avs_get_shear_rate_field.
+ * Purely additive since (no revision): the entries avs_check_solution and avs_check_csr_solution. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -652,6 +653,58 @@ avs_status avs_check_csr(int64_t n, int64_t nnz, const int32_t *row_ptr, const i
                          uint32_t what, double symmetry_tolerance, avs_memspace where, int32_t device, void *stream,
                          avs_csr_check *report);
 avs_status avs_check_system(avs_ctx *ctx, uint32_t what, double symmetry_tolerance, avs_csr_check *report);
+
+/* Did x solve A x = b?  The true residual r = b - A x in fp64, from the plain CSR: the output half of the checks above.  avs_solve_info.error
+ * is the recurrence's own sqrt(|r|^2 / |b|^2), the updated residual of whichever loop and storage form ran; this is the product itself.
+ * Nothing else in the library calls either entry, and every other entry behaves as without them.
+ * Rows (fp64, one rounding per operation): y_i = 0; for k = row_ptr[i] .. row_ptr[i + 1] - 1 in stored order: y_i = y_i + val[k] * x[col[k]];
+ *   r_i = b_i - y_i.  The order of the stream SpMV and of a plain CSR loop, so r is defined bit for bit (the sign and payload of a NaN aside).  Rows may
+ *   be unordered and may repeat columns; an empty row gives r_i = b_i.  AVS_PRECISION_F32 contexts are evaluated the same way on the float
+ *   values their fp64 arrays hold.  residual, if given, receives every r_i (n entries), non-finite ones included.
+ * Counters: nonfinite_x, nonfinite_b: entries that are NaN or +-Inf; nonfinite_residual: rows whose r_i is.  rows_summed: rows with x_i,
+ *   b_i and r_i all finite.  Every sum and every maximum below runs over those rows only:
+ *   rhs_norm2 = sum b_i b_i, residual_norm2 = sum r_i r_i, x_dot_ax = sum x_i y_i, x_dot_b = sum x_i b_i (the energy 0.5 xAx - xb is the
+ *   caller's subtraction), max_abs_x = max |x_i|, max_abs_residual = max |r_i| and max_residual_row the smallest row that attains it (-1
+ *   if rows_summed == 0); over the rows among them whose x0_i is finite too: update_norm2 = sum (x_i - x0_i)^2, max_abs_update = max
+ *   |x_i - x0_i| (both 0 when no x0 is known).  A sum is one partial sum per 256 consecutive rows, folded in a fixed order: the same
+ *   arrays give the same bytes on every call, in every context, for every grid.
+ * relative_residual = sqrt(residual_norm2 / rhs_norm2), Eigen's error() (cpp:630); with rhs_norm2 == 0: 0 if residual_norm2 == 0, else +Inf.
+ * avs_check_solution: the context's reference-numbered row_ptr, col, val and rhs, read in place (the arrays avs_check_system reads).
+ *   which = AVS_CHECK_OF_SOLUTION: x is the solution (avs_solve, avs_set_solution) and x0 the initial guess;
+ *   AVS_CHECK_OF_INITIAL_GUESS: x is the initial guess (the update is 0).  AVS_ESTATE without a system (and after avs_dist_assemble or on
+ *   a slab-local context: no global matrix exists) or without the named vector.  claimed_*: avs_solve_info of the last avs_solve, while
+ *   x is still what that solve left and the matrix the one it solved (avs_set_solution, a gathered partitioned solution and a
+ *   re-assembly drop the claim); else -1 / NaN.  Scratch stays in the context; nothing a later avs_solve reads is changed.
+ * avs_check_csr_solution (seam A): arguments and memory rules of avs_check_csr; b and x non-NULL when n > 0, x0 and residual may be NULL.
+ *   col is an address here, so rules 0 and 1 of avs_check_csr run first on the same stream: if either is violated the call returns
+ *   AVS_OK with evaluated = 0, every other figure 0 and residual untouched.  claimed_* = -1 / NaN.  n == 0: evaluated = 1, all 0.
+ * report may be NULL if residual is given (avs_check_csr_solution: report non-NULL); struct_size is IN (only that many bytes are written).
+ *   Unknown which / memory space, both outputs NULL, struct_size out of range: AVS_EINVAL with a message. */
+enum { AVS_CHECK_OF_SOLUTION = 0, AVS_CHECK_OF_INITIAL_GUESS = 1 };   /* same values as AVS_RATES_OF_* */
+typedef struct avs_solution_check {
+    int32_t struct_size;          /* IN: sizeof(avs_solution_check) of the caller's header */
+    int32_t which;
+    int32_t evaluated;            /* 1 = rows were walked; 0 = seam A only: rule 0 or 1 of avs_check_csr is violated, all else 0 */
+    int32_t claimed_converged;    /* avs_solve_info.converged of the solve that left x, else -1 */
+    int32_t claimed_iterations;   /* likewise, else -1 */
+    int32_t reserved;
+    int64_t n, nnz;
+    int64_t nonfinite_x, nonfinite_b, nonfinite_residual;
+    int64_t rows_summed;
+    double rhs_norm2, residual_norm2, relative_residual;
+    double max_abs_residual;
+    int64_t max_residual_row;
+    double max_abs_x;
+    double x_dot_ax, x_dot_b;
+    double update_norm2, max_abs_update;
+    double claimed_error;         /* avs_solve_info.error of that solve, else NaN */
+} avs_solution_check;
+avs_status avs_check_solution(avs_ctx *ctx, int32_t which, double *residual /* n, may be NULL */,
+                              avs_solution_check *report /* may be NULL if residual is given */, avs_memspace where);
+avs_status avs_check_csr_solution(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *col, const double *val,
+                                  const double *b, const double *x, const double *x0 /* may be NULL */,
+                                  double *residual /* may be NULL */, avs_memspace where, int32_t device, void *stream,
+                                  avs_solution_check *report);
 
 /* (measurement / test entries -- single SpMV launches, kernel sweeps, stream probes -- live in include/avs_probe.h and libavs_probe.so) */
 

@@ -435,6 +435,17 @@ bool HDK_AdaptiveViscosity::solveGasSubclass(SIM_Engine &engine, SIM_Object *obj
         UT_WorkBuffer extra;
         extra.sprintf("iterations=%d, error=%.6f, octree DOFS=%d, regular DOFs=%d", (int)sinfo.iterations, sinfo.error, (int)sinfo.n,
                       (int)pinfo.n_regular);
+        // New toggle "verifySolution" (a maintainer adds its PRM_Template next to the reference's, cpp:36-124; off by default): error= is
+        // the loop's own recurrence; true_error= is sqrt(|b - A x|^2 / |b|^2) of the solution it left, from the plain CSR in fp64
+        // (avs_check_solution: one pass over the matrix, well under a millisecond of device time at 512^3)
+        bool verify = false;
+        getOptions().getOptionB("verifySolution", verify);
+        if (verify) {
+            avs_solution_check vrep{};
+            vrep.struct_size = (int32_t)sizeof(vrep);
+            if (!check(avs_check_solution(h.ctx, AVS_CHECK_OF_SOLUTION, nullptr, &vrep, AVS_MEM_HOST))) return false;
+            extra.appendSprintf(", true_error=%.6g", vrep.relative_residual);
+        }
         event.setExtraInfo(extra.buffer());
     }
 
