@@ -82,7 +82,7 @@ ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_v
 PROBE_SYMBOLS = ["avs_spmv_csr", "avs_bench_spmv", "avs_spmv_sell", "avs_bench_stream", "avs_brick_spmv_probe", "avs_spmv_solver_form",
                  "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe", "avs_pcg_csr_plan",
                  "avs_merge_triplets_probe", "avs_exclusive_scan_probe", "avs_resident_plan_host", "avs_brick_form_probe", "avs_pcg_scalar_probe",
-                 "avs_sr_vector_probe", "avs_dist_plan_probe"]
+                 "avs_sr_vector_probe", "avs_dist_plan_probe", "avs_phase_loop_info"]
 DIST_PLAN_PROBE_PLAN, DIST_PLAN_PROBE_TAIL = 0, 1   # avs_dist_plan_probe modes
 BRICK_PROBE_FUSED_DOT, BRICK_PROBE_F32, BRICK_PROBE_MIXED, BRICK_PROBE_VALUE_CODES, BRICK_PROBE_DONE = 1, 2, 4, 8, 16   # avs_brick_form_probe flags
 VECTOR_PROBE_F32, VECTOR_PROBE_DS, VECTOR_PROBE_CODED, VECTOR_PROBE_KEEP, VECTOR_PROBE_FUSED = 1, 2, 4, 8, 16   # avs_vector_update_probe flags
@@ -233,6 +233,17 @@ class ResidentPlanInfo(C.Structure):
         self.struct_size = C.sizeof(ResidentPlanInfo)
 
 
+class PhaseLoopReport(C.Structure):
+    """avs_phase_loop_report (include/avs_probe.h): what the launch-per-phase PCG loop did in the calling thread's last solve"""
+    _fields_ = [(k, C.c_int32) for k in (
+        "struct_size", "solves", "chunks_launched", "chunks_replayed", "graphs_captured", "graph_broken", "alpha_folded", "alpha_launched",
+        "coded", "keep", "fuse_beta", "fuse_vectors", "g", "nb", "float_vectors", "reserved")]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(PhaseLoopReport)
+
+
 class ResidentHostPlanInfo(C.Structure):
     """avs_resident_host_plan_info (include/avs_probe.h): what the host-only planner of the CU-resident loop made of a row-pointer array"""
     _fields_ = [("struct_size", C.c_int32), ("refused", C.c_int32), ("lanes", C.c_int64), ("long_row_lanes", C.c_int32),
@@ -378,6 +389,7 @@ def load(probe=False):
         L.avs_brick_form_probe.argtypes = [i64, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, C.POINTER(f64), vp, i32,
                                            C.POINTER(BrickFormInfo), vp, i32, vp]
         L.avs_dist_plan_probe.argtypes = [i32, C.POINTER(DistPlanInput), C.POINTER(DistPlanOutput), C.POINTER(DistPlanInfo), vp]
+        L.avs_phase_loop_info.argtypes = [C.POINTER(PhaseLoopReport)]
     L.avs_prepass_create.argtypes = [C.POINTER(PrepassDesc), C.POINTER(vp)]
     L.avs_prepass_destroy.argtypes = [vp]
     L.avs_prepass_destroy.restype = None
@@ -461,6 +473,13 @@ def resident_plan_host(row_ptr, workgroups, max_quads=15, lane_fill=0.90, no_str
         return info, None
     L = int(info.lanes)
     return info, {"row0": row0[:L], "meta": meta[:L], "stream_quads": quads[:L], "wl": wl, "wr": wr}
+
+
+def phase_loop_report():
+    """avs_phase_loop_info (libavs_probe.so): the launch-per-phase loop's record of this thread's last solve through that library"""
+    rep = PhaseLoopReport()
+    check(load_probe().avs_phase_loop_info(C.byref(rep)))
+    return rep
 
 
 def brick_form_limits():

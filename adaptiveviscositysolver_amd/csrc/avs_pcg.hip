@@ -79,6 +79,14 @@ struct PcgWork {
     int resident_used = 0;                   // the last solve ran it
 };
 
+#ifdef AVS_PROBES
+// include/avs_probe.h, avs_phase_loop_info: what the launch-per-phase loop did in this thread's last solve (pcg_solve_phases resets it,
+// enqueue_chunk and the loop's enqueue_iteration count).  Probe build only: the product library keeps no such record.
+static thread_local avs_phase_loop_report tl_phase_report = {};
+static thread_local bool tl_phase_capturing = false; // enqueue_iteration is recording a graph: nothing is enqueued
+static thread_local bool tl_phase_folded = false;    // the last enqueue_iteration folded its alpha step into update_r
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // vector kernels
 // ---------------------------------------------------------------------------------------------
@@ -1035,13 +1043,22 @@ static avs_status enqueue_chunk(PcgWork *w, hipStream_t stream, const GraphKey *
         hipGraph_t gr = nullptr;
         bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) == hipSuccess;
         if (ok) {
+#ifdef AVS_PROBES
+            tl_phase_capturing = true;
+#endif
             for (int c = 0; c < kChunk && ok; ++c) ok = enqueue_iteration(c, false) == AVS_OK;
+#ifdef AVS_PROBES
+            tl_phase_capturing = false;
+#endif
             ok = (hipStreamEndCapture(stream, &gr) == hipSuccess) && ok && gr;
         }
         if (ok) ok = hipGraphInstantiate(&w->graph, gr, nullptr, nullptr, 0) == hipSuccess;
         if (gr) (void)hipGraphDestroy(gr);
         if (ok) {
             w->graph_key = *key;
+#ifdef AVS_PROBES
+            tl_phase_report.graphs_captured++;
+#endif
         } else { // plain launches for the rest of this workspace's life
             (void)hipGetLastError();
             w->graph = nullptr;
@@ -1055,6 +1072,16 @@ static avs_status enqueue_chunk(PcgWork *w, hipStream_t stream, const GraphKey *
         AVS_HIP(hipGraphLaunch(w->graph, stream));
     }
     AVS_HIP(hipGetLastError());
+#ifdef AVS_PROBES
+    if (cs->timed) {
+        tl_phase_report.chunks_launched++;
+    } else { // (its iterations: as the launch-by-launch chunk before it counted its own)
+        tl_phase_report.chunks_replayed++;
+        if (tl_phase_folded) tl_phase_report.alpha_folded += kChunk;
+        else tl_phase_report.alpha_launched += kChunk;
+    }
+    tl_phase_report.graph_broken = w->graph_broken ? 1 : 0;
+#endif
     cs->enqueued += chunk;
     cs->last = chunk;
     return AVS_OK;
@@ -2294,6 +2321,15 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
     bool fuse_vec = false; // fp64: one launch for the two vector kernels (k_update_fused)
     if constexpr (!F32) AVS_TRY(fused_vectors_setup(w, A, x, g, fuse_beta, keep, stream, &fuse_vec));
     const long long fused_timeout = (long long)cur_opt().fused_timeout_ms * 100000ll; // wall_clock64: 100 MHz
+#ifdef AVS_PROBES
+    {
+        const int solves = tl_phase_report.solves;
+        tl_phase_report = avs_phase_loop_report{};
+        tl_phase_report.solves = solves + 1;
+        tl_phase_report.coded = coded, tl_phase_report.keep = keep, tl_phase_report.fuse_beta = fuse_beta, tl_phase_report.fuse_vectors = fuse_vec;
+        tl_phase_report.g = g, tl_phase_report.float_vectors = MIXED ? 2 : (F32 ? 1 : 0);
+    }
+#endif
     auto enqueue_iteration = [&](int c, bool timed) -> avs_status {
         int nb = 0;
         if constexpr (!F32)
@@ -2305,6 +2341,11 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
         // reliable update leaves r.z where position 0 reads it), so c & 1 IS that parity
         const int parity = fuse_beta ? (c & 1) : 0;
         const bool fuse_alpha = fuse_beta && nb <= kFuseAlphaMax; // few SpMV partials: every workgroup of update_r folds them itself
+#ifdef AVS_PROBES
+        tl_phase_report.nb = nb;
+        tl_phase_folded = fuse_alpha; // (what the iterations of a replayed chunk count as)
+        if (!tl_phase_capturing) ++(fuse_alpha ? tl_phase_report.alpha_folded : tl_phase_report.alpha_launched);
+#endif
         double *vpart = (F32 || fuse_alpha) ? upper : partial;
         // the fused launch.  Where the SpMV leaves more partial sums than a workgroup folds for itself the alpha step stays a launch of
         // its own in front of it (nb = 0): only when the option is 1 -- "auto" (-1) takes the form that was measured
@@ -2609,6 +2650,16 @@ avs_status sr_vector_probe(int kernel, int flags, int g, int64_t n, const double
 } // namespace avs
 
 #ifdef AVS_PROBES
+extern "C" avs_status avs_phase_loop_info(avs_phase_loop_report *report)
+{
+    AVS_REQUIRE(report && report->struct_size >= 8, AVS_EINVAL, "report: struct_size not set");
+    avs_phase_loop_report o = avs::tl_phase_report;
+    const size_t nbytes = (size_t)report->struct_size < sizeof(o) ? (size_t)report->struct_size : sizeof(o);
+    o.struct_size = (int32_t)nbytes;
+    memcpy(report, &o, nbytes);
+    return AVS_OK;
+}
+
 extern "C" avs_status avs_vector_update_probe(int32_t flags, int32_t g, int64_t n, int32_t nb, int32_t parity, void *x, void *p, void *r,
                                               const void *t, const void *invd, const uint16_t *dcode, const double *spmv_partial,
                                               double *vpart, void *scalars, int32_t scalars_bytes, void *stream)

@@ -102,6 +102,34 @@ avs_status avs_resident_plan_host(int64_t n, const int32_t *row_ptr, int32_t wor
                                   double stream_cost, int32_t *lane_row0, uint32_t *lane_meta, int32_t *lane_stream_quads, int32_t *wg_lane0,
                                   int32_t *wg_row0, avs_resident_host_plan_info *info);
 
+/* What the launch-per-phase loop (pcg_solve_phases, csrc/avs_pcg.hip) did in the LAST solve of the calling thread that ran it -- through
+ * avs_pcg_csr, avs_pcg_csr_plan or avs_solve of this library --, so that a test which claims "graph replay" or "the alpha step as a
+ * launch of its own" does not pass on a solve that took another way.  The caller sets struct_size; fields past it are not written.  Every
+ * such solve starts a new record and adds 1 to `solves`; a solve the CU-resident loop took leaves the record of the solve before, so a
+ * caller that must know compares `solves` before and after.  chunks_launched + chunks_replayed chunks were enqueued (a chunk: up to 32 iterations; what was enqueued past convergence
+ * counts, the kernels of those iterations exit at once).  alpha_folded / alpha_launched count enqueued iterations by where their
+ * alpha step ran: folded into the update_r launch, or as a reduction launch of its own; the iterations of a replayed chunk count as
+ * the loop's launch-by-launch chunk before them did (every solve enqueues its first chunk launch by launch). */
+typedef struct {
+    int32_t struct_size;
+    int32_t solves;            /* launch-per-phase solves of this thread so far */
+    int32_t chunks_launched;   /* chunks enqueued launch by launch */
+    int32_t chunks_replayed;   /* chunks replayed from a captured hipGraph */
+    int32_t graphs_captured;   /* captures that were instantiated */
+    int32_t graph_broken;      /* a capture failed on the solve's workspace: plain launches from then on */
+    int32_t alpha_folded;
+    int32_t alpha_launched;
+    int32_t coded;             /* the vector kernels read 2-B diagonal codes and the table of inverted values */
+    int32_t keep;              /* plain instead of non-temporal loads and stores in the vector kernels */
+    int32_t fuse_beta;
+    int32_t fuse_vectors;      /* the single fused vector launch was set up for this solve */
+    int32_t g;                 /* workgroups of the vector kernels */
+    int32_t nb;                /* partial sums the last enqueued SpMV leaves */
+    int32_t float_vectors;     /* 0 fp64, 1 float vectors and scalars, 2 mixed precision */
+    int32_t reserved;
+} avs_phase_loop_report;
+avs_status avs_phase_loop_info(avs_phase_loop_report *report);
+
 /* Measurement: load balance of the brick kernel's row walk -- per G tile the quads of the slowest of the eight waves against the mean wave
  * (printed to stderr; out6 = {tiles, rows per tile, quads per row, slowest-wave quads, mean-wave quads, 0}) */
 avs_status avs_brick_wave_stats(avs_ctx *ctx, double *out6);
