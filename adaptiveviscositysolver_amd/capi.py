@@ -49,6 +49,9 @@ STRESS_RULES = 9
 RATES_OF_SOLUTION, RATES_OF_INITIAL_GUESS = 0, 1   # `which` of avs_get_strain_rates / avs_get_shear_rate_field
 EDGE_LOOKUP_OWN, EDGE_LOOKUP_CHILD, EDGE_LOOKUP_GRANDCHILD, EDGE_LOOKUP_SKIPPED = range(4)   # avs_strain_summary.edge_lookups
 CHECK_OF_SOLUTION, CHECK_OF_INITIAL_GUESS = 0, 1   # `which` of avs_check_solution
+SPECTRUM_OF_JACOBI, SPECTRUM_OF_MATRIX = 0, 1   # `op` of avs_estimate_spectrum
+SPECTRUM_START_RESIDUAL, SPECTRUM_START_HASH, SPECTRUM_START_VECTOR = 0, 1, 2   # its `start`
+SPECTRUM_MAX_STEPS = 512
 CSR_CHECK_VALUES, CSR_CHECK_ORDER, CSR_CHECK_DIAGONAL, CSR_CHECK_SYMMETRY, CSR_CHECK_ALL = 1, 2, 4, 8, 15   # bits of `what` of avs_check_csr
 (CSR_RULE_ROW_PTR, CSR_RULE_COLUMN, CSR_RULE_VALUE, CSR_RULE_VECTOR, CSR_RULE_ORDER, CSR_RULE_DIAGONAL, CSR_RULE_PATTERN,
  CSR_RULE_SYMMETRY) = range(8)
@@ -75,6 +78,7 @@ EXPORTED_SYMBOLS = [
     "avs_sample_velocity", "avs_get_octree_cells", "avs_prepass_get_octree_cells", "avs_check_octree", "avs_prepass_check_octree",
     "avs_check_csr", "avs_check_system", "avs_check_stress_indices", "avs_prepass_check_stress_indices",
     "avs_get_strain_rates", "avs_get_shear_rate_field", "avs_check_solution", "avs_check_csr_solution",
+    "avs_estimate_spectrum", "avs_estimate_csr_spectrum",
 ]
 # avs_allreduce_i32_fn: avs_status (*)(int32_t *device_data, int64_t count, void *stream, void *user)
 ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -217,6 +221,20 @@ class SolutionCheck(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(SolutionCheck)
+
+
+class Spectrum(C.Structure):
+    """avs_spectrum: the report of avs_estimate_spectrum / avs_estimate_csr_spectrum"""
+    _fields_ = [("struct_size", C.c_int32), ("evaluated", C.c_int32), ("op", C.c_int32), ("start", C.c_int32), ("steps_asked", C.c_int32),
+                ("steps_taken", C.c_int32), ("breakdown", C.c_int32), ("nonfinite", C.c_int32), ("indefinite", C.c_int32),
+                ("n", C.c_int64), ("nnz", C.c_int64), ("bad_diagonal", C.c_int64), ("start_norm", C.c_double), ("lambda_min", C.c_double),
+                ("lambda_max", C.c_double), ("lambda_min_bound", C.c_double), ("lambda_max_bound", C.c_double),
+                ("gershgorin_max", C.c_double), ("condition_estimate", C.c_double), ("tolerance", C.c_double),
+                ("iteration_bound", C.c_int64)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(Spectrum)
 
 
 class ResidentPlanInfo(C.Structure):
@@ -418,6 +436,9 @@ def load(probe=False):
     L.avs_check_system.argtypes = [vp, C.c_uint32, f64, C.POINTER(CsrCheck)]
     L.avs_check_solution.argtypes = [vp, i32, vp, C.POINTER(SolutionCheck), i32]
     L.avs_check_csr_solution.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(SolutionCheck)]
+    L.avs_estimate_spectrum.argtypes = [vp, i32, i32, i32, f64, vp, vp, vp, vp, vp, i32, C.POINTER(Spectrum)]
+    L.avs_estimate_csr_spectrum.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, f64, vp, vp, vp, vp, vp, i32, i32, vp,
+                                            C.POINTER(Spectrum)]
     L.avs_get_dof_table.argtypes = [vp, i32, vp, i32]
     L.avs_plan_owners.argtypes = [i64, vp, vp, i32, i32, i32, i32, vp]
     L.avs_plan_create.argtypes = [i64, vp, vp, vp, i32, i32, C.POINTER(vp)]

@@ -112,7 +112,7 @@ struct Options {
     int fused_timeout_ms = 2000; // AVS_PCG_FUSED_TIMEOUT_MS: bound of that barrier's wait
     int post_dof_sample = -1;    // AVS_POST_DOF_SAMPLE: the transfer samples its nodes from the velocity DOFs (1) / by a sweep over the node lattices (0);
                                  // -1: from the DOFs when the level-0 node lattice has more than 32 x as many nodes as there are DOFs
-    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) and of the octree, stress index and solution checks (avs_check.hip, avs_stress_check.hip, avs_solution_check.hip) at that many workgroups (tests: the walks wrap on small lattices)
+    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) and of the octree, stress index and solution checks and of the spectrum estimate (avs_check.hip, avs_stress_check.hip, avs_solution_check.hip, avs_spectrum.hip) at that many workgroups (tests: the walks wrap on small lattices)
     int prepass_temporal = 1;    // AVS_PREPASS_TEMPORAL: the device pre-pass skips what its allocations already hold from their last filling (0: every run fills everything)
     int f32_vectors = -1;        // AVS_F32_VECTORS: AVS_PRECISION_F32 contexts iterate on float vectors with float scalars (what Eigen's float CG does):
                                  // 1 always, 0 never (fp64 iteration on the float system), -1 auto: where the system is too large for the
@@ -681,6 +681,13 @@ struct SolutionCheckScratch {
     DevBuf<unsigned> wave_row;
 };
 
+// Spectrum estimate (avs_spectrum.hip): avs_estimate_spectrum / avs_estimate_csr_spectrum over one implementation.  Scratch kept across
+// calls: five n-vectors (the scale s, u = s o v_j, two Lanczos vectors that change roles, w), one partial sum per 256 rows, the raw words.
+struct SpectrumScratch {
+    DevBuf<double> s, u, va, vb, w, partial;
+    DevBuf<unsigned long long> raw;
+};
+
 // avs_desc::precision == AVS_PRECISION_F32: the solution as the reference's Eigen::VectorXf holds it (avs_api.hip)
 void narrow_solution_if_f32(avs_ctx *c, double *x, int64_t n);
 
@@ -920,6 +927,7 @@ struct avs_ctx {
     avs::StressCheckScratch stress_check; // avs_check_stress_indices (avs_stress_check.hip)
     avs::StrainScratch strain; // avs_get_strain_rates / avs_get_shear_rate_field (avs_strain.hip)
     avs::SolutionCheckScratch solution_check; // avs_check_solution (avs_solution_check.hip)
+    avs::SpectrumScratch spectrum; // avs_estimate_spectrum (avs_spectrum.hip)
 
     // brick-major copy of the system used by the solve (avs_reorder.hip); perm: new -> old
     avs::DevBuf<int32_t> perm, inv, p_row_ptr, p_col;

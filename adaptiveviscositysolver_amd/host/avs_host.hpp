@@ -140,6 +140,18 @@ public:
         check(avs_check_solution(myCtx, which, residual, &report, AVS_MEM_HOST), "avs_check_solution");
         return report;
     }
+    // why does the solve take the iterations it takes? (avs_estimate_spectrum: `steps` Lanczos steps in fp64 on the Jacobi-scaled matrix
+    // -- op = AVS_SPECTRUM_OF_MATRIX: on A -- started from the scaled initial residual.  report.lambda_min / lambda_max with their
+    // bounds, report.condition_estimate (a lower bound), report.iteration_bound for `tolerance`, report.indefinite.)  ritz: `steps`
+    // doubles on the host, or null.  Needs avs_assemble; changes nothing a later solve reads.
+    avs_spectrum estimateSpectrum(int32_t steps = 32, double tolerance = 1e-3, int32_t op = AVS_SPECTRUM_OF_JACOBI, double *ritz = nullptr)
+    {
+        avs_spectrum report{};
+        report.struct_size = (int32_t)sizeof(report);
+        check(avs_estimate_spectrum(myCtx, op, AVS_SPECTRUM_START_RESIDUAL, steps, tolerance, nullptr, nullptr, ritz, nullptr, nullptr, AVS_MEM_HOST, &report),
+              "avs_estimate_spectrum");
+        return report;
+    }
     SolveResult solveConjugateGradient(double solverTolerance = 1e-3, int maxSolverIterations = 2500)
     {
         avs_solve_info s{};

@@ -475,6 +475,18 @@ class ViscositySolve:
         torch.cuda.synchronize(dev)
         return _solution_check(rep, out)
 
+    def estimate_spectrum(self, op=capi.SPECTRUM_OF_JACOBI, start=capi.SPECTRUM_START_RESIDUAL, steps=32, tolerance=1e-3, scale=False, basis=False,
+                          device_arrays=False):
+        """Why does the solve take the iterations it takes?  (avs_estimate_spectrum: `steps` Lanczos steps in fp64 on D^-1/2 A D^-1/2 --
+        op=capi.SPECTRUM_OF_MATRIX: on A -- from the context's reference-numbered CSR, in place, started from the scaled initial residual
+        or from the hash vector.)  Returns a Spectrum: lambda_min / lambda_max with their error bounds, gershgorin_max,
+        condition_estimate (a lower bound), iteration_bound for `tolerance`, indefinite, and the arrays alpha, beta, ritz; with scale=True /
+        basis=True also .scale (n) and .basis (steps + 1 rows of n: row j = v_j) as NumPy arrays, or with device_arrays=True as torch
+        tensors on the context's device.  Changes nothing a later solve reads."""
+        n = int(self.info().n_velocity)
+        return _estimate(lambda *a: self.lib.avs_estimate_spectrum(self.h, *a), n, op, start, steps, tolerance, scale, basis,
+                         self.device if device_arrays else None)
+
     def strain_rates(self, which=capi.RATES_OF_SOLUTION, device_arrays=False):
         """The deformation of a velocity (avs_get_strain_rates): the rate of every edge stencil (eps_bc at an edge of axis a) and of every
         centre list (du_a/dx_a; list id = cell id + n_center * axis), the shear rate sqrt(2 eps:eps) of every ACTIVE cell (by centre id)
@@ -761,6 +773,99 @@ def check_csr_solution(row_ptr, col, val, b, x, x0=None, residual=False, device=
     capi.check(lib.avs_check_csr_solution(n, len(cl), rp.ctypes.data, ptr(cl), ptr(vl), ptr(vecs["b"]), ptr(vecs["x"]), ptr(vecs["x0"]),
                                           ptr(out), capi.MEM_HOST, device, None, C.byref(rep)))
     return _solution_check(rep, out)
+
+
+@dataclass(frozen=True)
+class Spectrum:
+    """report of estimate_spectrum / estimate_csr_spectrum (avs_spectrum, include/avs.h): the extreme Ritz values of steps_taken Lanczos
+    steps on the operator the solve inverts, each with the distance within which an eigenvalue lies (lambda_*_bound); condition_estimate =
+    lambda_max / lambda_min is a LOWER bound of the condition number, iteration_bound the classical CG bound for `tolerance` (-1: none);
+    indefinite: a Ritz value <= 0, the matrix is not positive definite; evaluated False: the row pointers or columns are out of range
+    (seam A) or bad_diagonal rows have no positive finite diagonal.  alpha, beta, ritz: NumPy arrays (steps, steps + 1, steps entries; 0
+    behind what steps_taken wrote); scale, basis: as asked for, else None"""
+    evaluated: bool
+    op: int
+    start: int
+    steps_asked: int
+    steps_taken: int
+    breakdown: bool
+    nonfinite: bool
+    indefinite: bool
+    n: int
+    nnz: int
+    bad_diagonal: int
+    start_norm: float
+    lambda_min: float
+    lambda_max: float
+    lambda_min_bound: float
+    lambda_max_bound: float
+    gershgorin_max: float
+    condition_estimate: float
+    tolerance: float
+    iteration_bound: int
+    alpha: object = None
+    beta: object = None
+    ritz: object = None
+    scale: object = None
+    basis: object = None
+
+
+_SPECTRUM_ARRAYS = ("alpha", "beta", "ritz", "scale", "basis")
+_SPECTRUM_FIELDS = [f for f in Spectrum.__dataclass_fields__ if f not in _SPECTRUM_ARRAYS]
+
+
+def _estimate(call, n, op, start, steps, tolerance, scale, basis, device):
+    """call(op, start, steps, tolerance, alpha, beta, ritz, scale, basis, where, report) -> status; device: None for NumPy outputs"""
+    steps = int(steps)
+    room = max(steps, 0)
+    alpha, beta, ritz = np.zeros(room), np.zeros(room + 1), np.zeros(room)
+    s_out = b_out = None
+    if device is None:
+        s_out = np.zeros(n) if scale else None
+        b_out = np.zeros((room + 1, n)) if basis else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        s_out = torch.zeros(n, dtype=torch.float64, device=dev) if scale else None
+        b_out = torch.zeros((room + 1, n), dtype=torch.float64, device=dev) if basis else None
+        torch.cuda.current_stream(dev).synchronize()   # (the stream rules of octree_cells)
+        ptr = lambda a: None if a is None else a.data_ptr()
+    rep = capi.Spectrum()
+    capi.check(call(int(op), int(start), steps, float(tolerance), alpha.ctypes.data, beta.ctypes.data, ritz.ctypes.data, ptr(s_out), ptr(b_out),
+                    capi.MEM_HOST if device is None else capi.MEM_DEVICE, C.byref(rep)))
+    if device is not None:
+        import torch
+        torch.cuda.synchronize(torch.device("cuda", device))
+    kinds = Spectrum.__annotations__
+    return Spectrum(**{f: {"int": int, "bool": bool, "float": float}[kinds[f]](getattr(rep, f)) for f in _SPECTRUM_FIELDS},
+                    alpha=alpha, beta=beta, ritz=ritz, scale=s_out, basis=b_out)
+
+
+def estimate_csr_spectrum(row_ptr, col, val, b=None, x0=None, start_vector=None, op=capi.SPECTRUM_OF_JACOBI, start=None, steps=32, tolerance=1e-3,
+                          scale=False, basis=False, device=0):
+    """The spectrum of this CSR matrix as a CG solve sees it (avs_estimate_csr_spectrum on host numpy arrays: `steps` Lanczos steps in fp64
+    on D^-1/2 A D^-1/2, or on A with op=capi.SPECTRUM_OF_MATRIX; rules 0 and 1 of check_csr run first, and .evaluated is False if they
+    fail).  start: capi.SPECTRUM_START_*; None picks the caller's start_vector if given, the scaled residual of (b, x0) if both are given,
+    else the hash vector.  Returns a Spectrum, with scale=True / basis=True its .scale / .basis filled."""
+    lib = capi.load()
+    rp = np.ascontiguousarray(row_ptr, np.int32)
+    cl = np.ascontiguousarray(col, np.int32)
+    vl = np.ascontiguousarray(val, np.float64)
+    n = len(rp) - 1
+    vecs = {k: None if v is None else np.ascontiguousarray(v, np.float64) for k, v in (("b", b), ("x0", x0), ("start_vector", start_vector))}
+    for name, v in vecs.items():
+        if v is not None and len(v) != n:
+            raise ValueError(f"{name} has {len(v)} entries for {n} rows")
+    if len(cl) != len(vl):
+        raise ValueError(f"col has {len(cl)} entries, val {len(vl)}")
+    if start is None:
+        start = capi.SPECTRUM_START_VECTOR if start_vector is not None else \
+            capi.SPECTRUM_START_RESIDUAL if b is not None and x0 is not None else capi.SPECTRUM_START_HASH
+    ptr = lambda a: None if a is None or len(a) == 0 else a.ctypes.data
+    return _estimate(lambda op_, start_, steps_, tol, *outs: lib.avs_estimate_csr_spectrum(
+        n, len(cl), rp.ctypes.data, ptr(cl), ptr(vl), ptr(vecs["b"]), ptr(vecs["x0"]), ptr(vecs["start_vector"]), op_, start_, steps_, tol, *outs[:6],
+        device, None, outs[6]), n, op, start, steps, tolerance, scale, basis, None)
 
 
 class DevicePrepass:

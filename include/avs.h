@@ -140,7 +140,8 @@ const char *avs_version(void);
  * Purely additive since (no revision): the entries avs_check_csr and avs_check_system.
  * Purely additive since (no revision): the entries avs_check_stress_indices and avs_prepass_check_stress_indices.
  * Purely additive since (no revision): the entries avs_get_strain_rates and avs_get_shear_rate_field.
- * Purely additive since (no revision): the entries avs_check_solution and avs_check_csr_solution. */
+ * Purely additive since (no revision): the entries avs_check_solution and avs_check_csr_solution.
+ * Purely additive since (no revision): the entries avs_estimate_spectrum and avs_estimate_csr_spectrum. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -705,6 +706,82 @@ avs_status avs_check_csr_solution(int64_t n, int64_t nnz, const int32_t *row_ptr
                                   const double *b, const double *x, const double *x0 /* may be NULL */,
                                   double *residual /* may be NULL */, avs_memspace where, int32_t device, void *stream,
                                   avs_solution_check *report);
+
+/* Why does a solve take the iterations it takes?  m steps of the symmetric Lanczos recurrence on the operator the solve inverts, S A S with
+ * S = diag(s): op = AVS_SPECTRUM_OF_JACOBI: s_i = 1 / sqrt(d_i), the Jacobi-scaled matrix D^-1/2 A D^-1/2; AVS_SPECTRUM_OF_MATRIX: s_i = 1,
+ * A itself (AVS_PRECONDITIONER_NONE).  The result is the Ritz values, error bounds of the two extreme ones, a Gershgorin bound of
+ * lambda_max, a condition estimate and the classical CG iteration bound; a Ritz value <= 0 certifies that the matrix is not positive
+ * definite.  The product is the fp64 stream product of avs_check_solution over the plain reference-numbered CSR, whichever storage form
+ * and loop a solve would use.  Nothing else in the library calls either entry, and every other entry behaves as without them.
+ * Everything is fp64 with one rounding per operation; the matrix is taken as symmetric (avs_check_csr, rule 7, says whether it is).
+ * Diagonal and scale: d_i is the LAST entry of row i with col == i (what the Jacobi preconditioner and rule 5 of avs_check_csr read);
+ *   s_i = 1.0 / sqrt(d_i).  A row without a diagonal entry, or whose d_i is not > 0 or not finite, counts in bad_diagonal and has s_i = 0;
+ *   with bad_diagonal > 0 nothing else is evaluated (evaluated = 0, AVS_OK).  OF_MATRIX never looks at the diagonal (bad_diagonal = 0).
+ * gershgorin_max = max_i g_i with g_i = 0; g_i = g_i + |val[k]| * (s_i * s_col[k]) for the entries of row i in stored order: an upper
+ *   bound of lambda_max up to its own rounding (it is NOT rounded outward).  The maximum is taken over bit patterns of non-negative
+ *   doubles, so it does not depend on any order; a row sum that is not finite gives +Inf.
+ * Start vector v: AVS_SPECTRUM_START_RESIDUAL: v = s o (b - A x0), rows formed as in avs_check_solution -- the Krylov space CG itself
+ *   works in; AVS_SPECTRUM_START_HASH: v_i = (double)(splitmix64(i) >> 11) * 2^-53 - 0.5, exact arithmetic, so the vector is defined
+ *   bit for bit (splitmix64(i): z = i + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) *
+ *   0x94D049BB133111EB; z ^ (z >> 31), in 64-bit unsigned arithmetic); AVS_SPECTRUM_START_VECTOR: the caller's array.  beta[0] =
+ *   start_norm = sqrt(sum v_i v_i); v_0 = v / beta[0], divided element by element.  A start norm that is zero or not finite gives
+ *   steps_taken = 0 (nonfinite = 1 if it was not finite).
+ * Step j = 0 .. steps - 1 (Paige's ordering): u = s o v_j; y_i = sum val[k] * u[col[k]], left to right in stored order; t_i = s_i * y_i
+ *   - beta[j] * v_{j-1,i} (no beta term at j = 0); alpha[j] = sum v_{j,i} t_i; w_i = t_i - alpha[j] * v_{j,i}; beta[j + 1] = sqrt(sum
+ *   w_i w_i); v_{j+1} = w / beta[j + 1], by division.  The effective number of steps is min(steps, n).  No reorthogonalisation.
+ * Stop before v_{j+1} is formed, with steps_taken = j + 1: alpha[j] or beta[j + 1] is not finite (nonfinite = 1); or not (beta[j + 1] >
+ *   2^-36 * (|alpha[j]| + beta[j])) (breakdown = 1: the Krylov space is invariant to working accuracy and the Ritz values are
+ *   eigenvalues).  The threshold lies some ten bits below the square root of the unit roundoff: sum v^2 is not exactly 1, so an exact
+ *   zero almost never occurs, and a w that small is rounding error of t and alpha v, not a new direction.
+ * Sums: every sum is one partial sum per 256 consecutive rows, folded in a fixed order, without floating-point atomics: the same arrays
+ *   give the same bytes on every call, in every context, for every grid.
+ * Host part, k = steps_taken: T_k = tridiag(beta[1 .. k - 1]; alpha[0 .. k - 1]); ritz = its eigenvalues in ascending order (implicit QL);
+ *   lambda_min, lambda_max the extreme ones; lambda_*_bound = beta[k] * |last component of that Ritz vector|: an eigenvalue of the
+ *   operator lies within that distance of the Ritz value.  indefinite = 1 if lambda_min <= 0.  condition_estimate = lambda_max /
+ *   lambda_min (+Inf if indefinite): a LOWER bound of the condition number, since the Ritz values lie inside the spectrum (lambda_min
+ *   converges from above).  iteration_bound = ceil(0.5 sqrt(condition_estimate) ln(2 / tolerance)) for tolerance in (0, 1) and a finite
+ *   estimate, else -1: the bound of the A-norm of the error, not Eigen's residual rule (avs_solve_info.error).  With steps_taken = 0:
+ *   all of these 0 and iteration_bound -1; if a step left a non-finite alpha or beta: NaN and -1.  Without reorthogonalisation the
+ *   extremes are reliable, multiplicities are not (converged Ritz values come back as copies).
+ * Outputs: alpha (steps), beta (steps + 1) and ritz (steps) are always HOST arrays and complete on return (0 behind what the steps taken
+ *   wrote); scale (n) and basis (n x (steps + 1), column-major, column j = v_j) follow `where`; every one may be NULL.  scale is written
+ *   whenever the diagonal was read (also with bad_diagonal > 0).  basis holds columns 0 .. steps_taken - 1, and column steps_taken unless
+ *   the recurrence stopped; what lies behind them is unspecified.  n == 0: evaluated = 1, steps_taken = 0.
+ * Scratch: five n-vectors of doubles (s, u, v_{j-1}, v_j, w), kept in the context: 300 MB at 512^3.  Nothing a later avs_assemble,
+ *   avs_solve or transfer reads is changed.  The recurrence is enqueued whole; the stop decision is a word in device memory.
+ * avs_estimate_spectrum: the context's reference-numbered row_ptr, col, val, rhs and initial guess, read in place.  AVS_ESTATE where
+ *   avs_check_solution(AVS_CHECK_OF_INITIAL_GUESS) returns it; AVS_SPECTRUM_START_VECTOR: AVS_EINVAL.
+ * avs_estimate_csr_spectrum (seam A): arguments and memory rules of avs_check_csr_solution; b and x0 non-NULL for START_RESIDUAL,
+ *   start_vector for START_VECTOR (n > 0), otherwise they may be NULL.  Rules 0 and 1 of avs_check_csr run first on the same stream: if
+ *   either is violated the call returns AVS_OK with evaluated = 0, every figure 0 and no array but alpha, beta and ritz (zeros) written.
+ * steps outside [1, AVS_SPECTRUM_MAX_STEPS], unknown op / start / memory space, report NULL or its struct_size out of range, n or nnz
+ *   outside [0, 2^31): AVS_EINVAL with a message.  struct_size is IN (only that many bytes are written). */
+enum { AVS_SPECTRUM_OF_JACOBI = 0, AVS_SPECTRUM_OF_MATRIX = 1 };              /* s_i = 1/sqrt(d_i)  |  s_i = 1 */
+enum { AVS_SPECTRUM_START_RESIDUAL = 0, AVS_SPECTRUM_START_HASH = 1, AVS_SPECTRUM_START_VECTOR = 2 };
+#define AVS_SPECTRUM_MAX_STEPS 512
+typedef struct avs_spectrum {
+    int32_t struct_size;          /* IN: sizeof(avs_spectrum) of the caller's header */
+    int32_t evaluated;            /* 1 = the recurrence was set up; 0 = rule 0 or 1 of avs_check_csr violated (seam A), or bad_diagonal > 0 */
+    int32_t op, start, steps_asked;
+    int32_t steps_taken;          /* k: alpha[0 .. k - 1] and beta[0 .. k] are the recurrence's */
+    int32_t breakdown, nonfinite, indefinite;
+    int64_t n, nnz;
+    int64_t bad_diagonal;
+    double start_norm;
+    double lambda_min, lambda_max, lambda_min_bound, lambda_max_bound;
+    double gershgorin_max;
+    double condition_estimate;
+    double tolerance;             /* as given */
+    int64_t iteration_bound;
+} avs_spectrum;
+avs_status avs_estimate_spectrum(avs_ctx *ctx, int32_t op, int32_t start, int32_t steps, double tolerance,
+                                 double *alpha /* steps */, double *beta /* steps + 1 */, double *ritz /* steps */, double *scale /* n */,
+                                 double *basis /* n x (steps + 1), column j = v_j, column-major */, avs_memspace where,
+                                 avs_spectrum *report);
+avs_status avs_estimate_csr_spectrum(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *col, const double *val,
+                                     const double *b, const double *x0, const double *start_vector, int32_t op, int32_t start,
+                                     int32_t steps, double tolerance, double *alpha, double *beta, double *ritz, double *scale,
+                                     double *basis, avs_memspace where, int32_t device, void *stream, avs_spectrum *report);
 
 /* (measurement / test entries -- single SpMV launches, kernel sweeps, stream probes -- live in include/avs_probe.h and libavs_probe.so) */
 
