@@ -12,7 +12,7 @@
 //                      LINEAR order: rows of n + 1 entries never line up with anything, the lattice as a whole does; the last entries
 //                      one by one).  Rules 4 and 6 need the entry alone, rule 5 the two cells the face lies between (and the parent of
 //                      an UP one) -- only for the faces that carry an id --, and every id in range counts itself in occ[id].
-//   k_check_numbering  rule 7 over the occurrence counters.
+//   k_index_numbering  rule 7 over the occurrence counters (shared with the stress index check, defined here).
 //
 // Every rule is independent: no label and no index is used as an address.  The only address formed from a lattice value is occ[id], and
 // that store is under the range test of rule 4.  Cells outside their lattice are never read (they count as INACTIVE).
@@ -20,13 +20,12 @@
 // reached from the other side of a face is the same ACTIVE cell, its DOWN parent, or its UP child (tests/test_octree_check_model.py
 // asserts it on its scenes).
 // Counts are 64-bit: a thread counts in registers, a wave adds its lanes and issues one atomic per rule it violated; the first violation
-// is one atomicMin of a packed key (avs_check_report.hpp) per violating wave.  Integer work only: the same lattices give the same report.
+// is one atomicMin of a packed key (lattice_key, avs_report.hpp) per violating wave (raw_commit, avs_report_device.hpp).  Integer work
+// only: the same lattices give the same report.
 #include "avs_internal.hpp"
+#include "avs_report_device.hpp"
 
 namespace avs {
-
-static constexpr int kCheckBlock = 256;
-static constexpr int kCheckGrid = 2048; // persistent grids: eight workgroups per CU
 
 struct CheckLevels { // by value; the level of a launch is a kernel argument: every table lookup is wave-uniform
     const int8_t *lab[AVS_MAX_LEVELS];
@@ -55,27 +54,6 @@ __device__ __forceinline__ uint32_t check_run(const int8_t *lab, int n0, int n1,
     return w;
 }
 __device__ __forceinline__ int check_byte(uint32_t w, int b) { return (int)(int8_t)(w >> (8 * b)); }
-
-// what a thread found, folded into the raw report: counts[r] += c[r] (one atomic per wave and rule), key = min(key, ...) (one per wave)
-template <int N>
-__device__ __forceinline__ void check_commit(const unsigned (&c)[N], const int (&rule)[N], unsigned long long key, unsigned long long *raw)
-{
-    const int lane = (int)threadIdx.x & 63;
-#pragma unroll
-    for (int r = 0; r < N; ++r) {
-        unsigned long long s = c[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += (unsigned long long)__shfl_xor((long long)s, o, 64);
-        if (lane == 0 && s) atomicAdd(raw + rule[r], s);
-    }
-    unsigned long long m = key;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = (unsigned long long)__shfl_xor((long long)m, o, 64);
-        m = other < m ? other : m;
-    }
-    if (lane == 0 && m != kCheckNoKey) atomicMin(raw + AVS_OCTREE_RULES, m);
-}
 
 // rule 3 for ACTIVE cell C of `level` and its in-lattice neighbour (ni, nj, nk) = C + s along axis d, whose label is nb
 __device__ __forceinline__ bool check_active_face(const CheckLevels &P, int level, int d, int s, int ni, int nj, int nk, int nb)
@@ -114,7 +92,7 @@ __device__ __forceinline__ void check_label_run(const CheckLevels &P, int level,
         const int v = check_byte(c, b);
         if (b < nv && (unsigned)v > 3u) { // rule 0
             ++cnt[0];
-            key = min(key, check_key(AVS_RULE_LABEL_VALUE, level, 0, lin0 + b));
+            key = min(key, lattice_key(AVS_RULE_LABEL_VALUE, level, 0, lin0 + b));
         }
         any_up |= b < nv && v == AVS_UP;
         any_act |= b < nv && v == AVS_ACTIVE;
@@ -152,7 +130,7 @@ __device__ __forceinline__ void check_label_run(const CheckLevels &P, int level,
             if (check_byte(c, b) == AVS_UP && !((found >> b) & 1u)) bad |= 1u << b;
             if (b < nv && ((bad >> b) & 1u)) {
                 ++cnt[1];
-                key = min(key, check_key(AVS_RULE_COLUMN, 0, 0, lin0 + b));
+                key = min(key, lattice_key(AVS_RULE_COLUMN, 0, 0, lin0 + b));
             }
         }
     }
@@ -182,7 +160,7 @@ __device__ __forceinline__ void check_label_run(const CheckLevels &P, int level,
             for (int f = 0; f < 6; ++f) bad |= in[f] && nbv[f] != AVS_ACTIVE && nbv[f] != AVS_UP;
             if (bad) {
                 ++cnt[2];
-                key = min(key, check_key(AVS_RULE_UP, level, 0, lin0 + b));
+                key = min(key, lattice_key(AVS_RULE_UP, level, 0, lin0 + b));
             }
         } else { // rule 3
 #pragma unroll
@@ -193,7 +171,7 @@ __device__ __forceinline__ void check_label_run(const CheckLevels &P, int level,
             }
             if (bad) {
                 ++cnt[3];
-                key = min(key, check_key(AVS_RULE_ACTIVE, level, 0, lin0 + b));
+                key = min(key, lattice_key(AVS_RULE_ACTIVE, level, 0, lin0 + b));
             }
         }
     }
@@ -264,7 +242,7 @@ __device__ __forceinline__ bool check_piece_passes(const CheckLevels &P, const i
 // seven loads in flight per sixteen cells.  (A run per thread, its ancestors fetched after its word, left the level-0 pass waiting on
 // two dependent rounds of loads for every four bytes.)
 template <bool pieces16>
-__global__ __launch_bounds__(kCheckBlock) void k_check_labels(CheckLevels P, int level_arg, unsigned long long *__restrict__ raw)
+__global__ __launch_bounds__(kBlock) void k_check_labels(CheckLevels P, int level_arg, unsigned long long *__restrict__ raw)
 {
     const int level = pieces16 ? 0 : level_arg; // (the piece form is level 0's: the compiler drops what only other levels need)
     const int L = P.levels;
@@ -272,13 +250,13 @@ __global__ __launch_bounds__(kCheckBlock) void k_check_labels(CheckLevels P, int
     const int8_t *lab = P.lab[level];
     const bool words = (P.word_mask >> level) & 1;
     unsigned cnt[4] = {0u, 0u, 0u, 0u};
-    unsigned long long key = kCheckNoKey;
+    unsigned long long key = kNoKey;
     // extents are powers of two (avs_create, avs_prepass_create): a run's place in the lattice is shifts and masks, no 64-bit division
     const int sy = __ffs(n1) - 1;
     if (pieces16) {
         const int px = n0 >> 4, sx = __ffs(px) - 1;
         const long long pieces = (long long)px * n1 * n2;
-        for (long long p = (long long)blockIdx.x * kCheckBlock + threadIdx.x; p < pieces; p += (long long)gridDim.x * kCheckBlock) {
+        for (long long p = (long long)blockIdx.x * kBlock + threadIdx.x; p < pieces; p += (long long)gridDim.x * kBlock) {
             const int ip = 16 * ((int)p & (px - 1)), j = (int)(p >> sx) & (n1 - 1), k = (int)(p >> (sx + sy));
             const uint4 cw = *reinterpret_cast<const uint4 *>(lab + ((size_t)n0 * ((size_t)j + (size_t)n1 * (size_t)k) + (size_t)ip));
             uint32_t w1a = 0u, w1b = 0u, w2 = 0u;
@@ -318,7 +296,7 @@ __global__ __launch_bounds__(kCheckBlock) void k_check_labels(CheckLevels P, int
     } else {
         const int rx = (n0 + 3) >> 2, sx = __ffs(rx) - 1;
         const long long runs = (long long)rx * n1 * n2;
-        for (long long r = (long long)blockIdx.x * kCheckBlock + threadIdx.x; r < runs; r += (long long)gridDim.x * kCheckBlock) {
+        for (long long r = (long long)blockIdx.x * kBlock + threadIdx.x; r < runs; r += (long long)gridDim.x * kBlock) {
             const int i0 = 4 * ((int)r & (rx - 1)), j = (int)(r >> sx) & (n1 - 1), k = (int)(r >> (sx + sy));
             const uint32_t c = check_run(lab, n0, n1, n2, words, i0, j, k);
             int a0[AVS_MAX_LEVELS] = {}, a1[AVS_MAX_LEVELS] = {};
@@ -334,7 +312,7 @@ __global__ __launch_bounds__(kCheckBlock) void k_check_labels(CheckLevels P, int
         }
     }
     const int rules[4] = {AVS_RULE_LABEL_VALUE, AVS_RULE_COLUMN, AVS_RULE_UP, AVS_RULE_ACTIVE};
-    check_commit(cnt, rules, key, raw);
+    raw_commit(cnt, rules, key, kCheckRawKey, raw);
 }
 
 // rules 4 .. 6 for entry `lin` = (i, j, k) of the face lattice of (level, axis) + the occurrence count of its id
@@ -343,11 +321,11 @@ __device__ __forceinline__ void check_face(const CheckLevels &P, int level, int 
 {
     if (v < AVS_OUTSIDE || v >= n_velocity) { // rule 4
         ++cnt[0];
-        key = min(key, check_key(AVS_RULE_INDEX_VALUE, level, axis, lin));
+        key = min(key, lattice_key(AVS_RULE_INDEX_VALUE, level, axis, lin));
     }
     if (level > 0 && (v == AVS_OUTSIDE || v == AVS_SOLIDBOUNDARY)) { // rule 6
         ++cnt[2];
-        key = min(key, check_key(AVS_RULE_SENTINEL, level, axis, lin));
+        key = min(key, lattice_key(AVS_RULE_SENTINEL, level, axis, lin));
     }
     if (v < 0) return;
     if (v < n_velocity) atomicAdd(occ + v, 1); // (in range: the only address a lattice value forms)
@@ -361,18 +339,18 @@ __device__ __forceinline__ void check_face(const CheckLevels &P, int level, int 
     }
     if (!ok) {
         ++cnt[1];
-        key = min(key, check_key(AVS_RULE_FACE, level, axis, lin));
+        key = min(key, lattice_key(AVS_RULE_FACE, level, axis, lin));
     }
 }
 
-__global__ __launch_bounds__(kCheckBlock) void k_check_index(CheckLevels P, int level, int axis, const int32_t *__restrict__ idx, int quads_ok,
+__global__ __launch_bounds__(kBlock) void k_check_index(CheckLevels P, int level, int axis, const int32_t *__restrict__ idx, int quads_ok,
                                                              int n_velocity, int32_t *__restrict__ occ, unsigned long long *__restrict__ raw)
 {
     const int f0 = (P.n[0] >> level) + (axis == 0 ? 1 : 0), f1 = (P.n[1] >> level) + (axis == 1 ? 1 : 0), f2 = (P.n[2] >> level) + (axis == 2 ? 1 : 0);
     const long long total = (long long)f0 * f1 * f2, quads = (total + 3) >> 2;
     unsigned cnt[3] = {0u, 0u, 0u};
-    unsigned long long key = kCheckNoKey;
-    for (long long q = (long long)blockIdx.x * kCheckBlock + threadIdx.x; q < quads; q += (long long)gridDim.x * kCheckBlock) {
+    unsigned long long key = kNoKey;
+    for (long long q = (long long)blockIdx.x * kBlock + threadIdx.x; q < quads; q += (long long)gridDim.x * kBlock) {
         const long long e0 = 4 * q;
         int v[4] = {AVS_UNASSIGNED, AVS_UNASSIGNED, AVS_UNASSIGNED, AVS_UNASSIGNED};
         const int nv = (int)min(4ll, total - e0);
@@ -411,35 +389,31 @@ __global__ __launch_bounds__(kCheckBlock) void k_check_index(CheckLevels P, int 
         }
     }
     const int rules[3] = {AVS_RULE_INDEX_VALUE, AVS_RULE_FACE, AVS_RULE_SENTINEL};
-    check_commit(cnt, rules, key, raw);
+    raw_commit(cnt, rules, key, kCheckRawKey, raw);
 }
 
-__global__ __launch_bounds__(kCheckBlock) void k_check_numbering(const int32_t *__restrict__ occ, int n_velocity, unsigned long long *__restrict__ raw)
+__global__ __launch_bounds__(kBlock) void k_index_numbering(const int32_t *__restrict__ occ, int n_ids, int rule, int key_word,
+                                                            unsigned long long *__restrict__ raw)
 {
-    unsigned cnt[1] = {0u};
-    unsigned long long key = kCheckNoKey;
-    for (long long id = (long long)blockIdx.x * kCheckBlock + threadIdx.x; id < n_velocity; id += (long long)gridDim.x * kCheckBlock)
+    unsigned cnt = 0u;
+    unsigned long long key = kNoKey;
+    for (long long id = (long long)blockIdx.x * kBlock + threadIdx.x; id < n_ids; id += (long long)gridDim.x * kBlock)
         if (occ[id] != 1) {
-            ++cnt[0];
-            key = min(key, check_key(AVS_RULE_NUMBERING, 0, 0, (unsigned long long)id));
+            ++cnt;
+            key = min(key, lattice_key(rule, 0, 0, (unsigned long long)id));
         }
-    const int rules[1] = {AVS_RULE_NUMBERING};
-    check_commit(cnt, rules, key, raw);
+    raw_add(cnt, rule, raw);
+    raw_min(key, key_word, raw);
 }
 
 static bool check_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-static unsigned check_grid(long long threads, int cap)
-{
-    const long long wgs = (threads + kCheckBlock - 1) / kCheckBlock, lim = cap > 0 ? cap : kCheckGrid;
-    return (unsigned)(wgs < 1 ? 1 : (wgs < lim ? wgs : lim));
-}
 
 // Shared implementation of avs_check_octree / avs_prepass_check_octree (rules and protocol: include/avs.h).  The caller has run
 // check_octree_args and the state checks of its object.
 avs_status check_octree(CheckScratch &S, const CheckSource &src, hipStream_t st, uint32_t what, avs_octree_check *report)
 {
     if (what == 0 || src.levels == 0) {
-        check_octree_hand_over(check_octree_passed(), report);
+        report_hand_over(check_octree_passed(), report);
         return AVS_OK;
     }
     CheckLevels P{};
@@ -459,16 +433,15 @@ avs_status check_octree(CheckScratch &S, const CheckSource &src, hipStream_t st,
     }
     const bool indices = (what & AVS_CHECK_VELOCITY_INDICES) != 0;
     AVS_REQUIRE(!indices || (src.n_velocity >= 0 && src.n_velocity < INT32_MAX), AVS_EINTERNAL, "octree check: velocity DOF count out of range");
-    AVS_TRY(S.raw.reserve(kCheckRawWords));
-    AVS_HIP(hipMemsetAsync(S.raw.p, 0, AVS_OCTREE_RULES * sizeof(unsigned long long), st));
-    AVS_HIP(hipMemsetAsync(S.raw.p + AVS_OCTREE_RULES, 0xff, sizeof(unsigned long long), st));
+    AVS_TRY(S.raw.begin(kCheckRawWords, kCheckRawKey, st));
     if (what & AVS_CHECK_LABELS)
         for (int l = 0; l < src.levels; ++l) {
             // level 0 in 16-byte pieces where its rows are whole pieces and the lattice starts on one
             const bool pieces16 = l == 0 && (src.n[0] & 15) == 0 && (reinterpret_cast<uintptr_t>(src.labels[0]) & 15u) == 0;
             const long long runs = (long long)(((src.n[0] >> l) + 3) >> 2) * (src.n[1] >> l) * (src.n[2] >> l);
-            if (pieces16) hipLaunchKernelGGL(k_check_labels<true>, dim3(check_grid(runs >> 2, src.grid_cap)), dim3(kCheckBlock), 0, st, P, l, S.raw.p);
-            else hipLaunchKernelGGL(k_check_labels<false>, dim3(check_grid(runs, src.grid_cap)), dim3(kCheckBlock), 0, st, P, l, S.raw.p);
+            const unsigned grid = report_grid(report_workgroups(pieces16 ? runs >> 2 : runs), src.grid_cap);
+            if (pieces16) hipLaunchKernelGGL(k_check_labels<true>, dim3(grid), dim3(kBlock), 0, st, P, l, S.raw.p);
+            else hipLaunchKernelGGL(k_check_labels<false>, dim3(grid), dim3(kBlock), 0, st, P, l, S.raw.p);
         }
     if (indices) {
         const int nvel = (int)src.n_velocity;
@@ -480,17 +453,16 @@ avs_status check_octree(CheckScratch &S, const CheckSource &src, hipStream_t st,
                 long long total = 1;
                 for (int d = 0; d < 3; ++d) total *= (src.n[d] >> l) + (d == a ? 1 : 0);
                 const int quads_ok = (reinterpret_cast<uintptr_t>(src.vidx[l][a]) & 15u) == 0 ? 1 : 0;
-                hipLaunchKernelGGL(k_check_index, dim3(check_grid((total + 3) >> 2, src.grid_cap)), dim3(kCheckBlock), 0, st, P, l, a, src.vidx[l][a],
-                                   quads_ok, nvel, S.occ.p, S.raw.p);
+                hipLaunchKernelGGL(k_check_index, dim3(report_grid(report_workgroups((total + 3) >> 2), src.grid_cap)), dim3(kBlock), 0, st, P, l, a,
+                                   src.vidx[l][a], quads_ok, nvel, S.occ.p, S.raw.p);
             }
         if (nvel > 0)
-            hipLaunchKernelGGL(k_check_numbering, dim3(check_grid(nvel, src.grid_cap)), dim3(kCheckBlock), 0, st, (const int32_t *)S.occ.p, nvel, S.raw.p);
+            hipLaunchKernelGGL(k_index_numbering, dim3(report_grid(report_workgroups(nvel), src.grid_cap)), dim3(kBlock), 0, st, (const int32_t *)S.occ.p, nvel,
+                               (int)AVS_RULE_NUMBERING, kCheckRawKey, S.raw.p);
     }
-    AVS_HIP(hipGetLastError());
     unsigned long long raw[kCheckRawWords];
-    AVS_HIP(hipMemcpyAsync(raw, S.raw.p, sizeof(raw), hipMemcpyDeviceToHost, st));
-    AVS_HIP(hipStreamSynchronize(st)); // the one wait: the report is on the host
-    check_octree_hand_over(check_octree_report(raw, what, src.n), report);
+    AVS_TRY(S.raw.read(raw, st)); // the one wait: the report is on the host
+    report_hand_over(check_octree_report(raw, what, src.n), report);
     return AVS_OK;
 }
 

@@ -21,68 +21,23 @@
 // No value read from the caller's arrays is used as an address without the range test of rule 1 (columns) or the verdict of rule 0
 // (pointers), and entry nnz and beyond is never read.  Counts are 64-bit: a lane counts in registers, a wave adds its lanes and issues
 // one atomic per rule it violated; the first violation is one atomicMin of a packed key (avs_csr_check_report.hpp) per violating wave;
-// the two maxima are atomicMax on the bit pattern of a non-negative double, which orders like the value: the same arrays give the same
-// report whatever the order of the waves.  Rule 7 is one subtraction and one comparison (-ffp-contract=off), integer work elsewhere.
+// the two maxima are atomicMax on the bit pattern of a non-negative double, which orders like the value (raw_commit and raw_max_bits,
+// avs_report_device.hpp): the same arrays give the same report whatever the order of the waves.  Rule 7 is one subtraction and one
+// comparison (-ffp-contract=off), integer work elsewhere.
 #include "avs_internal.hpp"
+#include "avs_report_device.hpp"
 
 namespace avs {
 
-static constexpr int kCsrCheckBlock = 256;
-static constexpr int kCsrCheckGrid = 2048; // persistent grids: eight workgroups per CU
-static constexpr int kCsrRowLanes = 16;    // lanes per row: four rows per wave
+static constexpr int kCsrRowLanes = 16; // lanes per row: four rows per wave
 
 __device__ __forceinline__ unsigned long long csr_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
-__device__ __forceinline__ bool csr_finite(double v) { return (csr_bits(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
 
-__device__ __forceinline__ unsigned long long csr_wave_sum(unsigned long long s)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += (unsigned long long)__shfl_xor((long long)s, o, 64);
-    return s;
-}
-__device__ __forceinline__ unsigned long long csr_wave_min(unsigned long long m)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = (unsigned long long)__shfl_xor((long long)m, o, 64);
-        m = other < m ? other : m;
-    }
-    return m;
-}
-__device__ __forceinline__ unsigned long long csr_wave_max(unsigned long long m)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = (unsigned long long)__shfl_xor((long long)m, o, 64);
-        m = other > m ? other : m;
-    }
-    return m;
-}
-// what a lane found, folded into the raw report: raw[word[r]] += c[r] (one atomic per wave and word), key = min(key, ...) (one per wave).
-// Every lane of the wave arrives here.
-template <int N>
-__device__ __forceinline__ void csr_commit(const unsigned (&c)[N], const int (&word)[N], unsigned long long key, unsigned long long *raw)
-{
-    const int lane = (int)threadIdx.x & 63;
-#pragma unroll
-    for (int r = 0; r < N; ++r) {
-        const unsigned long long s = csr_wave_sum(c[r]);
-        if (lane == 0 && s) atomicAdd(raw + word[r], s);
-    }
-    const unsigned long long m = csr_wave_min(key);
-    if (lane == 0 && m != kCsrNoKey) atomicMin(raw + kCsrRawKey, m);
-}
-__device__ __forceinline__ void csr_commit_max(unsigned long long v, int word, unsigned long long *raw)
-{
-    const unsigned long long m = csr_wave_max(v);
-    if (((int)threadIdx.x & 63) == 0 && m) atomicMax(raw + word, m);
-}
-
-__global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_row_ptr(const int32_t *__restrict__ rp, int n, int nnz, unsigned long long *__restrict__ raw)
+__global__ __launch_bounds__(kBlock) void k_csr_check_row_ptr(const int32_t *__restrict__ rp, int n, int nnz, unsigned long long *__restrict__ raw)
 {
     unsigned cnt[2] = {0u, 0u}; // rule 0, empty rows
-    unsigned long long key = kCsrNoKey, longest = 0ull;
-    for (long long i = (long long)blockIdx.x * kCsrCheckBlock + threadIdx.x; i <= n; i += (long long)gridDim.x * kCsrCheckBlock) {
+    unsigned long long key = kNoKey, longest = 0ull;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i <= n; i += (long long)gridDim.x * kBlock) {
         const int r = rp[i];
         bool bad = r < 0 || r > nnz || (i == 0 && r != 0) || (i == n && r != nnz);
         if (i < n) {
@@ -98,8 +53,8 @@ __global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_row_ptr(const int3
         }
     }
     const int words[2] = {AVS_CSR_RULE_ROW_PTR, kCsrRawEmptyRows};
-    csr_commit(cnt, words, key, raw);
-    csr_commit_max(longest, kCsrRawLongestRow, raw);
+    raw_commit(cnt, words, key, kCsrRawKey, raw);
+    raw_max_bits(longest, kCsrRawLongestRow, raw);
 }
 
 // The rows of a wave: group g of 16 lanes owns row base + g, base the same for the whole wave, so that every lane of a wave makes the same
@@ -114,13 +69,13 @@ __device__ __forceinline__ CsrRowWalk csr_row_walk()
     CsrRowWalk w;
     w.group = lane / kCsrRowLanes;
     w.sub = lane % kCsrRowLanes;
-    w.base = ((long long)blockIdx.x * kCsrCheckBlock + ((int)threadIdx.x & ~63)) / kCsrRowLanes;
-    w.stride = (long long)gridDim.x * kCsrCheckBlock / kCsrRowLanes;
+    w.base = ((long long)blockIdx.x * kBlock + ((int)threadIdx.x & ~63)) / kCsrRowLanes;
+    w.stride = (long long)gridDim.x * kBlock / kCsrRowLanes;
     return w;
 }
 
 // rules 1, 2, 4, 5 (need_order: rule 4 is asked for or the symmetry pass wants the ascending bytes)
-__global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_rows(const int32_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
+__global__ __launch_bounds__(kBlock) void k_csr_check_rows(const int32_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
                                                                    int n, uint32_t what, int write_ascending, uint8_t *__restrict__ ascending,
                                                                    unsigned long long *__restrict__ raw)
 {
@@ -128,7 +83,7 @@ __global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_rows(const int32_t
     const bool need_order = order || write_ascending != 0;
     const CsrRowWalk w = csr_row_walk();
     unsigned cnt[4] = {0u, 0u, 0u, 0u}; // rules 1, 2, 4, 5
-    unsigned long long key = kCsrNoKey;
+    unsigned long long key = kNoKey;
     for (long long base = w.base; base < n; base += w.stride) {
         const long long row = base + w.group;
         const bool live = row < n;
@@ -145,7 +100,7 @@ __global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_rows(const int32_t
                 ++cnt[0];
                 key = min(key, csr_check_key(AVS_CSR_RULE_COLUMN, (unsigned long long)k));
             }
-            if (values && !csr_finite(val[k])) { // rule 2
+            if (values && !finite_bits(val[k])) { // rule 2
                 ++cnt[1];
                 key = min(key, csr_check_key(AVS_CSR_RULE_VALUE, (unsigned long long)k));
             }
@@ -179,36 +134,36 @@ __global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_rows(const int32_t
         }
     }
     const int words[4] = {AVS_CSR_RULE_COLUMN, AVS_CSR_RULE_VALUE, AVS_CSR_RULE_ORDER, AVS_CSR_RULE_DIAGONAL};
-    csr_commit(cnt, words, key, raw);
+    raw_commit(cnt, words, key, kCsrRawKey, raw);
 }
 
 // rule 3 (b, x: either may be null, not both)
-__global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_vectors(const double *__restrict__ b, const double *__restrict__ x, int n,
+__global__ __launch_bounds__(kBlock) void k_csr_check_vectors(const double *__restrict__ b, const double *__restrict__ x, int n,
                                                                       unsigned long long *__restrict__ raw)
 {
     unsigned cnt[1] = {0u};
-    unsigned long long key = kCsrNoKey;
-    for (long long i = (long long)blockIdx.x * kCsrCheckBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kCsrCheckBlock) {
+    unsigned long long key = kNoKey;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
         bool bad = false;
-        if (b) bad = !csr_finite(b[i]);
-        if (x) bad = bad || !csr_finite(x[i]);
+        if (b) bad = !finite_bits(b[i]);
+        if (x) bad = bad || !finite_bits(x[i]);
         if (bad) {
             ++cnt[0];
             key = min(key, csr_check_key(AVS_CSR_RULE_VECTOR, (unsigned long long)i));
         }
     }
     const int words[1] = {AVS_CSR_RULE_VECTOR};
-    csr_commit(cnt, words, key, raw);
+    raw_commit(cnt, words, key, kCsrRawKey, raw);
 }
 
 // rules 6, 7 + asymmetric_entries, max_abs_value, max_abs_asymmetry
-__global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_symmetry(const int32_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
+__global__ __launch_bounds__(kBlock) void k_csr_check_symmetry(const int32_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
                                                                        int n, double tolerance, const uint8_t *__restrict__ ascending,
                                                                        unsigned long long *__restrict__ raw)
 {
     const CsrRowWalk w = csr_row_walk();
     unsigned cnt[3] = {0u, 0u, 0u}; // rule 6, rule 7, asymmetric pairs
-    unsigned long long key = kCsrNoKey, max_value = 0ull, max_asym = 0ull;
+    unsigned long long key = kNoKey, max_value = 0ull, max_asym = 0ull;
     for (long long base = w.base; base < n; base += w.stride) {
         const long long row = base + w.group;
         if (row >= n) continue; // (no group reduction in this pass: the lanes meet again at the commit)
@@ -217,7 +172,7 @@ __global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_symmetry(const int
         for (long long k = k0 + w.sub; k < k1; k += kCsrRowLanes) {
             const int j = col[k];
             const double v = val[k];
-            const bool finite = csr_finite(v);
+            const bool finite = finite_bits(v);
             if (finite) {
                 const unsigned long long a = csr_bits(v) & 0x7fffffffffffffffull; // |v|
                 max_value = a > max_value ? a : max_value;
@@ -246,7 +201,7 @@ __global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_symmetry(const int
                 continue;
             }
             const double vp = val[p];
-            if (!finite || !csr_finite(vp)) continue;
+            if (!finite || !finite_bits(vp)) continue;
             const double d = fabs(v - vp);
             if (v != vp) ++cnt[2];
             const unsigned long long db = csr_bits(d);
@@ -258,9 +213,9 @@ __global__ __launch_bounds__(kCsrCheckBlock) void k_csr_check_symmetry(const int
         }
     }
     const int words[3] = {AVS_CSR_RULE_PATTERN, AVS_CSR_RULE_SYMMETRY, kCsrRawAsymmetric};
-    csr_commit(cnt, words, key, raw);
-    csr_commit_max(max_value, kCsrRawMaxValue, raw);
-    csr_commit_max(max_asym, kCsrRawMaxAsymmetry, raw);
+    raw_commit(cnt, words, key, kCsrRawKey, raw);
+    raw_max_bits(max_value, kCsrRawMaxValue, raw);
+    raw_max_bits(max_asym, kCsrRawMaxAsymmetry, raw);
 }
 
 // the row that owns the first violating entry and its stored column (rules 3 and 5: the index is the row)
@@ -269,7 +224,7 @@ __global__ void k_csr_check_first(const int32_t *__restrict__ rp, const int32_t 
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     const unsigned long long key = raw[kCsrRawKey];
     long long row = -1, c = -1;
-    if (key != kCsrNoKey) {
+    if (key != kNoKey) {
         const int rule = csr_check_key_rule(key);
         const long long index = csr_check_key_index(key);
         if (rule == AVS_CSR_RULE_VECTOR || rule == AVS_CSR_RULE_DIAGONAL) {
@@ -289,44 +244,32 @@ __global__ void k_csr_check_first(const int32_t *__restrict__ rp, const int32_t 
     raw[kCsrRawFirstCol] = (unsigned long long)c;
 }
 
-static unsigned csr_check_grid(long long threads)
-{
-    const long long wgs = (threads + kCsrCheckBlock - 1) / kCsrCheckBlock;
-    return (unsigned)(wgs < 1 ? 1 : (wgs < kCsrCheckGrid ? wgs : kCsrCheckGrid));
-}
-
 // Shared implementation of avs_check_csr / avs_check_system (rules and protocol: include/avs.h).  The caller has run check_csr_args and
 // the pointer / state checks of its entry; the arrays of src lie on the device of st.
 avs_status check_csr(CsrCheckScratch &S, const CsrCheckSource &src, hipStream_t st, uint32_t what, double symmetry_tolerance, avs_csr_check *report)
 {
     const int n = (int)src.n, nnz = (int)src.nnz;
     const bool vectors = src.b || src.x, symmetry = (what & AVS_CSR_CHECK_SYMMETRY) != 0;
-    AVS_TRY(S.raw.reserve(kCsrRawWords));
     unsigned long long raw[kCsrRawWords];
-    AVS_HIP(hipMemsetAsync(S.raw.p, 0, kCsrRawWords * sizeof(unsigned long long), st));
-    AVS_HIP(hipMemsetAsync(S.raw.p + kCsrRawKey, 0xff, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_csr_check_row_ptr, dim3(csr_check_grid((long long)n + 1)), dim3(kCsrCheckBlock), 0, st, src.row_ptr, n, nnz, S.raw.p);
-    AVS_HIP(hipGetLastError());
-    AVS_HIP(hipMemcpyAsync(raw, S.raw.p, sizeof(raw), hipMemcpyDeviceToHost, st));
-    AVS_HIP(hipStreamSynchronize(st)); // rule 0 decides whether the rows may be walked
+    AVS_TRY(S.raw.begin(kCsrRawWords, kCsrRawKey, st));
+    hipLaunchKernelGGL(k_csr_check_row_ptr, dim3(report_grid(report_workgroups((long long)n + 1), 0)), dim3(kBlock), 0, st, src.row_ptr, n, nnz, S.raw.p);
+    AVS_TRY(S.raw.read(raw, st)); // rule 0 decides whether the rows may be walked
     if (raw[AVS_CSR_RULE_ROW_PTR] != 0 || n == 0) {
-        check_csr_hand_over(check_csr_report(raw, what, vectors, false), report);
+        report_hand_over(check_csr_report(raw, what, vectors, false), report);
         return AVS_OK;
     }
     if (symmetry) AVS_TRY(S.ascending.reserve((size_t)n));
-    const unsigned row_grid = csr_check_grid((long long)n * kCsrRowLanes);
-    hipLaunchKernelGGL(k_csr_check_rows, dim3(row_grid), dim3(kCsrCheckBlock), 0, st, src.row_ptr, src.col, src.val, n, what, symmetry ? 1 : 0,
+    const unsigned row_grid = report_grid(report_workgroups((long long)n * kCsrRowLanes), 0);
+    hipLaunchKernelGGL(k_csr_check_rows, dim3(row_grid), dim3(kBlock), 0, st, src.row_ptr, src.col, src.val, n, what, symmetry ? 1 : 0,
                        symmetry ? S.ascending.p : (uint8_t *)nullptr, S.raw.p);
     if ((what & AVS_CSR_CHECK_VALUES) && vectors)
-        hipLaunchKernelGGL(k_csr_check_vectors, dim3(csr_check_grid(n)), dim3(kCsrCheckBlock), 0, st, src.b, src.x, n, S.raw.p);
+        hipLaunchKernelGGL(k_csr_check_vectors, dim3(report_grid(report_workgroups(n), 0)), dim3(kBlock), 0, st, src.b, src.x, n, S.raw.p);
     if (symmetry)
-        hipLaunchKernelGGL(k_csr_check_symmetry, dim3(row_grid), dim3(kCsrCheckBlock), 0, st, src.row_ptr, src.col, src.val, n, symmetry_tolerance,
+        hipLaunchKernelGGL(k_csr_check_symmetry, dim3(row_grid), dim3(kBlock), 0, st, src.row_ptr, src.col, src.val, n, symmetry_tolerance,
                            (const uint8_t *)S.ascending.p, S.raw.p);
     hipLaunchKernelGGL(k_csr_check_first, dim3(1), dim3(64), 0, st, src.row_ptr, src.col, n, S.raw.p);
-    AVS_HIP(hipGetLastError());
-    AVS_HIP(hipMemcpyAsync(raw, S.raw.p, sizeof(raw), hipMemcpyDeviceToHost, st));
-    AVS_HIP(hipStreamSynchronize(st)); // the report is on the host
-    check_csr_hand_over(check_csr_report(raw, what, vectors, true), report);
+    AVS_TRY(S.raw.read(raw, st)); // the report is on the host
+    report_hand_over(check_csr_report(raw, what, vectors, true), report);
     return AVS_OK;
 }
 

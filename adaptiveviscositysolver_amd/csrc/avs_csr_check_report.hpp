@@ -1,18 +1,16 @@
 // avs_csr_check_report.hpp -- host side of avs_check_csr / avs_check_system that needs no HIP call: argument checks, the packed key of the
-// first violation, the layout of the raw report the kernels leave behind, and the report that goes back to the caller.  Plain C++ over
-// include/avs.h, so that a stand-alone program can run it under the host sanitizers (tests/csr_check_report_main.cpp).
+// first violation, the layout of the raw report the kernels leave behind, and the report that goes back to the caller (the hand-over:
+// avs_report.hpp).  Plain C++ over include/avs.h, so that a stand-alone program can run it under the host sanitizers
+// (tests/csr_check_report_main.cpp).
 #pragma once
 
 #include <cmath>
-#include <cstddef>
-#include <cstdint>
-#include <cstring>
 
-#include "avs.h"
+#include "avs_report.hpp"
 
 namespace avs {
 
-// What the kernels leave behind, in 64-bit words: a count per rule, the smallest key of a violating position (all ones: none), the
+// What the kernels leave behind, in 64-bit words: a count per rule, the smallest key of a violating position (kNoKey: none), the
 // measurements (the two maxima as the bit patterns of non-negative doubles: their order is the order of the values), and -- written by
 // k_csr_check_first once every pass has run -- the row and the stored column of the first violation (as signed 64-bit values).
 enum {
@@ -26,7 +24,6 @@ enum {
     kCsrRawFirstCol,
     kCsrRawWords
 };
-constexpr unsigned long long kCsrNoKey = ~0ull;
 // key = rule | index (a row_ptr index, an entry or a row: below 2^32): ascending keys are the order (rule, index) of the header
 constexpr int kCsrKeyIndexBits = 32;
 static_assert(AVS_CSR_RULES <= 8, "the rule above a 32-bit index");
@@ -55,7 +52,7 @@ inline avs_status check_csr_args(int64_t n, int64_t nnz, uint32_t what, double s
         *why = "csr check: unknown bits in `what`";
         return AVS_EINVAL;
     }
-    if (report->struct_size < (int32_t)(offsetof(avs_csr_check, passed) + sizeof(int32_t)) || report->struct_size > 4096) {
+    if (!report_size_ok(report, offsetof(avs_csr_check, passed) + sizeof(int32_t))) {
         *why = "avs_csr_check.struct_size must be set to sizeof(avs_csr_check) before the call";
         return AVS_EINVAL;
     }
@@ -109,21 +106,13 @@ inline avs_csr_check check_csr_report(const unsigned long long *raw, uint32_t wh
         memcpy(&r.max_abs_asymmetry, &raw[kCsrRawMaxAsymmetry], sizeof(double));
     }
     const unsigned long long key = raw[kCsrRawKey];
-    if (!any || key == kCsrNoKey) return r;
+    if (!any || key == kNoKey) return r;
     r.passed = 0;
     r.first_rule = csr_check_key_rule(key);
     r.first_index = csr_check_key_index(key);
     r.first_row = (int32_t)(int64_t)raw[kCsrRawFirstRow];
     r.first_col = (int32_t)(int64_t)raw[kCsrRawFirstCol];
     return r;
-}
-
-// only the bytes the caller's header knows are written (struct_size is IN, as in avs_matrix_format)
-inline void check_csr_hand_over(const avs_csr_check &full, avs_csr_check *out)
-{
-    const int32_t size = out->struct_size;
-    memcpy(out, &full, (size_t)size < sizeof(full) ? (size_t)size : sizeof(full));
-    out->struct_size = size;
 }
 
 } // namespace avs

@@ -112,7 +112,7 @@ struct Options {
     int fused_timeout_ms = 2000; // AVS_PCG_FUSED_TIMEOUT_MS: bound of that barrier's wait
     int post_dof_sample = -1;    // AVS_POST_DOF_SAMPLE: the transfer samples its nodes from the velocity DOFs (1) / by a sweep over the node lattices (0);
                                  // -1: from the DOFs when the level-0 node lattice has more than 32 x as many nodes as there are DOFs
-    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) and of the octree, stress index and solution checks and of the spectrum estimate (avs_check.hip, avs_stress_check.hip, avs_solution_check.hip, avs_spectrum.hip) at that many workgroups (tests: the walks wrap on small lattices)
+    int cells_grid_cap = 0;      // AVS_CELLS_GRID_CAP: > 0 caps the persistent grids of the octree cell export (avs_cells.hip) and of the octree, stress index and solution checks and of the spectrum estimate (avs_check.hip, avs_stress_check.hip, avs_solution_check.hip, avs_spectrum.hip: report_grid of avs_report_device.hpp) at that many workgroups (tests: the walks wrap on small lattices)
     int prepass_temporal = 1;    // AVS_PREPASS_TEMPORAL: the device pre-pass skips what its allocations already hold from their last filling (0: every run fills everything)
     int f32_vectors = -1;        // AVS_F32_VECTORS: AVS_PRECISION_F32 contexts iterate on float vectors with float scalars (what Eigen's float CG does):
                                  // 1 always, 0 never (fp64 iteration on the float system), -1 auto: where the system is too large for the
@@ -197,6 +197,28 @@ struct DevBuf {
             return AVS_ENOMEM;
         }
         n = count;
+        return AVS_OK;
+    }
+};
+
+// The raw report of a device diagnostic: 64-bit words its kernels fold into with integer atomics, kept across calls, read back whole.
+struct RawReport : DevBuf<unsigned long long> {
+    int words = 0;
+    // every word 0, but key_word (-1: none), which holds all ones: above every key of a first violation
+    avs_status begin(int count, int key_word, hipStream_t st)
+    {
+        AVS_TRY(reserve((size_t)count));
+        words = count;
+        AVS_HIP(hipMemsetAsync(p, 0, (size_t)count * sizeof(unsigned long long), st));
+        if (key_word >= 0) AVS_HIP(hipMemsetAsync(p + key_word, 0xff, sizeof(unsigned long long), st));
+        return AVS_OK;
+    }
+    // launch errors, the copy of the words begin() asked for, and the wait for it
+    avs_status read(unsigned long long *host, hipStream_t st)
+    {
+        AVS_HIP(hipGetLastError());
+        AVS_HIP(hipMemcpyAsync(host, p, (size_t)words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        AVS_HIP(hipStreamSynchronize(st));
         return AVS_OK;
     }
 };
@@ -623,7 +645,7 @@ avs_status export_octree_cells(CellsScratch &S, const CellsSource &src, hipStrea
 // one occurrence counter per velocity id and the raw report (a count per rule + the key of the first violation).
 struct CheckScratch {
     DevBuf<int32_t> occ;
-    DevBuf<unsigned long long> raw;
+    RawReport raw;
 };
 struct CheckSource {
     const int8_t *labels[AVS_MAX_LEVELS];
@@ -639,7 +661,7 @@ avs_status check_octree(CheckScratch &S, const CheckSource &src, hipStream_t st,
 // active counts).
 struct StressCheckScratch {
     DevBuf<int32_t> occ_edge, occ_center;
-    DevBuf<unsigned long long> raw;
+    RawReport raw;
 };
 struct StressCheckSource {
     const int8_t *labels[AVS_MAX_LEVELS];
@@ -656,14 +678,14 @@ avs_status check_stress_indices(StressCheckScratch &S, const StressCheckSource &
 // staging of a host-bound field.
 struct StrainScratch {
     DevBuf<double> edge, center, cell, partial;
-    DevBuf<unsigned long long> raw;
+    RawReport raw;
     DevBuf<float> field;
 };
 
 // CSR check (avs_csr_check.hip): avs_check_csr / avs_check_system over one implementation.  Scratch: the raw report and one byte per row
 // (1: the row's columns are strictly ascending, so the partner search of the symmetry pass may bisect it).
 struct CsrCheckScratch {
-    DevBuf<unsigned long long> raw;
+    RawReport raw;
     DevBuf<uint8_t> ascending;
 };
 struct CsrCheckSource { // device pointers; b, x: may be null
@@ -677,7 +699,8 @@ avs_status check_csr(CsrCheckScratch &S, const CsrCheckSource &src, hipStream_t 
 // calls: five partial sums per 256 rows, the arg-max pair of every wave of the grid, the raw report, and the staging of a host-bound residual.
 struct SolutionCheckScratch {
     DevBuf<double> partial, residual;
-    DevBuf<unsigned long long> wave_bits, raw;
+    DevBuf<unsigned long long> wave_bits;
+    RawReport raw;
     DevBuf<unsigned> wave_row;
 };
 
@@ -685,7 +708,7 @@ struct SolutionCheckScratch {
 // calls: five n-vectors (the scale s, u = s o v_j, two Lanczos vectors that change roles, w), one partial sum per 256 rows, the raw words.
 struct SpectrumScratch {
     DevBuf<double> s, u, va, vb, w, partial;
-    DevBuf<unsigned long long> raw;
+    RawReport raw;
 };
 
 // avs_desc::precision == AVS_PRECISION_F32: the solution as the reference's Eigen::VectorXf holds it (avs_api.hip)

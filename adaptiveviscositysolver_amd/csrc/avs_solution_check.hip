@@ -3,13 +3,10 @@
 // implementation.  Every convention is stated in include/avs.h (avs_check_solution); tests/solution_check_model.py restates them in NumPy.
 //
 //   k_solution_check  the stream product of avs_spmv.hip with the report behind it.  A 256-thread workgroup owns a chunk of 256 consecutive
-//                     rows, persistent workgroups walk the chunks.  Phase 1 streams the chunk's (val, col) pairs fully coalesced with
-//                     non-temporal loads, four independent trips in flight per lane (the matrix is read once and must not evict x from
-//                     L2), gathers x[col] with plain loads and parks the products in LDS tiles of kStreamCap; phase 2: one lane per row
-//                     adds its segment of the tile left to right, y_i = y_i + val[k] * x[col[k]] in stored order, across as many tiles
-//                     as the row has (the order of k_spmv_stream and of the oracle: r is defined bit for bit).  Then r_i = b_i - y_i, the
-//                     row's five terms, and one partial sum per term and CHUNK: wave sums without the LDS crossbar, the four waves
-//                     added in order by thread 0.
+//                     rows, persistent workgroups walk the chunks: y_i = y_i + val[k] * x[col[k]] in stored order (chunk_stream_product,
+//                     avs_report_device.hpp: the order of k_spmv_stream and of the oracle, r is defined bit for bit).  Then
+//                     r_i = b_i - y_i, the row's five terms, and one partial sum per term and CHUNK: wave sums without the LDS crossbar,
+//                     the four waves added in order by thread 0.
 //   k_solution_fold   workgroups 0 .. 4 fold the partial sums of one term each in a fixed order (thread t adds the chunks t, t + 256, ...,
 //                     then the block sum of avs_wave.hpp); workgroup 5 picks the largest |r_i| and the smallest row that attains it from
 //                     the pairs the waves of the grid left behind.
@@ -17,41 +14,16 @@
 // Bytes per call: 12 nnz + 4 (n + 1) + 24 n (b, x, x0; x is gathered out of L2) + 8 n for the residual: HBM-bound, the matrix stream is
 // nine tenths of it.  A partial sum belongs to a chunk, not to a workgroup, so the sums do not depend on the grid (Options::cells_grid_cap
 // caps it for the tests).  Counters are 64-bit integers and the maxima the bit patterns of non-negative doubles: a lane accumulates in
-// registers over its chunks, a wave folds its lanes and issues one integer atomic per word it has something for.  The arg-max is a pair
+// registers over its chunks, a wave folds its lanes and issues one integer atomic per word it has something for (avs_report_device.hpp).  The arg-max is a pair
 // (bits of |r_i|, row) under a total order (sol_check_better): lane, wave and fold keep the better pair, so the answer is the same
 // whoever compares first.  No floating atomics: the same arrays give the same bytes.  No index is read from a caller's array before
 // rules 0 and 1 of avs_check_csr have passed on it (check_csr, what = 0); the context's own arrays are the library's.
 #include "avs_internal.hpp"
+#include "avs_report_device.hpp"
 #include "avs_solution_check_report.hpp"
-#include "avs_wave.hpp"
 
 namespace avs {
 
-static constexpr int kSolGrid = 2048; // persistent grid: eight workgroups per CU
-
-__device__ __forceinline__ bool sol_finite(double v)
-{
-    return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
-// raw[word] += the wave's sum of v
-__device__ __forceinline__ void sol_count(unsigned long long v, int word, unsigned long long *raw)
-{
-    unsigned long long s = v;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += (unsigned long long)__shfl_xor((long long)s, o, 64);
-    if (((int)threadIdx.x & 63) == 0 && s) atomicAdd(raw + word, s);
-}
-// raw[word] = max(raw[word], the wave's largest v); v >= 0, not NaN: the bit patterns order as the values
-__device__ __forceinline__ void sol_max(double v, int word, unsigned long long *raw)
-{
-    unsigned long long m = (unsigned long long)__double_as_longlong(v);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = (unsigned long long)__shfl_xor((long long)m, o, 64);
-        m = other > m ? other : m;
-    }
-    if (((int)threadIdx.x & 63) == 0 && m) atomicMax(raw + word, m);
-}
 // the best pair of the wave, in every lane
 __device__ __forceinline__ void sol_wave_best(unsigned long long &bits, unsigned &row)
 {
@@ -83,43 +55,13 @@ __global__ __launch_bounds__(kBlock) void k_solution_check(const int32_t *__rest
     int parity = 0;
     for (long long chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x, parity ^= 1) { // (the same trips for every thread of the workgroup)
         const long long row0 = chunk * kBlock, row = row0 + tid;
-        const long long rlast = row0 + kBlock < n ? row0 + kBlock : n;
-        const long long s_blk = rp[row0], e_blk = rp[rlast];
-        long long rs = 0, re = 0;
-        if (row < n) {
-            rs = rp[row];
-            re = rp[row + 1];
-        }
-        double y = 0.;
-        for (long long ts = s_blk; ts < e_blk; ts += kStreamCap) {
-            const long long te = ts + kStreamCap < e_blk ? ts + kStreamCap : e_blk;
-            // phase 1: coalesced stream of (val, col), gather x, products to LDS; four independent loads per lane in flight per trip
-            long long k = ts + tid;
-            for (; k + 3 * kBlock < te; k += 4 * kBlock) {
-                const double v0 = stream_load<true>(val + k), v1 = stream_load<true>(val + k + kBlock), v2 = stream_load<true>(val + k + 2 * kBlock),
-                             v3 = stream_load<true>(val + k + 3 * kBlock);
-                const int c0 = stream_load<true>(col + k), c1 = stream_load<true>(col + k + kBlock), c2 = stream_load<true>(col + k + 2 * kBlock),
-                          c3 = stream_load<true>(col + k + 3 * kBlock);
-                const double x0v = x[c0], x1v = x[c1], x2v = x[c2], x3v = x[c3];
-                const int o = (int)(k - ts);
-                prod[o] = v0 * x0v;
-                prod[o + kBlock] = v1 * x1v;
-                prod[o + 2 * kBlock] = v2 * x2v;
-                prod[o + 3 * kBlock] = v3 * x3v;
-            }
-            for (; k < te; k += kBlock) prod[(int)(k - ts)] = stream_load<true>(val + k) * x[stream_load<true>(col + k)];
-            __syncthreads();
-            // phase 2: each row adds its part of the tile, left to right
-            const long long a = rs > ts ? rs : ts, e = re < te ? re : te;
-            for (long long j = a; j < e; ++j) y = y + prod[(int)(j - ts)];
-            __syncthreads();
-        }
+        const double y = chunk_stream_product(rp, col, val, x, n, row0, prod);
         double term[kSolSums] = {0., 0., 0., 0., 0.};
         if (row < n) {
             const double xi = x[row], bi = b[row];
             const double r = bi - y;
             if (residual) residual[row] = r;
-            const bool fx = sol_finite(xi), fb = sol_finite(bi), fr = sol_finite(r);
+            const bool fx = finite_bits(xi), fb = finite_bits(bi), fr = finite_bits(r);
             nonfinite_x += fx ? 0u : 1u;
             nonfinite_b += fb ? 0u : 1u;
             nonfinite_r += fr ? 0u : 1u;
@@ -137,7 +79,7 @@ __global__ __launch_bounds__(kBlock) void k_solution_check(const int32_t *__rest
                 }
                 if (x0) {
                     const double gi = x0[row];
-                    if (sol_finite(gi)) {
+                    if (finite_bits(gi)) {
                         const double d = xi - gi;
                         term[kSolSumUpdate] = d * d;
                         max_update = fmax(max_update, fabs(d));
@@ -155,12 +97,12 @@ __global__ __launch_bounds__(kBlock) void k_solution_check(const int32_t *__rest
         if (tid < kSolSums)
             partial[(long long)tid * chunks + chunk] = ((red[parity][tid][0] + red[parity][tid][1]) + red[parity][tid][2]) + red[parity][tid][3];
     }
-    sol_count(nonfinite_x, kSolRawNonfiniteX, raw);
-    sol_count(nonfinite_b, kSolRawNonfiniteB, raw);
-    sol_count(nonfinite_r, kSolRawNonfiniteResidual, raw);
-    sol_count(summed, kSolRawRowsSummed, raw);
-    sol_max(max_x, kSolRawMaxX, raw);
-    sol_max(max_update, kSolRawMaxUpdate, raw);
+    raw_add(nonfinite_x, kSolRawNonfiniteX, raw);
+    raw_add(nonfinite_b, kSolRawNonfiniteB, raw);
+    raw_add(nonfinite_r, kSolRawNonfiniteResidual, raw);
+    raw_add(summed, kSolRawRowsSummed, raw);
+    raw_max_bits(max_x, kSolRawMaxX, raw);
+    raw_max_bits(max_update, kSolRawMaxUpdate, raw);
     sol_wave_best(best_bits, best_row);
     if (lane == 0) {
         wave_bits[blockIdx.x * (kBlock / 64) + wave] = best_bits;
@@ -219,12 +161,11 @@ static avs_status check_solution(SolutionCheckScratch &S, const SolutionCheckSou
 {
     const int n = (int)src.n;
     if (n == 0) {
-        if (report) check_solution_hand_over(check_solution_report(nullptr, which, src.n, src.nnz, true, claim), report);
+        if (report) report_hand_over(check_solution_report(nullptr, which, src.n, src.nnz, true, claim), report);
         return AVS_OK;
     }
     const long long chunks = ((long long)n + kBlock - 1) / kBlock;
-    const long long lim = grid_cap > 0 ? grid_cap : kSolGrid;
-    const unsigned grid = (unsigned)(chunks < lim ? chunks : lim);
+    const unsigned grid = report_grid(chunks, grid_cap);
     const int waves = (int)grid * (kBlock / 64);
     const bool direct = where == AVS_MEM_DEVICE;
     double *d_res = residual;
@@ -235,8 +176,7 @@ static avs_status check_solution(SolutionCheckScratch &S, const SolutionCheckSou
     AVS_TRY(S.partial.reserve((size_t)(kSolSums * chunks)));
     AVS_TRY(S.wave_bits.reserve((size_t)waves));
     AVS_TRY(S.wave_row.reserve((size_t)waves));
-    AVS_TRY(S.raw.reserve(kSolRawWords));
-    AVS_HIP(hipMemsetAsync(S.raw.p, 0, kSolRawWords * sizeof(unsigned long long), st));
+    AVS_TRY(S.raw.begin(kSolRawWords, -1, st));
     hipLaunchKernelGGL(k_solution_check, dim3(grid), dim3(kBlock), 0, st, src.row_ptr, src.col, src.val, src.b, src.x, src.x0, n, chunks, d_res,
                        S.partial.p, S.wave_bits.p, S.wave_row.p, S.raw.p);
     if (report)
@@ -245,9 +185,9 @@ static avs_status check_solution(SolutionCheckScratch &S, const SolutionCheckSou
     AVS_HIP(hipGetLastError());
     if (residual && !direct) AVS_HIP(copy_out(residual, d_res, (size_t)n * sizeof(double), where, st));
     unsigned long long raw[kSolRawWords];
-    if (report) AVS_HIP(hipMemcpyAsync(raw, S.raw.p, sizeof(raw), hipMemcpyDeviceToHost, st));
-    if (report || !direct) AVS_HIP(hipStreamSynchronize(st));
-    if (report) check_solution_hand_over(check_solution_report(raw, which, src.n, src.nnz, true, claim), report);
+    if (report) AVS_TRY(S.raw.read(raw, st));
+    else if (!direct) AVS_HIP(hipStreamSynchronize(st));
+    if (report) report_hand_over(check_solution_report(raw, which, src.n, src.nnz, true, claim), report);
     return AVS_OK;
 }
 
@@ -346,7 +286,7 @@ extern "C" avs_status avs_check_csr_solution(int64_t n, int64_t nnz, const int32
             const CsrCheckSource csr{n, nnz, src.row_ptr, src.col, src.val, nullptr, nullptr};
             if ((rc = check_csr(rules, csr, s, 0u, 0., &rep01)) != AVS_OK) break;
             if (rep01.violations[AVS_CSR_RULE_ROW_PTR] != 0 || rep01.violations[AVS_CSR_RULE_COLUMN] != 0) {
-                check_solution_hand_over(check_solution_report(nullptr, AVS_CHECK_OF_SOLUTION, n, nnz, false, SolutionClaim()), report);
+                report_hand_over(check_solution_report(nullptr, AVS_CHECK_OF_SOLUTION, n, nnz, false, SolutionClaim()), report);
                 break;
             }
             rc = check_solution(scratch, src, s, AVS_CHECK_OF_SOLUTION, cur_opt().cells_grid_cap, SolutionClaim(), residual, where, report);

@@ -1,15 +1,13 @@
 // avs_solution_check_report.hpp -- host side of avs_check_solution / avs_check_csr_solution that needs no HIP call: argument checks, the
-// order of the arg-max pairs, the layout of the raw report the kernels leave behind, and the report that goes back to the caller.  Plain
-// C++ over include/avs.h, so that a stand-alone program can run it under the host sanitizers (tests/solution_check_report_main.cpp).
+// order of the arg-max pairs, the layout of the raw report the kernels leave behind, and the report that goes back to the caller (the
+// hand-over: avs_report.hpp).  Plain C++ over include/avs.h, so that a stand-alone program can run it under the host sanitizers
+// (tests/solution_check_report_main.cpp).
 #pragma once
 
 #include <cmath>
-#include <cstddef>
-#include <cstdint>
-#include <cstring>
 #include <limits>
 
-#include "avs.h"
+#include "avs_report.hpp"
 
 namespace avs {
 
@@ -62,7 +60,7 @@ inline avs_status check_solution_args(int32_t which, int where, const double *re
         *why = report_required ? "solution check: report must not be null" : "solution check: report and residual are both null";
         return AVS_EINVAL;
     }
-    if (report && (report->struct_size < (int32_t)(offsetof(avs_solution_check, evaluated) + sizeof(int32_t)) || report->struct_size > 4096)) {
+    if (report && !report_size_ok(report, offsetof(avs_solution_check, evaluated) + sizeof(int32_t))) {
         *why = "avs_solution_check.struct_size must be set to sizeof(avs_solution_check) before the call";
         return AVS_EINVAL;
     }
@@ -128,14 +126,6 @@ inline avs_solution_check check_solution_report(const unsigned long long *raw, i
         r.max_residual_row = (int64_t)row;
     }
     return r;
-}
-
-// only the bytes the caller's header knows are written (struct_size is IN, as in avs_csr_check)
-inline void check_solution_hand_over(const avs_solution_check &full, avs_solution_check *out)
-{
-    const int32_t size = out->struct_size;
-    memcpy(out, &full, (size_t)size < sizeof(full) ? (size_t)size : sizeof(full));
-    out->struct_size = size;
 }
 
 } // namespace avs

@@ -7,12 +7,9 @@
 //   k_spectrum_gershgorin  one lane per row: g_i = g_i + |val[k]| * (s_i * s_col[k]) in stored order; the maximum as a bit pattern
 //   k_spectrum_start       the start vector into w and the partial sums of w_i^2: s o (b - A x0) by the stream product, the hash, or the
 //                          caller's vector
-//   k_spectrum_product     the stream product of k_solution_check on u = s o v_j: a 256-thread workgroup owns a chunk of 256
-//                          consecutive rows, persistent workgroups walk the chunks.  Phase 1 streams the chunk's (val, col) pairs fully
-//                          coalesced with non-temporal loads, four independent trips in flight per lane, gathers u[col] and parks the
-//                          products in LDS tiles of kStreamCap; phase 2: one lane per row adds its segment of the tile left to right
-//                          across as many tiles as the row has.  Then t_i = s_i * y_i - beta[j] * v_{j-1,i} into w and the chunk's
-//                          partial sum of v_{j,i} t_i.
+//   k_spectrum_product     the stream product of k_solution_check on u = s o v_j (chunk_stream_product, avs_report_device.hpp): a
+//                          256-thread workgroup owns a chunk of 256 consecutive rows, persistent workgroups walk the chunks.  Then
+//                          t_i = s_i * y_i - beta[j] * v_{j-1,i} into w and the chunk's partial sum of v_{j,i} t_i (chunk_partial_sum).
 //   k_spectrum_orthogonalise  w_i = t_i - alpha[j] * v_{j,i} in place and the chunk's partial sum of w_i^2
 //   k_spectrum_fold        one workgroup folds the partial sums in a fixed order (thread t adds the chunks t, t + 256, ..., then the
 //                          block sum of avs_wave.hpp) and writes beta[0], alpha[j] or beta[j + 1]; behind beta it decides the stop
@@ -25,17 +22,11 @@
 // to a workgroup, so the sums do not depend on the grid (Options::cells_grid_cap caps it for the tests).  No floating atomics, no
 // hipGraph, no cooperative launch.  No index is read from a caller's array before rules 0 and 1 of avs_check_csr have passed on it.
 #include "avs_internal.hpp"
+#include "avs_report_device.hpp"
 #include "avs_spectrum_report.hpp"
-#include "avs_wave.hpp"
 
 namespace avs {
 
-static constexpr int kSpecGrid = 2048; // persistent grid: eight workgroups per CU
-
-__device__ __forceinline__ bool spec_finite(double v)
-{
-    return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
 // nothing behind a bad diagonal, a useless start vector, a breakdown or a non-finite step: the same answer in every thread of the grid
 __device__ __forceinline__ bool spec_halted(const unsigned long long *raw)
 {
@@ -59,15 +50,13 @@ __global__ __launch_bounds__(kBlock) void k_spectrum_scale(const int32_t *__rest
                     d = val[k];
                     have = true;
                 }
-            const bool ok = have && d > 0. && spec_finite(d);
+            const bool ok = have && d > 0. && finite_bits(d);
             si = ok ? 1.0 / sqrt(d) : 0.;
             bad += ok ? 0ull : 1ull;
         }
         s[row] = si;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bad += (unsigned long long)__shfl_xor((long long)bad, o, 64);
-    if (((int)threadIdx.x & 63) == 0 && bad) atomicAdd(raw + kSpecRawBadDiagonal, bad);
+    raw_add(bad, kSpecRawBadDiagonal, raw);
 }
 
 __global__ __launch_bounds__(kBlock) void k_spectrum_gershgorin(const int32_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
@@ -84,62 +73,7 @@ __global__ __launch_bounds__(kBlock) void k_spectrum_gershgorin(const int32_t *_
         const unsigned long long bits = (unsigned long long)__double_as_longlong(g); // g >= 0: the bit patterns order as the values
         m = bits > m ? bits : m;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = (unsigned long long)__shfl_xor((long long)m, o, 64);
-        m = other > m ? other : m;
-    }
-    if (((int)threadIdx.x & 63) == 0 && m) atomicMax(raw + kSpecRawGershgorin, m);
-}
-
-// y of row row0 + threadIdx.x of the chunk that starts at row0 (0 behind row n); every thread of the workgroup calls it.  prod: kStreamCap.
-__device__ __forceinline__ double spec_chunk_product(const int32_t *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
-                                                     const double *__restrict__ x, int n, long long row0, double *prod)
-{
-    const int tid = threadIdx.x;
-    const long long row = row0 + tid;
-    const long long rlast = row0 + kBlock < n ? row0 + kBlock : n;
-    const long long s_blk = rp[row0], e_blk = rp[rlast];
-    long long rs = 0, re = 0;
-    if (row < n) {
-        rs = rp[row];
-        re = rp[row + 1];
-    }
-    double y = 0.;
-    for (long long ts = s_blk; ts < e_blk; ts += kStreamCap) {
-        const long long te = ts + kStreamCap < e_blk ? ts + kStreamCap : e_blk;
-        // phase 1: coalesced stream of (val, col), gather x, products to LDS; four independent loads per lane in flight per trip
-        long long k = ts + tid;
-        for (; k + 3 * kBlock < te; k += 4 * kBlock) {
-            const double v0 = stream_load<true>(val + k), v1 = stream_load<true>(val + k + kBlock), v2 = stream_load<true>(val + k + 2 * kBlock),
-                         v3 = stream_load<true>(val + k + 3 * kBlock);
-            const int c0 = stream_load<true>(col + k), c1 = stream_load<true>(col + k + kBlock), c2 = stream_load<true>(col + k + 2 * kBlock),
-                      c3 = stream_load<true>(col + k + 3 * kBlock);
-            const double x0v = x[c0], x1v = x[c1], x2v = x[c2], x3v = x[c3];
-            const int o = (int)(k - ts);
-            prod[o] = v0 * x0v;
-            prod[o + kBlock] = v1 * x1v;
-            prod[o + 2 * kBlock] = v2 * x2v;
-            prod[o + 3 * kBlock] = v3 * x3v;
-        }
-        for (; k < te; k += kBlock) prod[(int)(k - ts)] = stream_load<true>(val + k) * x[stream_load<true>(col + k)];
-        __syncthreads();
-        // phase 2: each row adds its part of the tile, left to right
-        const long long a = rs > ts ? rs : ts, e = re < te ? re : te;
-        for (long long j = a; j < e; ++j) y = y + prod[(int)(j - ts)];
-        __syncthreads();
-    }
-    return y;
-}
-
-// the chunk's partial sum: wave sums (in lane 63), then ((w0 + w1) + w2) + w3 as block_sum of avs_wave.hpp adds them.  red: by the parity
-// of the workgroup's trip, thread 0 may still read one while the next is written.
-__device__ __forceinline__ void spec_chunk_sum(double term, double (*red)[4], int parity, double *out)
-{
-    const double w = wave_sum_dpp(term);
-    if (((int)threadIdx.x & 63) == 63) red[parity][(int)threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) *out = ((red[parity][0] + red[parity][1]) + red[parity][2]) + red[parity][3];
+    raw_max_bits(m, kSpecRawGershgorin, raw);
 }
 
 // START: AVS_SPECTRUM_START_*.  b, x0: RESIDUAL only; start_vector: VECTOR only.
@@ -156,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_spectrum_start(const int32_t *__rest
     for (long long chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x, parity ^= 1) { // (the same trips for every thread of the workgroup)
         const long long row0 = chunk * kBlock, row = row0 + threadIdx.x;
         double y = 0.;
-        if (START == AVS_SPECTRUM_START_RESIDUAL) y = spec_chunk_product(rp, col, val, x0, n, row0, prod);
+        if (START == AVS_SPECTRUM_START_RESIDUAL) y = chunk_stream_product(rp, col, val, x0, n, row0, prod);
         double term = 0.;
         if (row < n) {
             double v;
@@ -171,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void k_spectrum_start(const int32_t *__rest
             w[row] = v;
             term = v * v;
         }
-        spec_chunk_sum(term, red, parity, partial + chunk);
+        chunk_partial_sum(term, red, parity, partial + chunk);
     }
 }
 
@@ -188,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void k_spectrum_product(const int32_t *__re
     int parity = 0;
     for (long long chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x, parity ^= 1) {
         const long long row0 = chunk * kBlock, row = row0 + threadIdx.x;
-        const double y = spec_chunk_product(rp, col, val, u, n, row0, prod);
+        const double y = chunk_stream_product(rp, col, val, u, n, row0, prod);
         double term = 0.;
         if (row < n) {
             double t = s[row] * y;
@@ -196,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void k_spectrum_product(const int32_t *__re
             w[row] = t;
             term = v[row] * t;
         }
-        spec_chunk_sum(term, red, parity, partial + chunk);
+        chunk_partial_sum(term, red, parity, partial + chunk);
     }
 }
 
@@ -216,7 +150,7 @@ __global__ __launch_bounds__(kBlock) void k_spectrum_orthogonalise(const double 
             w[row] = wi;
             term = wi * wi;
         }
-        spec_chunk_sum(term, red, parity, partial + chunk);
+        chunk_partial_sum(term, red, parity, partial + chunk);
     }
 }
 
@@ -238,14 +172,14 @@ __global__ __launch_bounds__(kBlock) void k_spectrum_fold(const double *__restri
     const double beta = sqrt(sum);
     if (what == kSpecFoldStart) {
         raw[kSpecRawBeta] = (unsigned long long)__double_as_longlong(beta);
-        if (!spec_finite(beta)) raw[kSpecRawNonfinite] = 1ull;
-        if (!spec_finite(beta) || !(beta > 0.)) raw[kSpecRawStop] = 1ull;
+        if (!finite_bits(beta)) raw[kSpecRawNonfinite] = 1ull;
+        if (!finite_bits(beta) || !(beta > 0.)) raw[kSpecRawStop] = 1ull;
         return;
     }
     raw[kSpecRawBeta + j + 1] = (unsigned long long)__double_as_longlong(beta);
     raw[kSpecRawStepsTaken] = (unsigned long long)(j + 1);
     const double alpha = spec_word(raw, kSpecRawAlpha + j), before = spec_word(raw, kSpecRawBeta + j);
-    if (!spec_finite(alpha) || !spec_finite(beta)) {
+    if (!finite_bits(alpha) || !finite_bits(beta)) {
         raw[kSpecRawNonfinite] = 1ull;
         raw[kSpecRawStop] = 1ull;
     } else if (!(beta > kSpecBreakdown * (fabs(alpha) + before))) {
@@ -285,7 +219,7 @@ static avs_status spectrum_without_rows(const SpectrumAsk &ask, bool evaluated, 
     avs_spectrum full;
     (void)spectrum_report(nullptr, ask, evaluated, out.ritz, &full);
     spectrum_scalars(nullptr, ask.steps, out.alpha, out.beta);
-    spectrum_hand_over(full, report);
+    report_hand_over(full, report);
     return AVS_OK;
 }
 
@@ -298,8 +232,7 @@ static avs_status estimate_spectrum(SpectrumScratch &S, const SpectrumSource &sr
     if (n == 0) return spectrum_without_rows(ask, true, out, report);
     const int m = ask.steps < n ? ask.steps : n;
     const long long chunks = ((long long)n + kBlock - 1) / kBlock;
-    const long long lim = grid_cap > 0 ? grid_cap : kSpecGrid;
-    const unsigned grid = (unsigned)(chunks < lim ? chunks : lim);
+    const unsigned grid = report_grid(chunks, grid_cap);
     const bool direct = where == AVS_MEM_DEVICE;
     const size_t vec = (size_t)n * sizeof(double);
     AVS_TRY(S.s.reserve((size_t)n));
@@ -308,9 +241,8 @@ static avs_status estimate_spectrum(SpectrumScratch &S, const SpectrumSource &sr
     AVS_TRY(S.vb.reserve((size_t)n));
     AVS_TRY(S.w.reserve((size_t)n));
     AVS_TRY(S.partial.reserve((size_t)chunks));
-    AVS_TRY(S.raw.reserve(kSpecRawWords));
+    AVS_TRY(S.raw.begin(kSpecRawWords, -1, st));
     unsigned long long *raw = S.raw.p;
-    AVS_HIP(hipMemsetAsync(raw, 0, kSpecRawWords * sizeof(unsigned long long), st));
     if (out.basis && !direct) { // the column copies behind a stop copy what the two vectors hold: never memory nobody wrote
         AVS_HIP(hipMemsetAsync(S.va.p, 0, vec, st));
         AVS_HIP(hipMemsetAsync(S.vb.p, 0, vec, st));
@@ -353,14 +285,12 @@ static avs_status estimate_spectrum(SpectrumScratch &S, const SpectrumSource &sr
         v = vprev;
         vprev = was;
     }
-    AVS_HIP(hipGetLastError());
     std::vector<unsigned long long> words(kSpecRawWords);
-    AVS_HIP(hipMemcpyAsync(words.data(), raw, kSpecRawWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    AVS_HIP(hipStreamSynchronize(st));
+    AVS_TRY(S.raw.read(words.data(), st));
     avs_spectrum full;
     const bool converged = spectrum_report(words.data(), ask, true, out.ritz, &full);
     spectrum_scalars(words.data(), ask.steps, out.alpha, out.beta);
-    spectrum_hand_over(full, report);
+    report_hand_over(full, report);
     AVS_REQUIRE(converged, AVS_EINTERNAL, "spectrum: the eigenvalues of the Lanczos tridiagonal did not converge");
     return AVS_OK;
 }

@@ -1,18 +1,15 @@
 // avs_spectrum_report.hpp -- host side of avs_estimate_spectrum / avs_estimate_csr_spectrum that needs no HIP call: argument checks, the
 // layout of the raw words the kernels leave behind, the eigenvalues of the Lanczos tridiagonal with the last components of its two
-// extreme eigenvectors, and the report that goes back to the caller.  Plain C++ over include/avs.h, so that a stand-alone program can
-// run it under the host sanitizers (tests/spectrum_report_main.cpp).
+// extreme eigenvectors, and the report that goes back to the caller (the hand-over: avs_report.hpp).  Plain C++ over include/avs.h, so
+// that a stand-alone program can run it under the host sanitizers (tests/spectrum_report_main.cpp).
 #pragma once
 
 #include <algorithm>
 #include <cmath>
-#include <cstddef>
-#include <cstdint>
-#include <cstring>
 #include <limits>
 #include <vector>
 
-#include "avs.h"
+#include "avs_report.hpp"
 
 namespace avs {
 
@@ -71,7 +68,7 @@ inline avs_status spectrum_args(int32_t op, int32_t start, int32_t steps, int wh
         *why = "spectrum: report must not be null";
         return AVS_EINVAL;
     }
-    if (report->struct_size < (int32_t)(offsetof(avs_spectrum, evaluated) + sizeof(int32_t)) || report->struct_size > 4096) {
+    if (!report_size_ok(report, offsetof(avs_spectrum, evaluated) + sizeof(int32_t))) {
         *why = "avs_spectrum.struct_size must be set to sizeof(avs_spectrum) before the call";
         return AVS_EINVAL;
     }
@@ -237,14 +234,6 @@ inline void spectrum_scalars(const unsigned long long *raw, int32_t steps, doubl
         if (raw) memcpy(beta, raw + kSpecRawBeta, ((size_t)steps + 1) * sizeof(double));
         else memset(beta, 0, ((size_t)steps + 1) * sizeof(double));
     }
-}
-
-// only the bytes the caller's header knows are written (struct_size is IN, as in avs_csr_check)
-inline void spectrum_hand_over(const avs_spectrum &full, avs_spectrum *out)
-{
-    const int32_t size = out->struct_size;
-    memcpy(out, &full, (size_t)size < sizeof(full) ? (size_t)size : sizeof(full));
-    out->struct_size = size;
 }
 
 } // namespace avs

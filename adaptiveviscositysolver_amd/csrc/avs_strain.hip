@@ -3,7 +3,7 @@
 // them in NumPy).  The stencils of avs_build_stencils are rows of the deformation-rate operator: an edge stencil is eps_bc at an edge
 // of axis a, a centre list du_a/dx_a at a cell (cpp:443-498).
 //
-//   k_strain_rates  one lane per stencil, persistent workgroups over chunks of 256 consecutive stencils.  The records are SoA ([k * count
+//   k_strain_rates  one lane per stencil, persistent workgroups over chunks of 256 (kBlock) consecutive stencils.  The records are SoA ([k * count
 //                   + s]): consecutive lanes load consecutive words; a lane's loop runs to its own cnt (4-12 in practice, cap 32); u is
 //                   gathered with plain loads.  Edges: one partial sum of w_e eps_e^2 per chunk.
 //   k_cell_shear    one lane per centre id, located through the cdof table (level, ijk): the four slots of each edge axis on the cell's
@@ -17,16 +17,14 @@
 //
 // A partial sum belongs to a CHUNK, not to a workgroup: the sums do not depend on the grid (Options::cells_grid_cap).  Counters are
 // 64-bit integers and the maxima the bit patterns of non-negative doubles: a lane accumulates in registers, a wave folds its lanes and
-// issues one integer atomic per word it has something for.  No floating atomics: the same inputs give the same bytes.
+// issues one integer atomic per word it has something for (raw_add and raw_max_bits, avs_report_device.hpp).  No floating atomics: the
+// same inputs give the same bytes.
 #include <cmath>
 
 #include "avs_device_common.hpp"
-#include "avs_wave.hpp"
+#include "avs_report_device.hpp"
 
 namespace avs {
-
-static constexpr int kStrainBlock = 256; // = stencils per chunk
-static constexpr int kStrainGrid = 2048; // persistent grids: eight workgroups per CU
 
 // raw summary: 64-bit words
 enum {
@@ -44,39 +42,18 @@ struct StrainStencils { // read-only StencilView
     const double *coef, *bval, *weight;
 };
 
-// raw[word] += the wave's sum of v (integer work: one atomic per wave that has something to add; the floating sums go through block_sum
-// of avs_wave.hpp)
-__device__ __forceinline__ void strain_count(unsigned long long v, int word, unsigned long long *raw)
-{
-    unsigned long long s = v;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += (unsigned long long)__shfl_xor((long long)s, o, 64);
-    if (((int)threadIdx.x & 63) == 0 && s) atomicAdd(raw + word, s);
-}
-// raw[word] = max(raw[word], the wave's largest v); v >= 0 and finite: the bit patterns order as the values
-__device__ __forceinline__ void strain_max(double v, int word, unsigned long long *raw)
-{
-    unsigned long long m = (unsigned long long)__double_as_longlong(v);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = (unsigned long long)__shfl_xor((long long)m, o, 64);
-        m = other > m ? other : m;
-    }
-    if (((int)threadIdx.x & 63) == 0 && m) atomicMax(raw + word, m);
-}
-
 // EDGE: the stencils are the edge stresses (partial sums of w eps^2, when `partial` is given); else the centre lists
 template <bool EDGE>
-__global__ __launch_bounds__(kStrainBlock) void k_strain_rates(StrainStencils S, int cap, int bcap, const double *__restrict__ u, long long n_vel,
+__global__ __launch_bounds__(kBlock) void k_strain_rates(StrainStencils S, int cap, int bcap, const double *__restrict__ u, long long n_vel,
                                                                double *__restrict__ rate, double *__restrict__ partial,
                                                                unsigned long long *__restrict__ raw)
 {
     __shared__ double lds4[4];
-    const long long count = S.count, chunks = (count + kStrainBlock - 1) / kStrainBlock;
+    const long long count = S.count, chunks = (count + kBlock - 1) / kBlock;
     unsigned empty = 0u, boundary = 0u, nonfinite = 0u;
     double max_abs = 0.;
     for (long long chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) { // (the same trips for every thread of the workgroup)
-        const long long s = chunk * kStrainBlock + (long long)threadIdx.x;
+        const long long s = chunk * kBlock + (long long)threadIdx.x;
         double term = 0.;
         if (s < count) {
             const int cnt = min(max(S.cnt[s], 0), cap), bcnt = min(max(S.bcnt[s], 0), bcap);
@@ -103,10 +80,10 @@ __global__ __launch_bounds__(kStrainBlock) void k_strain_rates(StrainStencils S,
             if (threadIdx.x == 0) partial[chunk] = t;
         }
     }
-    strain_count(empty, EDGE ? kStrainEmptyEdges : kStrainEmptyCenters, raw);
-    strain_count(boundary, EDGE ? kStrainBoundaryEdges : kStrainBoundaryCenters, raw);
-    strain_count(nonfinite, kStrainNonfinite, raw);
-    strain_max(max_abs, EDGE ? kStrainMaxEdge : kStrainMaxCenter, raw);
+    raw_add(empty, EDGE ? kStrainEmptyEdges : kStrainEmptyCenters, raw);
+    raw_add(boundary, EDGE ? kStrainBoundaryEdges : kStrainBoundaryCenters, raw);
+    raw_add(nonfinite, kStrainNonfinite, raw);
+    raw_max_bits(max_abs, EDGE ? kStrainMaxEdge : kStrainMaxCenter, raw);
 }
 
 // edge index of edge e of axis a at level l; outside the lattice: UNASSIGNED
@@ -117,17 +94,17 @@ __device__ __forceinline__ int strain_edge_index(const PyramidView &P, int l, in
     return P.eidx[l][a][lin(r, e)];
 }
 
-__global__ __launch_bounds__(kStrainBlock) void k_cell_shear(PyramidView P, const int32_t *__restrict__ cdof, long long n_center, long long n_edge,
+__global__ __launch_bounds__(kBlock) void k_cell_shear(PyramidView P, const int32_t *__restrict__ cdof, long long n_center, long long n_edge,
                                                              const double *__restrict__ edge_rate, const double *__restrict__ center_rate,
                                                              const double *__restrict__ cw, double *__restrict__ cell, double *__restrict__ partial,
                                                              unsigned long long *__restrict__ raw)
 {
     __shared__ double lds4[4];
-    const long long chunks = (n_center + kStrainBlock - 1) / kStrainBlock;
+    const long long chunks = (n_center + kBlock - 1) / kBlock;
     unsigned looked[4] = {0u, 0u, 0u, 0u}, empty_pairs = 0u;
     double max_shear = 0.;
     for (long long chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
-        const long long cid = chunk * kStrainBlock + (long long)threadIdx.x;
+        const long long cid = chunk * kBlock + (long long)threadIdx.x;
         double term = 0.;
         if (cid < n_center) {
             const int4 rec = *reinterpret_cast<const int4 *>(cdof + 4 * cid); // level | axis << 8, i, j, k
@@ -210,21 +187,21 @@ __global__ __launch_bounds__(kStrainBlock) void k_cell_shear(PyramidView P, cons
         }
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) strain_count(looked[k], kStrainLookups + k, raw);
-    strain_count(empty_pairs, kStrainEmptyPairs, raw);
-    strain_max(max_shear, kStrainMaxShear, raw);
+    for (int k = 0; k < 4; ++k) raw_add(looked[k], kStrainLookups + k, raw);
+    raw_add(empty_pairs, kStrainEmptyPairs, raw);
+    raw_max_bits(max_shear, kStrainMaxShear, raw);
 }
 
 // workgroup 0: the edges' partial sums -> raw[kStrainDissipationEdge]; workgroup 1: the cells' -> raw[kStrainDissipationCenter].  Thread t adds
 // the partial sums t, t + 256, ... in that order, then the block sum of avs_wave.hpp: a fixed order.
-__global__ __launch_bounds__(kStrainBlock) void k_strain_fold(const double *__restrict__ partial, long long n_first, long long n_second,
+__global__ __launch_bounds__(kBlock) void k_strain_fold(const double *__restrict__ partial, long long n_first, long long n_second,
                                                               unsigned long long *__restrict__ raw)
 {
     __shared__ double lds4[4];
     const double *p = blockIdx.x == 0 ? partial : partial + n_first;
     const long long n = blockIdx.x == 0 ? n_first : n_second;
     double s = 0.;
-    for (long long i = threadIdx.x; i < n; i += kStrainBlock) s = s + p[i];
+    for (long long i = threadIdx.x; i < n; i += kBlock) s = s + p[i];
     s = block_sum(s, lds4);
     if (threadIdx.x == 0) raw[blockIdx.x == 0 ? kStrainDissipationEdge : kStrainDissipationCenter] = (unsigned long long)__double_as_longlong(s);
 }
@@ -293,12 +270,12 @@ __device__ __forceinline__ float4 paint_quad(const PyramidView &P, long long n_c
 // x-adjacent cells of one row: W = 4 (one 16-byte store) where fx and nx are multiples of 4, the array starts on a 16-byte boundary and the
 // level-0 labels on a 4-byte one, else 1.
 template <int W>
-__global__ __launch_bounds__(kStrainBlock) void k_paint_shear(PyramidView P, long long n_center, const double *__restrict__ cell, int fx, int fy, int fz,
+__global__ __launch_bounds__(kBlock) void k_paint_shear(PyramidView P, long long n_center, const double *__restrict__ cell, int fx, int fy, int fz,
                                                               float *__restrict__ field)
 {
     const int gx = fx / W; // groups per row
     const long long groups = (long long)gx * fy * fz;
-    for (long long g = (long long)blockIdx.x * kStrainBlock + threadIdx.x; g < groups; g += (long long)gridDim.x * kStrainBlock) {
+    for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < groups; g += (long long)gridDim.x * kBlock) {
         int x, y, z;
         if (groups <= 0xffffffffll) { // 32-bit division where the grid allows it
             const unsigned row = (unsigned)g / (unsigned)gx;
@@ -314,20 +291,6 @@ __global__ __launch_bounds__(kStrainBlock) void k_paint_shear(PyramidView P, lon
     }
 }
 
-static unsigned strain_grid(long long workgroups, int cap)
-{
-    const long long lim = cap > 0 ? cap : kStrainGrid;
-    return (unsigned)(workgroups < 1 ? 1 : (workgroups < lim ? workgroups : lim));
-}
-
-// only the bytes the caller's header knows are written (struct_size is IN, as in avs_stress_check)
-static void strain_hand_over(const avs_strain_summary &full, avs_strain_summary *out)
-{
-    const int32_t size = out->struct_size;
-    memcpy(out, &full, (size_t)size < sizeof(full) ? (size_t)size : sizeof(full));
-    out->struct_size = size;
-}
-
 // the shared implementation: any of the five outputs may be null (the entries have checked the arguments and the state)
 static avs_status strain_run(avs_ctx *c, int32_t which, double *edge_rate, double *center_rate, double *cell_shear, avs_strain_summary *summary,
                              float *field, avs_memspace where)
@@ -339,7 +302,7 @@ static avs_status strain_run(avs_ctx *c, int32_t which, double *edge_rate, doubl
     const bool direct = where == AVS_MEM_DEVICE;
     const double *u = which == AVS_RATES_OF_SOLUTION ? c->x.p : c->x0.p;
     const int cap = c->opt.cells_grid_cap;
-    const long long chunks_e = (ne + kStrainBlock - 1) / kStrainBlock, chunks_c = (nc + kStrainBlock - 1) / kStrainBlock;
+    const long long chunks_e = (ne + kBlock - 1) / kBlock, chunks_c = (nc + kBlock - 1) / kBlock;
 
     double *d_edge = edge_rate, *d_center = center_rate, *d_cell = cell_shear;
     if (want_edge && !(direct && edge_rate)) { AVS_TRY(S.edge.reserve((size_t)ne)); d_edge = S.edge.p; }
@@ -347,25 +310,24 @@ static avs_status strain_run(avs_ctx *c, int32_t which, double *edge_rate, doubl
     if (want_cell && !(direct && cell_shear)) { AVS_TRY(S.cell.reserve((size_t)nc)); d_cell = S.cell.p; }
     double *d_partial = nullptr;
     if (summary) { AVS_TRY(S.partial.reserve((size_t)(chunks_e + chunks_c))); d_partial = S.partial.p; }
-    AVS_TRY(S.raw.reserve(kStrainRawWords));
-    AVS_HIP(hipMemsetAsync(S.raw.p, 0, kStrainRawWords * sizeof(unsigned long long), st));
+    AVS_TRY(S.raw.begin(kStrainRawWords, -1, st));
 
     if (want_edge && ne > 0) {
         const StrainStencils E{ne, c->e_cnt.p, c->e_idx.p, c->e_bcnt.p, c->e_coef.p, c->e_bval.p, c->e_w.p};
-        hipLaunchKernelGGL(k_strain_rates<true>, dim3(strain_grid(chunks_e, cap)), dim3(kStrainBlock), 0, st, E, (int)AVS_EDGE_STENCIL_CAP,
+        hipLaunchKernelGGL(k_strain_rates<true>, dim3(report_grid(chunks_e, cap)), dim3(kBlock), 0, st, E, (int)AVS_EDGE_STENCIL_CAP,
                            (int)AVS_EDGE_BOUNDARY_CAP, u, (long long)c->n_vel, d_edge, d_partial, S.raw.p);
     }
     if (want_center && n3 > 0) {
         const StrainStencils C{n3, c->c_cnt.p, c->c_idx.p, c->c_bcnt.p, c->c_coef.p, c->c_bval.p, c->c_w.p};
-        hipLaunchKernelGGL(k_strain_rates<false>, dim3(strain_grid((n3 + kStrainBlock - 1) / kStrainBlock, cap)), dim3(kStrainBlock), 0, st, C,
+        hipLaunchKernelGGL(k_strain_rates<false>, dim3(report_grid((n3 + kBlock - 1) / kBlock, cap)), dim3(kBlock), 0, st, C,
                            (int)AVS_CENTER_STENCIL_CAP, (int)AVS_CENTER_BOUNDARY_CAP, u, (long long)c->n_vel, d_center, (double *)nullptr, S.raw.p);
     }
     if (want_cell && nc > 0)
-        hipLaunchKernelGGL(k_cell_shear, dim3(strain_grid(chunks_c, cap)), dim3(kStrainBlock), 0, st, c->view(), (const int32_t *)c->cdof.p, nc, ne,
+        hipLaunchKernelGGL(k_cell_shear, dim3(report_grid(chunks_c, cap)), dim3(kBlock), 0, st, c->view(), (const int32_t *)c->cdof.p, nc, ne,
                            (const double *)d_edge, (const double *)d_center, (const double *)c->c_w.p, d_cell, d_partial ? d_partial + chunks_e : nullptr,
                            S.raw.p);
     if (summary)
-        hipLaunchKernelGGL(k_strain_fold, dim3(2), dim3(kStrainBlock), 0, st, (const double *)d_partial, chunks_e, chunks_c, S.raw.p);
+        hipLaunchKernelGGL(k_strain_fold, dim3(2), dim3(kBlock), 0, st, (const double *)d_partial, chunks_e, chunks_c, S.raw.p);
     float *d_field = field;
     const long long cells = (long long)c->desc.field_nx * c->desc.field_ny * c->desc.field_nz;
     if (field) {
@@ -373,8 +335,8 @@ static avs_status strain_run(avs_ctx *c, int32_t which, double *edge_rate, doubl
         const bool quads = c->desc.field_nx % 4 == 0 && c->desc.nx % 4 == 0 && (reinterpret_cast<uintptr_t>(d_field) & 15u) == 0 &&
                            (reinterpret_cast<uintptr_t>(c->labels[0].p) & 3u) == 0;
         const long long groups = quads ? cells / 4 : cells;
-        hipLaunchKernelGGL(quads ? k_paint_shear<4> : k_paint_shear<1>, dim3(strain_grid((groups + kStrainBlock - 1) / kStrainBlock, cap)),
-                           dim3(kStrainBlock), 0, st, c->view(), nc, (const double *)d_cell, c->desc.field_nx, c->desc.field_ny, c->desc.field_nz,
+        hipLaunchKernelGGL(quads ? k_paint_shear<4> : k_paint_shear<1>, dim3(report_grid((groups + kBlock - 1) / kBlock, cap)),
+                           dim3(kBlock), 0, st, c->view(), nc, (const double *)d_cell, c->desc.field_nx, c->desc.field_ny, c->desc.field_nz,
                            d_field);
     }
     AVS_HIP(hipGetLastError());
@@ -385,8 +347,8 @@ static avs_status strain_run(avs_ctx *c, int32_t which, double *edge_rate, doubl
         if (field) AVS_HIP(copy_out(field, d_field, (size_t)cells * sizeof(float), where, st));
     }
     unsigned long long raw[kStrainRawWords];
-    if (summary) AVS_HIP(hipMemcpyAsync(raw, S.raw.p, sizeof(raw), hipMemcpyDeviceToHost, st));
-    if (summary || !direct) AVS_HIP(hipStreamSynchronize(st));
+    if (summary) AVS_TRY(S.raw.read(raw, st));
+    else if (!direct) AVS_HIP(hipStreamSynchronize(st));
     if (!summary) return AVS_OK;
     avs_strain_summary full;
     memset(&full, 0, sizeof(full));
@@ -411,7 +373,7 @@ static avs_status strain_run(avs_ctx *c, int32_t which, double *edge_rate, doubl
     full.max_abs_edge_rate = as_double(kStrainMaxEdge);
     full.max_abs_center_rate = as_double(kStrainMaxCenter);
     full.max_shear_rate = as_double(kStrainMaxShear);
-    strain_hand_over(full, summary);
+    report_hand_over(full, summary);
     return AVS_OK;
 }
 
@@ -420,8 +382,8 @@ static avs_status strain_check(avs_ctx *c, const char *entry, int32_t which, con
 {
     AVS_REQUIRE(which == AVS_RATES_OF_SOLUTION || which == AVS_RATES_OF_INITIAL_GUESS, AVS_EINVAL, "%s: unknown velocity %d", entry, (int)which);
     AVS_REQUIRE(where == AVS_MEM_HOST || where == AVS_MEM_DEVICE, AVS_EINVAL, "%s: unknown memory space %d", entry, (int)where);
-    AVS_REQUIRE(!summary || (summary->struct_size >= (int32_t)(offsetof(avs_strain_summary, which) + sizeof(int32_t)) && summary->struct_size <= 4096),
-                AVS_EINVAL, "avs_strain_summary.struct_size must be set to sizeof(avs_strain_summary) before the call");
+    AVS_REQUIRE(!summary || report_size_ok(summary, offsetof(avs_strain_summary, which) + sizeof(int32_t)), AVS_EINVAL,
+                "avs_strain_summary.struct_size must be set to sizeof(avs_strain_summary) before the call");
     AVS_REQUIRE(!c->slab.on, AVS_ESTATE, "%s: the context holds a slab-local pre-pass (this rank's window only)", entry);
     AVS_REQUIRE(c->stencils_ready && c->tables_ready, AVS_ESTATE, "%s: no stencils: call avs_build_stencils / avs_assemble first", entry);
     if (which == AVS_RATES_OF_SOLUTION)

@@ -9,20 +9,18 @@
 //   k_stress_lattice<1> one launch per level, the same walk over the cell lattice: rule 4 on the entry alone; rules 5, 6 and 7 -- the
 //                       cell's label, its six faces (and their children a level down) and its twelve edges (their children and
 //                       grandchildren one and two levels down) -- for the entries that carry an id.
-//   k_stress_numbering  rules 3 and 8 over the occurrence counters.
+//   k_index_numbering   rules 3 and 8 over the occurrence counters (the kernel of avs_check.hip).
 //
 // Every rule is independent and every read is bounds-tested first: a cell outside its lattice reads as INACTIVE, an index outside its
 // lattice as UNASSIGNED.  The only address formed from a lattice value is occ[id], and that store is under the range test of rule 0 / 4;
 // labels and velocity indices are only compared with sentinels, so a garbage pyramid of another kind cannot make the checker fault.
 // Counts are 64-bit: a thread counts in registers, a wave adds its lanes and issues one atomic per rule it violated; the first violation
-// is one atomicMin of a packed key (avs_stress_check_report.hpp) per violating wave.  Integer work only: the same lattices give the same
-// report.
+// is one atomicMin of a packed key (lattice_key, avs_report.hpp) per violating wave (raw_add and raw_min, avs_report_device.hpp).  Integer
+// work only: the same lattices give the same report.
 #include "avs_internal.hpp"
+#include "avs_report_device.hpp"
 
 namespace avs {
-
-static constexpr int kStressBlock = 256;
-static constexpr int kStressGrid = 2048; // persistent grids: eight workgroups per CU
 
 struct StressLevels { // by value; the level of a launch is a kernel argument: every table lookup is wave-uniform
     const int8_t *lab[AVS_MAX_LEVELS];
@@ -54,26 +52,6 @@ __device__ __forceinline__ int stress_edge(const StressLevels &P, int l, int a, 
     return P.eidx[l][a][(size_t)c[0] + (size_t)n0 * ((size_t)c[1] + (size_t)n1 * (size_t)c[2])];
 }
 
-// what a thread found, folded into the raw report: raw[word] += the wave's sum of v (one atomic per wave that has something to add)
-__device__ __forceinline__ void stress_wave_add(unsigned v, int word, unsigned long long *raw)
-{
-    unsigned long long s = v;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += (unsigned long long)__shfl_xor((long long)s, o, 64);
-    if (((int)threadIdx.x & 63) == 0 && s) atomicAdd(raw + word, s);
-}
-// key of the first violation = min(key, the wave's smallest key) (one atomic per violating wave)
-__device__ __forceinline__ void stress_wave_min(unsigned long long key, unsigned long long *raw)
-{
-    unsigned long long m = key;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = (unsigned long long)__shfl_xor((long long)m, o, 64);
-        m = other < m ? other : m;
-    }
-    if (((int)threadIdx.x & 63) == 0 && m != kStressNoKey) atomicMin(raw + kStressRawKey, m);
-}
-
 // rule 0 / 4: UNASSIGNED, OUTSIDE or an id below n
 __device__ __forceinline__ bool stress_value_ok(int v, int n) { return v == AVS_UNASSIGNED || v == AVS_OUTSIDE || (v >= 0 && v < n); }
 
@@ -84,7 +62,7 @@ __device__ __forceinline__ void stress_check_edge(const StressLevels &P, int lev
 {
     if (!stress_value_ok(v, n_edge)) { // rule 0
         ++cnt[0];
-        key = min(key, stress_key(AVS_STRESS_RULE_EDGE_VALUE, level, axis, lin));
+        key = min(key, lattice_key(AVS_STRESS_RULE_EDGE_VALUE, level, axis, lin));
     }
     if (v < 0) return;
     ++active;
@@ -107,7 +85,7 @@ __device__ __forceinline__ void stress_check_edge(const StressLevels &P, int lev
     }
     if (bad) {
         ++cnt[1];
-        key = min(key, stress_key(AVS_STRESS_RULE_EDGE_CELLS, level, axis, lin));
+        key = min(key, lattice_key(AVS_STRESS_RULE_EDGE_CELLS, level, axis, lin));
     }
     // rule 2: the two faces of each other axis that meet in the edge.  Not examined, where the reference's assert rejects what its own
     // classification writes on the border of the grid: a face on a border plane of its own lattice (never numbered, cpp:1210-1215), and
@@ -141,7 +119,7 @@ __device__ __forceinline__ void stress_check_edge(const StressLevels &P, int lev
     }
     if (bad) {
         ++cnt[2];
-        key = min(key, stress_key(AVS_STRESS_RULE_EDGE_FACES, level, axis, lin));
+        key = min(key, lattice_key(AVS_STRESS_RULE_EDGE_FACES, level, axis, lin));
     }
 }
 
@@ -151,14 +129,14 @@ __device__ __forceinline__ void stress_check_center(const StressLevels &P, int l
 {
     if (!stress_value_ok(v, n_center)) { // rule 4
         ++cnt[0];
-        key = min(key, stress_key(AVS_STRESS_RULE_CENTER_VALUE, level, 0, lin));
+        key = min(key, lattice_key(AVS_STRESS_RULE_CENTER_VALUE, level, 0, lin));
     }
     if (v < 0) return;
     ++active;
     if (v < n_center) atomicAdd(occ + v, 1); // (in range: the only address a lattice value forms)
     if (stress_label(P, level, cell) != AVS_ACTIVE) { // rule 5
         ++cnt[1];
-        key = min(key, stress_key(AVS_STRESS_RULE_CENTER_LABEL, level, 0, lin));
+        key = min(key, lattice_key(AVS_STRESS_RULE_CENTER_LABEL, level, 0, lin));
     }
     bool bad = false; // rule 6: the six faces, but for those on a border plane of their lattice (never numbered, cpp:1210-1215)
 #pragma unroll
@@ -192,7 +170,7 @@ __device__ __forceinline__ void stress_check_center(const StressLevels &P, int l
     }
     if (bad) {
         ++cnt[2];
-        key = min(key, stress_key(AVS_STRESS_RULE_CENTER_FACES, level, 0, lin));
+        key = min(key, lattice_key(AVS_STRESS_RULE_CENTER_FACES, level, 0, lin));
     }
     bad = false; // rule 7: the twelve edges
 #pragma unroll
@@ -228,22 +206,22 @@ __device__ __forceinline__ void stress_check_center(const StressLevels &P, int l
     }
     if (bad) {
         ++cnt[3];
-        key = min(key, stress_key(AVS_STRESS_RULE_CENTER_EDGES, level, 0, lin));
+        key = min(key, lattice_key(AVS_STRESS_RULE_CENTER_EDGES, level, 0, lin));
     }
 }
 
 // kind 0: the edge lattice of (level, axis); kind 1: the centre lattice of level (axis is 0).  f0, f1, f2: the lattice's extents.  The
 // axis is a template argument: every coordinate a rule touches is then a register, not an element of an array indexed at run time.
 template <int kind, int axis>
-__global__ __launch_bounds__(kStressBlock) void k_stress_lattice(StressLevels P, int level, const int32_t *__restrict__ idx, int quads_ok, int f0,
+__global__ __launch_bounds__(kBlock) void k_stress_lattice(StressLevels P, int level, const int32_t *__restrict__ idx, int quads_ok, int f0,
                                                                  int f1, int f2, int n_ids, int32_t *__restrict__ occ, unsigned long long *__restrict__ raw)
 {
     constexpr int kRules = kind == 0 ? 3 : 4;
     const long long total = (long long)f0 * f1 * f2, quads = (total + 3) >> 2;
     unsigned cnt[kRules] = {};
     unsigned active = 0u;
-    unsigned long long key = kStressNoKey;
-    for (long long q = (long long)blockIdx.x * kStressBlock + threadIdx.x; q < quads; q += (long long)gridDim.x * kStressBlock) {
+    unsigned long long key = kNoKey;
+    for (long long q = (long long)blockIdx.x * kBlock + threadIdx.x; q < quads; q += (long long)gridDim.x * kBlock) {
         const long long e0 = 4 * q;
         int v[4] = {AVS_UNASSIGNED, AVS_UNASSIGNED, AVS_UNASSIGNED, AVS_UNASSIGNED};
         const int nv = (int)min(4ll, total - e0);
@@ -282,28 +260,9 @@ __global__ __launch_bounds__(kStressBlock) void k_stress_lattice(StressLevels P,
     }
     constexpr int first_rule = kind == 0 ? AVS_STRESS_RULE_EDGE_VALUE : AVS_STRESS_RULE_CENTER_VALUE; // (the rules of a kind are consecutive)
 #pragma unroll
-    for (int r = 0; r < kRules; ++r) stress_wave_add(cnt[r], first_rule + r, raw);
-    stress_wave_add(active, kind == 0 ? kStressRawEdges : kStressRawCenters, raw);
-    stress_wave_min(key, raw);
-}
-
-__global__ __launch_bounds__(kStressBlock) void k_stress_numbering(const int32_t *__restrict__ occ, int n_ids, int rule, unsigned long long *__restrict__ raw)
-{
-    unsigned cnt = 0u;
-    unsigned long long key = kStressNoKey;
-    for (long long id = (long long)blockIdx.x * kStressBlock + threadIdx.x; id < n_ids; id += (long long)gridDim.x * kStressBlock)
-        if (occ[id] != 1) {
-            ++cnt;
-            key = min(key, stress_key(rule, 0, 0, (unsigned long long)id));
-        }
-    stress_wave_add(cnt, rule, raw);
-    stress_wave_min(key, raw);
-}
-
-static unsigned stress_grid(long long threads, int cap)
-{
-    const long long wgs = (threads + kStressBlock - 1) / kStressBlock, lim = cap > 0 ? cap : kStressGrid;
-    return (unsigned)(wgs < 1 ? 1 : (wgs < lim ? wgs : lim));
+    for (int r = 0; r < kRules; ++r) raw_add(cnt[r], first_rule + r, raw);
+    raw_add(active, kind == 0 ? kStressRawEdges : kStressRawCenters, raw);
+    raw_min(key, kStressRawKey, raw);
 }
 
 // Shared implementation of avs_check_stress_indices / avs_prepass_check_stress_indices (rules and protocol: include/avs.h).  The caller has
@@ -311,7 +270,7 @@ static unsigned stress_grid(long long threads, int cap)
 avs_status check_stress_indices(StressCheckScratch &S, const StressCheckSource &src, hipStream_t st, uint32_t what, avs_stress_check *report)
 {
     if (what == 0 || src.levels == 0) {
-        check_stress_hand_over(check_stress_passed(), report);
+        report_hand_over(check_stress_passed(), report);
         return AVS_OK;
     }
     const bool edges = (what & AVS_CHECK_EDGE_INDICES) != 0, centers = (what & AVS_CHECK_CENTER_INDICES) != 0;
@@ -335,9 +294,7 @@ avs_status check_stress_indices(StressCheckScratch &S, const StressCheckSource &
     }
     AVS_REQUIRE(!edges || (src.n_edge >= 0 && src.n_edge < INT32_MAX), AVS_EINTERNAL, "stress index check: edge count out of range");
     AVS_REQUIRE(!centers || (src.n_center >= 0 && src.n_center < INT32_MAX), AVS_EINTERNAL, "stress index check: centre count out of range");
-    AVS_TRY(S.raw.reserve(kStressRawWords));
-    AVS_HIP(hipMemsetAsync(S.raw.p, 0, kStressRawWords * sizeof(unsigned long long), st));
-    AVS_HIP(hipMemsetAsync(S.raw.p + kStressRawKey, 0xff, sizeof(unsigned long long), st));
+    AVS_TRY(S.raw.begin(kStressRawWords, kStressRawKey, st));
     if (edges) {
         const int n_edge = (int)src.n_edge;
         AVS_TRY(S.occ_edge.reserve((size_t)n_edge + 1));
@@ -349,12 +306,12 @@ avs_status check_stress_indices(StressCheckScratch &S, const StressCheckSource &
                 const long long total = (long long)f[0] * f[1] * f[2];
                 const int quads_ok = (reinterpret_cast<uintptr_t>(src.eidx[l][a]) & 15u) == 0 ? 1 : 0;
                 const auto kernel = a == 0 ? k_stress_lattice<0, 0> : (a == 1 ? k_stress_lattice<0, 1> : k_stress_lattice<0, 2>);
-                hipLaunchKernelGGL(kernel, dim3(stress_grid((total + 3) >> 2, src.grid_cap)), dim3(kStressBlock), 0, st, P, l, src.eidx[l][a], quads_ok,
+                hipLaunchKernelGGL(kernel, dim3(report_grid(report_workgroups((total + 3) >> 2), src.grid_cap)), dim3(kBlock), 0, st, P, l, src.eidx[l][a], quads_ok,
                                    f[0], f[1], f[2], n_edge, S.occ_edge.p, S.raw.p);
             }
         if (n_edge > 0)
-            hipLaunchKernelGGL(k_stress_numbering, dim3(stress_grid(n_edge, src.grid_cap)), dim3(kStressBlock), 0, st, (const int32_t *)S.occ_edge.p, n_edge,
-                               (int)AVS_STRESS_RULE_EDGE_NUMBERING, S.raw.p);
+            hipLaunchKernelGGL(k_index_numbering, dim3(report_grid(report_workgroups(n_edge), src.grid_cap)), dim3(kBlock), 0, st, (const int32_t *)S.occ_edge.p, n_edge,
+                               (int)AVS_STRESS_RULE_EDGE_NUMBERING, kStressRawKey, S.raw.p);
     }
     if (centers) {
         const int n_center = (int)src.n_center;
@@ -364,18 +321,16 @@ avs_status check_stress_indices(StressCheckScratch &S, const StressCheckSource &
             const int f[3] = {src.n[0] >> l, src.n[1] >> l, src.n[2] >> l};
             const long long total = (long long)f[0] * f[1] * f[2];
             const int quads_ok = (reinterpret_cast<uintptr_t>(src.cidx[l]) & 15u) == 0 ? 1 : 0;
-            hipLaunchKernelGGL((k_stress_lattice<1, 0>), dim3(stress_grid((total + 3) >> 2, src.grid_cap)), dim3(kStressBlock), 0, st, P, l, src.cidx[l],
+            hipLaunchKernelGGL((k_stress_lattice<1, 0>), dim3(report_grid(report_workgroups((total + 3) >> 2), src.grid_cap)), dim3(kBlock), 0, st, P, l, src.cidx[l],
                                quads_ok, f[0], f[1], f[2], n_center, S.occ_center.p, S.raw.p);
         }
         if (n_center > 0)
-            hipLaunchKernelGGL(k_stress_numbering, dim3(stress_grid(n_center, src.grid_cap)), dim3(kStressBlock), 0, st, (const int32_t *)S.occ_center.p,
-                               n_center, (int)AVS_STRESS_RULE_CENTER_NUMBERING, S.raw.p);
+            hipLaunchKernelGGL(k_index_numbering, dim3(report_grid(report_workgroups(n_center), src.grid_cap)), dim3(kBlock), 0, st, (const int32_t *)S.occ_center.p,
+                               n_center, (int)AVS_STRESS_RULE_CENTER_NUMBERING, kStressRawKey, S.raw.p);
     }
-    AVS_HIP(hipGetLastError());
     unsigned long long raw[kStressRawWords];
-    AVS_HIP(hipMemcpyAsync(raw, S.raw.p, sizeof(raw), hipMemcpyDeviceToHost, st));
-    AVS_HIP(hipStreamSynchronize(st)); // the one wait: the report is on the host
-    check_stress_hand_over(check_stress_report(raw, what, src.n), report);
+    AVS_TRY(S.raw.read(raw, st)); // the one wait: the report is on the host
+    report_hand_over(check_stress_report(raw, what, src.n), report);
     return AVS_OK;
 }
 

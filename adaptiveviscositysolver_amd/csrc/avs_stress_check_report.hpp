@@ -1,29 +1,17 @@
 // avs_stress_check_report.hpp -- host side of avs_check_stress_indices / avs_prepass_check_stress_indices that needs no HIP call: argument
-// checks, the packed key of the first violation, and the report that goes back to the caller.  Plain C++ over include/avs.h, so that a
-// stand-alone program can run it under the host sanitizers (tests/stress_check_report_main.cpp).
+// checks, the layout of the raw report, and the report that goes back to the caller (the key of the first violation and the hand-over:
+// avs_report.hpp).  Plain C++ over include/avs.h, so that a stand-alone program can run it under the host sanitizers
+// (tests/stress_check_report_main.cpp).
 #pragma once
 
-#include <cstddef>
-#include <cstdint>
-#include <cstring>
-
-#include "avs.h"
+#include "avs_report.hpp"
 
 namespace avs {
 
-// What the kernels leave behind: one 64-bit count per rule, the smallest key of a violating entry (all ones: none), then the number of
-// edge and of centre entries that carry an id.
+// What the kernels leave behind: one 64-bit count per rule, the smallest lattice_key of a violating entry (kNoKey: none), then the number
+// of edge and of centre entries that carry an id.
 constexpr int kStressRawKey = AVS_STRESS_RULES, kStressRawEdges = AVS_STRESS_RULES + 1, kStressRawCenters = AVS_STRESS_RULES + 2;
 constexpr int kStressRawWords = AVS_STRESS_RULES + 3;
-constexpr unsigned long long kStressNoKey = ~0ull;
-// key = rule | level | axis | linear index of the entry in its own lattice (rules 3 and 8: the id): ascending keys are the order of the header
-constexpr int kStressLinBits = 40, kStressAxisShift = kStressLinBits, kStressLevelShift = kStressAxisShift + 2, kStressRuleShift = kStressLevelShift + 3;
-static_assert(AVS_MAX_LEVELS <= 8 && AVS_STRESS_RULES <= 16, "three bits for the level and four for the rule in the key");
-
-constexpr unsigned long long stress_key(int rule, int level, int axis, unsigned long long lin)
-{
-    return (unsigned long long)rule << kStressRuleShift | (unsigned long long)level << kStressLevelShift | (unsigned long long)axis << kStressAxisShift | lin;
-}
 
 // AVS_OK, or AVS_EINVAL with *why set
 inline avs_status check_stress_args(uint32_t what, const avs_stress_check *report, const char **why)
@@ -36,7 +24,7 @@ inline avs_status check_stress_args(uint32_t what, const avs_stress_check *repor
         *why = "stress index check: unknown bits in `what`";
         return AVS_EINVAL;
     }
-    if (report->struct_size < (int32_t)(offsetof(avs_stress_check, passed) + sizeof(int32_t)) || report->struct_size > 4096) {
+    if (!report_size_ok(report, offsetof(avs_stress_check, passed) + sizeof(int32_t))) {
         *why = "avs_stress_check.struct_size must be set to sizeof(avs_stress_check) before the call";
         return AVS_EINVAL;
     }
@@ -69,35 +57,20 @@ inline avs_stress_check check_stress_report(const unsigned long long *raw, uint3
     r.active_edges = (what & AVS_CHECK_EDGE_INDICES) ? (int64_t)raw[kStressRawEdges] : 0;
     r.active_centers = (what & AVS_CHECK_CENTER_INDICES) ? (int64_t)raw[kStressRawCenters] : 0;
     const unsigned long long key = raw[kStressRawKey];
-    if (!any || key == kStressNoKey) return r;
+    if (!any || key == kNoKey) return r;
     r.passed = 0;
-    r.first_rule = (int32_t)(key >> kStressRuleShift & 15u);
-    r.first_level = (int32_t)(key >> kStressLevelShift & 7u);
-    r.first_axis = (int32_t)(key >> kStressAxisShift & 3u);
-    const unsigned long long lin = key & ((1ull << kStressLinBits) - 1ull);
+    r.first_rule = lattice_key_rule(key);
+    r.first_level = lattice_key_level(key);
+    r.first_axis = lattice_key_axis(key);
+    const unsigned long long lin = lattice_key_lin(key);
     if (r.first_rule == AVS_STRESS_RULE_EDGE_NUMBERING || r.first_rule == AVS_STRESS_RULE_CENTER_NUMBERING) { // the entry is an id
         r.first_ijk[0] = (int32_t)lin;
         r.first_ijk[1] = r.first_ijk[2] = 0;
         return r;
     }
-    unsigned long long e[3];
-    for (int a = 0; a < 3; ++a) {
-        e[a] = (unsigned long long)(n[a] >> r.first_level);
-        if (stress_rule_is_edge(r.first_rule) && a != r.first_axis) e[a] += 1; // edge lattice: one more on the two other axes
-        if (e[a] == 0) e[a] = 1;
-    }
-    r.first_ijk[0] = (int32_t)(lin % e[0]);
-    r.first_ijk[1] = (int32_t)(lin / e[0] % e[1]);
-    r.first_ijk[2] = (int32_t)(lin / (e[0] * e[1]));
+    // edge lattice: one more on the two other axes
+    lattice_entry_ijk(lin, n, r.first_level, stress_rule_is_edge(r.first_rule) ? 7u & ~(1u << r.first_axis) : 0u, r.first_ijk);
     return r;
-}
-
-// only the bytes the caller's header knows are written (struct_size is IN, as in avs_octree_check)
-inline void check_stress_hand_over(const avs_stress_check &full, avs_stress_check *out)
-{
-    const int32_t size = out->struct_size;
-    memcpy(out, &full, (size_t)size < sizeof(full) ? (size_t)size : sizeof(full));
-    out->struct_size = size;
 }
 
 } // namespace avs

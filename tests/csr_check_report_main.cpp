@@ -68,7 +68,7 @@ int main()
     for (int rule = 0; rule < AVS_CSR_RULES; ++rule)
         for (unsigned long long index : {0ull, 1ull, 2147483646ull, 2147483647ull}) {
             const unsigned long long key = csr_check_key(rule, index);
-            EXPECT(csr_check_key_rule(key) == rule && csr_check_key_index(key) == (long long)index && key < kCsrNoKey);
+            EXPECT(csr_check_key_rule(key) == rule && csr_check_key_index(key) == (long long)index && key < kNoKey);
         }
     EXPECT(csr_check_key(0, 2147483647ull) < csr_check_key(1, 0));
     EXPECT(csr_check_key(6, (1ull << kCsrKeyIndexBits) - 1ull) < csr_check_key(7, 0));
@@ -79,7 +79,7 @@ int main()
     EXPECT(csr_check_rules_asked(AVS_CSR_CHECK_DIAGONAL, true) == 35 && csr_check_rules_asked(AVS_CSR_CHECK_SYMMETRY, true) == 195);
     // a clean raw report
     unsigned long long raw[kCsrRawWords] = {};
-    raw[kCsrRawKey] = kCsrNoKey;
+    raw[kCsrRawKey] = kNoKey;
     raw[kCsrRawEmptyRows] = 2;
     raw[kCsrRawLongestRow] = 10000;
     raw[kCsrRawMaxValue] = bits_of(3.5);
@@ -120,7 +120,7 @@ int main()
         std::vector<unsigned char> block((size_t)size, 0x5a);
         avs_csr_check *out = reinterpret_cast<avs_csr_check *>(block.data());
         std::memcpy(block.data(), &size, sizeof(size));
-        check_csr_hand_over(r, out);
+        report_hand_over(r, out);
         int32_t back, passed;
         std::memcpy(&back, block.data(), 4);
         std::memcpy(&passed, block.data() + 4, 4);
@@ -135,7 +135,7 @@ int main()
         std::vector<unsigned char> block(200, 0x5a);
         const int32_t size = 200;
         std::memcpy(block.data(), &size, sizeof(size));
-        check_csr_hand_over(r, reinterpret_cast<avs_csr_check *>(block.data()));
+        report_hand_over(r, reinterpret_cast<avs_csr_check *>(block.data()));
         for (size_t b = sizeof(avs_csr_check); b < block.size(); ++b) EXPECT(block[b] == 0x5a);
     }
     std::puts("ok");

@@ -140,7 +140,7 @@ int main()
     for (int32_t size : {12, 16, 24, 32, 40, 96, 152, 160}) {
         std::vector<unsigned char> block((size_t)size, 0x5a);
         std::memcpy(block.data(), &size, sizeof(size));
-        check_solution_hand_over(r, reinterpret_cast<avs_solution_check *>(block.data()));
+        report_hand_over(r, reinterpret_cast<avs_solution_check *>(block.data()));
         int32_t back, which, evaluated;
         std::memcpy(&back, block.data(), 4);
         std::memcpy(&which, block.data() + 4, 4);
@@ -156,7 +156,7 @@ int main()
         std::vector<unsigned char> block(200, 0x5a);
         const int32_t size = 200;
         std::memcpy(block.data(), &size, sizeof(size));
-        check_solution_hand_over(r, reinterpret_cast<avs_solution_check *>(block.data()));
+        report_hand_over(r, reinterpret_cast<avs_solution_check *>(block.data()));
         for (size_t b = sizeof(avs_solution_check); b < block.size(); ++b) EXPECT(block[b] == 0x5a);
     }
     std::puts("ok");

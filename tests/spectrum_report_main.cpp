@@ -231,7 +231,7 @@ int main()
             std::memset(buf, 0x5a, sizeof(buf));
             avs_spectrum *o = reinterpret_cast<avs_spectrum *>(buf);
             o->struct_size = size;
-            spectrum_hand_over(full, o);
+            report_hand_over(full, o);
             const size_t n = (size_t)size < sizeof(full) ? (size_t)size : sizeof(full);
             EXPECT(o->struct_size == size && std::memcmp(buf + 4, reinterpret_cast<const unsigned char *>(&full) + 4, n - 4) == 0);
             for (size_t i = n; i < sizeof(buf); ++i) EXPECT(buf[i] == 0x5a);

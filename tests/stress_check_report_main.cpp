@@ -50,25 +50,25 @@ int main()
         EXPECT(check_stress_args(1u, &rep, &why) == AVS_OK);
     }
     // keys order by (rule, level, axis, linear index), the largest fields do not run into each other, and every field comes back
-    const unsigned long long lin_max = (1ull << kStressLinBits) - 1;
-    EXPECT(stress_key(0, 7, 2, lin_max) < stress_key(1, 0, 0, 0));
-    EXPECT(stress_key(3, 1, 2, lin_max) < stress_key(3, 2, 0, 0));
-    EXPECT(stress_key(5, 2, 0, lin_max) < stress_key(5, 2, 1, 0));
-    EXPECT(stress_key(7, 7, 2, lin_max) < stress_key(8, 0, 0, 0));
-    EXPECT(stress_key(AVS_STRESS_RULES - 1, 7, 2, lin_max) < kStressNoKey);
-    EXPECT(stress_key(15, 7, 3, lin_max) < kStressNoKey); // (even a full four-bit rule field stays below "none")
+    const unsigned long long lin_max = (1ull << kLatticeLinBits) - 1;
+    EXPECT(lattice_key(0, 7, 2, lin_max) < lattice_key(1, 0, 0, 0));
+    EXPECT(lattice_key(3, 1, 2, lin_max) < lattice_key(3, 2, 0, 0));
+    EXPECT(lattice_key(5, 2, 0, lin_max) < lattice_key(5, 2, 1, 0));
+    EXPECT(lattice_key(7, 7, 2, lin_max) < lattice_key(8, 0, 0, 0));
+    EXPECT(lattice_key(AVS_STRESS_RULES - 1, 7, 2, lin_max) < kNoKey);
+    EXPECT(lattice_key(15, 7, 3, lin_max) < kNoKey); // (even a full four-bit rule field stays below "none")
     for (int rule : {0, 8})
         for (int level : {0, 7})
             for (int axis : {0, 2})
                 for (unsigned long long lin : {0ull, lin_max}) {
-                    const unsigned long long key = stress_key(rule, level, axis, lin);
-                    EXPECT((int)(key >> kStressRuleShift & 15u) == rule && (int)(key >> kStressLevelShift & 7u) == level &&
-                           (int)(key >> kStressAxisShift & 3u) == axis && (key & lin_max) == lin);
+                    const unsigned long long key = lattice_key(rule, level, axis, lin);
+                    EXPECT((int)(key >> kLatticeRuleShift & 15u) == rule && (int)(key >> kLatticeLevelShift & 7u) == level &&
+                           (int)(key >> kLatticeAxisShift & 3u) == axis && (key & lin_max) == lin);
                 }
     // a clean raw report: the active counts come back for the kinds that were asked for
     const int n[3] = {1024, 512, 256};
     unsigned long long raw[kStressRawWords] = {};
-    raw[kStressRawKey] = kStressNoKey;
+    raw[kStressRawKey] = kNoKey;
     raw[kStressRawEdges] = 6000000000ull;
     raw[kStressRawCenters] = 77;
     avs_stress_check r = check_stress_report(raw, 3u, n);
@@ -82,15 +82,15 @@ int main()
     // last entry of each, and one in the middle
     raw[AVS_STRESS_RULE_EDGE_FACES] = 5000000000ull; // counts are 64-bit
     raw[AVS_STRESS_RULE_CENTER_LABEL] = 3;
-    raw[kStressRawKey] = stress_key(AVS_STRESS_RULE_EDGE_FACES, 2, 0, 256ull * 129ull * 65ull - 1ull);
+    raw[kStressRawKey] = lattice_key(AVS_STRESS_RULE_EDGE_FACES, 2, 0, 256ull * 129ull * 65ull - 1ull);
     r = check_stress_report(raw, 1u, n); // centres not asked for: their counts are dropped
     EXPECT(r.violations[AVS_STRESS_RULE_CENTER_LABEL] == 0 && r.violations[AVS_STRESS_RULE_EDGE_FACES] == 5000000000ll);
     EXPECT(first_is(r, AVS_STRESS_RULE_EDGE_FACES, 2, 0, 255, 128, 64));
-    raw[kStressRawKey] = stress_key(AVS_STRESS_RULE_EDGE_FACES, 2, 1, 257ull * 128ull * 65ull - 1ull);
+    raw[kStressRawKey] = lattice_key(AVS_STRESS_RULE_EDGE_FACES, 2, 1, 257ull * 128ull * 65ull - 1ull);
     EXPECT(first_is(check_stress_report(raw, 3u, n), AVS_STRESS_RULE_EDGE_FACES, 2, 1, 256, 127, 64));
-    raw[kStressRawKey] = stress_key(AVS_STRESS_RULE_EDGE_FACES, 2, 2, 257ull * 129ull * 64ull - 1ull);
+    raw[kStressRawKey] = lattice_key(AVS_STRESS_RULE_EDGE_FACES, 2, 2, 257ull * 129ull * 64ull - 1ull);
     EXPECT(first_is(check_stress_report(raw, 3u, n), AVS_STRESS_RULE_EDGE_FACES, 2, 2, 256, 128, 63));
-    raw[kStressRawKey] = stress_key(AVS_STRESS_RULE_EDGE_VALUE, 0, 1, 5ull + 1025ull * (7ull + 512ull * 200ull));
+    raw[kStressRawKey] = lattice_key(AVS_STRESS_RULE_EDGE_VALUE, 0, 1, 5ull + 1025ull * (7ull + 512ull * 200ull));
     raw[AVS_STRESS_RULE_EDGE_VALUE] = 1;
     EXPECT(first_is(check_stress_report(raw, 3u, n), AVS_STRESS_RULE_EDGE_VALUE, 0, 1, 5, 7, 200));
     r = check_stress_report(raw, 2u, n); // only the centre rules asked for
@@ -98,24 +98,24 @@ int main()
     // centre lattices are the cell lattices, whatever axis the key carries: level 1 is 512 x 256 x 128
     std::memset(raw, 0, sizeof(raw));
     raw[AVS_STRESS_RULE_CENTER_EDGES] = 1;
-    raw[kStressRawKey] = stress_key(AVS_STRESS_RULE_CENTER_EDGES, 1, 0, 512ull * 256ull * 128ull - 1ull);
+    raw[kStressRawKey] = lattice_key(AVS_STRESS_RULE_CENTER_EDGES, 1, 0, 512ull * 256ull * 128ull - 1ull);
     EXPECT(first_is(check_stress_report(raw, 2u, n), AVS_STRESS_RULE_CENTER_EDGES, 1, 0, 511, 255, 127));
-    raw[kStressRawKey] = stress_key(AVS_STRESS_RULE_CENTER_VALUE, 0, 0, 1023ull + 1024ull * (511ull + 512ull * 255ull));
+    raw[kStressRawKey] = lattice_key(AVS_STRESS_RULE_CENTER_VALUE, 0, 0, 1023ull + 1024ull * (511ull + 512ull * 255ull));
     raw[AVS_STRESS_RULE_CENTER_VALUE] = 1;
     EXPECT(first_is(check_stress_report(raw, 2u, n), AVS_STRESS_RULE_CENTER_VALUE, 0, 0, 1023, 511, 255));
     // a centre of level 7 on a lattice that is one cell wide there; the numbering rules report the id
     const int tiny[3] = {128, 128, 256};
     std::memset(raw, 0, sizeof(raw));
     raw[AVS_STRESS_RULE_CENTER_LABEL] = 1;
-    raw[kStressRawKey] = stress_key(AVS_STRESS_RULE_CENTER_LABEL, 7, 0, 1);
+    raw[kStressRawKey] = lattice_key(AVS_STRESS_RULE_CENTER_LABEL, 7, 0, 1);
     EXPECT(first_is(check_stress_report(raw, 2u, tiny), AVS_STRESS_RULE_CENTER_LABEL, 7, 0, 0, 0, 1));
     raw[AVS_STRESS_RULE_EDGE_CELLS] = 1; // ... and the x edges there are 1 x 2 x 3
-    raw[kStressRawKey] = stress_key(AVS_STRESS_RULE_EDGE_CELLS, 7, 0, 5);
+    raw[kStressRawKey] = lattice_key(AVS_STRESS_RULE_EDGE_CELLS, 7, 0, 5);
     EXPECT(first_is(check_stress_report(raw, 1u, tiny), AVS_STRESS_RULE_EDGE_CELLS, 7, 0, 0, 1, 2));
     for (int rule : {AVS_STRESS_RULE_EDGE_NUMBERING, AVS_STRESS_RULE_CENTER_NUMBERING}) {
         std::memset(raw, 0, sizeof(raw));
         raw[rule] = 2;
-        raw[kStressRawKey] = stress_key(rule, 0, 0, 2147483646ull);
+        raw[kStressRawKey] = lattice_key(rule, 0, 0, 2147483646ull);
         EXPECT(first_is(check_stress_report(raw, 3u, tiny), rule, 0, 0, 2147483646, 0, 0));
     }
     // a key without a count that was asked for (the violation belongs to the other kind): passed
@@ -129,7 +129,7 @@ int main()
         std::vector<unsigned char> block((size_t)size, 0x5a);
         avs_stress_check *out = reinterpret_cast<avs_stress_check *>(block.data());
         std::memcpy(&out->struct_size, &size, sizeof(size));
-        check_stress_hand_over(r, out);
+        report_hand_over(r, out);
         int32_t back, passed;
         std::memcpy(&back, block.data(), 4);
         std::memcpy(&passed, block.data() + 4, 4);
@@ -154,7 +154,7 @@ int main()
         std::vector<unsigned char> block(200, 0x5a);
         const int32_t size = 200;
         std::memcpy(block.data(), &size, sizeof(size));
-        check_stress_hand_over(r, reinterpret_cast<avs_stress_check *>(block.data()));
+        report_hand_over(r, reinterpret_cast<avs_stress_check *>(block.data()));
         int32_t back;
         std::memcpy(&back, block.data(), 4);
         EXPECT(back == 200);
