@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "avs.h"
@@ -200,6 +201,13 @@ struct DevBuf {
         return AVS_OK;
     }
 };
+// two buffers trade their allocations (found by argument-dependent lookup: swap(a, b))
+template <typename T>
+inline void swap(DevBuf<T> &a, DevBuf<T> &b)
+{
+    std::swap(a.p, b.p);
+    std::swap(a.n, b.n);
+}
 
 // The raw report of a device diagnostic: 64-bit words its kernels fold into with integer atomics, kept across calls, read back whole.
 struct RawReport : DevBuf<unsigned long long> {
@@ -758,7 +766,7 @@ size_t scan_tmp_elems(int64_t n);
 #ifdef AVS_PROBES
 int scan_tile_elems(); // elements per workgroup of the scan (the probes report it as a limit)
 #endif
-bool dist_matrix_format(avs_ctx *c, avs_matrix_format *fmt); // avs_dist.hip: local rows of a partitioned / distributed system
+bool dist_matrix_format(avs_ctx *c, avs_matrix_format *fmt); // avs_dist_plan.hip: local rows of a partitioned / distributed system
 avs_status build_stencils(avs_ctx *c);
 avs_status pad_stencils(avs_ctx *c, bool edge); // unused stencil slots := (-1, 0.0), before a read-back
 avs_status build_initial_guess(avs_ctx *c);

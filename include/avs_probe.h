@@ -318,7 +318,7 @@ avs_status avs_brick_form_probe(int64_t n_rows, int64_t n_cols, const int32_t *r
                                 int32_t flags, int32_t grid, int32_t walk, double *dot_out, double *partials, int32_t partial_capacity,
                                 avs_brick_form_info *info, int32_t *headers, int32_t header_capacity, void *stream);
 
-/* The device partition planners (csrc/avs_dist.hip) on the CALLER's arrays: the functions avs_dist_partition and avs_dist_assemble call,
+/* The device partition planners (csrc/avs_dist_plan.hip) on the CALLER's arrays: the functions avs_dist_partition and avs_dist_assemble call,
  * without a context.  All inputs are device arrays, every result is copied to a HOST array of a stated capacity (any may be NULL).
  *   PLAN  plan_from_source, the core of avs_dist_partition's device planner: a CSR of n rows (any columns in [0, n), any row lengths
  *         including 0, duplicates allowed, the pattern need not be symmetric), its values, one int4 dof record per DOF (level | axis << 8,

@@ -1,4 +1,4 @@
-"""Named edge cases of the device partition planners (csrc/avs_dist.hip: plan_from_source and dist_tail_from_rows, through
+"""Named edge cases of the device partition planners (csrc/avs_dist_plan.hip: plan_from_source and dist_tail_from_rows, through
 avs_dist_plan_probe), placed from the limits the code was compiled with (the probe's limits-only call) and a fixed seed.
 
 A case is a CSR matrix over n ids plus what the planner needs -- PLAN: one dof record per id, an optional perm, levels, extent, world;

@@ -1,4 +1,4 @@
-"""A plain model of the partition plan (csrc/avs_partition.cpp documents it, csrc/avs_dist.hip builds it on the device), written from
+"""A plain model of the partition plan (csrc/avs_partition.cpp documents it, csrc/avs_dist_plan.hip builds it on the device), written from
 the definitions in numpy and plain Python.  Nothing here follows the kernels: no flags, scans or scatters.
 
 The plan of rank r for a CSR matrix over n ids and an owner per id:

@@ -53,7 +53,7 @@ def test_model_equals_the_host_planner(name, built_lib):
         for k in PLAN_ARRAYS:
             assert np.array_equal(p[k], h[k]), (name, r, k)
         assert np.array_equal(bits(p["val_local"]), bits(c.val[h["val_src"]])), (name, r)
-        # tile lists: the host planner's rule (avs_dist.hip: plan_on_host) on the host planner's arrays
+        # tile lists: the host planner's rule (avs_dist_plan.hip: plan_on_host) on the host planner's arrays
         T, n_own = E.limits().T, len(h["own_global"])
         bnd = [t for t in range(-(-n_own // T))
                if (h["col_local"][h["row_ptr_local"][t * T]:h["row_ptr_local"][min((t + 1) * T, n_own)]] >= n_own).any()]

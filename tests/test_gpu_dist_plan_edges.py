@@ -1,4 +1,4 @@
-"""The device partition planners (csrc/avs_dist.hip) on the edge cases of tests/dist_plan_edges.py, through avs_dist_plan_probe
+"""The device partition planners (csrc/avs_dist_plan.hip) on the edge cases of tests/dist_plan_edges.py, through avs_dist_plan_probe
 (libavs_probe.so): plan_from_source, the core of avs_dist_partition's device planner, and dist_tail_from_rows, everything avs_dist_assemble
 does behind assemble_rows, on the caller's arrays -- every case, every rank of its world.
 
