@@ -48,6 +48,7 @@ CHECK_EDGE_INDICES, CHECK_CENTER_INDICES = 1, 2   # bits of `what` of avs_check_
 STRESS_RULES = 9
 RATES_OF_SOLUTION, RATES_OF_INITIAL_GUESS = 0, 1   # `which` of avs_get_strain_rates / avs_get_shear_rate_field
 EDGE_LOOKUP_OWN, EDGE_LOOKUP_CHILD, EDGE_LOOKUP_GRANDCHILD, EDGE_LOOKUP_SKIPPED = range(4)   # avs_strain_summary.edge_lookups
+VISCOSITY_CARREAU_YASUDA, VISCOSITY_HERSCHEL_BULKLEY = 0, 1   # avs_viscosity_model.kind
 CHECK_OF_SOLUTION, CHECK_OF_INITIAL_GUESS = 0, 1   # `which` of avs_check_solution
 SPECTRUM_OF_JACOBI, SPECTRUM_OF_MATRIX = 0, 1   # `op` of avs_estimate_spectrum
 SPECTRUM_START_RESIDUAL, SPECTRUM_START_HASH, SPECTRUM_START_VECTOR = 0, 1, 2   # its `start`
@@ -77,7 +78,7 @@ EXPORTED_SYMBOLS = [
     "avs_prepass_set_slab", "avs_prepass_get_window", "avs_dist_bind_prepass", "avs_dist_get_cuts", "avs_set_solution",
     "avs_sample_velocity", "avs_get_octree_cells", "avs_prepass_get_octree_cells", "avs_check_octree", "avs_prepass_check_octree",
     "avs_check_csr", "avs_check_system", "avs_check_stress_indices", "avs_prepass_check_stress_indices",
-    "avs_get_strain_rates", "avs_get_shear_rate_field", "avs_check_solution", "avs_check_csr_solution",
+    "avs_get_strain_rates", "avs_get_shear_rate_field", "avs_apply_viscosity_model", "avs_check_solution", "avs_check_csr_solution",
     "avs_estimate_spectrum", "avs_estimate_csr_spectrum",
 ]
 # avs_allreduce_i32_fn: avs_status (*)(int32_t *device_data, int64_t count, void *stream, void *user)
@@ -86,7 +87,7 @@ ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_v
 PROBE_SYMBOLS = ["avs_spmv_csr", "avs_bench_spmv", "avs_spmv_sell", "avs_bench_stream", "avs_brick_spmv_probe", "avs_spmv_solver_form",
                  "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe", "avs_pcg_csr_plan",
                  "avs_merge_triplets_probe", "avs_exclusive_scan_probe", "avs_resident_plan_host", "avs_brick_form_probe", "avs_pcg_scalar_probe",
-                 "avs_sr_vector_probe", "avs_dist_plan_probe", "avs_phase_loop_info"]
+                 "avs_sr_vector_probe", "avs_dist_plan_probe", "avs_phase_loop_info", "avs_viscosity_lattice_probe"]
 DIST_PLAN_PROBE_PLAN, DIST_PLAN_PROBE_TAIL = 0, 1   # avs_dist_plan_probe modes
 BRICK_PROBE_FUSED_DOT, BRICK_PROBE_F32, BRICK_PROBE_MIXED, BRICK_PROBE_VALUE_CODES, BRICK_PROBE_DONE = 1, 2, 4, 8, 16   # avs_brick_form_probe flags
 VECTOR_PROBE_F32, VECTOR_PROBE_DS, VECTOR_PROBE_CODED, VECTOR_PROBE_KEEP, VECTOR_PROBE_FUSED = 1, 2, 4, 8, 16   # avs_vector_update_probe flags
@@ -194,6 +195,30 @@ class StrainSummary(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(StrainSummary)
+
+
+class ViscosityModel(C.Structure):
+    """avs_viscosity_model: kind (VISCOSITY_*), the parameters of the two kinds, the clamp and the relaxation of avs_apply_viscosity_model"""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("mu_0", C.c_double), ("mu_inf", C.c_double), ("lambda_", C.c_double),
+                ("a", C.c_double), ("n", C.c_double), ("consistency", C.c_double), ("tau_y", C.c_double), ("regularisation", C.c_double),
+                ("mu_min", C.c_double), ("mu_max", C.c_double), ("relaxation", C.c_double)]
+
+    def __init__(self, *a, **k):
+        k.setdefault("relaxation", 1.0)
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(ViscosityModel)
+
+
+class ViscositySummary(C.Structure):
+    """avs_viscosity_summary: the counts and extrema of avs_apply_viscosity_model"""
+    _fields_ = [("struct_size", C.c_int32), ("which", C.c_int32), ("kind", C.c_int32), ("installed", C.c_int32), ("n_center", C.c_int64),
+                ("covered", C.c_int64), ("fringe", C.c_int64), ("untouched", C.c_int64), ("clamped_low", C.c_int64),
+                ("clamped_high", C.c_int64), ("nonfinite", C.c_int64), ("min_viscosity", C.c_double), ("max_viscosity", C.c_double),
+                ("max_shear_rate", C.c_double), ("max_relative_change", C.c_double)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(ViscositySummary)
 
 
 class CsrCheck(C.Structure):
@@ -408,6 +433,7 @@ def load(probe=False):
                                            C.POINTER(BrickFormInfo), vp, i32, vp]
         L.avs_dist_plan_probe.argtypes = [i32, C.POINTER(DistPlanInput), C.POINTER(DistPlanOutput), C.POINTER(DistPlanInfo), vp]
         L.avs_phase_loop_info.argtypes = [C.POINTER(PhaseLoopReport)]
+        L.avs_viscosity_lattice_probe.argtypes = [vp, vp, C.POINTER(C.c_float), C.POINTER(i32), i32]
     L.avs_prepass_create.argtypes = [C.POINTER(PrepassDesc), C.POINTER(vp)]
     L.avs_prepass_destroy.argtypes = [vp]
     L.avs_prepass_destroy.restype = None
@@ -432,6 +458,7 @@ def load(probe=False):
     L.avs_prepass_check_stress_indices.argtypes = [vp, C.c_uint32, C.POINTER(StressCheck)]
     L.avs_get_strain_rates.argtypes = [vp, i32, vp, vp, vp, C.POINTER(StrainSummary), i32]
     L.avs_get_shear_rate_field.argtypes = [vp, i32, vp, i32]
+    L.avs_apply_viscosity_model.argtypes = [vp, i32, C.POINTER(ViscosityModel), vp, i32, C.POINTER(ViscositySummary), i32]
     L.avs_check_csr.argtypes = [i64, i64, vp, vp, vp, vp, vp, C.c_uint32, f64, i32, i32, vp, C.POINTER(CsrCheck)]
     L.avs_check_system.argtypes = [vp, C.c_uint32, f64, C.POINTER(CsrCheck)]
     L.avs_check_solution.argtypes = [vp, i32, vp, C.POINTER(SolutionCheck), i32]

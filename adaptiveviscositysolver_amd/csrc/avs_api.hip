@@ -441,6 +441,21 @@ avs_status avs::set_scalar_field_lattice(avs_ctx *c, avs_field_kind kind, int32_
     return AVS_OK;
 }
 
+avs_status avs::install_viscosity_lattice(avs_ctx *c, DevBuf<float> &lattice)
+{
+    int r[3];
+    grid_res(c->desc, 2, 0, 0, r);
+    AVS_REQUIRE(lattice.p && lattice.n >= vol3(r), AVS_EINTERNAL, "viscosity lattice too small");
+    avs_ctx::Field &f = c->visc;
+    f.buf.lent.reset(); // (a lent lattice stays its lender's)
+    swap(f.buf.own, lattice);
+    f.buf.p = f.buf.own.p;
+    f.buf.n = f.buf.own.n;
+    f.is_const = false;
+    invalidate(c, false);
+    return AVS_OK;
+}
+
 uint64_t avs::next_buffer_id()
 {
     static std::atomic<uint64_t> counter{0};

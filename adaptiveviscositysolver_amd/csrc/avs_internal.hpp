@@ -689,6 +689,22 @@ struct StrainScratch {
     RawReport raw;
     DevBuf<float> field;
 };
+// the shared implementation of the two entries (any output may be null) and their argument / state checks; with where == AVS_MEM_DEVICE
+// the arrays are written in place on the context's stream (avs_viscosity.hip: the cells' shear rates into StrainScratch::cell itself)
+avs_status strain_run(::avs_ctx *c, int32_t which, double *edge_rate, double *center_rate, double *cell_shear, avs_strain_summary *summary,
+                      float *field, avs_memspace where);
+avs_status strain_check(::avs_ctx *c, const char *entry, int32_t which, const avs_strain_summary *summary, avs_memspace where);
+
+// Viscosity model (avs_viscosity.hip): avs_apply_viscosity_model.  Scratch kept across calls: the model viscosity per centre id, that
+// array painted onto the simulation grid, the staging of a host-bound result, the raw summary, and the lattice the next install fills
+// (it trades places with the context's viscosity lattice: the pass reads the old one while it writes the new one).
+struct ViscosityScratch {
+    DevBuf<float> model, painted, out, next;
+    RawReport raw;
+};
+// `lattice` (the padded centre lattice, filled on the context's stream) becomes the context's AVS_FIELD_VISCOSITY, with the invalidation
+// of avs_set_scalar_field; the lattice it replaces, if the context owned one, is handed back in `lattice` (avs_api.hip)
+avs_status install_viscosity_lattice(::avs_ctx *c, DevBuf<float> &lattice);
 
 // CSR check (avs_csr_check.hip): avs_check_csr / avs_check_system over one implementation.  Scratch: the raw report and one byte per row
 // (1: the row's columns are strictly ascending, so the partner search of the symmetry pass may bisect it).
@@ -957,6 +973,7 @@ struct avs_ctx {
     avs::CsrCheckScratch csr_check; // avs_check_system (avs_csr_check.hip)
     avs::StressCheckScratch stress_check; // avs_check_stress_indices (avs_stress_check.hip)
     avs::StrainScratch strain; // avs_get_strain_rates / avs_get_shear_rate_field (avs_strain.hip)
+    avs::ViscosityScratch viscosity; // avs_apply_viscosity_model (avs_viscosity.hip)
     avs::SolutionCheckScratch solution_check; // avs_check_solution (avs_solution_check.hip)
     avs::SpectrumScratch spectrum; // avs_estimate_spectrum (avs_spectrum.hip)
 

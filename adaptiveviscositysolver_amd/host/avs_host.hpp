@@ -130,6 +130,27 @@ public:
     {
         check(avs_get_shear_rate_field(myCtx, which, field, AVS_MEM_HOST), "avs_get_shear_rate_field");
     }
+    // a shear-dependent viscosity evaluated on the device (avs_apply_viscosity_model: Carreau-Yasuda or Herschel-Bulkley of the cells'
+    // shear rates, the liquid's values continued one cell into the air, relaxation against the current viscosity).  field: field_nx *
+    // field_ny * field_nz floats on the host, or null.  install: the result becomes AVS_FIELD_VISCOSITY on the device, as setField with
+    // it would -- stencils, system and solution are gone afterwards.  summary.max_relative_change is the stopping measure of a
+    // fixed-point loop.
+    avs_viscosity_summary applyViscosityModel(avs_viscosity_model model, int32_t which = AVS_RATES_OF_SOLUTION, bool install = false,
+                                              float *field = nullptr)
+    {
+        model.struct_size = (int32_t)sizeof(model);
+        avs_viscosity_summary summary{};
+        summary.struct_size = (int32_t)sizeof(summary);
+        check(avs_apply_viscosity_model(myCtx, which, &model, field, install ? 1 : 0, &summary, AVS_MEM_HOST), "avs_apply_viscosity_model");
+        return summary;
+    }
+    // the fixed-point (Picard) loop over it; declared behind solveConjugateGradient
+    struct ShearDependentSolve {
+        bool converged = false;
+        avs_viscosity_summary initial{};              // the evaluation on the restricted input velocity
+        std::vector<SolveResult> solves;              // one per solve
+        std::vector<avs_viscosity_summary> summaries; // the evaluation on each solve's solution
+    };
     // did x solve the assembled system? (avs_check_solution: the true b - A x in fp64 from the plain CSR, whatever loop and storage form
     // produced x; report.relative_residual next to report.claimed_error, the solve's own figure.)  residual: n doubles on the host, or
     // null.  which = AVS_CHECK_OF_INITIAL_GUESS: the residual the solve starts from.
@@ -163,6 +184,29 @@ public:
         r.solveMs = s.solve_ms;
         r.spmvMs = s.spmv_ms;
         myDofs = s.n;
+        return r;
+    }
+    // Provisional fields set: the model is evaluated on the restricted input velocity and installed; then assemble, solve, evaluate on
+    // the solution WITHOUT installing; max_relative_change <= picardTolerance ends the loop, else the same evaluation is installed and
+    // the loop goes again (at most maxPicard solves).  No field crosses the bus.  On return the context is solved by the system that
+    // produced its solution: the transfer and checkSolution work.
+    ShearDependentSolve solveShearDependent(const avs_viscosity_model &model, double solverTolerance = 1e-3, int maxSolverIterations = 2500,
+                                            double picardTolerance = 1e-3, int maxPicard = 20)
+    {
+        ShearDependentSolve r;
+        buildStressStencils();
+        buildVelocityMapping();
+        r.initial = applyViscosityModel(model, AVS_RATES_OF_INITIAL_GUESS, true);
+        for (int k = 0; k < (maxPicard > 1 ? maxPicard : 1); ++k) {
+            buildLinearSystem();
+            r.solves.push_back(solveConjugateGradient(solverTolerance, maxSolverIterations));
+            r.summaries.push_back(applyViscosityModel(model, AVS_RATES_OF_SOLUTION, false));
+            if (r.summaries.back().max_relative_change <= picardTolerance) {
+                r.converged = true;
+                break;
+            }
+            if (k + 1 < maxPicard) applyViscosityModel(model, AVS_RATES_OF_SOLUTION, true); // the same values, now the context's field
+        }
         return r;
     }
     std::vector<double> viscositySolution() const

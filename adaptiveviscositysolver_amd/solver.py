@@ -526,6 +526,52 @@ class ViscositySolve:
         torch.cuda.synchronize(dev)
         return out
 
+    def apply_viscosity_model(self, model, which=capi.RATES_OF_SOLUTION, install=False, device_array=False):
+        """A shear-dependent viscosity evaluated on the device (avs_apply_viscosity_model): model is a capi.ViscosityModel (carreau_yasuda /
+        herschel_bulkley of this module build one).  Returns (field, summary): the relaxed viscosity on the simulation grid, float32
+        (nz, ny, nx) -- covered cells the model of their cell's shear rate, the one-cell fringe around them the mean of its covered
+        neighbours, every other cell its current viscosity -- as a NumPy array or, with device_array=True, a torch tensor on the context's
+        device, and the ViscositySummary (max_relative_change: the stopping measure of a fixed-point loop).  install=True makes the field
+        the context's FIELD_VISCOSITY on the device, as set_field with it would: stencils, system and solution are gone afterwards."""
+        nx, ny, nz = self.field_res
+        summary = capi.ViscositySummary()
+        if not device_array:
+            out = np.empty((nz, ny, nx), np.float32)
+            capi.check(self.lib.avs_apply_viscosity_model(self.h, int(which), C.byref(model), out.ctypes.data, int(bool(install)), C.byref(summary),
+                                                          capi.MEM_HOST))
+            return out, _viscosity_summary(summary)
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()   # (the stream rules of octree_cells)
+        capi.check(self.lib.avs_apply_viscosity_model(self.h, int(which), C.byref(model), out.data_ptr(), int(bool(install)), C.byref(summary),
+                                                      capi.MEM_DEVICE))
+        torch.cuda.synchronize(dev)
+        return out, _viscosity_summary(summary)
+
+    def solve_shear_dependent(self, model, tol=1e-3, max_iters=2500, picard_tol=1e-3, max_picard=20):
+        """The fixed-point (Picard) loop of a shear-dependent viscosity, with every field on the device.  The provisional fields are set;
+        the model is evaluated on the restricted input velocity and installed; then assemble, solve, evaluate on the solution into a
+        device array WITHOUT installing it; max_relative_change <= picard_tol (over covered cells, relaxation included) ends the loop,
+        else that array becomes the viscosity and the loop goes again, at most max_picard solves.  On return the context is solved by
+        the system that produced its solution (the transfer entries and check_solution work); the viscosity field is the one that
+        system was assembled with.  Returns a ShearDependentSolve."""
+        self.build_stencils()
+        self.build_initial_guess()
+        _, initial = self.apply_viscosity_model(model, capi.RATES_OF_INITIAL_GUESS, install=True, device_array=True)
+        solves, summaries, converged = [], [], False
+        for _ in range(max(1, int(max_picard))):
+            self.assemble()
+            solves.append(self.solve(tol, max_iters))
+            field, summary = self.apply_viscosity_model(model, capi.RATES_OF_SOLUTION, install=False, device_array=True)
+            summaries.append(summary)
+            if summary.max_relative_change <= picard_tol:
+                converged = True
+                break
+            if len(solves) < max(1, int(max_picard)):
+                self.set_field(capi.FIELD_VISCOSITY, 0, field)
+        return ShearDependentSolve(converged, initial, tuple(solves), tuple(summaries))
+
     def edge_stencils(self):
         ne = self.info().n_edge
         return self._stencils(self.lib.avs_get_edge_stencils, ne, ne, capi.EDGE_STENCIL_CAP, capi.EDGE_BOUNDARY_CAP)
@@ -615,6 +661,56 @@ def _strain_summary(s):
                          int(s.boundary_centers), int(s.nonfinite), tuple(int(v) for v in s.edge_lookups), int(s.empty_pairs),
                          float(s.dissipation_edge), float(s.dissipation_center), float(s.max_abs_edge_rate), float(s.max_abs_center_rate),
                          float(s.max_shear_rate))
+
+
+@dataclass(frozen=True)
+class ViscositySummary:
+    """avs_viscosity_summary: kind of the model, installed; covered / fringe / untouched cells of the simulation grid; clamped_low /
+    clamped_high / nonfinite centre ids of n_center; min_viscosity, max_viscosity, max_shear_rate and max_relative_change
+    (max |new - old| / old) over covered cells"""
+    which: int
+    kind: int
+    installed: bool
+    n_center: int
+    covered: int
+    fringe: int
+    untouched: int
+    clamped_low: int
+    clamped_high: int
+    nonfinite: int
+    min_viscosity: float
+    max_viscosity: float
+    max_shear_rate: float
+    max_relative_change: float
+
+
+def _viscosity_summary(s):
+    return ViscositySummary(int(s.which), int(s.kind), bool(s.installed), int(s.n_center), int(s.covered), int(s.fringe), int(s.untouched),
+                            int(s.clamped_low), int(s.clamped_high), int(s.nonfinite), float(s.min_viscosity), float(s.max_viscosity),
+                            float(s.max_shear_rate), float(s.max_relative_change))
+
+
+@dataclass(frozen=True)
+class ShearDependentSolve:
+    """result of ViscositySolve.solve_shear_dependent: converged (the last max_relative_change <= picard_tol); initial = the summary of the
+    evaluation on the restricted input velocity; solves[k] the avs_solve_info of solve k and summaries[k] the ViscositySummary of the
+    evaluation on its solution"""
+    converged: bool
+    initial: ViscositySummary
+    solves: tuple
+    summaries: tuple
+
+
+def carreau_yasuda(mu_0, mu_inf, lambda_, a, n, mu_min, mu_max, relaxation=1.0):
+    """capi.ViscosityModel: mu = mu_inf + (mu_0 - mu_inf) (1 + (lambda gamma)^a)^((n - 1) / a), clamped to [mu_min, mu_max]"""
+    return capi.ViscosityModel(kind=capi.VISCOSITY_CARREAU_YASUDA, mu_0=mu_0, mu_inf=mu_inf, lambda_=lambda_, a=a, n=n, mu_min=mu_min,
+                               mu_max=mu_max, relaxation=relaxation)
+
+
+def herschel_bulkley(consistency, n, tau_y, regularisation, mu_min, mu_max, relaxation=1.0):
+    """capi.ViscosityModel: mu = consistency gamma^(n - 1) + tau_y (1 - exp(-regularisation gamma)) / gamma (Papanastasiou), clamped"""
+    return capi.ViscosityModel(kind=capi.VISCOSITY_HERSCHEL_BULKLEY, consistency=consistency, n=n, tau_y=tau_y, regularisation=regularisation,
+                               mu_min=mu_min, mu_max=mu_max, relaxation=relaxation)
 
 
 def _octree_cells(fn, handle, origin, device_arrays, device):
@@ -871,10 +967,11 @@ def estimate_csr_spectrum(row_ptr, col, val, b=None, x0=None, start_vector=None,
 class DevicePrepass:
     """Pre-pass on the GPU (avs_prepass_*): liquid / solid SDF -> weights, label pyramid, index pyramids."""
 
-    def __init__(self, res, dx, levels, n_super=3, extrapolation=0.5, device=0, stream=None, field_res=None):
+    def __init__(self, res, dx, levels, n_super=3, extrapolation=0.5, device=0, stream=None, field_res=None, probe=False):
         """`res`: octree (power-of-two) resolution; `field_res`: the simulation grid the SDFs live on when it is smaller
-        (HDK_OctreeGrid::init pads to powers of two, oct.cpp:10-24); None = res."""
-        self.lib = capi.load()
+        (HDK_OctreeGrid::init pads to powers of two, oct.cpp:10-24); None = res.  probe=True: the object lives in libavs_probe.so, for a
+        ViscositySolve(probe=True) to apply it to -- the two must come from the same library."""
+        self.lib = capi.load(probe=probe)
         self.res = tuple(int(r) for r in res)
         fr = tuple(int(r) for r in field_res) if field_res is not None else (0, 0, 0)
         self.field_res = tuple(fr[a] or self.res[a] for a in range(3))

@@ -141,7 +141,8 @@ const char *avs_version(void);
  * Purely additive since (no revision): the entries avs_check_stress_indices and avs_prepass_check_stress_indices.
  * Purely additive since (no revision): the entries avs_get_strain_rates and avs_get_shear_rate_field.
  * Purely additive since (no revision): the entries avs_check_solution and avs_check_csr_solution.
- * Purely additive since (no revision): the entries avs_estimate_spectrum and avs_estimate_csr_spectrum. */
+ * Purely additive since (no revision): the entries avs_estimate_spectrum and avs_estimate_csr_spectrum.
+ * Purely additive since (no revision): the entry avs_apply_viscosity_model. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -521,7 +522,8 @@ avs_status avs_check_stress_indices(avs_ctx *ctx, uint32_t what, avs_stress_chec
  *   (avs_solve, avs_set_solution, or avs_dist_get_solution on a context that is not slab-local).  AVS_RATES_OF_INITIAL_GUESS: the
  *   restricted input velocity of avs_build_initial_guess / avs_assemble (not the partial one of avs_dist_assemble) -- what a viscosity model
  *   uses BEFORE the solve: provisional fields, avs_build_stencils, avs_build_initial_guess, avs_get_shear_rate_field, mu(gamma),
- *   avs_set_scalar_field(AVS_FIELD_VISCOSITY), avs_assemble, avs_solve.  No system has to be assembled for either.
+ *   avs_set_scalar_field(AVS_FIELD_VISCOSITY), avs_assemble, avs_solve (avs_apply_viscosity_model below does the two middle steps on the
+ *   device).  No system has to be assembled for either.
  * Rate of a stencil s (of `count` stencils, SoA as in avs_get_edge_stencils): fp64, one rounding per operation.  acc = 0; for k = 0 ..
  *   cnt[s]-1 in stored order acc = acc + coef[k*count + s] * u[idx[k*count + s]]; then for k = 0 .. bcnt[s]-1 acc = acc + bval[k*count + s].
  *   Slots at or behind cnt / bcnt are never read.  cnt == 0 gives the sum of the boundary terms.  AVS_PRECISION_F32 contexts are
@@ -582,6 +584,69 @@ avs_status avs_get_strain_rates(avs_ctx *ctx, int32_t which,
                                 double *cell_shear_rate  /* n_center,    may be NULL */,
                                 avs_strain_summary *summary /* may be NULL */, avs_memspace where);
 avs_status avs_get_shear_rate_field(avs_ctx *ctx, int32_t which, float *field /* field_nx*field_ny*field_nz, x fastest */, avs_memspace where);
+
+/* A shear-dependent viscosity mu(gamma) evaluated on the device from the shear rates above and, if asked for, installed as the context's
+ * AVS_FIELD_VISCOSITY without a pass through the caller: provisional fields, avs_build_stencils, avs_build_initial_guess,
+ * avs_apply_viscosity_model(AVS_RATES_OF_INITIAL_GUESS, install = 1), avs_assemble, avs_solve -- and for a fixed-point (Picard) loop
+ * avs_apply_viscosity_model(AVS_RATES_OF_SOLUTION) after the solve, its max_relative_change the stopping measure.
+ * which, the state it needs, the memory-space rules and the struct_size protocol of the summary: those of avs_get_shear_rate_field /
+ *   avs_strain_summary.  Slab-local contexts: AVS_ESTATE.
+ * Per centre id cid: g = cell_shear_rate[cid], the fp64 value avs_get_strain_rates defines.  All of this step is fp64, one rounding per
+ *   operation; pow and expm1 are those of the device's math library.
+ *     AVS_VISCOSITY_CARREAU_YASUDA    m = mu_inf + (mu_0 - mu_inf) * pow(1 + pow(lambda * g, a), (n - 1) / a)
+ *     AVS_VISCOSITY_HERSCHEL_BULKLEY  m = consistency * pow(g, n - 1) + Y.  tau_y == 0: the term Y is skipped.  Else Y = tau_y * regularisation
+ *                                     where g == 0, and Y = (tau_y * (-expm1(-regularisation * g))) / g elsewhere (Papanastasiou).
+ *   A NaN m, or a g that is not finite: the id has no value and is counted in nonfinite.  Otherwise m < mu_min: m = mu_min (clamped_low);
+ *   m > mu_max: m = mu_max (clamped_high) -- a +inf from pow(0, n - 1) with n < 1 clamps to mu_max.  Then P[cid] = (float)m, one rounding
+ *   after the clamp; P > 0 always.
+ * Per cell of the simulation grid (field_n*), M, the model's value there:
+ *     covered    the climb of avs_get_shear_rate_field finds an ACTIVE cell whose centre index is an id that has a value: M = P of that id;
+ *     fringe     not covered, but at least one of the up to 26 neighbours (x, y, z each -1 .. +1) inside the simulation grid is covered:
+ *                M = (float)(S / count), S the fp64 sum of (double)P of the covered neighbours, added z slowest, x fastest, count their
+ *                number.  A free surface thus continues the liquid's viscosity one cell into the air, where the edge samples of the
+ *                assembly reach, instead of mu(0);
+ *     untouched  any other cell keeps the viscosity it has.
+ *   Relaxation against old, the context's current viscosity at the cell (its field, or its constant): untouched: new = old; relaxation ==
+ *   1: new = M; else new = (float)((double)old + relaxation * ((double)M - (double)old)).
+ * mu_out (may be NULL) receives new for every cell of the simulation grid.  install != 0: new becomes the context's AVS_FIELD_VISCOSITY
+ *   exactly as avs_set_scalar_field(AVS_FIELD_VISCOSITY) with that array would make it -- the border cells replicated onto the padded
+ *   lattice, and the same invalidation: stencils, initial guess, system and SOLUTION are gone afterwards (build or assemble again; a
+ *   second call, or a strain entry, then reports AVS_ESTATE until they are back).  The kernels write the context's next lattice
+ *   directly; no copy of the field is staged.
+ * Summary (may be NULL): counts of cells (covered + fringe + untouched = field_nx field_ny field_nz) and of centre ids (clamped_low,
+ *   clamped_high, nonfinite, of n_center).  Over covered cells: min_viscosity and max_viscosity of M (0 without a covered cell),
+ *   max_shear_rate = the largest g among the ids that give cells their value (ids with a value whose cell starts inside the simulation
+ *   grid), max_relative_change = max of fabs((double)new - (double)old) / (double)old in fp64 over the covered cells with old > 0.
+ *   Integer counts and maxima only, no floating atomics: the same inputs give the same bytes on every call, in every fresh context and for
+ *   every grid size.
+ * Parameters: those the kind reads are checked, the others ignored.  Carreau-Yasuda: mu_0, mu_inf, lambda finite and >= 0, a finite and
+ *   > 0, n finite.  Herschel-Bulkley: consistency, tau_y, regularisation finite and >= 0, regularisation > 0 where tau_y != 0, n finite.
+ *   Both: mu_min finite with (float)mu_min > 0, mu_max finite as a float, mu_min <= mu_max, relaxation in (0, 1], struct_size =
+ *   sizeof(avs_viscosity_model).  A violation (a NaN is one): AVS_EINVAL, the message names the parameter.  An unknown which / memory
+ *   space / kind, a NULL model: AVS_EINVAL.  mu_out == NULL, install == 0 and summary == NULL: AVS_OK, nothing is launched.
+ * AVS_MEM_DEVICE mu_out is written by the kernels on the context's stream; AVS_MEM_HOST is staged and complete on return; the call returns
+ *   once the summary, if asked for, is on the host.  Scratch (the per-id array, the painted array, staging, the lattice the next install
+ *   fills) stays in the context. */
+enum { AVS_VISCOSITY_CARREAU_YASUDA = 0, AVS_VISCOSITY_HERSCHEL_BULKLEY = 1 };
+typedef struct avs_viscosity_model {
+    int32_t struct_size, kind;                 /* sizeof(avs_viscosity_model), AVS_VISCOSITY_* */
+    double mu_0, mu_inf, lambda, a, n;         /* Carreau-Yasuda */
+    double consistency, tau_y, regularisation; /* Herschel-Bulkley (n shared); Papanastasiou m */
+    double mu_min, mu_max;                     /* clamp; (float)mu_min > 0, mu_min <= mu_max, both finite */
+    double relaxation;                         /* omega in (0, 1] */
+} avs_viscosity_model;
+typedef struct avs_viscosity_summary {
+    int32_t struct_size;                 /* IN: sizeof(avs_viscosity_summary) of the caller's header */
+    int32_t which;
+    int32_t kind, installed;             /* the model's kind; 1 = the result is the context's viscosity field now */
+    int64_t n_center;                    /* centre ids evaluated */
+    int64_t covered, fringe, untouched;  /* cells of the simulation grid */
+    int64_t clamped_low, clamped_high, nonfinite; /* centre ids */
+    double min_viscosity, max_viscosity, max_shear_rate, max_relative_change; /* over covered cells */
+} avs_viscosity_summary;
+avs_status avs_apply_viscosity_model(avs_ctx *ctx, int32_t which, const avs_viscosity_model *model,
+                                     float *mu_out /* field_nx*field_ny*field_nz, x fastest; may be NULL */,
+                                     int32_t install, avs_viscosity_summary *summary /* may be NULL */, avs_memspace where);
 
 /* ------------------------------------------------------------------------------------------
  * Seam A: only the solve (replaces cpp:611-643).  CSR with int32 row pointers/columns, fp64

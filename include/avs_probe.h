@@ -253,6 +253,9 @@ avs_status avs_merge_triplets_probe(int64_t n, const int32_t *raw_ptr, const int
  * plan) on device arrays: out[i] = in[0] + .. + in[i - 1] for i <= n.  A total above INT32_MAX comes back as out[n] == -1, and then only
  * out[n] is defined. */
 avs_status avs_exclusive_scan_probe(const int32_t *in, int32_t *out /* n + 1 */, int64_t n, void *stream);
+/* The context's AVS_FIELD_VISCOSITY as the assembly reads it: *is_const = 1 and *constant, or *is_const = 0 and, if lattice is not NULL,
+ * the padded centre lattice (nx*ny*nz floats, x fastest) -- what avs_set_scalar_field or avs_apply_viscosity_model(install) left there. */
+avs_status avs_viscosity_lattice_probe(avs_ctx *ctx, float *lattice /* may be NULL */, float *constant, int32_t *is_const, avs_memspace where);
 
 /* The brick-structured SpMV form (csrc/avs_brick_build.hip: build_brick_form(BrickForm &, const BrickSource &, ...), the function the solver
  * and the partitioned plan call) and its kernel (csrc/avs_brick.hip: k_spmv_brick) on the CALLER's system: a device CSR of n_rows rows and

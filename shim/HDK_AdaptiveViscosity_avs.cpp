@@ -403,6 +403,48 @@ bool HDK_AdaptiveViscosity::solveGasSubclass(SIM_Engine &engine, SIM_Object *obj
     if (const char *dump = std::getenv("AVS_DUMP_PATH"))
         (void)write_dump(dump, h.pp, pinfo, oct, sim, dx, timestep, getUseEnhancedGradients(), fw[0], fw[1], fw[2], visc, dens, vel, svel);
 
+    // ---- optional: a shear-dependent viscosity evaluated on the device ----------------------------------------------------------
+    // New integer parameter "viscosityModel" (a maintainer adds the PRM_Templates next to the reference's, cpp:36-124): 0 = off (the
+    // "viscosity" field as given), 1 = Carreau-Yasuda, 2 = Herschel-Bulkley with the Papanastasiou regularisation; float parameters
+    // "modelMu0", "modelMuInf", "modelLambda", "modelA", "modelN", "modelConsistency", "modelYieldStress", "modelRegularisation",
+    // "modelMuMin", "modelMuMax", "modelRelaxation".  The model is evaluated from the shear rate of the restricted input velocity and
+    // installed as the viscosity field of this substep (avs_apply_viscosity_model: the "viscosity" field given above is what the
+    // relaxation is taken against and what cells away from the liquid keep); nothing passes through the host.  One evaluation per
+    // substep: the fixed-point loop over solves is ViscositySolve.solve_shear_dependent / AdaptiveViscosity::solveShearDependent.
+    {
+        int64 model_kind = 0;
+        getOptions().getOptionI("viscosityModel", model_kind);
+        if (model_kind == 1 || model_kind == 2) {
+            UT_PerfMonAutoSolveEvent event(this, "Viscosity Model (GPU)");
+            avs_viscosity_model model{};
+            model.struct_size = (int32_t)sizeof(model);
+            model.kind = model_kind == 1 ? AVS_VISCOSITY_CARREAU_YASUDA : AVS_VISCOSITY_HERSCHEL_BULKLEY;
+            model.relaxation = 1.;
+            const auto parm = [&](const char *name, double &v) { fpreal64 f = v; if (getOptions().getOptionF(name, f)) v = f; };
+            parm("modelMu0", model.mu_0);
+            parm("modelMuInf", model.mu_inf);
+            parm("modelLambda", model.lambda);
+            parm("modelA", model.a);
+            parm("modelN", model.n);
+            parm("modelConsistency", model.consistency);
+            parm("modelYieldStress", model.tau_y);
+            parm("modelRegularisation", model.regularisation);
+            parm("modelMuMin", model.mu_min);
+            parm("modelMuMax", model.mu_max);
+            parm("modelRelaxation", model.relaxation);
+            avs_viscosity_summary vsum{};
+            vsum.struct_size = (int32_t)sizeof(vsum);
+            if (!check(avs_build_stencils(h.ctx)) || !check(avs_build_initial_guess(h.ctx)) ||
+                !check(avs_apply_viscosity_model(h.ctx, AVS_RATES_OF_INITIAL_GUESS, &model, nullptr, 1, &vsum, AVS_MEM_HOST)))
+                return false; // (invalid parameters: AVS_EINVAL, the message names the parameter)
+            UT_WorkBuffer extra;
+            extra.sprintf("viscosity %.6g .. %.6g, max shear rate %.6g, clamped %lld + %lld, fringe cells %lld, relative change %.6g", vsum.min_viscosity,
+                          vsum.max_viscosity, vsum.max_shear_rate, (long long)vsum.clamped_low, (long long)vsum.clamped_high, (long long)vsum.fringe,
+                          vsum.max_relative_change);
+            event.setExtraInfo(extra.buffer());
+        }
+    }
+
     // ---- the hot path: cpp:418-653 -----------------------------------------------------------------------------------------
     avs_assembly_info ainfo;
     avs_solve_info sinfo;
