@@ -90,58 +90,70 @@ static thread_local bool tl_phase_folded = false;    // the last enqueue_iterati
 // ---------------------------------------------------------------------------------------------
 // vector kernels
 // ---------------------------------------------------------------------------------------------
-// DiagonalPreconditioner::factorize: invdiag(j) = A(j,j) != 0 ? 1/A(j,j) : 1
-__global__ __launch_bounds__(kBlock) void k_inv_diag(CsrView A, double *__restrict__ invd)
+// T: the type of the vectors (double; float in the float and mixed-precision loops -- there the diagonal is narrowed, then inverted in float)
+// DiagonalPreconditioner<T>::factorize: invdiag(j) = A(j,j) != 0 ? 1/A(j,j) : 1
+template <typename T> __device__ __forceinline__ T inv_or_one(const CsrView &A, T d)
+{
+    return (d != T(0) && !A.no_precond) ? T(1) / d : T(1); // (no_precond: plain CG, z = r)
+}
+// entry i of the inverted dictionary of a value-indexed matrix; the extra entry, i == table_size, is 1 and stands for "no diagonal entry"
+template <typename T, typename I> __device__ __forceinline__ T inv_table_entry(const CsrView &A, I i)
+{
+    return inv_or_one<T>(A, i < A.table_size ? (T)A.table[i] : T(0));
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_inv_diag(CsrView A, T *__restrict__ invd)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= A.n) return;
-    double d = 0.;
+    T d = 0;
     for (int k = A.row_ptr[i]; k < A.row_ptr[i + 1]; ++k)
-        if (A.col[k] == (int32_t)i) d = A.val ? A.val[k] : A.table[(A.tab_ptr ? A.tab_ptr[i / kTileRows] : 0) + A.codes[k]];
-    invd[i] = (d != 0. && !A.no_precond) ? 1. / d : 1.; // (no_precond: plain CG, z = r)
+        if (A.col[k] == (int32_t)i) d = (T)(A.val ? A.val[k] : A.table[(A.tab_ptr ? A.tab_ptr[i / kTileRows] : 0) + A.codes[k]]);
+    invd[i] = inv_or_one<T>(A, d);
 }
 
-// r = b - t ; partials: [0..g) b.b, [g..2g) r.r
-__global__ __launch_bounds__(kBlock) void k_init_residual(int64_t n, const double *__restrict__ b,
-                                                          const double *__restrict__ t,
-                                                          double *__restrict__ r, double *__restrict__ partial)
+// r = b - t ; partials: [0..g) b.b, [g..2g) r.r (a thread's own terms are added in T, everything across threads in double)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_init_residual(int64_t n, const T *__restrict__ b, const T *__restrict__ t, T *__restrict__ r,
+                                                          double *__restrict__ partial)
 {
     __shared__ double red[4];
-    double bb = 0., rr = 0.;
+    T bb = 0, rr = 0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const double bi = b[i];
-        const double ri = bi - t[i];
+        const T bi = b[i];
+        const T ri = bi - t[i];
         r[i] = ri;
         bb += bi * bi;
         rr += ri * ri;
     }
-    bb = block_sum(bb, red);
-    rr = block_sum(rr, red);
+    const double sb = block_sum((double)bb, red);
+    const double sr = block_sum((double)rr, red);
     if (threadIdx.x == 0) {
-        partial[blockIdx.x] = bb;
-        partial[gridDim.x + blockIdx.x] = rr;
+        partial[blockIdx.x] = sb;
+        partial[gridDim.x + blockIdx.x] = sr;
     }
 }
 
-// p = invd * r ; partial r.p
-__global__ __launch_bounds__(kBlock) void k_init_p(int64_t n, const double *__restrict__ r,
-                                                   const double *__restrict__ invd, double *__restrict__ p,
-                                                   double *__restrict__ x, double *__restrict__ partial,
-                                                   const PcgScalars *sc)
+// p = invd * r ; partial r.p.  CODED: invd is the inverted dictionary, indexed by the rows' codes (the fp64 loop reads the per-row inverse)
+template <typename T, bool CODED>
+__global__ __launch_bounds__(kBlock) void k_init_p(int64_t n, const T *__restrict__ r, const T *__restrict__ invd,
+                                                   const uint16_t *__restrict__ dcode, T *__restrict__ p, T *__restrict__ x,
+                                                   double *__restrict__ partial, const PcgScalars *sc)
 {
     __shared__ double red[4];
     const int done = sc->done;
-    double rz = 0.;
+    T rz = 0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        if (done == 3) { x[i] = 0.; continue; } // rhsNorm2 == 0 -> x.setZero()
+        if (done == 3) { x[i] = 0; continue; } // rhsNorm2 == 0 -> x.setZero()
         if (done) continue;
-        const double ri = r[i];
-        const double zi = invd[i] * ri;
+        const T ri = r[i];
+        const T zi = (CODED ? invd[dcode[i]] : invd[i]) * ri;
         p[i] = zi;
         rz += ri * zi;
     }
-    rz = block_sum(rz, red);
-    if (threadIdx.x == 0) partial[blockIdx.x] = rz;
+    const double s = block_sum((double)rz, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // value-indexed matrix: invd[i] == invtab[dcode[i]], where invtab[c] = 1 / table[c] (1 for a zero) and the extra
@@ -149,21 +161,25 @@ __global__ __launch_bounds__(kBlock) void k_init_p(int64_t n, const double *__re
 __global__ __launch_bounds__(kBlock) void k_inv_diag_coded(CsrView A, uint16_t *__restrict__ dcode, double *__restrict__ invtab)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i <= A.table_size) {
-        const double d = i < A.table_size ? A.table[i] : 0.;
-        invtab[i] = (d != 0. && !A.no_precond) ? 1. / d : 1.;
-    }
+    if (i <= A.table_size) invtab[i] = inv_table_entry<double>(A, i);
     if (i >= A.n) return;
     unsigned code = (unsigned)A.table_size;
     for (int k = A.row_ptr[i]; k < A.row_ptr[i + 1]; ++k)
         if (A.col[k] == (int32_t)i) code = A.codes[k];
     dcode[i] = (uint16_t)code;
 }
+// the float loops' dictionary: the same table narrowed, then inverted in float (the codes are k_inv_diag_coded's)
+__global__ __launch_bounds__(kBlock) void k_f32_invtab(CsrView A, float *__restrict__ invtab)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i > A.table_size) return;
+    invtab[i] = inv_table_entry<float>(A, i);
+}
 
 // ---------------------------------------------------------------------------------------------
-// The scalar prologue of the vector kernels of the launch-per-phase loops (k_update_r, k_update_xp and their float twins in
-// avs_pcg_f32.inl).  None of a kernel's stream loads depends on alpha or beta, and the scalar loads do not depend on each other, so at
-// kernel entry every thread requests, in this order and without waiting for anything:
+// The scalar prologue of the vector kernels of the launch-per-phase loops (k_update_r and k_update_xp, below).  None of a
+// kernel's stream loads depends on alpha or beta, and the scalar loads do not depend on each other, so at kernel entry every thread
+// requests, in this order and without waiting for anything:
 //   1. vec_request: the scalars (uniform loads; a kernel uses the ones its form needs, the others are never loaded) and its share of
 //      the partial sums of the launch before (up to kFoldBatch per array: all of them in the loops' own launches);
 //   2. the stream loads of its first kVecAhead grid-stride trips (a lane without such a trip reads *sc and drops the value: with no
@@ -231,98 +247,168 @@ __device__ __forceinline__ const V *vec_src(bool live, const E *rows, const PcgS
     return live ? reinterpret_cast<const V *>(rows) : reinterpret_cast<const V *>(sc);
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_update_r and k_update_xp: T is the type of the vectors, S the type the scalar step is computed in.  The three loops:
+//   <double, double>  the fp64 loop;
+//   <float, float>    AVS_PRECISION_F32 -- alpha, beta and the threshold test are FLOAT operations on the float-rounded sums;
+//   <float, double>   the mixed-precision loop (avs_pcg_mixed.inl) -- double quotients of the unrounded sums, published unrounded and
+//                     rounded to float only where they multiply the float vectors.
+// A thread takes Vec16<T>::rows rows per trip (16-B accesses; the arrays are 16-B aligned); the rows behind the last full 16 B go
+// alone, to thread 0 of workgroup 0.  A thread's own sums are added in T, everything across threads, workgroups and launches in double.
+// ---------------------------------------------------------------------------------------------
+// f(k) for the rows k = 0 .. R - 1 of a 16-B access, as straight-line code
+template <int R, typename F> __device__ __forceinline__ void for_rows(F &&f)
+{
+    f(0);
+    f(1);
+    if constexpr (R == 4) {
+        f(2);
+        f(3);
+    }
+}
+// The rows behind a vector's last full 16 B go alone, to thread 0 of workgroup 0: rows [vec_tail_begin, n).  fp64 has one such row at
+// most and says so -- taken if n is odd, first row n - 1 --, which the compiler turns into a test where it would otherwise keep a loop.
+template <typename T> __device__ __forceinline__ bool vec_tail_mine(int64_t n)
+{
+    return (Vec16<T>::rows > 2 || (n & 1)) && blockIdx.x == 0 && threadIdx.x == 0;
+}
+template <typename T> __device__ __forceinline__ int64_t vec_tail_begin(int64_t n)
+{
+    return Vec16<T>::rows == 2 ? n - 1 : Vec16<T>::rows * (n >> Vec16<T>::log2_rows);
+}
+// KEEP of update_r's accesses to r.  The fp64 kernel hints them like its other read-once streams; the float kernels load and store r
+// plainly whatever KEEP is (as they were measured; hinting them is a performance change of its own).
+#ifndef AVS_EXP_NO_RNT
+template <typename T, bool KEEP> constexpr bool kKeepR = KEEP || std::is_same<T, float>::value;
+#else
+template <typename T, bool KEEP> constexpr bool kKeepR = true;
+#endif
+
+// The alpha step, alpha = r.z / p.Ap, as every workgroup takes it for itself.  FUSED: p.Ap is the folded sum of the SpMV's partials and
+// thread 0 of workgroup 0 publishes what OP_ALPHA would.  Else OP_ALPHA has run: its double quotient is read -- but S = float divides
+// again, in float, and publishes that (OP_ALPHA divided in double: k_update_xp reads this one).
+template <typename T, typename S, bool FUSED>
+__device__ __forceinline__ T alpha_step(const VecScalars &s, PcgScalars *sc)
+{
+    if (FUSED) {
+        const double pap = s.sum[0];
+        const S alpha = (S)s.rho_old / (S)pap;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            sc->red[0] = pap;
+            sc->pAp = (double)(S)pap;
+            sc->alpha = (double)alpha;
+        }
+        return (T)alpha;
+    }
+    if (std::is_same<S, double>::value) return (T)s.alpha;
+    const S alpha = (S)s.rho_old / (S)s.pAp;
+    if (blockIdx.x == 0 && threadIdx.x == 0) sc->alpha = (double)alpha;
+    return (T)alpha;
+}
+
+// The beta step of an iteration that is not done, as every workgroup takes it for itself: convergence test (Eigen: break before i++,
+// x += alpha p still pending: done = 2), else beta = r.z / old r.z; thread 0 of workgroup 0 publishes what OP_BETA would.  The sums, the
+// old r.z and the threshold are rounded to S first and the scalars published as S holds them.  Mixed loop (T = float, S = double): the
+// iteration that claims convergence leaves the r.z it started from in sc->rho whatever its parity (the reliable update reads it there;
+// nobody reads sc->rho in an odd iteration: it is the slot this iteration would have written).
+template <typename T, typename S>
+__device__ __forceinline__ T beta_step(const VecScalars &s, PcgScalars *sc, int parity, int &done)
+{
+    const S rr = (S)s.sum[0], rz = (S)s.sum[1];
+    const S absOld = (S)s.rho_old;
+    S beta = 0;
+    if (rr < (S)s.threshold) done = 2;
+    else beta = rz / absOld;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        sc->red[0] = (double)rr;
+        sc->red[1] = (double)rz;
+        sc->rr = (double)rr;
+        if (done == 2) {
+            sc->done = 2;
+            if (!std::is_same<T, S>::value && parity) sc->rho = (double)absOld;
+        } else {
+            if (parity) sc->rho = (double)rz;
+            else sc->rho_alt = (double)rz;
+            // (mixed loop: the quotient is formed again for the store, as that kernel always has -- keeps its code object as it was)
+            sc->beta = std::is_same<T, S>::value ? (double)beta : (double)(rz / absOld);
+            sc->iter += 1;
+        }
+    }
+    return (T)beta;
+}
+
 // r -= alpha t ; partials: r.r and r.(invd r).  (x += alpha p rides along with the p update below:
 // one vector pass less per iteration -- 10 n instead of 11 n doubles of traffic.)
 // FUSED (single-GPU loop, small systems): the alpha step -- fold of the SpMV's `nb` partial sums, alpha = r.z / p.Ap -- is done
 // here by every workgroup for itself, as k_update_xp does with the beta step; only worth it while the SpMV leaves few
 // partials (one per wave of 64 rows): the loop uses it up to kFuseAlphaMax of them.  The kernel's own partial sums then go
 // to a second array (`partial`), because other workgroups are still reading the SpMV's.
-template <bool CODED, bool FUSED, bool KEEP>
-__global__ __launch_bounds__(kBlock) void k_update_r(int64_t n, double *__restrict__ r, const double *__restrict__ t,
-                                                     const double *__restrict__ invd, const uint16_t *__restrict__ dcode,
-                                                     PcgScalars *sc, double *__restrict__ partial,
-                                                     const double *__restrict__ spmv_partial = nullptr, int nb = 0, int parity = 0)
+template <typename T, typename S, bool CODED, bool FUSED, bool KEEP>
+__global__ __launch_bounds__(kBlock) void k_update_r(int64_t n, T *__restrict__ r, const T *__restrict__ t, const T *__restrict__ invd,
+                                                     const uint16_t *__restrict__ dcode, PcgScalars *sc, double *__restrict__ partial,
+                                                     const double *__restrict__ spmv_partial, int nb, int parity)
 {
+    typedef typename Vec16<T>::type V;
+    typedef typename Vec16<T>::codes C;
+    constexpr int R = Vec16<T>::rows;
     __shared__ double pro[8], red[8];
     // t = A p is read for the last time here and r is next read one kernel later: the streams that nobody reads again before they
     // are overwritten are loaded / stored NON-TEMPORALLY, so that they do not push the matrix out of the caches between two products
     // (`keep`: matrix and vectors together fit the Infinity Cache -- then everything is left to it)
-    const int64_t n2 = n >> 1; // two rows per thread (16-B accesses), partial sums in the order (even row, odd row)
+    const int64_t nv = n >> Vec16<T>::log2_rows; // R rows per thread and trip, partial sums in the order of the rows
     const int64_t j0 = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
-    struct Trip { d2_t rv, tv, iv; unsigned cc; };
+    struct Trip { V rv, tv, iv; C cc; };
     auto request = [&](int64_t j, bool live, Trip &q) {
-        const int64_t i = 2 * j;
-#ifndef AVS_EXP_NO_RNT
-        q.rv = stream_load_k<KEEP>(vec_src<d2_t>(live, r + i, sc));
-#else
-        q.rv = *vec_src<d2_t>(live, r + i, sc);
-#endif
-        q.tv = stream_load_k<KEEP>(vec_src<d2_t>(live, t + i, sc));
-        if (CODED) q.cc = stream_load_k<KEEP>(vec_src<unsigned>(live, dcode + i, sc));
-        else q.iv = *vec_src<d2_t>(live, invd + i, sc);
+        const int64_t i = R * j;
+        q.rv = stream_load_k<kKeepR<T, KEEP>>(vec_src<V>(live, r + i, sc));
+        q.tv = stream_load_k<KEEP>(vec_src<V>(live, t + i, sc));
+        if (CODED) q.cc = stream_load_k<KEEP>(vec_src<C>(live, dcode + i, sc));
+        else q.iv = *vec_src<V>(live, invd + i, sc);
     };
     VecScalars s = vec_request<FUSED ? 1 : 0>(sc, parity, spmv_partial, nb, 0);
     Trip ahead[kVecAhead];
 #pragma unroll
-    for (int u = 0; u < kVecAhead; ++u) request(j0 + u * stride, j0 + u * stride < n2, ahead[u]);
+    for (int u = 0; u < kVecAhead; ++u) request(j0 + u * stride, j0 + u * stride < nv, ahead[u]);
     vec_fold<FUSED ? 1 : 0>(s, spmv_partial, nb, 0, pro);
     if (s.done) {
         if (FUSED && blockIdx.x == 0 && threadIdx.x == 0 && s.done == 2) sc->done = 1; // the pending x update has run (OP_ALPHA)
         return;
     }
-    double alpha;
-    if (FUSED) {
-        const double pap = s.sum[0];
-        alpha = s.rho_old / pap;
-        if (blockIdx.x == 0 && threadIdx.x == 0) { // what OP_ALPHA does
-            sc->red[0] = pap;
-            sc->pAp = pap;
-            sc->alpha = alpha;
-        }
-    } else alpha = s.alpha;
-    double rr = 0., rz = 0.;
-    auto row_pair = [&](int64_t j, const Trip &q) {
-        const int64_t i = 2 * j;
-        double id0, id1;
-        if (CODED) {
-            id0 = invd[q.cc & 0xffffu];
-            id1 = invd[q.cc >> 16];
-        } else {
-            id0 = q.iv.x;
-            id1 = q.iv.y;
-        }
-        d2_t rn;
-        rn.x = q.rv.x - alpha * q.tv.x;
-        rn.y = q.rv.y - alpha * q.tv.y;
-#ifndef AVS_EXP_NO_RNT
-        stream_store_k<KEEP>(rn, reinterpret_cast<d2_t *>(r + i));
-#else
-        *reinterpret_cast<d2_t *>(r + i) = rn;
-#endif
-        rr += rn.x * rn.x;
-        rz += rn.x * (id0 * rn.x);
-        rr += rn.y * rn.y;
-        rz += rn.y * (id1 * rn.y);
+    const T alpha = alpha_step<T, S, FUSED>(s, sc);
+    T rr = 0, rz = 0;
+    auto rows = [&](int64_t j, const Trip &q) {
+        const int64_t i = R * j;
+        V iv;
+        if (CODED) for_rows<R>([&](int k) { iv[k] = invd[code_of(q.cc, k)]; });
+        else iv = q.iv;
+        V rn;
+        for_rows<R>([&](int k) { rn[k] = q.rv[k] - alpha * q.tv[k]; });
+        stream_store_k<kKeepR<T, KEEP>>(rn, reinterpret_cast<V *>(r + i));
+        for_rows<R>([&](int k) {
+            rr += rn[k] * rn[k];
+            rz += rn[k] * (iv[k] * rn[k]);
+        });
     };
 #pragma unroll
     for (int u = 0; u < kVecAhead; ++u)
-        if (j0 + u * stride < n2) row_pair(j0 + u * stride, ahead[u]);
-    for (int64_t j = j0 + kVecAhead * stride; j < n2; j += stride) {
+        if (j0 + u * stride < nv) rows(j0 + u * stride, ahead[u]);
+    for (int64_t j = j0 + kVecAhead * stride; j < nv; j += stride) {
         Trip q;
         request(j, true, q);
-        row_pair(j, q);
+        rows(j, q);
     }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const int64_t i = n - 1;
-        const double ri = r[i] - alpha * t[i];
-        r[i] = ri;
-        rr += ri * ri;
-        rz += ri * ((CODED ? invd[dcode[i]] : invd[i]) * ri);
-    }
-    block_sum2(rr, rz, red);
+    if (vec_tail_mine<T>(n))
+        for (int64_t i = vec_tail_begin<T>(n); i < n; ++i) {
+            const T ri = r[i] - alpha * t[i];
+            r[i] = ri;
+            rr += ri * ri;
+            rz += ri * ((CODED ? invd[dcode[i]] : invd[i]) * ri);
+        }
+    double srr = (double)rr, srz = (double)rz;
+    block_sum2(srr, srz, red);
     if (threadIdx.x == 0) {
-        partial[blockIdx.x] = rr;
-        partial[gridDim.x + blockIdx.x] = rz;
+        partial[blockIdx.x] = srr;
+        partial[gridDim.x + blockIdx.x] = srz;
     }
 }
 
@@ -334,87 +420,68 @@ __global__ __launch_bounds__(kBlock) void k_update_r(int64_t n, double *__restri
 // bits everywhere), instead of in a k_reduce launch of its own between the two vector kernels (4.9 us + a launch gap per
 // iteration).  Workgroup 0 publishes the scalars; the old r.z is read from the slot of this iteration's parity and the new
 // one written to the other slot, so a workgroup that starts late still reads what the early ones read.
-template <bool CODED, bool FUSED, bool KEEP>
-__global__ __launch_bounds__(kBlock) void k_update_xp(int64_t n, double *__restrict__ x, double *__restrict__ p,
-                                                      const double *__restrict__ r, const double *__restrict__ invd,
-                                                      const uint16_t *__restrict__ dcode, PcgScalars *sc,
-                                                      const double *__restrict__ partial = nullptr, int g = 0, int parity = 0)
+// The float and mixed loops have only this form.
+template <typename T, typename S, bool CODED, bool FUSED, bool KEEP>
+__global__ __launch_bounds__(kBlock) void k_update_xp(int64_t n, T *__restrict__ x, T *__restrict__ p, const T *__restrict__ r,
+                                                      const T *__restrict__ invd, const uint16_t *__restrict__ dcode, PcgScalars *sc,
+                                                      const double *__restrict__ partial, int g, int parity)
 {
+    static_assert(FUSED || std::is_same<T, double>::value, "the loops on float vectors always take the beta step here");
+    typedef typename Vec16<T>::type V;
+    typedef typename Vec16<T>::codes C;
+    constexpr int R = Vec16<T>::rows;
     __shared__ double pro[8];
-    // two rows per thread: 16-B loads / stores (the arrays are 16-B aligned; the odd last row goes alone)
-    const int64_t n2 = n >> 1;
+    const int64_t nv = n >> Vec16<T>::log2_rows;
     const int64_t j0 = (int64_t)blockIdx.x * kBlock + threadIdx.x, stride = (int64_t)gridDim.x * kBlock;
-    struct Trip { d2_t pv, xv, rv, iv; unsigned cc; };
+    struct Trip { V pv, xv, rv, iv; C cc; };
     auto request = [&](int64_t j, bool live, Trip &q) {
-        const int64_t i = 2 * j;
-        q.pv = *vec_src<d2_t>(live, p + i, sc);
-        q.xv = stream_load_k<KEEP>(vec_src<d2_t>(live, x + i, sc));
-        q.rv = stream_load_k<KEEP>(vec_src<d2_t>(live, r + i, sc));
-        if (CODED) q.cc = stream_load_k<KEEP>(vec_src<unsigned>(live, dcode + i, sc));
-        else q.iv = *vec_src<d2_t>(live, invd + i, sc);
+        const int64_t i = R * j;
+        q.pv = *vec_src<V>(live, p + i, sc);
+        q.xv = stream_load_k<KEEP>(vec_src<V>(live, x + i, sc));
+        q.rv = stream_load_k<KEEP>(vec_src<V>(live, r + i, sc));
+        if (CODED) q.cc = stream_load_k<KEEP>(vec_src<C>(live, dcode + i, sc));
+        else q.iv = *vec_src<V>(live, invd + i, sc);
     };
     VecScalars s = vec_request<FUSED ? 2 : 0>(sc, parity, partial, g, g);
     Trip ahead[kVecAhead];
 #pragma unroll
-    for (int u = 0; u < kVecAhead; ++u) request(j0 + u * stride, j0 + u * stride < n2, ahead[u]);
+    for (int u = 0; u < kVecAhead; ++u) request(j0 + u * stride, j0 + u * stride < nv, ahead[u]);
     vec_fold<FUSED ? 2 : 0>(s, partial, g, g, pro);
     int done = s.done;
     if (done == 1 || done == 3) return;
-    const double alpha = s.alpha;
-    double beta = FUSED ? 0. : s.beta;
-    if (FUSED && done == 0) {
-        const double rr = s.sum[0], rz = s.sum[1];
-        const double absOld = s.rho_old;
-        if (rr < s.threshold) done = 2; // Eigen: break before i++ (x += alpha p still pending)
-        else beta = rz / absOld;
-        if (blockIdx.x == 0 && threadIdx.x == 0) { // what OP_BETA does
-            sc->red[0] = rr;
-            sc->red[1] = rz;
-            sc->rr = rr;
-            if (done == 2) sc->done = 2;
-            else {
-                if (parity) sc->rho = rz;
-                else sc->rho_alt = rz;
-                sc->beta = beta;
-                sc->iter += 1;
-            }
-        }
-    }
+    const T alpha = (T)s.alpha;
+    T beta = FUSED ? T(0) : (T)s.beta;
+    if (FUSED && done == 0) beta = beta_step<T, S>(s, sc, parity, done);
     if (done == 2) { // (the loads that went ahead are dropped)
         for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
             x[i] += alpha * p[i];
         return;
     }
-    auto row_pair = [&](int64_t j, const Trip &q) {
-        const int64_t i = 2 * j;
-        double id0, id1;
-        if (CODED) {
-            id0 = invd[q.cc & 0xffffu];
-            id1 = invd[q.cc >> 16];
-        } else {
-            id0 = q.iv.x;
-            id1 = q.iv.y;
-        }
-        d2_t xn, pn;
-        xn.x = q.xv.x + alpha * q.pv.x;       xn.y = q.xv.y + alpha * q.pv.y;
-        pn.x = id0 * q.rv.x + beta * q.pv.x;  pn.y = id1 * q.rv.y + beta * q.pv.y;
-        stream_store_k<KEEP>(xn, reinterpret_cast<d2_t *>(x + i)); // (x is touched once per iteration)
-        *reinterpret_cast<d2_t *>(p + i) = pn;
+    auto rows = [&](int64_t j, const Trip &q) {
+        const int64_t i = R * j;
+        V iv;
+        if (CODED) for_rows<R>([&](int k) { iv[k] = invd[code_of(q.cc, k)]; });
+        else iv = q.iv;
+        V xn, pn;
+        for_rows<R>([&](int k) { xn[k] = q.xv[k] + alpha * q.pv[k]; });
+        for_rows<R>([&](int k) { pn[k] = iv[k] * q.rv[k] + beta * q.pv[k]; });
+        stream_store_k<KEEP>(xn, reinterpret_cast<V *>(x + i)); // (x is touched once per iteration)
+        *reinterpret_cast<V *>(p + i) = pn;
     };
 #pragma unroll
     for (int u = 0; u < kVecAhead; ++u)
-        if (j0 + u * stride < n2) row_pair(j0 + u * stride, ahead[u]);
-    for (int64_t j = j0 + kVecAhead * stride; j < n2; j += stride) {
+        if (j0 + u * stride < nv) rows(j0 + u * stride, ahead[u]);
+    for (int64_t j = j0 + kVecAhead * stride; j < nv; j += stride) {
         Trip q;
         request(j, true, q);
-        row_pair(j, q);
+        rows(j, q);
     }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const int64_t i = n - 1;
-        const double pi = p[i];
-        x[i] += alpha * pi;
-        p[i] = (CODED ? invd[dcode[i]] : invd[i]) * r[i] + beta * pi;
-    }
+    if (vec_tail_mine<T>(n))
+        for (int64_t i = vec_tail_begin<T>(n); i < n; ++i) {
+            const T pi = p[i];
+            x[i] += alpha * pi;
+            p[i] = (CODED ? invd[dcode[i]] : invd[i]) * r[i] + beta * pi;
+        }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -556,7 +623,7 @@ __global__ __launch_bounds__(kFusedBlock) void k_update_fused(int64_t n, double 
         return;
     }
     pap = ((fold_a[q][0] + fold_a[q][1]) + fold_a[q][2]) + fold_a[q][3];
-    const double alpha = nb ? rho_old / pap : alpha_in; // (nb == 0: the alpha step was a launch of its own, as in front of k_update_r<., false, .>)
+    const double alpha = nb ? rho_old / pap : alpha_in; // (nb == 0: the alpha step was a launch of its own, as in front of k_update_r<., ., ., false, .>)
     // ---- phase 1: r -= alpha t
     d2_t rn[kFusedPairs]; // the new r of the first emulated workgroup's rows: registers
     double rr[2] = {0., 0.}, rz[2] = {0., 0.};
@@ -962,17 +1029,34 @@ static avs_status ensure_partials(PcgWork *w, size_t need)
     return AVS_OK;
 }
 
-// invd (nullptr: not wanted -- the float loop keeps its own) = the inverse of the diagonal; for a `coded` matrix (one dictionary of
-// few values) also the rows' 2-B diagonal codes and the table of inverted values (k_inv_diag_coded; never with tile-local tables)
-static avs_status prepare_diagonal(PcgWork *w, const CsrView &A, bool coded, double *invd, hipStream_t stream)
+// The inverse of the diagonal as the loops on vectors of T read it.  For a `coded` matrix (diag_coded(A): one dictionary of few values;
+// never with tile-local tables) the rows' 2-B diagonal codes and the table of inverted values, else one inverse per row.
+// *inv: what the vector kernels index -- by dcode[i] (coded) or by i.  fp64: w->invd is filled either way (the set-ups read it per row).
+template <typename T>
+static avs_status prepare_diagonal(PcgWork *w, const CsrView &A, bool coded, T **inv, const uint16_t **dcode, hipStream_t stream)
 {
+    constexpr bool F32 = std::is_same<T, float>::value;
     const int64_t n = A.n;
-    if (invd) hipLaunchKernelGGL(k_inv_diag, dim3(row_grid(n)), dim3(kBlock), 0, stream, A, invd);
-    if (!coded) return AVS_OK;
-    if (!w->dcode.p) AVS_TRY(w->dcode.alloc((size_t)n + 8)); // (+ 8: the float loop's vector loads)
-    if (!w->invtab.p) AVS_TRY(w->invtab.alloc((size_t)kViLdsTable + 1));
-    const int cg = (int)(((n > A.table_size + 1 ? n : A.table_size + 1) + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_inv_diag_coded, dim3(cg), dim3(kBlock), 0, stream, A, w->dcode.p, w->invtab.p);
+    if constexpr (!F32) hipLaunchKernelGGL(k_inv_diag<double>, dim3(row_grid(n)), dim3(kBlock), 0, stream, A, w->invd.p);
+    if (coded) {
+        if (!w->dcode.p) AVS_TRY(w->dcode.alloc((size_t)n + 8)); // (+ 8: the float loop's vector loads)
+        if (!w->invtab.p) AVS_TRY(w->invtab.alloc((size_t)kViLdsTable + 1));
+        const int cg = (int)(((n > A.table_size + 1 ? n : A.table_size + 1) + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_inv_diag_coded, dim3(cg), dim3(kBlock), 0, stream, A, w->dcode.p, w->invtab.p);
+    }
+    if constexpr (F32) {
+        if (coded) {
+            AVS_TRY(w->f_invtab.alloc((size_t)kViLdsTable + 1));
+            hipLaunchKernelGGL(k_f32_invtab, dim3((A.table_size + kBlock) / kBlock), dim3(kBlock), 0, stream, A, w->f_invtab.p);
+        } else {
+            AVS_TRY(w->f_invd.alloc((size_t)n + 8));
+            hipLaunchKernelGGL(k_inv_diag<float>, dim3(row_grid(n)), dim3(kBlock), 0, stream, A, w->f_invd.p);
+        }
+        *inv = coded ? w->f_invtab.p : w->f_invd.p;
+    } else {
+        *inv = coded ? w->invtab.p : w->invd.p;
+    }
+    *dcode = coded ? w->dcode.p : nullptr;
     return AVS_OK;
 }
 
@@ -1326,20 +1410,22 @@ static avs_status sr_setup(PcgWork *w, const CsrView &A, const double *b, double
         AVS_TRY(w->f_u.alloc(ne));
         AVS_HIP(hipMemsetAsync(w->f_p.p, 0, na * sizeof(float), stream));
         AVS_HIP(hipMemsetAsync(w->f_s.p, 0, na * sizeof(float), stream));
-        float *inv = nullptr;
-        const uint16_t *dcode = nullptr;
-        AVS_TRY(prepare_diagonal_f32(w, A, coded, &inv, &dcode, stream));
-        *v = {w->f_x.p, w->f_r.p, w->f_p.p, w->f_s.p, w->f_t.p, w->f_u.p, coded ? nullptr : inv, coded ? inv : nullptr, nullptr};
+        *v = {w->f_x.p, w->f_r.p, w->f_p.p, w->f_s.p, w->f_t.p, w->f_u.p, nullptr, nullptr, nullptr};
         w->float_vectors = 1;
     } else {
         AVS_TRY(w->s.alloc((size_t)n));
         AVS_TRY(w->u.alloc((size_t)w->n_ext));
         AVS_HIP(hipMemsetAsync(w->p.p, 0, (size_t)w->n_ext * sizeof(double), stream));
         AVS_HIP(hipMemsetAsync(w->s.p, 0, (size_t)n * sizeof(double), stream));
-        AVS_TRY(prepare_diagonal(w, A, coded, w->invd.p, stream));
-        *v = {x, w->r.p, w->p.p, w->s.p, w->t.p, w->u.p, w->invd.p, coded ? w->invtab.p : nullptr, nullptr};
+        *v = {x, w->r.p, w->p.p, w->s.p, w->t.p, w->u.p, nullptr, nullptr, nullptr};
     }
-    v->dcode = coded ? w->dcode.p : nullptr;
+    {
+        T *inv = nullptr;
+        AVS_TRY(prepare_diagonal<T>(w, A, coded, &inv, &v->dcode, stream));
+        v->invtab = coded ? inv : nullptr;
+        if constexpr (F32) v->invd = coded ? nullptr : inv;
+        else v->invd = w->invd.p; // (the fp64 set-up reads the per-row inverse of a coded matrix too)
+    }
     AVS_HIP(hipEventRecord(w->ev0, stream));
     if constexpr (MIXED) {
         AVS_HIP(hipMemsetAsync(v->x, 0, ((size_t)n + 8) * sizeof(float), stream));
@@ -2218,9 +2304,9 @@ static avs_status fused_vectors_setup(PcgWork *w, const CsrView &A, const double
 //   vectors       caller's x, w->p/r/t, fp64 diagonal    f_x = narrowed x, f_b = narrowed b,    f_x = the correction, zeroed; f_p/r/t;
 //                                                        f_p/r/t, float diagonal                t64 = w->t; float diagonal
 //   partials      grown only for a brick form            max(stream, brick)                     that, and >= 6 kVecGrid + 64
-//   start         spmv_launch, k_init_residual,          float SpMV, k_f32_init_residual,       fp64 SpMV into t64, k_mixed_residual<., true>
+//   start         spmv_launch, k_init_residual,          float SpMV, k_init_residual,           fp64 SpMV into t64, k_mixed_residual<., true>
 //                 OP_INIT, k_init_p, OP_RHO0             OP_INIT, k_f32_threshold,              into vpart, k_mixed_finish<true>,
-//                                                        k_f32_init_p, OP_RHO0                  k_f32_init_p (no reduction)
+//                                                        k_init_p<., coded>, OP_RHO0            k_init_p<., coded> (no reduction)
 //   vpart         upper half only with fuse_alpha        always the upper half                  as float
 //   unfused       update_r: parity 0                     the iteration's parity                 as float
 //   beta step     fuse_beta option, off with dist        always in update_xp                    as float
@@ -2236,6 +2322,7 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
 {
     constexpr bool F32 = std::is_same<T, float>::value;
     static_assert(F32 || !MIXED, "the mixed-precision loop iterates on float vectors");
+    typedef std::conditional_t<MIXED, double, T> S; // the type of the vector kernels' scalar steps
     static_assert(kChunk % 2 == 0, "the parity of an iteration is taken from its position in the chunk");
     const int64_t n = A.n;
     const size_t na = (size_t)n + 8;
@@ -2275,17 +2362,11 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
         hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, b, w->f_b.p);
         hipLaunchKernelGGL(k_f32_narrow, dim3(g), dim3(kBlock), 0, stream, n, (const double *)x, xv);
     }
-    if constexpr (F32) {
-        AVS_TRY(prepare_diagonal_f32(w, A, coded, &inv, &dcode, stream));
-    } else {
-        AVS_TRY(prepare_diagonal(w, A, coded, w->invd.p, stream));
-        inv = coded ? w->invtab.p : w->invd.p;
-        dcode = coded ? w->dcode.p : nullptr;
-    }
+    AVS_TRY(prepare_diagonal<T>(w, A, coded, &inv, &dcode, stream));
     AVS_HIP(hipEventRecord(w->ev0, stream));
 
     // residual = rhs - mat * x ; p = z = D^-1 r ; |b|^2, |r|^2, rho
-    if constexpr (MIXED) { // in fp64, r rounded to float; rho is the fp64 sum (k_f32_init_p's own r.z partials are not used)
+    if constexpr (MIXED) { // in fp64, r rounded to float; rho is the fp64 sum (k_init_p's own r.z partials are not used)
         AVS_TRY(spmv_launch(A, x, t64, variant, stream));
         with_flags([&](auto C) {
             hipLaunchKernelGGL((k_mixed_residual<C.value, true>), dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)t64, r, (const float *)inv,
@@ -2294,7 +2375,7 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
         hipLaunchKernelGGL(k_mixed_finish<true>, dim3(1), dim3(kRedBlock), 0, stream, (const double *)upper, g, sc, tol);
     } else if constexpr (F32) {
         AVS_TRY(product(std::false_type{}, xv, t, nullptr));
-        hipLaunchKernelGGL(k_f32_init_residual, dim3(g), dim3(kBlock), 0, stream, n, w->f_b.p, t, r, partial);
+        hipLaunchKernelGGL(k_init_residual<float>, dim3(g), dim3(kBlock), 0, stream, n, (const float *)w->f_b.p, (const float *)t, r, partial);
         AVS_TRY(reduce_stage(w, g, 2, OP_INIT, tol, 0, stream, nullptr));
         hipLaunchKernelGGL(k_f32_threshold, dim3(1), dim3(1), 0, stream, sc, tol);
     } else {
@@ -2303,13 +2384,18 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
             AVS_TRY(dist_halo_exchange(dist, p, stream));
         }
         AVS_TRY(product(std::false_type{}, dist ? p : x, t, nullptr));
-        hipLaunchKernelGGL(k_init_residual, dim3(g), dim3(kBlock), 0, stream, n, b, t, r, partial);
+        hipLaunchKernelGGL(k_init_residual<double>, dim3(g), dim3(kBlock), 0, stream, n, b, (const double *)t, r, partial);
         AVS_TRY(reduce_stage(w, g, 2, OP_INIT, tol, 0, stream, dist));
-        hipLaunchKernelGGL(k_init_p, dim3(g), dim3(kBlock), 0, stream, n, r, w->invd.p, p, x, partial, sc);
     }
+    // p = z: float vectors read the loop's diagonal, fp64 the per-row inverse, of a coded matrix too
     if constexpr (F32)
-        with_flags([&](auto C) { hipLaunchKernelGGL(k_f32_init_p<C.value>, dim3(g), dim3(kBlock), 0, stream, n, r, inv, dcode, p, xv, partial, sc); },
-                   coded);
+        with_flags([&](auto C) {
+            hipLaunchKernelGGL((k_init_p<float, C.value>), dim3(g), dim3(kBlock), 0, stream, n, (const float *)r, (const float *)inv, dcode, p, xv,
+                               partial, (const PcgScalars *)sc);
+        }, coded);
+    else
+        hipLaunchKernelGGL((k_init_p<double, false>), dim3(g), dim3(kBlock), 0, stream, n, (const double *)r, (const double *)w->invd.p,
+                           (const uint16_t *)nullptr, p, xv, partial, (const PcgScalars *)sc);
     if constexpr (!MIXED) AVS_TRY(reduce_stage(w, g, 1, OP_RHO0, tol, 0, stream, dist));
     AVS_HIP(hipGetLastError());
 
@@ -2363,21 +2449,14 @@ static avs_status pcg_solve_phases(PcgWork *w, const CsrView &A, const double *b
             }
         const int r_parity = (F32 || fuse_alpha) ? parity : 0; // (the unfused fp64 kernel reads what OP_ALPHA left: no parity)
         with_flags([&](auto C, auto FA, auto K) {
-            const double *spart = FA.value ? partial : nullptr;
-            if constexpr (F32)
-                hipLaunchKernelGGL((k_f32_update_r<C.value, FA.value, K.value, MIXED>), dim3(g), dim3(kBlock), 0, stream, n, r, t, inv, dcode, sc, vpart,
-                                   spart, FA.value ? nb : 0, r_parity);
-            else
-                hipLaunchKernelGGL((k_update_r<C.value, FA.value, K.value>), dim3(g), dim3(kBlock), 0, stream, n, r, t, inv, dcode, sc, vpart, spart,
-                                   FA.value ? nb : 0, r_parity);
+            hipLaunchKernelGGL((k_update_r<T, S, C.value, FA.value, K.value>), dim3(g), dim3(kBlock), 0, stream, n, r, (const T *)t, (const T *)inv,
+                               dcode, sc, vpart, FA.value ? (const double *)partial : nullptr, FA.value ? nb : 0, r_parity);
         }, coded, fuse_alpha, keep);
         if (!fuse_beta) AVS_TRY(reduce_stage(w, g, 2, OP_BETA, tol, 1, stream, dist));
         with_flags([&](auto C, auto FB, auto K) {
-            if constexpr (F32)
-                hipLaunchKernelGGL((k_f32_update_xp<C.value, K.value, MIXED>), dim3(g), dim3(kBlock), 0, stream, n, xv, p, r, inv, dcode, sc, vpart, g, parity);
-            else
-                hipLaunchKernelGGL((k_update_xp<C.value, FB.value, K.value>), dim3(g), dim3(kBlock), 0, stream, n, xv, p, r, inv, dcode, sc,
-                                   FB.value ? vpart : nullptr, FB.value ? g : 0, parity);
+            constexpr bool FBK = F32 || FB.value; // (float vectors: fuse_beta is always set, and there is no other kernel)
+            hipLaunchKernelGGL((k_update_xp<T, S, C.value, FBK, K.value>), dim3(g), dim3(kBlock), 0, stream, n, xv, p, (const T *)r, (const T *)inv, dcode,
+                               sc, FBK ? (const double *)vpart : nullptr, FBK ? g : 0, parity);
         }, coded, fuse_beta, keep);
         return AVS_OK;
     };
@@ -2489,25 +2568,17 @@ avs_status pcg_solve(PcgWork *w, const CsrView &A, const double *b, double *x, d
 // probe / test entry: one update_r launch followed by one update_xp launch of the launch-per-phase loops, any instantiation, on a grid
 // of `g` workgroups and a caller's PcgScalars image (the loops reach g < kVecGrid only with one trip per thread, and KEEP = false only
 // beyond the Infinity Cache)
-template <bool CODED, bool FUSED, bool KEEP>
-static void vector_probe_f64(int g, int64_t n, int nb, int parity, double *x, double *p, double *r, const double *t, const double *invd,
-                             const uint16_t *dcode, const double *spmv_partial, double *vpart, PcgScalars *sc, hipStream_t stream)
+template <typename T, typename S, bool CODED, bool FUSED, bool KEEP>
+static void vector_probe(int g, int64_t n, int nb, int parity, T *x, T *p, T *r, const T *t, const T *invd, const uint16_t *dcode,
+                         const double *spmv_partial, double *vpart, PcgScalars *sc, hipStream_t stream)
 {
-    // (the unfused form as pcg_solve launches it: OP_ALPHA / OP_BETA have left the scalars, no parity)
-    hipLaunchKernelGGL((k_update_r<CODED, FUSED, KEEP>), dim3(g), dim3(kBlock), 0, stream, n, r, t, invd, dcode, sc, vpart,
-                       FUSED ? spmv_partial : nullptr, FUSED ? nb : 0, FUSED ? parity : 0);
-    hipLaunchKernelGGL((k_update_xp<CODED, FUSED, KEEP>), dim3(g), dim3(kBlock), 0, stream, n, x, p, (const double *)r, invd, dcode, sc,
-                       FUSED ? (const double *)vpart : nullptr, FUSED ? g : 0, FUSED ? parity : 0);
-}
-template <bool CODED, bool FUSED, bool KEEP, bool DS>
-static void vector_probe_f32(int g, int64_t n, int nb, int parity, float *x, float *p, float *r, const float *t, const float *invd,
-                             const uint16_t *dcode, const double *spmv_partial, double *vpart, PcgScalars *sc, hipStream_t stream)
-{
-    // (the float loops have no unfused k_f32_update_xp: OP_ALPHA, then both kernels with the iteration's parity)
-    hipLaunchKernelGGL((k_f32_update_r<CODED, FUSED, KEEP, DS>), dim3(g), dim3(kBlock), 0, stream, n, r, t, invd, dcode, sc, vpart,
-                       FUSED ? spmv_partial : nullptr, FUSED ? nb : 0, parity);
-    hipLaunchKernelGGL((k_f32_update_xp<CODED, KEEP, DS>), dim3(g), dim3(kBlock), 0, stream, n, x, p, (const float *)r, invd, dcode, sc,
-                       (const double *)vpart, g, parity);
+    // the unfused forms as pcg_solve_phases launches them.  fp64: OP_ALPHA / OP_BETA have left the scalars, no parity.  Float vectors:
+    // there is no unfused k_update_xp -- OP_ALPHA, then both kernels with the iteration's parity
+    constexpr bool F32 = std::is_same<T, float>::value, FX = FUSED || F32;
+    hipLaunchKernelGGL((k_update_r<T, S, CODED, FUSED, KEEP>), dim3(g), dim3(kBlock), 0, stream, n, r, t, invd, dcode, sc, vpart,
+                       FUSED ? spmv_partial : nullptr, FUSED ? nb : 0, FX ? parity : 0);
+    hipLaunchKernelGGL((k_update_xp<T, S, CODED, FX, KEEP>), dim3(g), dim3(kBlock), 0, stream, n, x, p, (const T *)r, invd, dcode, sc,
+                       FX ? (const double *)vpart : nullptr, FX ? g : 0, FX ? parity : 0);
 }
 __global__ __launch_bounds__(kBlock) void k_probe_max_code(int64_t n, const uint16_t *__restrict__ dcode, unsigned long long *__restrict__ top)
 {
@@ -2548,12 +2619,14 @@ avs_status vector_update_probe(int flags, int g, int64_t n, int nb, int parity, 
         return AVS_OK;
     }
     with_flags([&](auto C, auto F, auto K) {
-        if (!f32) vector_probe_f64<C.value, F.value, K.value>(g, n, nb, parity, (double *)x, (double *)p, (double *)r, (const double *)t,
-                                                                (const double *)invd, dcode, spmv_partial, vpart, sc, stream);
-        else if (ds) vector_probe_f32<C.value, F.value, K.value, true>(g, n, nb, parity, (float *)x, (float *)p, (float *)r, (const float *)t,
-                                                                       (const float *)invd, dcode, spmv_partial, vpart, sc, stream);
-        else vector_probe_f32<C.value, F.value, K.value, false>(g, n, nb, parity, (float *)x, (float *)p, (float *)r, (const float *)t,
-                                                                (const float *)invd, dcode, spmv_partial, vpart, sc, stream);
+        auto launch = [&](auto tv, auto sv) {
+            typedef decltype(tv) T;
+            vector_probe<T, decltype(sv), C.value, F.value, K.value>(g, n, nb, parity, (T *)x, (T *)p, (T *)r, (const T *)t, (const T *)invd, dcode,
+                                                                     spmv_partial, vpart, sc, stream);
+        };
+        if (!f32) launch(0., 0.);
+        else if (ds) launch(0.f, 0.);
+        else launch(0.f, 0.f);
     }, (flags & AVS_VECTOR_PROBE_CODED) != 0, (flags & AVS_VECTOR_PROBE_FUSED) != 0, (flags & AVS_VECTOR_PROBE_KEEP) != 0);
     AVS_HIP(hipGetLastError());
     return AVS_OK;

@@ -90,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_mixed_residual(int64_t n, const doub
 
 // The scalar step of an update (one workgroup): folds k_mixed_residual's partial sums in a fixed order and applies the fp64 test.
 // INIT: the start of the solve (what OP_INIT + OP_RHO0 do for the fp64 loop).  Else: `done` on entry tells whether the recurrence froze
-// the chunk (1 / 2); sc->rho holds the r.z the frozen iteration started from (k_f32_update_xp<.., DS> leaves it there for both parities).
+// the chunk (1 / 2); sc->rho holds the r.z the frozen iteration started from (beta_step<float, double> of k_update_xp leaves it there for both parities).
 // red[3] = 1: p still owes its beta step (k_mixed_pstep, sc->beta), 0: not.  The next chunk starts at an even position: it reads sc->rho.
 template <bool INIT>
 __global__ __launch_bounds__(kRedBlock) void k_mixed_finish(const double *__restrict__ partial, int g, PcgScalars *sc, double tol)

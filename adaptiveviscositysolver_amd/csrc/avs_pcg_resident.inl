@@ -104,7 +104,7 @@ template <typename T> struct ResidentArgs {
     // a word's code indexes the table of the GROUP its row belongs to -- the whole workgroup (ltab_gpw = 1) or the wave that sums the
     // row (16) --, the distinct value bit patterns of the group's rows in ascending order, entry 0 = +0 (what the padding words
     // multiply with: table_size is 0 there).  `table` then holds the groups' tables back to back, and `invtab` ONE INVERSE
-    // PER ROW (the launch-per-phase loops' k_inv_diag / k_f32_inv_diag array: no LDS at all; dcode is not read)
+    // PER ROW (the launch-per-phase loops' k_inv_diag<T> array: no LDS at all; dcode is not read)
     const int32_t *ltab_cnt;              // G x ltab_gpw: entries of every group's table
     const int32_t *ltab_off;              // ... and where it starts in `table` (G x ltab_gpw + 1)
     int ltab_gpw;
@@ -423,10 +423,6 @@ __global__ __launch_bounds__(kResThreads) void k_resident_stream_layout(const in
 // boundaries: the inner loop is decode, two LDS reads and one FMA per word, and one end-of-row test per quad.  (Measured on the
 // 8-way partition of the 512^3 system, tools/probes/rowlen_local.py: rows of 2 / 12 / 15 / 17 / 18 / 20 / 26 words make up 97 %;
 // quads + <= 6 rows per lane need 0.89-0.92 of the chip's 262,144 lanes; slots of 15 or 18 words would need 1.06.)
-template <typename T> struct ResVec16;           // 16 B of T: the unit of the write-through stores of u
-template <> struct ResVec16<double> { typedef d2_t type; };
-template <> struct ResVec16<float> { typedef f4_t type; };
-
 // LT: local value tables (ResidentArgs::ltab_cnt): every wave reads the table of its group, the inverse diagonal comes per row.
 template <int NG, bool STREAM, typename T, bool LT = false>
 __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
@@ -639,7 +635,7 @@ __global__ __launch_bounds__(kResThreads) void k_cg_resident(ResidentArgs<T> a)
                 __hip_atomic_store(gu + wrow0 + tid, u_l[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int groups = (wrows - head) >> (K == 2 ? 1 : 2);
             for (int i = tid; i < groups; i += kResThreads) {
-                typename ResVec16<T>::type v;
+                typename Vec16<T>::type v; // the unit of the write-through stores of u
 #pragma unroll
                 for (int k = 0; k < K; ++k) v[k] = u_l[head + K * i + k];
                 res_store_wt16(gu + wrow0 + head + K * i, v);

@@ -19,6 +19,16 @@ typedef int i2_t __attribute__((ext_vector_type(2)));
 typedef unsigned short us4_t __attribute__((ext_vector_type(4)));
 typedef int i4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
+typedef float f4_t __attribute__((ext_vector_type(4)));
+typedef unsigned u2_t __attribute__((ext_vector_type(2)));
+
+// 16 B of a vector of T -- the unit of the vector kernels' accesses and of the resident kernel's write-through stores: `rows` rows,
+// and the rows' 2-B diagonal codes as `codes` (two codes per 32-bit word, the even row's in the low half)
+template <typename T> struct Vec16;
+template <> struct Vec16<double> { typedef d2_t type; typedef unsigned codes; static constexpr int rows = 2, log2_rows = 1; };
+template <> struct Vec16<float> { typedef f4_t type; typedef u2_t codes; static constexpr int rows = 4, log2_rows = 2; };
+__device__ __forceinline__ unsigned code_of(unsigned words, int k) { return k & 1 ? words >> 16 : words & 0xffffu; }
+__device__ __forceinline__ unsigned code_of(u2_t words, int k) { return code_of(k < 2 ? words.x : words.y, k); }
 
 // ---------------------------------------------------------------------------------------------
 // block reduction helpers (wave64 shuffles, then LDS across the 4 waves of a 256-thread block)

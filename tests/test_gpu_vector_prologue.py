@@ -1,5 +1,4 @@
-"""The two vector kernels of the launch-per-phase PCG loops (k_update_r / k_update_xp, k_f32_update_r / k_f32_update_xp: csrc/avs_pcg.hip,
-csrc/avs_pcg_f32.inl) against a NumPy model of their arithmetic, bit for bit, through avs_vector_update_probe (libavs_probe.so).
+"""The two vector kernels of the launch-per-phase PCG loops (k_update_r / k_update_xp<T, S, ...>: csrc/avs_pcg.hip) against a NumPy model of their arithmetic, bit for bit, through avs_vector_update_probe (libavs_probe.so).
 
 The kernels start their first D grid-stride trips' loads before the scalar prologue (the fold of the partial sums, alpha / beta); the
 shapes below put 0, 1, D, D + 1 and D + 2 trips into one launch, leave workgroups without work and end in odd tails.  The model was

@@ -56,11 +56,27 @@ def test_nontemporal_hints_are_in_the_instruction_stream():
         found = isa_check.kernels_matching(pattern)
         assert found, pattern
         return {k: [i for i in ins if i.startswith("global_") and i.split()[-1] == "nt"] for k, ins in found.items()}
-    for k, ops in nt_ops(r"avs::k_update_xp<true, true, false>").items():
+    # <T, S, CODED, FUSED, KEEP>: the fp64 loop, then the float (S = float) and mixed-precision (S = double) loops on float vectors
+    for k, ops in nt_ops(r"avs::k_update_xp<double, double, true, true, false>").items():
         assert sum(o.startswith("global_load") for o in ops) >= 3 and any(o.startswith("global_store") for o in ops), (k, ops)
-    for k, ops in nt_ops(r"avs::k_update_r<true, false, false>").items():
+    for k, ops in nt_ops(r"avs::k_update_r<double, double, true, false, false>").items():
         assert sum(o.startswith("global_load") for o in ops) >= 2, (k, ops)
-    for k, ops in {**nt_ops(r"avs::k_update_xp<true, true, true>"), **nt_ops(r"avs::k_update_r<true, false, true>")}.items():
+    for k, ops in {**nt_ops(r"avs::k_update_xp<double, double, true, true, true>"),
+                   **nt_ops(r"avs::k_update_r<double, double, true, false, true>")}.items():
         assert not ops, (k, ops)   # matrix + vectors fit the Infinity Cache: everything is left to it
+    for S in ("float", "double"):
+        found = nt_ops(rf"avs::k_update_xp<float, {S}, (true|false), true, false>")
+        assert len(found) == 2, found.keys()
+        for k, ops in found.items():   # x, r (two trips each) and the codes; the store of x
+            assert sum(o.startswith("global_load") for o in ops) >= 3 and any(o.startswith("global_store") for o in ops), (k, ops)
+        found = nt_ops(rf"avs::k_update_r<float, {S}, (true|false), (true|false), false>")
+        assert len(found) == 4, found.keys()
+        for k, ops in found.items():   # t and the codes (the float kernels load and store r plainly)
+            assert sum(o.startswith("global_load") for o in ops) >= 2, (k, ops)
+        found = {**nt_ops(rf"avs::k_update_xp<float, {S}, (true|false), true, true>"),
+                 **nt_ops(rf"avs::k_update_r<float, {S}, (true|false), (true|false), true>")}
+        assert len(found) == 6, found.keys()
+        for k, ops in found.items():
+            assert not ops, (k, ops)
     for k, ops in nt_ops(r"avs::k_spmv_vi2<512, 4096, true, true, true, 512, 0, false, false, false>").items():
         assert sum(o.startswith("global_load") for o in ops) >= 2, (k, ops)

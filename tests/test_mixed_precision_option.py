@@ -48,8 +48,15 @@ def test_the_value_type_is_a_template_parameter_of_the_kernels():
     assert re.search(r"template <bool DOT, bool VC = false, typename T = double, typename V = T>\s*\n__global__[^\n]*void k_spmv_brick", brick)
     f32 = _read("adaptiveviscositysolver_amd", "csrc", "avs_pcg_f32.inl")
     assert re.search(r"template <bool DOT, typename V = float>\s*\n__global__[^\n]*void k_f32_spmv_csr", f32)
-    assert re.search(r"template <bool CODED, bool FUSED, bool KEEP, bool DS = false>\s*\n__global__[^\n]*void k_f32_update_r", f32)
-    assert re.search(r"template <bool CODED, bool KEEP, bool DS = false>\s*\n__global__[^\n]*void k_f32_update_xp", f32)
+    # the vector kernels: one body each, the vector type T and the scalar type S are template parameters (mixed: <float, double>)
+    pcg = _read("adaptiveviscositysolver_amd", "csrc", "avs_pcg.hip")
+    assert re.search(r"template <typename T, typename S, bool CODED, bool FUSED, bool KEEP>\s*\n__global__[^\n]*void k_update_r\(", pcg)
+    assert re.search(r"template <typename T, typename S, bool CODED, bool FUSED, bool KEEP>\s*\n__global__[^\n]*void k_update_xp\(", pcg)
+    assert len(re.findall(r"void k_update_r\(", pcg)) == 1 and len(re.findall(r"void k_update_xp\(", pcg)) == 1
+    for name in sorted(os.listdir(os.path.join(ROOT, "adaptiveviscositysolver_amd", "csrc"))):   # (the sources: not what a build leaves there)
+        if name.endswith((".hip", ".inl", ".hpp", ".cpp", ".h")):
+            text = _read("adaptiveviscositysolver_amd", "csrc", name)
+            assert "k_f32_update_r" not in text and "k_f32_update_xp" not in text, name
     mixed = _read("adaptiveviscositysolver_amd", "csrc", "avs_pcg_mixed.inl")
     assert "k_mixed_fold" in mixed and "k_mixed_residual" in mixed
     assert '#include "avs_pcg_mixed.inl"' in _read("adaptiveviscositysolver_amd", "csrc", "avs_pcg.hip")
