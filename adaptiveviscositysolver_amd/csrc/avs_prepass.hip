@@ -25,6 +25,7 @@
 #include <new>
 
 #include "avs_device_common.hpp"
+#include "avs_refine.hpp"
 
 namespace avs {
 
@@ -371,12 +372,18 @@ __device__ __forceinline__ void mark_group(const TileGrid &tg, uint8_t *__restri
 // Level-0 labels and mask; V cells per thread along x (V = 4: one 16-B load, two 4-B stores -- one-byte stores per thread kept the kernel at
 // 2.7 TB/s).  `faces`: also marks the tiles of the level-0 face lattices by the SDF rule (cpp:907) -- the classification's occupancy pass
 // used to read the 4.3-GB SDF of a 1024^3 grid a second time for exactly this comparison.
-template <int V>
+// `inner`: dx * max(2, fine bandwidth), cpp:259-261 (the reference's own build always gets 2: its getter does not match the UI token;
+// AVS_PREPASS_OPTION_FINE_BANDWIDTH).  FLAGGED (avs_prepass_set_refinement): a deep cell the solid rule would coarsen stays fine where its
+// bit of R.bits is set -- the V = 4 cells of a thread lie in one word -- and the cells this changes are counted, one atomic per wave
+// (avs_refine.hpp: spread over kRefinedSlots words).
+// Without flags the other instantiation runs: R is not read.
+template <int V, bool FLAGGED>
 __global__ __launch_bounds__(kBlock) void k_mask_labels(const float *__restrict__ liquid, const float *__restrict__ solid,
-                                                        Box3 box, double dx, double extrapolation, int8_t *__restrict__ mask,
-                                                        int8_t *__restrict__ labels, Grid3 g, Grid3 sim, TileSets T, double occ_sdf, int faces)
+                                                        Box3 box, double dx, double inner, double extrapolation, int8_t *__restrict__ mask,
+                                                        int8_t *__restrict__ labels, Grid3 g, Grid3 sim, TileSets T, double occ_sdf, int faces, RefineView R)
 {
-    const double inner = dx * 2., outer = 3. * dx; // cpp:259-262 (fine bandwidth getter mismatch => 2)
+    const double outer = 3. * dx; // cpp:262
+    int refined = 0;
     Box3 bx = box;
     bx.n[0] /= V; // groups of V cells
     const size_t n = bx.vol();
@@ -406,7 +413,10 @@ __global__ __launch_bounds__(kBlock) void k_mask_labels(const float *__restrict_
                 sv[0] = liquid[o];
                 if (solid) so[0] = solid[o];
             }
+            // FLAGGED: the word that holds the cells' bits, asked for with the SDFs (behind the rule it would be a second round trip)
+            const uint32_t fword = FLAGGED ? R.bits[((size_t)ck * g.r[1] + cj) * R.wx + (ci >> 5)] : 0u;
             int8_t mk[V], lb[V];
+            unsigned coarse = 0u; // FLAGGED: the cells the rule below coarsens
 #pragma unroll
             for (int u = 0; u < V; ++u) {
                 const double sdf = (double)sv[u];
@@ -423,6 +433,21 @@ __global__ __launch_bounds__(kBlock) void k_mask_labels(const float *__restrict_
                 mk[u] = (int8_t)m;
                 lb[u] = (int8_t)(m == 0 ? AVS_ACTIVE : (m < 0 ? AVS_UP : AVS_INACTIVE)); // oct.cpp:383-388
                 if (sdf < occ_sdf) hits |= 1u << u;
+                if (FLAGGED && m < 0) coarse |= 1u << u;
+            }
+            if (FLAGGED && coarse) {
+                const unsigned keep = coarse & (fword >> (ci & 31));
+#pragma unroll
+                for (int u = 0; u < V; ++u)
+                    if ((keep >> u) & 1u) {
+                        mk[u] = 0;
+                        lb[u] = (int8_t)AVS_ACTIVE;
+                    }
+#pragma unroll
+                for (int u = 0; u < V; ++u) {
+                    const int c = R.axis == 0 ? ci + u : (R.axis == 1 ? cj : ck);
+                    refined += ((keep >> u) & 1u) && c >= R.lo && c < R.hi;
+                }
             }
             if (V == 4) {
                 *reinterpret_cast<uint32_t *>(mask + o) = (uint32_t)(uint8_t)mk[0] | ((uint32_t)(uint8_t)mk[1 % V] << 8) | ((uint32_t)(uint8_t)mk[2 % V] << 16) | ((uint32_t)(uint8_t)mk[3 % V] << 24);
@@ -438,6 +463,14 @@ __global__ __launch_bounds__(kBlock) void k_mask_labels(const float *__restrict_
             mark_group(T.tg[0][1], T.occ[0][1], ci, cj, ck, V, hits, 0, 1, 0);
             mark_group(T.tg[0][2], T.occ[0][2], ci, cj, ck, V, hits, 0, 0, 1);
         }
+    }
+    if (FLAGGED) { // (whole waves leave the loop together)
+        // the wave's sum, bit plane by bit plane through ballots: a wave lives for one group of cells, most have nothing to add and leave at
+        // the first ballot, the others need three planes -- a chain of six shuffles at the end of EVERY wave cost the kernel a quarter
+        unsigned long long total = 0;
+        for (int b = 0; __ballot((refined >> b) != 0) != 0ull; ++b) total += (unsigned long long)__popcll(__ballot((refined >> b) & 1)) << b;
+        const unsigned slot = (blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (unsigned)(kRefinedSlots - 1);
+        if ((threadIdx.x & 63) == 0 && total) atomicAdd(R.refined + (size_t)slot * kRefinedStride, total);
     }
 }
 
@@ -1082,6 +1115,8 @@ struct avs_prepass {
     avs::CheckScratch check; // avs_prepass_check_octree (avs_check.hip)
     avs::StressCheckScratch stress_check; // avs_prepass_check_stress_indices (avs_stress_check.hip)
     double ms[4] = {0, 0, 0, 0};
+    double fine_bandwidth = 2.; // AVS_PREPASS_OPTION_FINE_BANDWIDTH
+    avs::RefineState refine;    // avs_prepass_set_refinement (avs_refine.hip)
     bool ready = false;
 };
 
@@ -1304,6 +1339,84 @@ avs_status avs_prepass_get_window(avs_prepass *p, int32_t *lo, int32_t *hi, int6
     return AVS_OK;
 }
 
+avs_status avs_prepass_set_option(avs_prepass *p, avs_prepass_option option, double value)
+{
+    AVS_REQUIRE(p, AVS_EINVAL, "null argument");
+    AVS_REQUIRE(option == AVS_PREPASS_OPTION_FINE_BANDWIDTH, AVS_EINVAL, "avs_prepass_set_option: unknown option %d", (int)option);
+    AVS_REQUIRE(std::isfinite(value), AVS_EINVAL, "avs_prepass_set_option: the fine bandwidth must be finite");
+    p->fine_bandwidth = value;
+    return AVS_OK;
+}
+
+// the refinement flags: protocol in include/avs.h, bit lattice and kernels in avs_refine.hip
+avs_status avs_prepass_set_refinement(avs_prepass *p, const float *indicator, float threshold, int32_t dilate_cells, avs_memspace where)
+{
+    (void)hipGetLastError(); // (a stale error of the host application's own HIP calls on this thread is not ours: see OptScope)
+    AVS_REQUIRE(p, AVS_EINVAL, "null argument");
+    if (!indicator) { // off: the lattice stays allocated
+        p->refine.active = false;
+        p->refine.seeds = p->refine.flagged = 0;
+        p->refine.dilate = 0;
+        p->refine.threshold = 0.f;
+        p->refine.set_ms = 0.;
+        return AVS_OK;
+    }
+    AVS_REQUIRE(dilate_cells >= 0 && dilate_cells <= 16, AVS_EINVAL, "avs_prepass_set_refinement: dilate_cells %d outside 0 .. 16", dilate_cells);
+    AVS_REQUIRE(where == AVS_MEM_HOST || where == AVS_MEM_DEVICE, AVS_EINVAL, "avs_prepass_set_refinement: unknown memory space %d", (int)where);
+    AVS_HIP(hipSetDevice(p->desc.device));
+    const avs_prepass_desc &d = p->desc;
+    const int sim[3] = {d.field_nx, d.field_ny, d.field_nz}, oct[3] = {d.nx, d.ny, d.nz};
+    DevBuf<float> staged;
+    const float *src = indicator;
+    if (where == AVS_MEM_HOST) {
+        const size_t ns = (size_t)sim[0] * sim[1] * sim[2];
+        AVS_TRY(staged.alloc(ns));
+        AVS_HIP(copy_in(staged.p, indicator, ns * sizeof(float), where, p->stream));
+        src = staged.p;
+    }
+    Scope scope("Build Refinement Flags");
+    return avs::refine_set(p->refine, src, sim, oct, threshold, dilate_cells, p->stream); // (drains the stream: `staged` may go)
+}
+
+avs_status avs_prepass_get_refinement(avs_prepass *p, int8_t *flags, avs_memspace where)
+{
+    (void)hipGetLastError();
+    AVS_REQUIRE(p && flags, AVS_EINVAL, "null argument");
+    AVS_REQUIRE(where == AVS_MEM_HOST || where == AVS_MEM_DEVICE, AVS_EINVAL, "avs_prepass_get_refinement: unknown memory space %d", (int)where);
+    AVS_HIP(hipSetDevice(p->desc.device));
+    const int oct[3] = {p->desc.nx, p->desc.ny, p->desc.nz};
+    const size_t cells = (size_t)oct[0] * oct[1] * oct[2];
+    DevBuf<int8_t> staged;
+    int8_t *dst = flags;
+    if (where == AVS_MEM_HOST) {
+        AVS_TRY(staged.alloc(cells));
+        dst = staged.p;
+    }
+    AVS_TRY(avs::refine_expand(p->refine, oct, dst, p->stream));
+    if (where == AVS_MEM_HOST) AVS_HIP(copy_out(flags, staged.p, cells, where, p->stream));
+    AVS_HIP(hipStreamSynchronize(p->stream));
+    return AVS_OK;
+}
+
+avs_status avs_prepass_get_refinement_info(avs_prepass *p, avs_refinement_info *info)
+{
+    AVS_REQUIRE(p && info, AVS_EINVAL, "null argument");
+    AVS_REQUIRE(info->struct_size >= (int32_t)sizeof(int32_t) && info->struct_size <= 4096, AVS_EINVAL,
+                "avs_prepass_get_refinement_info: struct_size %d out of range", info->struct_size);
+    avs_refinement_info r{};
+    r.struct_size = info->struct_size;
+    r.dilate_cells = p->refine.dilate;
+    r.threshold = p->refine.threshold;
+    r.active = p->refine.active ? 1 : 0;
+    r.seeds = p->refine.seeds;
+    r.flagged = p->refine.flagged;
+    r.refined = p->refine.refined;
+    r.set_ms = p->refine.set_ms;
+    const size_t nbytes = (size_t)info->struct_size < sizeof(r) ? (size_t)info->struct_size : sizeof(r);
+    memcpy(info, &r, nbytes);
+    return AVS_OK;
+}
+
 void avs_prepass_destroy(avs_prepass *p)
 {
     if (!p) return;
@@ -1501,12 +1614,19 @@ avs_status avs_prepass_run(avs_prepass *p, const float *liquid, const float *sol
     {
         const Box3 b0 = cell_box(0, v_lo[0], v_hi[0]);
         const TileSets T0 = tile_sets(0);
-        if ((b0.lo[0] & 3) == 0 && (b0.n[0] & 3) == 0 && (r0[0] & 3) == 0)
-            hipLaunchKernelGGL(k_mask_labels<4>, dim3(grid_for(b0.vol() / 4)), dim3(kBlock), 0, st, p->liq, p->sol, b0, d.dx, extrapolation, p->mask.p,
-                               p->labels[0].p, g3(r0), g3(s0), T0, occ_sdf, 1);
-        else
-            hipLaunchKernelGGL(k_mask_labels<1>, dim3(grid_for(b0.vol())), dim3(kBlock), 0, st, p->liq, p->sol, b0, d.dx, extrapolation, p->mask.p,
-                               p->labels[0].p, g3(r0), g3(s0), T0, occ_sdf, 1);
+        const double inner = d.dx * (p->fine_bandwidth > 2. ? p->fine_bandwidth : 2.); // SYSmax(2., fpreal(getFineBandwidth())), cpp:259-261
+        const bool vec = (b0.lo[0] & 3) == 0 && (b0.n[0] & 3) == 0 && (r0[0] & 3) == 0;
+        const unsigned gm = vec ? grid_for(b0.vol() / 4) : grid_for(b0.vol());
+        RefineView R{};
+        p->refine.refined = 0;
+        const bool flagged = p->refine.active;
+        if (flagged) { // `refined` counts inside the rank's index window (all of the lattice without slabs)
+            R = RefineView{p->refine.bits.p, p->refine.wx, sa, win_lo[0], win_hi[0], p->refine.counters.p + kRefinedBase};
+            AVS_HIP(hipMemsetAsync(R.refined, 0, (size_t)kRefinedSlots * kRefinedStride * sizeof(unsigned long long), st));
+        }
+        auto mask_kernel = vec ? (flagged ? k_mask_labels<4, true> : k_mask_labels<4, false>) : (flagged ? k_mask_labels<1, true> : k_mask_labels<1, false>);
+        hipLaunchKernelGGL(mask_kernel, dim3(gm), dim3(kBlock), 0, st, p->liq, p->sol, b0, d.dx, inner, extrapolation, p->mask.p, p->labels[0].p, g3(r0),
+                           g3(s0), T0, occ_sdf, 1, R);
     }
     for (int l = 0; l < L - 1; ++l) {
         int r[3], rp[3];
@@ -1532,6 +1652,15 @@ avs_status avs_prepass_run(avs_prepass *p, const float *liquid, const float *sol
     int hflags[AVS_MAX_LEVELS] = {};
     int capped = L; // every level is classified: the flags come out of the classification's occupancy pass (k_mark_tiles_all)
     p->ms[1] = t.stop();
+    if (p->refine.active) { // the mask kernel's count of the cells the refinement flags kept fine
+        static_assert(sizeof(unsigned long long) == 8, "slot stride in bytes");
+        unsigned long long h[kRefinedSlots * kRefinedStride];
+        AVS_HIP(hipMemcpyAsync(h, p->refine.counters.p + kRefinedBase, sizeof(h), hipMemcpyDeviceToHost, st));
+        AVS_HIP(hipStreamSynchronize(st));
+        unsigned long long sum = 0;
+        for (int k = 0; k < kRefinedSlots; ++k) sum += h[k * kRefinedStride];
+        p->refine.refined = (int64_t)sum;
+    }
     for (int k = 0; k < 4; ++k) p->counts[k] = 0;
 
     // ---- P4 classification -----------------------------------------------------------------

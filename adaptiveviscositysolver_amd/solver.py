@@ -1032,6 +1032,46 @@ class DevicePrepass:
         L = self.info.levels if self.info is not None else 8
         return lo[:L], hi[:L], tuple(int(v) for v in nw)
 
+    def set_option(self, option, value):
+        """avs_prepass_set_option: capi.PREPASS_OPTION_FINE_BANDWIDTH -- the reference's "Fine Layer Bandwidth" (cells within
+        dx * max(2, value) inside the surface stay fine); takes effect at the next run."""
+        capi.check(self.lib.avs_prepass_set_option(self.h, int(option), float(value)))
+
+    def set_refinement(self, field=None, threshold=0.0, dilate=0):
+        """avs_prepass_set_refinement: the cells of `field` (simulation grid, float32, numpy array or torch tensor, host or device --
+        ViscositySolve.shear_rate_field(device_array=True) plugs in) above `threshold`, dilated by `dilate` cells, stay fine in every
+        following run wherever the surface rule would coarsen them.  field None: no refinement."""
+        if field is None:
+            capi.check(self.lib.avs_prepass_set_refinement(self.h, None, 0.0, 0, capi.MEM_HOST))
+            return
+        if isinstance(field, np.ndarray):
+            field = np.ascontiguousarray(field, np.float32)
+        else:
+            import torch
+            if field.dtype != torch.float32:
+                raise ValueError("the indicator must be float32")
+            field = field.contiguous()
+            if field.is_cuda:   # (the library reads it on the pre-pass's stream)
+                torch.cuda.current_stream(field.device).synchronize()
+        n = self.field_res[0] * self.field_res[1] * self.field_res[2]
+        if int(field.size if isinstance(field, np.ndarray) else field.numel()) != n:
+            raise ValueError(f"the indicator must have the {self.field_res} cells of the simulation grid")
+        ptr, where = capi.ptr_of(field)
+        capi.check(self.lib.avs_prepass_set_refinement(self.h, ptr, float(threshold), int(dilate), where))
+
+    def refinement(self):
+        """The refinement flags (0 / 1) on the octree centre lattice, shaped like mask()."""
+        out = np.empty(self._shape(2, 0, 0), np.int8)
+        capi.check(self.lib.avs_prepass_get_refinement(self.h, out.ctypes.data, capi.MEM_HOST))
+        return out
+
+    def refinement_info(self):
+        """avs_refinement_info: threshold, dilate_cells, active, the set call's seeds / flagged counts and time, the last run's refined"""
+        info = capi.RefinementInfo()
+        info.struct_size = C.sizeof(capi.RefinementInfo)
+        capi.check(self.lib.avs_prepass_get_refinement_info(self.h, C.byref(info)))
+        return info
+
     def apply(self, solver):
         capi.check(self.lib.avs_prepass_apply(self.h, solver.h))
         solver.counts = (self.info.n_velocity, self.info.n_edge, self.info.n_center)

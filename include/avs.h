@@ -142,7 +142,9 @@ const char *avs_version(void);
  * Purely additive since (no revision): the entries avs_get_strain_rates and avs_get_shear_rate_field.
  * Purely additive since (no revision): the entries avs_check_solution and avs_check_csr_solution.
  * Purely additive since (no revision): the entries avs_estimate_spectrum and avs_estimate_csr_spectrum.
- * Purely additive since (no revision): the entry avs_apply_viscosity_model. */
+ * Purely additive since (no revision): the entry avs_apply_viscosity_model.
+ * Purely additive since (no revision): the entries avs_prepass_set_option, avs_prepass_set_refinement, avs_prepass_get_refinement and
+ *   avs_prepass_get_refinement_info. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -879,6 +881,43 @@ typedef struct {
     double weights_ms, octree_ms, classify_ms, number_ms;
 } avs_prepass_info;
 avs_status avs_prepass_create(const avs_prepass_desc *desc, avs_prepass **out);
+/* Options of the refinement mask (cpp:815-867); they take effect at the next avs_prepass_run.
+ *   AVS_PREPASS_OPTION_FINE_BANDWIDTH  the reference's "Fine Layer Bandwidth": cells within inner = dx * max(2, value) INSIDE the liquid
+ *     surface stay fine (SYSmax(2., fpreal(getFineBandwidth())), cpp:259-261); inner also enters the solid rule, solid > -inner -
+ *     extrapolation (cpp:853).  Default 2, and anything <= 2 behaves as 2 -- which is all the reference's own build ever gets: its getter
+ *     does not match the UI token.  The outer band stays 3 dx.  A non-finite value or an unknown option: AVS_EINVAL, nothing
+ *     changes. */
+typedef enum { AVS_PREPASS_OPTION_FINE_BANDWIDTH = 0 } avs_prepass_option;
+avs_status avs_prepass_set_option(avs_prepass *pp, avs_prepass_option option, double value);
+/* Indicator-driven refinement: keep the octree fine where a field the host paints says so -- a shear band, a steep viscosity gradient
+ * deep inside the liquid, which the surface rule coarsens as far as the grading allows.
+ *   indicator: centre lattice of the SIMULATION grid (field_nx x field_ny x field_nz, x fastest) -- the lattice of the SDFs given to
+ *     avs_prepass_run and of avs_get_shear_rate_field.  NULL = no refinement (the default); the other arguments are then ignored.
+ *   A SEED is a cell with indicator > threshold (a float compare: NaN never marks, +inf does).  The FLAGS are all simulation-grid cells
+ *   within Chebyshev (box) distance dilate_cells (0 .. 16) of a seed; cells of the padded octree lattice outside the simulation grid are
+ *   never flagged.  The call computes the flags at once, over the whole lattice (slab-local mode included: a rank's window reads them), on
+ *   the pre-pass's stream, and returns when they are there; the pre-pass keeps them -- one bit per cell, allocated by the first call --
+ *   not the caller's array, for every following run until they are replaced or cleared.
+ *   Mask rule of avs_prepass_run: a DEEP cell (sdf <= -inner), which gets mask 0 if the solid rule passes and -1 (coarsen) otherwise, gets
+ *   mask 0 if the solid rule passes OR the cell is flagged.  A flag anywhere else has no effect; octree passes, grading, level cap,
+ *   classification and numbering are what they are without flags.
+ *   dilate_cells outside 0 .. 16 or an unknown memory space: AVS_EINVAL, nothing changes and nothing is launched.
+ * avs_prepass_get_refinement: the flags as 0 / 1 on the OCTREE centre lattice (nx * ny * nz, the lattice of avs_prepass_get_mask); all
+ *   zero before the first set call and after a clearing one.
+ * avs_refinement_info (struct_size: IN, only that many bytes are written): seeds and flagged are the counts of the set call (0 when
+ *   cleared); refined is the number of cells of the last avs_prepass_run whose mask the flags changed from -1 to 0 (slab-local mode: inside
+ *   the rank's window); set_ms the HIP-event time of the set call's kernels (a host indicator's upload not included). */
+avs_status avs_prepass_set_refinement(avs_prepass *pp, const float *indicator, float threshold, int32_t dilate_cells, avs_memspace where);
+avs_status avs_prepass_get_refinement(avs_prepass *pp, int8_t *flags /* octree centre lattice nx*ny*nz, 0 / 1 */, avs_memspace where);
+typedef struct {
+    int32_t struct_size;  /* IN: sizeof(avs_refinement_info) of the caller's header */
+    int32_t dilate_cells;
+    float threshold;
+    int32_t active;       /* 1: flags are set */
+    int64_t seeds, flagged, refined;
+    double set_ms;
+} avs_refinement_info;
+avs_status avs_prepass_get_refinement_info(avs_prepass *pp, avs_refinement_info *info);
 /* Slab-local pre-pass (round 6; SURVEY 8(e): "each GPU assembles the rows it owns from its slab of the pyramids plus a halo").  The
  * reference's loops are row-local (classification / numbering cpp:1087-1715, octree oct.cpp:395-565), so a rank of a partitioned solve
  * needs them on its slab only.  cuts[0 .. world]: fine-cell coordinates along cut_axis, cuts[0] = 0, cuts[world] = the axis' extent,
