@@ -90,7 +90,8 @@ ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_v
 PROBE_SYMBOLS = ["avs_spmv_csr", "avs_bench_spmv", "avs_spmv_sell", "avs_bench_stream", "avs_brick_spmv_probe", "avs_spmv_solver_form",
                  "avs_dist_spmv_local_form", "avs_brick_wave_stats", "avs_spmv_csr_form", "avs_vector_update_probe", "avs_pcg_csr_plan",
                  "avs_merge_triplets_probe", "avs_exclusive_scan_probe", "avs_resident_plan_host", "avs_brick_form_probe", "avs_pcg_scalar_probe",
-                 "avs_sr_vector_probe", "avs_dist_plan_probe", "avs_phase_loop_info", "avs_viscosity_lattice_probe"]
+                 "avs_sr_vector_probe", "avs_dist_plan_probe", "avs_phase_loop_info", "avs_viscosity_lattice_probe",
+                 "avs_prepass_plan_host"]
 DIST_PLAN_PROBE_PLAN, DIST_PLAN_PROBE_TAIL = 0, 1   # avs_dist_plan_probe modes
 BRICK_PROBE_FUSED_DOT, BRICK_PROBE_F32, BRICK_PROBE_MIXED, BRICK_PROBE_VALUE_CODES, BRICK_PROBE_DONE = 1, 2, 4, 8, 16   # avs_brick_form_probe flags
 VECTOR_PROBE_F32, VECTOR_PROBE_DS, VECTOR_PROBE_CODED, VECTOR_PROBE_KEEP, VECTOR_PROBE_FUSED = 1, 2, 4, 8, 16   # avs_vector_update_probe flags
@@ -307,6 +308,18 @@ class ResidentHostPlanInfo(C.Structure):
         self.struct_size = C.sizeof(ResidentHostPlanInfo)
 
 
+class PrepassPlanInfo(C.Structure):
+    """avs_prepass_plan_info (include/avs_probe.h): level cap, slab ranges per level and the numbering's tile layout of a pre-pass run"""
+    _fields_ = ([("struct_size", C.c_int32), ("levels", C.c_int32)]
+                + [(f"{r}_{e}", C.c_int32 * MAX_LEVELS) for r in ("win", "nl", "v", "p1") for e in ("lo", "hi")]
+                + [("level_tile0", C.c_int32 * (MAX_LEVELS + 1) * 4), ("tile0_of", C.c_int32 * 3 * MAX_LEVELS * 4),
+                   ("seg", C.c_int64 * 5), ("n_exchange", C.c_int64)])
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(PrepassPlanInfo)
+
+
 class TripletMergeInfo(C.Structure):
     """avs_triplet_merge_info (include/avs_probe.h): the limits of the device triplet merge and what an avs_merge_triplets_probe run reached"""
     _fields_ = [("struct_size", C.c_int32), ("fast_limit", C.c_int32), ("wave_limit", C.c_int32), ("merge_lds", C.c_int32),
@@ -443,6 +456,7 @@ def load(probe=False):
         L.avs_dist_plan_probe.argtypes = [i32, C.POINTER(DistPlanInput), C.POINTER(DistPlanOutput), C.POINTER(DistPlanInfo), vp]
         L.avs_phase_loop_info.argtypes = [C.POINTER(PhaseLoopReport)]
         L.avs_viscosity_lattice_probe.argtypes = [vp, vp, C.POINTER(C.c_float), C.POINTER(i32), i32]
+        L.avs_prepass_plan_host.argtypes = [vp, i32, i32, vp, i32, i32, C.POINTER(PrepassPlanInfo)]
     L.avs_prepass_create.argtypes = [C.POINTER(PrepassDesc), C.POINTER(vp)]
     L.avs_prepass_destroy.argtypes = [vp]
     L.avs_prepass_destroy.restype = None
@@ -534,6 +548,22 @@ def resident_plan_host(row_ptr, workgroups, max_quads=15, lane_fill=0.90, no_str
         return info, None
     L = int(info.lanes)
     return info, {"row0": row0[:L], "meta": meta[:L], "stream_quads": quads[:L], "wl": wl, "wr": wr}
+
+
+def prepass_plan_host(res, desired_levels, cut_axis=0, cuts=None, rank=0):
+    """avs_prepass_plan_host (libavs_probe.so, no GPU): the plan of a pre-pass run on an octree grid `res`; cuts (world + 1 entries): the
+    slab-local plan of `rank`.  Returns a dict: levels, the ranges win / nl / v / p1 as (lo, hi) arrays of `levels` entries, and the tile
+    layout level_tile0 [4][MAX_LEVELS + 1], tile0_of [4][MAX_LEVELS][3], seg [5], n_exchange."""
+    n = np.ascontiguousarray(res, dtype=np.int32)
+    c = None if cuts is None else np.ascontiguousarray(cuts, dtype=np.int32)
+    info = PrepassPlanInfo()
+    check(load_probe().avs_prepass_plan_host(n.ctypes.data, desired_levels, cut_axis, None if c is None else c.ctypes.data,
+                                             1 if c is None else len(c) - 1, rank, C.byref(info)))
+    L = int(info.levels)
+    out = {r: (np.array(getattr(info, r + "_lo"))[:L], np.array(getattr(info, r + "_hi"))[:L]) for r in ("win", "nl", "v", "p1")}
+    out.update(levels=L, level_tile0=np.array(info.level_tile0), tile0_of=np.array(info.tile0_of), seg=np.array(info.seg),
+               n_exchange=int(info.n_exchange))
+    return out
 
 
 def phase_loop_report():

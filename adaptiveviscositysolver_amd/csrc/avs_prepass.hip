@@ -26,6 +26,7 @@
 
 #include "avs_device_common.hpp"
 #include "avs_refine.hpp"
+#include "avs_prepass_plan.hpp"
 
 namespace avs {
 
@@ -1122,15 +1123,8 @@ struct avs_prepass {
 
 static void pp_res(const avs_prepass_desc &d, int kind, int level, int axis, int r[3])
 {
-    r[0] = d.nx >> level;
-    r[1] = d.ny >> level;
-    r[2] = d.nz >> level;
-    if (kind == 0) r[axis] += 1;
-    else if (kind == 1) {
-        r[0] += (axis != 0);
-        r[1] += (axis != 1);
-        r[2] += (axis != 2);
-    }
+    const int n[3] = {d.nx, d.ny, d.nz};
+    lattice_extents(n, kind, level, axis, r);
 }
 static Grid3 g3(const int r[3]) { return Grid3{{r[0], r[1], r[2]}}; }
 
@@ -1156,14 +1150,36 @@ static Box3 slab_box(const int r[3], int axis, int lo, int hi)
     return b;
 }
 
-static avs_status run_weights(avs_prepass *p, WeightFields &F)
+// Weights: allocates the seven weight lattices and enqueues the sign, triage, far and near launches that fill them (two host round
+// trips for the list lengths); leaves p->centerw, p->edgew, p->facew and the brick record of the allocations in p->wstate.
+static avs_status run_weights(avs_prepass *p)
 {
+    const avs_prepass_desc &d = p->desc;
+    WeightFields F{};
+    int nf = 0;
+    auto add = [&](float *out, const int res[3], bool cx, bool cy, bool cz) {
+        F.out[nf] = out;
+        F.tgt[nf] = g3(res);
+        F.centered[nf] = (cx ? 1 : 0) | (cy ? 2 : 0) | (cz ? 4 : 0);
+        ++nf;
+    };
+    int r0[3];
+    pp_res(d, 2, 0, 0, r0);
+    AVS_TRY(p->centerw.alloc(g3(r0).vol()));
+    add(p->centerw.p, r0, true, true, true);
+    for (int a = 0; a < 3; ++a) {
+        int er[3], fr[3];
+        pp_res(d, 1, 0, a, er);
+        pp_res(d, 0, 0, a, fr);
+        AVS_TRY(p->edgew[a].alloc(g3(er).vol()));
+        add(p->edgew[a].p, er, a == 0, a == 1, a == 2); // centred along the edge only
+        AVS_TRY(p->facew[a].alloc(g3(fr).vol()));
+        add(p->facew[a].p, fr, a != 0, a != 1, a != 2); // centred across the face
+    }
     F.n = p->desc.n_super;
     for (int c = 0; c < 2; ++c)
         for (int s = 0; s < F.n; ++s) sub_consts(F.n, c == 1, s, &F.di[c][s], &F.fr[c][s]);
-    int sr[3];
-    pp_res(p->desc, 2, 0, 0, sr);
-    const Grid3 bricks{{(sr[0] + 1 + kWBX - 1) / kWBX, (sr[1] + 1 + kWBY - 1) / kWBY, (sr[2] + 1 + kWBZ - 1) / kWBZ}};
+    const Grid3 bricks{{(r0[0] + 1 + kWBX - 1) / kWBX, (r0[1] + 1 + kWBY - 1) / kWBY, (r0[2] + 1 + kWBZ - 1) / kWBZ}};
     const size_t nb = bricks.vol();
     AVS_TRY(p->near_list.reserve(nb + 1));
     AVS_HIP(hipMemsetAsync(p->near_list.p, 0, sizeof(int32_t), p->stream));
@@ -1189,25 +1205,25 @@ static avs_status run_weights(avs_prepass *p, WeightFields &F)
     if (p->slab.on) {
         const int a = p->slab.axis, bs = a == 0 ? kWBX : (a == 1 ? kWBY : kWBZ);
         const int lo = (p->slab.win_lo[0] - 1 < 0 ? 0 : p->slab.win_lo[0] - 1) / bs;
-        const int hi_s = p->slab.win_hi[0] >= sr[a] ? sr[a] + 1 : p->slab.win_hi[0] + 2; // one past the last sample needed
+        const int hi_s = p->slab.win_hi[0] >= r0[a] ? r0[a] + 1 : p->slab.win_hi[0] + 2; // one past the last sample needed
         const int hi = (hi_s + bs - 1) / bs;
         tri = slab_box(bricks.r, a, lo, hi);
         sgn = slab_box(bricks.r, a, lo - 1, hi + 1);
     }
-    hipLaunchKernelGGL(k_sdf_sign_blocks, dim3(grid_for((sgn.vol() + 3) / 4 * kBlock, 1u << 15)), dim3(kBlock), 0, p->stream, p->liq, g3(sr), bricks, sgn, p->brick_signs.p);
+    hipLaunchKernelGGL(k_sdf_sign_blocks, dim3(grid_for((sgn.vol() + 3) / 4 * kBlock, 1u << 15)), dim3(kBlock), 0, p->stream, p->liq, g3(r0), bricks, sgn, p->brick_signs.p);
     hipLaunchKernelGGL(k_brick_triage, dim3(grid_for(tri.vol(), 1u << 15)), dim3(kBlock), 0, p->stream, bricks, tri, (const uint8_t *)p->brick_signs.p,
                        (const uint8_t *)ws->st.p, p->work_list.p);
     int32_t n_work = 0;
     AVS_HIP(hipMemcpyAsync(&n_work, p->work_list.p, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
     AVS_HIP(hipStreamSynchronize(p->stream));
     if (n_work > 0)
-        hipLaunchKernelGGL(k_sdf_weights_far, dim3((unsigned)n_work), dim3(kWThreads), 0, p->stream, p->liq, g3(sr), bricks, F, p->near_list.p, ws->st.p,
+        hipLaunchKernelGGL(k_sdf_weights_far, dim3((unsigned)n_work), dim3(kWThreads), 0, p->stream, p->liq, g3(r0), bricks, F, p->near_list.p, ws->st.p,
                            (const uint8_t *)p->brick_signs.p, (const int32_t *)p->work_list.p);
     int32_t n_near = 0;
     AVS_HIP(hipMemcpyAsync(&n_near, p->near_list.p, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
     AVS_HIP(hipStreamSynchronize(p->stream));
     if (n_near > 0)
-        hipLaunchKernelGGL(k_sdf_weights, dim3((unsigned)n_near), dim3(kWThreads), 0, p->stream, p->liq, g3(sr), bricks, F,
+        hipLaunchKernelGGL(k_sdf_weights, dim3((unsigned)n_near), dim3(kWThreads), 0, p->stream, p->liq, g3(r0), bricks, F,
                            (const int32_t *)p->near_list.p);
     AVS_HIP(hipGetLastError());
     return AVS_OK;
@@ -1216,7 +1232,7 @@ static avs_status run_weights(avs_prepass *p, WeightFields &F)
 // Index lattice -> AVS_UNASSIGNED everywhere.  `states`: the two records of this lattice (one per allocation of its SharedBuf).  Returns
 // the record the classification launch fills in (k_classify_batch keeps the occupancy; the id is set behind it); until then the record is void (id 0), so a run that
 // fails in between leaves no stale claim about the allocation.
-static avs_status unassign_lattice(avs_prepass *p, SharedBuf<int32_t> &buf, Grid3 g, TileGrid tg, size_t occ_cap, avs_prepass::TileState states[2],
+static avs_status unassign_lattice(avs_prepass *p, SharedBuf<int32_t> &buf, Grid3 g, size_t occ_cap, avs_prepass::TileState states[2],
                                    avs_prepass::TileState **out, const Box3 *window, const uint8_t **prev_occ)
 {
     // *prev_occ: the tiles the allocation's last classification visited (they go on the classification's work list and are reset by it),
@@ -1224,7 +1240,6 @@ static avs_status unassign_lattice(avs_prepass *p, SharedBuf<int32_t> &buf, Grid
     avs_prepass::TileState *ts = nullptr;
     for (int k = 0; k < 2 && !ts; ++k)
         if (p->temporal && states[k].id != 0 && states[k].id == buf.id && states[k].occ.n == occ_cap) ts = &states[k];
-    (void)tg;
     *prev_occ = nullptr;
     if (ts) {
         *prev_occ = ts->occ.p;
@@ -1250,6 +1265,530 @@ struct EvTimer {
     void start() { (void)hipEventRecord(a, s); }
     double stop() { (void)hipEventRecord(b, s); (void)hipEventSynchronize(b); float ms = 0.f; (void)hipEventElapsedTime(&ms, a, b); return ms; }
 };
+
+// ---------------------------------------------------------------------------------------------
+// avs_prepass_run, step by step (the integer geometry: avs_prepass_plan.cpp)
+// ---------------------------------------------------------------------------------------------
+// An index lattice of the pyramids with the two records of what its allocations hold: kind 0 velocity faces, 1 edges, else centres
+struct IndexLattice {
+    SharedBuf<int32_t> *buf;
+    avs_prepass::TileState *states;
+};
+static IndexLattice index_lattice(avs_prepass *p, int kind, int level, int axis)
+{
+    if (kind == 0) return {&p->vidx[level][axis], p->vstate[level][axis]};
+    if (kind == 1) return {&p->eidx[level][axis], p->estate[level][axis]};
+    return {&p->cidx[level], p->cstate[level]};
+}
+// lattice k of a level's seven, in the order of the work lists and the occupancy store: three face, three edge lattices, the cells
+static void work_lattice(int k, int *kind, int *axis)
+{
+    *kind = k < 3 ? 0 : (k < 6 ? 1 : 2);
+    *axis = k < 6 ? k % 3 : 0;
+}
+static double extrapolation_of(const avs_prepass_desc &d) { return d.dx * d.extrapolation_scale; } // cpp:243
+
+// The geometry of one run: the planned ranges along the cut axis and the boxes and tile grids the launches make of them
+struct RunGeom {
+    int n[3];       // octree grid
+    int L;          // levels of the run (the cap of the extents; the octree's own cap is known after the classification)
+    bool slab;
+    int sa;         // cut axis
+    SlabRanges R;
+    size_t occ_cap; // tile-occupancy flags per lattice
+    // entries [lo, hi) of a lattice with extents gr along the cut axis that the window covers / the tiles of a launch over them
+    Box3 win_box(const int gr[3], int l) const
+    {
+        if (!slab) return full_box(gr);
+        return slab_box(gr, sa, R.win_lo[l], R.win_hi[l] >= (n[sa] >> l) ? gr[sa] : R.win_hi[l]);
+    }
+    TileGrid win_tiles(const int gr[3], int l) const
+    {
+        TileGrid t = tile_grid(gr);
+        if (slab) {
+            const Box3 b = win_box(gr, l);
+            t.lo[sa] = b.lo[sa] / kTile;
+            t.bn[sa] = (b.lo[sa] + b.n[sa] + kTile - 1) / kTile - t.lo[sa];
+            if (b.n[sa] <= 0) t.bn[sa] = 0;
+        }
+        return t;
+    }
+    Box3 cell_box(int l, int lo, int hi) const
+    {
+        int r[3];
+        lattice_extents(n, 2, l, 0, r);
+        return slab ? slab_box(r, sa, lo, hi) : full_box(r);
+    }
+};
+// Tile-occupancy flags of the lattices of every level in p->occ_store ([level][slot][occ_cap]; slot: kind * 3 + axis of the face and edge
+// lattices, 6 the cell tiles), kept until the numbering, which skips the tiles nobody visited; the level-0 face lattices' flags are set by
+// the mask kernel (the SDF rule, cpp:907) and serve the regular-grid classification too
+static uint8_t *occ_of(const avs_prepass *p, const RunGeom &G, int l, int slot) { return p->occ_store.p + ((size_t)l * 7 + slot) * G.occ_cap; }
+static TileSets tile_sets(const avs_prepass *p, const RunGeom &G, int l)
+{
+    TileSets T;
+    for (int kind = 0; kind < 2; ++kind)
+        for (int a = 0; a < 3; ++a) {
+            int gr[3];
+            pp_res(p->desc, kind, l, a, gr);
+            T.tg[kind][a] = G.win_tiles(gr, l);
+            T.occ[kind][a] = occ_of(p, G, l, kind * 3 + a);
+        }
+    return T;
+}
+
+// Stage the SDFs: device arrays on the octree lattice are read in place; anything else is copied (and padded from the simulation grid)
+// into p->liquid / p->solid.  Leaves p->liq, p->sol, p->have_solid; host sources are on the device when it returns.
+static avs_status stage_sdfs(avs_prepass *p, const float *liquid, const float *solid, avs_memspace where)
+{
+    hipStream_t st = p->stream;
+    const avs_prepass_desc &d = p->desc;
+    int r0[3];
+    pp_res(d, 2, 0, 0, r0);
+    const size_t n0 = g3(r0).vol();
+    // the SDFs arrive on the simulation grid; outside it they are read with clamped coordinates (border replication)
+    const int s0[3] = {d.field_nx, d.field_ny, d.field_nz};
+    const bool padded = s0[0] != r0[0] || s0[1] != r0[1] || s0[2] != r0[2];
+    const size_t ns = g3(s0).vol();
+    auto take = [&](DevBuf<float> &dst, const float *src) -> avs_status {
+        AVS_TRY(dst.alloc(n0));
+        if (!padded) {
+            AVS_HIP(copy_in(dst.p, src, n0 * sizeof(float), where, st));
+            return AVS_OK;
+        }
+        DevBuf<float> tmp;
+        const float *sp = src;
+        if (where == AVS_MEM_HOST) {
+            AVS_TRY(tmp.alloc(ns));
+            AVS_HIP(copy_in(tmp.p, src, ns * sizeof(float), where, st));
+            sp = tmp.p;
+        }
+        AVS_TRY(pad_lattice_f32(sp, s0[0], s0[1], s0[2], dst.p, r0[0], r0[1], r0[2], true, 0.f, st));
+        AVS_HIP(hipStreamSynchronize(st)); // tmp dies here
+        return AVS_OK;
+    };
+    // device arrays on the octree lattice are read in place (round 6; they are only read while this call runs): the copy was a 4.3-GB
+    // pass per SDF and frame at 1024^3 -- and in slab-local mode a full-lattice pass for a window
+    const bool alias = where == AVS_MEM_DEVICE && !padded;
+    if (alias) p->liq = liquid;
+    else {
+        AVS_TRY(take(p->liquid, liquid));
+        p->liq = p->liquid.p;
+    }
+    p->have_solid = solid != nullptr;
+    p->sol = nullptr;
+    if (solid) {
+        if (alias) p->sol = solid;
+        else {
+            AVS_TRY(take(p->solid, solid));
+            p->sol = p->solid.p;
+        }
+    }
+    if (where == AVS_MEM_HOST) AVS_HIP(hipStreamSynchronize(st));
+    return AVS_OK;
+}
+
+// Plan: enqueues nothing.  Fills the run's geometry and the numbering's tile layout, publishes the index window in p->slab (what
+// avs_prepass_get_window and run_weights read and avs_prepass_apply lends) and voids the temporal-reuse records when they describe another window.
+static avs_status plan_run(avs_prepass *p, RunGeom *G, TileLayout *lay)
+{
+    const avs_prepass_desc &d = p->desc;
+    G->n[0] = d.nx; G->n[1] = d.ny; G->n[2] = d.nz;
+    G->L = p->max_levels;
+    G->slab = p->slab.on;
+    G->sa = p->slab.axis;
+    G->R = slab_ranges(G->n[G->sa], G->L, G->slab, p->slab.cuts, p->slab.rank, kSlabIndexMargin, kTile);
+    G->occ_cap = (size_t)(d.nx / kTile + 2) * (size_t)(d.ny / kTile + 2) * (size_t)(d.nz / kTile + 2);
+    if (G->slab) {
+        for (int l = 0; l < AVS_MAX_LEVELS; ++l) { p->slab.win_lo[l] = G->R.win_lo[l]; p->slab.win_hi[l] = G->R.win_hi[l]; } // (0 beyond L)
+        if (p->state_sig != p->slab_sig) { // the records of what the allocations hold describe another window: void
+            for (int l = 0; l < AVS_MAX_LEVELS; ++l)
+                for (int k = 0; k < 2; ++k) {
+                    p->cstate[l][k].id = 0;
+                    for (int a = 0; a < 3; ++a) p->vstate[l][a][k].id = p->estate[l][a][k].id = 0;
+                }
+            for (int a = 0; a < 3; ++a)
+                for (int k = 0; k < 2; ++k) p->rstate[a][k].id = 0;
+            for (int k = 0; k < 2; ++k) memset(p->wstate[k].ids, 0, sizeof(p->wstate[k].ids));
+            p->state_sig = p->slab_sig;
+        }
+    }
+    AVS_REQUIRE(tile_layout(G->n, G->L, kTile, lay), AVS_EINVAL, "too many tiles");
+    return AVS_OK;
+}
+
+// Octree: allocates the mask, the labels and the occupancy store; enqueues the labels' and the store's memsets, the mask launch (level-0
+// labels, mask, level-0 face / edge occupancy, the refined-cell counters), passes 1 - 3 per level pair, the top pass and the memset of
+// the levels' flags.  Leaves p->mask, p->labels, p->occ_store, p->lvl_flags (zero: the classification's occupancy pass sets them).
+static avs_status build_octree(avs_prepass *p, const RunGeom &G)
+{
+    hipStream_t st = p->stream;
+    const avs_prepass_desc &d = p->desc;
+    const SlabRanges &R = G.R;
+    const int L = G.L;
+    int r0[3];
+    pp_res(d, 2, 0, 0, r0);
+    const int s0[3] = {d.field_nx, d.field_ny, d.field_nz};
+    AVS_TRY(p->mask.alloc(g3(r0).vol()));
+    for (int l = 0; l < L; ++l) {
+        int r[3];
+        pp_res(d, 2, l, 0, r);
+        AVS_TRY(p->labels[l].alloc(g3(r).vol()));
+        if (l > 0) AVS_HIP(hipMemsetAsync(p->labels[l].p, 0, g3(r).vol(), st)); // INACTIVE, oct.cpp:59,69 (level 0 is written by the mask kernel wherever it is read)
+    }
+    const double occ_sdf = 2. * d.dx; // cpp:907
+    AVS_TRY(p->occ_store.reserve((size_t)L * 7 * G.occ_cap));
+    AVS_HIP(hipMemsetAsync(p->occ_store.p, 0, (size_t)L * 7 * G.occ_cap, st));
+    {
+        const Box3 b0 = G.cell_box(0, R.v_lo[0], R.v_hi[0]);
+        const TileSets T0 = tile_sets(p, G, 0);
+        const double inner = d.dx * (p->fine_bandwidth > 2. ? p->fine_bandwidth : 2.); // SYSmax(2., fpreal(getFineBandwidth())), cpp:259-261
+        const bool vec = (b0.lo[0] & 3) == 0 && (b0.n[0] & 3) == 0 && (r0[0] & 3) == 0;
+        const unsigned gm = vec ? grid_for(b0.vol() / 4) : grid_for(b0.vol());
+        RefineView V{};
+        p->refine.refined = 0;
+        const bool flagged = p->refine.active;
+        if (flagged) { // `refined` counts inside the rank's index window (all of the lattice without slabs)
+            V = RefineView{p->refine.bits.p, p->refine.wx, G.sa, R.win_lo[0], R.win_hi[0], p->refine.counters.p + kRefinedBase};
+            AVS_HIP(hipMemsetAsync(V.refined, 0, (size_t)kRefinedSlots * kRefinedStride * sizeof(unsigned long long), st));
+        }
+        auto mask_kernel = vec ? (flagged ? k_mask_labels<4, true> : k_mask_labels<4, false>) : (flagged ? k_mask_labels<1, true> : k_mask_labels<1, false>);
+        hipLaunchKernelGGL(mask_kernel, dim3(gm), dim3(kBlock), 0, st, p->liq, p->sol, b0, d.dx, inner, extrapolation_of(d), p->mask.p, p->labels[0].p, g3(r0),
+                           g3(s0), T0, occ_sdf, 1, V);
+    }
+    for (int l = 0; l < L - 1; ++l) {
+        int r[3], rp[3];
+        pp_res(d, 2, l, 0, r);
+        pp_res(d, 2, l + 1, 0, rp);
+        const Box3 b1 = G.cell_box(l + 1, R.p1_lo[l + 1], R.p1_hi[l + 1]), b2 = G.cell_box(l + 1, R.v_lo[l + 1], R.v_hi[l + 1]);
+        hipLaunchKernelGGL(k_oct_pass1, dim3(grid_for(b1.vol())), dim3(kBlock), 0, st, p->labels[l].p, g3(r), p->labels[l + 1].p, g3(rp), b1);
+        hipLaunchKernelGGL(k_oct_pass2, dim3(grid_for(b2.vol())), dim3(kBlock), 0, st, p->labels[l].p, g3(r), p->labels[l + 1].p, g3(rp), b2);
+        hipLaunchKernelGGL(k_oct_pass3, dim3(grid_for(b2.vol())), dim3(kBlock), 0, st, p->labels[l].p, g3(r), p->labels[l + 1].p, g3(rp), b2);
+    }
+    {
+        int r[3];
+        pp_res(d, 2, L - 1, 0, r);
+        const Box3 bt = G.cell_box(L - 1, R.v_lo[L - 1], R.v_hi[L - 1]);
+        hipLaunchKernelGGL(k_oct_top, dim3(grid_for(bt.vol())), dim3(kBlock), 0, st, p->labels[L - 1].p, g3(r), bt);
+    }
+    // cap at the first level without ACTIVE cells, oct.cpp:198-211: every level is classified, the flags come out of the classification's
+    // occupancy pass (k_mark_tiles_all); in slab mode they are a property of the WHOLE octree and travel with the tile counts
+    AVS_TRY(p->lvl_flags.reserve(AVS_MAX_LEVELS));
+    AVS_HIP(hipMemsetAsync(p->lvl_flags.p, 0, AVS_MAX_LEVELS * sizeof(int), st));
+    AVS_HIP(hipGetLastError());
+    return AVS_OK;
+}
+
+// ... and, behind the octree's timer: one round trip for the mask kernel's count of the cells the refinement flags kept fine.  Leaves
+// p->refine.refined.
+static avs_status read_refined_cells(avs_prepass *p)
+{
+    if (!p->refine.active) return AVS_OK;
+    static_assert(sizeof(unsigned long long) == 8, "slot stride in bytes");
+    unsigned long long h[kRefinedSlots * kRefinedStride];
+    AVS_HIP(hipMemcpyAsync(h, p->refine.counters.p + kRefinedBase, sizeof(h), hipMemcpyDeviceToHost, p->stream));
+    AVS_HIP(hipStreamSynchronize(p->stream));
+    unsigned long long sum = 0;
+    for (int k = 0; k < kRefinedSlots; ++k) sum += h[k * kRefinedStride];
+    p->refine.refined = (int64_t)sum;
+    return AVS_OK;
+}
+
+// One lattice of a classification launch: ClassifyBatch's kind (0 velocity faces, 1 edges, 2 centres, 3 regular-grid faces) and axis, its
+// buffer and the two records of the buffer's allocations, the tiles to launch over, their occupancy, and where the tiles' DOF counts go
+struct LatticeWork {
+    int kind, axis;
+    SharedBuf<int32_t> *buf;
+    avs_prepass::TileState *states;
+    TileGrid tg;
+    const uint8_t *occ;
+    int32_t *dofs;
+};
+// Classifies `count` <= 7 lattices of one level: allocates them, enqueues the memset of the list counters, per lattice its fresh fill
+// where no record of the last classification serves, ONE launch that lists the tiles to touch and ONE classification launch over the
+// lists.  Leaves the lattices filled and their records describing these allocations.
+static avs_status classify_lattices(avs_prepass *p, const RunGeom &G, int level, const LatticeWork *lat, int count)
+{
+    hipStream_t st = p->stream;
+    const avs_prepass_desc &d = p->desc;
+    WorkLists W{};
+    ClassifyBatch B{};
+    avs_prepass::TileState *tss[kWorkLattices] = {};
+    AVS_TRY(p->work_lists.reserve(8 + (size_t)kWorkLattices * G.occ_cap)); // [8 counters | 7 x tile ids]
+    AVS_HIP(hipMemsetAsync(p->work_lists.p, 0, 8 * sizeof(int32_t), st));
+    B.A.n[0] = d.nx; B.A.n[1] = d.ny; B.A.n[2] = d.nz;
+    B.A.level = level;
+    B.A.extrapolation = extrapolation_of(d);
+    B.A.lab = p->labels[level].p;
+    B.A.centerw = p->centerw.p;
+    for (int a = 0; a < 3; ++a) B.A.edgew[a] = p->edgew[a].p;
+    B.A.solid = p->sol;
+    B.occ_cap = (unsigned)G.occ_cap;
+    if (G.slab) {
+        B.own.on = 1; B.own.axis = G.sa; B.own.world = p->slab.world; B.own.rank = p->slab.rank;
+        for (int r = 0; r <= p->slab.world; ++r) B.own.cuts[r] = p->slab.cuts[r];
+    }
+    for (int k = 0; k < kWorkLattices; ++k) B.kind[k] = -1;
+    size_t max_launch = 0;
+    for (int k = 0; k < count; ++k) {
+        const LatticeWork &X = lat[k];
+        int gr[3];
+        pp_res(d, X.kind == 3 ? 0 : X.kind, level, X.axis, gr);
+        AVS_TRY(X.buf->alloc(g3(gr).vol()));
+        W.tg[k] = X.tg;
+        W.now[k] = X.occ;
+        W.cnt[k] = p->work_lists.p + k;
+        W.items[k] = p->work_lists.p + 8 + (size_t)k * G.occ_cap;
+        const Box3 wb = G.win_box(gr, level);
+        AVS_TRY(unassign_lattice(p, *X.buf, g3(gr), G.occ_cap, X.states, &tss[k], G.slab ? &wb : nullptr, &W.prev[k]));
+        if (X.tg.launch() > max_launch) max_launch = X.tg.launch();
+        B.kind[k] = X.kind; B.axis[k] = X.axis; B.g[k] = g3(gr); B.tg[k] = X.tg; B.occ[k] = X.occ; B.remember[k] = tss[k]->occ.p; B.out[k] = X.buf->p;
+        B.cnt[k] = W.cnt[k]; B.items[k] = W.items[k];
+        B.dofs[k] = X.dofs;
+    }
+    if (max_launch) hipLaunchKernelGGL(k_tile_worklists, dim3(grid_for(max_launch), kWorkLattices), dim3(kBlock), 0, st, W);
+    {   // (with no tile to launch over the occupancy is still remembered: the grid has at least one workgroup per lattice)
+        const unsigned grid = (unsigned)(max_launch < kListGrid ? (max_launch ? max_launch : 1) : kListGrid);
+        hipLaunchKernelGGL(k_classify_batch, dim3(grid, kWorkLattices), dim3(kBlock), 0, st, B);
+        AVS_HIP(hipGetLastError());
+    }
+    for (int k = 0; k < count; ++k) tss[k]->id = lat[k].buf->id; // the records describe these allocations from here on
+    return AVS_OK;
+}
+
+// Classification: allocates and zeroes the numbering's count buffer (the classification launch drops every tile's DOF count where the scan
+// will read it); per level the occupancy pass over the cells, the cell-tile launch and the level's seven lattices; then the regular
+// grid's three.  Without slabs one round trip for the levels' flags.  Leaves the index lattices, p->num_counts and p->levels (slab mode:
+// the cap is a property of the whole octree, known after the exchange -- every level counts until then).
+static avs_status classify(avs_prepass *p, const RunGeom &G, const TileLayout &lay)
+{
+    hipStream_t st = p->stream;
+    const avs_prepass_desc &d = p->desc;
+    AVS_TRY(p->num_counts.reserve((size_t)lay.n_exchange));
+    int32_t *counts = p->num_counts.p;
+    AVS_HIP(hipMemsetAsync(counts, 0, (size_t)lay.n_exchange * sizeof(int32_t), st));
+    LatticeWork lat[kWorkLattices];
+    for (int l = 0; l < G.L; ++l) {
+        int cr[3];
+        pp_res(d, 2, l, 0, cr);
+        const TileSets T = tile_sets(p, G, l);
+        {   // (slab mode: the cells whose faces / edges can lie in a tile of the window)
+            const Box3 mb = G.cell_box(l, G.R.win_lo[l] - 1, G.R.win_hi[l]);
+            if ((mb.lo[0] & 3) == 0 && (mb.n[0] & 3) == 0 && (cr[0] & 3) == 0)
+                hipLaunchKernelGGL(k_mark_tiles_all<4>, dim3(grid_for(mb.vol() / 4)), dim3(kBlock), 0, st, p->labels[l].p, g3(cr), mb, T, l > 0 ? 1 : 0, p->lvl_flags.p + l);
+            else
+                hipLaunchKernelGGL(k_mark_tiles_all<1>, dim3(grid_for(mb.vol())), dim3(kBlock), 0, st, p->labels[l].p, g3(cr), mb, T, l > 0 ? 1 : 0, p->lvl_flags.p + l);
+        }
+        const TileGrid tc = G.win_tiles(cr, l);
+        uint8_t *occ_c = occ_of(p, G, l, 6);
+        hipLaunchKernelGGL(k_center_tiles, dim3(grid_for(tc.vol())), dim3(kBlock), 0, st, (const uint8_t *)T.occ[1][0], T.tg[1][0], tc, occ_c);
+        for (int k = 0; k < kWorkLattices; ++k) {
+            int kind, a;
+            work_lattice(k, &kind, &a);
+            const IndexLattice X = index_lattice(p, kind, l, a);
+            lat[k] = LatticeWork{kind, a, X.buf, X.states, kind == 2 ? tc : T.tg[kind][a], kind == 2 ? occ_c : T.occ[kind][a],
+                                 counts + lay.seg[kind] + lay.tile0_of[kind][l][a]};
+        }
+        AVS_TRY(classify_lattices(p, G, l, lat, kWorkLattices));
+    }
+    {   // regular-grid faces, cpp:1457-1481: the tiles and the occupancy of the level-0 face lattices, marked above by the same rule (kind 0, SDF)
+        const TileSets T0 = tile_sets(p, G, 0);
+        for (int a = 0; a < 3; ++a)
+            lat[a] = LatticeWork{3, a, &p->ridx[a], p->rstate[a], T0.tg[0][a], T0.occ[0][a], counts + lay.seg[3] + lay.tile0_of[3][0][a]};
+        AVS_TRY(classify_lattices(p, G, 0, lat, 3));
+    }
+    AVS_HIP(hipGetLastError());
+    p->levels = G.L;
+    if (!G.slab) {
+        int hflags[AVS_MAX_LEVELS] = {};
+        AVS_HIP(hipMemcpyAsync(hflags, p->lvl_flags.p, sizeof(hflags), hipMemcpyDeviceToHost, st));
+        AVS_HIP(hipStreamSynchronize(st));
+        p->levels = first_level_without_active(hflags, G.L);
+    }
+    return AVS_OK;
+}
+
+// A run whose octree has no level with an ACTIVE cell -- no liquid in the refinement band: nothing to solve (the reference asserts here,
+// oct.cpp:206).  The counts are zero and the DOF tables invalid since the run began.  Two places find it out: the classification without
+// slabs, before the numbering starts (number_ms 0), and the exchange in slab mode, inside the numbering (number_ms: the time until then;
+// the window lists are empty).  avs_prepass_get_info reports the one and the other, so the difference stays.
+static avs_status finish_without_levels(avs_prepass *p, double number_ms)
+{
+    p->ms[3] = number_ms;
+    if (p->slab.on)
+        for (int k = 0; k < 3; ++k) p->n_window[k] = 0;
+    p->ready = true;
+    return AVS_OK;
+}
+
+// ---- numbering: what its steps share ----
+constexpr unsigned kNumGrid = 4096; // workgroups walking a list
+struct Numbering {
+    NumBatch batch[4]; // host copies (alive until the synchronisation behind the last batch: they are the sources of asynchronous copies)
+    NumStarts starts[4];
+    int eff_tiles[4];  // tiles of the levels below the cap
+    long long totals[4] = {0, 0, 0, 0};
+};
+
+// The batches' lattice lists, read off the layout the classification counted into; reserves the numbering's scratch and enqueues the
+// four uploads.  Leaves N.batch, N.starts and p->num_batches.
+static avs_status upload_batches(avs_prepass *p, const RunGeom &G, const TileLayout &lay, Numbering &N)
+{
+    const avs_prepass_desc &d = p->desc;
+    for (int counter = 0; counter < 4; ++counter) {
+        NumBatch &B = N.batch[counter];
+        B = NumBatch{};
+        auto add = [&](int32_t *grid, int kind, int l, int a, const uint8_t *occ, int tag) {
+            int gr[3];
+            pp_res(d, kind, l, a, gr);
+            NumLattice &Lt = B.lat[B.count++];
+            Lt.grid = grid;
+            Lt.occ = occ;
+            Lt.g = g3(gr);
+            Lt.ntx = (gr[0] + kTile - 1) / kTile;
+            Lt.nty = (gr[1] + kTile - 1) / kTile;
+            Lt.tile0 = lay.tile0_of[counter][l][a];
+            Lt.tag = tag;
+        };
+        if (counter < 3) {
+            for (int l = 0; l < G.L; ++l)
+                for (int a = 0; a < (counter == 2 ? 1 : 3); ++a) // (centres: the cell tiles with an ACTIVE cell, k_center_tiles)
+                    add(index_lattice(p, counter, l, a).buf->p, counter, l, a, occ_of(p, G, l, counter == 2 ? 6 : counter * 3 + a), l | (a << 8));
+        } else
+            for (int a = 0; a < 3; ++a) add(p->ridx[a].p, 0, 0, a, occ_of(p, G, 0, a), 0); // classified with the level-0 face occupancy
+        B.total_tiles = (int)lay.tiles(counter);
+    }
+    AVS_TRY(p->num_offsets.reserve((size_t)lay.seg[4]));
+    AVS_TRY(p->num_lists.reserve((size_t)lay.seg[4] + 4)); // per batch: [count | tile ids]  (a batch's segment has tiles + 1 entries)
+    AVS_TRY(p->num_batches.alloc(4));
+    for (int counter = 0; counter < 4; ++counter) {
+        const NumBatch &B = N.batch[counter];
+        AVS_TRY(p->num_scan_tmp.reserve(scan_tmp_elems((int64_t)B.total_tiles + 1)));
+        AVS_HIP(hipMemcpyAsync(p->num_batches.p + counter, &B, sizeof(NumBatch), hipMemcpyHostToDevice, p->stream)); // (pageable source: staged before the call returns)
+        for (int k = 0; k < kNumLattices; ++k) N.starts[counter].tile0[k] = k < B.count ? B.lat[k].tile0 : INT_MAX;
+        N.eff_tiles[counter] = B.total_tiles;
+    }
+    AVS_HIP(hipGetLastError());
+    return AVS_OK;
+}
+
+// Slab mode, ONE exchange: every tile's count from the rank that owns it, every level's "has an ACTIVE cell" from whoever saw one.
+// Enqueues the copy of the flags behind the counts, calls the all-reduce, reads the flags back (one round trip).  Leaves p->levels.
+static avs_status exchange_counts(avs_prepass *p, const RunGeom &G, const TileLayout &lay)
+{
+    hipStream_t st = p->stream;
+    int32_t *counts = p->num_counts.p;
+    int hflags[AVS_MAX_LEVELS] = {};
+    AVS_HIP(hipMemcpyAsync(counts + lay.seg[4], p->lvl_flags.p, AVS_MAX_LEVELS * sizeof(int), hipMemcpyDeviceToDevice, st));
+    const avs_status ex = p->slab_fn(counts, lay.n_exchange, (void *)st, p->slab_user);
+    AVS_REQUIRE(ex == AVS_OK, ex, "the all-reduce callback of avs_prepass_set_slab failed (%d)", (int)ex);
+    AVS_HIP(hipMemcpyAsync(hflags, counts + lay.seg[4], sizeof(hflags), hipMemcpyDeviceToHost, st));
+    AVS_HIP(hipStreamSynchronize(st));
+    p->levels = first_level_without_active(hflags, G.L);
+    return AVS_OK;
+}
+
+// Scans the four batches' counts, sizes the DOF tables -- slab mode exactly (one round trip for the totals, then a memset: entries outside
+// the window stay recognisably void); else room for the previous frame's count + 25 % (a first run has no estimate: the context builds
+// them) -- and enqueues, per batch with tiles, the list counter's memset, the selection and the id launch.  Leaves the ids in the
+// lattices, p->dof, p->dof_cap, N.totals (slab mode).
+static avs_status assign_ids(avs_prepass *p, const RunGeom &G, const TileLayout &lay, Numbering &N)
+{
+    hipStream_t st = p->stream;
+    const int64_t *seg = lay.seg;
+    int32_t *ids = p->num_offsets.p;
+    for (int c = 0; c < 3; ++c) N.eff_tiles[c] = lay.level_tile0[c][p->levels]; // (levels are the outer order of a batch: the capped ones are its tail)
+    for (int c = 0; c < 4; ++c)
+        AVS_TRY(exclusive_scan_i32(p->num_counts.p + seg[c], ids + seg[c], N.eff_tiles[c], p->num_scan_tmp.p, p->num_scan_tmp.n, st));
+    if (G.slab) {
+        int32_t tot[4];
+        for (int c = 0; c < 4; ++c) AVS_HIP(hipMemcpyAsync(&tot[c], ids + seg[c] + N.eff_tiles[c], sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        AVS_HIP(hipStreamSynchronize(st));
+        for (int c = 0; c < 4; ++c) {
+            AVS_REQUIRE(tot[c] >= 0, AVS_EINVAL, "DOF count exceeds int32");
+            N.totals[c] = tot[c];
+        }
+    }
+    for (int k = 0; k < 3; ++k) {
+        p->dof_valid[k] = false;
+        if (G.slab) p->dof_cap[k] = N.totals[k] > 0 ? N.totals[k] : 1;
+        else p->dof_cap[k] = (p->temporal && p->prev_counts[k] > 0) ? p->prev_counts[k] + p->prev_counts[k] / 4 + 4096 : 0;
+        if (p->dof_cap[k] > 0) AVS_TRY(p->dof[k].alloc((size_t)p->dof_cap[k] * 4));
+        if (G.slab) AVS_HIP(hipMemsetAsync(p->dof[k].p, 0xFF, (size_t)p->dof_cap[k] * 4 * sizeof(int32_t), st));
+    }
+    for (int c = 0; c < 4; ++c) {
+        const bool tab = c < 3 && p->dof_cap[c] > 0;
+        if (N.eff_tiles[c]) {
+            int32_t *list = p->num_lists.p + seg[c];
+            AVS_HIP(hipMemsetAsync(list, 0, sizeof(int32_t), st));
+            hipLaunchKernelGGL(k_tile_select_ids, dim3(grid_for((size_t)N.eff_tiles[c])), dim3(kBlock), 0, st, N.starts[c], p->num_batches.p + c,
+                               N.eff_tiles[c], (const int32_t *)(ids + seg[c]), list);
+            hipLaunchKernelGGL(k_tile_ids, dim3(kNumGrid), dim3(kBlock), 0, st, N.starts[c], p->num_batches.p + c, (const int32_t *)(ids + seg[c]),
+                               tab ? p->dof[c].p : (int32_t *)nullptr, tab ? p->dof_cap[c] : 0ll, p->num_totals.p + c, N.eff_tiles[c], (const int32_t *)list);
+        }
+    }
+    AVS_HIP(hipGetLastError());
+    return AVS_OK;
+}
+
+// Window lists (slab mode): the window's DOFs of every kind, ascending -- the tiles this rank classified, each a run of consecutive ids.
+// Per kind a count launch, a scan, one round trip for the length, the fill launch and a synchronisation.  Leaves p->wlist, p->n_window.
+static avs_status window_lists(avs_prepass *p, const TileLayout &lay, const Numbering &N)
+{
+    hipStream_t st = p->stream;
+    DevBuf<int32_t> &wcnt = p->win_cnt, &woff = p->win_off;
+    for (int k = 0; k < 3; ++k) {
+        const int tiles = N.eff_tiles[k];
+        const int32_t *ids = p->num_offsets.p + lay.seg[k];
+        AVS_TRY(wcnt.reserve((size_t)tiles + 1));
+        AVS_TRY(woff.reserve((size_t)tiles + 1));
+        hipLaunchKernelGGL(k_win_counts, dim3(grid_for((size_t)tiles)), dim3(kBlock), 0, st, N.starts[k], p->num_batches.p + k, ids, tiles, wcnt.p);
+        AVS_TRY(exclusive_scan_i32(wcnt.p, woff.p, tiles, p->num_scan_tmp.p, p->num_scan_tmp.n, st));
+        int32_t nw = 0;
+        AVS_HIP(hipMemcpyAsync(&nw, woff.p + tiles, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        AVS_HIP(hipStreamSynchronize(st));
+        p->n_window[k] = nw;
+        AVS_TRY(p->wlist[k].alloc((size_t)(nw > 0 ? nw : 1)));
+        if (tiles && nw) hipLaunchKernelGGL(k_win_fill, dim3((unsigned)tiles), dim3(kBlock), 0, st, ids, (const int32_t *)wcnt.p, (const int32_t *)woff.p, p->wlist[k].p);
+        AVS_HIP(hipGetLastError());
+        AVS_HIP(hipStreamSynchronize(st)); // wcnt / woff are reused
+    }
+    return AVS_OK;
+}
+
+// Numbering: zeroes the four DOF totals, then the steps above; without slabs one round trip for the totals at the end.  Leaves the ids,
+// the DOF tables, p->counts, p->dof_valid, p->prev_counts -- or, in slab mode, p->levels == 0 and nothing else when the exchange found
+// no level with an ACTIVE cell.
+static avs_status number_dofs(avs_prepass *p, const RunGeom &G, const TileLayout &lay)
+{
+    hipStream_t st = p->stream;
+    AVS_TRY(p->num_totals.alloc(4));
+    AVS_HIP(hipMemsetAsync(p->num_totals.p, 0, 4 * sizeof(long long), st));
+    PhaseTrace tr(st, "numbering", avs::options_from_env().trace_phases != 0);
+    Numbering N;
+    AVS_TRY(upload_batches(p, G, lay, N));
+    tr.mark("tile counts");
+    if (G.slab) {
+        AVS_TRY(exchange_counts(p, G, lay));
+        if (p->levels == 0) return AVS_OK;
+    }
+    tr.mark("exchange");
+    AVS_TRY(assign_ids(p, G, lay, N));
+    tr.mark("scans, tables, ids");
+    if (G.slab) {
+        AVS_TRY(window_lists(p, lay, N));
+    } else {
+        AVS_HIP(hipMemcpyAsync(N.totals, p->num_totals.p, sizeof(N.totals), hipMemcpyDeviceToHost, st));
+        AVS_HIP(hipStreamSynchronize(st));
+    }
+    tr.mark("window lists");
+    for (int k = 0; k < 4; ++k) p->counts[k] = N.totals[k];
+    for (int k = 0; k < 3; ++k) {
+        p->dof_valid[k] = p->dof_cap[k] > 0 && N.totals[k] <= p->dof_cap[k];
+        p->prev_counts[k] = N.totals[k];
+    }
+    return AVS_OK;
+}
 
 extern "C" {
 
@@ -1279,14 +1818,8 @@ avs_status avs_prepass_create(const avs_prepass_desc *d, avs_prepass **out)
         if (hipStreamCreate(&p->stream) != hipSuccess) { delete p; set_error("hipStreamCreate failed"); return AVS_EHIP; }
         p->own_stream = true;
     }
-    // level cap, oct.cpp:32-40
-    int L = d->desired_levels;
-    for (int n : {d->nx, d->ny, d->nz}) {
-        int lg = 0;
-        while ((1 << (lg + 1)) <= n) ++lg;
-        if (lg < L) L = lg;
-    }
-    p->max_levels = L < 1 ? 1 : L;
+    const int n[3] = {d->nx, d->ny, d->nz};
+    p->max_levels = level_cap(n, d->desired_levels);
     const avs::Options env_opt = avs::options_from_env();
     p->temporal = env_opt.prepass_temporal != 0;
     p->cells_grid_cap = env_opt.cells_grid_cap;
@@ -1431,538 +1964,78 @@ avs_status avs_prepass_run(avs_prepass *p, const float *liquid, const float *sol
     (void)hipGetLastError(); // (a stale error of the host application's own HIP calls on this thread is not ours: see OptScope)
     AVS_REQUIRE(p && liquid, AVS_EINVAL, "null argument");
     AVS_HIP(hipSetDevice(p->desc.device));
-    hipStream_t st = p->stream;
-    const avs_prepass_desc &d = p->desc;
-    int r0[3];
-    pp_res(d, 2, 0, 0, r0);
-    const size_t n0 = g3(r0).vol();
-    const double extrapolation = d.dx * d.extrapolation_scale; // cpp:243
     p->ready = false;
     for (int k = 0; k < 3; ++k) p->dof_valid[k] = false;
-    EvTimer t(st);
+    EvTimer t(p->stream);
+    RunGeom G;
+    TileLayout lay;
+    AVS_TRY(stage_sdfs(p, liquid, solid, where));
+    AVS_TRY(plan_run(p, &G, &lay));
 
-    // the SDFs arrive on the simulation grid; outside it they are read with clamped coordinates (border replication)
-    const int s0[3] = {d.field_nx, d.field_ny, d.field_nz};
-    const bool padded = s0[0] != r0[0] || s0[1] != r0[1] || s0[2] != r0[2];
-    const size_t ns = g3(s0).vol();
-    auto take = [&](DevBuf<float> &dst, const float *src) -> avs_status {
-        AVS_TRY(dst.alloc(n0));
-        if (!padded) {
-            AVS_HIP(copy_in(dst.p, src, n0 * sizeof(float), where, st));
-            return AVS_OK;
-        }
-        DevBuf<float> tmp;
-        const float *sp = src;
-        if (where == AVS_MEM_HOST) {
-            AVS_TRY(tmp.alloc(ns));
-            AVS_HIP(copy_in(tmp.p, src, ns * sizeof(float), where, st));
-            sp = tmp.p;
-        }
-        AVS_TRY(pad_lattice_f32(sp, s0[0], s0[1], s0[2], dst.p, r0[0], r0[1], r0[2], true, 0.f, st));
-        AVS_HIP(hipStreamSynchronize(st)); // tmp dies here
-        return AVS_OK;
-    };
-    // device arrays on the octree lattice are read in place (round 6; they are only read while this call runs): the copy was a 4.3-GB
-    // pass per SDF and frame at 1024^3 -- and in slab-local mode a full-lattice pass for a window
-    const bool alias = where == AVS_MEM_DEVICE && !padded;
-    if (alias) p->liq = liquid;
-    else {
-        AVS_TRY(take(p->liquid, liquid));
-        p->liq = p->liquid.p;
-    }
-    p->have_solid = solid != nullptr;
-    p->sol = nullptr;
-    if (solid) {
-        if (alias) p->sol = solid;
-        else {
-            AVS_TRY(take(p->solid, solid));
-            p->sol = p->solid.p;
-        }
-    }
-    if (where == AVS_MEM_HOST) AVS_HIP(hipStreamSynchronize(st));
-
-    // ---- slab-local mode: the window of every level along the cut axis, and what the octree passes must cover for it -------------
-    const int L = p->max_levels;
-    const bool slab = p->slab.on;
-    const int sa = p->slab.axis;
-    int win_lo[AVS_MAX_LEVELS] = {}, win_hi[AVS_MAX_LEVELS] = {}; // index window (level-l cells; multiples of 16 / the level's end)
-    int nl_lo[AVS_MAX_LEVELS] = {}, nl_hi[AVS_MAX_LEVELS] = {};   // labels the classification of the window reads
-    int v_lo[AVS_MAX_LEVELS] = {}, v_hi[AVS_MAX_LEVELS] = {};     // labels valid before the level serves as children
-    int p1_lo[AVS_MAX_LEVELS] = {}, p1_hi[AVS_MAX_LEVELS] = {};   // parents of pass 1 at level l (pass 2 / 3: v_lo .. v_hi)
-    {
-        const int na = sa == 0 ? d.nx : (sa == 1 ? d.ny : d.nz);
-        for (int l = 0; l < L; ++l) {
-            const int nl = na >> l;
-            if (!slab) { win_lo[l] = nl_lo[l] = v_lo[l] = p1_lo[l] = 0; win_hi[l] = nl_hi[l] = v_hi[l] = p1_hi[l] = nl; continue; }
-            const int s_lo = p->slab.cuts[p->slab.rank] >> l, s_hi = (p->slab.cuts[p->slab.rank + 1] + (1 << l) - 1) >> l;
-            int lo = s_lo - kSlabIndexMargin, hi = s_hi + kSlabIndexMargin;
-            lo = lo < 0 ? 0 : lo / kTile * kTile;
-            hi = (hi + kTile - 1) / kTile * kTile;
-            if (hi > nl) hi = nl;
-            win_lo[l] = lo; win_hi[l] = hi;
-            nl_lo[l] = lo - 2 < 0 ? 0 : lo - 2;
-            nl_hi[l] = hi + 2 > nl ? nl : hi + 2;
-        }
-        if (slab) {
-            v_lo[L - 1] = nl_lo[L - 1]; v_hi[L - 1] = nl_hi[L - 1];
-            for (int l = L - 2; l >= 0; --l) { // pass 2 of a parent reads the face neighbours of its children AFTER their own parents' pass 1
-                const int np = na >> (l + 1);
-                int a = v_lo[l + 1] - 1, b = v_hi[l + 1] + 1;
-                if (nl_lo[l] / 2 < a) a = nl_lo[l] / 2;
-                if ((nl_hi[l] + 1) / 2 > b) b = (nl_hi[l] + 1) / 2;
-                p1_lo[l + 1] = a < 0 ? 0 : a;
-                p1_hi[l + 1] = b > np ? np : b;
-                v_lo[l] = 2 * p1_lo[l + 1];
-                v_hi[l] = 2 * p1_hi[l + 1];
-            }
-            // (the mask kernel is pointwise: its box may be any superset -- whole groups of four cells keep it on its vector path along x)
-            v_lo[0] = v_lo[0] / 4 * 4;
-            v_hi[0] = (v_hi[0] + 3) / 4 * 4 > na ? na : (v_hi[0] + 3) / 4 * 4;
-            for (int l = 0; l < AVS_MAX_LEVELS; ++l) { p->slab.win_lo[l] = l < L ? win_lo[l] : 0; p->slab.win_hi[l] = l < L ? win_hi[l] : 0; }
-            if (p->state_sig != p->slab_sig) { // the records of what the allocations hold describe another window: void
-                for (int l = 0; l < AVS_MAX_LEVELS; ++l)
-                    for (int k = 0; k < 2; ++k) {
-                        p->cstate[l][k].id = 0;
-                        for (int a = 0; a < 3; ++a) p->vstate[l][a][k].id = p->estate[l][a][k].id = 0;
-                    }
-                for (int a = 0; a < 3; ++a)
-                    for (int k = 0; k < 2; ++k) p->rstate[a][k].id = 0;
-                for (int k = 0; k < 2; ++k) memset(p->wstate[k].ids, 0, sizeof(p->wstate[k].ids));
-                p->state_sig = p->slab_sig;
-            }
-        }
-    }
-    // entries [lo, hi) of a lattice with extents gr along the cut axis that the window covers / the tiles of a launch over them
-    auto win_box = [&](const int gr[3], int l) {
-        if (!slab) return full_box(gr);
-        return slab_box(gr, sa, win_lo[l], win_hi[l] >= ((sa == 0 ? d.nx : (sa == 1 ? d.ny : d.nz)) >> l) ? gr[sa] : win_hi[l]);
-    };
-    auto win_tiles = [&](const int gr[3], int l) {
-        TileGrid t = tile_grid(gr);
-        if (slab) {
-            const Box3 b = win_box(gr, l);
-            t.lo[sa] = b.lo[sa] / kTile;
-            t.bn[sa] = (b.lo[sa] + b.n[sa] + kTile - 1) / kTile - t.lo[sa];
-            if (b.n[sa] <= 0) t.bn[sa] = 0;
-        }
-        return t;
-    };
-    auto cell_box = [&](int l, int lo, int hi) {
-        int r[3];
-        pp_res(d, 2, l, 0, r);
-        return slab ? slab_box(r, sa, lo, hi) : full_box(r);
-    };
-
-    // ---- P1 weights ------------------------------------------------------------------------
     PhaseScope phase;
     phase.next("Compute Surface Weights"); // cpp:759 (+ "Compute Collision Weights", cpp:776: one fused launch here)
     t.start();
-    {
-        WeightFields F{};
-        int nf = 0;
-        auto add = [&](float *out, const int res[3], bool cx, bool cy, bool cz) {
-            F.out[nf] = out;
-            F.tgt[nf] = g3(res);
-            F.centered[nf] = (cx ? 1 : 0) | (cy ? 2 : 0) | (cz ? 4 : 0);
-            ++nf;
-        };
-        AVS_TRY(p->centerw.alloc(n0));
-        add(p->centerw.p, r0, true, true, true);
-        for (int a = 0; a < 3; ++a) {
-            int er[3], fr[3];
-            pp_res(d, 1, 0, a, er);
-            pp_res(d, 0, 0, a, fr);
-            AVS_TRY(p->edgew[a].alloc(g3(er).vol()));
-            add(p->edgew[a].p, er, a == 0, a == 1, a == 2); // centred along the edge only
-            AVS_TRY(p->facew[a].alloc(g3(fr).vol()));
-            add(p->facew[a].p, fr, a != 0, a != 1, a != 2); // centred across the face
-        }
-        AVS_TRY(run_weights(p, F));
-    }
+    AVS_TRY(run_weights(p));
     p->ms[0] = t.stop();
 
-    // ---- P2 + P3 octree --------------------------------------------------------------------
     phase.next("Build Octree"); // cpp:874 (+ "Build Mask for Octree", cpp:813)
     t.start();
-    AVS_TRY(p->mask.alloc(n0));
-    for (int l = 0; l < L; ++l) {
-        int r[3];
-        pp_res(d, 2, l, 0, r);
-        AVS_TRY(p->labels[l].alloc(g3(r).vol()));
-        if (l > 0) AVS_HIP(hipMemsetAsync(p->labels[l].p, 0, g3(r).vol(), st)); // INACTIVE, oct.cpp:59,69 (level 0 is written by the mask kernel wherever it is read)
-    }
-    // tile-occupancy flags of the lattices of every level ([level][kind][axis][occ_cap] + the cell tiles in slot 6), kept until the numbering,
-    // which skips the tiles nobody visited; the level-0 face lattices' flags are set by the mask kernel (the SDF rule, cpp:907) and serve the
-    // regular-grid classification too
-    const double occ_sdf = 2. * d.dx; // cpp:907
-    const size_t occ_cap = (size_t)(d.nx / kTile + 2) * (size_t)(d.ny / kTile + 2) * (size_t)(d.nz / kTile + 2);
-    DevBuf<uint8_t> &occ_all = p->occ_store;
-    AVS_TRY(occ_all.reserve((size_t)L * 7 * occ_cap));
-    AVS_HIP(hipMemsetAsync(occ_all.p, 0, (size_t)L * 7 * occ_cap, st));
-    auto tile_sets = [&](int l) {
-        TileSets T;
-        uint8_t *ob = occ_all.p + (size_t)l * 7 * occ_cap;
-        for (int kind = 0; kind < 2; ++kind)
-            for (int a = 0; a < 3; ++a) {
-                int gr[3];
-                pp_res(d, kind, l, a, gr);
-                T.tg[kind][a] = win_tiles(gr, l);
-                T.occ[kind][a] = ob + (size_t)(kind * 3 + a) * occ_cap;
-            }
-        return T;
-    };
-    {
-        const Box3 b0 = cell_box(0, v_lo[0], v_hi[0]);
-        const TileSets T0 = tile_sets(0);
-        const double inner = d.dx * (p->fine_bandwidth > 2. ? p->fine_bandwidth : 2.); // SYSmax(2., fpreal(getFineBandwidth())), cpp:259-261
-        const bool vec = (b0.lo[0] & 3) == 0 && (b0.n[0] & 3) == 0 && (r0[0] & 3) == 0;
-        const unsigned gm = vec ? grid_for(b0.vol() / 4) : grid_for(b0.vol());
-        RefineView R{};
-        p->refine.refined = 0;
-        const bool flagged = p->refine.active;
-        if (flagged) { // `refined` counts inside the rank's index window (all of the lattice without slabs)
-            R = RefineView{p->refine.bits.p, p->refine.wx, sa, win_lo[0], win_hi[0], p->refine.counters.p + kRefinedBase};
-            AVS_HIP(hipMemsetAsync(R.refined, 0, (size_t)kRefinedSlots * kRefinedStride * sizeof(unsigned long long), st));
-        }
-        auto mask_kernel = vec ? (flagged ? k_mask_labels<4, true> : k_mask_labels<4, false>) : (flagged ? k_mask_labels<1, true> : k_mask_labels<1, false>);
-        hipLaunchKernelGGL(mask_kernel, dim3(gm), dim3(kBlock), 0, st, p->liq, p->sol, b0, d.dx, inner, extrapolation, p->mask.p, p->labels[0].p, g3(r0),
-                           g3(s0), T0, occ_sdf, 1, R);
-    }
-    for (int l = 0; l < L - 1; ++l) {
-        int r[3], rp[3];
-        pp_res(d, 2, l, 0, r);
-        pp_res(d, 2, l + 1, 0, rp);
-        const Box3 b1 = cell_box(l + 1, p1_lo[l + 1], p1_hi[l + 1]), b2 = cell_box(l + 1, v_lo[l + 1], v_hi[l + 1]);
-        hipLaunchKernelGGL(k_oct_pass1, dim3(grid_for(b1.vol())), dim3(kBlock), 0, st, p->labels[l].p, g3(r), p->labels[l + 1].p, g3(rp), b1);
-        hipLaunchKernelGGL(k_oct_pass2, dim3(grid_for(b2.vol())), dim3(kBlock), 0, st, p->labels[l].p, g3(r), p->labels[l + 1].p, g3(rp), b2);
-        hipLaunchKernelGGL(k_oct_pass3, dim3(grid_for(b2.vol())), dim3(kBlock), 0, st, p->labels[l].p, g3(r), p->labels[l + 1].p, g3(rp), b2);
-    }
-    {
-        int r[3];
-        pp_res(d, 2, L - 1, 0, r);
-        const Box3 bt = cell_box(L - 1, v_lo[L - 1], v_hi[L - 1]);
-        hipLaunchKernelGGL(k_oct_top, dim3(grid_for(bt.vol())), dim3(kBlock), 0, st, p->labels[L - 1].p, g3(r), bt);
-    }
-    // cap at the first level without ACTIVE cells, oct.cpp:198-211 (slab mode: a property of the WHOLE octree -- the flags of the
-    // rank's part travel with the tile counts, the cap is known after the exchange; until then every level is classified)
-    DevBuf<int> &flags = p->lvl_flags;
-    AVS_TRY(flags.reserve(AVS_MAX_LEVELS));
-    AVS_HIP(hipMemsetAsync(flags.p, 0, AVS_MAX_LEVELS * sizeof(int), st));
-    AVS_HIP(hipGetLastError());
-    int hflags[AVS_MAX_LEVELS] = {};
-    int capped = L; // every level is classified: the flags come out of the classification's occupancy pass (k_mark_tiles_all)
+    AVS_TRY(build_octree(p, G));
     p->ms[1] = t.stop();
-    if (p->refine.active) { // the mask kernel's count of the cells the refinement flags kept fine
-        static_assert(sizeof(unsigned long long) == 8, "slot stride in bytes");
-        unsigned long long h[kRefinedSlots * kRefinedStride];
-        AVS_HIP(hipMemcpyAsync(h, p->refine.counters.p + kRefinedBase, sizeof(h), hipMemcpyDeviceToHost, st));
-        AVS_HIP(hipStreamSynchronize(st));
-        unsigned long long sum = 0;
-        for (int k = 0; k < kRefinedSlots; ++k) sum += h[k * kRefinedStride];
-        p->refine.refined = (int64_t)sum;
-    }
+    AVS_TRY(read_refined_cells(p));
     for (int k = 0; k < 4; ++k) p->counts[k] = 0;
 
-    // ---- P4 classification -----------------------------------------------------------------
     phase.next("Build Octree Velocity and Stress Labels"); // cpp:360 (+ "Build Regular Grid Velocity Labels", cpp:306)
     t.start();
-    size_t max_vol = 0;
-    // The numbering's tile space, laid out now: the classification launch drops every tile's DOF count where the scan will read it.  One
-    // batch per counter -- velocity faces, edges, centres (each over ALL levels, level-major, then axis: numbering order), regular-grid
-    // faces (cpp:1486-1509: one counter over the three axes); the four count arrays lie behind each other in ONE buffer (+ the levels'
-    // flags in slab mode: what the ranks sum).  Levels beyond the cap are the tail of their batch: the scans stop before them.
-    DevBuf<int32_t> &fl = p->num_counts;
-    int64_t seg[5] = {0, 0, 0, 0, 0};          // first count of every batch in the buffer (each batch: tiles + 1 entries)
-    int level_tile0[4][AVS_MAX_LEVELS + 1];     // first tile of every level inside a batch (counters 0 .. 2)
-    int tile0_of[4][AVS_MAX_LEVELS][3] = {};    // first tile of every lattice inside its batch
-    for (int counter = 0; counter < 4; ++counter) {
-        int64_t tiles = 0;
-        auto add = [&](int kind, int l, int a) {
-            int gr[3];
-            pp_res(d, kind, l, a, gr);
-            tile0_of[counter][l][a] = (int)tiles;
-            tiles += (int64_t)((gr[0] + kTile - 1) / kTile) * ((gr[1] + kTile - 1) / kTile) * ((gr[2] + kTile - 1) / kTile);
-        };
-        if (counter < 3) {
-            for (int l = 0; l < L; ++l) {
-                level_tile0[counter][l] = (int)tiles;
-                for (int a = 0; a < (counter == 2 ? 1 : 3); ++a) add(counter, l, a);
-            }
-            level_tile0[counter][L] = (int)tiles;
-        } else
-            for (int a = 0; a < 3; ++a) add(0, 0, a);
-        AVS_REQUIRE(tiles < (1ll << 31) - 1, AVS_EINVAL, "too many tiles");
-        seg[counter + 1] = seg[counter] + tiles + 1;
-    }
-    const int64_t n_exchange = seg[4] + AVS_MAX_LEVELS;
-    AVS_REQUIRE(n_exchange < (1ll << 31) - 1, AVS_EINVAL, "too many tiles");
-    AVS_TRY(fl.reserve((size_t)n_exchange));
-    AVS_HIP(hipMemsetAsync(fl.p, 0, (size_t)n_exchange * sizeof(int32_t), st));
-    SlabOwn own{};
-    if (slab) {
-        own.on = 1; own.axis = sa; own.world = p->slab.world; own.rank = p->slab.rank;
-        for (int r = 0; r <= p->slab.world; ++r) own.cuts[r] = p->slab.cuts[r];
-    }
-    TileGrid tg0[3];
-    for (int l = 0; l < capped; ++l) {
-        int cr[3];
-        pp_res(d, 2, l, 0, cr);
-        uint8_t *ob = occ_all.p + (size_t)l * 7 * occ_cap; // six lattices + the cell tiles (slot 6)
-        const TileSets T = tile_sets(l);
-        if (l == 0)
-            for (int a = 0; a < 3; ++a) tg0[a] = T.tg[0][a];
-        {   // (slab mode: the cells whose faces / edges can lie in a tile of the window)
-            const Box3 mb = cell_box(l, win_lo[l] - 1, win_hi[l]);
-            if ((mb.lo[0] & 3) == 0 && (mb.n[0] & 3) == 0 && (cr[0] & 3) == 0)
-                hipLaunchKernelGGL(k_mark_tiles_all<4>, dim3(grid_for(mb.vol() / 4)), dim3(kBlock), 0, st, p->labels[l].p, g3(cr), mb, T, l > 0 ? 1 : 0, flags.p + l);
-            else
-                hipLaunchKernelGGL(k_mark_tiles_all<1>, dim3(grid_for(mb.vol())), dim3(kBlock), 0, st, p->labels[l].p, g3(cr), mb, T, l > 0 ? 1 : 0, flags.p + l);
-        }
-        // the seven lattices of the level: fresh fill or the record of the last classification, ONE launch that lists the tiles to touch,
-        // then one classification launch per lattice over its list
-        WorkLists W{};
-        ClassifyBatch B{};
-        avs_prepass::TileState *tss[kWorkLattices] = {};
-        const TileGrid tc = win_tiles(cr, l);
-        uint8_t *occ_c = ob + 6 * occ_cap;
-        hipLaunchKernelGGL(k_center_tiles, dim3(grid_for(tc.vol())), dim3(kBlock), 0, st, (const uint8_t *)T.occ[1][0], T.tg[1][0], tc, occ_c);
-        AVS_TRY(p->work_lists.reserve(8 + (size_t)kWorkLattices * occ_cap)); // [8 counters | 7 x tile ids]
-        AVS_HIP(hipMemsetAsync(p->work_lists.p, 0, 8 * sizeof(int32_t), st));
-        B.A.n[0] = d.nx; B.A.n[1] = d.ny; B.A.n[2] = d.nz;
-        B.A.level = l;
-        B.A.extrapolation = extrapolation;
-        B.A.lab = p->labels[l].p;
-        B.A.centerw = p->centerw.p;
-        for (int b2 = 0; b2 < 3; ++b2) B.A.edgew[b2] = p->edgew[b2].p;
-        B.A.solid = p->sol;
-        B.occ_cap = (unsigned)occ_cap;
-        B.own = own;
-        size_t max_launch = 0;
-        for (int k = 0; k < kWorkLattices; ++k) {
-            const int kind = k < 3 ? 0 : (k < 6 ? 1 : 2), a = k < 6 ? k % 3 : 0;
-            int gr[3];
-            pp_res(d, kind, l, a, gr);
-            SharedBuf<int32_t> &buf = kind == 0 ? p->vidx[l][a] : (kind == 1 ? p->eidx[l][a] : p->cidx[l]);
-            AVS_TRY(buf.alloc(g3(gr).vol()));
-            if (g3(gr).vol() > max_vol) max_vol = g3(gr).vol();
-            W.tg[k] = kind == 2 ? tc : T.tg[kind][a];
-            W.now[k] = kind == 2 ? occ_c : T.occ[kind][a];
-            W.cnt[k] = p->work_lists.p + k;
-            W.items[k] = p->work_lists.p + 8 + (size_t)k * occ_cap;
-            const Box3 wb = win_box(gr, l);
-            AVS_TRY(unassign_lattice(p, buf, g3(gr), W.tg[k], occ_cap, kind == 0 ? p->vstate[l][a] : (kind == 1 ? p->estate[l][a] : p->cstate[l]), &tss[k],
-                                     slab ? &wb : nullptr, &W.prev[k]));
-            if (W.tg[k].launch() > max_launch) max_launch = W.tg[k].launch();
-            B.kind[k] = kind; B.axis[k] = a; B.g[k] = g3(gr); B.tg[k] = W.tg[k]; B.occ[k] = W.now[k]; B.remember[k] = tss[k]->occ.p; B.out[k] = buf.p;
-            B.cnt[k] = W.cnt[k]; B.items[k] = W.items[k];
-            B.dofs[k] = fl.p + seg[kind] + tile0_of[kind][l][a];
-        }
-        if (max_launch) hipLaunchKernelGGL(k_tile_worklists, dim3(grid_for(max_launch), kWorkLattices), dim3(kBlock), 0, st, W);
-        {   // (with no tile to launch over the occupancy is still remembered: the grid has at least one workgroup per lattice)
-            const unsigned grid = (unsigned)(max_launch < kListGrid ? (max_launch ? max_launch : 1) : kListGrid);
-            hipLaunchKernelGGL(k_classify_batch, dim3(grid, kWorkLattices), dim3(kBlock), 0, st, B);
-            AVS_HIP(hipGetLastError());
-        }
-        for (int k = 0; k < kWorkLattices; ++k) { // the records describe these allocations from here on
-            const int kind = k < 3 ? 0 : (k < 6 ? 1 : 2), a = k < 6 ? k % 3 : 0;
-            SharedBuf<int32_t> &buf = kind == 0 ? p->vidx[l][a] : (kind == 1 ? p->eidx[l][a] : p->cidx[l]);
-            tss[k]->id = buf.id;
-        }
-    }
-    { // regular-grid faces, cpp:1457-1481: the occupancy of the level-0 face lattices, marked above by the same rule (kind 0, SDF)
-        WorkLists W{};
-        ClassifyBatch B{};
-        avs_prepass::TileState *tss[3] = {};
-        size_t max_launch = 0;
-        AVS_TRY(p->work_lists.reserve(8 + (size_t)kWorkLattices * occ_cap));
-        AVS_HIP(hipMemsetAsync(p->work_lists.p, 0, 8 * sizeof(int32_t), st));
-        B.A.n[0] = d.nx; B.A.n[1] = d.ny; B.A.n[2] = d.nz;
-        B.A.level = 0;
-        B.A.extrapolation = extrapolation;
-        B.A.lab = p->labels[0].p;
-        B.A.centerw = p->centerw.p;
-        for (int b2 = 0; b2 < 3; ++b2) B.A.edgew[b2] = p->edgew[b2].p;
-        B.A.solid = p->sol;
-        B.occ_cap = (unsigned)occ_cap;
-        B.own = own;
-        for (int k = 0; k < kWorkLattices; ++k) B.kind[k] = -1;
-        for (int a = 0; a < 3; ++a) {
-            int gr[3];
-            pp_res(d, 0, 0, a, gr);
-            AVS_TRY(p->ridx[a].alloc(g3(gr).vol()));
-            W.tg[a] = tg0[a];
-            W.now[a] = occ_all.p + (size_t)a * occ_cap;
-            W.cnt[a] = p->work_lists.p + a;
-            W.items[a] = p->work_lists.p + 8 + (size_t)a * occ_cap;
-            const Box3 wb = win_box(gr, 0);
-            AVS_TRY(unassign_lattice(p, p->ridx[a], g3(gr), W.tg[a], occ_cap, p->rstate[a], &tss[a], slab ? &wb : nullptr, &W.prev[a]));
-            if (W.tg[a].launch() > max_launch) max_launch = W.tg[a].launch();
-            B.kind[a] = 3; B.axis[a] = a; B.g[a] = g3(gr); B.tg[a] = W.tg[a]; B.occ[a] = W.now[a]; B.remember[a] = tss[a]->occ.p; B.out[a] = p->ridx[a].p;
-            B.cnt[a] = W.cnt[a]; B.items[a] = W.items[a];
-            B.dofs[a] = fl.p + seg[3] + tile0_of[3][0][a];
-        }
-        if (max_launch) hipLaunchKernelGGL(k_tile_worklists, dim3(grid_for(max_launch), kWorkLattices), dim3(kBlock), 0, st, W);
-        {
-            const unsigned grid = (unsigned)(max_launch < kListGrid ? (max_launch ? max_launch : 1) : kListGrid);
-            hipLaunchKernelGGL(k_classify_batch, dim3(grid, kWorkLattices), dim3(kBlock), 0, st, B);
-            AVS_HIP(hipGetLastError());
-        }
-        for (int a = 0; a < 3; ++a) tss[a]->id = p->ridx[a].id;
-    }
-    AVS_HIP(hipGetLastError());
-    if (!slab) { // cap at the first level without ACTIVE cells, oct.cpp:198-211
-        AVS_HIP(hipMemcpyAsync(hflags, flags.p, sizeof(hflags), hipMemcpyDeviceToHost, st));
-        AVS_HIP(hipStreamSynchronize(st));
-        capped = 0;
-        while (capped < L && hflags[capped]) ++capped;
-    }
-    p->levels = capped;
+    AVS_TRY(classify(p, G, lay));
     p->ms[2] = t.stop();
-    if (capped == 0) { // no liquid in the refinement band: nothing to solve (the reference asserts here, oct.cpp:206)
-        p->ms[3] = 0.;
-        p->ready = true;
-        return AVS_OK;
-    }
+    if (p->levels == 0) return finish_without_levels(p, 0.);
 
-    // ---- P5 numbering ----------------------------------------------------------------------
     t.start();
-    DevBuf<int32_t> &ids = p->num_offsets, &scan_tmp = p->num_scan_tmp; // (scratch kept across frames)
-    DevBuf<long long> &base = p->num_totals;
-    (void)max_vol;
-    AVS_TRY(base.alloc(4));
-    AVS_HIP(hipMemsetAsync(base.p, 0, 4 * sizeof(long long), st));
-    PhaseTrace tr(st, "numbering", avs::options_from_env().trace_phases != 0);
-    // the batches' lattice lists (the layout is the one the classification counted into: tile0_of, seg)
-    NumBatch host_batches[4] = {}; // (alive until the synchronisation behind the last batch: they are the sources of asynchronous copies)
-    for (int counter = 0; counter < 4; ++counter) {
-        NumBatch &B = host_batches[counter];
-        auto add = [&](int32_t *grid, const int gr[3], const uint8_t *occ, int tag, int tile0) {
-            NumLattice &Lt = B.lat[B.count++];
-            Lt.grid = grid;
-            Lt.occ = occ;
-            Lt.g = g3(gr);
-            Lt.ntx = (gr[0] + kTile - 1) / kTile;
-            Lt.nty = (gr[1] + kTile - 1) / kTile;
-            Lt.tile0 = tile0;
-            Lt.tag = tag;
-        };
-        if (counter < 3) {
-            const int kind = counter;
-            for (int l = 0; l < L; ++l)
-                for (int a = 0; a < (kind == 2 ? 1 : 3); ++a) {
-                    int gr[3];
-                    pp_res(d, kind, l, a, gr);
-                    const uint8_t *oc = occ_all.p + ((size_t)l * 7 + (kind == 2 ? 6 : (size_t)kind * 3 + a)) * occ_cap; // (centres: the cell tiles with an ACTIVE cell, k_center_tiles)
-                    add(kind == 0 ? p->vidx[l][a].p : (kind == 1 ? p->eidx[l][a].p : p->cidx[l].p), gr, oc, l | (a << 8), tile0_of[counter][l][a]);
-                }
-        } else {
-            for (int a = 0; a < 3; ++a) {
-                int gr[3];
-                pp_res(d, 0, 0, a, gr);
-                add(p->ridx[a].p, gr, occ_all.p + (size_t)a * occ_cap, 0, tile0_of[3][0][a]); // classified with the level-0 face occupancy
-            }
-        }
-        B.total_tiles = (int)(seg[counter + 1] - seg[counter] - 1);
-    }
-    AVS_TRY(ids.reserve((size_t)seg[4]));
-    AVS_TRY(p->num_lists.reserve((size_t)seg[4] + 4)); // per batch: [count | tile ids]  (a batch's segment has tiles + 1 entries)
-    constexpr unsigned kNumGrid = 4096;                 // workgroups walking a list
-    AVS_TRY(p->num_batches.alloc(4));
-    NumStarts S[4];
-    for (int counter = 0; counter < 4; ++counter) {
-        const NumBatch &B = host_batches[counter];
-        AVS_TRY(scan_tmp.reserve(scan_tmp_elems((int64_t)B.total_tiles + 1)));
-        AVS_HIP(hipMemcpyAsync(p->num_batches.p + counter, &B, sizeof(NumBatch), hipMemcpyHostToDevice, st)); // (pageable source: staged before the call returns)
-        for (int k = 0; k < kNumLattices; ++k) S[counter].tile0[k] = k < B.count ? B.lat[k].tile0 : INT_MAX;
-    }
-    AVS_HIP(hipGetLastError());
-    tr.mark("tile counts");
-    int eff_tiles[4]; // tiles of the levels below the cap (slab mode: the cap is only known now)
-    for (int c = 0; c < 4; ++c) eff_tiles[c] = host_batches[c].total_tiles;
-    if (slab) { // ONE exchange: every tile's count from the rank that owns it, every level's "has an ACTIVE cell" from whoever saw one
-        AVS_HIP(hipMemcpyAsync(fl.p + seg[4], flags.p, AVS_MAX_LEVELS * sizeof(int), hipMemcpyDeviceToDevice, st));
-        const avs_status ex = p->slab_fn(fl.p, n_exchange, (void *)st, p->slab_user);
-        AVS_REQUIRE(ex == AVS_OK, ex, "the all-reduce callback of avs_prepass_set_slab failed (%d)", (int)ex);
-        AVS_HIP(hipMemcpyAsync(hflags, fl.p + seg[4], sizeof(hflags), hipMemcpyDeviceToHost, st));
-        AVS_HIP(hipStreamSynchronize(st));
-        capped = 0;
-        while (capped < L && hflags[capped]) ++capped;
-        p->levels = capped;
-        if (capped == 0) {
-            p->ms[3] = t.stop();
-            for (int k = 0; k < 3; ++k) p->n_window[k] = 0;
-            p->ready = true;
-            return AVS_OK;
-        }
-    }
-    for (int c = 0; c < 3; ++c) eff_tiles[c] = level_tile0[c][capped]; // (levels are the outer order of a batch: the capped ones are its tail)
-    tr.mark("exchange");
-    for (int counter = 0; counter < 4; ++counter)
-        AVS_TRY(exclusive_scan_i32(fl.p + seg[counter], ids.p + seg[counter], eff_tiles[counter], scan_tmp.p, scan_tmp.n, st));
-    // dof tables: slab mode sizes them exactly (the totals are read first); else room for the previous frame's count + 25 % (a first
-    // run has no estimate: the context builds them)
-    long long hb[4] = {0, 0, 0, 0};
-    if (slab) {
-        int32_t tot[4];
-        for (int c = 0; c < 4; ++c) AVS_HIP(hipMemcpyAsync(&tot[c], ids.p + seg[c] + eff_tiles[c], sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        AVS_HIP(hipStreamSynchronize(st));
-        for (int c = 0; c < 4; ++c) {
-            AVS_REQUIRE(tot[c] >= 0, AVS_EINVAL, "DOF count exceeds int32");
-            hb[c] = tot[c];
-        }
-    }
-    for (int k = 0; k < 3; ++k) {
-        p->dof_valid[k] = false;
-        if (slab) p->dof_cap[k] = hb[k] > 0 ? hb[k] : 1;
-        else p->dof_cap[k] = (p->temporal && p->prev_counts[k] > 0) ? p->prev_counts[k] + p->prev_counts[k] / 4 + 4096 : 0;
-        if (p->dof_cap[k] > 0) AVS_TRY(p->dof[k].alloc((size_t)p->dof_cap[k] * 4));
-        if (slab) AVS_HIP(hipMemsetAsync(p->dof[k].p, 0xFF, (size_t)p->dof_cap[k] * 4 * sizeof(int32_t), st)); // entries outside the window stay recognisably void
-    }
-    for (int counter = 0; counter < 4; ++counter) {
-        const bool tab = counter < 3 && p->dof_cap[counter] > 0;
-        if (eff_tiles[counter]) {
-            int32_t *list = p->num_lists.p + seg[counter];
-            AVS_HIP(hipMemsetAsync(list, 0, sizeof(int32_t), st));
-            hipLaunchKernelGGL(k_tile_select_ids, dim3(grid_for((size_t)eff_tiles[counter])), dim3(kBlock), 0, st, S[counter], p->num_batches.p + counter,
-                               eff_tiles[counter], (const int32_t *)(ids.p + seg[counter]), list);
-            hipLaunchKernelGGL(k_tile_ids, dim3(kNumGrid), dim3(kBlock), 0, st, S[counter], p->num_batches.p + counter,
-                               (const int32_t *)(ids.p + seg[counter]), tab ? p->dof[counter].p : (int32_t *)nullptr,
-                               tab ? p->dof_cap[counter] : 0ll, base.p + counter, eff_tiles[counter], (const int32_t *)list);
-        }
-    }
-    AVS_HIP(hipGetLastError());
-    tr.mark("scans, tables, ids");
-    if (slab) { // the window's DOFs of every kind, ascending: the tiles this rank classified, each a run of consecutive ids
-        DevBuf<int32_t> &wcnt = p->win_cnt, &woff = p->win_off;
-        for (int k = 0; k < 3; ++k) {
-            const int tiles = eff_tiles[k];
-            AVS_TRY(wcnt.reserve((size_t)tiles + 1));
-            AVS_TRY(woff.reserve((size_t)tiles + 1));
-            hipLaunchKernelGGL(k_win_counts, dim3(grid_for((size_t)tiles)), dim3(kBlock), 0, st, S[k], p->num_batches.p + k, (const int32_t *)(ids.p + seg[k]), tiles, wcnt.p);
-            AVS_TRY(exclusive_scan_i32(wcnt.p, woff.p, tiles, scan_tmp.p, scan_tmp.n, st));
-            int32_t nw = 0;
-            AVS_HIP(hipMemcpyAsync(&nw, woff.p + tiles, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            AVS_HIP(hipStreamSynchronize(st));
-            p->n_window[k] = nw;
-            AVS_TRY(p->wlist[k].alloc((size_t)(nw > 0 ? nw : 1)));
-            if (tiles && nw) hipLaunchKernelGGL(k_win_fill, dim3((unsigned)tiles), dim3(kBlock), 0, st, (const int32_t *)(ids.p + seg[k]), (const int32_t *)wcnt.p, (const int32_t *)woff.p, p->wlist[k].p);
-            AVS_HIP(hipGetLastError());
-            AVS_HIP(hipStreamSynchronize(st)); // wcnt / woff are reused
-        }
-    } else {
-        AVS_HIP(hipMemcpyAsync(hb, base.p, sizeof(hb), hipMemcpyDeviceToHost, st));
-        AVS_HIP(hipStreamSynchronize(st));
-    }
-    tr.mark("window lists");
-    for (int k = 0; k < 4; ++k) p->counts[k] = hb[k];
-    for (int k = 0; k < 3; ++k) {
-        p->dof_valid[k] = p->dof_cap[k] > 0 && hb[k] <= p->dof_cap[k];
-        p->prev_counts[k] = hb[k];
-    }
-    p->ms[3] = t.stop();
+    AVS_TRY(number_dofs(p, G, lay));
+    const double number_ms = t.stop();
+    if (p->levels == 0) return finish_without_levels(p, number_ms);
+    p->ms[3] = number_ms;
     p->ready = true;
     return AVS_OK;
 }
+
+#ifdef AVS_PROBES // measurement / test entries (include/avs_probe.h): compiled into libavs_probe.so only
+avs_status avs_prepass_plan_host(const int32_t *n, int32_t desired_levels, int32_t cut_axis, const int32_t *cuts, int32_t world, int32_t rank,
+                                 avs_prepass_plan_info *plan)
+{
+    AVS_REQUIRE(n && plan, AVS_EINVAL, "null argument");
+    AVS_REQUIRE(plan->struct_size == (int32_t)sizeof(*plan), AVS_EINVAL, "plan: struct_size not set");
+    auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    AVS_REQUIRE(pow2(n[0]) && pow2(n[1]) && pow2(n[2]), AVS_EINVAL, "base resolution must be a power of two per axis");
+    AVS_REQUIRE(desired_levels >= 1 && desired_levels <= AVS_MAX_LEVELS, AVS_EINVAL, "desired_levels out of range");
+    const bool on = cuts && world > 1;
+    if (on) {
+        AVS_REQUIRE(cut_axis >= 0 && cut_axis < 3 && world <= avs::kMaxRanks && rank >= 0 && rank < world, AVS_EINVAL, "slab: axis / world / rank out of range");
+        AVS_REQUIRE(cuts[0] == 0 && cuts[world] == n[cut_axis], AVS_EINVAL, "slab: cuts must run from 0 to the axis' extent (%d)", n[cut_axis]);
+        for (int r = 0; r < world; ++r) AVS_REQUIRE(cuts[r] <= cuts[r + 1], AVS_EINVAL, "slab: cuts must ascend");
+    }
+    const int L = level_cap(n, desired_levels);
+    const SlabRanges R = slab_ranges(n[on ? cut_axis : 0], L, on, cuts, rank, kSlabIndexMargin, kTile);
+    TileLayout T;
+    AVS_REQUIRE(tile_layout(n, L, kTile, &T), AVS_EINVAL, "too many tiles");
+    avs_prepass_plan_info o{};
+    o.struct_size = (int32_t)sizeof(o);
+    o.levels = L;
+    static_assert(sizeof(o.win_lo) == sizeof(R.win_lo) && sizeof(o.level_tile0) == sizeof(T.level_tile0) && sizeof(o.tile0_of) == sizeof(T.tile0_of) &&
+                      sizeof(o.seg) == sizeof(T.seg), "avs_prepass_plan_info mirrors SlabRanges and TileLayout");
+    memcpy(o.win_lo, R.win_lo, sizeof(o.win_lo)); memcpy(o.win_hi, R.win_hi, sizeof(o.win_hi));
+    memcpy(o.nl_lo, R.nl_lo, sizeof(o.nl_lo));    memcpy(o.nl_hi, R.nl_hi, sizeof(o.nl_hi));
+    memcpy(o.v_lo, R.v_lo, sizeof(o.v_lo));       memcpy(o.v_hi, R.v_hi, sizeof(o.v_hi));
+    memcpy(o.p1_lo, R.p1_lo, sizeof(o.p1_lo));    memcpy(o.p1_hi, R.p1_hi, sizeof(o.p1_hi));
+    memcpy(o.level_tile0, T.level_tile0, sizeof(o.level_tile0));
+    memcpy(o.tile0_of, T.tile0_of, sizeof(o.tile0_of));
+    memcpy(o.seg, T.seg, sizeof(o.seg));
+    o.n_exchange = T.n_exchange;
+    *plan = o;
+    return AVS_OK;
+}
+#endif
 
 avs_status avs_prepass_get_info(avs_prepass *p, avs_prepass_info *info)
 {
@@ -2011,8 +2084,7 @@ avs_status avs_prepass_get_index(avs_prepass *p, avs_index_kind kind, int32_t le
     AVS_HIP(hipSetDevice(p->desc.device));
     int r[3];
     pp_res(p->desc, (int)kind, level, axis, r);
-    const int32_t *src = kind == AVS_INDEX_VELOCITY ? p->vidx[level][axis].p : (kind == AVS_INDEX_EDGE ? p->eidx[level][axis].p : p->cidx[level].p);
-    AVS_HIP(copy_out(out, src, g3(r).vol() * sizeof(int32_t), where, p->stream));
+    AVS_HIP(copy_out(out, index_lattice(p, (int)kind, level, axis).buf->p, g3(r).vol() * sizeof(int32_t), where, p->stream));
     AVS_HIP(hipStreamSynchronize(p->stream));
     return AVS_OK;
 }

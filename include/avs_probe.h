@@ -102,6 +102,29 @@ avs_status avs_resident_plan_host(int64_t n, const int32_t *row_ptr, int32_t wor
                                   double stream_cost, int32_t *lane_row0, uint32_t *lane_meta, int32_t *lane_stream_quads, int32_t *wg_lane0,
                                   int32_t *wg_row0, avs_resident_host_plan_info *info);
 
+/* The integer geometry of a pre-pass run (csrc/avs_prepass_plan.cpp) without a device and without a HIP call, as avs_prepass_create and
+ * avs_prepass_run plan it for an octree grid n[3] (powers of two) and desired_levels: the level cap of the extents, the ranges of every
+ * level along the cut axis in level-l cells [lo, hi) -- win: the index window (avs_prepass_get_window), nl: the labels its classification
+ * reads, v: the labels valid before the level serves as children, p1: the parents of octree pass 1 (levels >= 1) -- and the numbering's
+ * tile layout: four batches (velocity faces, edges, centres over all levels, level-major then axis; the regular grid's three face
+ * lattices) of 16^3-entry tiles behind each other, batch c at seg[c] with its tiles + 1 entries, then AVS_MAX_LEVELS level flags.
+ * cuts (world + 1 entries from 0 to n[cut_axis], ascending) and world > 1 select the slab-local ranges of `rank`; cuts NULL or
+ * world <= 1: every range is the whole level.  Entries of levels >= `levels` are 0. */
+typedef struct {
+    int32_t struct_size;
+    int32_t levels;                                   /* min(desired_levels, what the extents carry) */
+    int32_t win_lo[AVS_MAX_LEVELS], win_hi[AVS_MAX_LEVELS];
+    int32_t nl_lo[AVS_MAX_LEVELS], nl_hi[AVS_MAX_LEVELS];
+    int32_t v_lo[AVS_MAX_LEVELS], v_hi[AVS_MAX_LEVELS];
+    int32_t p1_lo[AVS_MAX_LEVELS], p1_hi[AVS_MAX_LEVELS];
+    int32_t level_tile0[4][AVS_MAX_LEVELS + 1];       /* first tile of every level inside batches 0 .. 2; [levels]: the batch's tiles */
+    int32_t tile0_of[4][AVS_MAX_LEVELS][3];           /* first tile of lattice [level][axis] inside its batch (batch 3: level 0) */
+    int64_t seg[5];                                   /* first entry of every batch in the count buffer */
+    int64_t n_exchange;                               /* entries of the count buffer: what the ranks of a slab-local run sum */
+} avs_prepass_plan_info;
+avs_status avs_prepass_plan_host(const int32_t *n, int32_t desired_levels, int32_t cut_axis, const int32_t *cuts, int32_t world, int32_t rank,
+                                 avs_prepass_plan_info *plan);
+
 /* What the launch-per-phase loop (pcg_solve_phases, csrc/avs_pcg.hip) did in the LAST solve of the calling thread that ran it -- through
  * avs_pcg_csr, avs_pcg_csr_plan or avs_solve of this library --, so that a test which claims "graph replay" or "the alpha step as a
  * launch of its own" does not pass on a solve that took another way.  The caller sets struct_size; fields past it are not written.  Every

@@ -122,6 +122,8 @@ def test_window_of_the_prepass_equals_the_single_rank_prepass(scene, world, axis
     sc = scenes.to_device(SCENES[scene]("cpu"), dev)
     ref, counts = _reference_arrays(sc)
     cuts = _uniform_cuts(sc.res[axis], world)
+    # every rank's index window as the host-only plan has it (tests/test_prepass_plan_host.py checks that plan without a GPU)
+    planned = [capi.prepass_plan_host(sc.res, sc.levels, axis, cuts, r)["win"] for r in range(world)]
     hip = C.CDLL("libamdhip64.so")
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     hip.hipStreamSynchronize.argtypes = [C.c_void_p]
@@ -157,6 +159,7 @@ def test_window_of_the_prepass_equals_the_single_rank_prepass(scene, world, axis
                 continue
             lo, hi, nw = pp.window()
             _compare_window(pp, ref, info.levels, axis, lo, hi, sc.res)
+            assert np.array_equal(lo, planned[r][0][:info.levels]) and np.array_equal(hi, planned[r][1][:info.levels]), (r, frame)
             out.append((lo.copy(), hi.copy(), nw))
         pp.close()
         return out or True

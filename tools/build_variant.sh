@@ -10,5 +10,5 @@ for f in avs_api avs_brick avs_brick_build avs_pcg avs_spmv avs_assembly avs_dis
   ( /opt/rocm/bin/hipcc $FLAGS -c $f.hip -o exp_$TAG/$f.o ) &
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../exp/libavs_hip_$TAG.so exp_$TAG/*.o avs_partition.o avs_resident_plan.o -L/opt/rocm/lib -lrccl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../exp/libavs_hip_$TAG.so exp_$TAG/*.o avs_partition.o avs_resident_plan.o avs_prepass_plan.o -L/opt/rocm/lib -lrccl
 ls -la ../exp/libavs_hip_$TAG.so
