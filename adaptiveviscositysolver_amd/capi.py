@@ -54,6 +54,7 @@ SPECTRUM_OF_JACOBI, SPECTRUM_OF_MATRIX = 0, 1   # `op` of avs_estimate_spectrum
 SPECTRUM_START_RESIDUAL, SPECTRUM_START_HASH, SPECTRUM_START_VECTOR = 0, 1, 2   # its `start`
 SPECTRUM_MAX_STEPS = 512
 PREPASS_OPTION_FINE_BANDWIDTH = 0   # avs_prepass_set_option
+PREPASS_OPTION_APPLY_SOLID_WEIGHTS = 1   # ... the reference's "Apply Solid Weights": 0 off (default), 1 on
 REFINEMENT_MAX_DILATE = 16          # avs_prepass_set_refinement: dilate_cells in 0 .. 16
 CSR_CHECK_VALUES, CSR_CHECK_ORDER, CSR_CHECK_DIAGONAL, CSR_CHECK_SYMMETRY, CSR_CHECK_ALL = 1, 2, 4, 8, 15   # bits of `what` of avs_check_csr
 (CSR_RULE_ROW_PTR, CSR_RULE_COLUMN, CSR_RULE_VALUE, CSR_RULE_VECTOR, CSR_RULE_ORDER, CSR_RULE_DIAGONAL, CSR_RULE_PATTERN,
@@ -83,6 +84,7 @@ EXPORTED_SYMBOLS = [
     "avs_get_strain_rates", "avs_get_shear_rate_field", "avs_apply_viscosity_model", "avs_check_solution", "avs_check_csr_solution",
     "avs_estimate_spectrum", "avs_estimate_csr_spectrum",
     "avs_prepass_set_option", "avs_prepass_set_refinement", "avs_prepass_get_refinement", "avs_prepass_get_refinement_info",
+    "avs_prepass_get_solid_weights_info",
 ]
 # avs_allreduce_i32_fn: avs_status (*)(int32_t *device_data, int64_t count, void *stream, void *user)
 ALLREDUCE_I32_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -146,6 +148,13 @@ class RefinementInfo(C.Structure):
     """avs_refinement_info: what avs_prepass_get_refinement_info reports about the refinement flags"""
     _fields_ = [("struct_size", C.c_int32), ("dilate_cells", C.c_int32), ("threshold", C.c_float), ("active", C.c_int32),
                 ("seeds", C.c_int64), ("flagged", C.c_int64), ("refined", C.c_int64), ("set_ms", C.c_double)]
+
+
+class SolidWeightsInfo(C.Structure):
+    """avs_solid_weights_info: what the last run's weights pass did with the solid SDF; [4] = centre, edge x, edge y, edge z"""
+    _fields_ = [("struct_size", C.c_int32), ("enabled", C.c_int32), ("applied", C.c_int32), ("extrapolation", C.c_float),
+                ("modified", C.c_int64 * 4), ("zeroed", C.c_int64 * 4), ("above_one", C.c_int64 * 4), ("max_weight", C.c_float * 4),
+                ("near_bricks", C.c_int64)]
 
 
 class AssemblyInfo(C.Structure):
@@ -472,6 +481,7 @@ def load(probe=False):
     L.avs_prepass_set_refinement.argtypes = [vp, vp, f32, i32, i32]
     L.avs_prepass_get_refinement.argtypes = [vp, vp, i32]
     L.avs_prepass_get_refinement_info.argtypes = [vp, C.POINTER(RefinementInfo)]
+    L.avs_prepass_get_solid_weights_info.argtypes = [vp, C.POINTER(SolidWeightsInfo)]
     L.avs_set_regular_index_field.argtypes = [vp, i32, vp, i32]
     L.avs_transfer_to_regular_grid.argtypes = [vp, vp, vp, vp, i32]
     L.avs_transfer_to_regular_grid_in_place.argtypes = [vp, vp, vp, vp]

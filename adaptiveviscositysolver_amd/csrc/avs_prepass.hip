@@ -4,7 +4,8 @@
 //   P1 k_sdf_weights_far + k_sdf_weights   integration weights (cpp:712-766; HDK computeSDFWeightsSampled is not in the
 //                        reference tree: fraction of n^3 sub-samples with interpolated SDF < 0, defined in
 //                        oracle/avs_oracle.c and restated identically here, fp32, x then y then z); bricks whose SDF
-//                        window has one sign are finished by the first kernel, the surface bricks by the second
+//                        window has one sign are finished by the first kernel, the surface bricks by the second; as SOLID
+//                        instantiations also the collision weights and their division (cpp:768-790, "Apply Solid Weights")
 //   P2 k_mask_labels     refinement mask + level-0 labels (cpp:815-867, oct.cpp:383-388); marks the tiles of the level-0 face lattices
 //                        on the way (the SDF rule, cpp:907)
 //   P3 k_oct_*           label pyramid, three passes per level (oct.cpp:93-189) + top level (oct.cpp:843-875)
@@ -95,6 +96,48 @@ struct WeightFields {
     int n;
 };
 
+// "Apply Solid Weights" (AVS_PREPASS_OPTION_APPLY_SOLID_WEIGHTS; cpp:768-790, rule in include/avs.h): the kernels below take the solid
+// path as a template parameter SOLID.  g = solid + ext (one fp32 add per cell, BEFORE any interpolation, so the sign shortcuts stay exact
+// for g as they are for the liquid); S = the sub-sample count of g; centre and edge weights become w / W, 0 where S == 0.  Without SOLID
+// nothing of this struct is read.
+static constexpr int kWScaled = 4; // centre, edge x, edge y, edge z: WeightFields slots 0, 1, 3, 5
+struct SolidArgs {
+    const float *sol;
+    float ext;
+    unsigned long long *counts; // [kWScaled][3]: modified, zeroed, above_one (integer atomics: the same numbers on every run)
+    unsigned *maxbits;          // [kWScaled]: bit pattern of the largest weight (weights are >= 0: their bits order as they do)
+};
+__device__ __forceinline__ bool scaled_field(int f) { return f == 0 || (f & 1); }
+__device__ __forceinline__ int scaled_slot(int f) { return (f + 1) >> 1; }
+
+// What a far brick adds to the counts of avs_solid_weights_info, from its constant alone (one thread): the counts must not depend on
+// whether the brick is stored again or skipped (temporal reuse), so k_brick_triage calls this for the bricks it skips and
+// k_sdf_weights_far for the bricks it decides.  now 2: every sample holds 1 (w' == w); now 4: l == n^3 and S == 0 everywhere, w' = 0.
+// `counts` / `maxbits`: the global words, or a workgroup's accumulators in LDS.  The maximum is read before it is raised: nearly every
+// brick finds 1.0 there already, and tens of thousands of atomics on one word cost the triage more than everything else it does.
+__device__ __forceinline__ void far_brick_counts(const WeightFields &F, const int o0[3], int now, unsigned long long *counts, unsigned *maxbits)
+{
+    if (now != 2 && now != 4) return;
+    for (int f = 0; f < kWFields; ++f) {
+        if (!scaled_field(f)) continue;
+        const Grid3 tgt = F.tgt[f];
+        long long m = 1;
+        const int ext[3] = {kWBX, kWBY, kWBZ};
+        for (int a = 0; a < 3; ++a) {
+            const int left = tgt.r[a] - o0[a];
+            m *= left <= 0 ? 0 : (left < ext[a] ? left : ext[a]);
+        }
+        if (m == 0) continue;
+        const int k = scaled_slot(f);
+        if (now == 2) {
+            if (*(volatile unsigned *)(maxbits + k) < __float_as_uint(1.0f)) atomicMax(maxbits + k, __float_as_uint(1.0f));
+        } else {
+            atomicAdd(counts + k * 3 + 0, (unsigned long long)m);
+            atomicAdd(counts + k * 3 + 1, (unsigned long long)m);
+        }
+    }
+}
+
 // Pass 1 (every brick): the brick-level form of the exact sign shortcut -- a window of one sign gives every sample of the
 // brick n^3 or 0.  Away from the surface that is almost every brick; they are finished here (seven coalesced stores per
 // thread, few registers, full occupancy).  Bricks whose window changes sign go on a list for k_sdf_weights, whose 150
@@ -106,7 +149,10 @@ struct WeightFields {
 // it scan the window itself (the exact test, as before) -- it used to read the window of EVERY brick, 3.35x the lattice.
 // One WAVE per brick (eight cells per lane, a ballot instead of a block barrier), each workgroup walking many bricks: a workgroup per
 // brick is 2.2 M workgroups at 1024^3, and dispatching them -- ~3.4 ns each -- took as long as the old pass itself.
-__global__ __launch_bounds__(kBlock) void k_sdf_sign_blocks(const float *__restrict__ sdf, Grid3 src, Grid3 bricks, Box3 box, uint8_t *__restrict__ signs)
+// SOLID: bits 2 and 3 say the same of g = solid + ext, read in the same sweep.
+template <bool SOLID>
+__global__ __launch_bounds__(kBlock) void k_sdf_sign_blocks(const float *__restrict__ sdf, Grid3 src, Grid3 bricks, Box3 box, uint8_t *__restrict__ signs,
+                                                            SolidArgs A)
 {
     const size_t nb = box.vol();
     const int lane = threadIdx.x & 63;
@@ -115,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void k_sdf_sign_blocks(const float *__restr
         box_coords(box, t, bc[0], bc[1], bc[2]);
         const size_t b = (size_t)bc[0] + (size_t)bricks.r[0] * ((size_t)bc[1] + (size_t)bricks.r[1] * (size_t)bc[2]);
         const int o0[3] = {bc[0] * kWBX, bc[1] * kWBY, bc[2] * kWBZ};
-        int neg = 0, pos = 0;
+        int neg = 0, pos = 0, gneg = 0, gpos = 0;
 #pragma unroll
         for (int u = 0; u < kWThreads / 64; ++u) { // lanes 0..31: a 128-B row of x, lanes 32..63 the next y
             const int t = u * 64 + lane;
@@ -124,19 +170,37 @@ __global__ __launch_bounds__(kBlock) void k_sdf_sign_blocks(const float *__restr
                 const float v = sdf[lin3(src, c[0], c[1], c[2])];
                 if (v < 0.f) neg = 1;
                 else pos = 1;
+                if (SOLID) {
+                    const float g = A.sol[lin3(src, c[0], c[1], c[2])] + A.ext;
+                    if (g < 0.f) gneg = 1;
+                    else gpos = 1;
+                }
             }
         }
         const bool any_neg = __ballot(neg) != 0ull, any_pos = __ballot(pos) != 0ull;
-        if (lane == 0) signs[b] = (uint8_t)((any_neg ? 1 : 0) | (any_pos ? 2 : 0));
+        unsigned bits = (any_neg ? 1u : 0u) | (any_pos ? 2u : 0u);
+        if (SOLID) bits |= (__ballot(gneg) != 0ull ? 4u : 0u) | (__ballot(gpos) != 0ull ? 8u : 0u);
+        if (lane == 0) signs[b] = (uint8_t)bits;
     }
 }
 
 // Pass 1, one THREAD per brick: where the 27 bricks around it agree on a sign and the lattices already hold that constant for it
 // (`state`, temporal reuse below) there is nothing to do -- in a running simulation that is nearly every brick; the others go on the work
 // list of k_sdf_weights_far.
+// SOLID: a brick is far when the liquid neighbourhood is all non-negative (constant 1 whatever the solid does), or all negative with a
+// unanimous solid neighbourhood (2: solid all negative, 4: solid all non-negative).  A skipped brick still adds what it holds to the
+// counts (far_brick_counts).
+template <bool SOLID>
 __global__ __launch_bounds__(kBlock) void k_brick_triage(Grid3 bricks, Box3 box, const uint8_t *__restrict__ signs, const uint8_t *__restrict__ state,
-                                                         int32_t *__restrict__ work_list /* [0]: count, then brick ids */)
+                                                         int32_t *__restrict__ work_list /* [0]: count, then brick ids */, WeightFields F, SolidArgs A)
 {
+    __shared__ unsigned long long s_cnt[SOLID ? kWScaled * 3 : 1];
+    __shared__ unsigned s_max[SOLID ? kWScaled : 1];
+    if (SOLID) { // (no thread leaves the loop below early: every thread reaches both barriers)
+        if (threadIdx.x < kWScaled * 3) s_cnt[threadIdx.x] = 0ull;
+        if (threadIdx.x < kWScaled) s_max[threadIdx.x] = 0u;
+        __syncthreads();
+    }
     const size_t nb = box.vol();
     for (size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x; t < nb; t += (size_t)gridDim.x * kBlock) {
         int bc[3];
@@ -150,9 +214,22 @@ __global__ __launch_bounds__(kBlock) void k_brick_triage(Grid3 bricks, Box3 box,
                     if (q[0] >= 0 && q[1] >= 0 && q[2] >= 0 && q[0] < bricks.r[0] && q[1] < bricks.r[1] && q[2] < bricks.r[2])
                         sg |= signs[q[0] + (size_t)bricks.r[0] * (q[1] + (size_t)bricks.r[1] * q[2])];
                 }
-        const uint8_t now = sg == 1u ? 2 : (sg == 2u ? 1 : 0); // unanimous: the constant the brick gets (k_sdf_weights_far's encoding)
-        if (now != 0 && state[b] == now) continue;
+        uint8_t now = (sg & 3u) == 1u ? 2 : ((sg & 3u) == 2u ? 1 : 0); // unanimous: the constant the brick gets (k_sdf_weights_far's encoding)
+        if (SOLID && now == 2) now = (sg >> 2) == 1u ? 2 : ((sg >> 2) == 2u ? 4 : 0);
+        if (now != 0 && state[b] == now) {
+            if (SOLID) {
+                const int o0[3] = {bc[0] * kWBX, bc[1] * kWBY, bc[2] * kWBZ};
+                far_brick_counts(F, o0, now, s_cnt, s_max);
+            }
+            continue;
+        }
         work_list[1 + atomicAdd(work_list, 1)] = (int32_t)b; // (the order of the list does not matter)
+    }
+    if (SOLID) {
+        __syncthreads();
+        const int t = threadIdx.x;
+        if (t < kWScaled * 3 && s_cnt[t] != 0ull) atomicAdd(A.counts + t, s_cnt[t]);
+        if (t < kWScaled && s_max[t] != 0u && *(volatile unsigned *)(A.maxbits + t) < s_max[t]) atomicMax(A.maxbits + t, s_max[t]);
     }
 }
 
@@ -160,23 +237,32 @@ __global__ __launch_bounds__(kBlock) void k_brick_triage(Grid3 bricks, Box3 box,
 // filled -- 1: 0.0 everywhere, 2: 1.0 everywhere, 3: computed values, 0: unknown.  A far brick whose constant has not changed (a
 // simulation's next frame: every brick the surface has not reached or left) is not stored again: the pass then only READS the SDF
 // windows, instead of writing seven full-size lattices (30 GB at 1024^3) whatever the liquid's volume.
+// SOLID adds 4: centre and edge lattices 0.0, face lattices 1.0 (liquid all negative, g all non-negative: S == 0 everywhere, and the
+// faces are never scaled).  The record says what the lattices HOLD, not how it came about, so a record written with the option is as
+// valid for a run without it and the other way round: state 2 under the option holds what state 2 holds without it, and a brick that
+// holds 2 where this run wants 4 (or 4 where it wants 2) is simply stored again.
+template <bool SOLID>
 __global__ __launch_bounds__(kWThreads) void k_sdf_weights_far(const float *__restrict__ sdf, Grid3 src, Grid3 bricks, WeightFields F,
                                                                int32_t *__restrict__ near_list /* [0]: count, then brick ids */,
                                                                uint8_t *__restrict__ state, const uint8_t *__restrict__ signs,
-                                                               const int32_t *__restrict__ work_list)
+                                                               const int32_t *__restrict__ work_list, SolidArgs A)
 {
     const int n = F.n;
     const int b = work_list[1 + blockIdx.x];
     const uint8_t held = state[b]; // (read by every thread before the barriers below, written by thread 0 behind them)
     const int bc[3] = {b % bricks.r[0], (b / bricks.r[0]) % bricks.r[1], b / (bricks.r[0] * bricks.r[1])};
     const int o0[3] = {bc[0] * kWBX, bc[1] * kWBY, bc[2] * kWBZ};
-    int seen_neg = 0, seen_pos = 0;
+    int seen_neg = 0, seen_pos = 0, g_neg = 0, g_pos = 0;
     if (threadIdx.x < 27) { // the signs of the 27 bricks around this one: a superset of the window's
         const int q[3] = {bc[0] + (int)threadIdx.x % 3 - 1, bc[1] + ((int)threadIdx.x / 3) % 3 - 1, bc[2] + (int)threadIdx.x / 9 - 1};
         if (q[0] >= 0 && q[1] >= 0 && q[2] >= 0 && q[0] < bricks.r[0] && q[1] < bricks.r[1] && q[2] < bricks.r[2]) {
             const uint8_t sg = signs[q[0] + bricks.r[0] * (q[1] + bricks.r[1] * q[2])];
             seen_neg = sg & 1;
             seen_pos = (sg >> 1) & 1;
+            if (SOLID) {
+                g_neg = (sg >> 2) & 1;
+                g_pos = (sg >> 3) & 1;
+            }
         }
     }
     int any_neg = __syncthreads_or(seen_neg);
@@ -200,57 +286,56 @@ __global__ __launch_bounds__(kWThreads) void k_sdf_weights_far(const float *__re
         }
         return;
     }
-    const uint8_t now = any_neg ? 2 : 1;
+    uint8_t now = any_neg ? 2 : 1;
+    if (SOLID && any_neg) { // liquid everywhere: the solid window decides between 1 everywhere, 0 / faces 1, and the near list
+        int sol_neg = __syncthreads_or(g_neg);
+        int sol_pos = __syncthreads_or(g_pos);
+        if (sol_neg && sol_pos) {
+            g_neg = g_pos = 0;
+            for (int w = threadIdx.x; w < kWHX * kWHY * kWHZ; w += kWThreads) {
+                const int wx = w % kWHX, wy = (w / kWHX) % kWHY, wz = w / (kWHX * kWHY);
+                const float g = A.sol[lin3(src, clampi(o0[0] - 2 + wx, 0, src.r[0] - 1), clampi(o0[1] - 2 + wy, 0, src.r[1] - 1),
+                                           clampi(o0[2] - 2 + wz, 0, src.r[2] - 1))] + A.ext;
+                if (g < 0.f) g_neg = 1;
+                else g_pos = 1;
+            }
+            sol_neg = __syncthreads_or(g_neg);
+            sol_pos = __syncthreads_or(g_pos);
+        }
+        if (sol_neg && sol_pos) {
+            if (threadIdx.x == 0) {
+                near_list[1 + atomicAdd(near_list, 1)] = b;
+                state[b] = 3;
+            }
+            return;
+        }
+        now = sol_neg ? 2 : 4;
+    }
+    const int t = threadIdx.x;
+    if (SOLID && t == 0) far_brick_counts(F, o0, now, A.counts, A.maxbits);
     if (held == now) return; // the lattices already hold this brick's constant
     const float value = (float)(any_neg ? n * n * n : 0) / (float)(n * n * n);
-    const int t = threadIdx.x;
     if (t == 0) state[b] = now;
     const int p[3] = {o0[0] + t % kWBX, o0[1] + (t / kWBX) % kWBY, o0[2] + t / (kWBX * kWBY)};
     for (int f = 0; f < kWFields; ++f) {
         const Grid3 tgt = F.tgt[f];
-        if (p[0] < tgt.r[0] && p[1] < tgt.r[1] && p[2] < tgt.r[2]) F.out[f][lin3(tgt, p[0], p[1], p[2])] = value;
+        if (p[0] < tgt.r[0] && p[1] < tgt.r[1] && p[2] < tgt.r[2])
+            F.out[f][lin3(tgt, p[0], p[1], p[2])] = SOLID && now == 4 && scaled_field(f) ? 0.f : value;
     }
 }
 
-// Pass 2: the bricks near the surface (near_list), everything from LDS.
-__global__ __launch_bounds__(kWThreads) void k_sdf_weights(const float *__restrict__ sdf, Grid3 src, Grid3 bricks, WeightFields F,
-                                                           const int32_t *__restrict__ near_list)
+// The number of the n^3 sub-samples around sample p of field f whose trilinear interpolation of the staged window is < 0: the ONE
+// routine of the liquid count l and of the solid count S (k_sdf_weights calls it on either window).
+// NB: unclamped source coordinates c in [o0-2, o0+extent] map to the window cell that was filled with the clamped
+// coordinate, so `at` returns exactly what the reference's clamped read returns.
+__device__ __forceinline__ int window_sample_count(const float *__restrict__ win, const WeightFields &F, int f, const int o0[3], const int p[3])
 {
-    __shared__ float win[kWHX * kWHY * kWHZ];
     const int n = F.n;
-    const float n3 = (float)(n * n * n);
-    const int b = near_list[1 + blockIdx.x];
-    const int o0[3] = {(b % bricks.r[0]) * kWBX, ((b / bricks.r[0]) % bricks.r[1]) * kWBY, (b / (bricks.r[0] * bricks.r[1])) * kWBZ};
-    // window cell (wx, wy, wz) holds sdf at clamp(o0 - 2 + w): clamping here reproduces the clamped reads below
-    int seen_neg = 0, seen_pos = 0;
-    for (int w = threadIdx.x; w < kWHX * kWHY * kWHZ; w += kWThreads) {
-        const int wx = w % kWHX, wy = (w / kWHX) % kWHY, wz = w / (kWHX * kWHY);
-        const float v = sdf[lin3(src, clampi(o0[0] - 2 + wx, 0, src.r[0] - 1), clampi(o0[1] - 2 + wy, 0, src.r[1] - 1),
-                                 clampi(o0[2] - 2 + wz, 0, src.r[2] - 1))];
-        win[w] = v;
-        if (v < 0.f) seen_neg = 1;
-        else seen_pos = 1;
-    }
-    // brick-level form of the exact sign shortcut below: a window of one sign gives every sample of the brick n^3 / 0
-    // (away from the surface that is almost every brick, and it saves the per-sample 4^3 scan of the window)
-    const int any_neg = __syncthreads_or(seen_neg);
-    const int any_pos = __syncthreads_or(seen_pos);
-    const int t = threadIdx.x;
-    const int p[3] = {o0[0] + t % kWBX, o0[1] + (t / kWBX) % kWBY, o0[2] + t / (kWBX * kWBY)};
-    // NB: unclamped source coordinates c in [o0-2, o0+extent] map to the window cell that was filled with the clamped
-    // coordinate, so `at` returns exactly what the reference's clamped read returns.
     auto at = [&](int cx, int cy, int cz) {
         const int ix = clampi(cx - (o0[0] - 2), 0, kWHX - 1), iy = clampi(cy - (o0[1] - 2), 0, kWHY - 1), iz = clampi(cz - (o0[2] - 2), 0, kWHZ - 1);
         return win[ix + kWHX * (iy + kWHY * iz)];
     };
-    for (int f = 0; f < kWFields; ++f) {
-        const Grid3 tgt = F.tgt[f];
-        if (p[0] >= tgt.r[0] || p[1] >= tgt.r[1] || p[2] >= tgt.r[2]) continue;
-        float *out = F.out[f] + lin3(tgt, p[0], p[1], p[2]);
-        if (!any_pos || !any_neg) {
-            *out = (float)(any_neg ? n * n * n : 0) / n3;
-            continue;
-        }
+    {
         const int *di[3];
         const float *fr[3];
 #pragma unroll
@@ -294,7 +379,81 @@ __global__ __launch_bounds__(kWThreads) void k_sdf_weights(const float *__restri
                         if (lerp32(c0, c1, tz) < 0.f) ++count;
                     }
         }
-        *out = (float)count / n3;
+        return count;
+    }
+}
+
+// Pass 2: the bricks near the surface (near_list), everything from LDS.
+// SOLID: a second window holds g; on the centre and edge lattices a sample with l > 0 gets S from the same routine (brick-level and
+// per-sample sign shortcuts first) and then w / W.  S is formed after l is final, so the second count keeps nothing of the first alive
+// but l itself.  The counts of avs_solid_weights_info gather in LDS and leave the workgroup in at most 16 atomics.
+template <bool SOLID>
+__global__ __launch_bounds__(kWThreads) void k_sdf_weights(const float *__restrict__ sdf, Grid3 src, Grid3 bricks, WeightFields F,
+                                                           const int32_t *__restrict__ near_list, SolidArgs A)
+{
+    __shared__ float win[kWHX * kWHY * kWHZ];
+    __shared__ float gwin[SOLID ? kWHX * kWHY * kWHZ : 1];
+    __shared__ unsigned s_cnt[SOLID ? kWScaled * 3 : 1], s_max[SOLID ? kWScaled : 1];
+    const int n = F.n;
+    const float n3 = (float)(n * n * n);
+    const int b = near_list[1 + blockIdx.x];
+    const int o0[3] = {(b % bricks.r[0]) * kWBX, ((b / bricks.r[0]) % bricks.r[1]) * kWBY, (b / (bricks.r[0] * bricks.r[1])) * kWBZ};
+    // window cell (wx, wy, wz) holds sdf at clamp(o0 - 2 + w): clamping here reproduces the clamped reads below
+    int seen_neg = 0, seen_pos = 0, g_neg = 0, g_pos = 0;
+    for (int w = threadIdx.x; w < kWHX * kWHY * kWHZ; w += kWThreads) {
+        const int wx = w % kWHX, wy = (w / kWHX) % kWHY, wz = w / (kWHX * kWHY);
+        const size_t at = lin3(src, clampi(o0[0] - 2 + wx, 0, src.r[0] - 1), clampi(o0[1] - 2 + wy, 0, src.r[1] - 1),
+                               clampi(o0[2] - 2 + wz, 0, src.r[2] - 1));
+        const float v = sdf[at];
+        win[w] = v;
+        if (v < 0.f) seen_neg = 1;
+        else seen_pos = 1;
+        if (SOLID) {
+            const float g = A.sol[at] + A.ext;
+            gwin[w] = g;
+            if (g < 0.f) g_neg = 1;
+            else g_pos = 1;
+        }
+    }
+    if (SOLID) {
+        if (threadIdx.x < kWScaled * 3) s_cnt[threadIdx.x] = 0u;
+        if (threadIdx.x < kWScaled) s_max[threadIdx.x] = 0u;
+    }
+    // brick-level form of the exact sign shortcut below: a window of one sign gives every sample of the brick n^3 / 0
+    // (away from the surface that is almost every brick, and it saves the per-sample 4^3 scan of the window)
+    const int any_neg = __syncthreads_or(seen_neg);
+    const int any_pos = __syncthreads_or(seen_pos);
+    int sol_neg = 0, sol_pos = 0;
+    if (SOLID) {
+        sol_neg = __syncthreads_or(g_neg);
+        sol_pos = __syncthreads_or(g_pos);
+    }
+    const int t = threadIdx.x;
+    const int p[3] = {o0[0] + t % kWBX, o0[1] + (t / kWBX) % kWBY, o0[2] + t / (kWBX * kWBY)};
+    for (int f = 0; f < kWFields; ++f) {
+        const Grid3 tgt = F.tgt[f];
+        if (p[0] >= tgt.r[0] || p[1] >= tgt.r[1] || p[2] >= tgt.r[2]) continue;
+        float *out = F.out[f] + lin3(tgt, p[0], p[1], p[2]);
+        const int count = (!any_pos || !any_neg) ? (any_neg ? n * n * n : 0) : window_sample_count(win, F, f, o0, p);
+        float w = (float)count / n3;
+        if (SOLID && scaled_field(f)) {
+            const int k = scaled_slot(f);
+            if (count > 0) {
+                const int S = (!sol_pos || !sol_neg) ? (sol_neg ? n * n * n : 0) : window_sample_count(gwin, F, f, o0, p);
+                const float ws = S == 0 ? 0.f : (S == n * n * n ? w : __fdiv_rn(w, (float)S / n3));
+                if (ws != w) atomicAdd(&s_cnt[k * 3 + 0], 1u);
+                if (S == 0) atomicAdd(&s_cnt[k * 3 + 1], 1u);
+                if (ws > 1.f) atomicAdd(&s_cnt[k * 3 + 2], 1u);
+                if (__float_as_uint(ws) > *(volatile unsigned *)&s_max[k]) atomicMax(&s_max[k], __float_as_uint(ws)); // (read first: see far_brick_counts)
+                w = ws;
+            }
+        }
+        *out = w;
+    }
+    if (SOLID) {
+        __syncthreads();
+        if (t < kWScaled * 3 && s_cnt[t] != 0u) atomicAdd(A.counts + t, (unsigned long long)s_cnt[t]);
+        if (t < kWScaled && s_max[t] != 0u && *(volatile unsigned *)(A.maxbits + t) < s_max[t]) atomicMax(A.maxbits + t, s_max[t]);
     }
 }
 
@@ -1117,6 +1276,9 @@ struct avs_prepass {
     avs::StressCheckScratch stress_check; // avs_prepass_check_stress_indices (avs_stress_check.hip)
     double ms[4] = {0, 0, 0, 0};
     double fine_bandwidth = 2.; // AVS_PREPASS_OPTION_FINE_BANDWIDTH
+    bool apply_solid = false;   // AVS_PREPASS_OPTION_APPLY_SOLID_WEIGHTS
+    DevBuf<unsigned long long> solid_stats; // the kernels' side of avs_solid_weights_info: [12] counts, then [4] maxima as 32-bit patterns
+    avs_solid_weights_info solid_info{};    // ... and the last run's copy (enabled and struct_size are filled by the getter)
     avs::RefineState refine;    // avs_prepass_set_refinement (avs_refine.hip)
     bool ready = false;
 };
@@ -1210,22 +1372,67 @@ static avs_status run_weights(avs_prepass *p)
         tri = slab_box(bricks.r, a, lo, hi);
         sgn = slab_box(bricks.r, a, lo - 1, hi + 1);
     }
-    hipLaunchKernelGGL(k_sdf_sign_blocks, dim3(grid_for((sgn.vol() + 3) / 4 * kBlock, 1u << 15)), dim3(kBlock), 0, p->stream, p->liq, g3(r0), bricks, sgn, p->brick_signs.p);
-    hipLaunchKernelGGL(k_brick_triage, dim3(grid_for(tri.vol(), 1u << 15)), dim3(kBlock), 0, p->stream, bricks, tri, (const uint8_t *)p->brick_signs.p,
-                       (const uint8_t *)ws->st.p, p->work_list.p);
+    // "Apply Solid Weights": the SOLID instantiations, when the option is on and the run has a solid SDF; the others are what ran before
+    const bool solid = p->apply_solid && p->sol != nullptr;
+    avs_solid_weights_info &si = p->solid_info;
+    si = avs_solid_weights_info{};
+    SolidArgs A{};
+    if (solid) {
+        si.applied = 1;
+        si.extrapolation = (float)(d.dx * d.extrapolation_scale); // (extrapolation_of below: the product in double, rounded once)
+        AVS_TRY(p->solid_stats.alloc(kWScaled * 3 + kWScaled / 2));
+        AVS_HIP(hipMemsetAsync(p->solid_stats.p, 0, p->solid_stats.n * sizeof(unsigned long long), p->stream));
+        A.sol = p->sol;
+        A.ext = si.extrapolation;
+        A.counts = p->solid_stats.p;
+        A.maxbits = reinterpret_cast<unsigned *>(p->solid_stats.p + kWScaled * 3);
+    }
+    const dim3 sign_grid(grid_for((sgn.vol() + 3) / 4 * kBlock, 1u << 15)), tri_grid(grid_for(tri.vol(), 1u << 15));
+    if (solid) {
+        hipLaunchKernelGGL(k_sdf_sign_blocks<true>, sign_grid, dim3(kBlock), 0, p->stream, p->liq, g3(r0), bricks, sgn, p->brick_signs.p, A);
+        hipLaunchKernelGGL(k_brick_triage<true>, tri_grid, dim3(kBlock), 0, p->stream, bricks, tri, (const uint8_t *)p->brick_signs.p,
+                           (const uint8_t *)ws->st.p, p->work_list.p, F, A);
+    } else {
+        hipLaunchKernelGGL(k_sdf_sign_blocks<false>, sign_grid, dim3(kBlock), 0, p->stream, p->liq, g3(r0), bricks, sgn, p->brick_signs.p, A);
+        hipLaunchKernelGGL(k_brick_triage<false>, tri_grid, dim3(kBlock), 0, p->stream, bricks, tri, (const uint8_t *)p->brick_signs.p,
+                           (const uint8_t *)ws->st.p, p->work_list.p, F, A);
+    }
     int32_t n_work = 0;
     AVS_HIP(hipMemcpyAsync(&n_work, p->work_list.p, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
     AVS_HIP(hipStreamSynchronize(p->stream));
-    if (n_work > 0)
-        hipLaunchKernelGGL(k_sdf_weights_far, dim3((unsigned)n_work), dim3(kWThreads), 0, p->stream, p->liq, g3(r0), bricks, F, p->near_list.p, ws->st.p,
-                           (const uint8_t *)p->brick_signs.p, (const int32_t *)p->work_list.p);
+    if (n_work > 0) {
+        if (solid)
+            hipLaunchKernelGGL(k_sdf_weights_far<true>, dim3((unsigned)n_work), dim3(kWThreads), 0, p->stream, p->liq, g3(r0), bricks, F, p->near_list.p,
+                               ws->st.p, (const uint8_t *)p->brick_signs.p, (const int32_t *)p->work_list.p, A);
+        else
+            hipLaunchKernelGGL(k_sdf_weights_far<false>, dim3((unsigned)n_work), dim3(kWThreads), 0, p->stream, p->liq, g3(r0), bricks, F, p->near_list.p,
+                               ws->st.p, (const uint8_t *)p->brick_signs.p, (const int32_t *)p->work_list.p, A);
+    }
     int32_t n_near = 0;
     AVS_HIP(hipMemcpyAsync(&n_near, p->near_list.p, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
     AVS_HIP(hipStreamSynchronize(p->stream));
-    if (n_near > 0)
-        hipLaunchKernelGGL(k_sdf_weights, dim3((unsigned)n_near), dim3(kWThreads), 0, p->stream, p->liq, g3(r0), bricks, F,
-                           (const int32_t *)p->near_list.p);
+    si.near_bricks = n_near;
+    if (n_near > 0) {
+        if (solid)
+            hipLaunchKernelGGL(k_sdf_weights<true>, dim3((unsigned)n_near), dim3(kWThreads), 0, p->stream, p->liq, g3(r0), bricks, F,
+                               (const int32_t *)p->near_list.p, A);
+        else
+            hipLaunchKernelGGL(k_sdf_weights<false>, dim3((unsigned)n_near), dim3(kWThreads), 0, p->stream, p->liq, g3(r0), bricks, F,
+                               (const int32_t *)p->near_list.p, A);
+    }
     AVS_HIP(hipGetLastError());
+    if (solid) { // the counts of the run (one more round trip, with the option only)
+        unsigned long long h[kWScaled * 3 + kWScaled / 2];
+        AVS_HIP(hipMemcpyAsync(h, p->solid_stats.p, sizeof(h), hipMemcpyDeviceToHost, p->stream));
+        AVS_HIP(hipStreamSynchronize(p->stream));
+        const unsigned *mb = reinterpret_cast<const unsigned *>(h + kWScaled * 3);
+        for (int k = 0; k < kWScaled; ++k) {
+            si.modified[k] = (int64_t)h[k * 3 + 0];
+            si.zeroed[k] = (int64_t)h[k * 3 + 1];
+            si.above_one[k] = (int64_t)h[k * 3 + 2];
+            memcpy(&si.max_weight[k], &mb[k], sizeof(float));
+        }
+    }
     return AVS_OK;
 }
 
@@ -1875,9 +2082,29 @@ avs_status avs_prepass_get_window(avs_prepass *p, int32_t *lo, int32_t *hi, int6
 avs_status avs_prepass_set_option(avs_prepass *p, avs_prepass_option option, double value)
 {
     AVS_REQUIRE(p, AVS_EINVAL, "null argument");
-    AVS_REQUIRE(option == AVS_PREPASS_OPTION_FINE_BANDWIDTH, AVS_EINVAL, "avs_prepass_set_option: unknown option %d", (int)option);
+    AVS_REQUIRE(option == AVS_PREPASS_OPTION_FINE_BANDWIDTH || option == AVS_PREPASS_OPTION_APPLY_SOLID_WEIGHTS, AVS_EINVAL,
+                "avs_prepass_set_option: unknown option %d", (int)option);
+    if (option == AVS_PREPASS_OPTION_APPLY_SOLID_WEIGHTS) {
+        AVS_REQUIRE(value == 0. || value == 1., AVS_EINVAL, "avs_prepass_set_option: apply solid weights is 0 or 1"); // (NaN fails both)
+        p->apply_solid = value == 1.;
+        return AVS_OK;
+    }
     AVS_REQUIRE(std::isfinite(value), AVS_EINVAL, "avs_prepass_set_option: the fine bandwidth must be finite");
     p->fine_bandwidth = value;
+    return AVS_OK;
+}
+
+// what the last run's weights pass did with the solid SDF: protocol and fields in include/avs.h, counted by the P1 kernels
+avs_status avs_prepass_get_solid_weights_info(avs_prepass *p, avs_solid_weights_info *info)
+{
+    AVS_REQUIRE(p && info, AVS_EINVAL, "null argument");
+    AVS_REQUIRE(info->struct_size >= (int32_t)sizeof(int32_t) && info->struct_size <= 4096, AVS_EINVAL,
+                "avs_prepass_get_solid_weights_info: struct_size %d out of range", info->struct_size);
+    avs_solid_weights_info r = p->solid_info;
+    r.struct_size = info->struct_size;
+    r.enabled = p->apply_solid ? 1 : 0;
+    const size_t nbytes = (size_t)info->struct_size < sizeof(r) ? (size_t)info->struct_size : sizeof(r);
+    memcpy(info, &r, nbytes);
     return AVS_OK;
 }
 

@@ -1034,7 +1034,8 @@ class DevicePrepass:
 
     def set_option(self, option, value):
         """avs_prepass_set_option: capi.PREPASS_OPTION_FINE_BANDWIDTH -- the reference's "Fine Layer Bandwidth" (cells within
-        dx * max(2, value) inside the surface stay fine); takes effect at the next run."""
+        dx * max(2, value) inside the surface stay fine); capi.PREPASS_OPTION_APPLY_SOLID_WEIGHTS -- its "Apply Solid Weights" (0 / 1:
+        centre and edge weights divided by the open-space fraction of the solid SDF given to run()); takes effect at the next run."""
         capi.check(self.lib.avs_prepass_set_option(self.h, int(option), float(value)))
 
     def set_refinement(self, field=None, threshold=0.0, dilate=0):
@@ -1070,6 +1071,14 @@ class DevicePrepass:
         info = capi.RefinementInfo()
         info.struct_size = C.sizeof(capi.RefinementInfo)
         capi.check(self.lib.avs_prepass_get_refinement_info(self.h, C.byref(info)))
+        return info
+
+    def solid_weights_info(self):
+        """avs_solid_weights_info: enabled, applied, extrapolation, and per lattice (centre, edge x, y, z) the last run's modified /
+        zeroed / above_one counts and max_weight; near_bricks"""
+        info = capi.SolidWeightsInfo()
+        info.struct_size = C.sizeof(capi.SolidWeightsInfo)
+        capi.check(self.lib.avs_prepass_get_solid_weights_info(self.h, C.byref(info)))
         return info
 
     def apply(self, solver):

@@ -144,7 +144,8 @@ const char *avs_version(void);
  * Purely additive since (no revision): the entries avs_estimate_spectrum and avs_estimate_csr_spectrum.
  * Purely additive since (no revision): the entry avs_apply_viscosity_model.
  * Purely additive since (no revision): the entries avs_prepass_set_option, avs_prepass_set_refinement, avs_prepass_get_refinement and
- *   avs_prepass_get_refinement_info. */
+ *   avs_prepass_get_refinement_info.
+ * Purely additive since (no revision): the option AVS_PREPASS_OPTION_APPLY_SOLID_WEIGHTS and the entry avs_prepass_get_solid_weights_info. */
 #define AVS_ABI_VERSION 2
 int32_t avs_abi_version(void);
 
@@ -881,14 +882,49 @@ typedef struct {
     double weights_ms, octree_ms, classify_ms, number_ms;
 } avs_prepass_info;
 avs_status avs_prepass_create(const avs_prepass_desc *desc, avs_prepass **out);
-/* Options of the refinement mask (cpp:815-867); they take effect at the next avs_prepass_run.
+/* Options of the pre-pass; they take effect at the next avs_prepass_run.  FINE_BANDWIDTH belongs to the refinement mask (cpp:815-867),
+ * APPLY_SOLID_WEIGHTS to the integration weights (cpp:768-790).
  *   AVS_PREPASS_OPTION_FINE_BANDWIDTH  the reference's "Fine Layer Bandwidth": cells within inner = dx * max(2, value) INSIDE the liquid
  *     surface stay fine (SYSmax(2., fpreal(getFineBandwidth())), cpp:259-261); inner also enters the solid rule, solid > -inner -
  *     extrapolation (cpp:853).  Default 2, and anything <= 2 behaves as 2 -- which is all the reference's own build ever gets: its getter
  *     does not match the UI token.  The outer band stays 3 dx.  A non-finite value or an unknown option: AVS_EINVAL, nothing
- *     changes. */
-typedef enum { AVS_PREPASS_OPTION_FINE_BANDWIDTH = 0 } avs_prepass_option;
+ *     changes.
+ *   AVS_PREPASS_OPTION_APPLY_SOLID_WEIGHTS  the reference's "Apply Solid Weights" (UI token applySolidWeights, getter
+ *     doApplySolidWeights, cpp:60, 244, 768-790: "theta value for applying ghost fluid collision velocities").  0 (default): off;
+ *     1: on; any other value, NaN included: AVS_EINVAL, nothing changes.  With the option on AND a solid SDF given to avs_prepass_run the
+ *     centre and the three edge weight lattices are divided by the super-sampled fraction of open space; the face weights are never
+ *     touched (the reference's faceWeights is an input field that does not see this step).  The rule (HDK's arithmetic is closed source;
+ *     this is the project's definition, all fp32, one rounding per operation):
+ *       ext32 = (float)(dx * extrapolation_scale), the product in double;  g = solid + ext32 per cell of the lattice the SDFs are given
+ *       on (solid > 0 inside the solid: g < 0 is outside the solid grown by the extrapolation), read with clamped coordinates as the
+ *       liquid is;  l / S = the number of the n^3 sub-samples whose trilinear interpolation of the liquid / of g is < 0 (same constants,
+ *       same lerp order);  w = (float)l / n^3, W = (float)S / n^3;  w' = 0 if l == 0 or S == 0, else w / W (an IEEE fp32 division).
+ *     S == n^3 leaves w bit for bit; w' may exceed 1 (up to n^3); w' > 0 implies w > 0, so everything downstream (tile occupancy,
+ *     classification, numbering, assembly) runs unchanged on the new values.  avs_prepass_get_weights returns and avs_prepass_apply
+ *     lends the scaled lattices.  Without a solid SDF, or with the option off, every lattice is byte for byte what it is without the
+ *     option.  Two HDK behaviours are NOT pinned by the reference tree and assumed here: how computeSDFWeightsSampled
+ *     applies its dilate argument (here: the shift of the cell values above, never a non-zero threshold on interpolated values --
+ *     rounding inside the lerps would break the exact sign shortcuts), and what setScaleDivideThreshold does where the divisor is 0
+ *     (here: the result is 0). */
+typedef enum { AVS_PREPASS_OPTION_FINE_BANDWIDTH = 0, AVS_PREPASS_OPTION_APPLY_SOLID_WEIGHTS = 1 } avs_prepass_option;
 avs_status avs_prepass_set_option(avs_prepass *pp, avs_prepass_option option, double value);
+/* What the weights pass of the last avs_prepass_run did with the solid SDF (struct_size: IN, only that many bytes are written; callable
+ * before any run: everything but enabled is 0 then).  Per lattice, [4] = centre, edge x, edge y, edge z: modified = samples with
+ * w' != w, zeroed = samples with l > 0 and S == 0, above_one = samples with w' > 1, max_weight = the largest w'.  All zero when
+ * applied == 0.  The counts are integer atomics and the maximum is taken on the bit pattern: the same inputs give the same numbers in
+ * every call and every fresh object, whatever earlier runs left in the lattices (a brick that is not stored again still counts what it
+ * holds).  near_bricks: the 32x4x4 bricks of samples the near kernel computed (any run).  Slab-local mode: the numbers cover the
+ * bricks of the rank's window (whole bricks, so the windows of two ranks overlap): they are not meant to be summed over ranks. */
+typedef struct {
+    int32_t struct_size;   /* IN: sizeof(avs_solid_weights_info) of the caller's header */
+    int32_t enabled;       /* the option as set now */
+    int32_t applied;       /* 1: the last run had the option on AND a solid SDF */
+    float extrapolation;   /* ext32 of the last applied run */
+    int64_t modified[4], zeroed[4], above_one[4];
+    float max_weight[4];
+    int64_t near_bricks;
+} avs_solid_weights_info;
+avs_status avs_prepass_get_solid_weights_info(avs_prepass *pp, avs_solid_weights_info *info);
 /* Indicator-driven refinement: keep the octree fine where a field the host paints says so -- a shear band, a steep viscosity gradient
  * deep inside the liquid, which the surface rule coarsens as far as the grading allows.
  *   indicator: centre lattice of the SIMULATION grid (field_nx x field_ny x field_nz, x fastest) -- the lattice of the SDFs given to

@@ -301,6 +301,11 @@ bool HDK_AdaptiveViscosity::solveGasSubclass(SIM_Engine &engine, SIM_Object *obj
             for (int a = 0; a < 3; ++a) { h.oct[a] = oct[a]; h.sim[a] = sim[a]; }
             h.dx = dx; h.want_levels = pd.desired_levels; h.n_super = pd.n_super; h.extrapolation = pd.extrapolation_scale;
         }
+        // "Apply Solid Weights" (cpp:60, 768-790), read under its UI token: the reference's getter doApplySolidWeights does not match it,
+        // so its own build never sees the toggle.  The collision weights are computed and applied on the device.
+        bool apply_solid_weights = false;
+        getOptions().getOptionB("applySolidWeights", apply_solid_weights);
+        if (!check(avs_prepass_set_option(h.pp, AVS_PREPASS_OPTION_APPLY_SOLID_WEIGHTS, apply_solid_weights ? 1. : 0.))) return false;
         const Flat liquid_sdf = flatten(liquid), solid_sdf = flatten(*collision->getField());
         std::vector<float> liquid_dense, solid_dense; // the pre-pass wants dense SDFs
         auto dense = [&](const Flat &f, std::vector<float> &store) -> const float * {
