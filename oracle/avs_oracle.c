@@ -1104,6 +1104,7 @@ static void edge_stress_faces(const orc_ctx *c, int level, int axis, const int e
                     int sib[3] = {face[0], face[1], face[2]};
                     sib[axis] += (edge[axis] % 2 == 0) ? 1 : -1;
                     int32_t si = c->vidx[level][fa][lin(fr, sib)];
+                    if (si < 0) s->overflow = 2; /* reference: assert cpp:1820 */
                     st_push(s, si, .25 * sign / g);
                     st_push(s, vi, .25 * sign / g);
                 } else st_push(s, vi, .5 * sign / g); /* cpp:1827 */
